@@ -4,7 +4,19 @@ queries (avg ~265 aa before the 127-residue cap, L = 127) against a 10M-residue
 DB, default `aln` options (BLOSUM62 11/1, -b 10, -r 16, -t 2, -s 2).
 
     python bench.py [--gpus N --steps K --warmup W] [--preset cfg4|cfg3|cfg5|cfg2]
-                    [--queries N] [--cpu-sample 10000] [--cpu-sample-all 16000] [--no-cpu]
+                    [--queries N] [--dump-outputs DIR]
+                    [--full [--cpu-sample 10000] [--cpu-sample-all 16000] [--no-cpu] [--no-e2e]]
+
+A plain run does what the headline figure needs and no more: it builds the
+inputs, opens the session, warms up, times the K steps, compares the last step's
+whole output with the reference pin, writes --dump-outputs and prints the line.
+`--full` adds the legs that take runs of their own: the warm and cold end-to-end
+runs, the two CPU baselines and, at N > 1, rank 0's unsharded comparison run
+(`--no-e2e` / `--no-cpu` drop single legs of a full run).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller as
+DIR/<name>.npy (float64 / float32, see dump_outputs). The inputs are a function
+of the arguments alone, so two builds can be compared output for output.
 
 A step = one full `aln` pass over the rank's query shard with inputs resident in
 HBM: K1 seed -> K2 score -> K4 merge -> K3 traceback -> E-values + text
@@ -22,13 +34,13 @@ ends with one MIN all-reduce of every rank's ok flag (one rank's failure stops
 all ranks) and the one data-path collective: a gather of fixed-capacity hit
 record buffers with a count header. After the timed steps every rank writes its
 text at its offset of one output file, and rank 0 checks the assembled file
-against the reference pin.
+against the reference pin (and, with --full, against an unsharded run).
 
 Parity in the line: `full_output_matches_reference` compares the sha256 of the
 whole output of the last timed step (N = 1) or of the assembled file (N > 1) with
 the reference CPU program's output for the same full workload
-(tests/golden/full_golden.json). A mismatch (or a CPU-sample mismatch) nulls
-`value` and exits non-zero.
+(tests/golden/full_golden.json). A mismatch (or, with --full, a CPU-sample or
+end-to-end file mismatch) nulls `value` and exits non-zero.
 """
 from __future__ import annotations
 
@@ -214,6 +226,54 @@ def write_assembled(dist, coll_dev, rank: int, world: int, path: str, text: byte
     dist.barrier()
 
 
+DUMP_HIT_ROWS = 300_000    # x (8 fields + the row index) x float64 = 21.6 MB
+DUMP_TEXT_BYTES = 2_000_000  # x (float32 byte + float64 offset) = 24 MB
+
+
+def dump_outputs(out_dir: str, text: bytes, hits) -> None:
+    """What the last timed step handed its caller, as .npy arrays (float64 / float32,
+    under 46 MB in all, below the 64 MB a dump may take):
+
+      hits.npy              [rows, 8] float64: the hit records (HIT_DTYPE fields in
+                            order; the u32 fields are exact in float64). All of
+                            them, or the rows hits_rows.npy names.
+      hits_rows.npy         [rows] float64: the record index of each row of hits.npy
+                            (a fixed seeded sample, ascending, once there are more
+                            than DUMP_HIT_ROWS records)
+      hits_count.npy        [1] float64: records in all
+      output_text.npy       [n] float32: the output text's bytes at the offsets
+                            output_text_offsets.npy names (all of it, or a fixed
+                            seeded sample of DUMP_TEXT_BYTES offsets, ascending)
+      output_text_offsets.npy  [n] float64
+      output_bytes.npy      [1] float64: length of the whole text
+      output_sha256.npy     [32] float32: the sha256 digest of the whole text, one
+                            byte per element
+
+    N > 1: the records are the gathered ones (all ranks, rank order), the text is
+    rank 0's shard."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(20240607)
+    n = len(hits)
+    rows = np.arange(n) if n <= DUMP_HIT_ROWS else np.sort(rng.choice(n, DUMP_HIT_ROWS, replace=False))
+    picked = hits[rows]
+    table = np.empty((len(rows), len(hits.dtype.names)), dtype=np.float64)
+    for j, name in enumerate(hits.dtype.names):
+        table[:, j] = picked[name]
+    raw = np.frombuffer(text, dtype=np.uint8)
+    offs = (np.arange(len(raw)) if len(raw) <= DUMP_TEXT_BYTES
+            else np.sort(rng.choice(len(raw), DUMP_TEXT_BYTES, replace=False)))
+    digest = np.frombuffer(hashlib.sha256(text).digest(), dtype=np.uint8)
+    for name, arr in (("hits", table), ("hits_rows", rows.astype(np.float64)),
+                      ("hits_count", np.array([n], dtype=np.float64)),
+                      ("output_text", raw[offs].astype(np.float32)),
+                      ("output_text_offsets", offs.astype(np.float64)),
+                      ("output_bytes", np.array([len(raw)], dtype=np.float64)),
+                      ("output_sha256", digest.astype(np.float32))):
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def full_pin(preset: str, nq: int, aln: list) -> dict | None:
     """The reference pin for this exact workload, if it is the full preset."""
     pins = _json(FULL_GOLDEN) or {}
@@ -237,8 +297,13 @@ def main() -> None:
                     help="queries of the 1-core CPU baseline (default 10000; cfg5 4000)")
     ap.add_argument("--cpu-sample-all", type=int, default=None,
                     help="queries of the all-cores CPU baseline (default 16000; cfg5 8000)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: warm and cold end to end, the CPU "
+                         "baselines, (N > 1) the unsharded comparison run")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end-to-end legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--aln", default="", help="extra aln options appended to the preset's (e.g. '-l 16')")
     args = ap.parse_args()
@@ -419,10 +484,23 @@ def main() -> None:
     matches = None
     gather_check = None
     timed_sha = None  # rank 0: sha256 of the timed run's whole output
+    if args.dump_outputs and rank == 0:
+        recs = sess.hits()
+        if gatherer is not None:
+            import numpy as np
+
+            recs = np.concatenate([m.cpu().numpy().view(HIT_DTYPE) for m in gatherer.records()])
+        dump_outputs(args.dump_outputs, text, recs)
+        del recs
     if dist is None:
         timed_sha = hashlib.sha256(text).hexdigest()
         if pin:
             matches = len(text) == pin["bytes"] and timed_sha == pin["sha256"]
+    elif not args.full:  # the assembled file against the reference pin, no run of its own
+        if pin:
+            write_assembled(dist, coll_dev, rank, world, out_path, text)
+            if rank == 0:
+                matches = os.path.getsize(out_path) == pin["bytes"] and _sha_file(out_path) == pin["sha256"]
     else:  # also at world 1 under GHOSTM_BENCH_DIST=1: the gather path checks itself
         write_assembled(dist, coll_dev, rank, world, out_path, text)
         # rank 0 checks the last step's gather (the one collective) and the
@@ -461,7 +539,7 @@ def main() -> None:
     # page cache stalls now and then: single runs of cfg3 spread from 33 to 49
     # ms, profiles/r4n_e2e/)
     e2e = None
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         runs, files_ok, create_s = [], [], []
         for _ in range(5):
             # a fresh output path per run (truncating the last run's 0.5 GB file
@@ -520,7 +598,7 @@ def main() -> None:
     # (HIP runtime start, file loads, H2D, search, the output file; no device
     # blocks from an earlier session), spawn to exit, the median of three
     e2e_cold = None
-    if not args.no_e2e and world == 1 and dist is None:
+    if args.full and not args.no_e2e and world == 1 and dist is None:
         from ghostm_amd.native import BIN_PATH
 
         runs, files_ok = [], []
@@ -549,7 +627,7 @@ def main() -> None:
     k = args.steps
     per = {key: v / k for key, v in st_acc.items()}
     cpu = cpu_all = None
-    if rank == 0 and world == 1 and not args.no_cpu:  # the CPU baseline is an N=1 figure
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:  # the CPU baseline is an N=1 figure
         n1 = args.cpu_sample or w.get("cpu_sample", 10000)
         nall = args.cpu_sample_all or w.get("cpu_sample_all", 16000)
         cpu = cpu_baseline(workdir, preset, dbprefix, min(n1, nq), aln_args)

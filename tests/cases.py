@@ -250,8 +250,16 @@ def formatted_files(d: str) -> list[str]:
 def run_aln(exe: str, d: str, opts: list[str], env: dict, out: str) -> bytes:
     e = dict(os.environ)
     e.update(env)
-    subprocess.run([exe, "aln", "-i", os.path.join(d, "q"), "-d", os.path.join(d, "db"),
-                    "-o", out] + list(opts), check=True, env=e, capture_output=True)
+    if exe == REF_PLUGIN:
+        # the drop-in under test is this tree's library, wherever the reference
+        # build was linked or is kept (the search path comes before its runpath)
+        e["LD_LIBRARY_PATH"] = os.pathsep.join(
+            [os.path.join(REPO, "ghostm_amd", "lib")] + [p for p in [e.get("LD_LIBRARY_PATH")] if p])
+    r = subprocess.run([exe, "aln", "-i", os.path.join(d, "q"), "-d", os.path.join(d, "db"),
+                        "-o", out] + list(opts), env=e, capture_output=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"{exe} exited with status {r.returncode}: "
+                           f"{r.stderr.decode(errors='replace')[-2000:]}")
     with open(out, "rb") as f:
         return f.read()
 

@@ -32,7 +32,7 @@ def test_bench_rccl_data_path_world1(tmp_path):
     env.pop("GHOSTM_BENCH_BACKEND", None)
     env.pop("GHOSTM_BENCH_NO_BIND", None)
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--preset", "cfg4", "--queries", "20000",
-           "--steps", "2", "--warmup", "1", "--no-cpu", "--workdir", str(tmp_path)]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--workdir", str(tmp_path)]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=110, env=env)
     assert p.returncode == 0, p.stderr[-4000:]
     lines = [x for x in p.stdout.splitlines() if x.startswith("{")]
