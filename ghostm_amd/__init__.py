@@ -3,7 +3,8 @@
 Seed lookup, Gotoh score DP and traceback are hand-written HIP kernels in
 csrc/; the merge/E-value host logic and the C ABI live in libghostm_hip.so.
 """
-from .aligner import Aligner, GhostmError, HIT_DTYPE, Session, format_db, format_queries, run_cli, synth
+from .aligner import (Aligner, GhostmError, HIT_DTYPE, HIT_EXT_DTYPE, Session, format_db, format_queries, run_cli,
+                      synth, traceback_ext_host)
 from .native import BIN_PATH, LIB_PATH, NativeLibraryMissing, load
 
 __all__ = [
@@ -11,6 +12,8 @@ __all__ = [
     "Session",
     "GhostmError",
     "HIT_DTYPE",
+    "HIT_EXT_DTYPE",
+    "traceback_ext_host",
     "format_db",
     "format_queries",
     "synth",

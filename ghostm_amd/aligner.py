@@ -34,9 +34,40 @@ HIT_DTYPE = np.dtype(
     ]
 )
 
+# GhostmHitExt: one per hit of Session.hits(), zero-based query coordinates
+HIT_EXT_DTYPE = np.dtype([("q_start", "<u4"), ("q_end", "<u4"), ("mismatches", "<u4"), ("gap_opens", "<u4")])
+
 
 class GhostmError(RuntimeError):
     pass
+
+
+def traceback_ext_host(query_seqs, L, db, score_matrix, query_ids, db_ends, base_search_length,
+                       open_gap=-11, extend_gap=-1):
+    """The host model of the extended traceback (GhostmTraceBackExtHost; no
+    device): query_seqs = uint8 codes of nq records of L, db = the END-separated
+    uint8 codes of a DB chunk, score_matrix = 32x32 int32 M[db*32 + query].
+    Returns (db_starts, aln_lens, aln_matches, ext[HIT_EXT_DTYPE])."""
+    lib = native.load()
+    qs = np.ascontiguousarray(query_seqs, dtype=np.uint8).reshape(-1)
+    dbs = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
+    m = np.ascontiguousarray(score_matrix, dtype=np.int32).reshape(-1)
+    qid = np.ascontiguousarray(query_ids, dtype=np.uint32)
+    end = np.ascontiguousarray(db_ends, dtype=np.uint32)
+    if m.size != 32 * 32 or L <= 0 or qs.size % L or qid.shape != end.shape:
+        raise ValueError("traceback_ext_host: bad argument shapes")
+    n = len(qid)
+    start, alen, match = (np.zeros(n, dtype=np.uint32) for _ in range(3))
+    ext = np.zeros(n, dtype=HIT_EXT_DTYPE)
+    u8p, u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+    rc = lib.GhostmTraceBackExtHost(
+        qs.ctypes.data_as(u8p), qs.size // L, L, dbs.ctypes.data_as(u8p), dbs.size,
+        m.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n, qid.ctypes.data_as(u32p), end.ctypes.data_as(u32p),
+        base_search_length, open_gap, extend_gap, start.ctypes.data_as(u32p), alen.ctypes.data_as(u32p),
+        match.ctypes.data_as(u32p), ext.ctypes.data_as(ctypes.POINTER(native.GhostmHitExt)))
+    if rc != 0:
+        raise GhostmError(native.last_error())
+    return start, alen, match, ext
 
 
 class Aligner:
@@ -128,6 +159,18 @@ class Session:
         out = np.zeros(n, dtype=HIT_DTYPE)
         if n:
             lib.GhostmSessionHits(self._h, out.ctypes.data_as(ctypes.POINTER(native.GhostmHit)), n)
+        return out
+
+    def hits_ext(self) -> np.ndarray:
+        """One HIT_EXT_DTYPE record per hit of hits() (GhostmSessionHitsExt): query
+        coordinates, mismatches and gap opens, after a run with any -y."""
+        lib = native.load()
+        n = lib.GhostmSessionHitsExt(self._h, None, 0)
+        if n == ctypes.c_size_t(-1).value:
+            raise GhostmError(native.last_error())
+        out = np.zeros(n, dtype=HIT_EXT_DTYPE)
+        if n:
+            lib.GhostmSessionHitsExt(self._h, out.ctypes.data_as(ctypes.POINTER(native.GhostmHitExt)), n)
         return out
 
     def device_hits(self, device="cuda"):

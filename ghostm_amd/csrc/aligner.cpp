@@ -221,7 +221,7 @@ AlignerOptions ParseAlignerOptions(int argc, char **argv) {
   // small inputs); the oracle honours the same variable
   if (const char *e = getenv("GHOSTM_MAX_LIST_OVERRIDE")) o.max_list_length = (uint32_t)strtoul(e, nullptr, 10);
   o.matrix = ReadScoreMatrix(matrix_file);
-  if (o.output_style == 0) {
+  if (o.output_style == 0 || o.output_style == 6) {  // 6: BLAST-tabular, style 0's E-value and bit score
     // extension: GHOSTM_KARLIN=ungapped prices combinations the
     // reference's table lacks with the matrix's ungapped ideal parameters
     // (karlin_params.cpp); unset, they throw as the reference does
@@ -1461,8 +1461,147 @@ static size_t StreamPiecesPerWorker() {
 }
 
 const LineFormat &Session::Format() {
-  if (!format_) format_.reset(new LineFormat(opt_.output_style, opt_.karlin, 4095));
+  // -y 6 formats style-0 lines first: FormatTabular takes their identity,
+  // E-value and bit-score bytes
+  if (!format_) format_.reset(new LineFormat(opt_.output_style == 6 ? 0 : opt_.output_style, opt_.karlin, 4095));
   return *format_;
+}
+
+// The extended traceback of every final hit (HitsExt). A hit names its query
+// chunk and DB chunk through its global indices; its chunk-local query, its
+// absolute end and its known start go to one TraceBackExt call per (query
+// chunk, DB chunk). A hit record carries the last query of its name group (the
+// reference's result_list[last]), not the query that scored: for a group of
+// several queries (a DNA read's frames) every query of the group is traced and
+// the first that reproduces the hit's (db_start, aln_len, aln_match) is taken.
+const std::vector<GhostmHitExt> &Session::HitsExt() {
+  if (hits_ext_valid_) return hits_ext_;
+  formatter_->Drain();
+  const std::vector<GhostmHit> &hits = Hits();
+  hits_ext_.assign(hits.size(), GhostmHitExt{0, 0, 0, 0});
+  struct Item {
+    size_t hit;
+    uint32_t q0, q1, end, start;  // queries [q0, q1] of the chunk; absolute DB coordinates
+  };
+  std::vector<std::vector<Item>> groups(queries_.size() * dbs_.size());
+  for (size_t h = 0; h < hits.size(); ++h) {
+    const GhostmHit &r = hits[h];
+    size_t qi = 0, di = 0;
+    while (qi < queries_.size() &&
+           !(r.query_id >= queries_[qi].global_base && r.query_id - queries_[qi].global_base < queries_[qi].chunk.nseq))
+      ++qi;
+    while (di < dbs_.size() &&
+           !(r.db_id >= dbs_[di].global_base && r.db_id - dbs_[di].global_base < dbs_[di].chunk.nseq))
+      ++di;
+    if (qi == queries_.size() || di == dbs_.size()) throw Error("extended traceback: hit outside the loaded chunks");
+    const QueryData &q = queries_[qi];
+    const uint32_t local = r.query_id - q.global_base;
+    const size_t g = (size_t)(std::lower_bound(q.group_last.begin(), q.group_last.end(), local) - q.group_last.begin());
+    uint32_t q0 = local, q1 = local;
+    if (g < q.group_last.size() && q.group_first[g] <= local) q0 = q.group_first[g], q1 = q.group_last[g];
+    const uint32_t pos = dbs_[di].chunk.starts[r.db_id - dbs_[di].global_base];
+    groups[qi * dbs_.size() + di].push_back(Item{h, q0, q1, pos + r.db_end, pos + r.db_start});
+  }
+  DeviceModule &dev = DeviceModule::Get();
+  const DeviceTimes before = dev.times();
+  std::vector<uint32_t> qid, end, start_in, start, len, match;
+  std::vector<GhostmHitExt> ext;
+  for (size_t qi = 0; qi < queries_.size(); ++qi) {
+    for (size_t di = 0; di < dbs_.size(); ++di) {
+      const std::vector<Item> &items = groups[qi * dbs_.size() + di];
+      if (items.empty()) continue;
+      qid.clear();
+      end.clear();
+      start_in.clear();
+      for (const Item &it : items)
+        for (uint32_t f = it.q0; f <= it.q1; ++f) {
+          qid.push_back(f);
+          end.push_back(it.end);
+          start_in.push_back(it.start);
+        }
+      const uint32_t n = (uint32_t)qid.size();
+      start.resize(n);
+      len.resize(n);
+      match.resize(n);
+      ext.resize(n);
+      const QueryData &q = queries_[qi];
+      const uint32_t tb_base = q.chunk.L + 2 * opt_.extend * 2 * (1u << opt_.log_region);
+      dev.TraceBackExt(q.dev, dbs_[di].dev, n, qid.data(), end.data(), start_in.data(), tb_base, opt_.open_gap,
+                       opt_.extend_gap, start.data(), len.data(), match.data(), ext.data());
+      size_t k = 0;
+      for (const Item &it : items) {
+        const GhostmHit &r = hits[it.hit];
+        bool found = false;
+        for (uint32_t f = it.q0; f <= it.q1; ++f, ++k) {
+          if (found || start[k] != it.start || len[k] != r.aln_len || match[k] != r.aln_match) continue;
+          hits_ext_[it.hit] = ext[k];
+          found = true;
+        }
+        if (!found) throw Error("extended traceback: no query of the hit's name group reproduces its alignment");
+      }
+    }
+  }
+  const DeviceTimes &after = dev.times();
+  stats_.seconds_traceback_ext += after.traceback_ext - before.traceback_ext;
+  stats_.traceback_ext_launches += after.traceback_ext_launches - before.traceback_ext_launches;
+  stats_.traceback_ext_cells += after.traceback_ext_cells - before.traceback_ext_cells;
+  hits_ext_valid_ = true;
+  return hits_ext_;
+}
+
+// -y 6: qseqid sseqid pident length mismatch gapopen qstart qend sstart send
+// evalue bitscore, tab-separated. Every piece holds the style-0 lines of its
+// hits (name, name, pident, length, matches, start, end, E-value, bits, each
+// followed by a tab): the line keeps everything up to the length, then the
+// four new columns, then style 0's start, end, E-value and bit-score bytes.
+// The fields are found from the line's end, so a tab inside a name is harmless.
+void Session::FormatTabular() {
+  const std::vector<GhostmHitExt> &ext = HitsExt();
+  struct Piece {
+    std::string *text;
+    size_t first, n;
+  };
+  std::vector<Piece> pieces;
+  size_t at = 0;
+  for (size_t k = 0; k < used_parts_; ++k)
+    for (size_t t = 0; t < parts_[k].text.size(); ++t) {
+      pieces.push_back(Piece{&parts_[k].text[t], at, parts_[k].hits[t].size()});
+      at += parts_[k].hits[t].size();
+    }
+  ParallelFor(pieces.size(), threads_, [&](size_t b, size_t e, unsigned) {
+    std::string out;
+    for (size_t pi = b; pi < e; ++pi) {
+      const std::string &in = *pieces[pi].text;
+      out.clear();
+      out.reserve(in.size() + pieces[pi].n * 24);
+      size_t pos = 0;
+      for (size_t i = 0; i < pieces[pi].n; ++i) {
+        const size_t nl = in.find('\n', pos);
+        if (nl == std::string::npos) throw Error("tabular output: fewer lines than hits");
+        size_t tab[6], at_tab = nl;  // tab[0]: the line's trailing tab ... tab[5]: the one after the length
+        for (int c = 0; c < 6; ++c) {
+          if (at_tab <= pos) throw Error("tabular output: malformed line");
+          at_tab = in.rfind('\t', at_tab - 1);
+          if (at_tab == std::string::npos || at_tab < pos) throw Error("tabular output: malformed line");
+          tab[c] = at_tab;
+        }
+        const GhostmHitExt &x = ext[pieces[pi].first + i];
+        out.append(in, pos, tab[5] - pos);
+        char num[64], *p = num;
+        *p++ = '\t';
+        p = PutU32(p, x.mismatches); *p++ = '\t';
+        p = PutU32(p, x.gap_opens); *p++ = '\t';
+        p = PutU32(p, x.q_start + 1); *p++ = '\t';
+        p = PutU32(p, x.q_end + 1); *p++ = '\t';
+        out.append(num, (size_t)(p - num));
+        out.append(in, tab[4] + 1, tab[0] - tab[4] - 1);
+        out.push_back('\n');
+        pos = nl + 1;
+      }
+      *pieces[pi].text = out;
+    }
+  });
+  joined_valid_ = false;
 }
 
 void Session::Part::Reset(size_t pieces) {
@@ -1604,7 +1743,9 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  if (stream_to_file) {
+  // -y 6 is written after the post-pass (HitsExt), not while the search runs
+  const bool tabular = opt_.output_style == 6;
+  if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
     stream_fd_ = open(opt_.output_file.c_str(), O_WRONLY | O_CREAT | O_TRUNC, 0644);
@@ -1637,6 +1778,8 @@ void Session::Run(bool stream_to_file) {
   joined_valid_ = false;
   hits_.clear();
   hits_valid_ = false;
+  hits_ext_.clear();
+  hits_ext_valid_ = false;
   Format();  // built here, before any formatting task can need it
   dev.ResetRecords(HitCapacity());  // the most records the run can append
   records_on_device_ = true;
@@ -1704,6 +1847,14 @@ void Session::Run(bool stream_to_file) {
   stats_.tracebacks += dt.traced_hits;  // device merge (the host merge counts its own)
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
+  if (tabular) {
+    FormatTabular();
+    if (stream_to_file) {
+      WriteOutputFile();
+      streamed_ = true;
+    }
+    stats_.seconds_total = NowSeconds() - t0;
+  }
 }
 
 const std::string &Session::Output() {

@@ -144,6 +144,12 @@ class Session {
   const std::string &Output();         // text of the last run (joined on first use)
   void WriteOutputFile();
   const std::vector<GhostmHit> &Hits();
+  // One GhostmHitExt per hit of Hits(): a post-pass of the extended traceback
+  // over the final hits of the last run, grouped by (query chunk, DB chunk),
+  // with the known starts; computed on first use, kept until the next run.
+  // The search pipeline is not involved, so the records do not depend on the
+  // merge mode or the batch cuts. With -y 6 Run makes them and the text.
+  const std::vector<GhostmHitExt> &HitsExt();
   // Hit records of the last run in device memory (this session's GPU): copies
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
@@ -224,6 +230,8 @@ class Session {
   void PartDone(const Part *part);
   void StreamPart(Part *part);
   const LineFormat &Format();
+  // -y 6: rewrites the parts' style-0 lines as the twelve BLAST-tabular columns
+  void FormatTabular();
 
   AlignerOptions opt_;
   uint64_t shard_begin_ = 0, shard_end_ = UINT64_MAX;  // query range over the loaded chunks
@@ -238,6 +246,8 @@ class Session {
   bool joined_valid_ = false;
   std::vector<GhostmHit> hits_;
   bool hits_valid_ = false;
+  std::vector<GhostmHitExt> hits_ext_;
+  bool hits_ext_valid_ = false;
   bool records_on_device_ = false;
   GhostmStats stats_{};
   unsigned threads_ = 1;

@@ -122,6 +122,20 @@ size_t GhostmSessionHits(void *s, GhostmHit *hits, size_t cap) {
   return n;
 }
 
+size_t GhostmSessionHitsExt(void *s, GhostmHitExt *ext, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmHitExt> &h = static_cast<Session *>(s)->HitsExt();
+    if (!ext) return h.size();
+    const size_t n = std::min(cap, h.size());
+    std::memcpy(ext, h.data(), n * sizeof(GhostmHitExt));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
 size_t GhostmSessionDeviceHits(void *s, void *dst_device, size_t cap) {
   try {
     if (!s) throw Error("null session");

@@ -16,6 +16,8 @@
 #include <string>
 #include <vector>
 
+struct GhostmHitExt;  // include/ghostm_hip.h
+
 namespace ghostm {
 
 namespace kern {
@@ -92,6 +94,8 @@ struct DeviceTimes {
   uint64_t score_launches_sparse = 0;             // K2 launches of sparse segments run by k_score16f<16, true> (kScoreRowsSparse)
   uint64_t seed_table_full = 0;                   // ... queries redone by k_seed (bin table probe bound reached)
   uint64_t traced_hits = 0;                       // device merge: hits selected from new candidates (K3 run)
+  double traceback_ext = 0;                       // the extended traceback (k_traceback_ext): seconds,
+  uint64_t traceback_ext_launches = 0, traceback_ext_cells = 0;  // launches, L x processed columns
 };
 
 class DeviceModule {
@@ -205,6 +209,15 @@ class DeviceModule {
   void TraceBack(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const uint32_t *db_end,
                  uint32_t base_search_length, int open, int ext, uint32_t *db_start,
                  uint32_t *aln_len, uint32_t *aln_match, float *seq_id);
+
+  // The extended traceback (kern::k_traceback_ext) on n hits: K3's outputs plus
+  // one GhostmHitExt per hit. db_start_in (may be null): the hits' known
+  // starts; each DP then stops after end - start + 1 columns, and the hits run
+  // in the order of that count. Throws when L or the window exceeds the packed
+  // fields. Adds its device time, launches and cells to times().
+  void TraceBackExt(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const uint32_t *db_end,
+                    const uint32_t *db_start_in, uint32_t base_search_length, int open, int ext,
+                    uint32_t *db_start, uint32_t *aln_len, uint32_t *aln_match, GhostmHitExt *out);
 
   DeviceTimes &times() {
     SettleSeedTime();

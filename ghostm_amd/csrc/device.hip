@@ -269,6 +269,7 @@ struct DeviceModule::Impl {
   } deferred;
   // K3 work (tb_sort: two histograms + total, two cursor arrays)
   DevBuf tb_qid, tb_end, tb_start, tb_ml;
+  DevBuf tb_ext;  // k_traceback_ext's inputs, outputs and cell counter (TraceBackExt)
   DevBuf tb_width, tb_ncols, tb_skey, tb_key, tb_order1, tb_order2, tb_sort, tb_pair_a, tb_pair_b, tb_best;
   int cus = 256;
   // K4 work
@@ -2036,12 +2037,120 @@ void DeviceModule::TraceBack(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *
   }
 }
 
+// Rows per lane of k_traceback_ext: four state words per row (H, E, ml, x), so
+// S = 32 is left out (128 state registers per lane); otherwise ChooseLayout's
+// cost, the lane-steps per useful cell.
+static Layout ChooseExtLayout(uint32_t L, uint32_t width) {
+  Layout best{16, 8, 128, 8};
+  double best_cost = 1e300;
+  for (int S : {16, 8}) {
+    const uint32_t G = (L + S - 1) / S;
+    if (G == 0 || G > 16) continue;
+    const uint32_t gpw = 64 / G;
+    const double cost = (double)(G * S) * (double)(width + G - 1) / (double)(gpw * G);
+    if (cost < best_cost * 0.999) {
+      best_cost = cost;
+      best = Layout{S, G, G * (uint32_t)S, gpw};
+    }
+  }
+  return best;
+}
+
+void DeviceModule::TraceBackExt(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const uint32_t *db_end,
+                                const uint32_t *db_start_in, uint32_t base, int open, int ext,
+                                uint32_t *db_start, uint32_t *aln_len, uint32_t *aln_match, GhostmHitExt *out) {
+  Use();
+  Impl &I = *impl_;
+  if (n == 0) return;
+  // field widths of the packed words (kernels.h k_traceback_ext): origin row 7
+  // bits, mismatches 8 bits (at most L), gap opens 15 bits (at most the path
+  // length, below L + window)
+  if (q->L == 0 || q->L > 127) throw Error("extended traceback: query length outside 1..127");
+  if ((uint64_t)q->L + base >= 32768) throw Error("extended traceback: window too wide for the packed fields");
+  for (uint32_t k = 0; k < n; ++k) {
+    if (qid[k] >= q->nseq || db_end[k] >= d->len) throw Error("extended traceback: hit outside the resident chunk");
+    if (db_start_in && db_start_in[k] > db_end[k]) throw Error("extended traceback: start after end");
+  }
+  // qid, end, [ncols, order], start, ml, x, row, then the u64 cell counter
+  I.tb_ext.Reserve((size_t)n * 4 * 8 + 8);
+  uint32_t *w = I.tb_ext.as<uint32_t>();
+  uint32_t *d_qid = w, *d_end = w + n, *d_ncols = w + 2 * (size_t)n, *d_order = w + 3 * (size_t)n;
+  uint32_t *d_out = w + 4 * (size_t)n;  // start, ml, x, row
+  HIP_CHECK(hipMemcpyAsync(d_qid, qid, (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
+  HIP_CHECK(hipMemcpyAsync(d_end, db_end, (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
+  std::vector<uint32_t> ncols, order;
+  if (db_start_in) {
+    // hits of about equal column counts share a wave (its loop runs to the widest)
+    // (a stable counting sort: a count above the window is cut to it, as the kernel does)
+    ncols.resize(n);
+    order.resize(n);
+    std::vector<uint32_t> first((size_t)base + 2, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+      ncols[k] = std::min(db_end[k] - db_start_in[k] + 1, base);
+      ++first[ncols[k] + 1];
+    }
+    for (size_t c = 1; c < first.size(); ++c) first[c] += first[c - 1];
+    for (uint32_t k = 0; k < n; ++k) order[first[ncols[k]]++] = k;
+    HIP_CHECK(hipMemcpyAsync(d_ncols, ncols.data(), (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
+    HIP_CHECK(hipMemcpyAsync(d_order, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
+  }
+  const Layout lay = ChooseExtLayout(q->L, base);
+  kern::TbExtArgs ea{};
+  kern::TbArgs &a = ea.tb;
+  a.qseq = q->seq.as<uint8_t>();
+  a.L = q->L;
+  a.Lpad = lay.Lpad;
+  a.G = lay.G;
+  a.gpw = lay.gpw;
+  a.db = d->Residues();
+  a.mat_tb = I.mat_tb.as<int>();
+  a.qid = d_qid;
+  a.end = d_end;
+  a.n = n;
+  a.base = base;
+  a.open = open;
+  a.ext = ext;
+  a.out_start = d_out;
+  a.out_ml = d_out + n;
+  ea.out_x = d_out + 2 * (size_t)n;
+  ea.out_row = d_out + 3 * (size_t)n;
+  a.order = db_start_in ? d_order : nullptr;
+  a.ncols = db_start_in ? d_ncols : nullptr;
+  unsigned long long *cells_d = reinterpret_cast<unsigned long long *>(w + 8 * (size_t)n);
+  HIP_CHECK(hipMemsetAsync(cells_d, 0, 8, S(stream_)));
+  a.cells = cells_d;
+  const uint32_t per_block = lay.gpw * (kern::kTbBlock / 64);
+  const dim3 grid((n + per_block - 1) / per_block), block(kern::kTbBlock);
+  HIP_CHECK(hipEventRecord(I.ev0, S(stream_)));
+  if (lay.S == 8) hipLaunchKernelGGL(kern::k_traceback_ext<8>, grid, block, 0, S(stream_), ea);
+  else hipLaunchKernelGGL(kern::k_traceback_ext<16>, grid, block, 0, S(stream_), ea);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(I.ev1, S(stream_)));
+  std::vector<uint32_t> res((size_t)n * 4);
+  unsigned long long cells = 0;
+  HIP_CHECK(hipMemcpyAsync(res.data(), d_out, (size_t)n * 16, hipMemcpyDeviceToHost, S(stream_)));
+  HIP_CHECK(hipMemcpyAsync(&cells, cells_d, 8, hipMemcpyDeviceToHost, S(stream_)));
+  HIP_CHECK(hipStreamSynchronize(S(stream_)));
+  times_.traceback_ext += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+  times_.traceback_ext_launches += 1;
+  times_.traceback_ext_cells += cells;
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t ml = res[(size_t)n + k], x = res[2 * (size_t)n + k];
+    if (db_start) db_start[k] = res[k];
+    if (aln_len) aln_len[k] = ml >> 8;
+    if (aln_match) aln_match[k] = ml & 0xFFu;
+    if (out)
+      out[k] = GhostmHitExt{res[3 * (size_t)n + k], (x >> kern::kExtOriginShift) & 0x7Fu,
+                            (x >> kern::kExtMismShift) & 0xFFu, x >> kern::kExtOpenShift};
+  }
+}
+
 const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_amd/srchash.py)
 
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -2329,6 +2438,26 @@ int TraceBackGpu(uint32_t nhits, const uint32_t query_ids[], const uint32_t db_e
     if (query_sequence_length != r.query->L) throw Error("query shape differs from SetQueryGpu");
     DeviceModule::Get().TraceBack(r.query, r.db, nhits, query_ids, db_ends, base_search_length,
                                   open_gap, extend_gap, db_starts, aln_lens, aln_matches, seq_ids);
+    return 0;
+  } catch (std::exception &e) {
+    SetError(e.what());
+    return 1;
+  }
+}
+
+int TraceBackExtGpu(uint32_t nhits, const uint32_t query_ids[], const uint32_t db_ends[],
+                    const uint32_t db_starts_in[], uint32_t query_sequence_length,
+                    uint32_t base_search_length, int open_gap, int extend_gap, uint32_t db_starts[],
+                    uint32_t aln_lens[], uint32_t aln_matches[], GhostmHitExt ext[]) {
+  try {
+    if (nhits == 0) return 0;
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    if (!r.query || !r.db) throw Error("SetQueryGpu/SetDbGpu not called");
+    if (query_sequence_length != r.query->L) throw Error("query shape differs from SetQueryGpu");
+    if (!query_ids || !db_ends) throw Error("TraceBackExtGpu: null hit arrays");
+    DeviceModule::Get().TraceBackExt(r.query, r.db, nhits, query_ids, db_ends, db_starts_in, base_search_length,
+                                     open_gap, extend_gap, db_starts, aln_lens, aln_matches, ext);
     return 0;
   } catch (std::exception &e) {
     SetError(e.what());

@@ -2855,6 +2855,155 @@ __global__ __launch_bounds__(kTbBlock) void k_traceback(TbArgs a) {
   WaveAddCells(a.cells, (valid && i == 0) ? (unsigned long long)ncols * a.L : 0ull);
 }
 
+// k_traceback_ext: k_traceback with a second bookkeeping word per row, for the
+// BLAST-tabular columns (GhostmHitExt): besides ml = (len << 8) | matches every
+// H cell carries
+//   x = gap opens << 17 | mismatches << 9 | origin row << 2 | op
+// (op: 0 none, 1 diagonal, 2 E, 3 F; origin = the query row the path began
+// in). Like ml, x is taken from the H cell the step comes from, also for the E
+// and F chains: the diagonal keeps the opens and adds a mismatch, a gap step
+// adds an open unless that H cell was itself reached by the same kind of gap;
+// a step from a zero cell (ml == 0) starts the path in this row. The host
+// checks the field widths (L <= 127, path length below 2^15). With
+// ncols the DP stops after the hit's known column count (end - start + 1): the
+// first strict maximum of columns 0..j* is the whole window's. Outputs of the
+// first maximal cell: start, ml, x and its query row.
+struct TbExtArgs {
+  TbArgs tb;
+  uint32_t *out_x;
+  uint32_t *out_row;
+};
+constexpr uint32_t kExtOpMask = 3u, kExtDiag = 1u, kExtIns = 2u, kExtDel = 3u;
+constexpr uint32_t kExtOriginShift = 2, kExtMismShift = 9, kExtOpenShift = 17;
+
+// x of a gap step (op) in row k from the H cell (pml, px)
+__device__ inline uint32_t ExtGapStep(uint32_t pml, uint32_t px, uint32_t k, uint32_t op) {
+  const uint32_t x = pml ? px : (k << kExtOriginShift);
+  return ((x & ~kExtOpMask) | op) + ((x & kExtOpMask) != op ? (1u << kExtOpenShift) : 0u);
+}
+
+template <int S>
+__global__ __launch_bounds__(kTbBlock) void k_traceback_ext(TbExtArgs ea) {
+  GHOSTM_POISON_LDS();
+  const TbArgs &a = ea.tb;
+  __shared__ int s_mat[32 * 32];
+  for (uint32_t e = threadIdx.x; e < 32 * 32; e += kTbBlock) s_mat[e] = a.mat_tb[e];
+  __syncthreads();
+
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t g = lane / a.G, i = lane - g * a.G;
+  const uint32_t idx = (blockIdx.x * (kTbBlock / 64) + wave) * a.gpw + g;
+  const bool in_range = g < a.gpw && idx < a.n;
+  const uint32_t hit = in_range && a.order ? a.order[idx] : idx;
+  const bool valid = in_range;
+  uint32_t p0 = 0, width = 0;
+  // processing row U = i*S + u is query position krow0 - u (padding rows outside 0..L-1)
+  const int krow0 = (int)a.Lpad - 1 - (int)(i * S);
+  uint32_t qcode[S / 4];
+#pragma unroll
+  for (int w = 0; w < S / 4; ++w) qcode[w] = 0x1F1F1F1Fu;
+  if (valid) {
+    p0 = a.end[hit];
+    width = p0 < a.base ? p0 + 1 : a.base;
+    if (a.ncols) width = min(width, a.ncols[hit]);
+    const uint8_t *qs = a.qseq + (size_t)a.qid[hit] * a.L;
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+      const int k = krow0 - u;
+      const uint32_t code = (k >= 0 && k < (int)a.L) ? qs[k] : kPadCode;
+      qcode[u >> 2] = (qcode[u >> 2] & ~(0xFFu << (8 * (u & 3)))) | (code << (8 * (u & 3)));
+    }
+  }
+  int H[S], E[S];
+  uint32_t M[S], X[S];
+#pragma unroll
+  for (int u = 0; u < S; ++u) { H[u] = 0; E[u] = 0; M[u] = 0; X[u] = 0; }
+  int best = 0, best_col = 0;
+  uint32_t best_ml = 0, best_x = 0, best_row = 0;
+  int hout = 0, fout = 0, hprev = 0;
+  uint32_t mout = 0, xout = 0, mprev = 0, xprev = 0;
+  bool done = false;
+  uint32_t ncols = 0;
+  const int open = a.open, ext = a.ext;
+  int j = -(int)i;
+  const uint32_t wmax = WaveMax(valid ? width : 0u);
+  const uint32_t steps = wmax ? wmax + a.G - 1 : 0u;
+  for (uint32_t step = 0; step < steps; ++step, ++j) {
+    int hin = __shfl_up(hout, 1), fin = __shfl_up(fout, 1);
+    uint32_t min_ = (uint32_t)__shfl_up((int)mout, 1), xin = (uint32_t)__shfl_up((int)xout, 1);
+    if (i == 0) { hin = 0; fin = 0; min_ = 0; xin = 0; }
+    const int diag0 = hprev;
+    const uint32_t tml0 = mprev, tx0 = xprev;
+    hprev = hin;
+    mprev = min_;
+    xprev = xin;
+    bool active = valid && !done && j >= 0 && (uint32_t)j < width;
+    uint32_t c = 0;
+    if (active) {
+      c = a.db[p0 - j];
+      if (c == kSeqEnd) { done = true; active = false; }
+    }
+    if (active) {
+      const int *row = s_mat + c * 32;
+      int diag = diag0, F = fin, hup = hin;
+      uint32_t tml = tml0, tx = tx0, mup = min_, xup = xin;
+#pragma unroll
+      for (int u = 0; u < S; ++u) {
+        const uint32_t k = (uint32_t)(krow0 - u);
+        const int P = row[(qcode[u >> 2] >> (8 * (u & 3))) & 0xFFu];
+        const int s = diag + (P >> 16);
+        int h = 0;
+        uint32_t ml = 0, x = 0;
+        if (s > 0) {
+          h = s;
+          ml = tml + (uint32_t)(P & 0xFFFF);
+          const uint32_t px = tml ? tx : (k << kExtOriginShift);
+          x = ((px & ~kExtOpMask) | kExtDiag) + (((uint32_t)P & 1u) ? 0u : (1u << kExtMismShift));
+        }
+        const int e = max(E[u] + ext, H[u] + open);
+        E[u] = e;
+        if (e > h) { h = e; ml = M[u] + 0x100u; x = ExtGapStep(M[u], X[u], k, kExtIns); }
+        F = max(F + ext, hup + open);
+        if (F > h) { h = F; ml = mup + 0x100u; x = ExtGapStep(mup, xup, k, kExtDel); }
+        diag = H[u];
+        tml = M[u];
+        tx = X[u];
+        H[u] = h;
+        M[u] = ml;
+        X[u] = x;
+        hup = h;
+        mup = ml;
+        xup = x;
+        if (h > best) { best = h; best_col = j; best_ml = ml; best_x = x; best_row = k; }
+      }
+      hout = H[S - 1];
+      fout = F;
+      mout = M[S - 1];
+      xout = X[S - 1];
+      ++ncols;
+    } else {
+      hout = 0; fout = 0; mout = 0; xout = 0;
+    }
+  }
+  // first cell (column-major, rows in processing order) reaching the maximum
+  int B = best, C = best_col;
+  uint32_t ML = best_ml, BX = best_x, BR = best_row;
+  for (uint32_t k = 1; k < a.G; ++k) {
+    const int src = (int)(g * a.G + k);
+    const int ob = __shfl(best, src), oc = __shfl(best_col, src);
+    const uint32_t om = (uint32_t)__shfl((int)best_ml, src), ox = (uint32_t)__shfl((int)best_x, src);
+    const uint32_t orow = (uint32_t)__shfl((int)best_row, src);
+    if (ob > B || (ob == B && ob > 0 && oc < C)) { B = ob; C = oc; ML = om; BX = ox; BR = orow; }
+  }
+  if (valid && i == 0) {
+    a.out_start[hit] = p0 - (uint32_t)C;
+    a.out_ml[hit] = ML;
+    ea.out_x[hit] = BX;
+    ea.out_row[hit] = BR;
+  }
+  WaveAddCells(a.cells, (valid && i == 0) ? (unsigned long long)ncols * a.L : 0ull);
+}
+
 // k_traceback_key: the same reverse DP with each cell's (h, ml) folded into one
 // 32-bit key  h << 18 | prio << 16 | ml  (ml = len << 7 | matches). The
 // reference's selection — h = s if s > 0 else 0, then E if e > h, then F if

@@ -27,6 +27,7 @@ static int Usage() {
             << "       [-t threshold] [-r regionSize] [-e extendSize] [-G openGap] [-E extendGap]\n"
             << "       [-M scoreMatrix] [-y outputStyle] [-S startChunk] [-L endChunk] [-v]\n"
             << "       -i queries -d database -o output\n"
+            << "       (-y 6: BLAST-tabular, the twelve -outfmt 6 columns)\n"
             << "synth: ghostm synth -d db.fasta -q queries.fasta [-n nq] [-N dbResidues] [-s seed]\n";
   return 1;
 }

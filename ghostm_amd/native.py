@@ -40,6 +40,17 @@ class GhostmHit(ctypes.Structure):
     ]
 
 
+class GhostmHitExt(ctypes.Structure):
+    """what the BLAST-tabular columns need beyond a GhostmHit (16 bytes, zero-based)."""
+
+    _fields_ = [
+        ("q_start", c_uint32),
+        ("q_end", c_uint32),
+        ("mismatches", c_uint32),
+        ("gap_opens", c_uint32),
+    ]
+
+
 class GhostmStats(ctypes.Structure):
     _fields_ = [
         ("seconds_total", ctypes.c_double),
@@ -86,6 +97,9 @@ class GhostmStats(ctypes.Structure):
         ("score_launches_sparse", c_uint64),
         ("traceback_launches_keyframe", c_uint64),
         ("score_launches_levels", c_uint64),
+        ("seconds_traceback_ext", ctypes.c_double),
+        ("traceback_ext_launches", c_uint64),
+        ("traceback_ext_cells", c_uint64),
     ]
 
     def as_dict(self) -> dict:
@@ -118,6 +132,11 @@ SIGNATURES = {
     "GhostmDevicePoolInfo": (c_int, [POINTER(c_uint64), POINTER(c_uint64)]),
     "CountCandidatesGpu": (c_int, [c_uint32] * 6 + [u32p]),
     "TraceBackGpu": (c_int, [c_uint32, u32p, u32p, c_uint32, c_uint32, c_int, c_int, u32p, u32p, u32p, POINTER(c_float)]),
+    "TraceBackExtGpu": (c_int, [c_uint32, u32p, u32p, u32p, c_uint32, c_uint32, c_int, c_int, u32p, u32p, u32p,
+                                POINTER(GhostmHitExt)]),
+    "GhostmTraceBackExtHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, POINTER(ctypes.c_uint8), c_uint32,
+                                       POINTER(c_int), c_uint32, u32p, u32p, c_uint32, c_int, c_int, u32p, u32p, u32p,
+                                       POINTER(GhostmHitExt)]),
     "GhostmBuildIndexGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, u32p, u32p, u32p, c_int,
                                     POINTER(c_float)]),
     "GhostmFormatQueriesGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_uint32,
@@ -136,6 +155,7 @@ SIGNATURES = {
     "GhostmSessionOutput": (c_size_t, [c_void_p, c_char_p, c_size_t]),
     "GhostmSessionWrite": (c_int, [c_void_p]),
     "GhostmSessionHits": (c_size_t, [c_void_p, POINTER(GhostmHit), c_size_t]),
+    "GhostmSessionHitsExt": (c_size_t, [c_void_p, POINTER(GhostmHitExt), c_size_t]),
     "GhostmSessionDeviceHits": (c_size_t, [c_void_p, c_void_p, c_size_t]),
     "GhostmSessionStats": (c_int, [c_void_p, POINTER(GhostmStats)]),
     "GhostmSessionStatsSized": (c_size_t, [c_void_p, POINTER(GhostmStats), c_size_t]),

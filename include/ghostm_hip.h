@@ -115,6 +115,43 @@ int TraceBackGpu(uint32_t nhits, const uint32_t query_ids[], const uint32_t db_e
                  int open_gap, int extend_gap, uint32_t db_starts[], uint32_t aln_lens[],
                  uint32_t aln_matches[], float seq_ids[]);
 
+/* What the BLAST-tabular columns need beyond a GhostmHit (16 bytes): where the
+ * alignment lies in the query, its mismatches and its gap opens. Zero-based,
+ * "as printed minus one" like the GhostmHit coordinates. For a DNA query the
+ * query coordinates count residues of the translated frame record. */
+typedef struct GhostmHitExt {
+  uint32_t q_start;     /* query row of the first maximal cell of the reverse DP */
+  uint32_t q_end;       /* query row the path to that cell began in */
+  uint32_t mismatches;
+  uint32_t gap_opens;
+} GhostmHitExt;
+
+/* TraceBackGpu plus one GhostmHitExt per hit (kernel k_traceback_ext). The
+ * reference's traceback keeps, per H cell, the alignment length and matches of
+ * the H cell it steps from (also for its E and F chains); the extension carries
+ * mismatches, gap opens (a gap step opens a gap unless that H cell was reached
+ * by the same kind of gap step) and the path's first query row by the same
+ * rule, so aln_len = aln_match + mismatches + gap residues. db_starts,
+ * aln_lens and aln_matches are TraceBackGpu's. db_starts_in may be NULL; with
+ * the hits' known starts each DP stops at its first maximal column (same
+ * results, fewer columns). Fails (no wrapped field) when query_sequence_length
+ * > 127 or query_sequence_length + base_search_length >= 32768. */
+int TraceBackExtGpu(uint32_t nhits, const uint32_t query_ids[], const uint32_t db_ends[],
+                    const uint32_t db_starts_in[], uint32_t query_sequence_length,
+                    uint32_t base_search_length, int open_gap, int extend_gap, uint32_t db_starts[],
+                    uint32_t aln_lens[], uint32_t aln_matches[], GhostmHitExt ext[]);
+
+/* The same on the host, with no device call (the model the kernel is checked
+ * against): query_seqs = nq records of L codes, db = db_len END-separated
+ * codes, score_matrix = 32x32 M[db_code*32 + query_code]. Output arrays may be
+ * NULL. */
+int GhostmTraceBackExtHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, const uint8_t *db,
+                           uint32_t db_len, const int score_matrix[], uint32_t nhits,
+                           const uint32_t query_ids[], const uint32_t db_ends[],
+                           uint32_t base_search_length, int open_gap, int extend_gap,
+                           uint32_t db_starts[], uint32_t aln_lens[], uint32_t aln_matches[],
+                           GhostmHitExt ext[]);
+
 /* The `db` formatter's k-mer index of one DB chunk, built on the GPU
  * (replaces DBCreator::ConstructIndex, db_creator.cpp:167-241).
  * seq[len] = the chunk's END-separated residues (.seq); seed = the index seed mask
@@ -225,6 +262,10 @@ typedef struct GhostmStats {
   uint64_t traceback_launches_keyframe; /* K3 key DPs run with the column-framed E chain (k_traceback_key FRAME) */
   uint64_t score_launches_levels;   /* K2 launches of the 16-bit-row integer-pattern kernel with restart levels
                                        (k_score16f<S, true, false, true>) */
+  double seconds_traceback_ext;     /* the extended traceback post-pass (k_traceback_ext, device time); 0 until
+                                       -y 6 or GhostmSessionHitsExt asks for it */
+  uint64_t traceback_ext_launches;
+  uint64_t traceback_ext_cells;     /* sum over its DPs of L x processed columns */
 } GhostmStats;
 
 /* Session: parse `aln` options exactly like the reference (getopt string
@@ -298,7 +339,11 @@ int GhostmSessionRun(void *session);
 /* GhostmSessionRun that also writes the -o file while the search runs: each
  * segment's text is written, in output order, as soon as it is formatted (the
  * reference writes after each query chunk, aligner.cpp:211). The file equals
- * what GhostmSessionWrite writes; GhostmSessionWrite is then a no-op. */
+ * what GhostmSessionWrite writes; GhostmSessionWrite is then a no-op. With
+ * -y 6 (BLAST-tabular: qseqid sseqid pident length mismatch gapopen qstart qend
+ * sstart send evalue bitscore, one-based coordinates, pident/evalue/bitscore as
+ * -y 0 prints them) the text exists only after the GhostmHitExt post-pass, so
+ * the file is written at the end of the run. */
 int GhostmSessionRunToFile(void *session);
 
 /* Formatted output of the last run (reference WriteOutput/V1/V2 text). With
@@ -310,6 +355,15 @@ int GhostmSessionWrite(void *session);
 
 /* Hit records of the last run in output order; same NULL/cap convention. */
 size_t GhostmSessionHits(void *session, GhostmHit *hits, size_t cap);
+
+/* The GhostmHitExt of every hit of the last run (record i belongs to hit i of
+ * GhostmSessionHits); same NULL/cap convention, (size_t)-1 on error. Works
+ * after a run with any -y: a post-pass of k_traceback_ext over the final hits,
+ * grouped by (query chunk, DB chunk), computed on first use and kept until the
+ * next run. A hit of a name group of several queries (a DNA read's frames) is
+ * traced with the group's first query that reproduces its db_start, aln_len
+ * and aln_match. */
+size_t GhostmSessionHitsExt(void *session, GhostmHitExt *ext, size_t cap);
 
 /* The same records resident on the session's GPU, for a device-to-device
  * gather across ranks: copies min(n, cap) records to dst_device
