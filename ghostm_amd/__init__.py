@@ -3,8 +3,8 @@
 Seed lookup, Gotoh score DP and traceback are hand-written HIP kernels in
 csrc/; the merge/E-value host logic and the C ABI live in libghostm_hip.so.
 """
-from .aligner import (Aligner, GhostmError, HIT_DTYPE, HIT_EXT_DTYPE, Session, format_db, format_queries, run_cli,
-                      synth, traceback_ext_host)
+from .aligner import (Aligner, GhostmError, HIT_DTYPE, HIT_EXT_DTYPE, HIT_PATH_DTYPE, Session, cigar, format_db,
+                      format_queries, run_cli, synth, traceback_ext_host, traceback_path_host)
 from .native import BIN_PATH, LIB_PATH, NativeLibraryMissing, load
 
 __all__ = [
@@ -13,7 +13,10 @@ __all__ = [
     "GhostmError",
     "HIT_DTYPE",
     "HIT_EXT_DTYPE",
+    "HIT_PATH_DTYPE",
     "traceback_ext_host",
+    "traceback_path_host",
+    "cigar",
     "format_db",
     "format_queries",
     "synth",

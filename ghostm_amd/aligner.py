@@ -37,6 +37,18 @@ HIT_DTYPE = np.dtype(
 # GhostmHitExt: one per hit of Session.hits(), zero-based query coordinates
 HIT_EXT_DTYPE = np.dtype([("q_start", "<u4"), ("q_end", "<u4"), ("mismatches", "<u4"), ("gap_opens", "<u4")])
 
+# GhostmHitPath: one per hit, zero-based inclusive coordinates; the hit's
+# run-length words are ops[ops_offset : ops_offset + n_runs]
+HIT_PATH_DTYPE = np.dtype([("q_start", "<u4"), ("q_end", "<u4"), ("s_start", "<u4"), ("s_end", "<u4"),
+                           ("score", "<u4"), ("n_runs", "<u4"), ("ops_offset", "<u8")])
+
+PATH_OPS = "=XID"  # op codes 0..3 of a run-length word (length << 4 | op)
+
+
+def cigar(ops) -> str:
+    """The extended CIGAR of one hit's run-length words, for instance 31=1X2D40=."""
+    return "".join(f"{int(w) >> 4}{PATH_OPS[int(w) & 3]}" for w in ops)
+
 
 class GhostmError(RuntimeError):
     pass
@@ -68,6 +80,42 @@ def traceback_ext_host(query_seqs, L, db, score_matrix, query_ids, db_ends, base
     if rc != 0:
         raise GhostmError(native.last_error())
     return start, alen, match, ext
+
+
+def traceback_path_host(query_seqs, L, db, score_matrix, query_ids, db_ends, base_search_length,
+                        open_gap=-11, extend_gap=-1, db_starts_in=None):
+    """The host model of the path traceback (GhostmTraceBackPathHost; no device);
+    arguments as traceback_ext_host, db_starts_in = the hits' known starts or
+    None. Returns (records[HIT_PATH_DTYPE], ops[uint32])."""
+    lib = native.load()
+    qs = np.ascontiguousarray(query_seqs, dtype=np.uint8).reshape(-1)
+    dbs = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
+    m = np.ascontiguousarray(score_matrix, dtype=np.int32).reshape(-1)
+    qid = np.ascontiguousarray(query_ids, dtype=np.uint32)
+    end = np.ascontiguousarray(db_ends, dtype=np.uint32)
+    start = None if db_starts_in is None else np.ascontiguousarray(db_starts_in, dtype=np.uint32)
+    if m.size != 32 * 32 or L <= 0 or qs.size % L or qid.shape != end.shape or (
+            start is not None and start.shape != end.shape):
+        raise ValueError("traceback_path_host: bad argument shapes")
+    n = len(qid)
+    rec = np.zeros(n, dtype=HIT_PATH_DTYPE)
+    u8p, u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+
+    def call(ops, cap, used):
+        rc = lib.GhostmTraceBackPathHost(
+            qs.ctypes.data_as(u8p), qs.size // L, L, dbs.ctypes.data_as(u8p), dbs.size,
+            m.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n, qid.ctypes.data_as(u32p), end.ctypes.data_as(u32p),
+            None if start is None else start.ctypes.data_as(u32p), base_search_length, open_gap, extend_gap,
+            rec.ctypes.data_as(ctypes.POINTER(native.GhostmHitPath)), ops, cap, ctypes.byref(used))
+        if rc != 0:
+            raise GhostmError(native.last_error())
+
+    used = ctypes.c_size_t(0)
+    call(None, 0, used)  # the size needed
+    ops = np.zeros(used.value, dtype=np.uint32)
+    if used.value:
+        call(ops.ctypes.data_as(u32p), used.value, used)
+    return rec, ops
 
 
 class Aligner:
@@ -172,6 +220,27 @@ class Session:
         if n:
             lib.GhostmSessionHitsExt(self._h, out.ctypes.data_as(ctypes.POINTER(native.GhostmHitExt)), n)
         return out
+
+    def hits_path(self) -> tuple[np.ndarray, np.ndarray]:
+        """(records, ops): one HIT_PATH_DTYPE record per hit of hits()
+        (GhostmSessionHitsPath) and the run-length words they index
+        (GhostmSessionPathOps), after a run with any -y. cigar(ops[o:o + n]) is
+        a hit's extended CIGAR."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        n = lib.GhostmSessionHitsPath(self._h, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        rec = np.zeros(n, dtype=HIT_PATH_DTYPE)
+        if n:
+            lib.GhostmSessionHitsPath(self._h, rec.ctypes.data_as(ctypes.POINTER(native.GhostmHitPath)), n)
+        m = lib.GhostmSessionPathOps(self._h, None, 0)
+        if m == bad:
+            raise GhostmError(native.last_error())
+        ops = np.zeros(m, dtype=np.uint32)
+        if m:
+            lib.GhostmSessionPathOps(self._h, ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), m)
+        return rec, ops
 
     def device_hits(self, device="cuda"):
         """The hit records as a torch uint8 tensor on this session's GPU (32 bytes

@@ -221,7 +221,7 @@ AlignerOptions ParseAlignerOptions(int argc, char **argv) {
   // small inputs); the oracle honours the same variable
   if (const char *e = getenv("GHOSTM_MAX_LIST_OVERRIDE")) o.max_list_length = (uint32_t)strtoul(e, nullptr, 10);
   o.matrix = ReadScoreMatrix(matrix_file);
-  if (o.output_style == 0 || o.output_style == 6) {  // 6: BLAST-tabular, style 0's E-value and bit score
+  if (o.output_style == 0 || o.output_style == 6 || o.output_style == 7) {  // 6, 7: BLAST-tabular, style 0's E-value and bit score
     // extension: GHOSTM_KARLIN=ungapped prices combinations the
     // reference's table lacks with the matrix's ungapped ideal parameters
     // (karlin_params.cpp); unset, they throw as the reference does
@@ -1463,7 +1463,8 @@ static size_t StreamPiecesPerWorker() {
 const LineFormat &Session::Format() {
   // -y 6 formats style-0 lines first: FormatTabular takes their identity,
   // E-value and bit-score bytes
-  if (!format_) format_.reset(new LineFormat(opt_.output_style == 6 ? 0 : opt_.output_style, opt_.karlin, 4095));
+  const bool tabular = opt_.output_style == 6 || opt_.output_style == 7;
+  if (!format_) format_.reset(new LineFormat(tabular ? 0 : opt_.output_style, opt_.karlin, 4095));
   return *format_;
 }
 
@@ -1479,6 +1480,7 @@ const std::vector<GhostmHitExt> &Session::HitsExt() {
   formatter_->Drain();
   const std::vector<GhostmHit> &hits = Hits();
   hits_ext_.assign(hits.size(), GhostmHitExt{0, 0, 0, 0});
+  hit_source_.assign(hits.size(), HitSource{0, 0, 0, 0, 0});
   struct Item {
     size_t hit;
     uint32_t q0, q1, end, start;  // queries [q0, q1] of the chunk; absolute DB coordinates
@@ -1535,6 +1537,7 @@ const std::vector<GhostmHitExt> &Session::HitsExt() {
         for (uint32_t f = it.q0; f <= it.q1; ++f, ++k) {
           if (found || start[k] != it.start || len[k] != r.aln_len || match[k] != r.aln_match) continue;
           hits_ext_[it.hit] = ext[k];
+          hit_source_[it.hit] = HitSource{(uint32_t)qi, (uint32_t)di, f, it.end, it.start};
           found = true;
         }
         if (!found) throw Error("extended traceback: no query of the hit's name group reproduces its alignment");
@@ -1547,6 +1550,149 @@ const std::vector<GhostmHitExt> &Session::HitsExt() {
   stats_.traceback_ext_cells += after.traceback_ext_cells - before.traceback_ext_cells;
   hits_ext_valid_ = true;
   return hits_ext_;
+}
+
+// The alignment path of every final hit (HitsPath): each hit's chunk-local
+// query, absolute end and start as HitsExt() resolved them, one TraceBackPath
+// call per (query chunk, DB chunk); the subject coordinates are made relative
+// to the subject and the chunks' words joined in hit order.
+const std::vector<GhostmHitPath> &Session::HitsPath() {
+  if (hits_path_valid_) return hits_path_;
+  HitsExt();
+  const std::vector<GhostmHit> &hits = Hits();
+  hits_path_.assign(hits.size(), GhostmHitPath{0, 0, 0, 0, 0, 0, 0});
+  path_ops_.clear();
+  std::vector<std::vector<size_t>> groups(queries_.size() * dbs_.size());
+  for (size_t h = 0; h < hits.size(); ++h) groups[hit_source_[h].qi * dbs_.size() + hit_source_[h].di].push_back(h);
+  DeviceModule &dev = DeviceModule::Get();
+  const DeviceTimes before = dev.times();
+  std::vector<uint32_t> qid, end, start_in;
+  std::vector<GhostmHitPath> rec;
+  std::vector<std::vector<uint32_t>> words(groups.size());
+  for (size_t qi = 0; qi < queries_.size(); ++qi) {
+    for (size_t di = 0; di < dbs_.size(); ++di) {
+      const size_t gi = qi * dbs_.size() + di;
+      const std::vector<size_t> &items = groups[gi];
+      if (items.empty()) continue;
+      qid.clear();
+      end.clear();
+      start_in.clear();
+      for (size_t h : items) {
+        qid.push_back(hit_source_[h].query);
+        end.push_back(hit_source_[h].end);
+        start_in.push_back(hit_source_[h].start);
+      }
+      const uint32_t n = (uint32_t)items.size();
+      rec.resize(n);
+      const QueryData &q = queries_[qi];
+      const uint32_t tb_base = q.chunk.L + 2 * opt_.extend * 2 * (1u << opt_.log_region);
+      dev.TraceBackPath(q.dev, dbs_[di].dev, n, qid.data(), end.data(), start_in.data(), tb_base, opt_.open_gap,
+                        opt_.extend_gap, rec.data(), &words[gi]);
+      for (uint32_t k = 0; k < n; ++k) {
+        const GhostmHit &r = hits[items[k]];
+        const uint32_t pos = dbs_[di].chunk.starts[r.db_id - dbs_[di].global_base];
+        GhostmHitPath p = rec[k];
+        if (p.s_start != hit_source_[items[k]].start)
+          throw Error("path traceback: a path does not begin at its hit's start");
+        p.s_start -= pos;
+        p.s_end -= pos;
+        hits_path_[items[k]] = p;  // ops_offset: still within the chunk pair's words
+      }
+    }
+  }
+  // the words in hit order
+  for (size_t h = 0; h < hits.size(); ++h) {
+    GhostmHitPath &p = hits_path_[h];
+    const std::vector<uint32_t> &w = words[hit_source_[h].qi * dbs_.size() + hit_source_[h].di];
+    const size_t at = path_ops_.size();
+    path_ops_.insert(path_ops_.end(), w.begin() + p.ops_offset, w.begin() + p.ops_offset + p.n_runs);
+    p.ops_offset = at;
+  }
+  const DeviceTimes &after = dev.times();
+  stats_.seconds_traceback_path += after.traceback_path - before.traceback_path;
+  stats_.traceback_path_launches += after.traceback_path_launches - before.traceback_path_launches;
+  stats_.traceback_path_cells += after.traceback_path_cells - before.traceback_path_cells;
+  stats_.traceback_path_dir_bytes += after.traceback_path_dir_bytes - before.traceback_path_dir_bytes;
+  hits_path_valid_ = true;
+  return hits_path_;
+}
+
+const std::vector<uint32_t> &Session::PathOps() {
+  HitsPath();
+  return path_ops_;
+}
+
+// -y 7: the -y 6 columns with pident, length, mismatch, gapopen, qstart, qend,
+// sstart and send taken from the hit's path (so a line agrees with itself), and
+// a thirteenth column, the extended CIGAR. From the style-0 line: the two
+// names, then the E-value and bit-score bytes; the fields are found from the
+// line's end as in FormatTabular.
+void Session::FormatPathTabular() {
+  const std::vector<GhostmHitPath> &path = HitsPath();
+  const std::vector<uint32_t> &ops = path_ops_;
+  const LineFormat &w = Format();
+  struct Piece {
+    std::string *text;
+    size_t first, n;
+  };
+  std::vector<Piece> pieces;
+  size_t at = 0;
+  for (size_t k = 0; k < used_parts_; ++k)
+    for (size_t t = 0; t < parts_[k].text.size(); ++t) {
+      pieces.push_back(Piece{&parts_[k].text[t], at, parts_[k].hits[t].size()});
+      at += parts_[k].hits[t].size();
+    }
+  ParallelFor(pieces.size(), threads_, [&](size_t b, size_t e, unsigned) {
+    std::string out;
+    for (size_t pi = b; pi < e; ++pi) {
+      const std::string &in = *pieces[pi].text;
+      out.clear();
+      out.reserve(in.size() + pieces[pi].n * 64);
+      size_t pos = 0;
+      for (size_t i = 0; i < pieces[pi].n; ++i) {
+        const size_t nl = in.find('\n', pos);
+        if (nl == std::string::npos) throw Error("tabular output: fewer lines than hits");
+        size_t tab[8], at_tab = nl;  // tab[0]: the line's trailing tab ... tab[7]: the one after the subject name
+        for (int c = 0; c < 8; ++c) {
+          if (at_tab <= pos) throw Error("tabular output: malformed line");
+          at_tab = in.rfind('\t', at_tab - 1);
+          if (at_tab == std::string::npos || at_tab < pos) throw Error("tabular output: malformed line");
+          tab[c] = at_tab;
+        }
+        const GhostmHitPath &x = path[pieces[pi].first + i];
+        uint32_t count[4] = {0, 0, 0, 0}, gap_runs = 0;
+        for (uint32_t r = 0; r < x.n_runs; ++r) {
+          const uint32_t word = ops[x.ops_offset + r];
+          count[word & 3u] += word >> 4;
+          gap_runs += (word & 3u) >= 2;
+        }
+        const uint32_t length = count[0] + count[1] + count[2] + count[3];
+        out.append(in, pos, tab[7] + 1 - pos);
+        char num[160], *p = num;
+        p = w.PutId(p, length, count[0]); *p++ = '\t';
+        p = PutU32(p, length); *p++ = '\t';
+        p = PutU32(p, count[1]); *p++ = '\t';
+        p = PutU32(p, gap_runs); *p++ = '\t';
+        p = PutU32(p, x.q_start + 1); *p++ = '\t';
+        p = PutU32(p, x.q_end + 1); *p++ = '\t';
+        p = PutU32(p, x.s_start + 1); *p++ = '\t';
+        p = PutU32(p, x.s_end + 1); *p++ = '\t';
+        out.append(num, (size_t)(p - num));
+        out.append(in, tab[2] + 1, tab[0] - tab[2] - 1);
+        out.push_back('\t');
+        for (uint32_t r = 0; r < x.n_runs; ++r) {
+          const uint32_t word = ops[x.ops_offset + r];
+          p = PutU32(num, word >> 4);
+          *p++ = "=XID"[word & 3u];
+          out.append(num, (size_t)(p - num));
+        }
+        out.push_back('\n');
+        pos = nl + 1;
+      }
+      *pieces[pi].text = out;
+    }
+  });
+  joined_valid_ = false;
 }
 
 // -y 6: qseqid sseqid pident length mismatch gapopen qstart qend sstart send
@@ -1743,8 +1889,8 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  // -y 6 is written after the post-pass (HitsExt), not while the search runs
-  const bool tabular = opt_.output_style == 6;
+  // -y 6 and -y 7 are written after the post-pass (HitsExt, HitsPath), not while the search runs
+  const bool tabular = opt_.output_style == 6 || opt_.output_style == 7;
   if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
@@ -1780,6 +1926,10 @@ void Session::Run(bool stream_to_file) {
   hits_valid_ = false;
   hits_ext_.clear();
   hits_ext_valid_ = false;
+  hit_source_.clear();
+  hits_path_.clear();
+  path_ops_.clear();
+  hits_path_valid_ = false;
   Format();  // built here, before any formatting task can need it
   dev.ResetRecords(HitCapacity());  // the most records the run can append
   records_on_device_ = true;
@@ -1848,7 +1998,8 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    FormatTabular();
+    if (opt_.output_style == 7) FormatPathTabular();
+    else FormatTabular();
     if (stream_to_file) {
       WriteOutputFile();
       streamed_ = true;

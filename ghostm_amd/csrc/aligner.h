@@ -150,6 +150,14 @@ class Session {
   // The search pipeline is not involved, so the records do not depend on the
   // merge mode or the batch cuts. With -y 6 Run makes them and the text.
   const std::vector<GhostmHitExt> &HitsExt();
+  // One GhostmHitPath per hit of Hits() and the run-length words they index:
+  // a post-pass of the path traceback (DeviceModule::TraceBackPath), one call
+  // per (query chunk, DB chunk) that has hits, with the known starts and the
+  // query HitsExt() resolved for each hit; subject coordinates relative to the
+  // subject. Computed on first use, kept until the next run. With -y 7 Run
+  // makes them and the text.
+  const std::vector<GhostmHitPath> &HitsPath();
+  const std::vector<uint32_t> &PathOps();
   // Hit records of the last run in device memory (this session's GPU): copies
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
@@ -232,6 +240,8 @@ class Session {
   const LineFormat &Format();
   // -y 6: rewrites the parts' style-0 lines as the twelve BLAST-tabular columns
   void FormatTabular();
+  // -y 7: the same with columns 3 to 10 taken from the hit's path, and its CIGAR
+  void FormatPathTabular();
 
   AlignerOptions opt_;
   uint64_t shard_begin_ = 0, shard_end_ = UINT64_MAX;  // query range over the loaded chunks
@@ -248,6 +258,15 @@ class Session {
   bool hits_valid_ = false;
   std::vector<GhostmHitExt> hits_ext_;
   bool hits_ext_valid_ = false;
+  // per hit, from HitsExt(): query chunk, DB chunk, the chunk-local query that
+  // reproduced the hit, its absolute end and start
+  struct HitSource {
+    uint32_t qi, di, query, end, start;
+  };
+  std::vector<HitSource> hit_source_;
+  std::vector<GhostmHitPath> hits_path_;
+  std::vector<uint32_t> path_ops_;
+  bool hits_path_valid_ = false;
   bool records_on_device_ = false;
   GhostmStats stats_{};
   unsigned threads_ = 1;

@@ -136,6 +136,34 @@ size_t GhostmSessionHitsExt(void *s, GhostmHitExt *ext, size_t cap) {
   }
 }
 
+size_t GhostmSessionHitsPath(void *s, GhostmHitPath *rec, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmHitPath> &h = static_cast<Session *>(s)->HitsPath();
+    if (!rec) return h.size();
+    const size_t n = std::min(cap, h.size());
+    std::memcpy(rec, h.data(), n * sizeof(GhostmHitPath));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionPathOps(void *s, uint32_t *ops, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<uint32_t> &w = static_cast<Session *>(s)->PathOps();
+    if (!ops) return w.size();
+    const size_t n = std::min(cap, w.size());
+    std::memcpy(ops, w.data(), n * sizeof(uint32_t));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
 size_t GhostmSessionDeviceHits(void *s, void *dst_device, size_t cap) {
   try {
     if (!s) throw Error("null session");

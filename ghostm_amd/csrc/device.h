@@ -17,6 +17,7 @@
 #include <vector>
 
 struct GhostmHitExt;  // include/ghostm_hip.h
+struct GhostmHitPath;
 
 namespace ghostm {
 
@@ -96,6 +97,9 @@ struct DeviceTimes {
   uint64_t traced_hits = 0;                       // device merge: hits selected from new candidates (K3 run)
   double traceback_ext = 0;                       // the extended traceback (k_traceback_ext): seconds,
   uint64_t traceback_ext_launches = 0, traceback_ext_cells = 0;  // launches, L x processed columns
+  double traceback_path = 0;                      // the alignment paths (k_tb_path_fill + k_tb_path_walk): seconds,
+  uint64_t traceback_path_launches = 0, traceback_path_cells = 0;  // batches, L x processed columns,
+  uint64_t traceback_path_dir_bytes = 0;          // direction-buffer bytes of the batches
 };
 
 class DeviceModule {
@@ -218,6 +222,20 @@ class DeviceModule {
   void TraceBackExt(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const uint32_t *db_end,
                     const uint32_t *db_start_in, uint32_t base_search_length, int open, int ext,
                     uint32_t *db_start, uint32_t *aln_len, uint32_t *aln_match, GhostmHitExt *out);
+
+  // The alignment path of n hits (kern::k_tb_path_fill + kern::k_tb_path_walk):
+  // rec[n] (may be null) and the hits' run-length words in hit order (*ops is
+  // replaced; rec[i].ops_offset indexes it). db_start_in as for TraceBackExt.
+  // The hits run in batches whose direction buffer fits GHOSTM_PATH_SCRATCH_MB
+  // (default 1024) and that hold at most GHOSTM_PATH_BATCH_HITS hits; a batch's
+  // slots are packed on the device (kern::k_tb_path_compact, the offsets from
+  // the host's prefix sum over the records) and the batches' words joined in
+  // hit order on the host. Throws when L > 127
+  // or L + window >= 32768. Adds its device time, batches, cells and direction
+  // bytes to times().
+  void TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const uint32_t *db_end,
+                     const uint32_t *db_start_in, uint32_t base_search_length, int open, int ext,
+                     GhostmHitPath *rec, std::vector<uint32_t> *ops);
 
   DeviceTimes &times() {
     SettleSeedTime();

@@ -270,6 +270,9 @@ struct DeviceModule::Impl {
   // K3 work (tb_sort: two histograms + total, two cursor arrays)
   DevBuf tb_qid, tb_end, tb_start, tb_ml;
   DevBuf tb_ext;  // k_traceback_ext's inputs, outputs and cell counter (TraceBackExt)
+  // TraceBackPath: the hits' inputs, a batch's offsets / maxima / records / cell
+  // counter, its direction strips, its run-length slots and their packed words
+  DevBuf tb_path_in, tb_path_meta, tb_path_dir, tb_path_ops, tb_path_cmp;
   DevBuf tb_width, tb_ncols, tb_skey, tb_key, tb_order1, tb_order2, tb_sort, tb_pair_a, tb_pair_b, tb_best;
   int cus = 256;
   // K4 work
@@ -2145,12 +2148,193 @@ void DeviceModule::TraceBackExt(DevQuery *q, DevDb *d, uint32_t n, const uint32_
   }
 }
 
+static size_t EnvSize(const char *name, size_t def) {
+  const char *e = getenv(name);
+  if (!e || !*e) return def;
+  const unsigned long long v = strtoull(e, nullptr, 10);
+  return v ? (size_t)v : def;
+}
+
+void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const uint32_t *db_end,
+                                 const uint32_t *db_start_in, uint32_t base, int open, int ext, GhostmHitPath *rec,
+                                 std::vector<uint32_t> *ops) {
+  Use();
+  Impl &I = *impl_;
+  if (ops) ops->clear();
+  if (n == 0) return;
+  // a run-length word holds a length below 2^28; the limits are the extended traceback's
+  if (q->L == 0 || q->L > 127) throw Error("path traceback: query length outside 1..127");
+  if ((uint64_t)q->L + base >= 32768) throw Error("path traceback: window too wide for the run-length words");
+  if (base == 0) throw Error("path traceback: empty window");
+  for (uint32_t k = 0; k < n; ++k) {
+    if (qid[k] >= q->nseq || db_end[k] >= d->len) throw Error("path traceback: hit outside the resident chunk");
+    if (db_start_in && db_start_in[k] > db_end[k]) throw Error("path traceback: start after end");
+  }
+  const uint32_t L = q->L;
+  // every hit's column count (the window clipped at DB position 0, cut to the
+  // known start's) and the stable counting sort by it: hits of about equal
+  // column counts share a wave
+  std::vector<uint32_t> ncols(n), order(n);
+  {
+    std::vector<uint32_t> first((size_t)base + 2, 0);
+    for (uint32_t k = 0; k < n; ++k) {
+      uint32_t w = db_end[k] < base ? db_end[k] + 1 : base;
+      if (db_start_in) w = std::min(w, db_end[k] - db_start_in[k] + 1);
+      ncols[k] = w;
+      ++first[w + 1];
+    }
+    for (size_t c = 1; c < first.size(); ++c) first[c] += first[c - 1];
+    for (uint32_t k = 0; k < n; ++k) order[first[ncols[k]]++] = k;
+  }
+  I.tb_path_in.Reserve((size_t)n * 16);
+  uint32_t *w = I.tb_path_in.as<uint32_t>();
+  uint32_t *d_qid = w, *d_end = w + n, *d_ncols = w + 2 * (size_t)n, *d_order = w + 3 * (size_t)n;
+  HIP_CHECK(hipMemcpyAsync(d_qid, qid, (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
+  HIP_CHECK(hipMemcpyAsync(d_end, db_end, (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
+  HIP_CHECK(hipMemcpyAsync(d_ncols, ncols.data(), (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
+  HIP_CHECK(hipMemcpyAsync(d_order, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
+
+  const Layout lay = ChooseLayout(L, base);
+  const size_t colw = (size_t)lay.G * (size_t)(lay.S / 8);  // direction dwords per hit-column
+  const size_t budget = EnvSize("GHOSTM_PATH_SCRATCH_MB", 1024) << 20;
+  const size_t max_hits = EnvSize("GHOSTM_PATH_BATCH_HITS", SIZE_MAX);
+  // the batches' packed words (slot order) and where each hit's lie: batch, first word
+  std::vector<std::vector<uint32_t>> batch_words;
+  std::vector<uint32_t> hit_batch(ops ? n : 0);
+  std::vector<uint64_t> hit_at(ops ? n : 0);
+  std::vector<uint32_t> hit_runs(n);
+  std::vector<unsigned long long> off;  // dir_off[m], then ops_off[m]; dir_off later the packed offsets
+  std::vector<uint32_t> h_rec;
+  for (uint32_t b0 = 0; b0 < n;) {
+    // slots [b0, b1) of the sorted order: at least one hit, then as many as fit
+    uint32_t b1 = b0;
+    size_t dir_words = 0, ops_words = 0;
+    while (b1 < n && b1 - b0 < max_hits) {
+      const size_t dw = (size_t)ncols[order[b1]] * colw;
+      if (b1 > b0 && (dir_words + dw) * 4 > budget) break;
+      dir_words += dw;
+      ops_words += (size_t)ncols[order[b1]] + L;
+      ++b1;
+    }
+    const uint32_t m = b1 - b0;
+    off.resize(2 * (size_t)m);
+    {
+      size_t da = 0, oa = 0;
+      for (uint32_t s = 0; s < m; ++s) {
+        off[s] = da;
+        off[m + s] = oa;
+        da += (size_t)ncols[order[b0 + s]] * colw;
+        oa += (size_t)ncols[order[b0 + s]] + L;
+      }
+    }
+    // meta: dir_off[m], ops_off[m] (u64), the cell counter (u64), best[3m], rec[6m]
+    I.tb_path_meta.Reserve((size_t)m * 16 + 8 + (size_t)m * 36);
+    I.tb_path_dir.Reserve(dir_words * 4);
+    I.tb_path_ops.Reserve(ops_words * 4);
+    unsigned long long *d_off = I.tb_path_meta.as<unsigned long long>();
+    unsigned long long *cells_d = d_off + 2 * (size_t)m;
+    uint32_t *d_best = reinterpret_cast<uint32_t *>(cells_d + 1);
+    uint32_t *d_rec = d_best + 3 * (size_t)m;
+    HIP_CHECK(hipMemcpyAsync(d_off, off.data(), (size_t)m * 16, hipMemcpyHostToDevice, S(stream_)));
+    HIP_CHECK(hipMemsetAsync(cells_d, 0, 8, S(stream_)));
+    kern::TbPathArgs a{};
+    a.qseq = q->seq.as<uint8_t>();
+    a.L = L;
+    a.Lpad = lay.Lpad;
+    a.G = lay.G;
+    a.gpw = lay.gpw;
+    a.db = d->Residues();
+    a.mat_tb = I.mat_tb.as<int>();
+    a.qid = d_qid;
+    a.end = d_end;
+    a.ncols = d_ncols;
+    a.order = d_order + b0;
+    a.n = m;
+    a.open = open;
+    a.ext = ext;
+    a.dir_off = d_off;
+    a.dir = I.tb_path_dir.as<uint32_t>();
+    a.best = d_best;
+    a.cells = cells_d;
+    a.ops_off = d_off + m;
+    a.ops = I.tb_path_ops.as<uint32_t>();
+    a.rec = d_rec;
+    const uint32_t per_block = lay.gpw * (kern::kTbBlock / 64);
+    const dim3 grid((m + per_block - 1) / per_block), block(kern::kTbBlock);
+    const dim3 lane_grid((m + kern::kTbBlock - 1) / kern::kTbBlock);  // one lane per slot
+    HIP_CHECK(hipEventRecord(I.ev0, S(stream_)));
+    if (lay.S == 8) hipLaunchKernelGGL(kern::k_tb_path_fill<8>, grid, block, 0, S(stream_), a);
+    else if (lay.S == 16) hipLaunchKernelGGL(kern::k_tb_path_fill<16>, grid, block, 0, S(stream_), a);
+    else hipLaunchKernelGGL(kern::k_tb_path_fill<32>, grid, block, 0, S(stream_), a);
+    HIP_CHECK(hipGetLastError());
+    const uint32_t log2w = lay.S == 8 ? 0u : lay.S == 16 ? 1u : 2u;
+    hipLaunchKernelGGL(kern::k_tb_path_walk, lane_grid, block, 0, S(stream_), a, log2w);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(I.ev1, S(stream_)));
+    h_rec.resize((size_t)m * 6);
+    unsigned long long cells = 0;
+    HIP_CHECK(hipMemcpyAsync(h_rec.data(), d_rec, (size_t)m * 24, hipMemcpyDeviceToHost, S(stream_)));
+    HIP_CHECK(hipMemcpyAsync(&cells, cells_d, 8, hipMemcpyDeviceToHost, S(stream_)));
+    HIP_CHECK(hipStreamSynchronize(S(stream_)));
+    times_.traceback_path += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+    times_.traceback_path_launches += 1;
+    times_.traceback_path_cells += cells;
+    times_.traceback_path_dir_bytes += dir_words * 4;
+    // the scan of the compaction: every slot's first word in the packed array
+    size_t packed = 0;
+    for (uint32_t s = 0; s < m; ++s) {
+      const uint32_t hit = order[b0 + s];
+      const uint32_t *r = h_rec.data() + (size_t)s * 6;
+      if (r[5] > ncols[hit] + L) throw Error("path traceback: a hit's runs exceed its slot");
+      if (rec) rec[hit] = GhostmHitPath{r[0], r[1], r[2], r[3], r[4], r[5], 0};
+      hit_runs[hit] = r[5];
+      off[s] = packed;
+      if (ops) {
+        hit_batch[hit] = (uint32_t)batch_words.size();
+        hit_at[hit] = packed;
+      }
+      packed += r[5];
+    }
+    if (ops) {
+      batch_words.emplace_back(packed);
+      if (packed) {
+        I.tb_path_cmp.Reserve(packed * 4);
+        HIP_CHECK(hipMemcpyAsync(d_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
+        a.cmp_off = d_off;
+        a.cmp = I.tb_path_cmp.as<uint32_t>();
+        HIP_CHECK(hipEventRecord(I.ev0, S(stream_)));
+        hipLaunchKernelGGL(kern::k_tb_path_compact, lane_grid, block, 0, S(stream_), a);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipEventRecord(I.ev1, S(stream_)));
+        HIP_CHECK(hipMemcpyAsync(batch_words.back().data(), a.cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
+        HIP_CHECK(hipStreamSynchronize(S(stream_)));
+        times_.traceback_path += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+      }
+    }
+    b0 = b1;
+  }
+  // the batches' words joined in hit order
+  uint64_t total = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    if (rec) rec[k].ops_offset = total;
+    total += hit_runs[k];
+  }
+  if (ops) {
+    ops->resize(total);
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+      if (hit_runs[k]) memcpy(ops->data() + at, batch_words[hit_batch[k]].data() + hit_at[k], (size_t)hit_runs[k] * 4);
+      at += hit_runs[k];
+    }
+  }
+}
+
 const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_amd/srchash.py)
 
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -2458,6 +2642,33 @@ int TraceBackExtGpu(uint32_t nhits, const uint32_t query_ids[], const uint32_t d
     if (!query_ids || !db_ends) throw Error("TraceBackExtGpu: null hit arrays");
     DeviceModule::Get().TraceBackExt(r.query, r.db, nhits, query_ids, db_ends, db_starts_in, base_search_length,
                                      open_gap, extend_gap, db_starts, aln_lens, aln_matches, ext);
+    return 0;
+  } catch (std::exception &e) {
+    SetError(e.what());
+    return 1;
+  }
+}
+
+int TraceBackPathGpu(uint32_t nhits, const uint32_t query_ids[], const uint32_t db_ends[],
+                     const uint32_t db_starts_in[], uint32_t query_sequence_length,
+                     uint32_t base_search_length, int open_gap, int extend_gap, GhostmHitPath rec[],
+                     uint32_t ops[], size_t ops_cap, size_t *ops_used) {
+  try {
+    if (ops_used) *ops_used = 0;
+    if (nhits == 0) return 0;
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    if (!r.query || !r.db) throw Error("SetQueryGpu/SetDbGpu not called");
+    if (query_sequence_length != r.query->L) throw Error("query shape differs from SetQueryGpu");
+    if (!query_ids || !db_ends) throw Error("TraceBackPathGpu: null hit arrays");
+    std::vector<uint32_t> words;
+    DeviceModule::Get().TraceBackPath(r.query, r.db, nhits, query_ids, db_ends, db_starts_in, base_search_length,
+                                      open_gap, extend_gap, rec, &words);
+    if (ops_used) *ops_used = words.size();
+    if (ops) {
+      if (words.size() > ops_cap) throw Error("TraceBackPathGpu: the operations do not fit ops_cap");
+      std::copy(words.begin(), words.end(), ops);
+    }
     return 0;
   } catch (std::exception &e) {
     SetError(e.what());

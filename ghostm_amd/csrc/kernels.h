@@ -3032,6 +3032,241 @@ __device__ inline uint32_t Bfi(uint32_t m, uint32_t x, uint32_t y) {
 
 __device__ inline int ShiftUpI(int v) { return __builtin_amdgcn_update_dpp(0, v, 0x138, 0xF, 0xF, false); }
 
+// ------------------------------------------------------------------ alignment paths
+// k_tb_path_fill + k_tb_path_walk: the alignment path of every hit
+// (GhostmHitPath). The fill runs k_traceback_ext's DP (same lane groups, window,
+// END break and first strict maximum) on plain int32 H and E, two state words
+// per row, and records four bits per cell:
+//   bits 0-1 hsel: the term H took (0 zero, 1 diagonal, 2 E, 3 F; the
+//            reference's strict order), bit 2 eext: E extended, E(j-1,k) + ext >
+//            H(j-1,k) + open (a tie opens), bit 3 fext: the same for F.
+// Per column a lane packs its S cells into S / 8 dwords (processing row U of
+// the hit at bit 4 * (U & 7) of dword U >> 3) and writes them with one
+// non-temporal store: the direction strip of batch slot s is ncols x G x S/8
+// dwords at dir + dir_off[s], column-major. The walk (a separate launch, so
+// the strips are visible) follows them with one lane per hit from the first
+// strict maximum, in H state, towards column 0 and row L - 1:
+//   H: hsel 1 emits '=' or 'X' and goes to H(j-1, k+1); 2 / 3 enter E / F at
+//      the same cell; 0, a column < 0 or a row >= L stop.
+//   E: emits 'D', goes to E(j-1, k) if eext else H(j-1, k).
+//   F: emits 'I', goes to F(j, k+1) if fext else H(j, k+1).
+// It writes run-length words len << 4 | op into the slot's ncols + L words at
+// ops + ops_off[s] and six record words (q_start, q_end, s_start, s_end, score,
+// n_runs). k_tb_path_compact then copies every slot's n_runs words to its
+// place in one packed array (the offsets are the host's prefix sum over the
+// records it read back), so only the words used travel to the host. Padding rows (query position >= L) hold kPadCode: their H stays 0
+// and their E and F stay negative, so row L - 1 sees the same H and the same
+// positive F as with the host model's F = 0 start.
+struct TbPathArgs {
+  const uint8_t *qseq;
+  uint32_t L, Lpad, G, gpw;
+  const uint8_t *db;
+  const int *mat_tb;          // (score << 16) | ..., column 31 = kNeg << 16
+  const uint32_t *qid, *end;  // per hit
+  const uint32_t *ncols;      // per hit: columns of its DP (at most the window and end + 1)
+  const uint32_t *order;      // the batch's slots: hit index of slot s
+  uint32_t n;                 // slots of the batch
+  int open, ext;
+  const unsigned long long *dir_off;  // per slot: first dword of its direction strip
+  uint32_t *dir;
+  uint32_t *best;                     // per slot: j*, k*, score
+  unsigned long long *cells;          // += L x processed columns
+  const unsigned long long *ops_off;  // per slot: first of its ncols + L run-length words
+  uint32_t *ops;
+  uint32_t *rec;                      // per slot: q_start, q_end, s_start, s_end, score, n_runs
+  // compaction (k_tb_path_compact): the slots' words packed in slot order
+  const unsigned long long *cmp_off;  // per slot: its first word in cmp (the host's prefix sum of n_runs)
+  uint32_t *cmp;
+};
+constexpr uint32_t kPathEExt = 4u, kPathFExt = 8u;
+
+template <int W> __device__ inline void PathStoreDir(uint32_t *p, const uint32_t (&v)[W]) {
+  if constexpr (W == 1) {
+    __builtin_nontemporal_store(v[0], p);
+  } else if constexpr (W == 2) {
+    typedef uint32_t V2 __attribute__((ext_vector_type(2)));
+    V2 x = {v[0], v[1]};
+    __builtin_nontemporal_store(x, reinterpret_cast<V2 *>(p));
+  } else {
+    static_assert(W == 4, "S is 8, 16 or 32");
+    typedef uint32_t V4 __attribute__((ext_vector_type(4)));
+    V4 x = {v[0], v[1], v[2], v[3]};
+    __builtin_nontemporal_store(x, reinterpret_cast<V4 *>(p));
+  }
+}
+
+template <int S>
+__global__ __launch_bounds__(kTbBlock) void k_tb_path_fill(TbPathArgs a) {
+  GHOSTM_POISON_LDS();
+  constexpr int W = S / 8;
+  __shared__ int s_mat[32 * 32];
+  for (uint32_t e = threadIdx.x; e < 32 * 32; e += kTbBlock) s_mat[e] = a.mat_tb[e];
+  __syncthreads();
+
+  const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint32_t g = lane / a.G, i = lane - g * a.G;
+  const uint32_t slot = (blockIdx.x * (kTbBlock / 64) + wave) * a.gpw + g;
+  const bool valid = g < a.gpw && slot < a.n;
+  uint32_t p0 = 0, width = 0;
+  // processing row U = i*S + u is query position krow0 - u (padding rows at L and above)
+  const int krow0 = (int)a.Lpad - 1 - (int)(i * S);
+  uint32_t qcode[S / 4];
+#pragma unroll
+  for (int w = 0; w < S / 4; ++w) qcode[w] = 0x1F1F1F1Fu;
+  uint32_t *dp = nullptr;
+  if (valid) {
+    const uint32_t hit = a.order[slot];
+    p0 = a.end[hit];
+    width = min(a.ncols[hit], p0 + 1);
+    const uint8_t *qs = a.qseq + (size_t)a.qid[hit] * a.L;
+#pragma unroll
+    for (int u = 0; u < S; ++u) {
+      const int k = krow0 - u;
+      const uint32_t code = (k >= 0 && k < (int)a.L) ? qs[k] : kPadCode;
+      qcode[u >> 2] = (qcode[u >> 2] & ~(0xFFu << (8 * (u & 3)))) | (code << (8 * (u & 3)));
+    }
+    dp = a.dir + a.dir_off[slot] + (size_t)i * W;
+  }
+  const size_t colw = (size_t)a.G * W;
+  int H[S], E[S];
+#pragma unroll
+  for (int u = 0; u < S; ++u) { H[u] = 0; E[u] = 0; }
+  int best = 0, best_col = 0, best_row = 0;
+  int hout = 0, fout = 0, hprev = 0;
+  bool done = false;
+  uint32_t ncols = 0;
+  const int open = a.open, ext = a.ext;
+  int j = -(int)i;
+  const uint32_t wmax = WaveMax(valid ? width : 0u);
+  const uint32_t steps = wmax ? wmax + a.G - 1 : 0u;
+  for (uint32_t step = 0; step < steps; ++step, ++j) {
+    int hin = ShiftUpI(hout), fin = ShiftUpI(fout);
+    if (i == 0) { hin = 0; fin = 0; }
+    const int diag0 = hprev;
+    hprev = hin;
+    bool active = valid && !done && j >= 0 && (uint32_t)j < width;
+    uint32_t c = 0;
+    if (active) {
+      c = a.db[p0 - j];
+      if (c == kSeqEnd) { done = true; active = false; }
+    }
+    if (active) {
+      const int *row = s_mat + c * 32;
+      int diag = diag0, F = fin, hup = hin;
+      uint32_t pk[W];
+#pragma unroll
+      for (int w = 0; w < W; ++w) pk[w] = 0;
+#pragma unroll
+      for (int u = 0; u < S; ++u) {
+        const int P = row[(qcode[u >> 2] >> (8 * (u & 3))) & 0xFFu];
+        const int s = diag + (P >> 16);
+        int h = 0;
+        uint32_t bits = 0;
+        if (s > 0) { h = s; bits = 1; }
+        const int ee = E[u] + ext, eo = H[u] + open;
+        const int e = max(ee, eo);
+        E[u] = e;
+        if (e > h) { h = e; bits = 2; }
+        const int fe = F + ext, fo = hup + open;
+        F = max(fe, fo);
+        if (F > h) { h = F; bits = 3; }
+        bits |= (ee > eo ? kPathEExt : 0u) | (fe > fo ? kPathFExt : 0u);
+        pk[u >> 3] |= bits << (4 * (u & 7));
+        diag = H[u];
+        H[u] = h;
+        hup = h;
+        if (h > best) { best = h; best_col = j; best_row = krow0 - u; }
+      }
+      PathStoreDir<W>(dp + (size_t)j * colw, pk);
+      hout = H[S - 1];
+      fout = F;
+      ++ncols;
+    } else {
+      hout = 0; fout = 0;
+    }
+  }
+  // first cell (column-major, rows in processing order) reaching the maximum
+  int B = best, C = best_col, R = best_row;
+  for (uint32_t k = 1; k < a.G; ++k) {
+    const int src = (int)(g * a.G + k);
+    const int ob = __shfl(best, src), oc = __shfl(best_col, src), orow = __shfl(best_row, src);
+    if (ob > B || (ob == B && ob > 0 && oc < C)) { B = ob; C = oc; R = orow; }
+  }
+  if (valid && i == 0) {
+    a.best[3 * (size_t)slot] = (uint32_t)C;
+    a.best[3 * (size_t)slot + 1] = (uint32_t)R;
+    a.best[3 * (size_t)slot + 2] = (uint32_t)B;
+  }
+  WaveAddCells(a.cells, (valid && i == 0) ? (unsigned long long)ncols * a.L : 0ull);
+}
+
+// log2w: log2 of the fill's S / 8
+__global__ __launch_bounds__(kTbBlock) void k_tb_path_walk(TbPathArgs a, uint32_t log2w) {
+  GHOSTM_POISON_LDS();
+  const uint32_t slot = blockIdx.x * kTbBlock + threadIdx.x;
+  if (slot >= a.n) return;
+  const uint32_t hit = a.order[slot];
+  const uint32_t p0 = a.end[hit];
+  const uint32_t width = min(a.ncols[hit], p0 + 1);
+  const uint8_t *qs = a.qseq + (size_t)a.qid[hit] * a.L;
+  const uint32_t *dir = a.dir + a.dir_off[slot];
+  const size_t colw = (size_t)a.G << log2w;
+  uint32_t *out = a.ops + a.ops_off[slot];
+  const uint32_t cap = width + a.L;
+  const uint32_t bj = a.best[3 * (size_t)slot], bk = a.best[3 * (size_t)slot + 1], score = a.best[3 * (size_t)slot + 2];
+  int j = (int)bj, k = (int)bk;
+  uint32_t nruns = 0, cur = 0, len = 0;
+  if (score > 0 && bj < width) {
+    int state = 0;
+    // every operation consumes a query or a subject residue: at most cap of them
+    for (uint32_t it = 0; it < 2 * cap + 2 && j >= 0 && k < (int)a.L; ++it) {
+      const uint32_t U = a.Lpad - 1 - (uint32_t)k;
+      const uint32_t b = (dir[(size_t)j * colw + (U >> 3)] >> (4 * (U & 7))) & 0xFu;
+      uint32_t op;
+      if (state == 0) {
+        const uint32_t sel = b & 3u;
+        if (sel == 0) break;
+        if (sel != 1) { state = sel == 2 ? 1 : 2; continue; }
+        op = a.db[p0 - (uint32_t)j] == qs[k] ? 0u : 1u;
+        --j;
+        ++k;
+      } else if (state == 1) {
+        op = 3u;
+        state = (b & kPathEExt) ? 1 : 0;
+        --j;
+      } else {
+        op = 2u;
+        state = (b & kPathFExt) ? 2 : 0;
+        ++k;
+      }
+      if (len && op != cur) {
+        if (nruns < cap) out[nruns++] = len << 4 | cur;
+        len = 0;
+      }
+      cur = op;
+      ++len;
+    }
+    if (len && nruns < cap) out[nruns++] = len << 4 | cur;
+  }
+  uint32_t *r = a.rec + 6 * (size_t)slot;
+  r[0] = bk;
+  r[1] = score > 0 ? (uint32_t)(k - 1) : bk;
+  r[2] = p0 - bj;
+  r[3] = score > 0 ? p0 - (uint32_t)(j + 1) : p0 - bj;
+  r[4] = score;
+  r[5] = nruns;
+}
+
+__global__ __launch_bounds__(kTbBlock) void k_tb_path_compact(TbPathArgs a) {
+  GHOSTM_POISON_LDS();
+  const uint32_t slot = blockIdx.x * kTbBlock + threadIdx.x;
+  if (slot >= a.n) return;
+  const uint32_t n = a.rec[6 * (size_t)slot + 5];
+  const uint32_t *src = a.ops + a.ops_off[slot];
+  uint32_t *dst = a.cmp + a.cmp_off[slot];
+  for (uint32_t k = 0; k < n; ++k) dst[k] = src[k];
+}
+
 // FRAME (FINAL only, round 6): every key of column j is stored with FR_j =
 // j * (-ext) added to its h field, as K2's column frame, so E's extension needs
 // no add: E'(j) = max3(A', Bfi(HIGH, E'(j-1), A'), zero'(j)) with A' = K'(j-1) +

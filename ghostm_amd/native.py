@@ -51,6 +51,21 @@ class GhostmHitExt(ctypes.Structure):
     ]
 
 
+class GhostmHitPath(ctypes.Structure):
+    """the alignment path of one hit (32 bytes): zero-based inclusive coordinates,
+    its score and its run-length words ops[ops_offset : ops_offset + n_runs]."""
+
+    _fields_ = [
+        ("q_start", c_uint32),
+        ("q_end", c_uint32),
+        ("s_start", c_uint32),
+        ("s_end", c_uint32),
+        ("score", c_uint32),
+        ("n_runs", c_uint32),
+        ("ops_offset", c_uint64),
+    ]
+
+
 class GhostmStats(ctypes.Structure):
     _fields_ = [
         ("seconds_total", ctypes.c_double),
@@ -100,6 +115,10 @@ class GhostmStats(ctypes.Structure):
         ("seconds_traceback_ext", ctypes.c_double),
         ("traceback_ext_launches", c_uint64),
         ("traceback_ext_cells", c_uint64),
+        ("seconds_traceback_path", ctypes.c_double),
+        ("traceback_path_launches", c_uint64),
+        ("traceback_path_cells", c_uint64),
+        ("traceback_path_dir_bytes", c_uint64),
     ]
 
     def as_dict(self) -> dict:
@@ -137,6 +156,11 @@ SIGNATURES = {
     "GhostmTraceBackExtHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, POINTER(ctypes.c_uint8), c_uint32,
                                        POINTER(c_int), c_uint32, u32p, u32p, c_uint32, c_int, c_int, u32p, u32p, u32p,
                                        POINTER(GhostmHitExt)]),
+    "TraceBackPathGpu": (c_int, [c_uint32, u32p, u32p, u32p, c_uint32, c_uint32, c_int, c_int, POINTER(GhostmHitPath),
+                                 u32p, c_size_t, POINTER(c_size_t)]),
+    "GhostmTraceBackPathHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, POINTER(ctypes.c_uint8), c_uint32,
+                                        POINTER(c_int), c_uint32, u32p, u32p, u32p, c_uint32, c_int, c_int,
+                                        POINTER(GhostmHitPath), u32p, c_size_t, POINTER(c_size_t)]),
     "GhostmBuildIndexGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, u32p, u32p, u32p, c_int,
                                     POINTER(c_float)]),
     "GhostmFormatQueriesGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_uint32,
@@ -156,6 +180,8 @@ SIGNATURES = {
     "GhostmSessionWrite": (c_int, [c_void_p]),
     "GhostmSessionHits": (c_size_t, [c_void_p, POINTER(GhostmHit), c_size_t]),
     "GhostmSessionHitsExt": (c_size_t, [c_void_p, POINTER(GhostmHitExt), c_size_t]),
+    "GhostmSessionHitsPath": (c_size_t, [c_void_p, POINTER(GhostmHitPath), c_size_t]),
+    "GhostmSessionPathOps": (c_size_t, [c_void_p, u32p, c_size_t]),
     "GhostmSessionDeviceHits": (c_size_t, [c_void_p, c_void_p, c_size_t]),
     "GhostmSessionStats": (c_int, [c_void_p, POINTER(GhostmStats)]),
     "GhostmSessionStatsSized": (c_size_t, [c_void_p, POINTER(GhostmStats), c_size_t]),

@@ -152,6 +152,49 @@ int GhostmTraceBackExtHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, c
                            uint32_t db_starts[], uint32_t aln_lens[], uint32_t aln_matches[],
                            GhostmHitExt ext[]);
 
+/* The alignment path of one hit: which query residue lies against which
+ * subject residue. Coordinates are zero-based and inclusive; the path's
+ * operations are the n_runs run-length words at ops[ops_offset]: length << 4 |
+ * op, op 0 '=' (equal codes), 1 'X' (different codes), 2 'I' (a query residue
+ * against a gap), 3 'D' (a subject residue against a gap), in reading order of
+ * both sequences. s_end is the path's last subject residue; it may lie before
+ * the hit's db_end, which is where the forward search stopped. A hit of score
+ * 0 has an empty path (n_runs 0, the end coordinates equal the start's). */
+typedef struct GhostmHitPath {
+  uint32_t q_start, q_end;   /* first and last query row of the path */
+  uint32_t s_start, s_end;   /* first and last subject position of the path */
+  uint32_t score;            /* H of the first maximal cell */
+  uint32_t n_runs;
+  uint64_t ops_offset;       /* index of the hit's first word in ops[] */
+} GhostmHitPath;
+
+/* The path of every hit (kernels k_tb_path_fill + k_tb_path_walk), stage level
+ * like TraceBackExtGpu (after SetQueryGpu and SetDbGpu; subject coordinates
+ * absolute in the chunk). The DP is TraceBackExtGpu's; every cell records the
+ * term its H took (0, diagonal, E, F, each comparison strict in that order)
+ * and whether its E and F extended or opened (a tie opens), and the path is
+ * walked from the first strict maximum, in H state, towards column 0 and row
+ * L - 1. Record i belongs to hit i; the hits' words follow each other in hit
+ * order. ops == NULL: only *ops_used (the words needed) and rec (may be NULL)
+ * are written. Fails when ops_cap is too small, when query_sequence_length >
+ * 127 or query_sequence_length + base_search_length >= 32768. The direction
+ * buffer (4 bits per cell) is cut into batches of hits that fit
+ * GHOSTM_PATH_SCRATCH_MB (default 1024) and hold at most GHOSTM_PATH_BATCH_HITS
+ * hits (default: no limit). */
+int TraceBackPathGpu(uint32_t nhits, const uint32_t query_ids[], const uint32_t db_ends[],
+                     const uint32_t db_starts_in[], uint32_t query_sequence_length,
+                     uint32_t base_search_length, int open_gap, int extend_gap, GhostmHitPath rec[],
+                     uint32_t ops[], size_t ops_cap, size_t *ops_used);
+
+/* The same on the host, with no device call (the model the kernels are checked
+ * against); arguments as GhostmTraceBackExtHost, db_starts_in may be NULL. */
+int GhostmTraceBackPathHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, const uint8_t *db,
+                            uint32_t db_len, const int score_matrix[], uint32_t nhits,
+                            const uint32_t query_ids[], const uint32_t db_ends[],
+                            const uint32_t db_starts_in[], uint32_t base_search_length, int open_gap,
+                            int extend_gap, GhostmHitPath rec[], uint32_t ops[], size_t ops_cap,
+                            size_t *ops_used);
+
 /* The `db` formatter's k-mer index of one DB chunk, built on the GPU
  * (replaces DBCreator::ConstructIndex, db_creator.cpp:167-241).
  * seq[len] = the chunk's END-separated residues (.seq); seed = the index seed mask
@@ -266,6 +309,11 @@ typedef struct GhostmStats {
                                        -y 6 or GhostmSessionHitsExt asks for it */
   uint64_t traceback_ext_launches;
   uint64_t traceback_ext_cells;     /* sum over its DPs of L x processed columns */
+  double seconds_traceback_path;    /* the alignment-path post-pass (k_tb_path_fill + k_tb_path_walk, device
+                                       time); 0 until -y 7 or GhostmSessionHitsPath asks for it */
+  uint64_t traceback_path_launches; /* batches of hits (one fill and one walk launch each) */
+  uint64_t traceback_path_cells;    /* sum over its DPs of L x processed columns */
+  uint64_t traceback_path_dir_bytes; /* direction-buffer bytes its batches addressed */
 } GhostmStats;
 
 /* Session: parse `aln` options exactly like the reference (getopt string
@@ -343,7 +391,11 @@ int GhostmSessionRun(void *session);
  * -y 6 (BLAST-tabular: qseqid sseqid pident length mismatch gapopen qstart qend
  * sstart send evalue bitscore, one-based coordinates, pident/evalue/bitscore as
  * -y 0 prints them) the text exists only after the GhostmHitExt post-pass, so
- * the file is written at the end of the run. */
+ * the file is written at the end of the run. -y 7 is -y 6 with columns 3 to 10
+ * (pident = 100 * matches / length, length, mismatch, gapopen = the I and D
+ * runs, qstart, qend, sstart, send) taken from the hit's GhostmHitPath and a
+ * thirteenth column, the extended CIGAR (for instance 31=1X2D40=); it too is
+ * written at the end of the run. */
 int GhostmSessionRunToFile(void *session);
 
 /* Formatted output of the last run (reference WriteOutput/V1/V2 text). With
@@ -364,6 +416,17 @@ size_t GhostmSessionHits(void *session, GhostmHit *hits, size_t cap);
  * traced with the group's first query that reproduces its db_start, aln_len
  * and aln_match. */
 size_t GhostmSessionHitsExt(void *session, GhostmHitExt *ext, size_t cap);
+
+/* The GhostmHitPath of every hit of the last run (record i belongs to hit i)
+ * and the run-length words they index; both with the NULL/cap convention of
+ * GhostmSessionHitsExt, (size_t)-1 on error. s_start and s_end are relative to
+ * the subject, like GhostmHit.db_start. Works after a run with any -y: one
+ * TraceBackPathGpu-style call per (query chunk, DB chunk) that has hits, with
+ * the known starts, computed on first use and kept until the next run. A hit
+ * of a name group of several queries is traced with the query
+ * GhostmSessionHitsExt resolved. */
+size_t GhostmSessionHitsPath(void *session, GhostmHitPath *rec, size_t cap);
+size_t GhostmSessionPathOps(void *session, uint32_t *ops, size_t cap);
 
 /* The same records resident on the session's GPU, for a device-to-device
  * gather across ranks: copies min(n, cap) records to dst_device
