@@ -4,7 +4,7 @@ Seed lookup, Gotoh score DP and traceback are hand-written HIP kernels in
 csrc/; the merge/E-value host logic and the C ABI live in libghostm_hip.so.
 """
 from .aligner import (Aligner, GhostmError, HIT_DTYPE, HIT_EXT_DTYPE, HIT_PATH_DTYPE, Session, cigar, format_db,
-                      format_queries, run_cli, synth, traceback_ext_host, traceback_path_host)
+                      format_queries, query_chunk_cuts, run_cli, synth, traceback_ext_host, traceback_path_host)
 from .native import BIN_PATH, LIB_PATH, NativeLibraryMissing, load
 
 __all__ = [
@@ -19,6 +19,7 @@ __all__ = [
     "cigar",
     "format_db",
     "format_queries",
+    "query_chunk_cuts",
     "synth",
     "run_cli",
     "load",

@@ -8,6 +8,11 @@
                              E-value text), repeatable, with .output(), .hits(),
                              .stats().
 
+    Session.for_db(argv)     only the database resident; .set_queries(seqs, names)
+                             or .set_queries_fasta(path) replace the query set on
+                             the live session (coded and translated on the GPU),
+                             then .run() as above: many read sets, one database.
+
 Everything runs in libghostm_hip.so (HIP kernels for gfx950 + host merge); this
 module only marshals arguments.
 """
@@ -118,6 +123,20 @@ def traceback_path_host(query_seqs, L, db, score_matrix, query_ids, db_ends, bas
     return rec, ops
 
 
+def query_chunk_cuts(lengths, chunk_mb: int = 0, dna: bool = False) -> np.ndarray:
+    """`ghostm qry`'s chunk cuts over records of these letter counts
+    (GhostmQueryChunkCuts; no device): chunk c is records [cuts[c], cuts[c + 1]).
+    chunk_mb and dna as qry's -L (0: the default) and -t d."""
+    lib = native.load()
+    lens = np.ascontiguousarray(lengths, dtype=np.uint32)
+    cuts = np.zeros(len(lens) + 1, dtype=np.uint64)
+    n = lib.GhostmQueryChunkCuts(lens.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(lens), int(chunk_mb),
+                                 int(bool(dna)), cuts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(cuts))
+    if n < 0:
+        raise GhostmError(native.last_error())
+    return cuts[: n + 1]
+
+
 class Aligner:
     """reference class Aligner (aligner.h:63-92): Execute(argc, argv)."""
 
@@ -171,6 +190,87 @@ class Session:
                 raise errors[0]
         if not self._h:
             raise GhostmError(native.last_error())
+
+    @classmethod
+    def for_db(cls, argv: Sequence[str]) -> "Session":
+        """A database session (GhostmSessionCreateDb): `aln`'s options without -i,
+        -S and -L; the DB chunks are resident and the queries come from
+        set_queries / set_queries_fasta, any number of times."""
+        lib = native.load()
+        self = cls.__new__(cls)
+        args = ["aln"] + list(argv)
+        self._argv = native.argv_array(args)
+        self._h = lib.GhostmSessionCreateDb(len(args), self._argv)
+        if not self._h:
+            raise GhostmError(native.last_error())
+        return self
+
+    def set_queries(self, seqs: Sequence, names: Sequence, width: int = 75, dna: bool = False,
+                    chunk_mb: int = 0) -> None:
+        """Replaces the query set by these records (str or bytes letters and
+        names): what `ghostm qry -l width [-t d] -L chunk_mb` would format from
+        them, coded on the device (GhostmSessionSetQueries). The last run's
+        results are dropped."""
+        if len(seqs) != len(names):
+            raise ValueError("set_queries: one name per sequence")
+        as_bytes = lambda x: x.encode() if isinstance(x, str) else bytes(x)  # noqa: E731
+        bseqs = [as_bytes(x) for x in seqs]
+        bnames = [as_bytes(x) for x in names]
+        if any(b"\n" in x for x in bnames):
+            raise ValueError("set_queries: a name holds a newline")
+        n = len(bseqs)
+        lengths = np.array([len(x) for x in bseqs], dtype=np.uint32)
+        offsets = np.zeros(n, dtype=np.uint64)
+        if n > 1:
+            offsets[1:] = np.cumsum(lengths[:-1], dtype=np.uint64)
+        raw = np.frombuffer(b"".join(bseqs) or b"\0", dtype=np.uint8)
+        raw_len = int(lengths.sum(dtype=np.uint64))
+        name_buf = b"".join(x + b"\n" for x in bnames)
+        rc = native.load().GhostmSessionSetQueries(
+            self._h, raw.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), raw_len,
+            offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), name_buf, len(name_buf), n, int(width),
+            int(bool(dna)), int(chunk_mb))
+        if rc != 0:
+            raise GhostmError(native.last_error())
+
+    def set_queries_fasta(self, path: str, width: int = 75, dna: bool = False, chunk_mb: int = 0) -> int:
+        """set_queries from a FASTA file, read as `ghostm qry` reads it
+        (GhostmSessionSetQueriesFasta). Returns the number of output records
+        over the width (qry's warnings)."""
+        cut = ctypes.c_uint64(0)
+        rc = native.load().GhostmSessionSetQueriesFasta(self._h, str(path).encode(), int(width), int(bool(dna)),
+                                                        int(chunk_mb), ctypes.byref(cut))
+        if rc != 0:
+            raise GhostmError(native.last_error())
+        return int(cut.value)
+
+    def set_output(self, path: str) -> None:
+        """The -o path of later run(to_file=True) and write() calls."""
+        if native.load().GhostmSessionSetOutputFile(self._h, str(path).encode()) != 0:
+            raise GhostmError(native.last_error())
+
+    def query_lengths(self) -> np.ndarray:
+        """The length `aln` prints for every query record (last non-X code + 1, at
+        least 1), over the chunks in order."""
+        lib = native.load()
+        n = lib.GhostmSessionQueryLengths(self._h, None, 0)
+        out = np.zeros(n, dtype=np.uint32)
+        if n:
+            lib.GhostmSessionQueryLengths(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n)
+        return out
+
+    def query_records(self, chunk: int) -> np.ndarray:
+        """The coded records of one query chunk (the bytes of its .seq file),
+        copied back from the device."""
+        lib = native.load()
+        n = lib.GhostmSessionQueryRecords(self._h, int(chunk), None, 0)
+        if n == ctypes.c_size_t(-1).value:
+            raise GhostmError(native.last_error())
+        out = np.zeros(n, dtype=np.uint8)
+        if n:
+            lib.GhostmSessionQueryRecords(self._h, int(chunk), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), n)
+        return out
 
     def shard_range(self) -> tuple[int, int]:
         b, e = ctypes.c_uint64(), ctypes.c_uint64()
@@ -302,7 +402,7 @@ class Session:
 
 
 def run_cli(args: Sequence[str], **kw) -> subprocess.CompletedProcess:
-    """Run the native `ghostm` binary (db | qry | aln | synth)."""
+    """Run the native `ghostm` binary (db | qry | aln | search | synth)."""
     return subprocess.run([native.BIN_PATH] + list(args), check=True, capture_output=True, **kw)
 
 

@@ -20,6 +20,7 @@
 #include <thread>
 
 #include "common.h"
+#include "query_set.h"
 #include "worker_pool.h"
 
 namespace ghostm {
@@ -551,6 +552,17 @@ Session::Session(const AlignerOptions &opt, uint32_t shard_rank, uint32_t shard_
     : opt_(opt) {
   threads_ = HostThreads();
   if (shard_world == 0 || shard_rank >= shard_world) throw std::invalid_argument("shard rank outside the world");
+  CreateOrFree(shard_rank, shard_world, ex);
+}
+
+Session::Session(const AlignerOptions &opt, DbOnly) : opt_(opt), db_only_(true) {
+  threads_ = HostThreads();
+  if (!opt.query_prefix.empty() || opt.start_query_chunk != UINT32_MAX || opt.end_query_chunk != UINT32_MAX)
+    throw std::invalid_argument("a database session takes no -i, -S or -L: its queries come from SetQueries");
+  CreateOrFree(0, 1, nullptr);
+}
+
+void Session::CreateOrFree(uint32_t shard_rank, uint32_t shard_world, const ShardExchange *ex) {
   try {
     Create(shard_rank, shard_world, ex);
   } catch (...) {
@@ -660,6 +672,7 @@ void Session::Load(uint32_t shard_rank, uint32_t shard_world, bool local, std::v
   // (aligner.cpp:98-204), and every DB chunk; the chunk files are read on
   // parallel threads, then the chunks up to the first missing one are kept
   QueryFile qf(opt_.query_prefix);
+  if (db_only_) qf.division = 0;  // a database session: no query files
   uint32_t id = opt_.start_query_chunk == UINT32_MAX ? 0 : opt_.start_query_chunk;
   uint32_t base = 0;
   for (uint32_t k = 0; k < id && k < qf.division; ++k) {
@@ -766,7 +779,7 @@ void Session::Load(uint32_t shard_rank, uint32_t shard_world, bool local, std::v
               });
   uint32_t nchunks = 0;
   while (nchunks < nq_chunks && qok[nchunks]) ++nchunks;
-  if (nchunks == 0) throw std::runtime_error("[Aligner] error: don't find query file.");
+  if (nchunks == 0 && !db_only_) throw std::runtime_error("[Aligner] error: don't find query file.");
   if (!local) {
     std::vector<QueryData *> chunks;
     for (uint32_t k = 0; k < nchunks; ++k) chunks.push_back(&qread[k]);
@@ -1918,6 +1931,7 @@ void Session::Run(bool stream_to_file) {
   } close_stream{this};
   dev.ResetTimes();
   stats_ = GhostmStats{};
+  QueryStats();
   merge_epoch_ = 0;
   used_parts_ = 0;
   joined_.clear();
@@ -2148,6 +2162,223 @@ void Session::WriteOutputFile() {
   close(fd);
   for (char f : failed)
     if (f) throw Error("writing " + opt_.output_file + " failed");
+}
+
+// ------------------------------------------------------------------ query sets
+// The session's queries replaced on the live session: what `ghostm qry` would
+// write for the same records (query_set.h: the chunk cuts, the width rule) is
+// made resident chunk by chunk by DeviceModule::FormatQuery, without .seq files
+// and without the records visiting the host. The DB chunks, the matrix and the
+// options stay as they are.
+void Session::DropQueries() {
+  if (shard_world_ > 1) throw Error("a shard session's query set cannot be replaced");
+  if (formatter_) formatter_->Drain();
+  if (writer_) writer_->Drain();
+  DeviceModule &dev = DeviceModule::Get();
+  dev.Synchronize();
+  // the last run's results
+  used_parts_ = 0;
+  joined_.clear();
+  joined_valid_ = false;
+  hits_.clear();
+  hits_valid_ = false;
+  hits_ext_.clear();
+  hits_ext_valid_ = false;
+  hit_source_.clear();
+  hits_path_.clear();
+  path_ops_.clear();
+  hits_path_valid_ = false;
+  dev.ResetRecords(0);
+  records_on_device_ = true;
+  streamed_ = false;
+  stream_failed_ = false;
+  stream_off_ = 0;
+  seed_counts_.clear();
+  seed_offsets_.clear();
+  stats_ = GhostmStats{};
+  // the old chunks' device blocks go back to the pool
+  for (QueryData &q : queries_) dev.Free(q.dev);
+  queries_.clear();
+  shard_begin_ = 0;
+  shard_end_ = UINT64_MAX;
+  format_seconds_ = 0;
+  format_launches_ = 0;
+  read_seconds_ = 0;
+  load_seconds_ = 0;
+  QueryStats();
+}
+
+void Session::AddQueryChunk(const QueryRecordView *recs, uint32_t n, uint32_t width, bool dna, uint64_t *cut_records,
+                            std::vector<std::string> *cut_names) {
+  DeviceModule &dev = DeviceModule::Get();
+  const double t0 = NowSeconds();
+  const uint32_t per = dna ? 6 : 1;
+  // every read is cut/padded to the chunk's first read length (query_creator.cpp:254)
+  const uint32_t dna_len = dna ? recs[0].len : 0;
+  // the letters a record can contribute, concatenated
+  const uint32_t most = dna ? dna_len : width;
+  std::vector<uint64_t> off(n);
+  std::vector<uint32_t> len(n);
+  uint64_t total = 0;
+  for (uint32_t r = 0; r < n; ++r) {
+    off[r] = total;
+    len[r] = std::min(recs[r].len, most);
+    total += len[r];
+  }
+  std::vector<uint8_t> raw(total);
+  ParallelFor(n, std::max(1u, std::min(threads_, 8u)), [&](size_t b, size_t e, unsigned) {
+    for (size_t r = b; r < e; ++r)
+      if (len[r]) std::memcpy(raw.data() + off[r], recs[r].seq, len[r]);
+  });
+  QueryData q;
+  q.chunk.id = (uint32_t)queries_.size();
+  q.chunk.nseq = n * per;
+  q.chunk.L = width;
+  for (uint32_t r = 0; r < n; ++r) {
+    // qry's over-width warning, per output record (frames: dna_len / 3 letters)
+    const uint32_t letters = dna ? dna_len / 3 : recs[r].len;
+    for (uint32_t k = 0; k < per; ++k) {
+      q.chunk.names.push_back(recs[r].name);
+      if (letters > width) {
+        if (cut_records) ++*cut_records;
+        if (cut_names) cut_names->emplace_back(recs[r].name);
+      }
+    }
+  }
+  PrepareQueryChunk(&q, false);
+  q.qlen.assign(q.chunk.nseq, 1);
+  double seconds = 0;
+  q.dev = dev.FormatQuery(raw.data(), total, off.data(), len.data(), n, width, dna ? std::max(dna_len, 1u) : 0,
+                          q.qlen.data(), &seconds);
+  struct FreeUnadopted {
+    QueryData *q;
+    ~FreeUnadopted() {
+      if (q) DeviceModule::Get().Free(q->dev);
+    }
+  } guard{&q};
+  dev.SetQueryGroups(q.dev, q.group_first.data(), q.group_last.data(), (uint32_t)q.group_first.size());
+  q.global_base = queries_.empty() ? 0 : queries_.back().global_base + queries_.back().chunk.nseq;
+  format_seconds_ += seconds;
+  ++format_launches_;
+  queries_.push_back(std::move(q));
+  guard.q = nullptr;
+  load_seconds_ += NowSeconds() - t0 - seconds;
+}
+
+void Session::FinishQuerySet() {
+  ++query_sets_;
+  QueryStats();
+}
+
+void Session::QueryStats() {
+  stats_.seconds_query_format = format_seconds_;
+  stats_.query_format_launches = format_launches_;
+  stats_.query_sets = query_sets_;
+  stats_.seconds_query_read = read_seconds_;
+  stats_.seconds_query_load = load_seconds_;
+}
+
+namespace {
+struct WidthRule {
+  uint32_t width, max_concat;
+};
+WidthRule QuerySetRules(uint32_t width, bool dna, uint32_t chunk_mb, bool *capped) {
+  bool c = false;
+  WidthRule r{QueryRecordWidth(width, dna, &c), QueryChunkLimit(chunk_mb != 0, chunk_mb, dna)};
+  if (capped) *capped = c;
+  return r;
+}
+}  // namespace
+
+void Session::SetQueries(const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets, const uint32_t *lengths,
+                         const char *names, uint64_t names_len, uint32_t n, uint32_t width, bool dna,
+                         uint32_t chunk_mb) {
+  if (n && (!offsets || !lengths || !names || (!raw && raw_len))) throw Error("set queries: null argument");
+  std::vector<QueryRecordView> recs(n);
+  uint64_t at = 0;
+  for (uint32_t r = 0; r < n; ++r) {
+    if (offsets[r] > raw_len || lengths[r] > raw_len - offsets[r])
+      throw Error("set queries: record " + std::to_string(r) + " outside the letter buffer");
+    const char *nl = at < names_len ? static_cast<const char *>(std::memchr(names + at, '\n', names_len - at)) : nullptr;
+    if (!nl) throw Error("set queries: fewer than " + std::to_string(n) + " newline-terminated names");
+    recs[r] = QueryRecordView{reinterpret_cast<const char *>(raw) + offsets[r], lengths[r],
+                              std::string_view(names + at, (size_t)(nl - (names + at)))};
+    at = (uint64_t)(nl - names) + 1;
+  }
+  const WidthRule rule = QuerySetRules(width, dna, chunk_mb, nullptr);
+  std::vector<uint64_t> cuts;
+  const bool whole = QueryChunkCuts(lengths, n, rule.max_concat, &cuts);
+  DropQueries();
+  try {
+    for (size_t c = 0; c + 1 < cuts.size(); ++c)
+      AddQueryChunk(recs.data() + cuts[c], (uint32_t)(cuts[c + 1] - cuts[c]), rule.width, dna, nullptr, nullptr);
+    if (!whole) throw Error("set queries: too small max length.");
+  } catch (...) {
+    DropQueries();  // no half-made set
+    throw;
+  }
+  FinishQuerySet();
+}
+
+void Session::SetQueriesFasta(const std::string &path, uint32_t width, bool dna, uint32_t chunk_mb,
+                              uint64_t *cut_records, std::vector<std::string> *cut_names, bool *capped) {
+  const WidthRule rule = QuerySetRules(width, dna, chunk_mb, capped);
+  if (cut_records) *cut_records = 0;
+  {
+    std::ifstream probe(path.c_str());
+    if (!probe) throw Error("set queries: cannot open " + path);
+  }
+  DropQueries();
+  try {
+    QueryChunkReader reader(path, rule.max_concat);
+    std::vector<FastaRecord> recs;
+    std::vector<QueryRecordView> views;
+    for (;;) {
+      const double t0 = NowSeconds();
+      const int more = reader.Next(&recs);
+      read_seconds_ += NowSeconds() - t0;
+      if (more < 0) throw Error("set queries: too small max length.");
+      if (more == 0) break;
+      views.resize(recs.size());
+      for (size_t r = 0; r < recs.size(); ++r) {
+        if (recs[r].seq.size() > UINT32_MAX) throw Error("set queries: a record of over 4 G letters");
+        views[r] = QueryRecordView{recs[r].seq.data(), (uint32_t)recs[r].seq.size(), recs[r].name};
+      }
+      AddQueryChunk(views.data(), (uint32_t)views.size(), rule.width, dna, cut_records, cut_names);
+    }
+  } catch (...) {
+    DropQueries();  // no half-made set
+    throw;
+  }
+  FinishQuerySet();
+}
+
+void Session::SetOutputFile(const std::string &path) {
+  if (formatter_) formatter_->Drain();
+  if (writer_) writer_->Drain();
+  opt_.output_file = path;
+  streamed_ = false;  // the last run's text has not been written to this file
+}
+
+std::vector<uint32_t> Session::AllQueryLengths() const {
+  std::vector<uint32_t> out;
+  for (const QueryData &q : queries_) out.insert(out.end(), q.qlen.begin(), q.qlen.end());
+  return out;
+}
+
+size_t Session::QueryRecords(uint32_t chunk, uint8_t *codes, size_t cap) {
+  if (chunk >= queries_.size()) throw Error("query chunk " + std::to_string(chunk) + " of " + std::to_string(queries_.size()));
+  DeviceModule &dev = DeviceModule::Get();
+  const size_t n = dev.QueryBytes(queries_[chunk].dev);
+  if (!codes) return n;
+  if (cap >= n) {
+    dev.DownloadQuery(queries_[chunk].dev, codes);
+    return n;
+  }
+  std::vector<uint8_t> all(n);
+  dev.DownloadQuery(queries_[chunk].dev, all.data());
+  std::memcpy(codes, all.data(), cap);
+  return cap;
 }
 
 // defined after LineFormat (a complete type for format_)

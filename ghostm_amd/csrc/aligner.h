@@ -16,6 +16,7 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <string_view>
 #include <thread>
 #include <vector>
 
@@ -131,6 +132,31 @@ class Session {
   // of the set itself once.
   explicit Session(const AlignerOptions &opt, uint32_t shard_rank = 0, uint32_t shard_world = 1,
                    const ShardExchange *exchange = nullptr);
+  // A database session (GhostmSessionCreateDb): every DB chunk resident, no
+  // queries until SetQueries; -i, -S or -L in the options is an error.
+  struct DbOnly {};
+  Session(const AlignerOptions &opt, DbOnly);
+  // Replaces the query set by what `ghostm qry -l width [-t d] -L chunk_mb`
+  // would format from these records (chunk_mb 0: qry's default), formatted on
+  // the device straight into the resident chunks (DeviceModule::FormatQuery);
+  // the last run's results are dropped, the old chunks' device blocks go back
+  // to the pool. Throws on a shard session and on bad arguments (the session
+  // is then as it was); a set that fails while loading leaves the session
+  // with no queries. names: n names, each ended by '\n'.
+  void SetQueries(const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets, const uint32_t *lengths,
+                  const char *names, uint64_t names_len, uint32_t n, uint32_t width, bool dna, uint32_t chunk_mb);
+  // ... read from a FASTA file with the formatter's reader. cut_records (may be
+  // null): the output records over the width, cut_names (may be null): their
+  // names in qry's warning order, *capped (may be null): the width was over
+  // the limit (qry's other warning).
+  void SetQueriesFasta(const std::string &path, uint32_t width, bool dna, uint32_t chunk_mb, uint64_t *cut_records,
+                       std::vector<std::string> *cut_names = nullptr, bool *capped = nullptr);
+  // the -o path of later Run(true) and WriteOutputFile calls
+  void SetOutputFile(const std::string &path);
+  // every record's WriteOutput length over the chunks in order, and one
+  // chunk's coded records copied back from the device (NULL: their size)
+  std::vector<uint32_t> AllQueryLengths() const;
+  size_t QueryRecords(uint32_t chunk, uint8_t *codes, size_t cap);
   uint64_t ShardBegin() const { return shard_begin_; }
   uint64_t ShardEnd() const { return shard_end_; }
   // the most hit records one run can return: name groups x max(-b, 1)
@@ -206,6 +232,19 @@ class Session {
   using Results = std::vector<std::vector<HitRecord>>;
 
   static void PrepareQueryChunk(QueryData *q, bool qlen = true);
+  // one record of a set being loaded: its letters and its name
+  struct QueryRecordView {
+    const char *seq;
+    uint32_t len;
+    std::string_view name;
+  };
+  void CreateOrFree(uint32_t shard_rank, uint32_t shard_world, const ShardExchange *ex);
+  void DropQueries();  // the last run's results and the resident query chunks
+  // the next chunk of a set (qry's files for these records, resident)
+  void AddQueryChunk(const QueryRecordView *recs, uint32_t n, uint32_t width, bool dna, uint64_t *cut_records,
+                     std::vector<std::string> *cut_names);
+  void FinishQuerySet();
+  void QueryStats();  // the query-set fields of stats_
   void QueryLengths(std::vector<QueryData *> chunks);
   void ApplyShard(uint32_t rank, uint32_t world);
   // shard sessions: the batch plan of every (query chunk, DB chunk)
@@ -246,6 +285,10 @@ class Session {
   AlignerOptions opt_;
   uint64_t shard_begin_ = 0, shard_end_ = UINT64_MAX;  // query range over the loaded chunks
   uint32_t shard_world_ = 1;
+  bool db_only_ = false;
+  double format_seconds_ = 0;          // FormatQuery's device time, launches: the current set
+  uint64_t format_launches_ = 0, query_sets_ = 0;
+  double read_seconds_ = 0, load_seconds_ = 0;  // host: FASTA reading; packing, upload and read-back
   std::vector<QueryData> queries_;
   std::vector<DbData> dbs_;
   uint32_t db_sum_u32_ = 0;           // DBReader::GetSumDbLength() truncates to u32

@@ -1,4 +1,6 @@
 // capi.cpp — session part of the C ABI (include/ghostm_hip.h Part 2).
+#include <getopt.h>
+
 #include <algorithm>
 #include <cstring>
 #include <fstream>
@@ -8,6 +10,7 @@
 #include "../../include/ghostm_hip.h"
 #include "aligner.h"
 #include "common.h"
+#include "query_set.h"
 
 using namespace ghostm;
 
@@ -24,6 +27,89 @@ void *GhostmSessionCreate(int argc, char **argv) {
   } catch (std::exception &e) {
     SetLastErrorMessage(e.what());
     return nullptr;
+  }
+}
+
+void *GhostmSessionCreateDb(int argc, char **argv) {
+  try {
+    AlignerOptions opt = ParseAlignerOptions(argc, argv);
+    return new Session(opt, Session::DbOnly{});
+  } catch (std::exception &e) {
+    SetLastErrorMessage(*e.what() ? e.what() : "invalid option");
+    return nullptr;
+  }
+}
+
+int GhostmSessionSetQueries(void *s, const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets,
+                            const uint32_t *lengths, const char *names, uint64_t names_len, uint32_t n,
+                            uint32_t width, int dna, uint32_t chunk_mb) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetQueries(raw, raw_len, offsets, lengths, names, names_len, n, width, dna != 0,
+                                          chunk_mb);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+int GhostmSessionSetQueriesFasta(void *s, const char *path, uint32_t width, int dna, uint32_t chunk_mb,
+                                 uint64_t *cut_records) {
+  try {
+    if (!s) throw Error("null session");
+    if (!path) throw Error("set queries: null path");
+    static_cast<Session *>(s)->SetQueriesFasta(path, width, dna != 0, chunk_mb, cut_records);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+int GhostmSessionSetOutputFile(void *s, const char *path) {
+  try {
+    if (!s) throw Error("null session");
+    if (!path) throw Error("set output file: null path");
+    static_cast<Session *>(s)->SetOutputFile(path);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionQueryLengths(void *s, uint32_t *qlen, size_t cap) {
+  if (!s) return 0;
+  const std::vector<uint32_t> v = static_cast<Session *>(s)->AllQueryLengths();
+  if (!qlen) return v.size();
+  const size_t n = std::min(cap, v.size());
+  std::memcpy(qlen, v.data(), n * sizeof(uint32_t));
+  return n;
+}
+
+size_t GhostmSessionQueryRecords(void *s, uint32_t chunk, uint8_t *codes, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    return static_cast<Session *>(s)->QueryRecords(chunk, codes, cap);
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+int64_t GhostmQueryChunkCuts(const uint32_t lengths[], uint64_t n, uint32_t chunk_mb, int dna, uint64_t cuts[],
+                             uint64_t cap) {
+  try {
+    if (n && !lengths) throw Error("chunk cuts: null argument");
+    std::vector<uint64_t> c;
+    const bool whole = QueryChunkCuts(lengths, n, QueryChunkLimit(chunk_mb != 0, chunk_mb, dna != 0), &c);
+    if (cuts) std::copy(c.begin(), c.begin() + (long)std::min<uint64_t>(cap, c.size()), cuts);
+    if (!whole) throw Error("chunk cuts: too small max length.");
+    return (int64_t)c.size() - 1;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return -1;
   }
 }
 
@@ -204,6 +290,74 @@ int GhostmAlignMain(int argc, char **argv) {
                 << st.hits << "\n# seconds total " << st.seconds_total << " seed " << st.seconds_seed
                 << " score " << st.seconds_score << " traceback " << st.seconds_traceback
                 << " merge " << st.seconds_merge << " output " << st.seconds_output << std::endl;
+    }
+  } catch (std::exception &e) {
+    std::cerr << e.what() << std::endl;
+  }
+  return 0;
+}
+
+// `ghostm search`: one database session, then qry + aln per (FASTA, output) pair
+// without the formatted files. Usage errors return 1 before any device call.
+int GhostmSearchMain(int argc, char **argv) {
+  std::vector<char *> aln_argv{argv[0]};
+  uint32_t width = 75, chunk_mb = 0;
+  bool dna = false;
+  optind = 1;
+  opterr = 1;
+  int c;
+  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:")) >= 0) {
+    switch (c) {
+      case 'q':
+        if (strcmp(optarg, "d") == 0) dna = true;
+        else if (strcmp(optarg, "p") == 0) dna = false;
+        else return 1;
+        break;
+      case 'w': width = (uint32_t)atoi(optarg); break;
+      case 'c': chunk_mb = (uint32_t)atoi(optarg); break;
+      case 'i':
+      case 'o':
+      case 'S':
+      case 'L':
+      case '?': return 1;
+      case 'v': aln_argv.push_back(const_cast<char *>("-v")); break;
+      default: {
+        static const char *const kFlags[] = {"-b", "-d", "-D", "-e", "-E", "-G", "-l", "-M", "-r", "-s", "-t", "-y"};
+        for (const char *f : kFlags)
+          if (f[1] == c) aln_argv.push_back(const_cast<char *>(f));
+        aln_argv.push_back(optarg);
+      }
+    }
+  }
+  std::vector<std::string> pos(argv + optind, argv + argc);
+  if (pos.empty() || pos.size() % 2) return 1;
+  try {
+    aln_argv.push_back(nullptr);
+    AlignerOptions opt = ParseAlignerOptions((int)aln_argv.size() - 1, aln_argv.data());
+    Session session(opt, Session::DbOnly{});
+    for (size_t k = 0; k < pos.size(); k += 2) {
+      try {
+        { std::ofstream touch(pos[k + 1].c_str()); }
+        session.SetOutputFile(pos[k + 1]);
+        std::vector<std::string> cut;
+        bool capped = false;
+        session.SetQueriesFasta(pos[k], width, dna, chunk_mb, nullptr, &cut, &capped);
+        if (capped)
+          std::cerr << "Warring: over upper limit of query length. Max is " << kMaxQueryLength * (dna ? 3 : 1) << "."
+                    << std::endl;
+        for (const std::string &name : cut) std::cerr << "warning : the length of sequence is over. " << name << std::endl;
+        session.Run(true);
+        session.WriteOutputFile();
+        if (opt.verbose) {
+          const GhostmStats &st = session.Stats();
+          std::cout << "# " << pos[k] << " queries " << st.queries << " candidates " << st.candidates << " hits "
+                    << st.hits << " seconds " << st.seconds_total << " query format " << st.seconds_query_format
+                    << std::endl;
+        }
+      } catch (std::exception &e) {
+        std::cerr << e.what() << std::endl;
+      }
     }
   } catch (std::exception &e) {
     std::cerr << e.what() << std::endl;

@@ -124,6 +124,18 @@ class DeviceModule {
   // Host to device through page-locked staging on the main stream (see device.hip).
   void StagedUpload(void *dst, const void *src, size_t bytes);
   DevQuery *UploadQuery(const uint8_t *seq, uint32_t nseq, uint32_t L);
+  // UploadQuery from letters (the resident form of the `qry` formatter,
+  // qformat.hip): record r's letters are raw[off[r] .. off[r] + len[r]). They
+  // go up through StagedUpload and are coded (dna_len = 0) or six-frame
+  // translated (dna_len = the chunk's read length, at least 1) on the main
+  // stream straight into the chunk's records: n (x 6) records of `width` codes.
+  // Only qlen[n (x 6)], every record's QueryResidues, comes back. *seconds:
+  // the kernel's device time.
+  DevQuery *FormatQuery(const uint8_t *raw, uint64_t raw_len, const uint64_t *off, const uint32_t *len, uint32_t n,
+                        uint32_t width, uint32_t dna_len, uint32_t *qlen, double *seconds);
+  // A resident chunk's coded records (nseq * L bytes) back on the host.
+  size_t QueryBytes(const DevQuery *q) const;
+  void DownloadQuery(const DevQuery *q, uint8_t *dst);
   DevDb *UploadDb(const uint8_t *seq, uint32_t len, const uint32_t *keys_count, uint32_t kcl,
                   const uint32_t *positions, uint32_t npos);
   // Name groups of a query chunk (consecutive equal names), for the device merge.

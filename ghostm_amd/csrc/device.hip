@@ -17,6 +17,7 @@
 #include "device.h"
 #include "formats.h"
 #include "kernels.h"
+#include "qformat.h"
 #include "score_tasks.h"
 
 namespace ghostm {
@@ -305,6 +306,10 @@ struct DeviceModule::Impl {
   DevBuf counters;     // K2: u64 [0] score cells, u32 at [2] guard count
   DevBuf tb_counters;  // K3: u64 [0] traceback cells, [1] K3a scan cells, [2] hits traced (k_finalize)
   bool matrix_set = false;
+  // FormatQuery: the chunk's letters, offsets and lengths, the records'
+  // lengths, the kernels' tables; the kernel's events
+  DevBuf qf_raw, qf_off, qf_len, qf_qlen, qf_tab;
+  hipEvent_t ev_q0 = nullptr, ev_q1 = nullptr;
 };
 
 static constexpr uint32_t kSlotCap = kern::kMaxSlotCap;
@@ -396,7 +401,8 @@ void DeviceModule::Bind(int device) {
   }
 #endif
   for (hipEvent_t *e : {&impl_->ev0, &impl_->ev1, &impl_->ev_m0, &impl_->ev_m1, &impl_->ev_t0, &impl_->ev_t1, &impl_->ev_tk,
-                        &impl_->ev_done, &impl_->ev_tasks, &impl_->ev_s0, &impl_->ev_s1, &impl_->ev_nb})
+                        &impl_->ev_done, &impl_->ev_tasks, &impl_->ev_s0, &impl_->ev_s1, &impl_->ev_nb, &impl_->ev_q0,
+                        &impl_->ev_q1})
     HIP_CHECK(hipEventCreate(e));
   for (hipEvent_t &e : impl_->stage_ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   HIP_CHECK(hipFuncSetAttribute((const void *)kern::k_seed<1024, 16384, false>,
@@ -553,6 +559,59 @@ DevQuery *DeviceModule::UploadQuery(const uint8_t *seq, uint32_t nseq, uint32_t 
   q->seq.Reserve(b + 16);
   StagedUpload(q->seq.p, seq, b);
   return q;
+}
+
+DevQuery *DeviceModule::FormatQuery(const uint8_t *raw, uint64_t raw_len, const uint64_t *off, const uint32_t *len,
+                                    uint32_t n, uint32_t width, uint32_t dna_len, uint32_t *qlen, double *seconds) {
+  Use();
+  if (!impl_) throw Error("device not bound");
+  if (seconds) *seconds = 0;
+  if (width == 0 || width > kMaxQueryLength)
+    throw Error("query record width " + std::to_string(width) + " outside 1..127");
+  const uint64_t nout = (uint64_t)n * (dna_len ? 6 : 1);
+  if (n == 0 || nout > UINT32_MAX) throw Error("query chunk of " + std::to_string(n) + " records");
+  for (uint32_t r = 0; r < n; ++r)
+    if (off[r] > raw_len || len[r] > raw_len - off[r]) throw Error("query record outside the letter buffer");
+  Impl &I = *impl_;
+  if (!I.qf_tab.p) {
+    std::vector<uint8_t> tab(QueryFormatTableBytes());
+    QueryFormatTables(tab.data());
+    I.qf_tab.Reserve(tab.size());
+    HIP_CHECK(hipMemcpy(I.qf_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+  }
+  std::unique_ptr<DevQuery, std::function<void(DevQuery *)>> q(new DevQuery(), [this](DevQuery *p) { Free(p); });
+  q->nseq = (uint32_t)nout;
+  q->L = width;
+  q->seq.Reserve((size_t)nout * width + 16);
+  I.qf_raw.Reserve(raw_len);
+  I.qf_off.Reserve((size_t)n * 8);
+  I.qf_len.Reserve((size_t)n * 4);
+  I.qf_qlen.Reserve((size_t)nout * 4);
+  StagedUpload(I.qf_raw.p, raw, raw_len);
+  StagedUpload(I.qf_off.p, off, (size_t)n * 8);
+  StagedUpload(I.qf_len.p, len, (size_t)n * 4);
+  HIP_CHECK(hipEventRecord(I.ev_q0, S(stream_)));
+  LaunchQueryFormat(stream_, I.qf_raw.as<uint8_t>(), I.qf_off.as<uint64_t>(), I.qf_len.as<uint32_t>(), n, width,
+                    dna_len, q->seq.as<uint8_t>(), I.qf_qlen.as<uint32_t>(), I.qf_tab.p);
+  HIP_CHECK(hipEventRecord(I.ev_q1, S(stream_)));
+  HIP_CHECK(hipMemcpyAsync(qlen, I.qf_qlen.p, (size_t)nout * 4, hipMemcpyDeviceToHost, S(stream_)));
+  HIP_CHECK(hipStreamSynchronize(S(stream_)));
+  if (seconds) {
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, I.ev_q0, I.ev_q1));
+    *seconds = ms * 1e-3;
+  }
+  return q.release();
+}
+
+size_t DeviceModule::QueryBytes(const DevQuery *q) const { return (size_t)q->nseq * q->L; }
+
+void DeviceModule::DownloadQuery(const DevQuery *q, uint8_t *dst) {
+  Use();
+  const size_t b = QueryBytes(q);
+  if (!b) return;
+  HIP_CHECK(hipMemcpyAsync(dst, q->seq.p, b, hipMemcpyDeviceToHost, S(stream_)));
+  HIP_CHECK(hipStreamSynchronize(S(stream_)));
 }
 
 DevDb *DeviceModule::UploadDb(const uint8_t *seq, uint32_t len, const uint32_t *kc, uint32_t kcl,

@@ -23,45 +23,11 @@
 #include "../../include/ghostm_hip.h"
 #include "common.h"
 #include "formats.h"
+#include "query_set.h"
 
 namespace ghostm {
 
 namespace {
-
-struct FastaRecord {
-  std::string name, seq;
-};
-
-// One record per Next(); the header line of the following record is kept.
-class FastaReader {
- public:
-  explicit FastaReader(const std::string &path) : in_(path.c_str()) {}
-  bool Next(FastaRecord *r) {
-    if (in_.eof()) return false;
-    std::string line = held_;
-    while (!in_.eof() && (line.empty() || line[0] != '>')) std::getline(in_, line);
-    if (in_.eof()) return false;
-    if (line.back() == '\r') line.pop_back();
-    r->name.clear();
-    const size_t p = line.find_first_not_of("> ");
-    if (p != std::string::npos) r->name = line.substr(p);
-    r->seq.clear();
-    while (!in_.eof()) {
-      std::getline(in_, line);
-      if (line.empty()) continue;
-      if (line[0] == '>') break;
-      if (line.back() == '\r') line.pop_back();
-      if (line.at(line.size() - 1) == '+') line.pop_back();
-      r->seq += line;
-    }
-    held_ = line;
-    return true;
-  }
-
- private:
-  std::ifstream in_;
-  std::string held_;
-};
 
 template <class T> void WriteRaw(std::ofstream &f, const T *p, size_t n) {
   f.write(reinterpret_cast<const char *>(p), sizeof(T) * n);
@@ -73,6 +39,69 @@ void WriteNames(const std::string &path, const std::vector<FastaRecord> &recs) {
 }
 
 }  // namespace
+
+bool FastaReader::Next(FastaRecord *r) {
+  if (in_.eof()) return false;
+  std::string line = held_;
+  while (!in_.eof() && (line.empty() || line[0] != '>')) std::getline(in_, line);
+  if (in_.eof()) return false;
+  if (line.back() == '\r') line.pop_back();
+  r->name.clear();
+  const size_t p = line.find_first_not_of("> ");
+  if (p != std::string::npos) r->name = line.substr(p);
+  r->seq.clear();
+  while (!in_.eof()) {
+    std::getline(in_, line);
+    if (line.empty()) continue;
+    if (line[0] == '>') break;
+    if (line.back() == '\r') line.pop_back();
+    if (line.at(line.size() - 1) == '+') line.pop_back();
+    r->seq += line;
+  }
+  held_ = line;
+  return true;
+}
+
+int QueryChunkReader::Next(std::vector<FastaRecord> *recs) {
+  recs->clear();
+  if (!cut_.Begin(pending_valid_, (uint32_t)pending_.seq.size())) return -1;
+  if (pending_valid_) {
+    recs->push_back(pending_);
+    pending_valid_ = false;
+  }
+  FastaRecord r;
+  while (reader_.Next(&r)) {
+    if (!cut_.Add((uint32_t)r.seq.size())) {
+      pending_ = r;
+      pending_valid_ = true;
+      break;
+    }
+    recs->push_back(r);
+  }
+  return recs->empty() ? 0 : 1;
+}
+
+bool QueryChunkCuts(const uint32_t *len, uint64_t n, uint32_t max_concat, std::vector<uint64_t> *cuts) {
+  QueryChunkCutter cut(max_concat);
+  cuts->assign(1, 0);
+  uint64_t i = 0;
+  bool carried = false;
+  for (;;) {
+    const uint64_t first = i;
+    if (!cut.Begin(carried, carried ? len[i] : 0)) return false;
+    if (carried) ++i;
+    carried = false;
+    while (i < n) {
+      if (!cut.Add(len[i])) {
+        carried = true;
+        break;
+      }
+      ++i;
+    }
+    if (i == first) return true;  // an empty chunk ends the set
+    cuts->push_back(i);
+  }
+}
 
 // ------------------------------------------------------------------ db
 int DbFormatMain(int argc, char **argv) {
@@ -305,7 +334,8 @@ void FormatQueryChunkGpu(const std::vector<FastaRecord> &recs, bool dna, uint32_
 
 int QueryFormatMain(int argc, char **argv) {
   std::string in_path, out_prefix;
-  uint32_t max_concat = 1u << 27;
+  bool have_limit = false;
+  uint32_t limit_mb = 0;
   uint32_t width = 75;
   bool dna = false;
   int device = -1;  // -D d (extension): code / translate the records on GPU d
@@ -316,7 +346,10 @@ int QueryFormatMain(int argc, char **argv) {
       case 'i': in_path = optarg; break;
       case 'o': out_prefix = optarg; break;
       case 'l': width = atoi(optarg); break;
-      case 'L': max_concat = atoi(optarg) * (1 << 20); break;
+      case 'L':
+        have_limit = true;
+        limit_mb = (uint32_t)atoi(optarg);
+        break;
       case 'D': device = atoi(optarg); break;
       case 't':
         if (strcmp(optarg, "d") == 0) dna = true;
@@ -326,44 +359,22 @@ int QueryFormatMain(int argc, char **argv) {
       default: throw std::invalid_argument("");
     }
   }
-  if (dna) {
-    max_concat /= 2;
-    width /= 3;
-    if (width >= kMaxQueryLength) {
-      std::cerr << "Warring: over upper limit of query length. Max is " << kMaxQueryLength * 3 << "." << std::endl;
-      width = kMaxQueryLength;
-    }
-  } else if (width >= kMaxQueryLength) {
-    std::cerr << "Warring: over upper limit of query length. Max is " << kMaxQueryLength << "." << std::endl;
-    width = kMaxQueryLength;
-  }
-  FastaReader reader(in_path);
-  bool pending_valid = false;
-  FastaRecord pending;
+  const uint32_t max_concat = QueryChunkLimit(have_limit, limit_mb, dna);
+  bool capped = false;
+  width = QueryRecordWidth(width, dna, &capped);
+  if (capped)
+    std::cerr << "Warring: over upper limit of query length. Max is " << kMaxQueryLength * (dna ? 3 : 1) << "."
+              << std::endl;
+  QueryChunkReader reader(in_path, max_concat);
   uint32_t max_nseq = 0;
   for (int chunk = 0;; ++chunk) {
     std::vector<FastaRecord> recs;
-    uint32_t sum = 0;
-    if (pending_valid) {
-      sum = (uint32_t)pending.seq.size();
-      if (sum > max_concat) {
-        std::cerr << "error : too small max length." << std::endl;
-        return 1;
-      }
-      recs.push_back(pending);
-      pending_valid = false;
+    const int more = reader.Next(&recs);
+    if (more < 0) {
+      std::cerr << "error : too small max length." << std::endl;
+      return 1;
     }
-    FastaRecord r;
-    while (reader.Next(&r)) {
-      sum += (uint32_t)r.seq.size();
-      if (sum > max_concat) {
-        pending = r;
-        pending_valid = true;
-        break;
-      }
-      recs.push_back(r);
-    }
-    if (recs.empty()) {
+    if (more == 0) {
       std::ofstream f((out_prefix + ".inf").c_str(), std::ios::binary);
       const int32_t division = chunk;
       WriteRaw(f, &division, 1);

@@ -1,5 +1,6 @@
 // main.cpp — the `ghostm` command line (reference main.cpp:36-122): db | qry | aln,
-// plus `synth` (synthetic benchmark inputs). `aln` always runs on the GPU
+// plus `synth` (synthetic benchmark inputs) and `search` (qry + aln for several
+// FASTA files against one resident database). `aln` always runs on the GPU
 // (-D selects the device, default 0). Errors are printed and the process exits 0
 // like the reference; usage or an unknown command exits 1.
 #include <unistd.h>
@@ -28,6 +29,9 @@ static int Usage() {
             << "       [-M scoreMatrix] [-y outputStyle] [-S startChunk] [-L endChunk] [-v]\n"
             << "       -i queries -d database -o output\n"
             << "       (-y 6: BLAST-tabular, the twelve -outfmt 6 columns)\n"
+            << "search: ghostm search [aln options except -i -o -S -L] [-q d|p] [-w maxLength] [-c chunkSizeMB]\n"
+            << "       -d database q1.fasta out1 [q2.fasta out2 ...]\n"
+            << "       (qry + aln per pair on one resident database; -q -w -c as qry's -t -l -L)\n"
             << "synth: ghostm synth -d db.fasta -q queries.fasta [-n nq] [-N dbResidues] [-s seed]\n";
   return 1;
 }
@@ -36,8 +40,10 @@ int main(int argc, char **argv) {
   if (argc < 2) return Usage();
   const char *cmd = argv[1];
   try {
-    if (strcmp(cmd, "aln") == 0) {
-      const int rc = GhostmAlignMain(argc - 1, argv + 1);
+    const bool search = strcmp(cmd, "search") == 0;
+    if (search || strcmp(cmd, "aln") == 0) {
+      const int rc = search ? GhostmSearchMain(argc - 1, argv + 1) : GhostmAlignMain(argc - 1, argv + 1);
+      if (search && rc != 0) return Usage();
       // the session is gone and its output file closed: leave without the HIP
       // runtime's teardown (tens of ms of a cold run; GHOSTM_FAST_EXIT=0 keeps it)
       std::cout.flush();

@@ -16,14 +16,21 @@
 //   k_qry_frames   one wave per read, 64 letters of a frame at a time; the
 //                  stop/ATG state (a scan along the frame in the reference) is
 //                  the last event at or before each letter, found by ballots
+// Both are templates on QLEN: the resident form (DeviceModule::FormatQuery, a
+// session's query set formatted straight into its DevQuery) also takes each
+// record's QueryResidues from a ballot of the non-X lanes per 64 codes, so only
+// the 4-byte lengths come back; GhostmFormatQueriesGpu (qry -D) runs the same
+// bodies without it.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 #include <string>
 
 #include "../../include/ghostm_hip.h"
 #include "common.h"
 #include "formats.h"
+#include "qformat.h"
 
 namespace ghostm {
 
@@ -54,13 +61,22 @@ struct QfArgs {
   uint32_t nrec, width, dna_len;
   uint8_t *out;
   const QfTables *tab;
+  uint32_t *qlen;  // QLEN kernels: QueryResidues of every output record
 };
 
 constexpr uint32_t kQfWaves = kQfBlock / 64;
 
+// QueryResidues (formats.h) of a record from the wave's own codes: `last` is
+// one past the last non-X code seen so far, nonx the ballot of the non-X lanes
+// of the 64 codes starting at k0.
+__device__ __forceinline__ uint32_t LastResidue(uint32_t last, unsigned long long nonx, uint32_t k0) {
+  return nonx ? k0 + 64u - (uint32_t)__clzll(nonx) : last;
+}
+
 // One wave per record (grid-stride): lanes walk the record's letters and its
-// output bytes contiguously, the code table in LDS.
-__global__ __launch_bounds__(kQfBlock) void k_qry_protein(QfArgs a) {
+// output bytes contiguously, the code table in LDS. QLEN: the record's
+// QueryResidues too (the resident form, DeviceModule::FormatQuery).
+template <bool QLEN> __global__ __launch_bounds__(kQfBlock) void k_qry_protein(QfArgs a) {
   __shared__ uint8_t s_code[256];
   s_code[threadIdx.x] = a.tab->protein[threadIdx.x];
   __syncthreads();
@@ -69,7 +85,14 @@ __global__ __launch_bounds__(kQfBlock) void k_qry_protein(QfArgs a) {
     const uint32_t n = min(a.len[r], a.width);
     const uint8_t *src = a.raw + a.off[r];
     uint8_t *dst = a.out + (uint64_t)r * a.width;
-    for (uint32_t k = lane; k < a.width; k += 64) dst[k] = k < n ? s_code[src[k]] : (uint8_t)kBaseX;
+    uint32_t last = 0;
+    for (uint32_t k0 = 0; k0 < a.width; k0 += 64) {
+      const uint32_t k = k0 + lane;
+      const uint8_t code = k < n ? s_code[src[k]] : (uint8_t)kBaseX;
+      if (k < a.width) dst[k] = code;
+      if (QLEN) last = LastResidue(last, __ballot(code != kBaseX), k0);
+    }
+    if (QLEN && lane == 0) a.qlen[r] = max(last, 1u);
   }
 }
 
@@ -78,7 +101,7 @@ __global__ __launch_bounds__(kQfBlock) void k_qry_protein(QfArgs a) {
 // stop/ATG state of a letter is the type of the last event (ATG clears, a stop
 // codon sets) at or before it, else the state carried from the previous 64
 // letters: two ballots and a leading-bit search, no sequential walk.
-__global__ __launch_bounds__(kQfBlock) void k_qry_frames(QfArgs a) {
+template <bool QLEN> __global__ __launch_bounds__(kQfBlock) void k_qry_frames(QfArgs a) {
   __shared__ uint8_t s_base[256];
   __shared__ uint8_t s_codon[128];
   s_base[threadIdx.x] = a.tab->dna[threadIdx.x];
@@ -103,6 +126,7 @@ __global__ __launch_bounds__(kQfBlock) void k_qry_frames(QfArgs a) {
       };
       uint8_t *rec = a.out + ((uint64_t)r * 6 + f) * a.width;
       uint32_t carry = 0;  // stop state entering this group of 64 letters
+      uint32_t last = 0;
       for (uint32_t t0 = 0; t0 < keep; t0 += 64) {
         const uint32_t t = t0 + lane, k = o + 2 + 3 * t;
         uint32_t code = 24, ev = 0;  // '*' padding past the last codon
@@ -115,10 +139,13 @@ __global__ __launch_bounds__(kQfBlock) void k_qry_frames(QfArgs a) {
         const unsigned long long evm = __ballot(ev != 0), setm = __ballot(ev == 2);
         const unsigned long long mine = evm & upto;
         const uint32_t stop = mine ? (uint32_t)(setm >> (63 - __clzll(mine))) & 1u : carry;
-        if (t < keep) rec[t] = stop ? (uint8_t)24 : (uint8_t)code;
+        const uint32_t put = stop ? 24u : code;
+        if (t < keep) rec[t] = (uint8_t)put;
+        if (QLEN) last = LastResidue(last, __ballot(t < keep && put != kBaseX), t0);
         carry = evm ? (uint32_t)(setm >> (63 - __clzll(evm))) & 1u : carry;
       }
       for (uint32_t t = keep + lane; t < a.width; t += 64) rec[t] = kBaseX;
+      if (QLEN && lane == 0) a.qlen[(uint64_t)r * 6 + f] = max(last, 1u);
     }
   }
 }
@@ -149,6 +176,27 @@ QfTables MakeTables() {
 }
 
 }  // namespace
+
+size_t QueryFormatTableBytes() { return sizeof(QfTables); }
+
+void QueryFormatTables(void *dst) {
+  const QfTables t = MakeTables();
+  std::memcpy(dst, &t, sizeof(t));
+}
+
+void LaunchQueryFormat(void *stream, const uint8_t *d_raw, const uint64_t *d_off, const uint32_t *d_len, uint32_t n,
+                       uint32_t width, uint32_t dna_len, uint8_t *d_out, uint32_t *d_qlen, const void *d_tab) {
+  QfArgs a{d_raw, reinterpret_cast<const unsigned long long *>(d_off), d_len, n, width, dna_len, d_out,
+           static_cast<const QfTables *>(d_tab), d_qlen};
+  // one wave per record / read, grid-stride over at most 64 K blocks
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + kQfWaves - 1) / kQfWaves, 65536);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (dna_len && d_qlen) hipLaunchKernelGGL(k_qry_frames<true>, dim3(blocks), dim3(kQfBlock), 0, st, a);
+  else if (dna_len) hipLaunchKernelGGL(k_qry_frames<false>, dim3(blocks), dim3(kQfBlock), 0, st, a);
+  else if (d_qlen) hipLaunchKernelGGL(k_qry_protein<true>, dim3(blocks), dim3(kQfBlock), 0, st, a);
+  else hipLaunchKernelGGL(k_qry_protein<false>, dim3(blocks), dim3(kQfBlock), 0, st, a);
+  QF_CHECK(hipGetLastError());
+}
 
 void FormatQueriesDevice(const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets, const uint32_t *lengths,
                          uint32_t n, uint32_t width, uint32_t dna_len, uint8_t *records, int device,
@@ -184,14 +232,9 @@ void FormatQueriesDevice(const uint8_t *raw, uint64_t raw_len, const uint64_t *o
   QF_CHECK(hipMemcpyAsync(d_len.p, lengths, 4ull * n, hipMemcpyHostToDevice, st));
   const QfTables tables = MakeTables();
   QF_CHECK(hipMemcpyAsync(d_tab.p, &tables, sizeof(tables), hipMemcpyHostToDevice, st));
-  QfArgs a{d_raw.as<uint8_t>(), d_off.as<unsigned long long>(), d_len.as<uint32_t>(), n, width, dna_len,
-           d_out.as<uint8_t>(), d_tab.as<QfTables>()};
-  // one wave per record / read, grid-stride over at most 64 K blocks
-  const uint32_t blocks = (uint32_t)std::min<uint64_t>((n + kQfWaves - 1) / kQfWaves, 65536);
   QF_CHECK(hipEventRecord(e0, st));
-  if (dna_len) hipLaunchKernelGGL(k_qry_frames, dim3(blocks), dim3(kQfBlock), 0, st, a);
-  else hipLaunchKernelGGL(k_qry_protein, dim3(blocks), dim3(kQfBlock), 0, st, a);
-  QF_CHECK(hipGetLastError());
+  LaunchQueryFormat(st, d_raw.as<uint8_t>(), d_off.as<uint64_t>(), d_len.as<uint32_t>(), n, width, dna_len,
+                    d_out.as<uint8_t>(), nullptr, d_tab.p);
   QF_CHECK(hipEventRecord(e1, st));
   QF_CHECK(hipMemcpyAsync(records, d_out.p, nout * width, hipMemcpyDeviceToHost, st));
   QF_CHECK(hipStreamSynchronize(st));

@@ -119,6 +119,11 @@ class GhostmStats(ctypes.Structure):
         ("traceback_path_launches", c_uint64),
         ("traceback_path_cells", c_uint64),
         ("traceback_path_dir_bytes", c_uint64),
+        ("seconds_query_format", ctypes.c_double),
+        ("query_format_launches", c_uint64),
+        ("query_sets", c_uint64),
+        ("seconds_query_read", ctypes.c_double),
+        ("seconds_query_load", ctypes.c_double),
     ]
 
     def as_dict(self) -> dict:
@@ -169,6 +174,14 @@ SIGNATURES = {
     "GhostmReadScoreMatrix": (c_int, [c_char_p, POINTER(c_int)]),
     "GhostmLengthAdjustment": (c_int, [c_float, c_float, c_float, c_float, c_int, c_uint32, c_int, POINTER(c_int)]),
     "GhostmSessionCreate": (c_void_p, [c_int, POINTER(c_char_p)]),
+    "GhostmSessionCreateDb": (c_void_p, [c_int, POINTER(c_char_p)]),
+    "GhostmSessionSetQueries": (c_int, [c_void_p, POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_char_p,
+                                        c_uint64, c_uint32, c_uint32, c_int, c_uint32]),
+    "GhostmSessionSetQueriesFasta": (c_int, [c_void_p, c_char_p, c_uint32, c_int, c_uint32, POINTER(c_uint64)]),
+    "GhostmSessionSetOutputFile": (c_int, [c_void_p, c_char_p]),
+    "GhostmSessionQueryLengths": (c_size_t, [c_void_p, u32p, c_size_t]),
+    "GhostmSessionQueryRecords": (c_size_t, [c_void_p, c_uint32, POINTER(ctypes.c_uint8), c_size_t]),
+    "GhostmQueryChunkCuts": (ctypes.c_int64, [u32p, c_uint64, c_uint32, c_int, POINTER(c_uint64), c_uint64]),
     "GhostmSessionCreateShard": (c_void_p, [c_int, POINTER(c_char_p), c_int, c_int]),
     "GhostmSessionCreateShardEx": (c_void_p, [c_int, POINTER(c_char_p), c_int, c_int, c_void_p, c_void_p]),
     "GhostmSessionShardRange": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),
@@ -187,6 +200,7 @@ SIGNATURES = {
     "GhostmSessionStatsSized": (c_size_t, [c_void_p, POINTER(GhostmStats), c_size_t]),
     "GhostmSessionDestroy": (None, [c_void_p]),
     "GhostmAlignMain": (c_int, [c_int, POINTER(c_char_p)]),
+    "GhostmSearchMain": (c_int, [c_int, POINTER(c_char_p)]),
 }
 
 _lib = None

@@ -314,6 +314,15 @@ typedef struct GhostmStats {
   uint64_t traceback_path_launches; /* batches of hits (one fill and one walk launch each) */
   uint64_t traceback_path_cells;    /* sum over its DPs of L x processed columns */
   uint64_t traceback_path_dir_bytes; /* direction-buffer bytes its batches addressed */
+  double seconds_query_format;      /* the resident query formatting (k_qry_protein / k_qry_frames with the
+                                       record lengths, device time) of the last GhostmSessionSetQueries*; 0 for
+                                       a query set read from formatted files */
+  uint64_t query_format_launches;   /* ... its launches (one per query chunk) */
+  uint64_t query_sets;              /* GhostmSessionSetQueries* calls that replaced the set, since creation */
+  double seconds_query_read;        /* ... of the last one, host wall clock: reading the FASTA file and cutting
+                                       it into chunks (0 for GhostmSessionSetQueries) */
+  double seconds_query_load;        /* ... packing the letters, the names and name groups, the staged upload and
+                                       the lengths' read-back, without seconds_query_format */
 } GhostmStats;
 
 /* Session: parse `aln` options exactly like the reference (getopt string
@@ -321,6 +330,60 @@ typedef struct GhostmStats {
  * load every query and DB chunk and make them resident on the device given by
  * -D (default 0). Returns NULL on error. */
 void *GhostmSessionCreate(int argc, char **argv);
+
+/* A database session: `aln`'s options without -i, -S and -L (giving one is an
+ * error); every DB chunk is loaded and made resident, with no queries.
+ * GhostmSessionRun before any query set gives empty output and no hits. The
+ * queries come from GhostmSessionSetQueries / GhostmSessionSetQueriesFasta, any
+ * number of times: many read sets against one resident database. Returns NULL
+ * on error. */
+void *GhostmSessionCreateDb(int argc, char **argv);
+
+/* Replaces the session's query set by n records given as letters: record r is
+ * raw[offsets[r] .. offsets[r] + lengths[r]), names holds the n names, each
+ * terminated by '\n'. width is given as `qry -l`, dna as `qry -t d`, chunk_mb
+ * as `qry -L` (0: qry's default). Afterwards the session holds what a session
+ * created with -i P would hold after `ghostm qry -i <that FASTA> -o P -l width
+ * [-t d] -L chunk_mb`: the same chunk cuts (the halved limit for DNA), the same
+ * width (a third for DNA, at most 127), DNA reads cut or padded to their
+ * chunk's first read length and translated in six frames under the read's name,
+ * records cut at the width. The letters are coded on the device straight into
+ * the resident chunks; only the records' lengths come back. The results of the
+ * previous run are dropped and the old chunks' device memory is kept for
+ * re-use; the DB chunks, the matrix and the options are untouched. Works on
+ * any unsharded session; fails on a shard session and on null arguments,
+ * which leaves the session as it was (as does a record outside the letter
+ * buffer or a file that cannot be opened); after a failure while the set is
+ * being loaded the session holds no queries. Returns 0 on success. */
+int GhostmSessionSetQueries(void *session, const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets,
+                            const uint32_t *lengths, const char *names, uint64_t names_len, uint32_t n,
+                            uint32_t width, int dna, uint32_t chunk_mb);
+
+/* The same from a FASTA file, read as `ghostm qry` reads it. cut_records (may
+ * be NULL) receives the number of output records over the width, for each of
+ * which qry prints a warning; the library prints nothing. */
+int GhostmSessionSetQueriesFasta(void *session, const char *path, uint32_t width, int dna, uint32_t chunk_mb,
+                                 uint64_t *cut_records);
+
+/* The -o path of later GhostmSessionRunToFile and GhostmSessionWrite calls. */
+int GhostmSessionSetOutputFile(void *session, const char *path);
+
+/* The length `aln` prints for every query record (index of the last non-X code
+ * + 1, at least 1), over the session's chunks in order; the NULL/cap convention
+ * of GhostmSessionHits. */
+size_t GhostmSessionQueryLengths(void *session, uint32_t *qlen, size_t cap);
+
+/* The coded records of query chunk `chunk` (the bytes of its .seq file) copied
+ * back from the device; same convention, (size_t)-1 on error. */
+size_t GhostmSessionQueryRecords(void *session, uint32_t chunk, uint8_t *codes, size_t cap);
+
+/* qry's chunk cuts on their own (host only, no device): over n records of the
+ * given letter counts, with `qry -L chunk_mb` (0: the default) and -t d when
+ * dna. Chunk c is records [cuts[c], cuts[c + 1]). Returns the number of chunks
+ * (cuts[0..chunks] written while they fit cap entries), or -1 when a record
+ * alone is over the limit (qry's "too small max length"). */
+int64_t GhostmQueryChunkCuts(const uint32_t lengths[], uint64_t n, uint32_t chunk_mb, int dna, uint64_t cuts[],
+                             uint64_t cap);
 
 /* Multi-GPU (the reference has no multi-GPU path, common.h:37):
  * one process per GPU, each opening a shard session. The query set selected by
@@ -448,6 +511,15 @@ void GhostmSessionDestroy(void *session);
 /* `ghostm aln ...` end to end (create + run + write + destroy). Exit status like
  * the reference CLI: errors are printed and 0 is still returned (main.cpp:116-121). */
 int GhostmAlignMain(int argc, char **argv);
+
+/* `ghostm search [aln options except -i -o -S -L] [-q d|p] [-w maxLength]
+ * [-c chunkSizeMB] -d database q1.fasta out1 [q2.fasta out2 ...]`: one database
+ * session; for each pair the queries are set from the FASTA file (-q, -w, -c as
+ * qry's -t, -l, -L; qry's warnings on stderr) and searched into the output
+ * file, which equals `ghostm qry` + `ghostm aln` on that FASTA. Wrong usage (no
+ * pairs, an odd number of positionals, -i, -o, -S or -L) returns 1 before any
+ * device call; errors are printed and 0 returned, as GhostmAlignMain. */
+int GhostmSearchMain(int argc, char **argv);
 
 #ifdef __cplusplus
 }
