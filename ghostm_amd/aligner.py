@@ -55,6 +55,19 @@ def cigar(ops) -> str:
     return "".join(f"{int(w) >> 4}{PATH_OPS[int(w) & 3]}" for w in ops)
 
 
+# GhostmHitRows: one per hit; the hit's 3 * columns bytes (query row, midline,
+# subject row) are rows[rows_offset : rows_offset + 3 * columns]
+HIT_ROWS_DTYPE = np.dtype([("query_record", "<u4"), ("columns", "<u4"), ("identities", "<u4"), ("positives", "<u4"),
+                           ("gap_residues", "<u4"), ("rescore", "<i4"), ("rows_offset", "<u8")])
+
+
+def rows_of(rec, rows, h) -> tuple[bytes, bytes, bytes]:
+    """(query row, midline, subject row) of hit h of a (rec, rows) pair."""
+    o, n = int(rec["rows_offset"][h]), int(rec["columns"][h])
+    b = bytes(rows[o:o + 3 * n])
+    return b[:n], b[n:2 * n], b[2 * n:]
+
+
 class GhostmError(RuntimeError):
     pass
 
@@ -135,6 +148,41 @@ def query_chunk_cuts(lengths, chunk_mb: int = 0, dna: bool = False) -> np.ndarra
     if n < 0:
         raise GhostmError(native.last_error())
     return cuts[: n + 1]
+
+
+def path_rows_host(query_seqs, L, db, score_matrix, query_ids, rec, ops, open_gap=-11, extend_gap=-1):
+    """The host model of the aligned rows (GhostmPathRowsHost; no device):
+    query_seqs = the chunk's records of L codes, db = the chunk's residues, rec =
+    HIT_PATH_DTYPE records with s_start absolute in the chunk, ops = the words
+    they index. Returns (records[HIT_ROWS_DTYPE], rows[uint8])."""
+    lib = native.load()
+    qs = np.ascontiguousarray(query_seqs, dtype=np.uint8).reshape(-1)
+    dbs = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
+    m = np.ascontiguousarray(score_matrix, dtype=np.int32).reshape(-1)
+    qid = np.ascontiguousarray(query_ids, dtype=np.uint32)
+    p = np.ascontiguousarray(rec, dtype=HIT_PATH_DTYPE)
+    w = np.ascontiguousarray(ops, dtype=np.uint32)
+    if m.size != 32 * 32 or L <= 0 or qs.size % L or qid.shape != p.shape:
+        raise ValueError("path_rows_host: bad argument shapes")
+    n = len(qid)
+    out = np.zeros(n, dtype=HIT_ROWS_DTYPE)
+    u8p, u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+
+    def call(rows, cap, used):
+        rc = lib.GhostmPathRowsHost(
+            qs.ctypes.data_as(u8p), qs.size // L, L, dbs.ctypes.data_as(u8p), dbs.size,
+            m.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), n, qid.ctypes.data_as(u32p),
+            p.ctypes.data_as(ctypes.POINTER(native.GhostmHitPath)), w.ctypes.data_as(u32p), w.size, L, open_gap,
+            extend_gap, out.ctypes.data_as(ctypes.POINTER(native.GhostmHitRows)), rows, cap, ctypes.byref(used))
+        if rc != 0:
+            raise GhostmError(native.last_error())
+
+    used = ctypes.c_size_t(0)
+    call(None, 0, used)  # the size needed
+    rows = np.zeros(used.value, dtype=np.uint8)
+    if used.value:
+        call(rows.ctypes.data_as(u8p), used.value, used)
+    return out, rows
 
 
 class Aligner:
@@ -341,6 +389,27 @@ class Session:
         if m:
             lib.GhostmSessionPathOps(self._h, ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), m)
         return rec, ops
+
+    def hits_rows(self) -> tuple[np.ndarray, np.ndarray]:
+        """(records, rows): one HIT_ROWS_DTYPE record per hit of hits()
+        (GhostmSessionHitsRows) and the row bytes they index
+        (GhostmSessionRowBytes), after a run with any -y. rows_of(rec, rows, h)
+        is hit h's (query row, midline, subject row)."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        n = lib.GhostmSessionHitsRows(self._h, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        rec = np.zeros(n, dtype=HIT_ROWS_DTYPE)
+        if n:
+            lib.GhostmSessionHitsRows(self._h, rec.ctypes.data_as(ctypes.POINTER(native.GhostmHitRows)), n)
+        m = lib.GhostmSessionRowBytes(self._h, None, 0)
+        if m == bad:
+            raise GhostmError(native.last_error())
+        rows = np.zeros(m, dtype=np.uint8)
+        if m:
+            lib.GhostmSessionRowBytes(self._h, rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), m)
+        return rec, rows
 
     def device_hits(self, device="cuda"):
         """The hit records as a torch uint8 tensor on this session's GPU (32 bytes

@@ -222,7 +222,7 @@ AlignerOptions ParseAlignerOptions(int argc, char **argv) {
   // small inputs); the oracle honours the same variable
   if (const char *e = getenv("GHOSTM_MAX_LIST_OVERRIDE")) o.max_list_length = (uint32_t)strtoul(e, nullptr, 10);
   o.matrix = ReadScoreMatrix(matrix_file);
-  if (o.output_style == 0 || o.output_style == 6 || o.output_style == 7) {  // 6, 7: BLAST-tabular, style 0's E-value and bit score
+  if (o.output_style == 0 || (o.output_style >= 6 && o.output_style <= 9)) {  // 6 to 9: style 0's E-value and bit score
     // extension: GHOSTM_KARLIN=ungapped prices combinations the
     // reference's table lacks with the matrix's ungapped ideal parameters
     // (karlin_params.cpp); unset, they throw as the reference does
@@ -1476,7 +1476,7 @@ static size_t StreamPiecesPerWorker() {
 const LineFormat &Session::Format() {
   // -y 6 formats style-0 lines first: FormatTabular takes their identity,
   // E-value and bit-score bytes
-  const bool tabular = opt_.output_style == 6 || opt_.output_style == 7;
+  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 9;
   if (!format_) format_.reset(new LineFormat(tabular ? 0 : opt_.output_style, opt_.karlin, 4095));
   return *format_;
 }
@@ -1708,6 +1708,148 @@ void Session::FormatPathTabular() {
   joined_valid_ = false;
 }
 
+// The aligned rows of every final hit (HitsRows): the hits' column counts give
+// every hit its place in hit order, then one PathRows call per (query chunk, DB
+// chunk) writes the bytes there; the paths' subject coordinates are made
+// absolute in the chunk again.
+const std::vector<GhostmHitRows> &Session::HitsRows() {
+  if (hits_rows_valid_) return hits_rows_;
+  const std::vector<GhostmHitPath> &path = HitsPath();
+  const std::vector<GhostmHit> &hits = Hits();
+  hits_rows_.assign(hits.size(), GhostmHitRows{0, 0, 0, 0, 0, 0, 0});
+  std::vector<uint64_t> place(hits.size());
+  uint64_t total = 0;
+  for (size_t h = 0; h < hits.size(); ++h) {
+    uint64_t cols = 0;
+    for (uint32_t r = 0; r < path[h].n_runs; ++r) cols += path_ops_[path[h].ops_offset + r] >> 4;
+    place[h] = total;
+    total += 3 * cols;
+  }
+  row_bytes_.assign(total, 0);
+  std::vector<std::vector<size_t>> groups(queries_.size() * dbs_.size());
+  for (size_t h = 0; h < hits.size(); ++h) groups[hit_source_[h].qi * dbs_.size() + hit_source_[h].di].push_back(h);
+  DeviceModule &dev = DeviceModule::Get();
+  const DeviceTimes before = dev.times();
+  std::vector<uint32_t> qid;
+  std::vector<uint64_t> dst;
+  std::vector<GhostmHitPath> rec;
+  std::vector<GhostmHitRows> out;
+  for (size_t qi = 0; qi < queries_.size(); ++qi) {
+    for (size_t di = 0; di < dbs_.size(); ++di) {
+      const std::vector<size_t> &items = groups[qi * dbs_.size() + di];
+      if (items.empty()) continue;
+      qid.clear();
+      dst.clear();
+      rec.clear();
+      for (size_t h : items) {
+        GhostmHitPath p = path[h];
+        const uint32_t pos = dbs_[di].chunk.starts[hits[h].db_id - dbs_[di].global_base];
+        p.s_start += pos;
+        p.s_end += pos;
+        qid.push_back(hit_source_[h].query);
+        dst.push_back(place[h]);
+        rec.push_back(p);
+      }
+      out.resize(items.size());
+      dev.PathRows(queries_[qi].dev, dbs_[di].dev, (uint32_t)items.size(), qid.data(), rec.data(), path_ops_.data(),
+                   path_ops_.size(), opt_.open_gap, opt_.extend_gap, queries_[qi].global_base, out.data(),
+                   row_bytes_.data(), row_bytes_.size(), dst.data());
+      for (size_t k = 0; k < items.size(); ++k) hits_rows_[items[k]] = out[k];
+    }
+  }
+  const DeviceTimes &after = dev.times();
+  stats_.seconds_path_rows += after.path_rows - before.path_rows;
+  stats_.path_rows_launches += after.path_rows_launches - before.path_rows_launches;
+  stats_.path_rows_columns += after.path_rows_columns - before.path_rows_columns;
+  stats_.path_rows_bytes += after.path_rows_bytes - before.path_rows_bytes;
+  hits_rows_valid_ = true;
+  return hits_rows_;
+}
+
+const std::vector<uint8_t> &Session::RowBytes() {
+  HitsRows();
+  return row_bytes_;
+}
+
+// -y 8 and -y 9, from the -y 7 text FormatPathTabular left in the pieces (one
+// line per hit, thirteen columns) and the hits' rows. -y 8 appends positives,
+// the query row and the subject row to the line. -y 9 writes a block per hit:
+// '#' and the first fourteen columns, then the three rows between their
+// one-based first and last coordinates (columns 7 to 10 of the line), then an
+// empty line.
+void Session::FormatRows() {
+  const std::vector<GhostmHitRows> &rows = HitsRows();
+  const std::vector<GhostmHitPath> &path = hits_path_;
+  const std::vector<uint8_t> &bytes = row_bytes_;
+  const bool pairwise = opt_.output_style == 9;
+  struct Piece {
+    std::string *text;
+    size_t first, n;
+  };
+  std::vector<Piece> pieces;
+  size_t at = 0;
+  for (size_t k = 0; k < used_parts_; ++k)
+    for (size_t t = 0; t < parts_[k].text.size(); ++t) {
+      pieces.push_back(Piece{&parts_[k].text[t], at, parts_[k].hits[t].size()});
+      at += parts_[k].hits[t].size();
+    }
+  ParallelFor(pieces.size(), threads_, [&](size_t b, size_t e, unsigned) {
+    std::string out;
+    for (size_t pi = b; pi < e; ++pi) {
+      const std::string &in = *pieces[pi].text;
+      out.clear();
+      size_t need = in.size() + pieces[pi].n * 48;
+      for (size_t i = 0; i < pieces[pi].n; ++i) need += 3 * (size_t)rows[pieces[pi].first + i].columns;
+      out.reserve(need);
+      size_t pos = 0;
+      for (size_t i = 0; i < pieces[pi].n; ++i) {
+        const size_t nl = in.find('\n', pos);
+        if (nl == std::string::npos) throw Error("rows output: fewer lines than hits");
+        const GhostmHitRows &x = rows[pieces[pi].first + i];
+        const GhostmHitPath &p = path[pieces[pi].first + i];
+        const char *q = reinterpret_cast<const char *>(bytes.data() + x.rows_offset);
+        const size_t n = x.columns;
+        char num[16], *end;
+        if (pairwise) out.append("# ");
+        out.append(in, pos, nl - pos);
+        out.push_back('\t');
+        end = PutU32(num, x.positives);
+        out.append(num, (size_t)(end - num));
+        if (!pairwise) {
+          out.push_back('\t');
+          out.append(q, n);
+          out.push_back('\t');
+          out.append(q + 2 * n, n);
+          out.push_back('\n');
+        } else {
+          out.append("\nQuery\t");
+          end = PutU32(num, p.q_start + 1);
+          out.append(num, (size_t)(end - num));
+          out.push_back('\t');
+          out.append(q, n);
+          out.push_back('\t');
+          end = PutU32(num, p.q_end + 1);
+          out.append(num, (size_t)(end - num));
+          out.append("\n\t\t");
+          out.append(q + n, n);
+          out.append("\t\nSbjct\t");
+          end = PutU32(num, p.s_start + 1);
+          out.append(num, (size_t)(end - num));
+          out.push_back('\t');
+          out.append(q + 2 * n, n);
+          out.push_back('\t');
+          end = PutU32(num, p.s_end + 1);
+          out.append(num, (size_t)(end - num));
+          out.append("\n\n");
+        }
+        pos = nl + 1;
+      }
+      *pieces[pi].text = out;
+    }
+  });
+  joined_valid_ = false;
+}
+
 // -y 6: qseqid sseqid pident length mismatch gapopen qstart qend sstart send
 // evalue bitscore, tab-separated. Every piece holds the style-0 lines of its
 // hits (name, name, pident, length, matches, start, end, E-value, bits, each
@@ -1902,8 +2044,8 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  // -y 6 and -y 7 are written after the post-pass (HitsExt, HitsPath), not while the search runs
-  const bool tabular = opt_.output_style == 6 || opt_.output_style == 7;
+  // -y 6 to -y 9 are written after the post-pass (HitsExt, HitsPath, HitsRows), not while the search runs
+  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 9;
   if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
@@ -1944,6 +2086,10 @@ void Session::Run(bool stream_to_file) {
   hits_path_.clear();
   path_ops_.clear();
   hits_path_valid_ = false;
+  hits_rows_.clear();
+  row_bytes_.clear();
+  row_bytes_.shrink_to_fit();
+  hits_rows_valid_ = false;
   Format();  // built here, before any formatting task can need it
   dev.ResetRecords(HitCapacity());  // the most records the run can append
   records_on_device_ = true;
@@ -2012,8 +2158,9 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    if (opt_.output_style == 7) FormatPathTabular();
-    else FormatTabular();
+    if (opt_.output_style == 6) FormatTabular();
+    else FormatPathTabular();
+    if (opt_.output_style >= 8) FormatRows();
     if (stream_to_file) {
       WriteOutputFile();
       streamed_ = true;
@@ -2188,6 +2335,10 @@ void Session::DropQueries() {
   hits_path_.clear();
   path_ops_.clear();
   hits_path_valid_ = false;
+  hits_rows_.clear();
+  row_bytes_.clear();
+  row_bytes_.shrink_to_fit();
+  hits_rows_valid_ = false;
   dev.ResetRecords(0);
   records_on_device_ = true;
   streamed_ = false;

@@ -184,6 +184,14 @@ class Session {
   // makes them and the text.
   const std::vector<GhostmHitPath> &HitsPath();
   const std::vector<uint32_t> &PathOps();
+  // One GhostmHitRows per hit of Hits() and the row bytes they index, in hit
+  // order: a post-pass of DeviceModule::PathRows over HitsPath(), one call per
+  // (query chunk, DB chunk) that has hits, every hit's bytes landing at its
+  // place in hit order. query_record is the global index of the record
+  // HitsExt() resolved. Computed on first use, kept until the next run or the
+  // next query set. With -y 8 and -y 9 Run makes them and the text.
+  const std::vector<GhostmHitRows> &HitsRows();
+  const std::vector<uint8_t> &RowBytes();
   // Hit records of the last run in device memory (this session's GPU): copies
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
@@ -281,6 +289,10 @@ class Session {
   void FormatTabular();
   // -y 7: the same with columns 3 to 10 taken from the hit's path, and its CIGAR
   void FormatPathTabular();
+  // -y 8: the -y 7 line plus positives, the query row and the subject row;
+  // -y 9: the pairwise view (a '#' line of the first fourteen columns, the
+  // three rows, an empty line). Both rewrite the -y 7 text of FormatPathTabular.
+  void FormatRows();
 
   AlignerOptions opt_;
   uint64_t shard_begin_ = 0, shard_end_ = UINT64_MAX;  // query range over the loaded chunks
@@ -310,6 +322,9 @@ class Session {
   std::vector<GhostmHitPath> hits_path_;
   std::vector<uint32_t> path_ops_;
   bool hits_path_valid_ = false;
+  std::vector<GhostmHitRows> hits_rows_;
+  std::vector<uint8_t> row_bytes_;
+  bool hits_rows_valid_ = false;
   bool records_on_device_ = false;
   GhostmStats stats_{};
   unsigned threads_ = 1;

@@ -250,6 +250,34 @@ size_t GhostmSessionPathOps(void *s, uint32_t *ops, size_t cap) {
   }
 }
 
+size_t GhostmSessionHitsRows(void *s, GhostmHitRows *rec, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmHitRows> &h = static_cast<Session *>(s)->HitsRows();
+    if (!rec) return h.size();
+    const size_t n = std::min(cap, h.size());
+    std::memcpy(rec, h.data(), n * sizeof(GhostmHitRows));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionRowBytes(void *s, uint8_t *rows, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<uint8_t> &b = static_cast<Session *>(s)->RowBytes();
+    if (!rows) return b.size();
+    const size_t n = std::min(cap, b.size());
+    std::memcpy(rows, b.data(), n);
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
 size_t GhostmSessionDeviceHits(void *s, void *dst_device, size_t cap) {
   try {
     if (!s) throw Error("null session");

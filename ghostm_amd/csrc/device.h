@@ -18,6 +18,7 @@
 
 struct GhostmHitExt;  // include/ghostm_hip.h
 struct GhostmHitPath;
+struct GhostmHitRows;
 
 namespace ghostm {
 
@@ -100,6 +101,8 @@ struct DeviceTimes {
   double traceback_path = 0;                      // the alignment paths (k_tb_path_fill + k_tb_path_walk): seconds,
   uint64_t traceback_path_launches = 0, traceback_path_cells = 0;  // batches, L x processed columns,
   uint64_t traceback_path_dir_bytes = 0;          // direction-buffer bytes of the batches
+  double path_rows = 0;                           // the aligned rows (k_path_rows): seconds,
+  uint64_t path_rows_launches = 0, path_rows_columns = 0, path_rows_bytes = 0;  // batches, columns, row bytes
 };
 
 class DeviceModule {
@@ -248,6 +251,23 @@ class DeviceModule {
   void TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const uint32_t *db_end,
                      const uint32_t *db_start_in, uint32_t base_search_length, int open, int ext,
                      GhostmHitPath *rec, std::vector<uint32_t> *ops);
+
+  // The aligned residue rows of n hits (kern::k_path_rows): hit i lies in query
+  // record qid[i]; rec[i] gives q_start, s_start (absolute in the chunk) and its
+  // words in ops[ops_len]. Everything is checked first (ValidatePathRows,
+  // path_rows.h; throws with the reason before any upload or launch, the
+  // outputs untouched). out[n] (may be null) receives the records, with
+  // query_record = qid[i] + record_base. rows (may be null: counts only)
+  // receives hit i's 3 * columns bytes at dst_off[i], or, with dst_off null, the
+  // hits' bytes one after the other from 0; out[i].rows_offset is that offset.
+  // Throws ("rows_cap") when a hit's bytes would end past rows_cap. Returns the
+  // hits' bytes together. The hits run in hit order in batches whose row bytes
+  // fit GHOSTM_ROWS_SCRATCH_MB (default 1024) and that hold at most
+  // GHOSTM_ROWS_BATCH_HITS hits. Adds its device time, batches, columns and
+  // bytes to times().
+  size_t PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const GhostmHitPath *rec,
+                  const uint32_t *ops, size_t ops_len, int open, int ext, uint32_t record_base,
+                  GhostmHitRows *out, uint8_t *rows, size_t rows_cap, const uint64_t *dst_off);
 
   DeviceTimes &times() {
     SettleSeedTime();

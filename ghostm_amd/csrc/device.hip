@@ -17,6 +17,7 @@
 #include "device.h"
 #include "formats.h"
 #include "kernels.h"
+#include "path_rows.h"
 #include "qformat.h"
 #include "score_tasks.h"
 
@@ -274,6 +275,8 @@ struct DeviceModule::Impl {
   // TraceBackPath: the hits' inputs, a batch's offsets / maxima / records / cell
   // counter, its direction strips, its run-length slots and their packed words
   DevBuf tb_path_in, tb_path_meta, tb_path_dir, tb_path_ops, tb_path_cmp;
+  // PathRows: a batch's per-hit inputs, its words, its counts and its row bytes
+  DevBuf path_rows_hit, path_rows_ops, path_rows_out, path_rows_buf;
   DevBuf tb_width, tb_ncols, tb_skey, tb_key, tb_order1, tb_order2, tb_sort, tb_pair_a, tb_pair_b, tb_best;
   int cus = 256;
   // K4 work
@@ -2388,12 +2391,113 @@ void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32
   }
 }
 
+size_t DeviceModule::PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const GhostmHitPath *rec,
+                              const uint32_t *ops, size_t ops_len, int open, int ext, uint32_t record_base,
+                              GhostmHitRows *out, uint8_t *rows, size_t rows_cap, const uint64_t *dst_off) {
+  Use();
+  Impl &I = *impl_;
+  if (n == 0) return 0;
+  // every index the kernel will use, checked here: nothing is uploaded or launched for a refused call
+  std::vector<uint32_t> columns;
+  const std::string why = ValidatePathRows(q->nseq, q->L, d->len, n, qid, rec, ops, ops_len, &columns);
+  if (!why.empty()) throw Error("path rows: " + why);
+  size_t total = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    const size_t b = 3 * (size_t)columns[k], at = dst_off ? (size_t)dst_off[k] : total;
+    if (rows && (at > rows_cap || b > rows_cap - at)) throw Error("path rows: the rows do not fit rows_cap");
+    total += b;
+  }
+  if (!out && !rows) return total;
+  const size_t budget = EnvSize("GHOSTM_ROWS_SCRATCH_MB", 1024) << 20;
+  const size_t max_hits = EnvSize("GHOSTM_ROWS_BATCH_HITS", SIZE_MAX);
+  std::vector<kern::PathRowsHit> hh;
+  std::vector<uint32_t> words, counts;
+  std::vector<uint8_t> stage;  // a batch's bytes on their way to dst_off
+  size_t done_bytes = 0;
+  for (uint32_t b0 = 0; b0 < n;) {
+    // hits [b0, b1): at least one, then as many as fit
+    uint32_t b1 = b0;
+    size_t bytes = 0, nwords = 0;
+    while (b1 < n && b1 - b0 < max_hits) {
+      const size_t sz = 3 * (size_t)columns[b1];
+      if (b1 > b0 && bytes + sz > budget) break;
+      bytes += sz;
+      nwords += rec[b1].n_runs;
+      ++b1;
+    }
+    const uint32_t m = b1 - b0;
+    hh.resize(m);
+    words.resize(nwords);
+    {
+      size_t wa = 0, ra = 0;
+      for (uint32_t s = 0; s < m; ++s) {
+        const GhostmHitPath &p = rec[b0 + s];
+        hh[s] = kern::PathRowsHit{qid[b0 + s], p.q_start, p.s_start, p.n_runs, columns[b0 + s], 0, wa, ra};
+        if (p.n_runs) memcpy(words.data() + wa, ops + p.ops_offset, (size_t)p.n_runs * 4);
+        wa += p.n_runs;
+        ra += 3 * (size_t)columns[b0 + s];
+      }
+    }
+    I.path_rows_hit.Reserve((size_t)m * sizeof(kern::PathRowsHit));
+    I.path_rows_ops.Reserve(std::max<size_t>(nwords, 1) * 4);
+    I.path_rows_out.Reserve((size_t)m * 16);
+    if (rows) I.path_rows_buf.Reserve(std::max<size_t>(bytes, 1));
+    HIP_CHECK(hipMemcpyAsync(I.path_rows_hit.p, hh.data(), (size_t)m * sizeof(kern::PathRowsHit), hipMemcpyHostToDevice,
+                             S(stream_)));
+    if (nwords) HIP_CHECK(hipMemcpyAsync(I.path_rows_ops.p, words.data(), nwords * 4, hipMemcpyHostToDevice, S(stream_)));
+    kern::PathRowsArgs a{};
+    a.qseq = q->seq.as<uint8_t>();
+    a.L = q->L;
+    a.db = d->Residues();
+    a.mat = I.mat_raw.as<int>();
+    a.hit = I.path_rows_hit.as<kern::PathRowsHit>();
+    a.n = m;
+    a.ops = I.path_rows_ops.as<uint32_t>();
+    a.open = open;
+    a.ext = ext;
+    a.rows = rows ? I.path_rows_buf.as<uint8_t>() : nullptr;
+    a.out = I.path_rows_out.as<uint32_t>();
+    const dim3 grid((m + kern::kTbBlock / 64 - 1) / (kern::kTbBlock / 64)), block(kern::kTbBlock);  // one wave per hit
+    HIP_CHECK(hipEventRecord(I.ev0, S(stream_)));
+    hipLaunchKernelGGL(kern::k_path_rows, grid, block, 0, S(stream_), a);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipEventRecord(I.ev1, S(stream_)));
+    counts.resize((size_t)m * 4);
+    HIP_CHECK(hipMemcpyAsync(counts.data(), a.out, (size_t)m * 16, hipMemcpyDeviceToHost, S(stream_)));
+    uint8_t *land = nullptr;
+    if (rows && bytes) {
+      if (dst_off) {
+        stage.resize(bytes);
+        land = stage.data();
+      } else {
+        land = rows + done_bytes;  // hit order: the batch's bytes are consecutive
+      }
+      HIP_CHECK(hipMemcpyAsync(land, a.rows, bytes, hipMemcpyDeviceToHost, S(stream_)));
+    }
+    HIP_CHECK(hipStreamSynchronize(S(stream_)));
+    times_.path_rows += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+    times_.path_rows_launches += 1;
+    times_.path_rows_columns += bytes / 3;
+    times_.path_rows_bytes += rows ? bytes : 0;
+    for (uint32_t s = 0; s < m; ++s) {
+      const uint32_t k = b0 + s;
+      const uint64_t at = dst_off ? dst_off[k] : done_bytes + hh[s].rows_off;
+      if (land && dst_off && columns[k]) memcpy(rows + at, land + hh[s].rows_off, 3 * (size_t)columns[k]);
+      const uint32_t *c = counts.data() + (size_t)s * 4;
+      if (out) out[k] = GhostmHitRows{qid[k] + record_base, columns[k], c[0], c[1], c[2], (int32_t)c[3], at};
+    }
+    done_bytes += bytes;
+    b0 = b1;
+  }
+  return total;
+}
+
 const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_amd/srchash.py)
 
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -2728,6 +2832,29 @@ int TraceBackPathGpu(uint32_t nhits, const uint32_t query_ids[], const uint32_t 
       if (words.size() > ops_cap) throw Error("TraceBackPathGpu: the operations do not fit ops_cap");
       std::copy(words.begin(), words.end(), ops);
     }
+    return 0;
+  } catch (std::exception &e) {
+    SetError(e.what());
+    return 1;
+  }
+}
+
+int PathRowsGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPath rec[], const uint32_t ops[],
+                size_t ops_len, uint32_t query_sequence_length, int open_gap, int extend_gap, GhostmHitRows out[],
+                uint8_t rows[], size_t rows_cap, size_t *rows_used) {
+  try {
+    if (nhits == 0) {
+      if (rows_used) *rows_used = 0;
+      return 0;
+    }
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    if (!r.query || !r.db) throw Error("SetQueryGpu/SetDbGpu not called");
+    if (query_sequence_length != r.query->L) throw Error("query shape differs from SetQueryGpu");
+    if (!query_ids || !rec) throw Error("PathRowsGpu: null hit arrays");
+    const size_t used = DeviceModule::Get().PathRows(r.query, r.db, nhits, query_ids, rec, ops, ops_len, open_gap,
+                                                     extend_gap, 0, out, rows, rows_cap, nullptr);
+    if (rows_used) *rows_used = used;
     return 0;
   } catch (std::exception &e) {
     SetError(e.what());

@@ -3267,6 +3267,126 @@ __global__ __launch_bounds__(kTbBlock) void k_tb_path_compact(TbPathArgs a) {
   for (uint32_t k = 0; k < n; ++k) dst[k] = src[k];
 }
 
+// ------------------------------------------------------------------ aligned residue rows
+// k_path_rows: the query row, the midline and the subject row of every hit's
+// path (GhostmHitRows), one wave per hit, lanes along the path's columns. The
+// hit's run-length words are taken 64 at a time, one per lane: three wave
+// scans give every run its first column, its first query residue and its first
+// subject residue, carried from one group of 64 runs to the next. The columns
+// of a group are then taken 64 at a time: a lane finds its column's run with a
+// six-step search over the lanes' first columns (ds_bpermute), loads its two
+// codes and stores its three bytes, so each row is written as consecutive bytes
+// by consecutive lanes and the codes are read the same way. The counts and the
+// rescore are wave sums; lane 0 writes them. The host has checked every index
+// (ValidatePathRows, path_rows.h): a word has a length and no bits 2-3, the
+// residues lie inside the query record and the DB chunk, the words inside ops.
+struct PathRowsHit {
+  uint32_t qid, q_start, s_start, n_runs;
+  uint32_t columns, pad;
+  unsigned long long ops_off;   // first word of the hit in ops
+  unsigned long long rows_off;  // first byte of the hit's 3 * columns bytes in rows
+};
+struct PathRowsArgs {
+  const uint8_t *qseq;
+  uint32_t L;
+  const uint8_t *db;
+  const int *mat;  // M[db code * 32 + query code]
+  const PathRowsHit *hit;
+  uint32_t n;
+  const uint32_t *ops;
+  int open, ext;
+  uint8_t *rows;   // null: the counts only
+  uint32_t *out;   // per hit: identities, positives, gap_residues, rescore
+};
+
+__global__ __launch_bounds__(kTbBlock) void k_path_rows(PathRowsArgs a) {
+  GHOSTM_POISON_LDS();
+  __shared__ int s_mat[32 * 32];
+  __shared__ uint8_t s_let[32];
+  for (uint32_t e = threadIdx.x; e < 32 * 32; e += kTbBlock) s_mat[e] = a.mat[e];
+  if (threadIdx.x < 32) s_let[threadIdx.x] = threadIdx.x < 25 ? (uint8_t)"ARNDCQEGHILKMFPSTWYVBJZX*"[threadIdx.x] : (uint8_t)'?';
+  __syncthreads();
+
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t h = blockIdx.x * (kTbBlock / 64) + (threadIdx.x >> 6);
+  if (h >= a.n) return;  // the whole wave
+  const PathRowsHit hit = a.hit[h];
+  const uint8_t *qs = a.qseq + (size_t)hit.qid * a.L;
+  const uint32_t *words = a.ops + hit.ops_off;
+  uint8_t *row_q = a.rows ? a.rows + hit.rows_off : nullptr;
+  uint32_t col0 = 0, q0 = hit.q_start, s0 = hit.s_start;  // of the group's first run
+  uint32_t ident = 0, posit = 0, gaps = 0;
+  int score = 0;
+  for (uint32_t r0 = 0; r0 < hit.n_runs; r0 += 64) {
+    const uint32_t w = r0 + lane < hit.n_runs ? words[r0 + lane] : 0u;  // past the last run: length 0
+    const uint32_t len = w >> 4, op = w & 3u;
+    uint32_t tc, tq, ts;
+    const uint32_t c = col0 + WaveExclusiveScan(len, &tc);
+    const uint32_t q = q0 + WaveExclusiveScan(op != 3u ? len : 0u, &tq);
+    const uint32_t s = s0 + WaveExclusiveScan(op != 2u ? len : 0u, &ts);
+    const uint32_t c1 = col0 + tc;
+    for (uint32_t base = col0; base < c1; base += 64) {
+      const bool on = base + lane < c1;
+      const uint32_t col = on ? base + lane : c1 - 1;
+      // the last lane whose run begins at or before col (the lanes past the last run begin at c1)
+      uint32_t r = 0;
+#pragma unroll
+      for (uint32_t step = 32; step; step >>= 1) {
+        const uint32_t v = (uint32_t)__shfl((int)c, (int)(r + step));
+        if (v <= col) r += step;
+      }
+      const uint32_t k = col - (uint32_t)__shfl((int)c, (int)r);
+      const uint32_t rq = (uint32_t)__shfl((int)q, (int)r), rs = (uint32_t)__shfl((int)s, (int)r);
+      const uint32_t rop = (uint32_t)__shfl((int)op, (int)r);
+      if (on) {
+        uint32_t qc = 0, sc = 0;
+        uint8_t ql = '-', sl = '-', ml = ' ';
+        if (rop != 3u) {
+          qc = qs[rq + k];
+          ql = qc < 25u ? s_let[qc] : (uint8_t)'?';
+        }
+        if (rop != 2u) {
+          sc = a.db[rs + k];
+          sl = sc < 25u ? s_let[sc] : (uint8_t)'?';
+        }
+        if (rop < 2u) {
+          const int m = s_mat[(sc & 31u) * 32 + (qc & 31u)];
+          score += m;
+          posit += m > 0;
+          ident += rop == 0u;
+          if (rop == 0u) ml = ql;
+          else if (m > 0) ml = '+';
+        } else {
+          ++gaps;
+          score += k == 0 ? a.open : a.ext;
+        }
+        if (row_q) {
+          row_q[col] = ql;
+          row_q[(size_t)hit.columns + col] = ml;
+          row_q[2 * (size_t)hit.columns + col] = sl;
+        }
+      }
+    }
+    col0 = c1;
+    q0 += tq;
+    s0 += ts;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    ident += __shfl_xor(ident, d);
+    posit += __shfl_xor(posit, d);
+    gaps += __shfl_xor(gaps, d);
+    score += __shfl_xor(score, d);
+  }
+  if (lane == 0) {
+    uint32_t *o = a.out + 4 * (size_t)h;
+    o[0] = ident;
+    o[1] = posit;
+    o[2] = gaps;
+    o[3] = (uint32_t)score;
+  }
+}
+
 // FRAME (FINAL only, round 6): every key of column j is stored with FR_j =
 // j * (-ext) added to its h field, as K2's column frame, so E's extension needs
 // no add: E'(j) = max3(A', Bfi(HIGH, E'(j-1), A'), zero'(j)) with A' = K'(j-1) +

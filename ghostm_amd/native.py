@@ -66,6 +66,22 @@ class GhostmHitPath(ctypes.Structure):
     ]
 
 
+class GhostmHitRows(ctypes.Structure):
+    """the aligned rows of one hit (32 bytes): the record the path lies in, its
+    counts and its 3 * columns bytes rows[rows_offset:] (query row, midline,
+    subject row)."""
+
+    _fields_ = [
+        ("query_record", c_uint32),
+        ("columns", c_uint32),
+        ("identities", c_uint32),
+        ("positives", c_uint32),
+        ("gap_residues", c_uint32),
+        ("rescore", ctypes.c_int32),
+        ("rows_offset", c_uint64),
+    ]
+
+
 class GhostmStats(ctypes.Structure):
     _fields_ = [
         ("seconds_total", ctypes.c_double),
@@ -124,6 +140,10 @@ class GhostmStats(ctypes.Structure):
         ("query_sets", c_uint64),
         ("seconds_query_read", ctypes.c_double),
         ("seconds_query_load", ctypes.c_double),
+        ("seconds_path_rows", ctypes.c_double),
+        ("path_rows_launches", c_uint64),
+        ("path_rows_columns", c_uint64),
+        ("path_rows_bytes", c_uint64),
     ]
 
     def as_dict(self) -> dict:
@@ -166,6 +186,12 @@ SIGNATURES = {
     "GhostmTraceBackPathHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, POINTER(ctypes.c_uint8), c_uint32,
                                         POINTER(c_int), c_uint32, u32p, u32p, u32p, c_uint32, c_int, c_int,
                                         POINTER(GhostmHitPath), u32p, c_size_t, POINTER(c_size_t)]),
+    "PathRowsGpu": (c_int, [c_uint32, u32p, POINTER(GhostmHitPath), u32p, c_size_t, c_uint32, c_int, c_int,
+                            POINTER(GhostmHitRows), POINTER(ctypes.c_uint8), c_size_t, POINTER(c_size_t)]),
+    "GhostmPathRowsHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, POINTER(ctypes.c_uint8), c_uint32,
+                                   POINTER(c_int), c_uint32, u32p, POINTER(GhostmHitPath), u32p, c_size_t, c_uint32,
+                                   c_int, c_int, POINTER(GhostmHitRows), POINTER(ctypes.c_uint8), c_size_t,
+                                   POINTER(c_size_t)]),
     "GhostmBuildIndexGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, u32p, u32p, u32p, c_int,
                                     POINTER(c_float)]),
     "GhostmFormatQueriesGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_uint32,
@@ -195,6 +221,8 @@ SIGNATURES = {
     "GhostmSessionHitsExt": (c_size_t, [c_void_p, POINTER(GhostmHitExt), c_size_t]),
     "GhostmSessionHitsPath": (c_size_t, [c_void_p, POINTER(GhostmHitPath), c_size_t]),
     "GhostmSessionPathOps": (c_size_t, [c_void_p, u32p, c_size_t]),
+    "GhostmSessionHitsRows": (c_size_t, [c_void_p, POINTER(GhostmHitRows), c_size_t]),
+    "GhostmSessionRowBytes": (c_size_t, [c_void_p, POINTER(ctypes.c_uint8), c_size_t]),
     "GhostmSessionDeviceHits": (c_size_t, [c_void_p, c_void_p, c_size_t]),
     "GhostmSessionStats": (c_int, [c_void_p, POINTER(GhostmStats)]),
     "GhostmSessionStatsSized": (c_size_t, [c_void_p, POINTER(GhostmStats), c_size_t]),

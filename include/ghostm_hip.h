@@ -195,6 +195,66 @@ int GhostmTraceBackPathHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, 
                             int extend_gap, GhostmHitPath rec[], uint32_t ops[], size_t ops_cap,
                             size_t *ops_used);
 
+/* The alignment of one hit as text: its 3 * columns bytes at rows[rows_offset]
+ * are the query row, the midline and the subject row, each columns bytes long
+ * and without a terminator. The letter of residue code c is
+ * "ARNDCQEGHILKMFPSTWYVBJZX*"[c]; codes of 25 and above give '?'. A '=' or 'X'
+ * column holds both letters, an 'I' column the query letter and '-' in the
+ * subject row, a 'D' column '-' in the query row and the subject letter. The
+ * midline holds the query letter in a '=' column, '+' in an 'X' column whose
+ * matrix entry M[db code * 32 + query code] is > 0, and a space elsewhere (the
+ * matrix is indexed with the codes' low five bits). */
+typedef struct GhostmHitRows {   /* 32 bytes */
+  uint32_t query_record;  /* the query record the path lies in: stage level = query_ids[i]; session level =
+                             its global index over the session's query chunks in order. For a DNA set,
+                             query_record % 6 is the frame: 0..2 forward +0 +1 +2, 3..5 reverse complement
+                             +0 +1 +2 */
+  uint32_t columns;       /* the path's columns: the sum of its words' lengths */
+  uint32_t identities;    /* '=' columns */
+  uint32_t positives;     /* '=' and 'X' columns whose matrix entry is > 0 (an identical pair with a
+                             non-positive score, such as X/X, is not one) */
+  uint32_t gap_residues;  /* 'I' and 'D' columns */
+  int32_t rescore;        /* the pair columns' matrix entries plus, per word of 'I' or 'D', open_gap for its
+                             first column and extend_gap for every further one (both negative); equals
+                             GhostmHitPath.score for a path TraceBackPathGpu made */
+  uint64_t rows_offset;   /* first byte of the hit's 3 * columns bytes in rows[] */
+} GhostmHitRows;
+
+/* The rows of every hit (kernel k_path_rows), stage level like TraceBackPathGpu
+ * (after SetQueryGpu and SetDbGpu): hit i lies in query record query_ids[i],
+ * rec[i] gives its first query row, its first subject position (absolute in
+ * the chunk) and its n_runs words at ops[ops_offset]; q_end, s_end and score
+ * are not read. Any well-formed path is accepted, not only one a traceback
+ * made. Record i belongs to hit i; the hits' bytes follow each other in hit
+ * order. rows == NULL: only *rows_used (the bytes needed) and out (may be NULL)
+ * are written. A path without words gives columns 0, counts 0 and no bytes.
+ * Everything is checked on the host before any upload or launch; a refused
+ * call leaves out, rows and *rows_used untouched and names its reason in
+ * GhostmGetLastError:
+ *   "ops"      ops_offset + n_runs > ops_len
+ *   "word"     a word with bits 2-3 set or a zero length
+ *   "bounds"   a path whose query residues run past query_sequence_length or
+ *              whose subject residues run past the resident DB chunk
+ *   "query"    a query_ids[i] outside the resident chunk
+ *   "rows_cap" rows_cap smaller than the bytes needed
+ * The row buffer is cut into batches of hits that fit GHOSTM_ROWS_SCRATCH_MB
+ * (default 1024) and hold at most GHOSTM_ROWS_BATCH_HITS hits (default: no
+ * limit); a batch holds at least one hit. */
+int PathRowsGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPath rec[],
+                const uint32_t ops[], size_t ops_len, uint32_t query_sequence_length,
+                int open_gap, int extend_gap, GhostmHitRows out[], uint8_t rows[],
+                size_t rows_cap, size_t *rows_used);
+
+/* The same on the host, with no device call (the model the kernel is checked
+ * against) and the same checks: query_seqs = nq records of L codes, db = the
+ * chunk's db_len residues, score_matrix = M[db code * 32 + query code];
+ * query_sequence_length must equal L. */
+int GhostmPathRowsHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, const uint8_t *db,
+                       uint32_t db_len, const int score_matrix[], uint32_t nhits,
+                       const uint32_t query_ids[], const GhostmHitPath rec[], const uint32_t ops[],
+                       size_t ops_len, uint32_t query_sequence_length, int open_gap, int extend_gap,
+                       GhostmHitRows out[], uint8_t rows[], size_t rows_cap, size_t *rows_used);
+
 /* The `db` formatter's k-mer index of one DB chunk, built on the GPU
  * (replaces DBCreator::ConstructIndex, db_creator.cpp:167-241).
  * seq[len] = the chunk's END-separated residues (.seq); seed = the index seed mask
@@ -323,6 +383,11 @@ typedef struct GhostmStats {
                                        it into chunks (0 for GhostmSessionSetQueries) */
   double seconds_query_load;        /* ... packing the letters, the names and name groups, the staged upload and
                                        the lengths' read-back, without seconds_query_format */
+  double seconds_path_rows;         /* the aligned-rows post-pass (k_path_rows, device time); 0 until -y 8, -y 9
+                                       or GhostmSessionHitsRows / GhostmSessionRowBytes asks for it */
+  uint64_t path_rows_launches;      /* batches of hits (one launch each) */
+  uint64_t path_rows_columns;       /* sum of the hits' columns */
+  uint64_t path_rows_bytes;         /* row bytes written: 3 x path_rows_columns */
 } GhostmStats;
 
 /* Session: parse `aln` options exactly like the reference (getopt string
@@ -458,7 +523,16 @@ int GhostmSessionRun(void *session);
  * (pident = 100 * matches / length, length, mismatch, gapopen = the I and D
  * runs, qstart, qend, sstart, send) taken from the hit's GhostmHitPath and a
  * thirteenth column, the extended CIGAR (for instance 31=1X2D40=); it too is
- * written at the end of the run. */
+ * written at the end of the run. -y 8 is the -y 7 line followed by three more
+ * columns from the hit's GhostmHitRows: positives, qseq (the query row) and
+ * sseq (the subject row), sixteen in all. -y 9 is a pairwise view, one block
+ * of five lines per hit:
+ *   # <the first fourteen -y 8 columns, tab-separated>
+ *   Query\t<qstart>\t<query row>\t<qend>
+ *   \t\t<midline>\t
+ *   Sbjct\t<sstart>\t<subject row>\t<send>
+ *   <empty line>
+ * Both price hits like -y 0 and are written at the end of the run. */
 int GhostmSessionRunToFile(void *session);
 
 /* Formatted output of the last run (reference WriteOutput/V1/V2 text). With
@@ -490,6 +564,18 @@ size_t GhostmSessionHitsExt(void *session, GhostmHitExt *ext, size_t cap);
  * GhostmSessionHitsExt resolved. */
 size_t GhostmSessionHitsPath(void *session, GhostmHitPath *rec, size_t cap);
 size_t GhostmSessionPathOps(void *session, uint32_t *ops, size_t cap);
+
+/* The GhostmHitRows of every hit of the last run (record i belongs to hit i)
+ * and the row bytes they index, in hit order; both with the NULL/cap
+ * convention of GhostmSessionHitsPath, (size_t)-1 on error. Works after a run
+ * with any -y and on shard sessions: computed on first use from the paths of
+ * GhostmSessionHitsPath, one PathRowsGpu-style call per (query chunk, DB chunk)
+ * that has hits, and kept until the next run or GhostmSessionSetQueries*.
+ * query_record is the global index, over the query chunks in order, of the
+ * record the hit was traced with (GhostmHit.query_id names the last record of
+ * its name group instead). */
+size_t GhostmSessionHitsRows(void *session, GhostmHitRows *rec, size_t cap);
+size_t GhostmSessionRowBytes(void *session, uint8_t *rows, size_t cap);
 
 /* The same records resident on the session's GPU, for a device-to-device
  * gather across ranks: copies min(n, cap) records to dst_device
