@@ -964,7 +964,7 @@ void Session::HostMergeBatch(QueryData &q, DbData &d, uint32_t bq0, uint32_t bq1
     qid[k] = h.query;
     e[k] = h.end;
   }
-  const uint32_t tb_base = q.chunk.L + 2 * opt_.extend * 2 * (1u << opt_.log_region);
+  const uint32_t tb_base = TbBase(q);
   DeviceModule::Get().TraceBack(q.dev, d.dev, nh, qid.data(), e.data(), tb_base, opt_.open_gap,
                                 opt_.extend_gap, st.data(), len.data(), mt.data(), sid.data());
   stats_.tracebacks += nh;
@@ -997,7 +997,7 @@ void Session::DevicePass(QueryData &q, DbData &d, const std::vector<uint32_t> &c
   gap.open = opt_.open_gap;
   gap.ext = opt_.extend_gap;
   const uint32_t base = q.chunk.L + 2 * opt_.extend + 2 * (1u << opt_.log_region);
-  const uint32_t tb_base = q.chunk.L + 2 * opt_.extend * 2 * (1u << opt_.log_region);
+  const uint32_t tb_base = TbBase(q);
   const uint32_t cap = std::max<uint32_t>(opt_.best, 1);
   // segments of ~16M candidates (fewer host round trips per step);
   // GHOSTM_SEGMENT_CANDS / GHOSTM_TAIL_CANDS shrink them so that small test
@@ -1481,6 +1481,61 @@ const LineFormat &Session::Format() {
   return *format_;
 }
 
+uint32_t Session::TbBase(const QueryData &q) const {
+  return q.chunk.L + 2 * opt_.extend * 2 * (1u << opt_.log_region);
+}
+
+std::vector<std::vector<size_t>> Session::HitsByChunkPair() const {
+  std::vector<std::vector<size_t>> groups(queries_.size() * dbs_.size());
+  for (size_t h = 0; h < hit_source_.size(); ++h)
+    groups[hit_source_[h].qi * dbs_.size() + hit_source_[h].di].push_back(h);
+  return groups;
+}
+
+template <class Item, class F> void Session::ForChunkPairs(const std::vector<std::vector<Item>> &groups, F fn) {
+  for (size_t qi = 0; qi < queries_.size(); ++qi)
+    for (size_t di = 0; di < dbs_.size(); ++di)
+      if (!groups[qi * dbs_.size() + di].empty()) fn(qi, di, groups[qi * dbs_.size() + di]);
+}
+
+template <class Extra, class Line> void Session::RewriteLines(const char *what, int tabs, Extra extra, Line line) {
+  struct Piece {
+    std::string *text;
+    size_t first, n;
+  };
+  std::vector<Piece> pieces;
+  size_t at = 0;
+  for (size_t k = 0; k < used_parts_; ++k)
+    for (size_t t = 0; t < parts_[k].text.size(); ++t) {
+      pieces.push_back(Piece{&parts_[k].text[t], at, parts_[k].hits[t].size()});
+      at += parts_[k].hits[t].size();
+    }
+  ParallelFor(pieces.size(), threads_, [&](size_t b, size_t e, unsigned) {
+    std::string out;
+    for (size_t pi = b; pi < e; ++pi) {
+      const std::string &in = *pieces[pi].text;
+      out.clear();
+      out.reserve(in.size() + extra(pieces[pi].first, pieces[pi].n));
+      size_t pos = 0, tab[8];
+      for (size_t i = 0; i < pieces[pi].n; ++i) {
+        const size_t nl = in.find('\n', pos);
+        if (nl == std::string::npos) throw Error(std::string(what) + ": fewer lines than hits");
+        size_t at_tab = nl;
+        for (int c = 0; c < tabs; ++c) {
+          if (at_tab <= pos) throw Error(std::string(what) + ": malformed line");
+          at_tab = in.rfind('\t', at_tab - 1);
+          if (at_tab == std::string::npos || at_tab < pos) throw Error(std::string(what) + ": malformed line");
+          tab[c] = at_tab;
+        }
+        line(pieces[pi].first + i, in, pos, nl, tab, out);
+        pos = nl + 1;
+      }
+      *pieces[pi].text = out;
+    }
+  });
+  joined_valid_ = false;
+}
+
 // The extended traceback of every final hit (HitsExt). A hit names its query
 // chunk and DB chunk through its global indices; its chunk-local query, its
 // absolute end and its known start go to one TraceBackExt call per (query
@@ -1521,42 +1576,37 @@ const std::vector<GhostmHitExt> &Session::HitsExt() {
   const DeviceTimes before = dev.times();
   std::vector<uint32_t> qid, end, start_in, start, len, match;
   std::vector<GhostmHitExt> ext;
-  for (size_t qi = 0; qi < queries_.size(); ++qi) {
-    for (size_t di = 0; di < dbs_.size(); ++di) {
-      const std::vector<Item> &items = groups[qi * dbs_.size() + di];
-      if (items.empty()) continue;
-      qid.clear();
-      end.clear();
-      start_in.clear();
-      for (const Item &it : items)
-        for (uint32_t f = it.q0; f <= it.q1; ++f) {
-          qid.push_back(f);
-          end.push_back(it.end);
-          start_in.push_back(it.start);
-        }
-      const uint32_t n = (uint32_t)qid.size();
-      start.resize(n);
-      len.resize(n);
-      match.resize(n);
-      ext.resize(n);
-      const QueryData &q = queries_[qi];
-      const uint32_t tb_base = q.chunk.L + 2 * opt_.extend * 2 * (1u << opt_.log_region);
-      dev.TraceBackExt(q.dev, dbs_[di].dev, n, qid.data(), end.data(), start_in.data(), tb_base, opt_.open_gap,
-                       opt_.extend_gap, start.data(), len.data(), match.data(), ext.data());
-      size_t k = 0;
-      for (const Item &it : items) {
-        const GhostmHit &r = hits[it.hit];
-        bool found = false;
-        for (uint32_t f = it.q0; f <= it.q1; ++f, ++k) {
-          if (found || start[k] != it.start || len[k] != r.aln_len || match[k] != r.aln_match) continue;
-          hits_ext_[it.hit] = ext[k];
-          hit_source_[it.hit] = HitSource{(uint32_t)qi, (uint32_t)di, f, it.end, it.start};
-          found = true;
-        }
-        if (!found) throw Error("extended traceback: no query of the hit's name group reproduces its alignment");
+  ForChunkPairs(groups, [&](size_t qi, size_t di, const std::vector<Item> &items) {
+    qid.clear();
+    end.clear();
+    start_in.clear();
+    for (const Item &it : items)
+      for (uint32_t f = it.q0; f <= it.q1; ++f) {
+        qid.push_back(f);
+        end.push_back(it.end);
+        start_in.push_back(it.start);
       }
+    const uint32_t n = (uint32_t)qid.size();
+    start.resize(n);
+    len.resize(n);
+    match.resize(n);
+    ext.resize(n);
+    const QueryData &q = queries_[qi];
+    dev.TraceBackExt(q.dev, dbs_[di].dev, n, qid.data(), end.data(), start_in.data(), TbBase(q), opt_.open_gap,
+                     opt_.extend_gap, start.data(), len.data(), match.data(), ext.data());
+    size_t k = 0;
+    for (const Item &it : items) {
+      const GhostmHit &r = hits[it.hit];
+      bool found = false;
+      for (uint32_t f = it.q0; f <= it.q1; ++f, ++k) {
+        if (found || start[k] != it.start || len[k] != r.aln_len || match[k] != r.aln_match) continue;
+        hits_ext_[it.hit] = ext[k];
+        hit_source_[it.hit] = HitSource{(uint32_t)qi, (uint32_t)di, f, it.end, it.start};
+        found = true;
+      }
+      if (!found) throw Error("extended traceback: no query of the hit's name group reproduces its alignment");
     }
-  }
+  });
   const DeviceTimes &after = dev.times();
   stats_.seconds_traceback_ext += after.traceback_ext - before.traceback_ext;
   stats_.traceback_ext_launches += after.traceback_ext_launches - before.traceback_ext_launches;
@@ -1575,44 +1625,37 @@ const std::vector<GhostmHitPath> &Session::HitsPath() {
   const std::vector<GhostmHit> &hits = Hits();
   hits_path_.assign(hits.size(), GhostmHitPath{0, 0, 0, 0, 0, 0, 0});
   path_ops_.clear();
-  std::vector<std::vector<size_t>> groups(queries_.size() * dbs_.size());
-  for (size_t h = 0; h < hits.size(); ++h) groups[hit_source_[h].qi * dbs_.size() + hit_source_[h].di].push_back(h);
+  const std::vector<std::vector<size_t>> groups = HitsByChunkPair();
   DeviceModule &dev = DeviceModule::Get();
   const DeviceTimes before = dev.times();
   std::vector<uint32_t> qid, end, start_in;
   std::vector<GhostmHitPath> rec;
   std::vector<std::vector<uint32_t>> words(groups.size());
-  for (size_t qi = 0; qi < queries_.size(); ++qi) {
-    for (size_t di = 0; di < dbs_.size(); ++di) {
-      const size_t gi = qi * dbs_.size() + di;
-      const std::vector<size_t> &items = groups[gi];
-      if (items.empty()) continue;
-      qid.clear();
-      end.clear();
-      start_in.clear();
-      for (size_t h : items) {
-        qid.push_back(hit_source_[h].query);
-        end.push_back(hit_source_[h].end);
-        start_in.push_back(hit_source_[h].start);
-      }
-      const uint32_t n = (uint32_t)items.size();
-      rec.resize(n);
-      const QueryData &q = queries_[qi];
-      const uint32_t tb_base = q.chunk.L + 2 * opt_.extend * 2 * (1u << opt_.log_region);
-      dev.TraceBackPath(q.dev, dbs_[di].dev, n, qid.data(), end.data(), start_in.data(), tb_base, opt_.open_gap,
-                        opt_.extend_gap, rec.data(), &words[gi]);
-      for (uint32_t k = 0; k < n; ++k) {
-        const GhostmHit &r = hits[items[k]];
-        const uint32_t pos = dbs_[di].chunk.starts[r.db_id - dbs_[di].global_base];
-        GhostmHitPath p = rec[k];
-        if (p.s_start != hit_source_[items[k]].start)
-          throw Error("path traceback: a path does not begin at its hit's start");
-        p.s_start -= pos;
-        p.s_end -= pos;
-        hits_path_[items[k]] = p;  // ops_offset: still within the chunk pair's words
-      }
+  ForChunkPairs(groups, [&](size_t qi, size_t di, const std::vector<size_t> &items) {
+    qid.clear();
+    end.clear();
+    start_in.clear();
+    for (size_t h : items) {
+      qid.push_back(hit_source_[h].query);
+      end.push_back(hit_source_[h].end);
+      start_in.push_back(hit_source_[h].start);
     }
-  }
+    const uint32_t n = (uint32_t)items.size();
+    rec.resize(n);
+    const QueryData &q = queries_[qi];
+    dev.TraceBackPath(q.dev, dbs_[di].dev, n, qid.data(), end.data(), start_in.data(), TbBase(q), opt_.open_gap,
+                      opt_.extend_gap, rec.data(), &words[qi * dbs_.size() + di]);
+    for (uint32_t k = 0; k < n; ++k) {
+      const GhostmHit &r = hits[items[k]];
+      const uint32_t pos = dbs_[di].chunk.starts[r.db_id - dbs_[di].global_base];
+      GhostmHitPath p = rec[k];
+      if (p.s_start != hit_source_[items[k]].start)
+        throw Error("path traceback: a path does not begin at its hit's start");
+      p.s_start -= pos;
+      p.s_end -= pos;
+      hits_path_[items[k]] = p;  // ops_offset: still within the chunk pair's words
+    }
+  });
   // the words in hit order
   for (size_t h = 0; h < hits.size(); ++h) {
     GhostmHitPath &p = hits_path_[h];
@@ -1644,68 +1687,38 @@ void Session::FormatPathTabular() {
   const std::vector<GhostmHitPath> &path = HitsPath();
   const std::vector<uint32_t> &ops = path_ops_;
   const LineFormat &w = Format();
-  struct Piece {
-    std::string *text;
-    size_t first, n;
-  };
-  std::vector<Piece> pieces;
-  size_t at = 0;
-  for (size_t k = 0; k < used_parts_; ++k)
-    for (size_t t = 0; t < parts_[k].text.size(); ++t) {
-      pieces.push_back(Piece{&parts_[k].text[t], at, parts_[k].hits[t].size()});
-      at += parts_[k].hits[t].size();
+  // tab[7]: the tab after the subject name
+  RewriteLines("tabular output", 8, [](size_t, size_t n) { return n * 64; },
+               [&](size_t hit, const std::string &in, size_t pos, size_t, const size_t *tab, std::string &out) {
+    const GhostmHitPath &x = path[hit];
+    uint32_t count[4] = {0, 0, 0, 0}, gap_runs = 0;
+    for (uint32_t r = 0; r < x.n_runs; ++r) {
+      const uint32_t word = ops[x.ops_offset + r];
+      count[word & 3u] += word >> 4;
+      gap_runs += (word & 3u) >= 2;
     }
-  ParallelFor(pieces.size(), threads_, [&](size_t b, size_t e, unsigned) {
-    std::string out;
-    for (size_t pi = b; pi < e; ++pi) {
-      const std::string &in = *pieces[pi].text;
-      out.clear();
-      out.reserve(in.size() + pieces[pi].n * 64);
-      size_t pos = 0;
-      for (size_t i = 0; i < pieces[pi].n; ++i) {
-        const size_t nl = in.find('\n', pos);
-        if (nl == std::string::npos) throw Error("tabular output: fewer lines than hits");
-        size_t tab[8], at_tab = nl;  // tab[0]: the line's trailing tab ... tab[7]: the one after the subject name
-        for (int c = 0; c < 8; ++c) {
-          if (at_tab <= pos) throw Error("tabular output: malformed line");
-          at_tab = in.rfind('\t', at_tab - 1);
-          if (at_tab == std::string::npos || at_tab < pos) throw Error("tabular output: malformed line");
-          tab[c] = at_tab;
-        }
-        const GhostmHitPath &x = path[pieces[pi].first + i];
-        uint32_t count[4] = {0, 0, 0, 0}, gap_runs = 0;
-        for (uint32_t r = 0; r < x.n_runs; ++r) {
-          const uint32_t word = ops[x.ops_offset + r];
-          count[word & 3u] += word >> 4;
-          gap_runs += (word & 3u) >= 2;
-        }
-        const uint32_t length = count[0] + count[1] + count[2] + count[3];
-        out.append(in, pos, tab[7] + 1 - pos);
-        char num[160], *p = num;
-        p = w.PutId(p, length, count[0]); *p++ = '\t';
-        p = PutU32(p, length); *p++ = '\t';
-        p = PutU32(p, count[1]); *p++ = '\t';
-        p = PutU32(p, gap_runs); *p++ = '\t';
-        p = PutU32(p, x.q_start + 1); *p++ = '\t';
-        p = PutU32(p, x.q_end + 1); *p++ = '\t';
-        p = PutU32(p, x.s_start + 1); *p++ = '\t';
-        p = PutU32(p, x.s_end + 1); *p++ = '\t';
-        out.append(num, (size_t)(p - num));
-        out.append(in, tab[2] + 1, tab[0] - tab[2] - 1);
-        out.push_back('\t');
-        for (uint32_t r = 0; r < x.n_runs; ++r) {
-          const uint32_t word = ops[x.ops_offset + r];
-          p = PutU32(num, word >> 4);
-          *p++ = "=XID"[word & 3u];
-          out.append(num, (size_t)(p - num));
-        }
-        out.push_back('\n');
-        pos = nl + 1;
-      }
-      *pieces[pi].text = out;
+    const uint32_t length = count[0] + count[1] + count[2] + count[3];
+    out.append(in, pos, tab[7] + 1 - pos);
+    char num[160], *p = num;
+    p = w.PutId(p, length, count[0]); *p++ = '\t';
+    p = PutU32(p, length); *p++ = '\t';
+    p = PutU32(p, count[1]); *p++ = '\t';
+    p = PutU32(p, gap_runs); *p++ = '\t';
+    p = PutU32(p, x.q_start + 1); *p++ = '\t';
+    p = PutU32(p, x.q_end + 1); *p++ = '\t';
+    p = PutU32(p, x.s_start + 1); *p++ = '\t';
+    p = PutU32(p, x.s_end + 1); *p++ = '\t';
+    out.append(num, (size_t)(p - num));
+    out.append(in, tab[2] + 1, tab[0] - tab[2] - 1);
+    out.push_back('\t');
+    for (uint32_t r = 0; r < x.n_runs; ++r) {
+      const uint32_t word = ops[x.ops_offset + r];
+      p = PutU32(num, word >> 4);
+      *p++ = "=XID"[word & 3u];
+      out.append(num, (size_t)(p - num));
     }
+    out.push_back('\n');
   });
-  joined_valid_ = false;
 }
 
 // The aligned rows of every final hit (HitsRows): the hits' column counts give
@@ -1726,37 +1739,31 @@ const std::vector<GhostmHitRows> &Session::HitsRows() {
     total += 3 * cols;
   }
   row_bytes_.assign(total, 0);
-  std::vector<std::vector<size_t>> groups(queries_.size() * dbs_.size());
-  for (size_t h = 0; h < hits.size(); ++h) groups[hit_source_[h].qi * dbs_.size() + hit_source_[h].di].push_back(h);
   DeviceModule &dev = DeviceModule::Get();
   const DeviceTimes before = dev.times();
   std::vector<uint32_t> qid;
   std::vector<uint64_t> dst;
   std::vector<GhostmHitPath> rec;
   std::vector<GhostmHitRows> out;
-  for (size_t qi = 0; qi < queries_.size(); ++qi) {
-    for (size_t di = 0; di < dbs_.size(); ++di) {
-      const std::vector<size_t> &items = groups[qi * dbs_.size() + di];
-      if (items.empty()) continue;
-      qid.clear();
-      dst.clear();
-      rec.clear();
-      for (size_t h : items) {
-        GhostmHitPath p = path[h];
-        const uint32_t pos = dbs_[di].chunk.starts[hits[h].db_id - dbs_[di].global_base];
-        p.s_start += pos;
-        p.s_end += pos;
-        qid.push_back(hit_source_[h].query);
-        dst.push_back(place[h]);
-        rec.push_back(p);
-      }
-      out.resize(items.size());
-      dev.PathRows(queries_[qi].dev, dbs_[di].dev, (uint32_t)items.size(), qid.data(), rec.data(), path_ops_.data(),
-                   path_ops_.size(), opt_.open_gap, opt_.extend_gap, queries_[qi].global_base, out.data(),
-                   row_bytes_.data(), row_bytes_.size(), dst.data());
-      for (size_t k = 0; k < items.size(); ++k) hits_rows_[items[k]] = out[k];
+  ForChunkPairs(HitsByChunkPair(), [&](size_t qi, size_t di, const std::vector<size_t> &items) {
+    qid.clear();
+    dst.clear();
+    rec.clear();
+    for (size_t h : items) {
+      GhostmHitPath p = path[h];
+      const uint32_t pos = dbs_[di].chunk.starts[hits[h].db_id - dbs_[di].global_base];
+      p.s_start += pos;
+      p.s_end += pos;
+      qid.push_back(hit_source_[h].query);
+      dst.push_back(place[h]);
+      rec.push_back(p);
     }
-  }
+    out.resize(items.size());
+    dev.PathRows(queries_[qi].dev, dbs_[di].dev, (uint32_t)items.size(), qid.data(), rec.data(), path_ops_.data(),
+                 path_ops_.size(), opt_.open_gap, opt_.extend_gap, queries_[qi].global_base, out.data(),
+                 row_bytes_.data(), row_bytes_.size(), dst.data());
+    for (size_t k = 0; k < items.size(); ++k) hits_rows_[items[k]] = out[k];
+  });
   const DeviceTimes &after = dev.times();
   stats_.seconds_path_rows += after.path_rows - before.path_rows;
   stats_.path_rows_launches += after.path_rows_launches - before.path_rows_launches;
@@ -1782,72 +1789,51 @@ void Session::FormatRows() {
   const std::vector<GhostmHitPath> &path = hits_path_;
   const std::vector<uint8_t> &bytes = row_bytes_;
   const bool pairwise = opt_.output_style == 9;
-  struct Piece {
-    std::string *text;
-    size_t first, n;
+  const auto extra = [&](size_t first, size_t n) {
+    size_t need = n * 48;
+    for (size_t i = 0; i < n; ++i) need += 3 * (size_t)rows[first + i].columns;
+    return need;
   };
-  std::vector<Piece> pieces;
-  size_t at = 0;
-  for (size_t k = 0; k < used_parts_; ++k)
-    for (size_t t = 0; t < parts_[k].text.size(); ++t) {
-      pieces.push_back(Piece{&parts_[k].text[t], at, parts_[k].hits[t].size()});
-      at += parts_[k].hits[t].size();
-    }
-  ParallelFor(pieces.size(), threads_, [&](size_t b, size_t e, unsigned) {
-    std::string out;
-    for (size_t pi = b; pi < e; ++pi) {
-      const std::string &in = *pieces[pi].text;
-      out.clear();
-      size_t need = in.size() + pieces[pi].n * 48;
-      for (size_t i = 0; i < pieces[pi].n; ++i) need += 3 * (size_t)rows[pieces[pi].first + i].columns;
-      out.reserve(need);
-      size_t pos = 0;
-      for (size_t i = 0; i < pieces[pi].n; ++i) {
-        const size_t nl = in.find('\n', pos);
-        if (nl == std::string::npos) throw Error("rows output: fewer lines than hits");
-        const GhostmHitRows &x = rows[pieces[pi].first + i];
-        const GhostmHitPath &p = path[pieces[pi].first + i];
-        const char *q = reinterpret_cast<const char *>(bytes.data() + x.rows_offset);
-        const size_t n = x.columns;
-        char num[16], *end;
-        if (pairwise) out.append("# ");
-        out.append(in, pos, nl - pos);
-        out.push_back('\t');
-        end = PutU32(num, x.positives);
-        out.append(num, (size_t)(end - num));
-        if (!pairwise) {
-          out.push_back('\t');
-          out.append(q, n);
-          out.push_back('\t');
-          out.append(q + 2 * n, n);
-          out.push_back('\n');
-        } else {
-          out.append("\nQuery\t");
-          end = PutU32(num, p.q_start + 1);
-          out.append(num, (size_t)(end - num));
-          out.push_back('\t');
-          out.append(q, n);
-          out.push_back('\t');
-          end = PutU32(num, p.q_end + 1);
-          out.append(num, (size_t)(end - num));
-          out.append("\n\t\t");
-          out.append(q + n, n);
-          out.append("\t\nSbjct\t");
-          end = PutU32(num, p.s_start + 1);
-          out.append(num, (size_t)(end - num));
-          out.push_back('\t');
-          out.append(q + 2 * n, n);
-          out.push_back('\t');
-          end = PutU32(num, p.s_end + 1);
-          out.append(num, (size_t)(end - num));
-          out.append("\n\n");
-        }
-        pos = nl + 1;
-      }
-      *pieces[pi].text = out;
+  RewriteLines("rows output", 0, extra,
+               [&](size_t hit, const std::string &in, size_t pos, size_t nl, const size_t *, std::string &out) {
+    const GhostmHitRows &x = rows[hit];
+    const GhostmHitPath &p = path[hit];
+    const char *q = reinterpret_cast<const char *>(bytes.data() + x.rows_offset);
+    const size_t n = x.columns;
+    char num[16], *end;
+    if (pairwise) out.append("# ");
+    out.append(in, pos, nl - pos);
+    out.push_back('\t');
+    end = PutU32(num, x.positives);
+    out.append(num, (size_t)(end - num));
+    if (!pairwise) {
+      out.push_back('\t');
+      out.append(q, n);
+      out.push_back('\t');
+      out.append(q + 2 * n, n);
+      out.push_back('\n');
+    } else {
+      out.append("\nQuery\t");
+      end = PutU32(num, p.q_start + 1);
+      out.append(num, (size_t)(end - num));
+      out.push_back('\t');
+      out.append(q, n);
+      out.push_back('\t');
+      end = PutU32(num, p.q_end + 1);
+      out.append(num, (size_t)(end - num));
+      out.append("\n\t\t");
+      out.append(q + n, n);
+      out.append("\t\nSbjct\t");
+      end = PutU32(num, p.s_start + 1);
+      out.append(num, (size_t)(end - num));
+      out.push_back('\t');
+      out.append(q + 2 * n, n);
+      out.push_back('\t');
+      end = PutU32(num, p.s_end + 1);
+      out.append(num, (size_t)(end - num));
+      out.append("\n\n");
     }
   });
-  joined_valid_ = false;
 }
 
 // -y 6: qseqid sseqid pident length mismatch gapopen qstart qend sstart send
@@ -1858,51 +1844,21 @@ void Session::FormatRows() {
 // The fields are found from the line's end, so a tab inside a name is harmless.
 void Session::FormatTabular() {
   const std::vector<GhostmHitExt> &ext = HitsExt();
-  struct Piece {
-    std::string *text;
-    size_t first, n;
-  };
-  std::vector<Piece> pieces;
-  size_t at = 0;
-  for (size_t k = 0; k < used_parts_; ++k)
-    for (size_t t = 0; t < parts_[k].text.size(); ++t) {
-      pieces.push_back(Piece{&parts_[k].text[t], at, parts_[k].hits[t].size()});
-      at += parts_[k].hits[t].size();
-    }
-  ParallelFor(pieces.size(), threads_, [&](size_t b, size_t e, unsigned) {
-    std::string out;
-    for (size_t pi = b; pi < e; ++pi) {
-      const std::string &in = *pieces[pi].text;
-      out.clear();
-      out.reserve(in.size() + pieces[pi].n * 24);
-      size_t pos = 0;
-      for (size_t i = 0; i < pieces[pi].n; ++i) {
-        const size_t nl = in.find('\n', pos);
-        if (nl == std::string::npos) throw Error("tabular output: fewer lines than hits");
-        size_t tab[6], at_tab = nl;  // tab[0]: the line's trailing tab ... tab[5]: the one after the length
-        for (int c = 0; c < 6; ++c) {
-          if (at_tab <= pos) throw Error("tabular output: malformed line");
-          at_tab = in.rfind('\t', at_tab - 1);
-          if (at_tab == std::string::npos || at_tab < pos) throw Error("tabular output: malformed line");
-          tab[c] = at_tab;
-        }
-        const GhostmHitExt &x = ext[pieces[pi].first + i];
-        out.append(in, pos, tab[5] - pos);
-        char num[64], *p = num;
-        *p++ = '\t';
-        p = PutU32(p, x.mismatches); *p++ = '\t';
-        p = PutU32(p, x.gap_opens); *p++ = '\t';
-        p = PutU32(p, x.q_start + 1); *p++ = '\t';
-        p = PutU32(p, x.q_end + 1); *p++ = '\t';
-        out.append(num, (size_t)(p - num));
-        out.append(in, tab[4] + 1, tab[0] - tab[4] - 1);
-        out.push_back('\n');
-        pos = nl + 1;
-      }
-      *pieces[pi].text = out;
-    }
+  // tab[5]: the tab after the length
+  RewriteLines("tabular output", 6, [](size_t, size_t n) { return n * 24; },
+               [&](size_t hit, const std::string &in, size_t pos, size_t, const size_t *tab, std::string &out) {
+    const GhostmHitExt &x = ext[hit];
+    out.append(in, pos, tab[5] - pos);
+    char num[64], *p = num;
+    *p++ = '\t';
+    p = PutU32(p, x.mismatches); *p++ = '\t';
+    p = PutU32(p, x.gap_opens); *p++ = '\t';
+    p = PutU32(p, x.q_start + 1); *p++ = '\t';
+    p = PutU32(p, x.q_end + 1); *p++ = '\t';
+    out.append(num, (size_t)(p - num));
+    out.append(in, tab[4] + 1, tab[0] - tab[4] - 1);
+    out.push_back('\n');
   });
-  joined_valid_ = false;
 }
 
 void Session::Part::Reset(size_t pieces) {
@@ -2037,6 +1993,24 @@ void Session::FormatSelected(const QueryData &q, uint32_t g0, const std::vector<
   }
 }
 
+void Session::DropResults() {
+  used_parts_ = 0;
+  joined_.clear();
+  joined_valid_ = false;
+  hits_.clear();
+  hits_valid_ = false;
+  hits_ext_.clear();
+  hits_ext_valid_ = false;
+  hit_source_.clear();
+  hits_path_.clear();
+  path_ops_.clear();
+  hits_path_valid_ = false;
+  hits_rows_.clear();
+  row_bytes_.clear();
+  row_bytes_.shrink_to_fit();
+  hits_rows_valid_ = false;
+}
+
 void Session::Run(bool stream_to_file) {
   DeviceModule &dev = DeviceModule::Get();
   formatter_->Drain();
@@ -2075,21 +2049,7 @@ void Session::Run(bool stream_to_file) {
   stats_ = GhostmStats{};
   QueryStats();
   merge_epoch_ = 0;
-  used_parts_ = 0;
-  joined_.clear();
-  joined_valid_ = false;
-  hits_.clear();
-  hits_valid_ = false;
-  hits_ext_.clear();
-  hits_ext_valid_ = false;
-  hit_source_.clear();
-  hits_path_.clear();
-  path_ops_.clear();
-  hits_path_valid_ = false;
-  hits_rows_.clear();
-  row_bytes_.clear();
-  row_bytes_.shrink_to_fit();
-  hits_rows_valid_ = false;
+  DropResults();
   Format();  // built here, before any formatting task can need it
   dev.ResetRecords(HitCapacity());  // the most records the run can append
   records_on_device_ = true;
@@ -2323,22 +2283,7 @@ void Session::DropQueries() {
   if (writer_) writer_->Drain();
   DeviceModule &dev = DeviceModule::Get();
   dev.Synchronize();
-  // the last run's results
-  used_parts_ = 0;
-  joined_.clear();
-  joined_valid_ = false;
-  hits_.clear();
-  hits_valid_ = false;
-  hits_ext_.clear();
-  hits_ext_valid_ = false;
-  hit_source_.clear();
-  hits_path_.clear();
-  path_ops_.clear();
-  hits_path_valid_ = false;
-  hits_rows_.clear();
-  row_bytes_.clear();
-  row_bytes_.shrink_to_fit();
-  hits_rows_valid_ = false;
+  DropResults();
   dev.ResetRecords(0);
   records_on_device_ = true;
   streamed_ = false;

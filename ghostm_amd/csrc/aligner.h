@@ -285,6 +285,21 @@ class Session {
   void PartDone(const Part *part);
   void StreamPart(Part *part);
   const LineFormat &Format();
+  void DropResults();  // forgets the last run's results and everything derived from them
+  uint32_t TbBase(const QueryData &q) const;  // the traceback's DP window of a query chunk
+  // The detail passes (HitsExt, HitsPath, HitsRows) make one device call per
+  // (query chunk, DB chunk): the hit indices of pair [qi * dbs_.size() + di] as
+  // HitsExt() resolved them (hit_source_), and fn(qi, di, items) for every pair
+  // that has any.
+  std::vector<std::vector<size_t>> HitsByChunkPair() const;
+  template <class Item, class F> void ForChunkPairs(const std::vector<std::vector<Item>> &groups, F fn);
+  // Rewrites the parts' text, one line per hit in hit order, pieces in
+  // parallel: line(hit, in, pos, nl, tab, out) appends hit's new text to out
+  // from its line in[pos, nl), with tab[0 .. tabs) the line's last tabs found
+  // from its end (tab[0] the trailing one); extra(first, n) is what to reserve
+  // beyond the input's size for hits [first, first + n). Throws "<what>: ..."
+  // on fewer lines than hits or fewer tabs than asked for.
+  template <class Extra, class Line> void RewriteLines(const char *what, int tabs, Extra extra, Line line);
   // -y 6: rewrites the parts' style-0 lines as the twelve BLAST-tabular columns
   void FormatTabular();
   // -y 7: the same with columns 3 to 10 taken from the hit's path, and its CIGAR

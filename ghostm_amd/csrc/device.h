@@ -232,8 +232,10 @@ class DeviceModule {
   // The extended traceback (kern::k_traceback_ext) on n hits: K3's outputs plus
   // one GhostmHitExt per hit. db_start_in (may be null): the hits' known
   // starts; each DP then stops after end - start + 1 columns, and the hits run
-  // in the order of that count. Throws when L or the window exceeds the packed
-  // fields. Adds its device time, launches and cells to times().
+  // in the order of that count (ColumnOrder, hit_batches.h). Throws what
+  // RefuseHits (hit_batches.h) says: L or the window exceeds the packed
+  // fields, or a hit lies outside the chunks. Adds its device time, launches
+  // and cells to times().
   void TraceBackExt(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const uint32_t *db_end,
                     const uint32_t *db_start_in, uint32_t base_search_length, int open, int ext,
                     uint32_t *db_start, uint32_t *aln_len, uint32_t *aln_match, GhostmHitExt *out);
@@ -241,13 +243,15 @@ class DeviceModule {
   // The alignment path of n hits (kern::k_tb_path_fill + kern::k_tb_path_walk):
   // rec[n] (may be null) and the hits' run-length words in hit order (*ops is
   // replaced; rec[i].ops_offset indexes it). db_start_in as for TraceBackExt.
-  // The hits run in batches whose direction buffer fits GHOSTM_PATH_SCRATCH_MB
-  // (default 1024) and that hold at most GHOSTM_PATH_BATCH_HITS hits; a batch's
-  // slots are packed on the device (kern::k_tb_path_compact, the offsets from
-  // the host's prefix sum over the records) and the batches' words joined in
-  // hit order on the host. Throws when L > 127
-  // or L + window >= 32768. Adds its device time, batches, cells and direction
-  // bytes to times().
+  // The hits run in the order of their column counts, in batches cut by
+  // CutBatch (hit_batches.h) with the direction buffer's bytes as the cost,
+  // GHOSTM_PATH_SCRATCH_MB (default 1024) as the budget and
+  // GHOSTM_PATH_BATCH_HITS as the hit cap; a batch's slots are packed on the
+  // device (kern::k_tb_path_compact, the offsets from the host's prefix sum
+  // over the records) and the batches' words joined in hit order on the host.
+  // Throws what RefuseHits says (L > 127, L + window >= 32768, an empty
+  // window, a hit outside the chunks). Adds its device time, batches, cells
+  // and direction bytes to times().
   void TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const uint32_t *db_end,
                      const uint32_t *db_start_in, uint32_t base_search_length, int open, int ext,
                      GhostmHitPath *rec, std::vector<uint32_t> *ops);
@@ -261,10 +265,10 @@ class DeviceModule {
   // receives hit i's 3 * columns bytes at dst_off[i], or, with dst_off null, the
   // hits' bytes one after the other from 0; out[i].rows_offset is that offset.
   // Throws ("rows_cap") when a hit's bytes would end past rows_cap. Returns the
-  // hits' bytes together. The hits run in hit order in batches whose row bytes
-  // fit GHOSTM_ROWS_SCRATCH_MB (default 1024) and that hold at most
-  // GHOSTM_ROWS_BATCH_HITS hits. Adds its device time, batches, columns and
-  // bytes to times().
+  // hits' bytes together. The hits run in hit order in CutBatch's batches
+  // (hit_batches.h): the cost a hit's row bytes, the budget
+  // GHOSTM_ROWS_SCRATCH_MB (default 1024), the cap GHOSTM_ROWS_BATCH_HITS.
+  // Adds its device time, batches, columns and bytes to times().
   size_t PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const GhostmHitPath *rec,
                   const uint32_t *ops, size_t ops_len, int open, int ext, uint32_t record_base,
                   GhostmHitRows *out, uint8_t *rows, size_t rows_cap, const uint64_t *dst_off);

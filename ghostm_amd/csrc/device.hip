@@ -16,6 +16,7 @@
 #include "common.h"
 #include "device.h"
 #include "formats.h"
+#include "hit_batches.h"
 #include "kernels.h"
 #include "path_rows.h"
 #include "qformat.h"
@@ -736,6 +737,54 @@ static float ElapsedMs(hipEvent_t a, hipEvent_t b) {
   HIP_CHECK(hipEventSynchronize(b));
   HIP_CHECK(hipEventElapsedTime(&ms, a, b));
   return ms;
+}
+
+// Records a, runs launch() (its kernel launches on st), checks them and records
+// b: after the stream's next synchronisation ElapsedMs(a, b) is their device time.
+template <class F> static void TimedLaunch(hipEvent_t a, hipEvent_t b, hipStream_t st, F launch) {
+  HIP_CHECK(hipEventRecord(a, st));
+  launch();
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(b, st));
+}
+
+// The fields kern::TbArgs and kern::TbPathArgs share: the query chunk, the DP's
+// layout, the DB, the traceback matrix, the hits and the gap costs.
+template <class Args>
+static void FillDpArgs(Args *a, const DevQuery *q, const DevDb *d, const Layout &lay, const int *mat_tb,
+                       const uint32_t *qid, const uint32_t *end, uint32_t n, int open, int ext) {
+  a->qseq = q->seq.as<uint8_t>();
+  a->L = q->L;
+  a->Lpad = lay.Lpad;
+  a->G = lay.G;
+  a->gpw = lay.gpw;
+  a->db = d->Residues();
+  a->mat_tb = mat_tb;
+  a->qid = qid;
+  a->end = end;
+  a->n = n;
+  a->open = open;
+  a->ext = ext;
+}
+
+// qid[n] | end[n] | ncols[n] | order[n] at the front of buf, then extra bytes
+// of the caller's. ncols and order are uploaded when given, else their device
+// pointers are null.
+struct DevHits {
+  uint32_t *qid, *end, *ncols, *order;
+};
+static DevHits UploadHits(DevBuf *buf, size_t extra, uint32_t n, const uint32_t *qid, const uint32_t *end,
+                          const uint32_t *ncols, const uint32_t *order, hipStream_t st) {
+  buf->Reserve((size_t)n * 16 + extra);
+  uint32_t *w = buf->as<uint32_t>();
+  DevHits h{w, w + n, ncols ? w + 2 * (size_t)n : nullptr, ncols ? w + 3 * (size_t)n : nullptr};
+  HIP_CHECK(hipMemcpyAsync(h.qid, qid, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(h.end, end, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  if (ncols) {
+    HIP_CHECK(hipMemcpyAsync(h.ncols, ncols, (size_t)n * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(h.order, order, (size_t)n * 4, hipMemcpyHostToDevice, st));
+  }
+  return h;
 }
 
 // K1's device time, read when something has waited for the stream anyway (the
@@ -1901,16 +1950,9 @@ void DeviceModule::MergeLaunch(DevQuery *q, DevDb *d, uint32_t g0, uint32_t g1, 
 
   // K3 over the slots (empty slots carry qid 0xFFFFFFFF and are skipped)
   kern::TbArgs a{};
-  a.qseq = q->seq.as<uint8_t>();
-  a.L = q->L;
-  a.db = d->Residues();
-  a.mat_tb = I.mat_tb.as<int>();
-  a.qid = I.tb_qid.as<uint32_t>();
-  a.end = I.tb_end.as<uint32_t>();
-  a.n = (uint32_t)slots;
+  FillDpArgs(&a, q, d, ChooseLayout(q->L, tb_base), I.mat_tb.as<int>(), I.tb_qid.as<uint32_t>(),
+             I.tb_end.as<uint32_t>(), (uint32_t)slots, open, ext);
   a.base = tb_base;
-  a.open = open;
-  a.ext = ext;
   a.out_start = I.tb_start.as<uint32_t>();
   a.out_ml = I.tb_ml.as<uint32_t>();
   // K3 counters: [0] traceback cells, [1] K3a scan cells
@@ -2062,24 +2104,15 @@ void DeviceModule::TraceBack(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *
   HIP_CHECK(hipMemcpyAsync(I.tb_qid.p, qid, (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
   HIP_CHECK(hipMemcpyAsync(I.tb_end.p, db_end, (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
   kern::TbArgs a{};
-  a.qseq = q->seq.as<uint8_t>();
-  a.L = q->L;
-  a.db = d->Residues();
-  a.mat_tb = I.mat_tb.as<int>();
-  a.qid = I.tb_qid.as<uint32_t>();
-  a.end = I.tb_end.as<uint32_t>();
-  a.n = n;
+  FillDpArgs(&a, q, d, ChooseLayout(q->L, base), I.mat_tb.as<int>(), I.tb_qid.as<uint32_t>(),
+             I.tb_end.as<uint32_t>(), n, open, ext);
   a.base = base;
-  a.open = open;
-  a.ext = ext;
   a.out_start = I.tb_start.as<uint32_t>();
   a.out_ml = I.tb_ml.as<uint32_t>();
   I.tb_counters.Reserve(16);
   HIP_CHECK(hipMemsetAsync(I.tb_counters.p, 0, 16, S(stream_)));
   a.cells = I.tb_counters.as<unsigned long long>();
-  HIP_CHECK(hipEventRecord(I.ev0, S(stream_)));
-  LaunchTraceback(a, q, n, d, kern::kPairRun);
-  HIP_CHECK(hipEventRecord(I.ev1, S(stream_)));
+  TimedLaunch(I.ev0, I.ev1, S(stream_), [&] { LaunchTraceback(a, q, n, d, kern::kPairRun); });
   std::vector<uint32_t> ml(n);
   HIP_CHECK(hipMemcpyAsync(db_start, I.tb_start.p, (size_t)n * 4, hipMemcpyDeviceToHost, S(stream_)));
   HIP_CHECK(hipMemcpyAsync(ml.data(), I.tb_ml.p, (size_t)n * 4, hipMemcpyDeviceToHost, S(stream_)));
@@ -2130,67 +2163,36 @@ void DeviceModule::TraceBackExt(DevQuery *q, DevDb *d, uint32_t n, const uint32_
   // field widths of the packed words (kernels.h k_traceback_ext): origin row 7
   // bits, mismatches 8 bits (at most L), gap opens 15 bits (at most the path
   // length, below L + window)
-  if (q->L == 0 || q->L > 127) throw Error("extended traceback: query length outside 1..127");
-  if ((uint64_t)q->L + base >= 32768) throw Error("extended traceback: window too wide for the packed fields");
-  for (uint32_t k = 0; k < n; ++k) {
-    if (qid[k] >= q->nseq || db_end[k] >= d->len) throw Error("extended traceback: hit outside the resident chunk");
-    if (db_start_in && db_start_in[k] > db_end[k]) throw Error("extended traceback: start after end");
-  }
-  // qid, end, [ncols, order], start, ml, x, row, then the u64 cell counter
-  I.tb_ext.Reserve((size_t)n * 4 * 8 + 8);
-  uint32_t *w = I.tb_ext.as<uint32_t>();
-  uint32_t *d_qid = w, *d_end = w + n, *d_ncols = w + 2 * (size_t)n, *d_order = w + 3 * (size_t)n;
-  uint32_t *d_out = w + 4 * (size_t)n;  // start, ml, x, row
-  HIP_CHECK(hipMemcpyAsync(d_qid, qid, (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
-  HIP_CHECK(hipMemcpyAsync(d_end, db_end, (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
+  const std::string why = RefuseHits("extended traceback: ", "the packed fields", false, q->nseq, q->L, d->len, n, qid,
+                                     db_end, db_start_in, base);
+  if (!why.empty()) throw Error(why);
+  // with known starts the hits run in the order of their column counts (hit_batches.h)
   std::vector<uint32_t> ncols, order;
-  if (db_start_in) {
-    // hits of about equal column counts share a wave (its loop runs to the widest)
-    // (a stable counting sort: a count above the window is cut to it, as the kernel does)
-    ncols.resize(n);
-    order.resize(n);
-    std::vector<uint32_t> first((size_t)base + 2, 0);
-    for (uint32_t k = 0; k < n; ++k) {
-      ncols[k] = std::min(db_end[k] - db_start_in[k] + 1, base);
-      ++first[ncols[k] + 1];
-    }
-    for (size_t c = 1; c < first.size(); ++c) first[c] += first[c - 1];
-    for (uint32_t k = 0; k < n; ++k) order[first[ncols[k]]++] = k;
-    HIP_CHECK(hipMemcpyAsync(d_ncols, ncols.data(), (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
-    HIP_CHECK(hipMemcpyAsync(d_order, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
-  }
+  if (db_start_in) ColumnOrder(n, db_end, db_start_in, base, false, &ncols, &order);
+  // qid, end, [ncols, order], start, ml, x, row, then the u64 cell counter
+  const DevHits h = UploadHits(&I.tb_ext, (size_t)n * 16 + 8, n, qid, db_end, db_start_in ? ncols.data() : nullptr,
+                               order.data(), S(stream_));
+  uint32_t *d_out = h.qid + 4 * (size_t)n;  // start, ml, x, row
   const Layout lay = ChooseExtLayout(q->L, base);
   kern::TbExtArgs ea{};
   kern::TbArgs &a = ea.tb;
-  a.qseq = q->seq.as<uint8_t>();
-  a.L = q->L;
-  a.Lpad = lay.Lpad;
-  a.G = lay.G;
-  a.gpw = lay.gpw;
-  a.db = d->Residues();
-  a.mat_tb = I.mat_tb.as<int>();
-  a.qid = d_qid;
-  a.end = d_end;
-  a.n = n;
+  FillDpArgs(&a, q, d, lay, I.mat_tb.as<int>(), h.qid, h.end, n, open, ext);
   a.base = base;
-  a.open = open;
-  a.ext = ext;
   a.out_start = d_out;
   a.out_ml = d_out + n;
   ea.out_x = d_out + 2 * (size_t)n;
   ea.out_row = d_out + 3 * (size_t)n;
-  a.order = db_start_in ? d_order : nullptr;
-  a.ncols = db_start_in ? d_ncols : nullptr;
-  unsigned long long *cells_d = reinterpret_cast<unsigned long long *>(w + 8 * (size_t)n);
+  a.order = h.order;
+  a.ncols = h.ncols;
+  unsigned long long *cells_d = reinterpret_cast<unsigned long long *>(h.qid + 8 * (size_t)n);
   HIP_CHECK(hipMemsetAsync(cells_d, 0, 8, S(stream_)));
   a.cells = cells_d;
   const uint32_t per_block = lay.gpw * (kern::kTbBlock / 64);
   const dim3 grid((n + per_block - 1) / per_block), block(kern::kTbBlock);
-  HIP_CHECK(hipEventRecord(I.ev0, S(stream_)));
-  if (lay.S == 8) hipLaunchKernelGGL(kern::k_traceback_ext<8>, grid, block, 0, S(stream_), ea);
-  else hipLaunchKernelGGL(kern::k_traceback_ext<16>, grid, block, 0, S(stream_), ea);
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipEventRecord(I.ev1, S(stream_)));
+  TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
+    if (lay.S == 8) hipLaunchKernelGGL(kern::k_traceback_ext<8>, grid, block, 0, S(stream_), ea);
+    else hipLaunchKernelGGL(kern::k_traceback_ext<16>, grid, block, 0, S(stream_), ea);
+  });
   std::vector<uint32_t> res((size_t)n * 4);
   unsigned long long cells = 0;
   HIP_CHECK(hipMemcpyAsync(res.data(), d_out, (size_t)n * 16, hipMemcpyDeviceToHost, S(stream_)));
@@ -2225,36 +2227,15 @@ void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32
   if (ops) ops->clear();
   if (n == 0) return;
   // a run-length word holds a length below 2^28; the limits are the extended traceback's
-  if (q->L == 0 || q->L > 127) throw Error("path traceback: query length outside 1..127");
-  if ((uint64_t)q->L + base >= 32768) throw Error("path traceback: window too wide for the run-length words");
-  if (base == 0) throw Error("path traceback: empty window");
-  for (uint32_t k = 0; k < n; ++k) {
-    if (qid[k] >= q->nseq || db_end[k] >= d->len) throw Error("path traceback: hit outside the resident chunk");
-    if (db_start_in && db_start_in[k] > db_end[k]) throw Error("path traceback: start after end");
-  }
+  const std::string why = RefuseHits("path traceback: ", "the run-length words", true, q->nseq, q->L, d->len, n, qid,
+                                     db_end, db_start_in, base);
+  if (!why.empty()) throw Error(why);
   const uint32_t L = q->L;
   // every hit's column count (the window clipped at DB position 0, cut to the
-  // known start's) and the stable counting sort by it: hits of about equal
-  // column counts share a wave
-  std::vector<uint32_t> ncols(n), order(n);
-  {
-    std::vector<uint32_t> first((size_t)base + 2, 0);
-    for (uint32_t k = 0; k < n; ++k) {
-      uint32_t w = db_end[k] < base ? db_end[k] + 1 : base;
-      if (db_start_in) w = std::min(w, db_end[k] - db_start_in[k] + 1);
-      ncols[k] = w;
-      ++first[w + 1];
-    }
-    for (size_t c = 1; c < first.size(); ++c) first[c] += first[c - 1];
-    for (uint32_t k = 0; k < n; ++k) order[first[ncols[k]]++] = k;
-  }
-  I.tb_path_in.Reserve((size_t)n * 16);
-  uint32_t *w = I.tb_path_in.as<uint32_t>();
-  uint32_t *d_qid = w, *d_end = w + n, *d_ncols = w + 2 * (size_t)n, *d_order = w + 3 * (size_t)n;
-  HIP_CHECK(hipMemcpyAsync(d_qid, qid, (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
-  HIP_CHECK(hipMemcpyAsync(d_end, db_end, (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
-  HIP_CHECK(hipMemcpyAsync(d_ncols, ncols.data(), (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
-  HIP_CHECK(hipMemcpyAsync(d_order, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, S(stream_)));
+  // known start's) and the launch order by it (hit_batches.h)
+  std::vector<uint32_t> ncols, order;
+  ColumnOrder(n, db_end, db_start_in, base, true, &ncols, &order);
+  const DevHits h = UploadHits(&I.tb_path_in, 0, n, qid, db_end, ncols.data(), order.data(), S(stream_));
 
   const Layout lay = ChooseLayout(L, base);
   const size_t colw = (size_t)lay.G * (size_t)(lay.S / 8);  // direction dwords per hit-column
@@ -2268,30 +2249,22 @@ void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32
   std::vector<unsigned long long> off;  // dir_off[m], then ops_off[m]; dir_off later the packed offsets
   std::vector<uint32_t> h_rec;
   for (uint32_t b0 = 0; b0 < n;) {
-    // slots [b0, b1) of the sorted order: at least one hit, then as many as fit
-    uint32_t b1 = b0;
-    size_t dir_words = 0, ops_words = 0;
-    while (b1 < n && b1 - b0 < max_hits) {
-      const size_t dw = (size_t)ncols[order[b1]] * colw;
-      if (b1 > b0 && (dir_words + dw) * 4 > budget) break;
-      dir_words += dw;
-      ops_words += (size_t)ncols[order[b1]] + L;
-      ++b1;
-    }
+    // slots [b0, b1) of the sorted order, cut by their direction bytes (hit_batches.h)
+    size_t dir_bytes = 0;
+    const uint32_t b1 =
+        CutBatch(b0, n, max_hits, budget, [&](uint32_t s) { return (size_t)ncols[order[s]] * colw * 4; }, &dir_bytes);
     const uint32_t m = b1 - b0;
     off.resize(2 * (size_t)m);
-    {
-      size_t da = 0, oa = 0;
-      for (uint32_t s = 0; s < m; ++s) {
-        off[s] = da;
-        off[m + s] = oa;
-        da += (size_t)ncols[order[b0 + s]] * colw;
-        oa += (size_t)ncols[order[b0 + s]] + L;
-      }
+    size_t ops_words = 0;
+    for (size_t s = 0, da = 0; s < m; ++s) {
+      off[s] = da;
+      off[m + s] = ops_words;
+      da += (size_t)ncols[order[b0 + s]] * colw;
+      ops_words += (size_t)ncols[order[b0 + s]] + L;
     }
     // meta: dir_off[m], ops_off[m] (u64), the cell counter (u64), best[3m], rec[6m]
     I.tb_path_meta.Reserve((size_t)m * 16 + 8 + (size_t)m * 36);
-    I.tb_path_dir.Reserve(dir_words * 4);
+    I.tb_path_dir.Reserve(dir_bytes);
     I.tb_path_ops.Reserve(ops_words * 4);
     unsigned long long *d_off = I.tb_path_meta.as<unsigned long long>();
     unsigned long long *cells_d = d_off + 2 * (size_t)m;
@@ -2300,20 +2273,9 @@ void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32
     HIP_CHECK(hipMemcpyAsync(d_off, off.data(), (size_t)m * 16, hipMemcpyHostToDevice, S(stream_)));
     HIP_CHECK(hipMemsetAsync(cells_d, 0, 8, S(stream_)));
     kern::TbPathArgs a{};
-    a.qseq = q->seq.as<uint8_t>();
-    a.L = L;
-    a.Lpad = lay.Lpad;
-    a.G = lay.G;
-    a.gpw = lay.gpw;
-    a.db = d->Residues();
-    a.mat_tb = I.mat_tb.as<int>();
-    a.qid = d_qid;
-    a.end = d_end;
-    a.ncols = d_ncols;
-    a.order = d_order + b0;
-    a.n = m;
-    a.open = open;
-    a.ext = ext;
+    FillDpArgs(&a, q, d, lay, I.mat_tb.as<int>(), h.qid, h.end, m, open, ext);
+    a.ncols = h.ncols;
+    a.order = h.order + b0;
     a.dir_off = d_off;
     a.dir = I.tb_path_dir.as<uint32_t>();
     a.best = d_best;
@@ -2324,15 +2286,14 @@ void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32
     const uint32_t per_block = lay.gpw * (kern::kTbBlock / 64);
     const dim3 grid((m + per_block - 1) / per_block), block(kern::kTbBlock);
     const dim3 lane_grid((m + kern::kTbBlock - 1) / kern::kTbBlock);  // one lane per slot
-    HIP_CHECK(hipEventRecord(I.ev0, S(stream_)));
-    if (lay.S == 8) hipLaunchKernelGGL(kern::k_tb_path_fill<8>, grid, block, 0, S(stream_), a);
-    else if (lay.S == 16) hipLaunchKernelGGL(kern::k_tb_path_fill<16>, grid, block, 0, S(stream_), a);
-    else hipLaunchKernelGGL(kern::k_tb_path_fill<32>, grid, block, 0, S(stream_), a);
-    HIP_CHECK(hipGetLastError());
-    const uint32_t log2w = lay.S == 8 ? 0u : lay.S == 16 ? 1u : 2u;
-    hipLaunchKernelGGL(kern::k_tb_path_walk, lane_grid, block, 0, S(stream_), a, log2w);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(I.ev1, S(stream_)));
+    TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
+      if (lay.S == 8) hipLaunchKernelGGL(kern::k_tb_path_fill<8>, grid, block, 0, S(stream_), a);
+      else if (lay.S == 16) hipLaunchKernelGGL(kern::k_tb_path_fill<16>, grid, block, 0, S(stream_), a);
+      else hipLaunchKernelGGL(kern::k_tb_path_fill<32>, grid, block, 0, S(stream_), a);
+      HIP_CHECK(hipGetLastError());
+      const uint32_t log2w = lay.S == 8 ? 0u : lay.S == 16 ? 1u : 2u;
+      hipLaunchKernelGGL(kern::k_tb_path_walk, lane_grid, block, 0, S(stream_), a, log2w);
+    });
     h_rec.resize((size_t)m * 6);
     unsigned long long cells = 0;
     HIP_CHECK(hipMemcpyAsync(h_rec.data(), d_rec, (size_t)m * 24, hipMemcpyDeviceToHost, S(stream_)));
@@ -2341,7 +2302,7 @@ void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32
     times_.traceback_path += ElapsedMs(I.ev0, I.ev1) * 1e-3;
     times_.traceback_path_launches += 1;
     times_.traceback_path_cells += cells;
-    times_.traceback_path_dir_bytes += dir_words * 4;
+    times_.traceback_path_dir_bytes += dir_bytes;
     // the scan of the compaction: every slot's first word in the packed array
     size_t packed = 0;
     for (uint32_t s = 0; s < m; ++s) {
@@ -2364,10 +2325,8 @@ void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32
         HIP_CHECK(hipMemcpyAsync(d_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
         a.cmp_off = d_off;
         a.cmp = I.tb_path_cmp.as<uint32_t>();
-        HIP_CHECK(hipEventRecord(I.ev0, S(stream_)));
-        hipLaunchKernelGGL(kern::k_tb_path_compact, lane_grid, block, 0, S(stream_), a);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipEventRecord(I.ev1, S(stream_)));
+        TimedLaunch(I.ev0, I.ev1, S(stream_),
+                    [&] { hipLaunchKernelGGL(kern::k_tb_path_compact, lane_grid, block, 0, S(stream_), a); });
         HIP_CHECK(hipMemcpyAsync(batch_words.back().data(), a.cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
         HIP_CHECK(hipStreamSynchronize(S(stream_)));
         times_.traceback_path += ElapsedMs(I.ev0, I.ev1) * 1e-3;
@@ -2415,29 +2374,19 @@ size_t DeviceModule::PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t 
   std::vector<uint8_t> stage;  // a batch's bytes on their way to dst_off
   size_t done_bytes = 0;
   for (uint32_t b0 = 0; b0 < n;) {
-    // hits [b0, b1): at least one, then as many as fit
-    uint32_t b1 = b0;
-    size_t bytes = 0, nwords = 0;
-    while (b1 < n && b1 - b0 < max_hits) {
-      const size_t sz = 3 * (size_t)columns[b1];
-      if (b1 > b0 && bytes + sz > budget) break;
-      bytes += sz;
-      nwords += rec[b1].n_runs;
-      ++b1;
-    }
+    // hits [b0, b1) in hit order, cut by their row bytes (hit_batches.h)
+    size_t bytes = 0;
+    const uint32_t b1 = CutBatch(b0, n, max_hits, budget, [&](uint32_t k) { return 3 * (size_t)columns[k]; }, &bytes);
     const uint32_t m = b1 - b0;
     hh.resize(m);
-    words.resize(nwords);
-    {
-      size_t wa = 0, ra = 0;
-      for (uint32_t s = 0; s < m; ++s) {
-        const GhostmHitPath &p = rec[b0 + s];
-        hh[s] = kern::PathRowsHit{qid[b0 + s], p.q_start, p.s_start, p.n_runs, columns[b0 + s], 0, wa, ra};
-        if (p.n_runs) memcpy(words.data() + wa, ops + p.ops_offset, (size_t)p.n_runs * 4);
-        wa += p.n_runs;
-        ra += 3 * (size_t)columns[b0 + s];
-      }
+    words.clear();
+    for (size_t s = 0, ra = 0; s < m; ++s) {
+      const GhostmHitPath &p = rec[b0 + s];
+      hh[s] = kern::PathRowsHit{qid[b0 + s], p.q_start, p.s_start, p.n_runs, columns[b0 + s], 0, words.size(), ra};
+      if (p.n_runs) words.insert(words.end(), ops + p.ops_offset, ops + p.ops_offset + p.n_runs);
+      ra += 3 * (size_t)columns[b0 + s];
     }
+    const size_t nwords = words.size();
     I.path_rows_hit.Reserve((size_t)m * sizeof(kern::PathRowsHit));
     I.path_rows_ops.Reserve(std::max<size_t>(nwords, 1) * 4);
     I.path_rows_out.Reserve((size_t)m * 16);
@@ -2458,10 +2407,7 @@ size_t DeviceModule::PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t 
     a.rows = rows ? I.path_rows_buf.as<uint8_t>() : nullptr;
     a.out = I.path_rows_out.as<uint32_t>();
     const dim3 grid((m + kern::kTbBlock / 64 - 1) / (kern::kTbBlock / 64)), block(kern::kTbBlock);  // one wave per hit
-    HIP_CHECK(hipEventRecord(I.ev0, S(stream_)));
-    hipLaunchKernelGGL(kern::k_path_rows, grid, block, 0, S(stream_), a);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipEventRecord(I.ev1, S(stream_)));
+    TimedLaunch(I.ev0, I.ev1, S(stream_), [&] { hipLaunchKernelGGL(kern::k_path_rows, grid, block, 0, S(stream_), a); });
     counts.resize((size_t)m * 4);
     HIP_CHECK(hipMemcpyAsync(counts.data(), a.out, (size_t)m * 16, hipMemcpyDeviceToHost, S(stream_)));
     uint8_t *land = nullptr;
