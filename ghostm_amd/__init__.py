@@ -3,9 +3,10 @@
 Seed lookup, Gotoh score DP and traceback are hand-written HIP kernels in
 csrc/; the merge/E-value host logic and the C ABI live in libghostm_hip.so.
 """
-from .aligner import (Aligner, GhostmError, HIT_DTYPE, HIT_EXT_DTYPE, HIT_PATH_DTYPE, HIT_ROWS_DTYPE, Session, cigar,
-                      format_db, format_queries, path_rows_host, query_chunk_cuts, rows_of, run_cli, synth,
-                      traceback_ext_host, traceback_path_host)
+from .aligner import (Aligner, GhostmError, HIT_DTYPE, HIT_EXT_DTYPE, HIT_PATH_DTYPE, HIT_ROWS_DTYPE,
+                      SUBJECT_PILEUP_DTYPE, Session, cigar, consensus_text, format_db, format_queries, path_pileup_host,
+                      path_rows_host, query_chunk_cuts, rows_of, run_cli, synth, traceback_ext_host,
+                      traceback_path_host)
 from .native import BIN_PATH, LIB_PATH, NativeLibraryMissing, load
 
 __all__ = [
@@ -20,6 +21,9 @@ __all__ = [
     "traceback_path_host",
     "cigar",
     "path_rows_host",
+    "SUBJECT_PILEUP_DTYPE",
+    "path_pileup_host",
+    "consensus_text",
     "rows_of",
     "format_db",
     "format_queries",

@@ -68,6 +68,27 @@ def rows_of(rec, rows, h) -> tuple[bytes, bytes, bytes]:
     return b[:n], b[n:2 * n], b[2 * n:]
 
 
+# GhostmSubjectPileup: one per subject in db_id order; the subject's positions
+# are [offset, offset + length) of the session-level pile-up arrays
+SUBJECT_PILEUP_DTYPE = np.dtype([("length", "<u4"), ("hits", "<u4"), ("covered", "<u4"), ("max_depth", "<u4"),
+                                 ("depth_sum", "<u8"), ("identities_sum", "<u8"), ("offset", "<u8")])
+
+RESIDUE_LETTERS = b"ARNDCQEGHILKMFPSTWYVBJZX*"
+
+
+def consensus_text(consensus, depth) -> bytes:
+    """The pile-up's consensus as text: the residue letter, '-' where depth > 0
+    and consensus is 255 (only codes from 25 up or deletions were seen), '.'
+    where depth is 0."""
+    c = np.asarray(consensus, dtype=np.uint8)
+    d = np.asarray(depth)
+    table = np.full(256, ord("-"), dtype=np.uint8)
+    table[:25] = np.frombuffer(RESIDUE_LETTERS, dtype=np.uint8)
+    out = table[c]
+    out[d == 0] = ord(".")
+    return out.tobytes()
+
+
 class GhostmError(RuntimeError):
     pass
 
@@ -183,6 +204,34 @@ def path_rows_host(query_seqs, L, db, score_matrix, query_ids, rec, ops, open_ga
     if used.value:
         call(rows.ctypes.data_as(u8p), used.value, used)
     return out, rows
+
+
+def path_pileup_host(query_seqs, L, db, query_ids, rec, ops, profile=False):
+    """The host model of the subject pile-up (GhostmPathPileupHost; no device):
+    arguments as path_rows_host. Returns (depth, identities, consensus), each
+    one element per residue of db, and with profile=True a fourth array of
+    shape (len(db), 32)."""
+    lib = native.load()
+    qs = np.ascontiguousarray(query_seqs, dtype=np.uint8).reshape(-1)
+    dbs = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
+    qid = np.ascontiguousarray(query_ids, dtype=np.uint32)
+    p = np.ascontiguousarray(rec, dtype=HIT_PATH_DTYPE)
+    w = np.ascontiguousarray(ops, dtype=np.uint32)
+    if L <= 0 or qs.size % L or qid.shape != p.shape:
+        raise ValueError("path_pileup_host: bad argument shapes")
+    depth = np.zeros(dbs.size, dtype=np.uint32)
+    ident = np.zeros(dbs.size, dtype=np.uint32)
+    cons = np.zeros(dbs.size, dtype=np.uint8)
+    prof = np.zeros((dbs.size, 32), dtype=np.uint32) if profile else None
+    u8p, u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+    rc = lib.GhostmPathPileupHost(
+        qs.ctypes.data_as(u8p), qs.size // L, L, dbs.ctypes.data_as(u8p), dbs.size, None, len(qid),
+        qid.ctypes.data_as(u32p), p.ctypes.data_as(ctypes.POINTER(native.GhostmHitPath)), w.ctypes.data_as(u32p), w.size,
+        L, depth.ctypes.data_as(u32p), ident.ctypes.data_as(u32p), cons.ctypes.data_as(u8p),
+        prof.ctypes.data_as(u32p) if profile else None)
+    if rc != 0:
+        raise GhostmError(native.last_error())
+    return (depth, ident, cons, prof) if profile else (depth, ident, cons)
 
 
 class Aligner:
@@ -410,6 +459,45 @@ class Session:
         if m:
             lib.GhostmSessionRowBytes(self._h, rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), m)
         return rec, rows
+
+    def pileup(self) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(subjects, depth, identities, consensus): one SUBJECT_PILEUP_DTYPE
+        record per subject in db_id order (GhostmSessionPileup) and the
+        subjects' positions concatenated (GhostmSessionPileupArrays); subject i
+        is [offset, offset + length). After a run with any -y."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        n = lib.GhostmSessionPileup(self._h, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        subj = np.zeros(n, dtype=SUBJECT_PILEUP_DTYPE)
+        if n:
+            lib.GhostmSessionPileup(self._h, subj.ctypes.data_as(ctypes.POINTER(native.GhostmSubjectPileup)), n)
+        m = lib.GhostmSessionPileupArrays(self._h, None, None, None, 0)
+        if m == bad:
+            raise GhostmError(native.last_error())
+        depth = np.zeros(m, dtype=np.uint32)
+        ident = np.zeros(m, dtype=np.uint32)
+        cons = np.full(m, 255, dtype=np.uint8)
+        if m:
+            u32p = ctypes.POINTER(ctypes.c_uint32)
+            lib.GhostmSessionPileupArrays(self._h, depth.ctypes.data_as(u32p), ident.ctypes.data_as(u32p),
+                                          cons.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), m)
+        return subj, depth, ident, cons
+
+    def subject_profile(self, db_id: int) -> np.ndarray:
+        """The 32-slot rows of subject db_id, shape (length, 32)
+        (GhostmSessionSubjectProfile): made on demand, nothing is kept."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        n = lib.GhostmSessionSubjectProfile(self._h, db_id, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        prof = np.zeros(n, dtype=np.uint32)
+        if n and lib.GhostmSessionSubjectProfile(self._h, db_id, prof.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                 n) == bad:
+            raise GhostmError(native.last_error())
+        return prof.reshape(-1, 32)
 
     def device_hits(self, device="cuda"):
         """The hit records as a torch uint8 tensor on this session's GPU (32 bytes

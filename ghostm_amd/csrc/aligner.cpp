@@ -222,7 +222,8 @@ AlignerOptions ParseAlignerOptions(int argc, char **argv) {
   // small inputs); the oracle honours the same variable
   if (const char *e = getenv("GHOSTM_MAX_LIST_OVERRIDE")) o.max_list_length = (uint32_t)strtoul(e, nullptr, 10);
   o.matrix = ReadScoreMatrix(matrix_file);
-  if (o.output_style == 0 || (o.output_style >= 6 && o.output_style <= 9)) {  // 6 to 9: style 0's E-value and bit score
+  // 6 to 9: style 0's E-value and bit score; 10 and 11 (the pile-up) print none, like 1 and 2
+  if (o.output_style == 0 || (o.output_style >= 6 && o.output_style <= 9)) {
     // extension: GHOSTM_KARLIN=ungapped prices combinations the
     // reference's table lacks with the matrix's ungapped ideal parameters
     // (karlin_params.cpp); unset, they throw as the reference does
@@ -1477,7 +1478,9 @@ const LineFormat &Session::Format() {
   // -y 6 formats style-0 lines first: FormatTabular takes their identity,
   // E-value and bit-score bytes
   const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 9;
-  if (!format_) format_.reset(new LineFormat(tabular ? 0 : opt_.output_style, opt_.karlin, 4095));
+  // -y 10 and -y 11 replace the hit lines after the run: style 1's lines, which need no E-value, stand in
+  const bool pileup = opt_.output_style == 10 || opt_.output_style == 11;
+  if (!format_) format_.reset(new LineFormat(tabular ? 0 : pileup ? 1 : opt_.output_style, opt_.karlin, 4095));
   return *format_;
 }
 
@@ -1778,6 +1781,176 @@ const std::vector<uint8_t> &Session::RowBytes() {
   return row_bytes_;
 }
 
+// A subject's residues: every subject of a chunk is followed by one END.
+uint32_t Session::SubjectLength(const DbData &d, uint32_t subject) const {
+  const uint32_t next = subject + 1 < d.chunk.nseq ? d.chunk.starts[subject + 1] : d.chunk.len;
+  return next - d.chunk.starts[subject] - 1;
+}
+
+void Session::PileupChunk(size_t di, const std::vector<size_t> &items, uint32_t p0, uint32_t p1, uint32_t *depth,
+                          uint32_t *identities, uint8_t *consensus, uint32_t *profile) {
+  const std::vector<GhostmHitPath> &path = HitsPath();
+  const std::vector<GhostmHit> &hits = Hits();
+  // the hits by query chunk, their subject coordinates absolute in the chunk again
+  std::vector<std::vector<uint32_t>> qid(queries_.size());
+  std::vector<std::vector<GhostmHitPath>> rec(queries_.size());
+  for (size_t h : items) {
+    GhostmHitPath p = path[h];
+    const uint32_t pos = dbs_[di].chunk.starts[hits[h].db_id - dbs_[di].global_base];
+    p.s_start += pos;
+    p.s_end += pos;
+    qid[hit_source_[h].qi].push_back(hit_source_[h].query);
+    rec[hit_source_[h].qi].push_back(p);
+  }
+  std::vector<DeviceModule::PileupGroup> groups;
+  for (size_t qi = 0; qi < queries_.size(); ++qi)
+    if (!qid[qi].empty())
+      groups.push_back(DeviceModule::PileupGroup{queries_[qi].dev, (uint32_t)qid[qi].size(), qid[qi].data(),
+                                                 rec[qi].data()});
+  DeviceModule &dev = DeviceModule::Get();
+  const DeviceTimes before = dev.times();
+  dev.PathPileup(dbs_[di].dev, groups.data(), groups.size(), path_ops_.data(), path_ops_.size(), p0, p1, depth,
+                 identities, consensus, profile);
+  const DeviceTimes &after = dev.times();
+  stats_.seconds_pileup += after.pileup - before.pileup;
+  stats_.pileup_launches += after.pileup_launches - before.pileup_launches;
+  stats_.pileup_windows += after.pileup_windows - before.pileup_windows;
+  stats_.pileup_parts += after.pileup_parts - before.pileup_parts;
+  stats_.pileup_columns += after.pileup_columns - before.pileup_columns;
+}
+
+const std::vector<GhostmSubjectPileup> &Session::Pileup() {
+  if (pileup_valid_) return pileup_subj_;
+  HitsPath();
+  const std::vector<GhostmHit> &hits = Hits();
+  size_t nsubj = 0;
+  uint64_t total = 0;
+  for (const DbData &d : dbs_) {
+    nsubj = std::max<size_t>(nsubj, (size_t)d.global_base + d.chunk.nseq);
+    total += d.chunk.len - d.chunk.nseq;
+  }
+  pileup_subj_.assign(nsubj, GhostmSubjectPileup{0, 0, 0, 0, 0, 0, 0});
+  pileup_depth_.assign(total, 0);
+  pileup_ident_.assign(total, 0);
+  pileup_cons_.assign(total, 255);
+  // every subject's place: db_id order is chunk order, subject order within a chunk
+  std::vector<size_t> order(dbs_.size());
+  for (size_t di = 0; di < dbs_.size(); ++di) order[di] = di;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return dbs_[a].global_base < dbs_[b].global_base; });
+  uint64_t at = 0;
+  for (size_t di : order)
+    for (uint32_t s = 0; s < dbs_[di].chunk.nseq; ++s) {
+      GhostmSubjectPileup &x = pileup_subj_[dbs_[di].global_base + s];
+      x.length = SubjectLength(dbs_[di], s);
+      x.offset = at;
+      at += x.length;
+    }
+  std::vector<std::vector<size_t>> by_db(dbs_.size());
+  for (size_t h = 0; h < hits.size(); ++h) {
+    by_db[hit_source_[h].di].push_back(h);
+    ++pileup_subj_[hits[h].db_id].hits;
+  }
+  std::vector<uint32_t> depth, ident;
+  std::vector<uint8_t> cons;
+  for (size_t di = 0; di < dbs_.size(); ++di) {
+    if (by_db[di].empty()) continue;  // nothing landed on the chunk: zeros and 255s
+    const DbData &d = dbs_[di];
+    depth.assign(d.chunk.len, 0);
+    ident.assign(d.chunk.len, 0);
+    cons.assign(d.chunk.len, 255);
+    PileupChunk(di, by_db[di], 0, d.chunk.len, depth.data(), ident.data(), cons.data(), nullptr);
+    for (uint32_t s = 0; s < d.chunk.nseq; ++s) {
+      GhostmSubjectPileup &x = pileup_subj_[d.global_base + s];
+      if (!x.hits || !x.length) continue;
+      const uint32_t p = d.chunk.starts[s];
+      std::copy(depth.begin() + p, depth.begin() + p + x.length, pileup_depth_.begin() + x.offset);
+      std::copy(ident.begin() + p, ident.begin() + p + x.length, pileup_ident_.begin() + x.offset);
+      std::copy(cons.begin() + p, cons.begin() + p + x.length, pileup_cons_.begin() + x.offset);
+      for (uint32_t k = 0; k < x.length; ++k) {
+        const uint32_t v = depth[p + k];
+        x.covered += v > 0;
+        x.max_depth = std::max(x.max_depth, v);
+        x.depth_sum += v;
+        x.identities_sum += ident[p + k];
+      }
+    }
+  }
+  pileup_valid_ = true;
+  return pileup_subj_;
+}
+
+const std::vector<uint32_t> &Session::PileupDepth() {
+  Pileup();
+  return pileup_depth_;
+}
+
+const std::vector<uint32_t> &Session::PileupIdentities() {
+  Pileup();
+  return pileup_ident_;
+}
+
+const std::vector<uint8_t> &Session::PileupConsensus() {
+  Pileup();
+  return pileup_cons_;
+}
+
+std::vector<uint32_t> Session::SubjectProfile(uint32_t db_id, bool count_only) {
+  if (!count_only) HitsPath();
+  const std::vector<GhostmHit> &hits = Hits();
+  size_t di = 0;
+  while (di < dbs_.size() && !(db_id >= dbs_[di].global_base && db_id - dbs_[di].global_base < dbs_[di].chunk.nseq))
+    ++di;
+  if (di == dbs_.size()) throw Error("subject profile: db_id outside the loaded chunks");
+  const uint32_t s = db_id - dbs_[di].global_base, len = SubjectLength(dbs_[di], s);
+  std::vector<uint32_t> profile((size_t)len * 32, 0);
+  std::vector<size_t> items;
+  if (count_only) return profile;
+  for (size_t h = 0; h < hits.size(); ++h)
+    if (hits[h].db_id == db_id) items.push_back(h);
+  if (len && !items.empty()) {
+    const uint32_t p = dbs_[di].chunk.starts[s];
+    PileupChunk(di, items, p, p + len, nullptr, nullptr, nullptr, profile.data());
+  }
+  return profile;
+}
+
+// -y 10 and -y 11: one line per subject with at least one hit, in db_id order:
+// name, length, hits, covered, depth_sum, identities_sum, max_depth and, with
+// -y 11, the consensus text (the residue letter, '-' where depth > 0 and no
+// residue was seen, '.' where depth is 0). The text replaces the hit lines: it
+// goes into the first piece, the other pieces are emptied.
+void Session::FormatPileup() {
+  const std::vector<GhostmSubjectPileup> &subj = Pileup();
+  static const char kLetters[] = "ARNDCQEGHILKMFPSTWYVBJZX*";  // formats.cpp's order
+  std::string out;
+  for (const DbData &d : dbs_)
+    for (uint32_t s = 0; s < d.chunk.nseq; ++s) {
+      const GhostmSubjectPileup &x = subj[d.global_base + s];
+      if (!x.hits) continue;
+      out.append(d.chunk.names[s]);
+      const uint64_t cols[6] = {x.length, x.hits, x.covered, x.depth_sum, x.identities_sum, x.max_depth};
+      for (uint64_t v : cols) {
+        out.push_back('\t');
+        out.append(std::to_string(v));
+      }
+      if (opt_.output_style == 11) {
+        out.push_back('\t');
+        for (uint32_t k = 0; k < x.length; ++k) {
+          const uint8_t c = pileup_cons_[x.offset + k];
+          out.push_back(pileup_depth_[x.offset + k] == 0 ? '.' : c < 25 ? kLetters[c] : '-');
+        }
+      }
+      out.push_back('\n');
+    }
+  bool placed = false;
+  for (size_t k = 0; k < used_parts_; ++k)
+    for (std::string &t : parts_[k].text) {
+      t.clear();
+      if (!placed) t.swap(out), placed = true;
+    }
+  joined_valid_ = false;
+}
+
 // -y 8 and -y 9, from the -y 7 text FormatPathTabular left in the pieces (one
 // line per hit, thirteen columns) and the hits' rows. -y 8 appends positives,
 // the query row and the subject row to the line. -y 9 writes a block per hit:
@@ -2009,6 +2182,14 @@ void Session::DropResults() {
   row_bytes_.clear();
   row_bytes_.shrink_to_fit();
   hits_rows_valid_ = false;
+  pileup_subj_.clear();
+  pileup_depth_.clear();
+  pileup_depth_.shrink_to_fit();
+  pileup_ident_.clear();
+  pileup_ident_.shrink_to_fit();
+  pileup_cons_.clear();
+  pileup_cons_.shrink_to_fit();
+  pileup_valid_ = false;
 }
 
 void Session::Run(bool stream_to_file) {
@@ -2018,8 +2199,8 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  // -y 6 to -y 9 are written after the post-pass (HitsExt, HitsPath, HitsRows), not while the search runs
-  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 9;
+  // -y 6 to -y 11 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup), not while the search runs
+  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 11;
   if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
@@ -2118,9 +2299,10 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    if (opt_.output_style == 6) FormatTabular();
+    if (opt_.output_style >= 10) FormatPileup();
+    else if (opt_.output_style == 6) FormatTabular();
     else FormatPathTabular();
-    if (opt_.output_style >= 8) FormatRows();
+    if (opt_.output_style == 8 || opt_.output_style == 9) FormatRows();
     if (stream_to_file) {
       WriteOutputFile();
       streamed_ = true;

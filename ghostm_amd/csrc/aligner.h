@@ -192,6 +192,23 @@ class Session {
   // next query set. With -y 8 and -y 9 Run makes them and the text.
   const std::vector<GhostmHitRows> &HitsRows();
   const std::vector<uint8_t> &RowBytes();
+  // The subject pile-up of the last run's hits (include/ghostm_hip.h): one
+  // GhostmSubjectPileup per subject over all DB chunks in db_id order, and the
+  // subjects' depth, identities and consensus concatenated without the END
+  // separators. A post-pass of DeviceModule::PathPileup over HitsPath() with
+  // the records HitsExt() resolved: per DB chunk one call, which goes window by
+  // window and, inside a window, query chunk by query chunk; the summary is
+  // made here from the arrays that came back. Computed on first use, kept until
+  // the next run or the next query set. With -y 10 and -y 11 Run makes them and
+  // the text.
+  const std::vector<GhostmSubjectPileup> &Pileup();
+  const std::vector<uint32_t> &PileupDepth();
+  const std::vector<uint32_t> &PileupIdentities();
+  const std::vector<uint8_t> &PileupConsensus();
+  // The 32-slot rows of one subject (length x 32), made on demand by the same
+  // kernels on that subject's hits only; nothing is kept.
+  // count_only: zeros of that size, no device work.
+  std::vector<uint32_t> SubjectProfile(uint32_t db_id, bool count_only = false);
   // Hit records of the last run in device memory (this session's GPU): copies
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
@@ -308,6 +325,14 @@ class Session {
   // -y 9: the pairwise view (a '#' line of the first fourteen columns, the
   // three rows, an empty line). Both rewrite the -y 7 text of FormatPathTabular.
   void FormatRows();
+  // -y 10 and -y 11: replaces the parts' text by one line per subject with hits
+  void FormatPileup();
+  // One PathPileup call on DB chunk di for the hits `items` (indices of Hits()),
+  // grouped by query chunk, over the chunk's positions [p0, p1); adds the
+  // device's counters to stats_.
+  void PileupChunk(size_t di, const std::vector<size_t> &items, uint32_t p0, uint32_t p1, uint32_t *depth,
+                   uint32_t *identities, uint8_t *consensus, uint32_t *profile);
+  uint32_t SubjectLength(const DbData &d, uint32_t subject) const;
 
   AlignerOptions opt_;
   uint64_t shard_begin_ = 0, shard_end_ = UINT64_MAX;  // query range over the loaded chunks
@@ -340,6 +365,10 @@ class Session {
   std::vector<GhostmHitRows> hits_rows_;
   std::vector<uint8_t> row_bytes_;
   bool hits_rows_valid_ = false;
+  std::vector<GhostmSubjectPileup> pileup_subj_;
+  std::vector<uint32_t> pileup_depth_, pileup_ident_;
+  std::vector<uint8_t> pileup_cons_;
+  bool pileup_valid_ = false;
   bool records_on_device_ = false;
   GhostmStats stats_{};
   unsigned threads_ = 1;

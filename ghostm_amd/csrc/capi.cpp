@@ -278,6 +278,51 @@ size_t GhostmSessionRowBytes(void *s, uint8_t *rows, size_t cap) {
   }
 }
 
+size_t GhostmSessionPileup(void *s, GhostmSubjectPileup *subj, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmSubjectPileup> &p = static_cast<Session *>(s)->Pileup();
+    if (!subj) return p.size();
+    const size_t n = std::min(cap, p.size());
+    std::memcpy(subj, p.data(), n * sizeof(GhostmSubjectPileup));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionPileupArrays(void *s, uint32_t *depth, uint32_t *identities, uint8_t *consensus, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    Session *ses = static_cast<Session *>(s);
+    const std::vector<uint32_t> &d = ses->PileupDepth();
+    if (!depth && !identities && !consensus) return d.size();
+    const size_t n = std::min(cap, d.size());
+    if (depth && n) std::memcpy(depth, d.data(), n * 4);
+    if (identities && n) std::memcpy(identities, ses->PileupIdentities().data(), n * 4);
+    if (consensus && n) std::memcpy(consensus, ses->PileupConsensus().data(), n);
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionSubjectProfile(void *s, uint32_t db_id, uint32_t *profile, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<uint32_t> p = static_cast<Session *>(s)->SubjectProfile(db_id, !profile);
+    if (!profile) return p.size();
+    const size_t n = std::min(cap, p.size());
+    if (n) std::memcpy(profile, p.data(), n * 4);
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
 size_t GhostmSessionDeviceHits(void *s, void *dst_device, size_t cap) {
   try {
     if (!s) throw Error("null session");

@@ -103,6 +103,9 @@ struct DeviceTimes {
   uint64_t traceback_path_dir_bytes = 0;          // direction-buffer bytes of the batches
   double path_rows = 0;                           // the aligned rows (k_path_rows): seconds,
   uint64_t path_rows_launches = 0, path_rows_columns = 0, path_rows_bytes = 0;  // batches, columns, row bytes
+  double pileup = 0;                              // the subject pile-up (k_pileup + k_pileup_finish): seconds,
+  uint64_t pileup_launches = 0, pileup_windows = 0, pileup_parts = 0, pileup_columns = 0;  // k_pileup launches,
+                                                  // profile windows, (tile, part) workgroups, columns added
 };
 
 class DeviceModule {
@@ -272,6 +275,28 @@ class DeviceModule {
   size_t PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const GhostmHitPath *rec,
                   const uint32_t *ops, size_t ops_len, int open, int ext, uint32_t record_base,
                   GhostmHitRows *out, uint8_t *rows, size_t rows_cap, const uint64_t *dst_off);
+
+  // The pile-up of hits on positions [p0, p1) of the resident DB chunk d
+  // (kern::k_pileup, kern::k_pileup_finish; include/ghostm_hip.h has the
+  // definitions). The hits come in groups, one per query chunk: group g's hit i
+  // lies in record qid[i] of chunk q, rec[i] as for PathRows, the words in
+  // ops[ops_len]. Every group is checked first (ValidatePathRows; throws with
+  // the reason before any upload or launch, the outputs untouched). depth,
+  // identities, consensus (p1 - p0 elements) and profile ((p1 - p0) x 32) may
+  // each be null. The tiles meeting [p0, p1) are cut into windows whose profile
+  // fits GHOSTM_PILEUP_SCRATCH_MB (pileup_plan.h); per window: a memset, one
+  // k_pileup launch per group and upload batch with hits there (at most
+  // GHOSTM_PILEUP_BATCH_HITS hits), k_pileup_finish, and the read-back. Adds its
+  // device time, launches, windows, parts and columns to times().
+  struct PileupGroup {
+    DevQuery *q;
+    uint32_t n;
+    const uint32_t *qid;
+    const GhostmHitPath *rec;
+  };
+  void PathPileup(DevDb *d, const PileupGroup *groups, size_t ngroups, const uint32_t *ops, size_t ops_len,
+                  uint32_t p0, uint32_t p1, uint32_t *depth, uint32_t *identities, uint8_t *consensus,
+                  uint32_t *profile);
 
   DeviceTimes &times() {
     SettleSeedTime();

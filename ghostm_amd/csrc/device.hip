@@ -19,6 +19,7 @@
 #include "hit_batches.h"
 #include "kernels.h"
 #include "path_rows.h"
+#include "pileup_plan.h"
 #include "qformat.h"
 #include "score_tasks.h"
 
@@ -278,6 +279,8 @@ struct DeviceModule::Impl {
   DevBuf tb_path_in, tb_path_meta, tb_path_dir, tb_path_ops, tb_path_cmp;
   // PathRows: a batch's per-hit inputs, its words, its counts and its row bytes
   DevBuf path_rows_hit, path_rows_ops, path_rows_out, path_rows_buf;
+  // PathPileup: a batch's hits, words, plan lists and parts; a window's profile and finished arrays; the column counter
+  DevBuf pileup_hit, pileup_ops, pileup_list, pileup_part, pileup_prof, pileup_out, pileup_cols;
   DevBuf tb_width, tb_ncols, tb_skey, tb_key, tb_order1, tb_order2, tb_sort, tb_pair_a, tb_pair_b, tb_best;
   int cus = 256;
   // K4 work
@@ -2438,12 +2441,150 @@ size_t DeviceModule::PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t 
   return total;
 }
 
+static_assert(kern::kPileupTileMax == kPileupTileMax, "the kernel's LDS histogram holds the plan's largest tile");
+
+void DeviceModule::PathPileup(DevDb *d, const PileupGroup *groups, size_t ngroups, const uint32_t *ops,
+                              size_t ops_len, uint32_t p0, uint32_t p1, uint32_t *depth, uint32_t *identities,
+                              uint8_t *consensus, uint32_t *profile) {
+  Use();
+  Impl &I = *impl_;
+  if (p0 > p1 || p1 > d->len) throw Error("pileup: positions outside the resident chunk (db_len)");
+  // every index the kernels will use, checked here: nothing is uploaded or launched for a refused call
+  std::vector<std::vector<uint32_t>> span(ngroups);  // per hit: its subject residues
+  for (size_t g = 0; g < ngroups; ++g) {
+    const PileupGroup &G = groups[g];
+    if (G.n == 0) continue;
+    const std::string why = ValidatePathRows(G.q->nseq, G.q->L, d->len, G.n, G.qid, G.rec, ops, ops_len, nullptr);
+    if (!why.empty()) throw Error("pileup: " + why);
+    span[g].resize(G.n);
+    for (uint32_t k = 0; k < G.n; ++k) {
+      uint32_t s = 0;
+      for (uint32_t r = 0; r < G.rec[k].n_runs; ++r) {
+        const uint32_t w = ops[G.rec[k].ops_offset + r];
+        if ((w & 3u) != 2u) s += w >> 4;
+      }
+      span[g][k] = s;
+    }
+  }
+  if (p0 == p1) return;
+  const uint32_t T = PileupClampTile(EnvSize("GHOSTM_PILEUP_TILE", kPileupTileDefault));
+  const uint32_t P = (uint32_t)std::min<size_t>(EnvSize("GHOSTM_PILEUP_PART_HITS", kPileupPartDefault), UINT32_MAX);
+  const size_t budget = EnvSize("GHOSTM_PILEUP_SCRATCH_MB", 1024) << 20;
+  const size_t max_hits = EnvSize("GHOSTM_PILEUP_BATCH_HITS", (size_t)1 << 22);
+  const size_t upload_budget = (size_t)256 << 20;  // a batch's hit records, words and plan
+  const uint32_t t_lo = p0 / T, t_hi = (p1 - 1) / T + 1;
+  const std::vector<uint32_t> win =
+      PileupWindows((uint32_t)std::min<uint64_t>((uint64_t)(t_hi - t_lo) * T, UINT32_MAX), T, budget);
+  I.pileup_cols.Reserve(8);
+  unsigned long long *cols_d = I.pileup_cols.as<unsigned long long>();
+  HIP_CHECK(hipMemsetAsync(cols_d, 0, 8, S(stream_)));
+  std::vector<uint32_t> sel, words;
+  std::vector<kern::PileupHit> hh;
+  PileupPlan plan;
+  for (size_t w = 0; w + 1 < win.size(); ++w) {
+    const uint32_t ta = t_lo + win[w], tb = t_lo + win[w + 1];
+    const uint32_t win0 = ta * T, win1 = (uint32_t)std::min<uint64_t>((uint64_t)tb * T, d->len);
+    const uint32_t npos = win1 - win0;
+    I.pileup_prof.Reserve((size_t)npos * kPileupSlots * 4);
+    HIP_CHECK(hipMemsetAsync(I.pileup_prof.p, 0, (size_t)npos * kPileupSlots * 4, S(stream_)));
+    for (size_t g = 0; g < ngroups; ++g) {
+      const PileupGroup &G = groups[g];
+      // the group's hits that meet the window, in hit order
+      sel.clear();
+      for (uint32_t k = 0; k < G.n; ++k)
+        if (span[g][k] && G.rec[k].s_start < win1 && (uint64_t)G.rec[k].s_start + span[g][k] > win0) sel.push_back(k);
+      const uint32_t n = (uint32_t)sel.size();
+      for (uint32_t b0 = 0, b1 = 0; b0 < n; b0 = b1) {
+        // hits sel[b0, b1): an upload batch (hit_batches.h), cut by its records, words and list entries
+        size_t bytes = 0;
+        b1 = CutBatch(b0, n, max_hits, upload_budget, [&](uint32_t s) {
+          return sizeof(kern::PileupHit) + 4 * (size_t)G.rec[sel[s]].n_runs + 4 * ((size_t)span[g][sel[s]] / T + 2);
+        }, &bytes);
+        const uint32_t m = b1 - b0;
+        if (!BuildPileupPlan(m, [&](uint32_t s) { return G.rec[sel[b0 + s]].s_start; },
+                             [&](uint32_t s) { return span[g][sel[b0 + s]]; }, T, ta, tb, P, &plan))
+          throw Error("pileup: a batch's plan exceeds 2^32 - 1 entries (lower GHOSTM_PILEUP_BATCH_HITS)");
+        if (plan.parts.empty()) continue;
+        hh.resize(m);
+        words.clear();
+        for (uint32_t s = 0; s < m; ++s) {
+          const GhostmHitPath &p = G.rec[sel[b0 + s]];
+          hh[s] = kern::PileupHit{G.qid[sel[b0 + s]], p.q_start, p.s_start, p.n_runs, words.size()};
+          words.insert(words.end(), ops + p.ops_offset, ops + p.ops_offset + p.n_runs);
+        }
+        static_assert(sizeof(kern::PileupPartArg) == sizeof(PileupPart), "the plan's parts are uploaded as they are");
+        const size_t nparts = plan.parts.size();
+        I.pileup_hit.Reserve((size_t)m * sizeof(kern::PileupHit));
+        I.pileup_ops.Reserve(words.size() * 4);
+        I.pileup_list.Reserve(plan.list.size() * 4);
+        I.pileup_part.Reserve(nparts * sizeof(PileupPart));
+        HIP_CHECK(hipMemcpyAsync(I.pileup_hit.p, hh.data(), (size_t)m * sizeof(kern::PileupHit), hipMemcpyHostToDevice,
+                                 S(stream_)));
+        HIP_CHECK(hipMemcpyAsync(I.pileup_ops.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, S(stream_)));
+        HIP_CHECK(hipMemcpyAsync(I.pileup_list.p, plan.list.data(), plan.list.size() * 4, hipMemcpyHostToDevice,
+                                 S(stream_)));
+        HIP_CHECK(hipMemcpyAsync(I.pileup_part.p, plan.parts.data(), nparts * sizeof(PileupPart), hipMemcpyHostToDevice,
+                                 S(stream_)));
+        kern::PileupArgs a{};
+        a.qseq = G.q->seq.as<uint8_t>();
+        a.L = G.q->L;
+        a.hit = I.pileup_hit.as<kern::PileupHit>();
+        a.ops = I.pileup_ops.as<uint32_t>();
+        a.list = I.pileup_list.as<uint32_t>();
+        a.part = I.pileup_part.as<kern::PileupPartArg>();
+        a.T = T;
+        a.win0 = win0;
+        a.win1 = win1;
+        a.profile = I.pileup_prof.as<uint32_t>();
+        a.columns = cols_d;
+        if (nparts > 0x7FFFFFFFu) throw Error("pileup: too many parts in one launch (lower GHOSTM_PILEUP_BATCH_HITS)");
+        const dim3 grid((uint32_t)nparts), block(kern::kTbBlock);  // one workgroup per (tile, part)
+        TimedLaunch(I.ev0, I.ev1, S(stream_), [&] { hipLaunchKernelGGL(kern::k_pileup, grid, block, 0, S(stream_), a); });
+        HIP_CHECK(hipStreamSynchronize(S(stream_)));
+        times_.pileup += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+        times_.pileup_launches += 1;
+        times_.pileup_parts += nparts;
+      }
+    }
+    // the window's positions finished; those inside [p0, p1) go back
+    I.pileup_out.Reserve((size_t)npos * 9);
+    kern::PileupFinishArgs f{};
+    f.profile = I.pileup_prof.as<uint32_t>();
+    f.db = d->Residues() + win0;
+    f.n = npos;
+    f.depth = I.pileup_out.as<uint32_t>();
+    f.identities = f.depth + npos;
+    f.consensus = reinterpret_cast<uint8_t *>(f.identities + npos);
+    const dim3 fgrid((npos + kern::kTbBlock - 1) / kern::kTbBlock), block(kern::kTbBlock);
+    TimedLaunch(I.ev0, I.ev1, S(stream_),
+                [&] { hipLaunchKernelGGL(kern::k_pileup_finish, fgrid, block, 0, S(stream_), f); });
+    const uint32_t c0 = std::max(win0, p0), c1 = std::min(win1, p1);
+    if (c0 < c1) {
+      const size_t cn = c1 - c0, from = c0 - win0, to = c0 - p0;
+      if (depth) HIP_CHECK(hipMemcpyAsync(depth + to, f.depth + from, cn * 4, hipMemcpyDeviceToHost, S(stream_)));
+      if (identities)
+        HIP_CHECK(hipMemcpyAsync(identities + to, f.identities + from, cn * 4, hipMemcpyDeviceToHost, S(stream_)));
+      if (consensus) HIP_CHECK(hipMemcpyAsync(consensus + to, f.consensus + from, cn, hipMemcpyDeviceToHost, S(stream_)));
+      if (profile)
+        HIP_CHECK(hipMemcpyAsync(profile + to * kPileupSlots, f.profile + from * kPileupSlots, cn * kPileupSlots * 4,
+                                 hipMemcpyDeviceToHost, S(stream_)));
+    }
+    HIP_CHECK(hipStreamSynchronize(S(stream_)));
+    times_.pileup += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+    times_.pileup_windows += 1;
+  }
+  unsigned long long cols = 0;
+  HIP_CHECK(hipMemcpyAsync(&cols, cols_d, 8, hipMemcpyDeviceToHost, S(stream_)));
+  HIP_CHECK(hipStreamSynchronize(S(stream_)));
+  times_.pileup_columns += cols;
+}
+
 const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_amd/srchash.py)
 
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_pileup/k_pileup_finish, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -2801,6 +2942,26 @@ int PathRowsGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPath 
     const size_t used = DeviceModule::Get().PathRows(r.query, r.db, nhits, query_ids, rec, ops, ops_len, open_gap,
                                                      extend_gap, 0, out, rows, rows_cap, nullptr);
     if (rows_used) *rows_used = used;
+    return 0;
+  } catch (std::exception &e) {
+    SetError(e.what());
+    return 1;
+  }
+}
+
+int PathPileupGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPath rec[], const uint32_t ops[],
+                  size_t ops_len, uint32_t query_sequence_length, uint32_t db_len, uint32_t depth[],
+                  uint32_t identities[], uint8_t consensus[], uint32_t profile[]) {
+  try {
+    if (!depth || !identities || !consensus) throw Error("PathPileupGpu: null output array");
+    if (nhits && (!query_ids || !rec)) throw Error("PathPileupGpu: null hit arrays");
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    if (!r.query || !r.db) throw Error("SetQueryGpu/SetDbGpu not called");
+    if (query_sequence_length != r.query->L) throw Error("query shape differs from SetQueryGpu");
+    if (db_len != r.db->len) throw Error("PathPileupGpu: db_len differs from the resident chunk's");
+    const DeviceModule::PileupGroup g{r.query, nhits, query_ids, rec};
+    DeviceModule::Get().PathPileup(r.db, &g, 1, ops, ops_len, 0, db_len, depth, identities, consensus, profile);
     return 0;
   } catch (std::exception &e) {
     SetError(e.what());

@@ -3387,6 +3387,148 @@ __global__ __launch_bounds__(kTbBlock) void k_path_rows(PathRowsArgs a) {
   }
 }
 
+// ------------------------------------------------------------------ subject pile-up
+// k_pileup: the hits' columns added into the profile of a window of the DB
+// chunk (32 counters per position: query codes 0..24, 25 for every code from 25
+// up, 26 for a 'D' column; include/ghostm_hip.h). One workgroup per (tile,
+// part) of the host's plan (pileup_plan.h): a tile is T consecutive positions,
+// a part at most P of the hits that meet it. The workgroup zeroes its LDS
+// histogram of the tile, its waves take the part's hits one at a time and walk
+// their columns as k_path_rows does (64 runs at a time, three wave scans with a
+// carry, the six-step run search), and a lane whose column lies in the tile
+// does one LDS atomic add on (position - tile0, slot). A position's row has a
+// stride of 33 dwords: consecutive lanes hit consecutive positions, mostly
+// with few distinct slots, and a stride of 32 would put a wave on one bank. At
+// the end the non-zero counters go to the window's profile, zeroed by the
+// host, with return-less global atomic adds: one per touched counter and part,
+// consecutive lanes on consecutive dwords of a row. All sums are integer, so
+// the result does not depend on the order of anything. The host has checked
+// every index (ValidatePathRows, the plan's tiles inside the window).
+constexpr uint32_t kPileupTileMax = 256;  // = ghostm::kPileupTileMax (pileup_plan.h, checked in device.hip)
+constexpr uint32_t kPileupStride = 33;
+struct PileupHit {
+  uint32_t qid, q_start, s_start, n_runs;
+  unsigned long long ops_off;  // first word of the hit in ops
+};
+struct PileupPartArg {
+  uint32_t tile, first, count;  // tile: absolute in the chunk; list[first .. first + count)
+};
+struct PileupArgs {
+  const uint8_t *qseq;
+  uint32_t L;
+  const PileupHit *hit;
+  const uint32_t *ops;
+  const uint32_t *list;          // the plan's hit slots, per tile
+  const PileupPartArg *part;     // one per workgroup
+  uint32_t T;                    // positions per tile, 32..kPileupTileMax
+  uint32_t win0, win1;           // the window's positions [win0, win1), win0 a multiple of T
+  uint32_t *profile;             // (win1 - win0) x 32
+  unsigned long long *columns;   // += the '=', 'X' and 'D' columns added
+};
+
+__global__ __launch_bounds__(kTbBlock) void k_pileup(PileupArgs a) {
+  GHOSTM_POISON_LDS();
+  __shared__ uint32_t s_cnt[kPileupTileMax * kPileupStride];
+  for (uint32_t e = threadIdx.x; e < a.T * kPileupStride; e += kTbBlock) s_cnt[e] = 0;
+  __syncthreads();
+
+  const uint32_t lane = threadIdx.x & 63;
+  const PileupPartArg part = a.part[blockIdx.x];
+  const uint32_t tile0 = part.tile * a.T;
+  const uint32_t tile1 = a.win1 - tile0 < a.T ? a.win1 : tile0 + a.T;
+  uint32_t added = 0;
+  for (uint32_t i = threadIdx.x >> 6; i < part.count; i += kTbBlock / 64) {  // wave-uniform
+    const PileupHit hit = a.hit[a.list[part.first + i]];
+    const uint8_t *qs = a.qseq + (size_t)hit.qid * a.L;
+    const uint32_t *words = a.ops + hit.ops_off;
+    uint32_t col0 = 0, q0 = hit.q_start, s0 = hit.s_start;  // of the group's first run
+    for (uint32_t r0 = 0; r0 < hit.n_runs && s0 < tile1; r0 += 64) {
+      const uint32_t w = r0 + lane < hit.n_runs ? words[r0 + lane] : 0u;  // past the last run: length 0
+      const uint32_t len = w >> 4, op = w & 3u;
+      uint32_t tc, tq, ts;
+      const uint32_t c = col0 + WaveExclusiveScan(len, &tc);
+      const uint32_t q = q0 + WaveExclusiveScan(op != 3u ? len : 0u, &tq);
+      const uint32_t s = s0 + WaveExclusiveScan(op != 2u ? len : 0u, &ts);
+      const uint32_t c1 = col0 + tc;
+      if (s0 + ts > tile0) {  // the group's subject residues meet the tile
+        for (uint32_t base = col0; base < c1; base += 64) {
+          const bool on = base + lane < c1;
+          const uint32_t col = on ? base + lane : c1 - 1;
+          // the last lane whose run begins at or before col (the lanes past the last run begin at c1)
+          uint32_t r = 0;
+#pragma unroll
+          for (uint32_t step = 32; step; step >>= 1) {
+            const uint32_t v = (uint32_t)__shfl((int)c, (int)(r + step));
+            if (v <= col) r += step;
+          }
+          const uint32_t k = col - (uint32_t)__shfl((int)c, (int)r);
+          const uint32_t rq = (uint32_t)__shfl((int)q, (int)r), rs = (uint32_t)__shfl((int)s, (int)r);
+          const uint32_t rop = (uint32_t)__shfl((int)op, (int)r);
+          const uint32_t p = rs + k;
+          if (on && rop != 2u && p >= tile0 && p < tile1) {
+            uint32_t slot = 26;
+            if (rop != 3u) {
+              const uint32_t qc = qs[rq + k];
+              slot = qc < 25u ? qc : 25u;
+            }
+            atomicAdd(&s_cnt[(p - tile0) * kPileupStride + slot], 1u);
+            ++added;
+          }
+        }
+      }
+      col0 = c1;
+      q0 += tq;
+      s0 += ts;
+    }
+  }
+  __syncthreads();
+  uint32_t *out = a.profile + (size_t)(tile0 - a.win0) * 32;
+  for (uint32_t e = threadIdx.x; e < (tile1 - tile0) * 32; e += kTbBlock) {
+    const uint32_t v = s_cnt[(e >> 5) * kPileupStride + (e & 31u)];
+    if (v) atomicAdd(out + e, v);
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) added += __shfl_xor(added, d);
+  if (lane == 0 && added) atomicAdd(a.columns, (unsigned long long)added);
+}
+
+// k_pileup_finish: one thread per position of the window reads its counters as
+// 128-bit loads (seven: slots 28..31 are never set) and writes the position's depth (slots 0..26), its
+// identities (the slot of the DB residue) and its consensus (the largest of
+// slots 0..24, the lowest on a tie, 255 when they are all zero). It writes no
+// profile bytes.
+struct PileupFinishArgs {
+  const uint32_t *profile;  // n x 32, 16-byte aligned
+  const uint8_t *db;        // the window's first residue
+  uint32_t n;
+  uint32_t *depth, *identities;
+  uint8_t *consensus;
+};
+
+__global__ __launch_bounds__(kTbBlock) void k_pileup_finish(PileupFinishArgs a) {
+  GHOSTM_POISON_LDS();
+  const uint32_t i = blockIdx.x * kTbBlock + threadIdx.x;
+  if (i >= a.n) return;
+  const uint4 *row = reinterpret_cast<const uint4 *>(a.profile + (size_t)i * 32);
+  const uint32_t code = a.db[i], mine = code < 25u ? code : 25u;
+  uint32_t sum = 0, best = 0, arg = 255, ident = 0;
+#pragma unroll
+  for (uint32_t v = 0; v < 7; ++v) {
+    const uint4 x = row[v];
+    const uint32_t c[4] = {x.x, x.y, x.z, x.w};
+#pragma unroll
+    for (uint32_t j = 0; j < 4; ++j) {
+      const uint32_t slot = v * 4 + j;
+      if (slot < 27) sum += c[j];
+      if (slot < 25 && c[j] > best) best = c[j], arg = slot;
+      if (slot == mine) ident = c[j];
+    }
+  }
+  a.depth[i] = sum;
+  a.identities[i] = ident;
+  a.consensus[i] = (uint8_t)arg;
+}
+
 // FRAME (FINAL only, round 6): every key of column j is stored with FR_j =
 // j * (-ext) added to its h field, as K2's column frame, so E's extension needs
 // no add: E'(j) = max3(A', Bfi(HIGH, E'(j-1), A'), zero'(j)) with A' = K'(j-1) +

@@ -82,6 +82,21 @@ class GhostmHitRows(ctypes.Structure):
     ]
 
 
+class GhostmSubjectPileup(ctypes.Structure):
+    """one subject's summary of the pile-up (40 bytes); offset is its first
+    element in the session-level depth / identities / consensus arrays."""
+
+    _fields_ = [
+        ("length", c_uint32),
+        ("hits", c_uint32),
+        ("covered", c_uint32),
+        ("max_depth", c_uint32),
+        ("depth_sum", c_uint64),
+        ("identities_sum", c_uint64),
+        ("offset", c_uint64),
+    ]
+
+
 class GhostmStats(ctypes.Structure):
     _fields_ = [
         ("seconds_total", ctypes.c_double),
@@ -144,6 +159,11 @@ class GhostmStats(ctypes.Structure):
         ("path_rows_launches", c_uint64),
         ("path_rows_columns", c_uint64),
         ("path_rows_bytes", c_uint64),
+        ("seconds_pileup", ctypes.c_double),
+        ("pileup_launches", c_uint64),
+        ("pileup_windows", c_uint64),
+        ("pileup_parts", c_uint64),
+        ("pileup_columns", c_uint64),
     ]
 
     def as_dict(self) -> dict:
@@ -192,6 +212,11 @@ SIGNATURES = {
                                    POINTER(c_int), c_uint32, u32p, POINTER(GhostmHitPath), u32p, c_size_t, c_uint32,
                                    c_int, c_int, POINTER(GhostmHitRows), POINTER(ctypes.c_uint8), c_size_t,
                                    POINTER(c_size_t)]),
+    "PathPileupGpu": (c_int, [c_uint32, u32p, POINTER(GhostmHitPath), u32p, c_size_t, c_uint32, c_uint32, u32p, u32p,
+                              POINTER(ctypes.c_uint8), u32p]),
+    "GhostmPathPileupHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, POINTER(ctypes.c_uint8), c_uint32,
+                                     POINTER(c_int), c_uint32, u32p, POINTER(GhostmHitPath), u32p, c_size_t, c_uint32,
+                                     u32p, u32p, POINTER(ctypes.c_uint8), u32p]),
     "GhostmBuildIndexGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, u32p, u32p, u32p, c_int,
                                     POINTER(c_float)]),
     "GhostmFormatQueriesGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_uint32,
@@ -223,6 +248,9 @@ SIGNATURES = {
     "GhostmSessionPathOps": (c_size_t, [c_void_p, u32p, c_size_t]),
     "GhostmSessionHitsRows": (c_size_t, [c_void_p, POINTER(GhostmHitRows), c_size_t]),
     "GhostmSessionRowBytes": (c_size_t, [c_void_p, POINTER(ctypes.c_uint8), c_size_t]),
+    "GhostmSessionPileup": (c_size_t, [c_void_p, POINTER(GhostmSubjectPileup), c_size_t]),
+    "GhostmSessionPileupArrays": (c_size_t, [c_void_p, u32p, u32p, POINTER(ctypes.c_uint8), c_size_t]),
+    "GhostmSessionSubjectProfile": (c_size_t, [c_void_p, c_uint32, u32p, c_size_t]),
     "GhostmSessionDeviceHits": (c_size_t, [c_void_p, c_void_p, c_size_t]),
     "GhostmSessionStats": (c_int, [c_void_p, POINTER(GhostmStats)]),
     "GhostmSessionStatsSized": (c_size_t, [c_void_p, POINTER(GhostmStats), c_size_t]),

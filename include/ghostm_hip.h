@@ -255,6 +255,63 @@ int GhostmPathRowsHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, const
                        size_t ops_len, uint32_t query_sequence_length, int open_gap, int extend_gap,
                        GhostmHitRows out[], uint8_t rows[], size_t rows_cap, size_t *rows_used);
 
+/* The subject pile-up: what a set of hits says about every position of a DB
+ * chunk. All of it is integer sums, so a result does not depend on the order
+ * of the hits or of the additions. With slot(c) = c for c < 25 and 25
+ * otherwise, a profile row is 32 uint32_t per position p:
+ *   a '=' or 'X' column at p adds 1 to profile[p][slot(query code)]
+ *   a 'D' column at p adds 1 to profile[p][26]
+ *   an 'I' column touches no subject position and adds nothing
+ *   slots 27..31 stay 0
+ *   depth[p]      = the sum of slots 0..26
+ *   identities[p] = profile[p][slot(db[p])]
+ *   consensus[p]  = the slot in 0..24 with the largest count, the lowest slot
+ *                   winning a tie; 255 when slots 0..24 are all zero
+ * A hit with an empty path adds nothing.
+ *
+ * PathPileupGpu (kernels k_pileup and k_pileup_finish) is stage level like
+ * PathRowsGpu (after SetQueryGpu and SetDbGpu) and takes the same hits:
+ * query_ids[i], rec[i] (q_start, s_start absolute in the chunk, n_runs words at
+ * ops[ops_offset]). db_len must be the resident chunk's length; depth,
+ * identities and consensus hold db_len elements, profile db_len * 32 or is
+ * NULL. nhits == 0 gives zeros and 255s. Everything is checked on the host
+ * before any upload or launch; a refused call leaves every output untouched
+ * and names its reason in GhostmGetLastError: PathRowsGpu's "ops", "word",
+ * "bounds" and "query", "db_len" when db_len is not the resident chunk's
+ * length, and "null" for a null depth, identities or consensus, or null hit
+ * arrays with nhits > 0.
+ * The chunk's positions are cut into tiles of GHOSTM_PILEUP_TILE positions
+ * (32..256, default 256) and every tile's hits into parts of
+ * GHOSTM_PILEUP_PART_HITS hits (default 512), one workgroup per (tile, part);
+ * the profile exists on the device one window of whole tiles at a time, a
+ * window fitting GHOSTM_PILEUP_SCRATCH_MB (default 1024; a position costs
+ * 128 bytes), so a chunk may be far larger than device memory / 128. Hits and
+ * words are uploaded in batches of at most GHOSTM_PILEUP_BATCH_HITS hits. */
+int PathPileupGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPath rec[],
+                  const uint32_t ops[], size_t ops_len, uint32_t query_sequence_length,
+                  uint32_t db_len, uint32_t depth[], uint32_t identities[], uint8_t consensus[],
+                  uint32_t profile[]);
+
+/* The same on the host, with no device call (the model the kernels are checked
+ * against) and the same checks and reasons; the argument head is
+ * GhostmPathRowsHost's (score_matrix is not read and may be NULL). */
+int GhostmPathPileupHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, const uint8_t *db,
+                         uint32_t db_len, const int score_matrix[], uint32_t nhits,
+                         const uint32_t query_ids[], const GhostmHitPath rec[], const uint32_t ops[],
+                         size_t ops_len, uint32_t query_sequence_length, uint32_t depth[],
+                         uint32_t identities[], uint8_t consensus[], uint32_t profile[]);
+
+/* One subject's summary of the session-level pile-up (GhostmSessionPileup). */
+typedef struct GhostmSubjectPileup {   /* 40 bytes */
+  uint32_t length;          /* the subject's residues */
+  uint32_t hits;            /* hits on it, those with an empty path included */
+  uint32_t covered;         /* positions with depth > 0 */
+  uint32_t max_depth;
+  uint64_t depth_sum;
+  uint64_t identities_sum;
+  uint64_t offset;          /* the subject's first element in the session-level arrays */
+} GhostmSubjectPileup;
+
 /* The `db` formatter's k-mer index of one DB chunk, built on the GPU
  * (replaces DBCreator::ConstructIndex, db_creator.cpp:167-241).
  * seq[len] = the chunk's END-separated residues (.seq); seed = the index seed mask
@@ -388,6 +445,14 @@ typedef struct GhostmStats {
   uint64_t path_rows_launches;      /* batches of hits (one launch each) */
   uint64_t path_rows_columns;       /* sum of the hits' columns */
   uint64_t path_rows_bytes;         /* row bytes written: 3 x path_rows_columns */
+  double seconds_pileup;            /* the pile-up post-pass (k_pileup and k_pileup_finish, device time); 0, like
+                                       the four below, until -y 10, -y 11 or GhostmSessionPileup /
+                                       GhostmSessionPileupArrays / GhostmSessionSubjectProfile asks for it */
+  uint64_t pileup_launches;         /* k_pileup launches */
+  uint64_t pileup_windows;          /* profile windows zeroed and finished */
+  uint64_t pileup_parts;            /* (tile, part) workgroups */
+  uint64_t pileup_columns;          /* '=', 'X' and 'D' columns charged; after one GhostmSessionPileup the sum
+                                       of the subjects' depth_sum */
 } GhostmStats;
 
 /* Session: parse `aln` options exactly like the reference (getopt string
@@ -532,7 +597,14 @@ int GhostmSessionRun(void *session);
  *   \t\t<midline>\t
  *   Sbjct\t<sstart>\t<subject row>\t<send>
  *   <empty line>
- * Both price hits like -y 0 and are written at the end of the run. */
+ * Both price hits like -y 0 and are written at the end of the run.
+ * -y 10 replaces the hit lines by the pile-up's summary (GhostmSessionPileup):
+ * one line per subject with at least one hit, in db_id order, tab-separated
+ * integers after the name: subject name, length, hits, covered, depth_sum,
+ * identities_sum, max_depth. -y 11 is that line with an eighth column, the
+ * subject's consensus as text: the residue letter, '-' where depth > 0 and
+ * consensus is 255, '.' where depth is 0. Neither prints an E-value, so like
+ * -y 1 and -y 2 they need no Karlin parameters. */
 int GhostmSessionRunToFile(void *session);
 
 /* Formatted output of the last run (reference WriteOutput/V1/V2 text). With
@@ -576,6 +648,31 @@ size_t GhostmSessionPathOps(void *session, uint32_t *ops, size_t cap);
  * its name group instead). */
 size_t GhostmSessionHitsRows(void *session, GhostmHitRows *rec, size_t cap);
 size_t GhostmSessionRowBytes(void *session, uint8_t *rows, size_t cap);
+
+/* The pile-up of the last run's hits on every subject (the definitions above
+ * PathPileupGpu), built on the paths of GhostmSessionHitsPath with the record
+ * each hit was traced with, so a DNA hit piles up the frame that reproduced
+ * it. GhostmSessionPileup returns one GhostmSubjectPileup per subject over all
+ * DB chunks, in db_id order; GhostmSessionPileupArrays the subjects' depth,
+ * identities and consensus, concatenated in db_id order without the END
+ * separators (subject i begins at subj[i].offset; a NULL array is skipped).
+ * Both return the count with subj == NULL / all arrays NULL, else copy
+ * min(cap, count) elements; (size_t)-1 on error. Works after a run with any
+ * -y: per (DB chunk, profile window) one k_pileup launch per query chunk with
+ * hits there, then k_pileup_finish and 9 bytes per position read back; the
+ * summary is made on the host. Computed on first use and kept until the next
+ * run or GhostmSessionSetQueries*. A shard session piles up its own hits:
+ * depth, identities, the profile and the summary's hits, depth_sum and
+ * identities_sum add up across the ranks; consensus, covered and max_depth do
+ * not and have to be made again from the summed arrays. */
+size_t GhostmSessionPileup(void *session, GhostmSubjectPileup *subj, size_t cap);
+size_t GhostmSessionPileupArrays(void *session, uint32_t *depth, uint32_t *identities,
+                                 uint8_t *consensus, size_t cap);
+
+/* The full 32-slot rows of subject db_id: length x 32 values (NULL: the
+ * count), made on demand by the same kernels on that subject's hits only;
+ * nothing is kept. (size_t)-1 on error (a db_id outside the loaded chunks). */
+size_t GhostmSessionSubjectProfile(void *session, uint32_t db_id, uint32_t *profile, size_t cap);
 
 /* The same records resident on the session's GPU, for a device-to-device
  * gather across ranks: copies min(n, cap) records to dst_device
