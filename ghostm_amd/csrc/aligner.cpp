@@ -2261,40 +2261,7 @@ void Session::Run(bool stream_to_file) {
   TraceMark("run_end");
   TraceDump();
   const DeviceTimes &dt = dev.times();
-  stats_.seconds_seed = dt.seed;
-  stats_.seconds_score = dt.score;
-  stats_.seconds_traceback = dt.traceback;
-  stats_.seconds_traceback_scan = dt.traceback_scan;
-  stats_.score_launches = dt.score_launches;
-  stats_.score_launches_packed = dt.score_launches_packed;
-  stats_.score_launches_half = dt.score_launches_half;
-  stats_.traceback_launches = dt.traceback_launches;
-  stats_.traceback_launches_key = dt.traceback_launches_key;
-  stats_.seed_runs_hash = dt.seed_launches_hash;
-  stats_.score_rechecks = dt.score_rechecks;
-  stats_.seed_bytes = dt.seed_bytes;
-  stats_.seed_list_entries = dt.seed_list_entries;
-  stats_.score_cells = dt.score_cells;
-  stats_.traceback_cells = dt.traceback_cells;
-  stats_.traceback_launches_scan = dt.traceback_launches_scan;
-  stats_.traceback_scan_cells = dt.traceback_scan_cells;
-  stats_.merge_launches = dt.merge_launches;
-  stats_.merge_launches_wave = dt.merge_launches_wave;
-  stats_.score_launches_framed = dt.score_launches_framed;
-  for (int c = 0; c < 4; ++c) stats_.seed_queries_class[c] = dt.seed_queries_class[c];
-  stats_.seed_queries_wide = dt.seed_queries_wide;
-  stats_.seed_runs_filter = dt.seed_launches_filter;
-  stats_.seed_filter_overflows = dt.seed_filter_overflows;
-  stats_.seed_table_full = dt.seed_table_full;
-  stats_.seed_compact_redo = dt.seed_compact_redo;
-  stats_.score_launches_sparse = dt.score_launches_sparse;
-  stats_.traceback_launches_keyframe = dt.traceback_launches_keyframe;
-  stats_.score_launches_levels = dt.score_launches_levels;
-  stats_.score_launches_swar = dt.score_launches_swar;
-  stats_.score_launches_unit = dt.score_launches_unit;
-  stats_.score_launches_pair = dt.score_launches_pair;
-  stats_.traceback_launches_strips = dt.traceback_launches_strips;
-  stats_.traceback_launches_scan_swar = dt.traceback_launches_scan_swar;
+  StageCounters(dt, &stats_);
   stats_.tracebacks += dt.traced_hits;  // device merge (the host merge counts its own)
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();

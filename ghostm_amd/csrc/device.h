@@ -19,6 +19,7 @@
 struct GhostmHitExt;  // include/ghostm_hip.h
 struct GhostmHitPath;
 struct GhostmHitRows;
+struct GhostmStats;
 
 namespace ghostm {
 
@@ -186,7 +187,7 @@ class DeviceModule {
   void ScoreDeferNext(bool on) { defer_next_ = on; }
   void ScorePrepareNext(const std::vector<uint32_t> &counts, const std::vector<uint64_t> &offsets);
 
-  uint32_t ScorePerBlock(DevQuery *q, uint32_t base_search_length, const GapConfig &gap) const;
+  uint32_t ScorePerBlock(DevQuery *q, const DevDb *d, uint32_t base_search_length, const GapConfig &gap) const;
 
   // K4 + K3 for a batch that covers every group of the chunk and starts from
   // empty result lists (first batch, first DB chunk): the reference Merge
@@ -321,6 +322,9 @@ class DeviceModule {
   Impl *impl_ = nullptr;
   friend struct DeviceModuleAccess;
 };
+
+// dt's timings and counters in the GhostmStats fields of the same meaning.
+void StageCounters(const DeviceTimes &dt, GhostmStats *st);
 
 const char *DeviceBuildInfo();
 

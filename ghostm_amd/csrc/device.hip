@@ -220,6 +220,8 @@ struct DevDb {
   DevBuf low;                      // kern::k_low_keys' bitmap
   uint32_t len = 0, kcl = 0, npos = 0;
   bool codes_le26 = false;         // every residue code <= 26 (the sparse K2 profiles hold rows 0..26)
+  bool codes_le25 = false;         // every code a residue (0..24) or END: the packed K2 kernels and the K3 scan
+                                   // read codes 26..31 as END or as a zero row, k_score and the K3 DPs as M's row
   uint32_t end_gap = UINT32_MAX;   // fewest positions from one END to the next (K2 restart levels)
   const uint8_t *Residues() const { return seq.as<uint8_t>() + kDbFront; }
   DevBuf subj;                     // subject starts (device merge)
@@ -430,6 +432,10 @@ void DeviceModule::Bind(int device) {
                                 (int)kFilterLds1));
   HIP_CHECK(hipFuncSetAttribute((const void *)GHOSTM_FILTER2, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)kFilterLds2));
+  // k_score: four 32-row int profiles, 66 KB at L = 127
+  for (const void *f : {(const void *)kern::k_score<32>, (const void *)kern::k_score<16>, (const void *)kern::k_score<8>})
+    HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(kern::kScoreQmax * kern::kProfRows * ((kMaxQueryLength + 7) / 8 * 8 + 4) * 4)));
   // the sparse rows K2 (kScoreRowsSparse): seven 27-row profiles, ~53 KB at L = 127
   for (const void *f : {(const void *)kern::k_score16f<16, true>, (const void *)kern::k_score16f<16, true, false, true>})
     HIP_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -627,6 +633,7 @@ DevDb *DeviceModule::UploadDb(const uint8_t *seq, uint32_t len, const uint32_t *
   if (!impl_) throw Error("device not bound");
   // the kernels index 32-entry tables by residue code (checked 8 bytes at a time)
   uint64_t over26 = 0;  // a byte >= 27 sets its top bit in (byte + 101) (codes < 32 do not carry)
+  uint64_t over25 = 0;  // ... a byte >= 26 in (byte + 102)
   {
     uint64_t hi = 0;
     uint32_t k = 0;
@@ -635,10 +642,12 @@ DevDb *DeviceModule::UploadDb(const uint8_t *seq, uint32_t len, const uint32_t *
       std::memcpy(&w, seq + k, 8);
       hi |= w;
       over26 |= (w & 0x1F1F1F1F1F1F1F1Full) + 0x6565656565656565ull;
+      over25 |= (w & 0x1F1F1F1F1F1F1F1Full) + 0x6666666666666666ull;
     }
     for (; k < len; ++k) {
       hi |= seq[k];
       over26 |= (uint64_t)((seq[k] & 0x1Fu) + 0x65u);
+      over25 |= (uint64_t)((seq[k] & 0x1Fu) + 0x66u);
     }
     if (hi & 0xE0E0E0E0E0E0E0E0ull) throw Error("database residue code out of range");
   }
@@ -653,6 +662,7 @@ DevDb *DeviceModule::UploadDb(const uint8_t *seq, uint32_t len, const uint32_t *
   DevDb *d = new DevDb();
   d->end_gap = end_gap;
   d->codes_le26 = (over26 & 0x8080808080808080ull) == 0;
+  d->codes_le25 = (over25 & 0x8080808080808080ull) == 0;
   d->len = len;
   d->kcl = kcl;
   d->npos = npos;
@@ -1236,19 +1246,22 @@ void DeviceModule::CopyStarts(uint64_t begin, uint64_t n, uint32_t *out) {
 
 
 // the packed K2 encodings (two candidates per lane) whenever every value fits
-static bool ScorePacked(const int *h_matrix, uint32_t L, uint32_t base, const GapConfig &gap) {
+// and the chunk holds residues and ENDs only: the packed kernels take every
+// code from 25 up for END (one sign test per column) and build no profile rows
+// for 26..31, so a chunk with such codes runs k_score, which reads M's rows
+static bool ScorePacked(const int *h_matrix, const DevDb *d, uint32_t L, uint32_t base, const GapConfig &gap) {
   int max_abs = 0;
   for (int k = 0; k < 32 * 32; ++k) max_abs = std::max(max_abs, h_matrix[k] < 0 ? -h_matrix[k] : h_matrix[k]);
   const char *force = getenv("GHOSTM_K2");
   const bool gaps_ok = gap.open <= 0 && gap.ext <= 0 && -gap.open < 2000 && -gap.ext < 2000;
   const int64_t bound = (int64_t)L * max_abs;
   const bool allow_packed = !(force && strcmp(force, "int32") == 0);
-  return allow_packed && gaps_ok && bound < 30000 && base + 64 < kDbBack;
+  return allow_packed && gaps_ok && bound < 30000 && base + 64 < kDbBack && d->codes_le25;
 }
 
-uint32_t DeviceModule::ScorePerBlock(DevQuery *q, uint32_t base, const GapConfig &gap) const {
+uint32_t DeviceModule::ScorePerBlock(DevQuery *q, const DevDb *d, uint32_t base, const GapConfig &gap) const {
   const Layout lay = ChooseLayout(q->L, base);
-  return (kern::kScoreBlock / 64) * lay.gpw * (ScorePacked(impl_->h_matrix, q->L, base, gap) ? 2 : 1);
+  return (kern::kScoreBlock / 64) * lay.gpw * (ScorePacked(impl_->h_matrix, d, q->L, base, gap) ? 2 : 1);
 }
 
 // The sparse rows kernel's layout (16 rows per lane) and its candidates per
@@ -1285,7 +1298,7 @@ void DeviceModule::ScoreLaunch(DevQuery *q, DevDb *d, uint64_t cand_begin, uint6
   // else int16 pairs, else int32 (GHOSTM_K2=int32|int16|f16 restricts the choice)
   const char *force = getenv("GHOSTM_K2");
   const int64_t bound = (int64_t)q->L * max_abs;
-  const bool packed = ScorePacked(I.h_matrix, q->L, base, gap);
+  const bool packed = ScorePacked(I.h_matrix, d, q->L, base, gap);
   // f16 is exact below 2048; beyond that it runs with a guard and the int16
   // kernel re-scores the (rare) candidates whose best reaches it
   const bool half = packed && !(force && strcmp(force, "int16") == 0);
@@ -1316,7 +1329,7 @@ void DeviceModule::ScoreLaunch(DevQuery *q, DevDb *d, uint64_t cand_begin, uint6
   // post-END one while best + sigma_max < 2040; beyond, the guard flags them
   int guard = swar ? 0 : framed ? (bound + sigma_max < 2040 ? 0 : (int)(2040 - sigma_max)) : (bound < 2048 ? 0 : 2000);
   if (half && getenv("GHOSTM_K2_GUARD")) guard = atoi(getenv("GHOSTM_K2_GUARD"));  // tests: force re-scores
-  const uint32_t per_block = ScorePerBlock(q, base, gap);
+  const uint32_t per_block = ScorePerBlock(q, d, base, gap);
   const uint32_t sparse_pb = swar ? SparsePerBlock(q, d) : 0u;
   // tasks, and with them the kernel (score_tasks.h BuildTasks: the unit-pair
   // kernel where its blocks are not too many more): prepared for this range by
@@ -1638,7 +1651,8 @@ void DeviceModule::LaunchTraceback(kern::TbArgs a, DevQuery *q, uint32_t n, cons
   const char *scan_env = getenv("GHOSTM_K3_SCAN");
   const bool scan_off = scan_env && strcmp(scan_env, "0") == 0;
   const bool scan_gaps = a.open <= 0 && a.ext <= 0 && -a.open < 2000 && -a.ext < 2000;
-  const bool scan = !scan_off && n > 0 && scan_gaps && hmax < 30000 && a.base < 65536;
+  // (the scan scores codes 26..31 as zero rows, the DPs below with M's: a chunk that holds such codes is not scanned)
+  const bool scan = !scan_off && n > 0 && scan_gaps && hmax < 30000 && a.base < 65536 && (!d || d->codes_le25);
   if (scan) {
     const bool half = hmax < 2048 && !(scan_env && strcmp(scan_env, "int16") == 0);
     // the column-framed f16 scan: values up to best + (window + 2G) * ext_pen
@@ -2596,6 +2610,46 @@ const char *DeviceBuildInfo() {
   return info.c_str();
 }
 
+// The device module's timings and counters in the GhostmStats fields of the
+// same meaning (a session's run and GhostmStageStats share this list); fields
+// the module does not count stay as they are.
+void StageCounters(const DeviceTimes &dt, GhostmStats *st) {
+  st->seconds_seed = dt.seed;
+  st->seconds_score = dt.score;
+  st->seconds_traceback = dt.traceback;
+  st->seconds_traceback_scan = dt.traceback_scan;
+  st->score_launches = dt.score_launches;
+  st->score_launches_packed = dt.score_launches_packed;
+  st->score_launches_half = dt.score_launches_half;
+  st->traceback_launches = dt.traceback_launches;
+  st->traceback_launches_key = dt.traceback_launches_key;
+  st->seed_runs_hash = dt.seed_launches_hash;
+  st->score_rechecks = dt.score_rechecks;
+  st->seed_bytes = dt.seed_bytes;
+  st->seed_list_entries = dt.seed_list_entries;
+  st->score_cells = dt.score_cells;
+  st->traceback_cells = dt.traceback_cells;
+  st->traceback_launches_scan = dt.traceback_launches_scan;
+  st->traceback_scan_cells = dt.traceback_scan_cells;
+  st->merge_launches = dt.merge_launches;
+  st->merge_launches_wave = dt.merge_launches_wave;
+  st->score_launches_framed = dt.score_launches_framed;
+  for (int c = 0; c < 4; ++c) st->seed_queries_class[c] = dt.seed_queries_class[c];
+  st->seed_queries_wide = dt.seed_queries_wide;
+  st->seed_runs_filter = dt.seed_launches_filter;
+  st->seed_filter_overflows = dt.seed_filter_overflows;
+  st->seed_table_full = dt.seed_table_full;
+  st->seed_compact_redo = dt.seed_compact_redo;
+  st->score_launches_sparse = dt.score_launches_sparse;
+  st->traceback_launches_keyframe = dt.traceback_launches_keyframe;
+  st->score_launches_levels = dt.score_launches_levels;
+  st->score_launches_swar = dt.score_launches_swar;
+  st->score_launches_unit = dt.score_launches_unit;
+  st->score_launches_pair = dt.score_launches_pair;
+  st->traceback_launches_strips = dt.traceback_launches_strips;
+  st->traceback_launches_scan_swar = dt.traceback_launches_scan_swar;
+}
+
 // ============================================================ reference C ABI
 namespace {
 
@@ -2859,6 +2913,33 @@ int CountCandidatesGpu(uint32_t query_sequence_length, uint32_t number_query_seq
     SetError(e.what());
     return 1;
   }
+}
+
+size_t GhostmStageStats(GhostmStats *stats, size_t size) {
+  if (!stats) return 0;
+  RefState &r = Ref();
+  std::lock_guard<std::mutex> lk(r.mu);
+  const DeviceTimes &dt = DeviceModule::Get().times();
+  GhostmStats st{};
+  StageCounters(dt, &st);
+  st.seconds_traceback_ext = dt.traceback_ext;
+  st.traceback_ext_launches = dt.traceback_ext_launches;
+  st.traceback_ext_cells = dt.traceback_ext_cells;
+  st.seconds_traceback_path = dt.traceback_path;
+  st.traceback_path_launches = dt.traceback_path_launches;
+  st.traceback_path_cells = dt.traceback_path_cells;
+  st.traceback_path_dir_bytes = dt.traceback_path_dir_bytes;
+  st.seconds_path_rows = dt.path_rows;
+  st.path_rows_launches = dt.path_rows_launches;
+  st.path_rows_columns = dt.path_rows_columns;
+  st.path_rows_bytes = dt.path_rows_bytes;
+  st.seconds_pileup = dt.pileup;
+  st.pileup_launches = dt.pileup_launches;
+  st.pileup_windows = dt.pileup_windows;
+  st.pileup_parts = dt.pileup_parts;
+  st.pileup_columns = dt.pileup_columns;
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmStats)));
+  return sizeof(GhostmStats);
 }
 
 int TraceBackGpu(uint32_t nhits, const uint32_t query_ids[], const uint32_t db_ends[],

@@ -1424,7 +1424,7 @@ __device__ inline void WaveAddCells(unsigned long long *counter, unsigned long l
 
 // ------------------------------------------------------------------ K2 score
 constexpr int kScoreBlock = 256;
-constexpr uint32_t kProfRows = 26;
+constexpr uint32_t kProfRows = 32;    // k_score: one profile row per residue code
 constexpr uint32_t kProfRows16 = 32;  // packed kernels: one profile row per residue code
 constexpr uint32_t kFillCode = 26;     // k_score16f: profile row of the columns before the window
 constexpr uint32_t kDbFrontPad = 64;  // END bytes in front of the DB residues (device.hip)
@@ -1477,15 +1477,16 @@ __global__ __launch_bounds__(kScoreBlock) void k_score(ScoreArgs a) {
   const uint32_t RS = a.Lpad + 4;  // padded profile row (spreads LDS banks)
 
   // per-query profiles: prof[slot][c][r] = M[c][q[r - pad]], padding rows kNeg.
-  // Rows 0..24 are the residue codes; row 25 stands for codes 26..31, whose
-  // matrix rows are all zero (the reader only fills codes <= 24).
+  // One row per DB code, as the contract's M[db * 32 + query] has: a chunk with
+  // codes 26..31 (none comes from the formatter) is scored by this kernel alone
+  // (device.hip ScorePacked); row 25, END, is never read.
   const uint32_t per_slot = kProfRows * a.Lpad;
   const uint32_t total = t.q_count * per_slot;
   for (uint32_t e = threadIdx.x; e < total; e += kScoreBlock) {
     const uint32_t slot = e / per_slot, rem = e - slot * per_slot;
     const uint32_t c = rem / a.Lpad, r = rem - c * a.Lpad;
     int v = kNeg;
-    if (r >= a.pad) v = c < 25 ? a.mat[c * 32 + a.qseq[(size_t)(t.q_first + slot) * a.L + (r - a.pad)]] : 0;
+    if (r >= a.pad) v = a.mat[c * 32 + a.qseq[(size_t)(t.q_first + slot) * a.L + (r - a.pad)]];
     s_prof[(slot * kProfRows + c) * RS + r] = v;
   }
   __syncthreads();
@@ -1532,7 +1533,7 @@ __global__ __launch_bounds__(kScoreBlock) void k_score(ScoreArgs a) {
 #pragma unroll
         for (int k = 0; k < S; ++k) { H[k] = 0; E[k] = 0; }
       } else {
-        const int *p = prof + (c < 25 ? c : 25u) * RS;
+        const int *p = prof + (c & 31u) * RS;
         int diag = diag0, F = fin, cm = 0;
 #pragma unroll
         for (int k = 0; k < S; k += 4) {

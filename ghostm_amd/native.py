@@ -254,6 +254,7 @@ SIGNATURES = {
     "GhostmSessionDeviceHits": (c_size_t, [c_void_p, c_void_p, c_size_t]),
     "GhostmSessionStats": (c_int, [c_void_p, POINTER(GhostmStats)]),
     "GhostmSessionStatsSized": (c_size_t, [c_void_p, POINTER(GhostmStats), c_size_t]),
+    "GhostmStageStats": (c_size_t, [POINTER(GhostmStats), c_size_t]),
     "GhostmSessionDestroy": (None, [c_void_p]),
     "GhostmAlignMain": (c_int, [c_int, POINTER(c_char_p)]),
     "GhostmSearchMain": (c_int, [c_int, POINTER(c_char_p)]),

@@ -689,6 +689,19 @@ int GhostmSessionStats(void *session, GhostmStats *stats);
  * a null argument. */
 size_t GhostmSessionStatsSized(void *session, GhostmStats *stats, size_t size);
 
+/* The stage-level calls (SearchNextGpu, CountCandidatesGpu, CalculateScoreGpu,
+ * TraceBackGpu and the other calls on the chunks of SetQueryGpu / SetDbGpu)
+ * belong to no session; this reads the device module's timings and counters
+ * behind them, sized like GhostmSessionStatsSized. The device-side fields
+ * (seconds_seed/score/traceback*, the *_launches*, *_cells, score_rechecks,
+ * seed_*, and the post-pass counters) are filled, the others are 0. The
+ * counters add up over the process's stage calls and start again at 0 with
+ * every GhostmSessionRun, so a caller takes the difference around its calls:
+ * which K2 encoding a CalculateScoreGpu chose, which K3 formulation a
+ * TraceBackGpu. No device call. Returns the library's sizeof, or 0 on a null
+ * argument. */
+size_t GhostmStageStats(GhostmStats *stats, size_t size);
+
 void GhostmSessionDestroy(void *session);
 
 /* `ghostm aln ...` end to end (create + run + write + destroy). Exit status like

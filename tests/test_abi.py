@@ -35,6 +35,21 @@ def test_hit_record_layout():
     assert HIT_DTYPE.itemsize == 32
 
 
+def test_stage_stats_sized(built):
+    """GhostmStageStats is sized like GhostmSessionStatsSized and makes no
+    device call: the fields the device module does not count are 0, a shorter
+    struct gets exactly its bytes, a null pointer gives 0."""
+    lib = native.load()
+    st = native.GhostmStats()
+    ctypes.memset(ctypes.byref(st), 0xEE, ctypes.sizeof(st))
+    assert lib.GhostmStageStats(ctypes.byref(st), ctypes.sizeof(st)) == ctypes.sizeof(st)
+    assert st.queries == 0 and st.hits == 0 and st.batches == 0 and st.seconds_total == 0.0
+    buf = (ctypes.c_uint8 * 128)(*([0xEE] * 128))
+    assert lib.GhostmStageStats(ctypes.cast(buf, ctypes.POINTER(native.GhostmStats)), 64) == ctypes.sizeof(st)
+    assert bytes(buf[64:]) == b"\xee" * 64 and bytes(buf[48:64]) == bytes(16)  # queries, query_residues
+    assert lib.GhostmStageStats(None, ctypes.sizeof(st)) == 0
+
+
 def test_reference_host_links_against_plugin():
     """Where the reference was compiled here, ghostm_ref_plugin resolves the ten
     plugin symbols from libghostm_hip.so (drop-in at the symbol level), while the
