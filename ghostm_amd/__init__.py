@@ -4,7 +4,7 @@ Seed lookup, Gotoh score DP and traceback are hand-written HIP kernels in
 csrc/; the merge/E-value host logic and the C ABI live in libghostm_hip.so.
 """
 from .aligner import (Aligner, GhostmError, HIT_DTYPE, HIT_EXT_DTYPE, HIT_PATH_DTYPE, HIT_ROWS_DTYPE,
-                      SUBJECT_PILEUP_DTYPE, Session, cigar, consensus_text, format_db, format_queries, path_pileup_host,
+                      SUBJECT_PILEUP_DTYPE, Session, cigar, consensus_text, db_chunk_cuts, format_db, format_queries, path_pileup_host,
                       path_rows_host, query_chunk_cuts, rows_of, run_cli, synth, traceback_ext_host,
                       traceback_path_host)
 from .native import BIN_PATH, LIB_PATH, NativeLibraryMissing, load
@@ -28,6 +28,7 @@ __all__ = [
     "format_db",
     "format_queries",
     "query_chunk_cuts",
+    "db_chunk_cuts",
     "synth",
     "run_cli",
     "load",

@@ -8,6 +8,11 @@
                              E-value text), repeatable, with .output(), .hits(),
                              .stats().
 
+    Session.for_queries(argv)  no database yet (-i optional); .set_db(seqs, names)
+                             or .set_db_fasta(path) replace the database on the
+                             live session (coded and indexed on the GPU): one
+                             read set, many databases, no formatted files.
+
     Session.for_db(argv)     only the database resident; .set_queries(seqs, names)
                              or .set_queries_fasta(path) replace the query set on
                              the live session (coded and translated on the GPU),
@@ -171,6 +176,21 @@ def query_chunk_cuts(lengths, chunk_mb: int = 0, dna: bool = False) -> np.ndarra
     return cuts[: n + 1]
 
 
+def db_chunk_cuts(lengths, chunk_mb: int = 0) -> np.ndarray:
+    """`ghostm db`'s chunk cuts over records of these letter counts
+    (GhostmDbChunkCuts; no device): chunk c is records [cuts[c], cuts[c + 1]).
+    chunk_mb as db's -l (0: the default). Raises when a record alone is over
+    the limit, the first one included, and when chunk_mb is above 2047."""
+    lib = native.load()
+    lens = np.ascontiguousarray(lengths, dtype=np.uint32)
+    cuts = np.zeros(len(lens) + 1, dtype=np.uint64)
+    n = lib.GhostmDbChunkCuts(lens.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), len(lens), int(chunk_mb),
+                              cuts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), len(cuts))
+    if n < 0:
+        raise GhostmError(native.last_error())
+    return cuts[: n + 1]
+
+
 def path_rows_host(query_seqs, L, db, score_matrix, query_ids, rec, ops, open_gap=-11, extend_gap=-1):
     """The host model of the aligned rows (GhostmPathRowsHost; no device):
     query_seqs = the chunk's records of L codes, db = the chunk's residues, rec =
@@ -301,6 +321,91 @@ class Session:
         if not self._h:
             raise GhostmError(native.last_error())
         return self
+
+    @classmethod
+    def for_queries(cls, argv: Sequence[str]) -> "Session":
+        """A session without a database (GhostmSessionCreateQueries): `aln`'s
+        options without -d; -i is optional. The database comes from set_db /
+        set_db_fasta, any number of times; the queries from -i or from
+        set_queries / set_queries_fasta."""
+        lib = native.load()
+        self = cls.__new__(cls)
+        args = ["aln"] + list(argv)
+        self._argv = native.argv_array(args)
+        self._h = lib.GhostmSessionCreateQueries(len(args), self._argv)
+        if not self._h:
+            raise GhostmError(native.last_error())
+        return self
+
+    def set_db(self, seqs: Sequence, names: Sequence, k: int = 4, chunk_mb: int = 0) -> None:
+        """Replaces the database by these records (str or bytes letters and
+        names): what `ghostm db -k k -l chunk_mb` would format from them, coded
+        and indexed on the device (GhostmSessionSetDb). The last run's results
+        are dropped; the queries stay."""
+        if len(seqs) != len(names):
+            raise ValueError("set_db: one name per sequence")
+        as_bytes = lambda x: x.encode() if isinstance(x, str) else bytes(x)  # noqa: E731
+        bseqs = [as_bytes(x) for x in seqs]
+        bnames = [as_bytes(x) for x in names]
+        if any(b"\n" in x for x in bnames):
+            raise ValueError("set_db: a name holds a newline")
+        n = len(bseqs)
+        lengths = np.array([len(x) for x in bseqs], dtype=np.uint32)
+        offsets = np.zeros(n, dtype=np.uint64)
+        if n > 1:
+            offsets[1:] = np.cumsum(lengths[:-1], dtype=np.uint64)
+        raw = np.frombuffer(b"".join(bseqs) or b"\0", dtype=np.uint8)
+        raw_len = int(lengths.sum(dtype=np.uint64))
+        name_buf = b"".join(x + b"\n" for x in bnames)
+        rc = native.load().GhostmSessionSetDb(
+            self._h, raw.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), raw_len,
+            offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), name_buf, len(name_buf), n, int(k),
+            int(chunk_mb))
+        if rc != 0:
+            raise GhostmError(native.last_error())
+
+    def set_db_fasta(self, path: str, k: int = 4, chunk_mb: int = 0) -> None:
+        """set_db from a FASTA file, read as `ghostm db` reads it
+        (GhostmSessionSetDbFasta)."""
+        if native.load().GhostmSessionSetDbFasta(self._h, str(path).encode(), int(k), int(chunk_mb)) != 0:
+            raise GhostmError(native.last_error())
+
+    def db_chunks(self) -> list[dict]:
+        """The resident DB chunks in order (GhostmSessionDbChunks): id, nseq, len,
+        seed, kcl and npos of each, as its .inf and .ind headers hold them."""
+        lib = native.load()
+        n = lib.GhostmSessionDbChunks(self._h, None, 0)
+        info = (native.GhostmDbChunkInfo * max(n, 1))()
+        n = lib.GhostmSessionDbChunks(self._h, info, n) if n else 0
+        return [{f: int(getattr(info[c], f)) for f, _ in native.GhostmDbChunkInfo._fields_} for c in range(n)]
+
+    def db_records(self, chunk: int) -> np.ndarray:
+        """The residues of one DB chunk (the bytes of its .seq file), copied
+        back from the device."""
+        lib = native.load()
+        n = lib.GhostmSessionDbRecords(self._h, int(chunk), None, 0)
+        if n == ctypes.c_size_t(-1).value:
+            raise GhostmError(native.last_error())
+        out = np.zeros(n, dtype=np.uint8)
+        if n:
+            lib.GhostmSessionDbRecords(self._h, int(chunk), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), n)
+        return out
+
+    def db_index(self, chunk: int) -> tuple[int, np.ndarray, np.ndarray]:
+        """(seed, keys_count, positions) of one DB chunk's index (its .ind file),
+        copied back from the device (GhostmSessionDbIndex)."""
+        chunks = self.db_chunks()
+        if not 0 <= int(chunk) < len(chunks):
+            raise GhostmError(f"DB chunk {chunk} of {len(chunks)}")
+        c = chunks[int(chunk)]
+        kc = np.zeros(c["kcl"], dtype=np.uint32)
+        pos = np.zeros(c["npos"], dtype=np.uint32)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        if native.load().GhostmSessionDbIndex(self._h, int(chunk), kc.ctypes.data_as(u32p), kc.size,
+                                              pos.ctypes.data_as(u32p), pos.size) != 0:
+            raise GhostmError(native.last_error())
+        return c["seed"], kc, pos
 
     def set_queries(self, seqs: Sequence, names: Sequence, width: int = 75, dna: bool = False,
                     chunk_mb: int = 0) -> None:
@@ -538,7 +643,12 @@ class Session:
         st = native.GhostmStats()
         # the sized call: a library built with more fields writes only ours
         native.load().GhostmSessionStatsSized(self._h, ctypes.byref(st), ctypes.sizeof(st))
-        return st.as_dict()
+        out = st.as_dict()
+        # the database sets' counters (GhostmSessionDbStats), under their own names
+        db = native.GhostmDbSetStats()
+        native.load().GhostmSessionDbStats(self._h, ctypes.byref(db), ctypes.sizeof(db))
+        out.update({name: getattr(db, name) for name, _ in db._fields_})
+        return out
 
     def close(self) -> None:
         if self._h:

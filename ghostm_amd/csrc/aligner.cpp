@@ -20,6 +20,7 @@
 #include <thread>
 
 #include "common.h"
+#include "db_set.h"
 #include "query_set.h"
 #include "worker_pool.h"
 
@@ -563,6 +564,13 @@ Session::Session(const AlignerOptions &opt, DbOnly) : opt_(opt), db_only_(true) 
   CreateOrFree(0, 1, nullptr);
 }
 
+Session::Session(const AlignerOptions &opt, NoDb) : opt_(opt), no_db_(true) {
+  threads_ = HostThreads();
+  if (!opt.db_prefix.empty())
+    throw std::invalid_argument("a session without a database takes no -d: its database comes from SetDb");
+  CreateOrFree(0, 1, nullptr);
+}
+
 void Session::CreateOrFree(uint32_t shard_rank, uint32_t shard_world, const ShardExchange *ex) {
   try {
     Create(shard_rank, shard_world, ex);
@@ -674,6 +682,7 @@ void Session::Load(uint32_t shard_rank, uint32_t shard_world, bool local, std::v
   // parallel threads, then the chunks up to the first missing one are kept
   QueryFile qf(opt_.query_prefix);
   if (db_only_) qf.division = 0;  // a database session: no query files
+  if (no_db_ && opt_.query_prefix.empty()) qf.division = 0;  // ... or neither input yet
   uint32_t id = opt_.start_query_chunk == UINT32_MAX ? 0 : opt_.start_query_chunk;
   uint32_t base = 0;
   for (uint32_t k = 0; k < id && k < qf.division; ++k) {
@@ -689,7 +698,7 @@ void Session::Load(uint32_t shard_rank, uint32_t shard_world, bool local, std::v
     nq_chunks = (uint32_t)(last >= id ? last - id + 1 : 1);
   }
   DbFile df(opt_.db_prefix);
-  const uint32_t nd_chunks = (int64_t)df.division > 0 ? (uint32_t)df.division : 0u;
+  const uint32_t nd_chunks = (int64_t)df.division > 0 && !no_db_ ? (uint32_t)df.division : 0u;
   std::vector<QueryData> qread(nq_chunks);
   std::vector<QueryChunkIndex> qidx(local ? nq_chunks : 0);
   std::vector<DbData> dread(nd_chunks);
@@ -780,7 +789,8 @@ void Session::Load(uint32_t shard_rank, uint32_t shard_world, bool local, std::v
               });
   uint32_t nchunks = 0;
   while (nchunks < nq_chunks && qok[nchunks]) ++nchunks;
-  if (nchunks == 0 && !db_only_) throw std::runtime_error("[Aligner] error: don't find query file.");
+  if (nchunks == 0 && !db_only_ && !(no_db_ && opt_.query_prefix.empty()))
+    throw std::runtime_error("[Aligner] error: don't find query file.");
   if (!local) {
     std::vector<QueryData *> chunks;
     for (uint32_t k = 0; k < nchunks; ++k) chunks.push_back(&qread[k]);
@@ -788,7 +798,7 @@ void Session::Load(uint32_t shard_rank, uint32_t shard_world, bool local, std::v
   }
   TraceMark("queries_read", nchunks);
 
-  db_sum_u32_ = (uint32_t)df.sum_length;
+  db_sum_u32_ = no_db_ ? 0 : (uint32_t)df.sum_length;
   uint32_t dbase = 0;
   uint32_t nd_kept = 0;
   for (; nd_kept < nd_chunks && dok[nd_kept]; ++nd_kept) {
@@ -798,7 +808,7 @@ void Session::Load(uint32_t shard_rank, uint32_t shard_world, bool local, std::v
     dread[nd_kept].dev = nullptr;
   }
   // chunks read past a missing one are not used (freed by `unadopted`)
-  if (dbs_.empty()) throw std::runtime_error("[Aligner] error: don't find db file.");
+  if (dbs_.empty() && !no_db_) throw std::runtime_error("[Aligner] error: don't find db file.");
   TraceMark("db_read", dbs_.size());
   {
     std::vector<uint32_t> bases;
@@ -2245,6 +2255,7 @@ void Session::Run(bool stream_to_file) {
   if (run_sync_) dev.Synchronize();
   TraceMark("run_idle");
   for (QueryData &q : queries_) {
+    if (dbs_.empty()) break;  // no database (yet): empty output, no hits
     RunQueryChunk(q);
     stats_.queries += q.chunk.nseq;
     for (uint32_t v : q.qlen) stats_.query_residues += v;
@@ -2596,6 +2607,207 @@ void Session::SetQueriesFasta(const std::string &path, uint32_t width, bool dna,
     throw;
   }
   FinishQuerySet();
+}
+
+// ------------------------------------------------------------------ database sets
+// The session's database replaced on the live session: what `ghostm db` would
+// write for the same records (db_set.h: the chunk cuts) is made resident chunk
+// by chunk by DeviceModule::FormatDb, coded and indexed on the device, without
+// files. The query chunks, the matrix and the options stay as they are.
+void Session::DropDb() {
+  if (shard_world_ > 1) throw Error("a shard session's database cannot be replaced: its batch plan was agreed on it");
+  if (formatter_) formatter_->Drain();
+  if (writer_) writer_->Drain();
+  DeviceModule &dev = DeviceModule::Get();
+  dev.Synchronize();
+  DropResults();
+  dev.ResetRecords(0);
+  records_on_device_ = true;
+  streamed_ = false;
+  stream_failed_ = false;
+  stream_off_ = 0;
+  seed_counts_.clear();
+  seed_offsets_.clear();
+  stats_ = GhostmStats{};
+  // the old chunks' device blocks go back to the pool
+  for (DbData &d : dbs_) dev.Free(d.dev);
+  dbs_.clear();
+  db_sum_u32_ = 0;
+  // the E-value text cache is keyed by (query length, score) and was priced
+  // with the old database's residue sum
+  format_.reset();
+  dev.SetChunkBases(nullptr, 0);
+  db_format_seconds_ = 0;
+  db_code_seconds_ = 0;
+  db_format_launches_ = 0;
+  db_read_seconds_ = 0;
+  db_load_seconds_ = 0;
+  QueryStats();
+}
+
+void Session::AddDbChunk(const QueryRecordView *recs, uint32_t n, uint32_t seed) {
+  DeviceModule &dev = DeviceModule::Get();
+  const double t0 = NowSeconds();
+  // every record's letters followed by the separator (kernels.h k_db_code)
+  std::vector<uint32_t> len(n), starts(n);
+  uint64_t total = 0;
+  for (uint32_t r = 0; r < n; ++r) {
+    starts[r] = (uint32_t)total;
+    len[r] = recs[r].len;
+    total += (uint64_t)len[r] + 1;
+  }
+  if (total > UINT32_MAX) throw Error("set db: a chunk of over 4 G bytes");
+  std::vector<uint8_t> packed(total);
+  ParallelFor(n, std::max(1u, std::min(threads_, 8u)), [&](size_t b, size_t e, unsigned) {
+    for (size_t r = b; r < e; ++r) {
+      uint8_t *dst = packed.data() + starts[r];
+      if (len[r]) std::memcpy(dst, recs[r].seq, len[r]);
+      // a letter equal to the separator (records given in memory only) is any
+      // other unknown letter: X
+      for (uint8_t *p = dst; (p = static_cast<uint8_t *>(std::memchr(p, '\n', (size_t)(dst + len[r] - p)))); ++p)
+        *p = '?';
+      dst[len[r]] = '\n';
+    }
+  });
+  DbData d;
+  d.chunk.id = (uint32_t)dbs_.size();
+  d.chunk.nseq = n;
+  d.chunk.len = (uint32_t)total;
+  d.chunk.seed = seed;
+  d.chunk.kcl = (1u << (kCharBits * SeedWeight(seed))) + 1;
+  for (uint32_t r = 0; r < n; ++r) d.chunk.names.push_back(recs[r].name);
+  double code_s = 0, index_s = 0;
+  d.dev = dev.FormatDb(packed.data(), (uint32_t)total, len.data(), n, seed, &d.chunk.npos, &code_s, &index_s);
+  struct FreeUnadopted {
+    DbData *d;
+    ~FreeUnadopted() {
+      if (d) DeviceModule::Get().Free(d->dev);
+    }
+  } guard{&d};
+  dev.SetDbSubjects(d.dev, starts.data(), n);
+  d.chunk.starts = std::move(starts);
+  d.global_base = dbs_.empty() ? 0 : dbs_.back().global_base + dbs_.back().chunk.nseq;
+  db_sum_u32_ += (uint32_t)(total - n);  // DBReader::GetSumDbLength() truncates to u32
+  db_format_seconds_ += code_s + index_s;
+  db_code_seconds_ += code_s;
+  ++db_format_launches_;
+  dbs_.push_back(std::move(d));
+  guard.d = nullptr;
+  db_load_seconds_ += NowSeconds() - t0 - code_s - index_s;
+}
+
+void Session::FinishDbSet() {
+  std::vector<uint32_t> bases;
+  for (const DbData &d : dbs_) bases.push_back(d.global_base);
+  DeviceModule::Get().SetChunkBases(bases.data(), (uint32_t)bases.size());
+  ++db_sets_;
+}
+
+GhostmDbSetStats Session::DbSetStats() const {
+  GhostmDbSetStats st{};
+  st.seconds_db_format = db_format_seconds_;
+  st.seconds_db_code = db_code_seconds_;
+  st.db_format_launches = db_format_launches_;
+  st.db_sets = db_sets_;
+  st.seconds_db_read = db_read_seconds_;
+  st.seconds_db_load = db_load_seconds_;
+  return st;
+}
+
+void Session::RefuseDbSet(uint32_t k, uint32_t chunk_mb) const {
+  if (shard_world_ > 1) throw Error("a shard session's database cannot be replaced: its batch plan was agreed on it");
+  if (k == 0 || k > 6) throw Error("set db: k = " + std::to_string(k) + " outside 1..6 (the index's seed weights)");
+  if (chunk_mb > kDbChunkMbMax) throw Error("set db: chunk size above " + std::to_string(kDbChunkMbMax) + " MiB");
+}
+
+void Session::SetDb(const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets, const uint32_t *lengths,
+                    const char *names, uint64_t names_len, uint32_t n, uint32_t k, uint32_t chunk_mb) {
+  if (n && (!offsets || !lengths || !names || (!raw && raw_len))) throw Error("set db: null argument");
+  RefuseDbSet(k, chunk_mb);
+  std::vector<QueryRecordView> recs(n);
+  uint64_t at = 0;
+  for (uint32_t r = 0; r < n; ++r) {
+    if (offsets[r] > raw_len || lengths[r] > raw_len - offsets[r])
+      throw Error("set db: record " + std::to_string(r) + " outside the letter buffer");
+    const char *nl = at < names_len ? static_cast<const char *>(std::memchr(names + at, '\n', names_len - at)) : nullptr;
+    if (!nl) throw Error("set db: fewer than " + std::to_string(n) + " newline-terminated names");
+    recs[r] = QueryRecordView{reinterpret_cast<const char *>(raw) + offsets[r], lengths[r],
+                              std::string_view(names + at, (size_t)(nl - (names + at)))};
+    at = (uint64_t)(nl - names) + 1;
+  }
+  std::vector<uint64_t> cuts;
+  if (!DbChunkCuts(lengths, n, DbChunkLimit(chunk_mb), &cuts)) throw Error("set db: too small max length.");
+  const uint32_t seed = (1u << k) - 1;
+  DropDb();
+  try {
+    for (size_t c = 0; c + 1 < cuts.size(); ++c)
+      AddDbChunk(recs.data() + cuts[c], (uint32_t)(cuts[c + 1] - cuts[c]), seed);
+  } catch (...) {
+    DropDb();  // no half-made database
+    throw;
+  }
+  FinishDbSet();
+}
+
+void Session::SetDbFasta(const std::string &path, uint32_t k, uint32_t chunk_mb) {
+  RefuseDbSet(k, chunk_mb);
+  {
+    std::ifstream probe(path.c_str());
+    if (!probe) throw Error("set db: cannot open " + path);
+  }
+  const uint32_t seed = (1u << k) - 1;
+  DropDb();
+  try {
+    DbChunkReader reader(path, DbChunkLimit(chunk_mb));
+    std::vector<FastaRecord> recs;
+    std::vector<QueryRecordView> views;
+    for (;;) {
+      const double t0 = NowSeconds();
+      const int more = reader.Next(&recs);
+      db_read_seconds_ += NowSeconds() - t0;
+      if (more < 0) throw Error("set db: too small max length.");
+      if (more == 0) break;
+      views.resize(recs.size());
+      for (size_t r = 0; r < recs.size(); ++r) {
+        if (recs[r].seq.size() >= UINT32_MAX) throw Error("set db: a record of over 4 G letters");
+        views[r] = QueryRecordView{recs[r].seq.data(), (uint32_t)recs[r].seq.size(), recs[r].name};
+      }
+      AddDbChunk(views.data(), (uint32_t)views.size(), seed);
+    }
+  } catch (...) {
+    DropDb();  // no half-made database
+    throw;
+  }
+  FinishDbSet();
+}
+
+void Session::DbChunkInfo(uint32_t chunk, GhostmDbChunkInfo *info) const {
+  if (chunk >= dbs_.size()) throw Error("DB chunk " + std::to_string(chunk) + " of " + std::to_string(dbs_.size()));
+  const DbChunk &c = dbs_[chunk].chunk;
+  *info = GhostmDbChunkInfo{c.id, c.nseq, c.len, c.seed, c.kcl, c.npos};
+}
+
+size_t Session::DbRecords(uint32_t chunk, uint8_t *codes, size_t cap) {
+  if (chunk >= dbs_.size()) throw Error("DB chunk " + std::to_string(chunk) + " of " + std::to_string(dbs_.size()));
+  const size_t n = dbs_[chunk].chunk.len;
+  if (!codes) return n;
+  DeviceModule &dev = DeviceModule::Get();
+  if (cap >= n) {
+    dev.DownloadDb(dbs_[chunk].dev, codes, nullptr, nullptr);
+    return n;
+  }
+  std::vector<uint8_t> all(n);
+  dev.DownloadDb(dbs_[chunk].dev, all.data(), nullptr, nullptr);
+  std::memcpy(codes, all.data(), cap);
+  return cap;
+}
+
+void Session::DbIndex(uint32_t chunk, uint32_t *keys_count, size_t kc_cap, uint32_t *positions, size_t pos_cap) {
+  if (chunk >= dbs_.size()) throw Error("DB chunk " + std::to_string(chunk) + " of " + std::to_string(dbs_.size()));
+  const DbChunk &c = dbs_[chunk].chunk;
+  if ((keys_count && kc_cap < c.kcl) || (positions && pos_cap < c.npos))
+    throw Error("DB index: the arrays need " + std::to_string(c.kcl) + " and " + std::to_string(c.npos) + " words");
+  DeviceModule::Get().DownloadDb(dbs_[chunk].dev, nullptr, keys_count, positions);
 }
 
 void Session::SetOutputFile(const std::string &path) {

@@ -136,6 +136,35 @@ class Session {
   // queries until SetQueries; -i, -S or -L in the options is an error.
   struct DbOnly {};
   Session(const AlignerOptions &opt, DbOnly);
+  // A session without a database (GhostmSessionCreateQueries): `aln`'s options
+  // without -d (giving it is an error); with -i the query chunks are loaded as
+  // usual, without it the session starts with neither input. The database
+  // comes from SetDb / SetDbFasta; Run before that gives empty output.
+  struct NoDb {};
+  Session(const AlignerOptions &opt, NoDb);
+  // Replaces the database by what `ghostm db -k k -l chunk_mb` would format
+  // from these records (chunk_mb 0: db's default), made resident chunk by chunk
+  // by DeviceModule::FormatDb: neither the codes nor the index visit the host
+  // and no file is written. The record layout is SetQueries'. The last run's
+  // results are dropped, the old chunks' device blocks go back to the pool;
+  // the query chunks stay. Throws on a shard session (its batch plan was
+  // agreed on the old database) and on bad arguments (a null argument, a
+  // record outside the buffer, a seed the index refuses, chunk_mb over
+  // kDbChunkMbMax, a record that alone is over the chunk limit): the session
+  // is then as it was. A failure while the chunks load leaves the session
+  // with no database.
+  void SetDb(const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets, const uint32_t *lengths,
+             const char *names, uint64_t names_len, uint32_t n, uint32_t k, uint32_t chunk_mb);
+  // ... read from a FASTA file with the formatter's reader. A file that cannot
+  // be opened leaves the session as it was; a record over the chunk limit is
+  // found only while the chunks load.
+  void SetDbFasta(const std::string &path, uint32_t k, uint32_t chunk_mb);
+  // the resident DB chunks: their number; one chunk's header values, its
+  // residues (the .seq bytes; NULL: their size) and its index copied back
+  size_t DbChunkCount() const { return dbs_.size(); }
+  void DbChunkInfo(uint32_t chunk, GhostmDbChunkInfo *info) const;
+  size_t DbRecords(uint32_t chunk, uint8_t *codes, size_t cap);
+  void DbIndex(uint32_t chunk, uint32_t *keys_count, size_t kc_cap, uint32_t *positions, size_t pos_cap);
   // Replaces the query set by what `ghostm qry -l width [-t d] -L chunk_mb`
   // would format from these records (chunk_mb 0: qry's default), formatted on
   // the device straight into the resident chunks (DeviceModule::FormatQuery);
@@ -213,6 +242,8 @@ class Session {
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
   const GhostmStats &Stats() const { return stats_; }
+  // the counters of the database sets (GhostmSessionDbStats): all 0 for a database read from files
+  GhostmDbSetStats DbSetStats() const;
 
  private:
   struct QueryData {
@@ -265,6 +296,14 @@ class Session {
   };
   void CreateOrFree(uint32_t shard_rank, uint32_t shard_world, const ShardExchange *ex);
   void DropQueries();  // the last run's results and the resident query chunks
+  // The one place a database is forgotten: the last run's results, the resident
+  // DB chunks and everything priced or planned with them (the E-value text
+  // cache of format_, the seed counts, the device's chunk bases).
+  void DropDb();
+  // the next chunk of a database being set (db's files for these records, resident)
+  void AddDbChunk(const QueryRecordView *recs, uint32_t n, uint32_t seed);
+  void RefuseDbSet(uint32_t k, uint32_t chunk_mb) const;  // throws on a shard session, a bad k or chunk_mb
+  void FinishDbSet();
   // the next chunk of a set (qry's files for these records, resident)
   void AddQueryChunk(const QueryRecordView *recs, uint32_t n, uint32_t width, bool dna, uint64_t *cut_records,
                      std::vector<std::string> *cut_names);
@@ -337,7 +376,10 @@ class Session {
   AlignerOptions opt_;
   uint64_t shard_begin_ = 0, shard_end_ = UINT64_MAX;  // query range over the loaded chunks
   uint32_t shard_world_ = 1;
-  bool db_only_ = false;
+  bool db_only_ = false, no_db_ = false;
+  double db_format_seconds_ = 0, db_code_seconds_ = 0;  // FormatDb's device time: the current database
+  uint64_t db_format_launches_ = 0, db_sets_ = 0;
+  double db_read_seconds_ = 0, db_load_seconds_ = 0;    // host: FASTA reading; packing, upload, subjects
   double format_seconds_ = 0;          // FormatQuery's device time, launches: the current set
   uint64_t format_launches_ = 0, query_sets_ = 0;
   double read_seconds_ = 0, load_seconds_ = 0;  // host: FASTA reading; packing, upload and read-back

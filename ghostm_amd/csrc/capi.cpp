@@ -5,11 +5,14 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <memory>
+#include <string>
 #include <vector>
 
 #include "../../include/ghostm_hip.h"
 #include "aligner.h"
 #include "common.h"
+#include "db_set.h"
 #include "query_set.h"
 
 using namespace ghostm;
@@ -104,6 +107,95 @@ int64_t GhostmQueryChunkCuts(const uint32_t lengths[], uint64_t n, uint32_t chun
     if (n && !lengths) throw Error("chunk cuts: null argument");
     std::vector<uint64_t> c;
     const bool whole = QueryChunkCuts(lengths, n, QueryChunkLimit(chunk_mb != 0, chunk_mb, dna != 0), &c);
+    if (cuts) std::copy(c.begin(), c.begin() + (long)std::min<uint64_t>(cap, c.size()), cuts);
+    if (!whole) throw Error("chunk cuts: too small max length.");
+    return (int64_t)c.size() - 1;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return -1;
+  }
+}
+
+void *GhostmSessionCreateQueries(int argc, char **argv) {
+  try {
+    AlignerOptions opt = ParseAlignerOptions(argc, argv);
+    return new Session(opt, Session::NoDb{});
+  } catch (std::exception &e) {
+    SetLastErrorMessage(*e.what() ? e.what() : "invalid option");
+    return nullptr;
+  }
+}
+
+int GhostmSessionSetDb(void *s, const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets,
+                       const uint32_t *lengths, const char *names, uint64_t names_len, uint32_t n, uint32_t k,
+                       uint32_t chunk_mb) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetDb(raw, raw_len, offsets, lengths, names, names_len, n, k, chunk_mb);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+int GhostmSessionSetDbFasta(void *s, const char *path, uint32_t k, uint32_t chunk_mb) {
+  try {
+    if (!s) throw Error("null session");
+    if (!path) throw Error("set db: null path");
+    static_cast<Session *>(s)->SetDbFasta(path, k, chunk_mb);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionDbChunks(void *s, GhostmDbChunkInfo *info, size_t cap) {
+  if (!s) return 0;
+  const Session *p = static_cast<Session *>(s);
+  const size_t all = p->DbChunkCount();
+  if (!info) return all;
+  const size_t n = std::min(cap, all);
+  for (size_t c = 0; c < n; ++c) p->DbChunkInfo((uint32_t)c, &info[c]);
+  return n;
+}
+
+size_t GhostmSessionDbRecords(void *s, uint32_t chunk, uint8_t *codes, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    return static_cast<Session *>(s)->DbRecords(chunk, codes, cap);
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+int GhostmSessionDbIndex(void *s, uint32_t chunk, uint32_t *keys_count, size_t kc_cap, uint32_t *positions,
+                         size_t pos_cap) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->DbIndex(chunk, keys_count, kc_cap, positions, pos_cap);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionDbStats(void *s, GhostmDbSetStats *stats, size_t size) {
+  if (!s || !stats) return 0;
+  const GhostmDbSetStats st = static_cast<Session *>(s)->DbSetStats();
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmDbSetStats)));
+  return sizeof(GhostmDbSetStats);
+}
+
+int64_t GhostmDbChunkCuts(const uint32_t lengths[], uint64_t n, uint32_t chunk_mb, uint64_t cuts[], uint64_t cap) {
+  try {
+    if (n && !lengths) throw Error("chunk cuts: null argument");
+    if (chunk_mb > kDbChunkMbMax) throw Error("chunk cuts: chunk size above " + std::to_string(kDbChunkMbMax) + " MiB");
+    std::vector<uint64_t> c;
+    const bool whole = DbChunkCuts(lengths, n, DbChunkLimit(chunk_mb), &c);
     if (cuts) std::copy(c.begin(), c.begin() + (long)std::min<uint64_t>(cap, c.size()), cuts);
     if (!whole) throw Error("chunk cuts: too small max length.");
     return (int64_t)c.size() - 1;
@@ -370,18 +462,24 @@ int GhostmAlignMain(int argc, char **argv) {
   return 0;
 }
 
-// `ghostm search`: one database session, then qry + aln per (FASTA, output) pair
-// without the formatted files. Usage errors return 1 before any device call.
+// `ghostm search`: one session with the database resident (-d: from its files;
+// -f: formatted on the device from FASTA), then qry + aln per (FASTA, output)
+// pair without the formatted files. Usage errors return 1 before any device call.
 int GhostmSearchMain(int argc, char **argv) {
   std::vector<char *> aln_argv{argv[0]};
   uint32_t width = 75, chunk_mb = 0;
-  bool dna = false;
+  bool dna = false, have_d = false;
+  std::string db_fasta;
+  uint32_t db_k = 4, db_mb = 0;
   optind = 1;
   opterr = 1;
   int c;
-  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c
-  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:")) >= 0) {
+  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c and -f, -k, -m
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:")) >= 0) {
     switch (c) {
+      case 'f': db_fasta = optarg; break;
+      case 'k': db_k = (uint32_t)atoi(optarg); break;
+      case 'm': db_mb = (uint32_t)atoi(optarg); break;
       case 'q':
         if (strcmp(optarg, "d") == 0) dna = true;
         else if (strcmp(optarg, "p") == 0) dna = false;
@@ -396,6 +494,7 @@ int GhostmSearchMain(int argc, char **argv) {
       case '?': return 1;
       case 'v': aln_argv.push_back(const_cast<char *>("-v")); break;
       default: {
+        if (c == 'd') have_d = true;
         static const char *const kFlags[] = {"-b", "-d", "-D", "-e", "-E", "-G", "-l", "-M", "-r", "-s", "-t", "-y"};
         for (const char *f : kFlags)
           if (f[1] == c) aln_argv.push_back(const_cast<char *>(f));
@@ -405,10 +504,13 @@ int GhostmSearchMain(int argc, char **argv) {
   }
   std::vector<std::string> pos(argv + optind, argv + argc);
   if (pos.empty() || pos.size() % 2) return 1;
+  if (have_d == !db_fasta.empty()) return 1;  // -d or -f, not both
   try {
     aln_argv.push_back(nullptr);
     AlignerOptions opt = ParseAlignerOptions((int)aln_argv.size() - 1, aln_argv.data());
-    Session session(opt, Session::DbOnly{});
+    std::unique_ptr<Session> made(have_d ? new Session(opt, Session::DbOnly{}) : new Session(opt, Session::NoDb{}));
+    Session &session = *made;
+    if (!have_d) session.SetDbFasta(db_fasta, db_k, db_mb);
     for (size_t k = 0; k < pos.size(); k += 2) {
       try {
         { std::ofstream touch(pos[k + 1].c_str()); }

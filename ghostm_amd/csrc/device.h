@@ -145,6 +145,25 @@ class DeviceModule {
   void DownloadQuery(const DevQuery *q, uint8_t *dst);
   DevDb *UploadDb(const uint8_t *seq, uint32_t len, const uint32_t *keys_count, uint32_t kcl,
                   const uint32_t *positions, uint32_t npos);
+  // UploadDb from letters (the resident form of the `db` formatter): the
+  // chunk's n >= 1 records packed one after the other, each record's letters
+  // followed by one '\n' (len bytes together, lengths[r] letters in record r;
+  // no letter may be '\n'). The bytes go up through StagedUpload, are coded on
+  // the main stream straight into the chunk's residues (kern::k_db_code:
+  // ProteinCode per letter, END per separator), and the k-mer index of `seed`
+  // is built from those device residues by the index.hip kernels into the
+  // chunk's keys_count and positions; k_low_keys as UploadDb. The result is
+  // what UploadDb makes of the files `ghostm db` writes for these records
+  // (end_gap and the code flags from the lengths). Only *npos, the number of
+  // positions, comes back. The temporaries (the packed letters and 16 bytes
+  // per position) are module buffers, kept for the next call. *code_seconds,
+  // *index_seconds: the device time of the coding kernel and of the index
+  // build. Throws what CheckIndexSeed says and on lengths that do not add up.
+  DevDb *FormatDb(const uint8_t *packed, uint32_t len, const uint32_t *lengths, uint32_t n, uint32_t seed,
+                  uint32_t *npos, double *code_seconds, double *index_seconds);
+  // A resident DB chunk back on the host: its residues (len bytes, the .seq
+  // file), keys_count (kcl words) and positions (npos words); null: not copied.
+  void DownloadDb(const DevDb *d, uint8_t *seq, uint32_t *keys_count, uint32_t *positions);
   // Name groups of a query chunk (consecutive equal names), for the device merge.
   void SetQueryGroups(DevQuery *q, const uint32_t *first, const uint32_t *last, uint32_t ng);
   // Subject start offsets (.pos) of a DB chunk, for the device merge.

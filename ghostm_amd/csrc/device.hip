@@ -17,6 +17,7 @@
 #include "device.h"
 #include "formats.h"
 #include "hit_batches.h"
+#include "index.h"
 #include "kernels.h"
 #include "path_rows.h"
 #include "pileup_plan.h"
@@ -319,6 +320,13 @@ struct DeviceModule::Impl {
   // lengths, the kernels' tables; the kernel's events
   DevBuf qf_raw, qf_off, qf_len, qf_qlen, qf_tab;
   hipEvent_t ev_q0 = nullptr, ev_q1 = nullptr;
+  // FormatDb: the chunk's packed letters, the index build's (key, position)
+  // pairs with their ping-pong copies and its scan arrays; the kernels' events
+  // (coding: ev_d0..ev_d1, index: ev_d1..ev_d2), the word that comes back
+  DevBuf dbf_raw, dbf_key, dbf_key2, dbf_val, dbf_val2, dbf_tiles, dbf_hist;
+  hipEvent_t ev_d0 = nullptr, ev_d1 = nullptr, ev_d2 = nullptr;
+  kern::DbCodeTable dbf_tab{};
+  bool dbf_tab_set = false;
 };
 
 static constexpr uint32_t kSlotCap = kern::kMaxSlotCap;
@@ -403,15 +411,14 @@ void DeviceModule::Bind(int device) {
   stream_ = s;
   copy_stream_ = c;
 #ifdef GHOSTM_LDS_POISON
-  {  // the pattern every kernel writes over its LDS before its own code runs
-    uint32_t v = 0xA5A5A5A5u;
-    if (const char *e = getenv("GHOSTM_LDS_POISON_PATTERN")) v = (uint32_t)strtoul(e, nullptr, 0);
+  {
+    const uint32_t v = kern::LdsPoisonPattern();
     HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(kern::g_lds_poison), &v, sizeof(v)));
   }
 #endif
   for (hipEvent_t *e : {&impl_->ev0, &impl_->ev1, &impl_->ev_m0, &impl_->ev_m1, &impl_->ev_t0, &impl_->ev_t1, &impl_->ev_tk,
                         &impl_->ev_done, &impl_->ev_tasks, &impl_->ev_s0, &impl_->ev_s1, &impl_->ev_nb, &impl_->ev_q0,
-                        &impl_->ev_q1})
+                        &impl_->ev_q1, &impl_->ev_d0, &impl_->ev_d1, &impl_->ev_d2})
     HIP_CHECK(hipEventCreate(e));
   for (hipEvent_t &e : impl_->stage_ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   HIP_CHECK(hipFuncSetAttribute((const void *)kern::k_seed<1024, 16384, false>,
@@ -682,6 +689,92 @@ DevDb *DeviceModule::UploadDb(const uint8_t *seq, uint32_t len, const uint32_t *
     HIP_CHECK(hipGetLastError());
   }
   return d;
+}
+
+static float ElapsedMs(hipEvent_t a, hipEvent_t b);
+template <class F> static void TimedLaunch(hipEvent_t a, hipEvent_t b, hipStream_t st, F launch);
+
+DevDb *DeviceModule::FormatDb(const uint8_t *packed, uint32_t len, const uint32_t *lengths, uint32_t n,
+                              uint32_t seed, uint32_t *npos, double *code_seconds, double *index_seconds) {
+  Use();
+  if (!impl_) throw Error("device not bound");
+  if (code_seconds) *code_seconds = 0;
+  if (index_seconds) *index_seconds = 0;
+  const uint32_t kcl = SeedWeight(seed) <= 6 ? (1u << (kCharBits * SeedWeight(seed))) + 1 : 0;
+  CheckIndexSeed(seed, kcl);
+  if (n == 0) throw Error("database chunk without records");
+  uint64_t sum = 0;
+  uint32_t end_gap = UINT32_MAX;  // as UploadDb finds it in the bytes: END r - 1 to END r is record r's length + 1
+  for (uint32_t r = 0; r < n; ++r) {
+    sum += (uint64_t)lengths[r] + 1;
+    if (r) end_gap = (uint32_t)std::min<uint64_t>(end_gap, (uint64_t)lengths[r] + 1);
+  }
+  if (sum != len) throw Error("database chunk: the record lengths do not add up to the packed letters");
+  Impl &I = *impl_;
+  if (!I.dbf_tab_set) {
+    uint8_t code[256];
+    for (int b = 0; b < 256; ++b) code[b] = ProteinCode((unsigned char)b);
+    code[kern::kDbCodeSeparator] = kSeqEnd;
+    std::memcpy(I.dbf_tab.w, code, sizeof(code));
+    I.dbf_tab_set = true;
+  }
+  std::unique_ptr<DevDb, std::function<void(DevDb *)>> d(new DevDb(), [this](DevDb *p) { Free(p); });
+  d->end_gap = end_gap;
+  d->codes_le26 = d->codes_le25 = true;  // ProteinCode gives 0..24, the separators END
+  d->len = len;
+  d->kcl = kcl;
+  hipStream_t st = S(stream_);
+  d->seq.Reserve((size_t)kDbFront + len + kDbBack);
+  d->kc.Reserve((size_t)kcl * 4);
+  const IndexScratchBytes sz = IndexScratchSize(len, kcl);
+  I.dbf_raw.Reserve(len);
+  I.dbf_key.Reserve(sz.pairs);
+  I.dbf_key2.Reserve(sz.pairs);
+  I.dbf_val.Reserve(sz.pairs);
+  I.dbf_val2.Reserve(sz.pairs);
+  I.dbf_tiles.Reserve(sz.tiles);
+  I.dbf_hist.Reserve(sz.hist);
+  uint8_t *res = d->seq.as<uint8_t>() + kDbFront;
+  HIP_CHECK(hipMemsetAsync(d->seq.p, (int)kern::kSeqEnd, kDbFront, st));
+  HIP_CHECK(hipMemsetAsync(res + len, (int)kern::kSeqEnd, kDbBack, st));
+  StagedUpload(I.dbf_raw.p, packed, len);
+  TimedLaunch(I.ev_d0, I.ev_d1, st, [&] {
+    hipLaunchKernelGGL(kern::k_db_code, dim3((len + kern::kDbCodeTile - 1) / kern::kDbCodeTile),
+                       dim3(kern::kDbCodeBlock), 0, st, I.dbf_raw.as<uint8_t>(), len, I.dbf_tab, res);
+  });
+  const uint32_t *sorted = LaunchIndexBuild(
+      stream_, res, len, seed, kcl, d->kc.as<uint32_t>(),
+      IndexScratch{I.dbf_key.as<uint32_t>(), I.dbf_key2.as<uint32_t>(), I.dbf_val.as<uint32_t>(),
+                   I.dbf_val2.as<uint32_t>(), I.dbf_tiles.as<uint32_t>(), I.dbf_hist.as<uint32_t>()});
+  HIP_CHECK(hipEventRecord(I.ev_d2, st));
+  uint32_t np = 0;
+  HIP_CHECK(hipMemcpyAsync(&np, d->kc.as<uint32_t>() + (kcl - 1), 4, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  if (np > len) throw Error("index: position count out of range");
+  d->npos = np;
+  d->pos.Reserve(((size_t)np + kern::kPosTailPad) * 4);
+  if (np) HIP_CHECK(hipMemcpyAsync(d->pos.p, sorted, (size_t)np * 4, hipMemcpyDeviceToDevice, st));
+  HIP_CHECK(hipMemsetAsync(d->pos.as<uint32_t>() + np, 0, (size_t)kern::kPosTailPad * 4, st));
+  const uint32_t nkeys = kcl - 1;
+  d->low.Reserve(((size_t)nkeys + 63) / 64 * 8 + 8);
+  hipLaunchKernelGGL(kern::k_low_keys, dim3((nkeys + 255) / 256), dim3(256), 0, st, d->kc.as<uint32_t>(),
+                     d->pos.as<uint32_t>(), nkeys, d->low.as<unsigned long long>());
+  HIP_CHECK(hipGetLastError());
+  if (code_seconds) *code_seconds = ElapsedMs(I.ev_d0, I.ev_d1) * 1e-3;
+  if (index_seconds) *index_seconds = ElapsedMs(I.ev_d1, I.ev_d2) * 1e-3;
+  *npos = np;
+  return d.release();
+}
+
+void DeviceModule::DownloadDb(const DevDb *d, uint8_t *seq, uint32_t *keys_count, uint32_t *positions) {
+  Use();
+  hipStream_t st = S(stream_);
+  if (seq && d->len) HIP_CHECK(hipMemcpyAsync(seq, d->Residues(), d->len, hipMemcpyDeviceToHost, st));
+  if (keys_count && d->kcl)
+    HIP_CHECK(hipMemcpyAsync(keys_count, d->kc.p, (size_t)d->kcl * 4, hipMemcpyDeviceToHost, st));
+  if (positions && d->npos)
+    HIP_CHECK(hipMemcpyAsync(positions, d->pos.p, (size_t)d->npos * 4, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
 }
 
 void DeviceModule::Free(DevQuery *q) {

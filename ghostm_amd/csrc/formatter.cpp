@@ -22,6 +22,7 @@
 
 #include "../../include/ghostm_hip.h"
 #include "common.h"
+#include "db_set.h"
 #include "formats.h"
 #include "query_set.h"
 
@@ -123,32 +124,15 @@ int DbFormatMain(int argc, char **argv) {
   }
   const uint32_t seed_len = SeedLength(seed), weight = SeedWeight(seed);
   const uint32_t kcl = (uint32_t)pow(32.0, (double)weight) + 1;
-  FastaReader reader(in_path);
-  bool pending_valid = false;
-  FastaRecord pending;
+  DbChunkReader reader(in_path, max_concat);
   uint64_t sum_length = 0;
   for (int chunk = 0;; ++chunk) {
     std::vector<FastaRecord> recs;
-    uint32_t sum = 0;
-    if (pending_valid) {
-      sum = (uint32_t)pending.seq.size() + 1;
-      if (sum > max_concat) {
-        std::cerr << "error : too small max length." << std::endl;
-        return 1;
-      }
-      recs.push_back(pending);
-      pending_valid = false;
-    }
-    FastaRecord r;
-    while (reader.Next(&r)) {
-      sum += (uint32_t)r.seq.size() + 1;
-      if (sum > max_concat) {
-        pending = r;
-        pending_valid = true;
-        sum -= (uint32_t)r.seq.size() + 1;
-        break;
-      }
-      recs.push_back(r);
+    // (db_set.h) a record alone over the limit: carried from an earlier chunk
+    // it is an error; as the file's first record it ends the database silently
+    if (reader.Next(&recs) < 0 && chunk > 0) {
+      std::cerr << "error : too small max length." << std::endl;
+      return 1;
     }
     if (recs.empty()) {
       std::ofstream f((out_prefix + ".inf").c_str(), std::ios::binary);

@@ -18,6 +18,12 @@
 //                   ballot matching of the digit bits, across waves by an LDS
 //                   prefix). j ascending within each key, the keyless windows
 //                   (sentinel) last, so positions = the first npos values.
+//
+// The launch sequence is LaunchIndexBuild (index.h): device residues, a stream
+// and scratch arrays of the caller's. GhostmBuildIndexGpu (`db -D`) uploads the
+// residues and copies keys_count and positions back; a session's replaced
+// database (DeviceModule::FormatDb) runs it on the module's main stream over
+// the residues it has just coded, and keeps both arrays on the device.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +33,8 @@
 #include "../../include/ghostm_hip.h"
 #include "common.h"
 #include "formats.h"
+#include "index.h"
+#include "lds_poison.h"
 
 namespace ghostm {
 
@@ -91,6 +99,7 @@ __device__ inline uint32_t BlockInclusiveScan(uint32_t v, uint32_t *s_part) {
 }
 
 __global__ __launch_bounds__(kIdxBlock) void k_scan_tiles(uint32_t *x, uint32_t n, uint32_t *tile_sum) {
+  GHOSTM_POISON_LDS();
   __shared__ uint32_t s_part[kIdxBlock / 64];
   const uint32_t base = blockIdx.x * kScanTile + threadIdx.x * kScanItems;
   uint32_t v[kScanItems], sum = 0;
@@ -111,6 +120,7 @@ __global__ __launch_bounds__(kIdxBlock) void k_scan_tiles(uint32_t *x, uint32_t 
 
 // exclusive prefix of the tile sums, in place (one block, any count)
 __global__ __launch_bounds__(kIdxBlock) void k_scan_sums(uint32_t *tile_sum, uint32_t ntiles) {
+  GHOSTM_POISON_LDS();
   __shared__ uint32_t s_part[kIdxBlock / 64];
   __shared__ uint32_t s_carry;
   if (threadIdx.x == 0) s_carry = 0;
@@ -141,6 +151,7 @@ static_assert(kIdxBlock == 64 * kRsWaves && kIdxBlock == kRsDigits, "one thread 
 // Digit counts of tile t, digit-major: hist[d * ntiles + t].
 __global__ __launch_bounds__(kIdxBlock) void k_rs_hist(const uint32_t *key, uint32_t n, uint32_t shift,
                                                         uint32_t ntiles, uint32_t *hist) {
+  GHOSTM_POISON_LDS();
   __shared__ uint32_t s_h[kRsDigits];
   s_h[threadIdx.x] = 0;
   __syncthreads();
@@ -161,6 +172,7 @@ __global__ __launch_bounds__(kIdxBlock) void k_rs_hist(const uint32_t *key, uint
 __global__ __launch_bounds__(kIdxBlock) void k_rs_scatter(const uint32_t *key_in, const uint32_t *val_in, uint32_t n,
                                                            uint32_t shift, uint32_t ntiles, const uint32_t *incl,
                                                            uint32_t *key_out, uint32_t *val_out, bool write_keys) {
+  GHOSTM_POISON_LDS();
   __shared__ uint32_t s_cnt[kRsWaves][kRsDigits];
   __shared__ uint32_t s_base[kRsDigits];
   const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -233,15 +245,74 @@ uint32_t Bits(uint32_t v) {
   return b;
 }
 
+// LDS poison build: this translation unit's pattern, before a build's launches
+void SetPoisonPattern() {
+#ifdef GHOSTM_LDS_POISON
+  const uint32_t v = kern::LdsPoisonPattern();
+  IDX_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(kern::g_lds_poison), &v, sizeof(v)));
+#endif
+}
+
 }  // namespace
+
+void CheckIndexSeed(uint32_t seed, uint32_t kcl) {
+  if (seed == 0) throw Error("index: empty seed");
+  const uint32_t weight = SeedWeight(seed);
+  if (weight > 6) throw Error("index: seed weight above 6");
+  if (kcl != (1u << (kCharBits * weight)) + 1) throw Error("index: keys_count length must be 32^weight + 1");
+}
+
+IndexScratchBytes IndexScratchSize(uint32_t len, uint32_t kcl) {
+  const uint32_t rs_tiles = (uint32_t)(((uint64_t)len + kRsTile - 1) / kRsTile);
+  const uint32_t rs_hist_n = rs_tiles * kRsDigits;
+  const uint32_t scan_n = std::max(kcl, rs_hist_n);
+  IndexScratchBytes b;
+  b.pairs = 4ull * len;
+  b.tiles = 4ull * ((scan_n + kScanTile - 1) / kScanTile);
+  b.hist = 4ull * rs_hist_n;
+  return b;
+}
+
+const uint32_t *LaunchIndexBuild(void *stream, const uint8_t *d_seq, uint32_t len, uint32_t seed, uint32_t kcl,
+                                 uint32_t *d_counts, const IndexScratch &s) {
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  SetPoisonPattern();
+  const uint32_t span = SeedLength(seed), weight = SeedWeight(seed);
+  const uint32_t sentinel = 1u << (kCharBits * weight);
+  const uint32_t rs_tiles = (uint32_t)(((uint64_t)len + kRsTile - 1) / kRsTile);
+  const uint32_t rs_hist_n = rs_tiles * kRsDigits;
+  const uint32_t ntiles = (kcl + kScanTile - 1) / kScanTile;
+  const uint32_t end_bit = Bits(sentinel);
+  IDX_CHECK(hipMemsetAsync(d_counts, 0, 4ull * kcl, st));
+  hipLaunchKernelGGL(k_index_keys, dim3((len + kIdxBlock - 1) / kIdxBlock), dim3(kIdxBlock), 0, st, d_seq, len, seed,
+                     span, sentinel, s.key, s.val, d_counts);
+  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kIdxBlock), 0, st, d_counts, kcl, s.tiles);
+  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kIdxBlock), 0, st, s.tiles, ntiles);
+  hipLaunchKernelGGL(k_scan_add, dim3((kcl + kIdxBlock - 1) / kIdxBlock), dim3(kIdxBlock), 0, st, d_counts, kcl,
+                     s.tiles);
+  IDX_CHECK(hipGetLastError());
+  // stable LSD radix sort of (key, j), ping-ponging between the two buffer pairs
+  uint32_t *kin = s.key, *vin = s.val, *kout = s.key2, *vout = s.val2;
+  const uint32_t hist_tiles = (rs_hist_n + kScanTile - 1) / kScanTile;
+  for (uint32_t shift = 0; shift < end_bit; shift += kRsBits) {
+    const bool last = shift + kRsBits >= end_bit;
+    hipLaunchKernelGGL(k_rs_hist, dim3(rs_tiles), dim3(kIdxBlock), 0, st, kin, len, shift, rs_tiles, s.hist);
+    hipLaunchKernelGGL(k_scan_tiles, dim3(hist_tiles), dim3(kIdxBlock), 0, st, s.hist, rs_hist_n, s.tiles);
+    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kIdxBlock), 0, st, s.tiles, hist_tiles);
+    hipLaunchKernelGGL(k_scan_add, dim3((rs_hist_n + kIdxBlock - 1) / kIdxBlock), dim3(kIdxBlock), 0, st, s.hist,
+                       rs_hist_n, s.tiles);
+    hipLaunchKernelGGL(k_rs_scatter, dim3(rs_tiles), dim3(kIdxBlock), 0, st, kin, vin, len, shift, rs_tiles, s.hist,
+                       kout, vout, !last);
+    IDX_CHECK(hipGetLastError());
+    std::swap(kin, kout);
+    std::swap(vin, vout);
+  }
+  return vin;
+}
 
 void BuildIndexDevice(const uint8_t *seq, uint32_t len, uint32_t seed, uint32_t kcl, uint32_t *keys_count,
                       uint32_t *positions, uint32_t *npos, int device, float *device_ms) {
-  if (seed == 0) throw Error("index: empty seed");
-  const uint32_t span = SeedLength(seed), weight = SeedWeight(seed);
-  if (weight > 6) throw Error("index: seed weight above 6");
-  const uint32_t sentinel = 1u << (kCharBits * weight);
-  if (kcl != sentinel + 1) throw Error("index: keys_count length must be 32^weight + 1");
+  CheckIndexSeed(seed, kcl);
   int ndev = 0;
   IDX_CHECK(hipGetDeviceCount(&ndev));
   if (device < 0 || device >= ndev) throw Error("index: no such device");
@@ -258,13 +329,9 @@ void BuildIndexDevice(const uint8_t *seq, uint32_t len, uint32_t seed, uint32_t 
     hipStream_t s;
     ~StreamGuard() { (void)hipStreamDestroy(s); }
   } sg{st};
-  const uint32_t rs_tiles = (uint32_t)(((uint64_t)len + kRsTile - 1) / kRsTile);
-  const uint32_t rs_hist_n = rs_tiles * kRsDigits;
-  const uint32_t scan_n = std::max(kcl, rs_hist_n);
-  const uint32_t ntiles = (kcl + kScanTile - 1) / kScanTile;
-  Buf d_seq(len), d_key(4ull * len), d_key2(4ull * len), d_val(4ull * len), d_val2(4ull * len);
-  Buf d_counts(4ull * kcl), d_tiles(4ull * ((scan_n + kScanTile - 1) / kScanTile)), d_hist(4ull * rs_hist_n);
-  const uint32_t end_bit = Bits(sentinel);
+  const IndexScratchBytes sz = IndexScratchSize(len, kcl);
+  Buf d_seq(len), d_key(sz.pairs), d_key2(sz.pairs), d_val(sz.pairs), d_val2(sz.pairs);
+  Buf d_counts(4ull * kcl), d_tiles(sz.tiles), d_hist(sz.hist);
   hipEvent_t e0, e1;
   IDX_CHECK(hipEventCreate(&e0));
   IDX_CHECK(hipEventCreate(&e1));
@@ -277,41 +344,16 @@ void BuildIndexDevice(const uint8_t *seq, uint32_t len, uint32_t seed, uint32_t 
   } eg{e0, e1};
   IDX_CHECK(hipMemcpyAsync(d_seq.p, seq, len, hipMemcpyHostToDevice, st));
   IDX_CHECK(hipEventRecord(e0, st));
-  IDX_CHECK(hipMemsetAsync(d_counts.p, 0, 4ull * kcl, st));
-  hipLaunchKernelGGL(k_index_keys, dim3((len + kIdxBlock - 1) / kIdxBlock), dim3(kIdxBlock), 0, st,
-                     d_seq.as<uint8_t>(), len, seed, span, sentinel, d_key.as<uint32_t>(), d_val.as<uint32_t>(),
-                     d_counts.as<uint32_t>());
-  hipLaunchKernelGGL(k_scan_tiles, dim3(ntiles), dim3(kIdxBlock), 0, st, d_counts.as<uint32_t>(), kcl,
-                     d_tiles.as<uint32_t>());
-  hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kIdxBlock), 0, st, d_tiles.as<uint32_t>(), ntiles);
-  hipLaunchKernelGGL(k_scan_add, dim3((kcl + kIdxBlock - 1) / kIdxBlock), dim3(kIdxBlock), 0, st,
-                     d_counts.as<uint32_t>(), kcl, d_tiles.as<uint32_t>());
-  IDX_CHECK(hipGetLastError());
-  // stable LSD radix sort of (key, j), ping-ponging between the two buffer pairs
-  uint32_t *kin = d_key.as<uint32_t>(), *vin = d_val.as<uint32_t>();
-  uint32_t *kout = d_key2.as<uint32_t>(), *vout = d_val2.as<uint32_t>();
-  const uint32_t hist_tiles = (rs_hist_n + kScanTile - 1) / kScanTile;
-  for (uint32_t shift = 0; shift < end_bit; shift += kRsBits) {
-    const bool last = shift + kRsBits >= end_bit;
-    hipLaunchKernelGGL(k_rs_hist, dim3(rs_tiles), dim3(kIdxBlock), 0, st, kin, len, shift, rs_tiles,
-                       d_hist.as<uint32_t>());
-    hipLaunchKernelGGL(k_scan_tiles, dim3(hist_tiles), dim3(kIdxBlock), 0, st, d_hist.as<uint32_t>(), rs_hist_n,
-                       d_tiles.as<uint32_t>());
-    hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(kIdxBlock), 0, st, d_tiles.as<uint32_t>(), hist_tiles);
-    hipLaunchKernelGGL(k_scan_add, dim3((rs_hist_n + kIdxBlock - 1) / kIdxBlock), dim3(kIdxBlock), 0, st,
-                       d_hist.as<uint32_t>(), rs_hist_n, d_tiles.as<uint32_t>());
-    hipLaunchKernelGGL(k_rs_scatter, dim3(rs_tiles), dim3(kIdxBlock), 0, st, kin, vin, len, shift, rs_tiles,
-                       d_hist.as<uint32_t>(), kout, vout, !last);
-    IDX_CHECK(hipGetLastError());
-    std::swap(kin, kout);
-    std::swap(vin, vout);
-  }
+  const uint32_t *sorted = LaunchIndexBuild(
+      st, d_seq.as<uint8_t>(), len, seed, kcl, d_counts.as<uint32_t>(),
+      IndexScratch{d_key.as<uint32_t>(), d_key2.as<uint32_t>(), d_val.as<uint32_t>(), d_val2.as<uint32_t>(),
+                   d_tiles.as<uint32_t>(), d_hist.as<uint32_t>()});
   IDX_CHECK(hipEventRecord(e1, st));
   IDX_CHECK(hipMemcpyAsync(keys_count, d_counts.p, 4ull * kcl, hipMemcpyDeviceToHost, st));
   IDX_CHECK(hipStreamSynchronize(st));
   const uint32_t n = keys_count[kcl - 1];
   if (n > len) throw Error("index: position count out of range");
-  if (n) IDX_CHECK(hipMemcpyAsync(positions, vin, 4ull * n, hipMemcpyDeviceToHost, st));
+  if (n) IDX_CHECK(hipMemcpyAsync(positions, sorted, 4ull * n, hipMemcpyDeviceToHost, st));
   IDX_CHECK(hipStreamSynchronize(st));
   *npos = n;
   if (device_ms) IDX_CHECK(hipEventElapsedTime(device_ms, e0, e1));

@@ -24,37 +24,13 @@
 
 #include <type_traits>
 
+#include "lds_poison.h"
 #include "libstdcxx_sort.h"
 #include "score_task.h"
 #include "seed_lists.h"
 
 namespace ghostm {
 namespace kern {
-
-// LDS poison build (-DGHOSTM_LDS_POISON=1, ghostm_amd/lib/libghostm_hip_poison.so):
-// every kernel first fills its whole LDS allocation, static and dynamic (the
-// dispatch packet's group_segment_size), with g_lds_poison, so a read of LDS
-// the kernel never wrote returns that pattern instead of whatever an earlier
-// workgroup left there. Tests run the golden variants under two patterns: a
-// result that depends on such a read differs under one of them.
-#ifdef GHOSTM_LDS_POISON
-__device__ uint32_t g_lds_poison = 0xA5A5A5A5u;  // set at Bind from GHOSTM_LDS_POISON_PATTERN
-__device__ __forceinline__ void PoisonLds() {
-  // hsa_kernel_dispatch_packet_t: group_segment_size at byte 28
-  typedef const __attribute__((address_space(4))) uint32_t *PacketWords;
-  const uint32_t bytes = ((PacketWords)__builtin_amdgcn_dispatch_ptr())[7];
-  const uint32_t v = g_lds_poison;
-  const uint32_t nthreads = blockDim.x * blockDim.y * blockDim.z;
-  const uint32_t tid = threadIdx.x + blockDim.x * (threadIdx.y + blockDim.y * threadIdx.z);
-  for (uint32_t off = tid * 4; off + 4 <= bytes; off += nthreads * 4)
-    asm volatile("ds_write_b32 %0, %1" : : "v"(off), "v"(v) : "memory");
-  asm volatile("s_waitcnt lgkmcnt(0)" : : : "memory");
-  __syncthreads();
-}
-#define GHOSTM_POISON_LDS() ::ghostm::kern::PoisonLds()
-#else
-#define GHOSTM_POISON_LDS() ((void)0)
-#endif
 
 constexpr uint32_t kSeqEnd = 25;
 constexpr uint32_t kPadCode = 31;      // unused residue code: query padding rows
@@ -117,6 +93,49 @@ __global__ __launch_bounds__(256) void k_low_keys(const uint32_t *keys_count, co
   }
   const unsigned long long m = __ballot(bit);
   if ((threadIdx.x & 63) == 0 && k < nkeys) low[k >> 6] = m;
+}
+
+// ------------------------------------------------------------------ DB coding
+// k_db_code: a resident database chunk from letters (DeviceModule::FormatDb).
+// The host packs every record's letters followed by one '\n', a byte no FASTA
+// letter can be (the reader splits lines on it), so the chunk's .seq bytes are
+// a pure byte map of the packed buffer: letter -> ProteinCode, '\n' -> END. No
+// record boundary is looked at. Each lane maps 16 bytes (one dwordx4 load, one
+// dwordx4 store: raw and out are 16-byte aligned), the last lanes of the chunk
+// their bytes one by one. The 256-entry table comes in the kernel arguments
+// and is staged into LDS, 64 words by the first wave.
+constexpr uint32_t kDbCodeBlock = 256, kDbCodeVec = 16;
+constexpr uint32_t kDbCodeTile = kDbCodeBlock * kDbCodeVec;  // bytes per workgroup
+constexpr uint8_t kDbCodeSeparator = '\n';
+struct DbCodeTable {
+  uint32_t w[64];  // byte b's code is byte b & 3 of w[b >> 2]
+};
+
+__device__ __forceinline__ uint32_t DbCodeWord(const uint8_t *s_code, uint32_t w) {
+  return (uint32_t)s_code[w & 255u] | (uint32_t)s_code[(w >> 8) & 255u] << 8 |
+         (uint32_t)s_code[(w >> 16) & 255u] << 16 | (uint32_t)s_code[w >> 24] << 24;
+}
+
+__global__ __launch_bounds__(kDbCodeBlock) void k_db_code(const uint8_t *raw, uint32_t len, DbCodeTable tab,
+                                                          uint8_t *out) {
+  GHOSTM_POISON_LDS();
+  __shared__ uint32_t s_tab[64];
+  const uint64_t i = ((uint64_t)blockIdx.x * kDbCodeBlock + threadIdx.x) * kDbCodeVec;
+  const bool whole = i + kDbCodeVec <= len;
+  // the letters are asked for before the table is staged: the two waits overlap
+  uint4 v = whole ? *reinterpret_cast<const uint4 *>(raw + i) : make_uint4(0, 0, 0, 0);
+  if (threadIdx.x < 64) s_tab[threadIdx.x] = tab.w[threadIdx.x];
+  __syncthreads();
+  const uint8_t *s_code = reinterpret_cast<const uint8_t *>(s_tab);
+  if (whole) {
+    v.x = DbCodeWord(s_code, v.x);
+    v.y = DbCodeWord(s_code, v.y);
+    v.z = DbCodeWord(s_code, v.z);
+    v.w = DbCodeWord(s_code, v.w);
+    *reinterpret_cast<uint4 *>(out + i) = v;
+  } else {
+    for (uint64_t k = i; k < len; ++k) out[k] = s_code[raw[k]];
+  }
 }
 
 __global__ __launch_bounds__(256) void k_seed_lists(SeedListArgs a) {

@@ -1,6 +1,7 @@
 // main.cpp — the `ghostm` command line (reference main.cpp:36-122): db | qry | aln,
 // plus `synth` (synthetic benchmark inputs) and `search` (qry + aln for several
-// FASTA files against one resident database). `aln` always runs on the GPU
+// FASTA files against one resident database, given as formatted files or, with
+// -f, as FASTA formatted on the GPU). `aln` always runs on the GPU
 // (-D selects the device, default 0). Errors are printed and the process exits 0
 // like the reference; usage or an unknown command exits 1.
 #include <unistd.h>
@@ -30,8 +31,9 @@ static int Usage() {
             << "       -i queries -d database -o output\n"
             << "       (-y 6: BLAST-tabular, the twelve -outfmt 6 columns)\n"
             << "search: ghostm search [aln options except -i -o -S -L] [-q d|p] [-w maxLength] [-c chunkSizeMB]\n"
-            << "       -d database q1.fasta out1 [q2.fasta out2 ...]\n"
-            << "       (qry + aln per pair on one resident database; -q -w -c as qry's -t -l -L)\n"
+            << "       (-d database | -f db.fasta [-k kSize] [-m chunkSizeMB]) q1.fasta out1 [q2.fasta out2 ...]\n"
+            << "       (qry + aln per pair on one resident database; -q -w -c as qry's -t -l -L;\n"
+            << "        -f: the database formatted on the GPU from FASTA, -k -m as db's -k -l)\n"
             << "synth: ghostm synth -d db.fasta -q queries.fasta [-n nq] [-N dbResidues] [-s seed]\n";
   return 1;
 }

@@ -97,6 +97,25 @@ class GhostmSubjectPileup(ctypes.Structure):
     ]
 
 
+class GhostmDbChunkInfo(ctypes.Structure):
+    """one resident DB chunk: the values of its .inf and .ind headers."""
+
+    _fields_ = [(n, c_uint32) for n in ("id", "nseq", "len", "seed", "kcl", "npos")]
+
+
+class GhostmDbSetStats(ctypes.Structure):
+    """the counters of a session's database sets (GhostmSessionDbStats)."""
+
+    _fields_ = [
+        ("seconds_db_format", ctypes.c_double),
+        ("seconds_db_code", ctypes.c_double),
+        ("db_format_launches", c_uint64),
+        ("db_sets", c_uint64),
+        ("seconds_db_read", ctypes.c_double),
+        ("seconds_db_load", ctypes.c_double),
+    ]
+
+
 class GhostmStats(ctypes.Structure):
     _fields_ = [
         ("seconds_total", ctypes.c_double),
@@ -233,6 +252,15 @@ SIGNATURES = {
     "GhostmSessionQueryLengths": (c_size_t, [c_void_p, u32p, c_size_t]),
     "GhostmSessionQueryRecords": (c_size_t, [c_void_p, c_uint32, POINTER(ctypes.c_uint8), c_size_t]),
     "GhostmQueryChunkCuts": (ctypes.c_int64, [u32p, c_uint64, c_uint32, c_int, POINTER(c_uint64), c_uint64]),
+    "GhostmSessionCreateQueries": (c_void_p, [c_int, POINTER(c_char_p)]),
+    "GhostmSessionSetDb": (c_int, [c_void_p, POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_char_p,
+                                   c_uint64, c_uint32, c_uint32, c_uint32]),
+    "GhostmSessionSetDbFasta": (c_int, [c_void_p, c_char_p, c_uint32, c_uint32]),
+    "GhostmSessionDbChunks": (c_size_t, [c_void_p, POINTER(GhostmDbChunkInfo), c_size_t]),
+    "GhostmSessionDbRecords": (c_size_t, [c_void_p, c_uint32, POINTER(ctypes.c_uint8), c_size_t]),
+    "GhostmSessionDbIndex": (c_int, [c_void_p, c_uint32, u32p, c_size_t, u32p, c_size_t]),
+    "GhostmSessionDbStats": (c_size_t, [c_void_p, POINTER(GhostmDbSetStats), c_size_t]),
+    "GhostmDbChunkCuts": (ctypes.c_int64, [u32p, c_uint64, c_uint32, POINTER(c_uint64), c_uint64]),
     "GhostmSessionCreateShard": (c_void_p, [c_int, POINTER(c_char_p), c_int, c_int]),
     "GhostmSessionCreateShardEx": (c_void_p, [c_int, POINTER(c_char_p), c_int, c_int, c_void_p, c_void_p]),
     "GhostmSessionShardRange": (c_int, [c_void_p, POINTER(c_uint64), POINTER(c_uint64)]),

@@ -515,6 +515,90 @@ size_t GhostmSessionQueryRecords(void *session, uint32_t chunk, uint8_t *codes, 
 int64_t GhostmQueryChunkCuts(const uint32_t lengths[], uint64_t n, uint32_t chunk_mb, int dna, uint64_t cuts[],
                              uint64_t cap);
 
+/* A session without a database: `aln`'s options without -d (giving it is an
+ * error). With -i the query chunks are loaded as GhostmSessionCreate loads
+ * them; without -i the session starts with neither input and the queries come
+ * from GhostmSessionSetQueries*. The database comes from GhostmSessionSetDb /
+ * GhostmSessionSetDbFasta, any number of times: one read set against many
+ * databases, and with both setters a search needs no formatted file at all.
+ * GhostmSessionRun before any database gives empty output and no hits. Returns
+ * NULL on error. */
+void *GhostmSessionCreateQueries(int argc, char **argv);
+
+/* Replaces the session's database by n records given as letters, in the layout
+ * of GhostmSessionSetQueries. k is given as `db -k` (the seed mask is 2^k - 1),
+ * chunk_mb as `db -l` (0: db's default of 128). Afterwards the session holds
+ * what a session created with -d P would hold after `ghostm db -i <that FASTA>
+ * -o P -k k -l chunk_mb`: the same chunk cuts, residues, subject starts, names
+ * and k-mer index, and the search space of the E-values is the new database's.
+ * The letters are coded on the device straight into the resident chunks and
+ * the index is built there from the device residues; only one word per chunk
+ * (the number of positions) comes back, and no file is written. The results of
+ * the previous run are dropped and the old chunks' device memory is kept for
+ * re-use; the query chunks, the matrix and the options are untouched. Works on
+ * any unsharded session, one created with -d included. Fails on a shard
+ * session (its batch plan was agreed on the old database), on null arguments,
+ * a record outside the letter buffer, a file that cannot be opened, k = 0 or a
+ * seed of weight above 6, chunk_mb above 2047, and a record that alone is over
+ * the chunk limit: all of these leave the session as it was. A failure while
+ * the chunks are being loaded (from a FASTA file, a record over the chunk
+ * limit is found only then) leaves the session with no database. Returns 0 on
+ * success. */
+int GhostmSessionSetDb(void *session, const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets,
+                       const uint32_t *lengths, const char *names, uint64_t names_len, uint32_t n, uint32_t k,
+                       uint32_t chunk_mb);
+
+/* The same from a FASTA file, read as `ghostm db` reads it. */
+int GhostmSessionSetDbFasta(void *session, const char *path, uint32_t k, uint32_t chunk_mb);
+
+/* One resident DB chunk: the values of its <p>_<id>.inf and .ind headers. */
+typedef struct GhostmDbChunkInfo {
+  uint32_t id, nseq, len, seed, kcl, npos;
+} GhostmDbChunkInfo;
+
+/* The session's DB chunks in order, file-loaded or set; the NULL/cap convention
+ * of GhostmSessionHits. */
+size_t GhostmSessionDbChunks(void *session, GhostmDbChunkInfo *info, size_t cap);
+
+/* The residues of DB chunk `chunk` (the bytes of its .seq file) copied back
+ * from the device; the convention of GhostmSessionQueryRecords. */
+size_t GhostmSessionDbRecords(void *session, uint32_t chunk, uint8_t *codes, size_t cap);
+
+/* The index of DB chunk `chunk` copied back from the device: keys_count (kcl
+ * words) and positions (npos words) of its .ind file, each may be NULL; a cap
+ * below the array's length is an error. Returns 0 on success. */
+int GhostmSessionDbIndex(void *session, uint32_t chunk, uint32_t *keys_count, size_t kc_cap, uint32_t *positions,
+                         size_t pos_cap);
+
+/* The counters of the session's database sets. They are a struct of their own
+ * and not fields of GhostmStats, whose layout and end stay as they are for
+ * existing callers. All are 0 for a database read from formatted files. */
+typedef struct GhostmDbSetStats {
+  double seconds_db_format;         /* the resident database formatting of the last GhostmSessionSetDb*: the coding
+                                       kernel (k_db_code) and the index build (index.hip), device time over its
+                                       chunks */
+  double seconds_db_code;           /* ... of which the coding kernel alone */
+  uint64_t db_format_launches;      /* ... its DeviceModule::FormatDb passes (one per DB chunk) */
+  uint64_t db_sets;                 /* GhostmSessionSetDb* calls that replaced the database, since creation */
+  double seconds_db_read;           /* ... of the last one, host wall clock: reading the FASTA file and cutting it
+                                       into chunks (0 for GhostmSessionSetDb) */
+  double seconds_db_load;           /* ... packing the letters, names and starts, the staged upload, the subject
+                                       table, without seconds_db_format */
+} GhostmDbSetStats;
+
+/* Copies min(size, sizeof(GhostmDbSetStats)) bytes and returns the library's
+ * sizeof (the convention of GhostmSessionStatsSized); 0 on a null argument. */
+size_t GhostmSessionDbStats(void *session, GhostmDbSetStats *stats, size_t size);
+
+/* The chunk cuts of `ghostm db` on their own (host only, no device): over n
+ * records of the given letter counts with `db -l chunk_mb` (0: the default). A
+ * record joins the chunk while the sum of length + 1 stays within chunk_mb
+ * MiB. The conventions of GhostmQueryChunkCuts. Returns -1 when a record alone
+ * is over the limit, as the file's first record too (where `ghostm db` itself
+ * silently writes a database without chunks), and when chunk_mb is above 2047
+ * (the chunk's 32-bit offsets). */
+int64_t GhostmDbChunkCuts(const uint32_t lengths[], uint64_t n, uint32_t chunk_mb, uint64_t cuts[], uint64_t cap);
+
 /* Multi-GPU (the reference has no multi-GPU path, common.h:37):
  * one process per GPU, each opening a shard session. The query set selected by
  * -i/-S/-L is cut into `world` contiguous ranges of about equal residues, only
@@ -709,12 +793,16 @@ void GhostmSessionDestroy(void *session);
 int GhostmAlignMain(int argc, char **argv);
 
 /* `ghostm search [aln options except -i -o -S -L] [-q d|p] [-w maxLength]
- * [-c chunkSizeMB] -d database q1.fasta out1 [q2.fasta out2 ...]`: one database
- * session; for each pair the queries are set from the FASTA file (-q, -w, -c as
- * qry's -t, -l, -L; qry's warnings on stderr) and searched into the output
- * file, which equals `ghostm qry` + `ghostm aln` on that FASTA. Wrong usage (no
- * pairs, an odd number of positionals, -i, -o, -S or -L) returns 1 before any
- * device call; errors are printed and 0 returned, as GhostmAlignMain. */
+ * [-c chunkSizeMB] (-d database | -f db.fasta [-k kSize] [-m chunkSizeMB])
+ * q1.fasta out1 [q2.fasta out2 ...]`: one session with the database resident,
+ * from its formatted files (-d) or formatted on the device from FASTA (-f, with
+ * -k and -m as db's -k and -l: GhostmSessionCreateQueries and one
+ * GhostmSessionSetDbFasta); for each pair the queries are set from the FASTA
+ * file (-q, -w, -c as qry's -t, -l, -L; qry's warnings on stderr) and searched
+ * into the output file, which equals [`ghostm db` +] `ghostm qry` + `ghostm
+ * aln` on those files. Wrong usage (no pairs, an odd number of positionals,
+ * -i, -o, -S or -L, both or neither of -d and -f) returns 1 before any device
+ * call; errors are printed and 0 returned, as GhostmAlignMain. */
 int GhostmSearchMain(int argc, char **argv);
 
 #ifdef __cplusplus
