@@ -66,6 +66,28 @@ HIT_ROWS_DTYPE = np.dtype([("query_record", "<u4"), ("columns", "<u4"), ("identi
                            ("gap_residues", "<u4"), ("rescore", "<i4"), ("rows_offset", "<u8")])
 
 
+# GhostmQueryTile: one per output record of a tiled query set
+QUERY_TILE_DTYPE = np.dtype([("record", "<u4"), ("offset", "<u4"), ("letters", "<u4"), ("frame", "<u4")])
+
+
+def tile_plan(lengths, width: int = 75, dna: bool = False, max_len: int = 0, step: int = 1):
+    """The tile table a tiled set_queries would make of records of these letter
+    counts (GhostmQueryTilePlan; no device): (tiles[QUERY_TILE_DTYPE],
+    cut_records). width, dna, max_len and step as given to set_queries."""
+    lib = native.load()
+    lens = np.ascontiguousarray(lengths, dtype=np.uint32)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    cut = ctypes.c_uint64(0)
+    args = (lens.ctypes.data_as(u32p), len(lens), int(width), int(bool(dna)), int(max_len), int(step))
+    n = lib.GhostmQueryTilePlan(*args, None, 0, ctypes.byref(cut))
+    if n < 0:
+        raise GhostmError(native.last_error())
+    out = np.zeros(n, dtype=QUERY_TILE_DTYPE)
+    if n:
+        lib.GhostmQueryTilePlan(*args, out.ctypes.data_as(ctypes.POINTER(native.GhostmQueryTile)), n, ctypes.byref(cut))
+    return out, int(cut.value)
+
+
 def rows_of(rec, rows, h) -> tuple[bytes, bytes, bytes]:
     """(query row, midline, subject row) of hit h of a (rec, rows) pair."""
     o, n = int(rec["rows_offset"][h]), int(rec["columns"][h])
@@ -408,11 +430,16 @@ class Session:
         return c["seed"], kc, pos
 
     def set_queries(self, seqs: Sequence, names: Sequence, width: int = 75, dna: bool = False,
-                    chunk_mb: int = 0) -> None:
+                    chunk_mb: int = 0, tile_step: int | None = None, max_len: int = 0) -> None:
         """Replaces the query set by these records (str or bytes letters and
         names): what `ghostm qry -l width [-t d] -L chunk_mb` would format from
         them, coded on the device (GhostmSessionSetQueries). The last run's
-        results are dropped."""
+        results are dropped. With tile_step the set is tiled
+        (GhostmSessionSetQueriesTiled): every record is cut at max_len (letters,
+        nt for DNA; 0: no cut) and enters as overlapping tile records of the
+        width, tile_step letters apart; query_tiles() gives the table."""
+        if tile_step is None and max_len:
+            raise ValueError("set_queries: max_len cuts a tiled set only (give tile_step)")
         if len(seqs) != len(names):
             raise ValueError("set_queries: one name per sequence")
         as_bytes = lambda x: x.encode() if isinstance(x, str) else bytes(x)  # noqa: E731
@@ -428,24 +455,49 @@ class Session:
         raw = np.frombuffer(b"".join(bseqs) or b"\0", dtype=np.uint8)
         raw_len = int(lengths.sum(dtype=np.uint64))
         name_buf = b"".join(x + b"\n" for x in bnames)
-        rc = native.load().GhostmSessionSetQueries(
-            self._h, raw.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), raw_len,
-            offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
-            lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), name_buf, len(name_buf), n, int(width),
-            int(bool(dna)), int(chunk_mb))
+        args = (self._h, raw.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), raw_len,
+                offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+                lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), name_buf, len(name_buf), n, int(width),
+                int(bool(dna)), int(chunk_mb))
+        if tile_step is None:
+            rc = native.load().GhostmSessionSetQueries(*args)
+        else:
+            rc = native.load().GhostmSessionSetQueriesTiled(*args, int(max_len), int(tile_step))
         if rc != 0:
             raise GhostmError(native.last_error())
 
-    def set_queries_fasta(self, path: str, width: int = 75, dna: bool = False, chunk_mb: int = 0) -> int:
+    def set_queries_fasta(self, path: str, width: int = 75, dna: bool = False, chunk_mb: int = 0,
+                          tile_step: int | None = None, max_len: int = 0) -> int:
         """set_queries from a FASTA file, read as `ghostm qry` reads it
         (GhostmSessionSetQueriesFasta). Returns the number of output records
-        over the width (qry's warnings)."""
+        over the width (qry's warnings). With tile_step the set is tiled
+        (GhostmSessionSetQueriesFastaTiled) and the count is of the records
+        max_len cut (six per DNA read)."""
+        if tile_step is None and max_len:
+            raise ValueError("set_queries_fasta: max_len cuts a tiled set only (give tile_step)")
         cut = ctypes.c_uint64(0)
-        rc = native.load().GhostmSessionSetQueriesFasta(self._h, str(path).encode(), int(width), int(bool(dna)),
-                                                        int(chunk_mb), ctypes.byref(cut))
+        if tile_step is None:
+            rc = native.load().GhostmSessionSetQueriesFasta(self._h, str(path).encode(), int(width), int(bool(dna)),
+                                                            int(chunk_mb), ctypes.byref(cut))
+        else:
+            rc = native.load().GhostmSessionSetQueriesFastaTiled(self._h, str(path).encode(), int(width),
+                                                                 int(bool(dna)), int(chunk_mb), int(max_len),
+                                                                 int(tile_step), ctypes.byref(cut))
         if rc != 0:
             raise GhostmError(native.last_error())
         return int(cut.value)
+
+    def query_tiles(self) -> np.ndarray:
+        """The tile table of a tiled query set (GhostmSessionQueryTiles): one
+        QUERY_TILE_DTYPE entry per query record over the chunks in order, the
+        indexing of query_lengths() and of hits_rows()'s query_record; empty on
+        an untiled set."""
+        lib = native.load()
+        n = lib.GhostmSessionQueryTiles(self._h, None, 0)
+        out = np.zeros(n, dtype=QUERY_TILE_DTYPE)
+        if n:
+            lib.GhostmSessionQueryTiles(self._h, out.ctypes.data_as(ctypes.POINTER(native.GhostmQueryTile)), n)
+        return out
 
     def set_output(self, path: str) -> None:
         """The -o path of later run(to_file=True) and write() calls."""

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "db_set.h"
 #include "query_set.h"
+#include "query_tiles.h"
 #include "worker_pool.h"
 
 namespace ghostm {
@@ -1717,8 +1718,9 @@ void Session::FormatPathTabular() {
     p = PutU32(p, length); *p++ = '\t';
     p = PutU32(p, count[1]); *p++ = '\t';
     p = PutU32(p, gap_runs); *p++ = '\t';
-    p = PutU32(p, x.q_start + 1); *p++ = '\t';
-    p = PutU32(p, x.q_end + 1); *p++ = '\t';
+    const uint32_t q0 = TileOffset(hit) + 1;  // a tiled set prints read coordinates
+    p = PutU32(p, x.q_start + q0); *p++ = '\t';
+    p = PutU32(p, x.q_end + q0); *p++ = '\t';
     p = PutU32(p, x.s_start + 1); *p++ = '\t';
     p = PutU32(p, x.s_end + 1); *p++ = '\t';
     out.append(num, (size_t)(p - num));
@@ -1997,12 +1999,13 @@ void Session::FormatRows() {
       out.push_back('\n');
     } else {
       out.append("\nQuery\t");
-      end = PutU32(num, p.q_start + 1);
+      const uint32_t q0 = TileOffset(hit) + 1;  // a tiled set prints read coordinates
+      end = PutU32(num, p.q_start + q0);
       out.append(num, (size_t)(end - num));
       out.push_back('\t');
       out.append(q, n);
       out.push_back('\t');
-      end = PutU32(num, p.q_end + 1);
+      end = PutU32(num, p.q_end + q0);
       out.append(num, (size_t)(end - num));
       out.append("\n\t\t");
       out.append(q + n, n);
@@ -2036,8 +2039,9 @@ void Session::FormatTabular() {
     *p++ = '\t';
     p = PutU32(p, x.mismatches); *p++ = '\t';
     p = PutU32(p, x.gap_opens); *p++ = '\t';
-    p = PutU32(p, x.q_start + 1); *p++ = '\t';
-    p = PutU32(p, x.q_end + 1); *p++ = '\t';
+    const uint32_t q0 = TileOffset(hit) + 1;  // a tiled set prints read coordinates
+    p = PutU32(p, x.q_start + q0); *p++ = '\t';
+    p = PutU32(p, x.q_end + q0); *p++ = '\t';
     out.append(num, (size_t)(p - num));
     out.append(in, tab[4] + 1, tab[0] - tab[4] - 1);
     out.push_back('\n');
@@ -2455,6 +2459,7 @@ void Session::DropQueries() {
   // the old chunks' device blocks go back to the pool
   for (QueryData &q : queries_) dev.Free(q.dev);
   queries_.clear();
+  tile_table_.clear();  // a tiled set's table goes with the set
   shard_begin_ = 0;
   shard_end_ = UINT64_MAX;
   format_seconds_ = 0;
@@ -2607,6 +2612,147 @@ void Session::SetQueriesFasta(const std::string &path, uint32_t width, bool dna,
     throw;
   }
   FinishQuerySet();
+}
+
+// ------------------------------------------------------------------ tiled query sets
+// A set whose records may be longer than the width: every record enters as
+// overlapping tile records under its name (query_tiles.h), so the name group
+// merges a read's tiles as it merges a DNA read's frames and the search behind
+// the formatter runs unchanged. The whole set is planned on the host (chunk
+// cuts over the kept letters, tile counts, the chunks' row counts) before the
+// old set is dropped, so every refusal leaves the session as it was.
+void Session::AddQueryChunkTiled(const QueryRecordView *recs, uint32_t n, uint32_t record_base,
+                                 const TiledRule &rule) {
+  DeviceModule &dev = DeviceModule::Get();
+  const double t0 = NowSeconds();
+  std::vector<uint64_t> off(n);
+  std::vector<uint32_t> len(n), first(n + 1);
+  std::vector<GhostmQueryTile> table;
+  uint64_t total = 0;
+  for (uint32_t r = 0; r < n; ++r) {
+    off[r] = total;
+    len[r] = recs[r].len;
+    total += len[r];
+    first[r] = (uint32_t)table.size();
+    AppendTiles(record_base + r, len[r], rule.width, rule.dna, rule.step, &table);
+  }
+  first[n] = (uint32_t)table.size();
+  CheckTiledChunk(table.size(), rule.width);
+  std::vector<uint8_t> raw(total);
+  ParallelFor(n, std::max(1u, std::min(threads_, 8u)), [&](size_t b, size_t e, unsigned) {
+    for (size_t r = b; r < e; ++r)
+      if (len[r]) std::memcpy(raw.data() + off[r], recs[r].seq, len[r]);
+  });
+  QueryData q;
+  q.chunk.id = (uint32_t)queries_.size();
+  q.chunk.nseq = first[n];
+  q.chunk.L = rule.width;
+  for (uint32_t r = 0; r < n; ++r)
+    for (uint32_t k = first[r]; k < first[r + 1]; ++k) q.chunk.names.push_back(recs[r].name);
+  PrepareQueryChunk(&q, false);
+  q.qlen.assign(q.chunk.nseq, 1);
+  double seconds = 0;
+  q.dev = dev.FormatQueryTiled(raw.data(), total, off.data(), len.data(), first.data(), n, rule.width, rule.dna,
+                               rule.step, q.qlen.data(), &seconds);
+  struct FreeUnadopted {
+    QueryData *q;
+    ~FreeUnadopted() {
+      if (q) DeviceModule::Get().Free(q->dev);
+    }
+  } guard{&q};
+  dev.SetQueryGroups(q.dev, q.group_first.data(), q.group_last.data(), (uint32_t)q.group_first.size());
+  q.global_base = queries_.empty() ? 0 : queries_.back().global_base + queries_.back().chunk.nseq;
+  if ((uint64_t)q.global_base + q.chunk.nseq > UINT32_MAX) throw Error("set queries: over 4 G tile records");
+  tile_table_.insert(tile_table_.end(), table.begin(), table.end());
+  format_seconds_ += seconds;
+  ++format_launches_;
+  queries_.push_back(std::move(q));
+  guard.q = nullptr;
+  load_seconds_ += NowSeconds() - t0 - seconds;
+}
+
+void Session::SetTiledRecords(const QueryRecordView *recs, uint32_t n, const TiledRule &rule) {
+  if (shard_world_ > 1) throw Error("a shard session's query set cannot be replaced");
+  CheckTileStep(rule.width, rule.step);
+  std::vector<uint32_t> len(n);
+  for (uint32_t r = 0; r < n; ++r) len[r] = recs[r].len;
+  std::vector<uint64_t> cuts;
+  const bool whole = QueryChunkCuts(len.data(), n, rule.max_concat, &cuts);
+  if (!whole || cuts.back() != n) throw Error("set queries: too small max length.");
+  uint64_t all = 0;
+  for (size_t c = 0; c + 1 < cuts.size(); ++c) {
+    uint64_t rows = 0;
+    for (uint64_t r = cuts[c]; r < cuts[c + 1]; ++r)
+      rows += AppendTiles((uint32_t)r, len[r], rule.width, rule.dna, rule.step, nullptr);
+    CheckTiledChunk(rows, rule.width);
+    all += rows;
+  }
+  if (all > UINT32_MAX) throw Error("set queries: over 4 G tile records");
+  DropQueries();
+  try {
+    for (size_t c = 0; c + 1 < cuts.size(); ++c)
+      AddQueryChunkTiled(recs + cuts[c], (uint32_t)(cuts[c + 1] - cuts[c]), (uint32_t)cuts[c], rule);
+  } catch (...) {
+    DropQueries();  // no half-made set
+    throw;
+  }
+  FinishQuerySet();
+}
+
+void Session::SetQueriesTiled(const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets, const uint32_t *lengths,
+                              const char *names, uint64_t names_len, uint32_t n, uint32_t width, bool dna,
+                              uint32_t chunk_mb, uint32_t max_len, uint32_t step, uint64_t *cut_records) {
+  if (n && (!offsets || !lengths || !names || (!raw && raw_len))) throw Error("set queries: null argument");
+  if (cut_records) *cut_records = 0;
+  std::vector<QueryRecordView> recs(n);
+  uint64_t at = 0, cut = 0;
+  for (uint32_t r = 0; r < n; ++r) {
+    if (offsets[r] > raw_len || lengths[r] > raw_len - offsets[r])
+      throw Error("set queries: record " + std::to_string(r) + " outside the letter buffer");
+    const char *nl = at < names_len ? static_cast<const char *>(std::memchr(names + at, '\n', names_len - at)) : nullptr;
+    if (!nl) throw Error("set queries: fewer than " + std::to_string(n) + " newline-terminated names");
+    const uint32_t kept = TileKept(lengths[r], max_len);
+    cut += kept < lengths[r] ? (dna ? 6 : 1) : 0;
+    recs[r] = QueryRecordView{reinterpret_cast<const char *>(raw) + offsets[r], kept,
+                              std::string_view(names + at, (size_t)(nl - (names + at)))};
+    at = (uint64_t)(nl - names) + 1;
+  }
+  const WidthRule rule = QuerySetRules(width, dna, chunk_mb, nullptr);
+  SetTiledRecords(recs.data(), n, TiledRule{rule.width, rule.max_concat, step, dna});
+  if (cut_records) *cut_records = cut;
+}
+
+void Session::SetQueriesFastaTiled(const std::string &path, uint32_t width, bool dna, uint32_t chunk_mb,
+                                   uint32_t max_len, uint32_t step, uint64_t *cut_records, bool *capped) {
+  const WidthRule rule = QuerySetRules(width, dna, chunk_mb, capped);
+  if (cut_records) *cut_records = 0;
+  if (shard_world_ > 1) throw Error("a shard session's query set cannot be replaced");
+  CheckTileStep(rule.width, step);
+  {
+    std::ifstream probe(path.c_str());
+    if (!probe) throw Error("set queries: cannot open " + path);
+  }
+  const double t0 = NowSeconds();
+  std::vector<FastaRecord> recs;
+  {
+    FastaReader reader(path);
+    FastaRecord r;
+    while (reader.Next(&r)) recs.push_back(r);
+  }
+  if (recs.size() > UINT32_MAX) throw Error("set queries: over 4 G records");
+  std::vector<QueryRecordView> views(recs.size());
+  uint64_t cut = 0;
+  for (size_t r = 0; r < recs.size(); ++r) {
+    if (recs[r].seq.size() > UINT32_MAX) throw Error("set queries: a record of over 4 G letters");
+    const uint32_t kept = TileKept((uint32_t)recs[r].seq.size(), max_len);
+    cut += kept < recs[r].seq.size() ? (dna ? 6 : 1) : 0;
+    views[r] = QueryRecordView{recs[r].seq.data(), kept, recs[r].name};
+  }
+  const double read = NowSeconds() - t0;
+  SetTiledRecords(views.data(), (uint32_t)views.size(), TiledRule{rule.width, rule.max_concat, step, dna});
+  read_seconds_ = read;
+  QueryStats();
+  if (cut_records) *cut_records = cut;
 }
 
 // ------------------------------------------------------------------ database sets

@@ -180,6 +180,23 @@ class Session {
   // the limit (qry's other warning).
   void SetQueriesFasta(const std::string &path, uint32_t width, bool dna, uint32_t chunk_mb, uint64_t *cut_records,
                        std::vector<std::string> *cut_names = nullptr, bool *capped = nullptr);
+  // SetQueries with tiles (query_tiles.h): every record is cut at max_len
+  // (letters, nt for DNA; 0: no cut) and then enters as overlapping tile
+  // records of the width under its name, made on the device by
+  // DeviceModule::FormatQueryTiled. The chunk cuts are over the kept letters.
+  // Everything is planned before the old set is dropped: besides SetQueries'
+  // refusals, step 0, step over the width, a record over kMaxTileRecords and a
+  // chunk that would wrap a 32-bit field leave the session as it was.
+  // cut_records (may be null): the records max_len cut (x 6 for DNA reads).
+  void SetQueriesTiled(const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets, const uint32_t *lengths,
+                       const char *names, uint64_t names_len, uint32_t n, uint32_t width, bool dna,
+                       uint32_t chunk_mb, uint32_t max_len, uint32_t step, uint64_t *cut_records = nullptr);
+  // ... read from a FASTA file, the whole file before the first chunk is made.
+  void SetQueriesFastaTiled(const std::string &path, uint32_t width, bool dna, uint32_t chunk_mb, uint32_t max_len,
+                            uint32_t step, uint64_t *cut_records, bool *capped = nullptr);
+  // The tile table of a tiled set, one entry per query record over the chunks
+  // in order; empty for any other set. Forgotten with the set (DropQueries).
+  const std::vector<GhostmQueryTile> &QueryTiles() const { return tile_table_; }
   // the -o path of later Run(true) and WriteOutputFile calls
   void SetOutputFile(const std::string &path);
   // every record's WriteOutput length over the chunks in order, and one
@@ -307,6 +324,20 @@ class Session {
   // the next chunk of a set (qry's files for these records, resident)
   void AddQueryChunk(const QueryRecordView *recs, uint32_t n, uint32_t width, bool dna, uint64_t *cut_records,
                      std::vector<std::string> *cut_names);
+  // the tiled set of these records (len: already cut at max_len), planned
+  // whole before the old set is dropped
+  struct TiledRule {
+    uint32_t width, max_concat, step;
+    bool dna;
+  };
+  void SetTiledRecords(const QueryRecordView *recs, uint32_t n, const TiledRule &rule);
+  // its next chunk; record_base: recs[0]'s index in the set
+  void AddQueryChunkTiled(const QueryRecordView *recs, uint32_t n, uint32_t record_base, const TiledRule &rule);
+  // the offset a detail line adds to hit's query coordinates: its tile's, 0 on an untiled set
+  uint32_t TileOffset(size_t hit) const {
+    return tile_table_.empty() ? 0u
+                               : tile_table_[queries_[hit_source_[hit].qi].global_base + hit_source_[hit].query].offset;
+  }
   void FinishQuerySet();
   void QueryStats();  // the query-set fields of stats_
   void QueryLengths(std::vector<QueryData *> chunks);
@@ -384,6 +415,7 @@ class Session {
   uint64_t format_launches_ = 0, query_sets_ = 0;
   double read_seconds_ = 0, load_seconds_ = 0;  // host: FASTA reading; packing, upload and read-back
   std::vector<QueryData> queries_;
+  std::vector<GhostmQueryTile> tile_table_;  // a tiled set's table, by global query record; else empty
   std::vector<DbData> dbs_;
   uint32_t db_sum_u32_ = 0;           // DBReader::GetSumDbLength() truncates to u32
   uint64_t merge_epoch_ = 0;

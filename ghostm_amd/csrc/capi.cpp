@@ -14,6 +14,7 @@
 #include "common.h"
 #include "db_set.h"
 #include "query_set.h"
+#include "query_tiles.h"
 
 using namespace ghostm;
 
@@ -110,6 +111,70 @@ int64_t GhostmQueryChunkCuts(const uint32_t lengths[], uint64_t n, uint32_t chun
     if (cuts) std::copy(c.begin(), c.begin() + (long)std::min<uint64_t>(cap, c.size()), cuts);
     if (!whole) throw Error("chunk cuts: too small max length.");
     return (int64_t)c.size() - 1;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return -1;
+  }
+}
+
+int GhostmSessionSetQueriesTiled(void *s, const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets,
+                                 const uint32_t *lengths, const char *names, uint64_t names_len, uint32_t n,
+                                 uint32_t width, int dna, uint32_t chunk_mb, uint32_t max_len, uint32_t step) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetQueriesTiled(raw, raw_len, offsets, lengths, names, names_len, n, width, dna != 0,
+                                               chunk_mb, max_len, step);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+int GhostmSessionSetQueriesFastaTiled(void *s, const char *path, uint32_t width, int dna, uint32_t chunk_mb,
+                                      uint32_t max_len, uint32_t step, uint64_t *cut_records) {
+  try {
+    if (!s) throw Error("null session");
+    if (!path) throw Error("set queries: null path");
+    static_cast<Session *>(s)->SetQueriesFastaTiled(path, width, dna != 0, chunk_mb, max_len, step, cut_records);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionQueryTiles(void *s, GhostmQueryTile *tiles, size_t cap) {
+  if (!s) return 0;
+  const std::vector<GhostmQueryTile> &v = static_cast<Session *>(s)->QueryTiles();
+  if (!tiles) return v.size();
+  const size_t n = std::min(cap, v.size());
+  if (n) std::memcpy(tiles, v.data(), n * sizeof(GhostmQueryTile));
+  return n;
+}
+
+int64_t GhostmQueryTilePlan(const uint32_t lengths[], uint64_t n, uint32_t width, int dna, uint32_t max_len,
+                            uint32_t step, GhostmQueryTile tiles[], uint64_t cap, uint64_t *cut_records) {
+  try {
+    if (n && !lengths) throw Error("tile plan: null argument");
+    if (n > UINT32_MAX) throw Error("tile plan: over 4 G records");
+    bool capped = false;
+    const uint32_t W = QueryRecordWidth(width, dna != 0, &capped);
+    CheckTileStep(W, step);
+    uint64_t rows = 0, cut = 0;
+    std::vector<GhostmQueryTile> one;
+    for (uint64_t r = 0; r < n; ++r) {
+      const uint32_t kept = TileKept(lengths[r], max_len);
+      cut += kept < lengths[r] ? (dna ? 6 : 1) : 0;
+      one.clear();
+      AppendTiles((uint32_t)r, kept, W, dna != 0, step, &one);
+      for (const GhostmQueryTile &t : one) {
+        if (tiles && rows < cap) tiles[rows] = t;
+        ++rows;
+      }
+    }
+    if (cut_records) *cut_records = cut;
+    return (int64_t)rows;
   } catch (std::exception &e) {
     SetLastErrorMessage(e.what());
     return -1;
@@ -467,16 +532,24 @@ int GhostmAlignMain(int argc, char **argv) {
 // pair without the formatted files. Usage errors return 1 before any device call.
 int GhostmSearchMain(int argc, char **argv) {
   std::vector<char *> aln_argv{argv[0]};
-  uint32_t width = 75, chunk_mb = 0;
-  bool dna = false, have_d = false;
+  uint32_t width = 75, chunk_mb = 0, tile_step = 0, max_len = 0;
+  bool dna = false, have_d = false, tiled = false, have_x = false;
   std::string db_fasta;
   uint32_t db_k = 4, db_mb = 0;
   optind = 1;
   opterr = 1;
   int c;
-  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c and -f, -k, -m
-  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:")) >= 0) {
+  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:")) >= 0) {
     switch (c) {
+      case 'T':  // reads longer than the width as overlapping tiles, this many letters apart
+        tiled = true;
+        tile_step = (uint32_t)atoi(optarg);
+        break;
+      case 'X':  // with -T: every read cut at this many letters (nt for DNA) first
+        have_x = true;
+        max_len = (uint32_t)atoi(optarg);
+        break;
       case 'f': db_fasta = optarg; break;
       case 'k': db_k = (uint32_t)atoi(optarg); break;
       case 'm': db_mb = (uint32_t)atoi(optarg); break;
@@ -505,6 +578,7 @@ int GhostmSearchMain(int argc, char **argv) {
   std::vector<std::string> pos(argv + optind, argv + argc);
   if (pos.empty() || pos.size() % 2) return 1;
   if (have_d == !db_fasta.empty()) return 1;  // -d or -f, not both
+  if (have_x && !tiled) return 1;             // -X cuts a tiled set only
   try {
     aln_argv.push_back(nullptr);
     AlignerOptions opt = ParseAlignerOptions((int)aln_argv.size() - 1, aln_argv.data());
@@ -517,7 +591,8 @@ int GhostmSearchMain(int argc, char **argv) {
         session.SetOutputFile(pos[k + 1]);
         std::vector<std::string> cut;
         bool capped = false;
-        session.SetQueriesFasta(pos[k], width, dna, chunk_mb, nullptr, &cut, &capped);
+        if (tiled) session.SetQueriesFastaTiled(pos[k], width, dna, chunk_mb, max_len, tile_step, nullptr, &capped);
+        else session.SetQueriesFasta(pos[k], width, dna, chunk_mb, nullptr, &cut, &capped);
         if (capped)
           std::cerr << "Warring: over upper limit of query length. Max is " << kMaxQueryLength * (dna ? 3 : 1) << "."
                     << std::endl;

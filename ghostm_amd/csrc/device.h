@@ -140,6 +140,13 @@ class DeviceModule {
   // the kernel's device time.
   DevQuery *FormatQuery(const uint8_t *raw, uint64_t raw_len, const uint64_t *off, const uint32_t *len, uint32_t n,
                         uint32_t width, uint32_t dna_len, uint32_t *qlen, double *seconds);
+  // FormatQuery for a tiled set (query_tiles.h): record r becomes the output
+  // records first[r] .. first[r + 1] (first holds n + 1 entries, first[n] =
+  // nout) by the tiled kernels of qformat.hip; len[r] is the record's kept
+  // letters (nt for DNA, each read translated at its own length).
+  DevQuery *FormatQueryTiled(const uint8_t *raw, uint64_t raw_len, const uint64_t *off, const uint32_t *len,
+                             const uint32_t *first, uint32_t n, uint32_t width, bool dna, uint32_t step,
+                             uint32_t *qlen, double *seconds);
   // A resident chunk's coded records (nseq * L bytes) back on the host.
   size_t QueryBytes(const DevQuery *q) const;
   void DownloadQuery(const DevQuery *q, uint8_t *dst);

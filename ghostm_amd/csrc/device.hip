@@ -22,6 +22,7 @@
 #include "path_rows.h"
 #include "pileup_plan.h"
 #include "qformat.h"
+#include "query_tiles.h"
 #include "score_tasks.h"
 
 namespace ghostm {
@@ -318,7 +319,7 @@ struct DeviceModule::Impl {
   bool matrix_set = false;
   // FormatQuery: the chunk's letters, offsets and lengths, the records'
   // lengths, the kernels' tables; the kernel's events
-  DevBuf qf_raw, qf_off, qf_len, qf_qlen, qf_tab;
+  DevBuf qf_raw, qf_off, qf_len, qf_qlen, qf_tab, qf_first;  // qf_first: FormatQueryTiled's first output rows
   hipEvent_t ev_q0 = nullptr, ev_q1 = nullptr;
   // FormatDb: the chunk's packed letters, the index build's (key, position)
   // pairs with their ping-pong copies and its scan arrays; the kernels' events
@@ -613,6 +614,61 @@ DevQuery *DeviceModule::FormatQuery(const uint8_t *raw, uint64_t raw_len, const 
   HIP_CHECK(hipEventRecord(I.ev_q0, S(stream_)));
   LaunchQueryFormat(stream_, I.qf_raw.as<uint8_t>(), I.qf_off.as<uint64_t>(), I.qf_len.as<uint32_t>(), n, width,
                     dna_len, q->seq.as<uint8_t>(), I.qf_qlen.as<uint32_t>(), I.qf_tab.p);
+  HIP_CHECK(hipEventRecord(I.ev_q1, S(stream_)));
+  HIP_CHECK(hipMemcpyAsync(qlen, I.qf_qlen.p, (size_t)nout * 4, hipMemcpyDeviceToHost, S(stream_)));
+  HIP_CHECK(hipStreamSynchronize(S(stream_)));
+  if (seconds) {
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, I.ev_q0, I.ev_q1));
+    *seconds = ms * 1e-3;
+  }
+  return q.release();
+}
+
+DevQuery *DeviceModule::FormatQueryTiled(const uint8_t *raw, uint64_t raw_len, const uint64_t *off,
+                                         const uint32_t *len, const uint32_t *first, uint32_t n, uint32_t width,
+                                         bool dna, uint32_t step, uint32_t *qlen, double *seconds) {
+  Use();
+  if (!impl_) throw Error("device not bound");
+  if (seconds) *seconds = 0;
+  if (width == 0 || width > kMaxQueryLength)
+    throw Error("query record width " + std::to_string(width) + " outside 1..127");
+  if (step == 0 || step > width) throw Error("tile step " + std::to_string(step) + " outside 1.." + std::to_string(width));
+  if (n == 0) throw Error("query chunk of 0 records");
+  const uint64_t nout = first[n];
+  // every record's output rows lie inside the chunk: the kernels write nowhere else
+  for (uint32_t r = 0; r < n; ++r) {
+    if (off[r] > raw_len || len[r] > raw_len - off[r]) throw Error("query record outside the letter buffer");
+    const uint32_t m = dna ? len[r] / 3 : len[r];
+    const uint64_t rows = (uint64_t)TileCount(m, width, step) * (dna ? 6 : 1);
+    if (first[r] > first[r + 1] || first[r + 1] - first[r] != rows) throw Error("tiled query chunk: rows disagree with the plan");
+  }
+  if (first[0] != 0 || nout == 0) throw Error("tiled query chunk: rows disagree with the plan");
+  CheckTiledChunk(nout, width);
+  Impl &I = *impl_;
+  if (!I.qf_tab.p) {
+    std::vector<uint8_t> tab(QueryFormatTableBytes());
+    QueryFormatTables(tab.data());
+    I.qf_tab.Reserve(tab.size());
+    HIP_CHECK(hipMemcpy(I.qf_tab.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+  }
+  std::unique_ptr<DevQuery, std::function<void(DevQuery *)>> q(new DevQuery(), [this](DevQuery *p) { Free(p); });
+  q->nseq = (uint32_t)nout;
+  q->L = width;
+  q->seq.Reserve((size_t)nout * width + 16);
+  I.qf_raw.Reserve(raw_len);
+  I.qf_off.Reserve((size_t)n * 8);
+  I.qf_len.Reserve((size_t)n * 4);
+  I.qf_first.Reserve((size_t)n * 4);
+  I.qf_qlen.Reserve((size_t)nout * 4);
+  StagedUpload(I.qf_raw.p, raw, raw_len);
+  StagedUpload(I.qf_off.p, off, (size_t)n * 8);
+  StagedUpload(I.qf_len.p, len, (size_t)n * 4);
+  StagedUpload(I.qf_first.p, first, (size_t)n * 4);
+  HIP_CHECK(hipEventRecord(I.ev_q0, S(stream_)));
+  LaunchQueryFormatTiled(stream_, I.qf_raw.as<uint8_t>(), I.qf_off.as<uint64_t>(), I.qf_len.as<uint32_t>(),
+                         I.qf_first.as<uint32_t>(), n, width, dna, step, q->seq.as<uint8_t>(), I.qf_qlen.as<uint32_t>(),
+                         I.qf_tab.p);
   HIP_CHECK(hipEventRecord(I.ev_q1, S(stream_)));
   HIP_CHECK(hipMemcpyAsync(qlen, I.qf_qlen.p, (size_t)nout * 4, hipMemcpyDeviceToHost, S(stream_)));
   HIP_CHECK(hipStreamSynchronize(S(stream_)));

@@ -34,6 +34,8 @@ static int Usage() {
             << "       (-d database | -f db.fasta [-k kSize] [-m chunkSizeMB]) q1.fasta out1 [q2.fasta out2 ...]\n"
             << "       (qry + aln per pair on one resident database; -q -w -c as qry's -t -l -L;\n"
             << "        -f: the database formatted on the GPU from FASTA, -k -m as db's -k -l)\n"
+            << "       [-T tileStep [-X maxReadLength]]: reads longer than the record width searched as\n"
+            << "        overlapping tiles tileStep letters apart, each read first cut at maxReadLength\n"
             << "synth: ghostm synth -d db.fasta -q queries.fasta [-n nq] [-N dbResidues] [-s seed]\n";
   return 1;
 }

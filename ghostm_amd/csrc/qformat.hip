@@ -21,6 +21,11 @@
 // record's QueryResidues from a ballot of the non-X lanes per 64 codes, so only
 // the 4-byte lengths come back; GhostmFormatQueriesGpu (qry -D) runs the same
 // bodies without it.
+//   k_qry_protein_tiled, k_qry_frames_tiled  the tiled forms
+//                  (DeviceModule::FormatQueryTiled, query_tiles.h): a record
+//                  or frame longer than the width becomes overlapping tile
+//                  records; the frame is still translated once, each group of
+//                  64 letters stored into every tile that covers it
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,6 +35,7 @@
 #include "../../include/ghostm_hip.h"
 #include "common.h"
 #include "formats.h"
+#include "lds_poison.h"
 #include "qformat.h"
 
 namespace ghostm {
@@ -150,6 +156,128 @@ template <bool QLEN> __global__ __launch_bounds__(kQfBlock) void k_qry_frames(Qf
   }
 }
 
+// ---------------------------------------------------------------- tiled forms
+// A source longer than the width becomes overlapping tiles of `width` letters
+// (query_tiles.h: the plan; TileCount / TileStart restated here). Output
+// record first[r] is record r's first; always with the records' QueryResidues.
+struct QfTileArgs {
+  const uint8_t *raw;
+  const unsigned long long *off;
+  const uint32_t *len;    // kept letters (nt for DNA): cut at max_len by the host
+  const uint32_t *first;  // first output record of every source record
+  uint32_t nrec, width, step;
+  uint8_t *out;
+  const QfTables *tab;
+  uint32_t *qlen;
+};
+
+__device__ __forceinline__ uint32_t QfTileCount(uint32_t m, uint32_t W, uint32_t step) {
+  return m <= W ? 1u : 1u + (m - W + step - 1) / step;  // no wrap: the host refused a record over 1024 tiles
+}
+
+__device__ __forceinline__ uint32_t QfTileStart(uint32_t t, uint32_t tiles, uint32_t m, uint32_t W, uint32_t step) {
+  return t + 1 < tiles ? t * step : (m > W ? m - W : 0u);
+}
+
+// One wave per record (grid-stride), its tiles in turn: tile t is what
+// k_qry_protein makes of letters [start, start + width), X past the record's
+// end. Overlapping tiles read their letters again (cache hits); the stores
+// are the tile records' contiguous bytes.
+__global__ __launch_bounds__(kQfBlock) void k_qry_protein_tiled(QfTileArgs a) {
+  __shared__ uint8_t s_code[256];
+  GHOSTM_POISON_LDS();
+  s_code[threadIdx.x] = a.tab->protein[threadIdx.x];
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63, W = a.width;
+  for (uint32_t r = blockIdx.x * kQfWaves + (threadIdx.x >> 6); r < a.nrec; r += gridDim.x * kQfWaves) {
+    const uint32_t m = a.len[r], tiles = QfTileCount(m, W, a.step);
+    const uint8_t *src = a.raw + a.off[r];
+    for (uint32_t t = 0; t < tiles; ++t) {
+      const uint32_t start = QfTileStart(t, tiles, m, W, a.step);
+      uint8_t *dst = a.out + (uint64_t)(a.first[r] + t) * W;
+      uint32_t last = 0;
+      for (uint32_t k0 = 0; k0 < W; k0 += 64) {
+        const uint32_t k = k0 + lane;
+        const uint8_t code = (k < W && start + k < m) ? s_code[src[start + k]] : (uint8_t)kBaseX;
+        if (k < W) dst[k] = code;
+        last = LastResidue(last, __ballot(code != kBaseX), k0);
+      }
+      if (lane == 0) a.qlen[a.first[r] + t] = max(last, 1u);
+    }
+  }
+}
+
+// One wave per (read, frame) (grid-stride): the frame is translated once over
+// its whole length (n / 3 letters of the read's own kept length n), 64 letters
+// at a time as k_qry_frames does, the stop/ATG state carried along the whole
+// frame. Each group of 64 letters is then stored into every tile that covers
+// it: output record first[r] + 6 t + f, byte (letter - start(t)). A tile's
+// QueryResidues is the group ballot masked to the tile's range; groups come in
+// increasing order, so lane 0 writes the length at the tile's first group (1
+// when nothing is set yet) and again whenever a later group has a non-X letter
+// in the tile.
+__global__ __launch_bounds__(kQfBlock) void k_qry_frames_tiled(QfTileArgs a) {
+  __shared__ uint8_t s_base[256];
+  __shared__ uint8_t s_codon[128];
+  GHOSTM_POISON_LDS();
+  s_base[threadIdx.x] = a.tab->dna[threadIdx.x];
+  if (threadIdx.x < 128) s_codon[threadIdx.x] = a.tab->codon[threadIdx.x];
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63, W = a.width, step = a.step;
+  const unsigned long long upto = ~0ull >> (63 - lane);  // lanes 0..lane
+  const uint64_t work = (uint64_t)a.nrec * 6;
+  for (uint64_t w = blockIdx.x * kQfWaves + (threadIdx.x >> 6); w < work; w += (uint64_t)gridDim.x * kQfWaves) {
+    const uint32_t r = (uint32_t)(w / 6), f = (uint32_t)(w - (uint64_t)r * 6);
+    const uint32_t s = f / 3, o = f - s * 3;
+    const uint32_t n = a.len[r], m = n / 3, tiles = QfTileCount(m, W, step);
+    const uint32_t last_start = m > W ? m - W : 0u;
+    const uint8_t *dna = a.raw + a.off[r];
+    const uint64_t rec0 = (uint64_t)a.first[r] + f;  // tile t: record rec0 + 6 t
+    auto base = [&](uint32_t j) -> uint32_t {  // base at strand position j < n
+      uint32_t b = s_base[dna[s ? n - 1 - j : j]];
+      if (s && b <= 3) b = (~b) & 3u;
+      return b;
+    };
+    // the group's letters into tile t (start st): bytes and length
+    auto put_tile = [&](uint32_t t, uint32_t st, uint32_t t0, uint32_t letter, uint32_t put) {
+      const uint32_t rel = letter - st;  // wraps below the tile's start
+      const bool in = letter < m && letter >= st && rel < W;
+      if (in) a.out[(rec0 + 6ull * t) * W + rel] = (uint8_t)put;
+      const unsigned long long nonx = __ballot(in && put != kBaseX);
+      const bool opens = st >= t0;  // the first group that touches this tile
+      if (lane == 0 && (opens || nonx))
+        a.qlen[rec0 + 6ull * t] = nonx ? t0 - st + 64u - (uint32_t)__clzll(nonx) : 1u;
+    };
+    uint32_t carry = 0;  // stop state entering this group of 64 letters
+    for (uint32_t t0 = 0; t0 < m; t0 += 64) {
+      const uint32_t t = t0 + lane, k = o + 2 + 3 * t;
+      uint32_t code = 24, ev = 0;  // '*' padding past the last whole codon
+      if (t < m && k < n) {
+        const uint32_t b0 = base(k - 2), b1 = base(k - 1), b2 = base(k);
+        const uint32_t codon = (b0 > 3 || b1 > 3 || b2 > 3) ? 64u : (b0 << 4 | b1 << 2 | b2);
+        code = s_codon[codon];
+        ev = codon == 14 ? 1u : (codon == 48 || codon == 50 || codon == 56) ? 2u : 0u;  // ATG / TAA TAG TGA
+      }
+      const unsigned long long evm = __ballot(ev != 0), setm = __ballot(ev == 2);
+      const unsigned long long mine = evm & upto;
+      const uint32_t stop = mine ? (uint32_t)(setm >> (63 - __clzll(mine))) & 1u : carry;
+      const uint32_t put = stop ? 24u : code;
+      carry = evm ? (uint32_t)(setm >> (63 - __clzll(evm))) & 1u : carry;
+      // the regular tiles (start tt * step) with start + W > t0 and start < t0 + 64, then the flush-right one
+      const uint32_t lo = t0 >= W ? (t0 - W) / step + 1 : 0u;
+      const uint32_t hi = min(tiles - 1, (t0 + 64 + step - 1) / step);
+      for (uint32_t tt = lo; tt < hi; ++tt) put_tile(tt, tt * step, t0, t, put);
+      if (last_start < t0 + 64 && last_start + W > t0) put_tile(tiles - 1, last_start, t0, t, put);
+    }
+    // a frame shorter than the width (its only tile): X past its letters; no letters at all: length 1
+    if (m < W) {
+      uint8_t *rec = a.out + rec0 * W;
+      for (uint32_t t = m + lane; t < W; t += 64) rec[t] = kBaseX;
+      if (m == 0 && lane == 0) a.qlen[rec0] = 1u;
+    }
+  }
+}
+
 struct Buf {
   void *p = nullptr;
   explicit Buf(size_t bytes) { QF_CHECK(hipMalloc(&p, bytes < 256 ? 256 : bytes)); }
@@ -195,6 +323,24 @@ void LaunchQueryFormat(void *stream, const uint8_t *d_raw, const uint64_t *d_off
   else if (dna_len) hipLaunchKernelGGL(k_qry_frames<false>, dim3(blocks), dim3(kQfBlock), 0, st, a);
   else if (d_qlen) hipLaunchKernelGGL(k_qry_protein<true>, dim3(blocks), dim3(kQfBlock), 0, st, a);
   else hipLaunchKernelGGL(k_qry_protein<false>, dim3(blocks), dim3(kQfBlock), 0, st, a);
+  QF_CHECK(hipGetLastError());
+}
+
+void LaunchQueryFormatTiled(void *stream, const uint8_t *d_raw, const uint64_t *d_off, const uint32_t *d_len,
+                            const uint32_t *d_first, uint32_t n, uint32_t width, bool dna, uint32_t step,
+                            uint8_t *d_out, uint32_t *d_qlen, const void *d_tab) {
+  QfTileArgs a{d_raw, reinterpret_cast<const unsigned long long *>(d_off), d_len, d_first, n, width, step, d_out,
+               static_cast<const QfTables *>(d_tab), d_qlen};
+  // one wave per record / per (read, frame), grid-stride over at most 64 K blocks
+  const uint64_t waves = (uint64_t)n * (dna ? 6 : 1);
+  const uint32_t blocks = (uint32_t)std::min<uint64_t>((waves + kQfWaves - 1) / kQfWaves, 65536);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#ifdef GHOSTM_LDS_POISON
+  const uint32_t v = kern::LdsPoisonPattern();
+  QF_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(kern::g_lds_poison), &v, sizeof(v)));
+#endif
+  if (dna) hipLaunchKernelGGL(k_qry_frames_tiled, dim3(blocks), dim3(kQfBlock), 0, st, a);
+  else hipLaunchKernelGGL(k_qry_protein_tiled, dim3(blocks), dim3(kQfBlock), 0, st, a);
   QF_CHECK(hipGetLastError());
 }
 

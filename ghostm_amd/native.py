@@ -51,6 +51,18 @@ class GhostmHitExt(ctypes.Structure):
     ]
 
 
+class GhostmQueryTile(ctypes.Structure):
+    """one output record of a tiled query set (16 bytes): the source record, the
+    tile's first letter in the record or frame, the source's letters, the frame."""
+
+    _fields_ = [
+        ("record", c_uint32),
+        ("offset", c_uint32),
+        ("letters", c_uint32),
+        ("frame", c_uint32),
+    ]
+
+
 class GhostmHitPath(ctypes.Structure):
     """the alignment path of one hit (32 bytes): zero-based inclusive coordinates,
     its score and its run-length words ops[ops_offset : ops_offset + n_runs]."""
@@ -252,6 +264,14 @@ SIGNATURES = {
     "GhostmSessionQueryLengths": (c_size_t, [c_void_p, u32p, c_size_t]),
     "GhostmSessionQueryRecords": (c_size_t, [c_void_p, c_uint32, POINTER(ctypes.c_uint8), c_size_t]),
     "GhostmQueryChunkCuts": (ctypes.c_int64, [u32p, c_uint64, c_uint32, c_int, POINTER(c_uint64), c_uint64]),
+    "GhostmSessionSetQueriesTiled": (c_int, [c_void_p, POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p,
+                                             c_char_p, c_uint64, c_uint32, c_uint32, c_int, c_uint32, c_uint32,
+                                             c_uint32]),
+    "GhostmSessionSetQueriesFastaTiled": (c_int, [c_void_p, c_char_p, c_uint32, c_int, c_uint32, c_uint32, c_uint32,
+                                                  POINTER(c_uint64)]),
+    "GhostmSessionQueryTiles": (c_size_t, [c_void_p, POINTER(GhostmQueryTile), c_size_t]),
+    "GhostmQueryTilePlan": (ctypes.c_int64, [u32p, c_uint64, c_uint32, c_int, c_uint32, c_uint32,
+                                             POINTER(GhostmQueryTile), c_uint64, POINTER(c_uint64)]),
     "GhostmSessionCreateQueries": (c_void_p, [c_int, POINTER(c_char_p)]),
     "GhostmSessionSetDb": (c_int, [c_void_p, POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_char_p,
                                    c_uint64, c_uint32, c_uint32, c_uint32]),

@@ -515,6 +515,72 @@ size_t GhostmSessionQueryRecords(void *session, uint32_t chunk, uint8_t *codes, 
 int64_t GhostmQueryChunkCuts(const uint32_t lengths[], uint64_t n, uint32_t chunk_mb, int dna, uint64_t cuts[],
                              uint64_t cap);
 
+/* Tiled query sets: reads longer than one record of W letters (the width rule
+ * above: at most 127) enter the search as overlapping W-letter tile records
+ * under the read's name, instead of losing every letter past W. A source is a
+ * protein record's kept letters or one frame of a DNA read (n / 3 letters);
+ * with m letters and 1 <= step <= W it becomes
+ *   tiles = 1 when m <= W, else 1 + ceil((m - W) / step)
+ * records, tile t starting at letter t x step, the last one flush right at
+ * max(m - W, 0): every tile of a long source is full width, consecutive tiles
+ * overlap by at least W - step letters, and every window of at most
+ * W - step + 1 letters lies wholly inside some tile. A protein record's tiles
+ * are consecutive records; a DNA read's are tile-major and frame-minor (read
+ * base + 6 t + f), so a read of one tile gives the six records of the untiled
+ * setter. Each DNA read is translated at its own kept length, every frame once
+ * over its whole length with the stop/ATG state carried along it; a tile is a
+ * window of that frame. A tile is searched, scored and priced as a query of its
+ * own (its own length in the E-value), exactly as a frame record is; the name
+ * group merges a read's tiles into one result list. An alignment longer than
+ * W - step + 1 residues may be reported truncated to a tile: tiles are not
+ * stitched.
+ *
+ * One entry per output record, in output order. */
+typedef struct GhostmQueryTile {
+  uint32_t record;  /* index of the source record in the set given */
+  uint32_t offset;  /* the tile's first letter in the record (protein) or in the frame (DNA) */
+  uint32_t letters; /* the source's letter count m: the record's kept letters, or n / 3 of the read's kept n */
+  uint32_t frame;   /* 0 for protein; DNA: 0..2 forward, 3..5 reverse complement */
+} GhostmQueryTile;
+
+/* GhostmSessionSetQueries with tiles. max_len (letters, nt for DNA; 0: no cut)
+ * cuts every record first; step is the tile step in letters of the record or
+ * frame. The chunk cuts are GhostmQueryChunkCuts' over the kept letters, and a
+ * record's tiles never straddle a chunk. One source record may become at most
+ * 1024 output records (1024 protein tiles, 170 tiles x 6 frames). The contract
+ * of GhostmSessionSetQueries otherwise; step 0, step over the width, a record
+ * over that limit, and a chunk whose row count or bytes would wrap a 32-bit
+ * field are refused too and leave the session as it was. On a tiled set the
+ * query coordinates of the -y 6, 7, 8 and 9 text are in read coordinates (the
+ * tile's plus its offset); the structs (GhostmHitExt, GhostmHitPath,
+ * GhostmHitRows) stay relative to the tile, the record
+ * GhostmHitRows.query_record names, whose offset GhostmSessionQueryTiles gives. */
+int GhostmSessionSetQueriesTiled(void *session, const uint8_t *raw, uint64_t raw_len, const uint64_t *offsets,
+                                 const uint32_t *lengths, const char *names, uint64_t names_len, uint32_t n,
+                                 uint32_t width, int dna, uint32_t chunk_mb, uint32_t max_len, uint32_t step);
+
+/* The same from a FASTA file (the whole file is read before the first chunk is
+ * made, so every refusal leaves the session as it was). cut_records (may be
+ * NULL) receives what the untiled setter would count for a set cut at max_len:
+ * one per record cut, six per DNA read cut; 0 when max_len is 0. */
+int GhostmSessionSetQueriesFastaTiled(void *session, const char *path, uint32_t width, int dna, uint32_t chunk_mb,
+                                      uint32_t max_len, uint32_t step, uint64_t *cut_records);
+
+/* The tile table of the session's query set, one entry per query record over
+ * the chunks in order (the indexing of GhostmSessionQueryLengths and of
+ * GhostmHitRows.query_record); the NULL/cap convention of GhostmSessionHits.
+ * 0 entries on a set that was not made by a tiled setter. */
+size_t GhostmSessionQueryTiles(void *session, GhostmQueryTile *tiles, size_t cap);
+
+/* The tile plan on its own (host only, no device): the table a tiled setter
+ * would make of n records of the given letter counts, with width, dna, max_len
+ * and step as given to it. Returns the number of output records (tiles[0..]
+ * written while they fit cap entries; tiles may be NULL), or -1 on what the
+ * setter refuses (step, a record over the per-record limit). cut_records (may be
+ * NULL) as above. */
+int64_t GhostmQueryTilePlan(const uint32_t lengths[], uint64_t n, uint32_t width, int dna, uint32_t max_len,
+                            uint32_t step, GhostmQueryTile tiles[], uint64_t cap, uint64_t *cut_records);
+
 /* A session without a database: `aln`'s options without -d (giving it is an
  * error). With -i the query chunks are loaded as GhostmSessionCreate loads
  * them; without -i the session starts with neither input and the queries come
