@@ -184,6 +184,73 @@ def traceback_path_host(query_seqs, L, db, score_matrix, query_ids, db_ends, bas
     return rec, ops
 
 
+# GhostmBandSource: one source of the read-level band pass (its tile records in
+# the query chunk, its letters)
+BAND_SOURCE_DTYPE = np.dtype([("first_record", "<u4"), ("stride", "<u4"), ("tiles", "<u4"), ("letters", "<u4")])
+
+
+def _band_call(fn, head, src, diagonal, s_lo, s_hi, W, step, band, open_gap, extend_gap):
+    """Both band entry points take the same tail: the size call, then the words."""
+    srcs = np.ascontiguousarray(src, dtype=BAND_SOURCE_DTYPE)
+    diag = np.ascontiguousarray(diagonal, dtype=np.int32)
+    lo = np.ascontiguousarray(s_lo, dtype=np.uint32)
+    hi = np.ascontiguousarray(s_hi, dtype=np.uint32)
+    if not (srcs.shape == diag.shape == lo.shape == hi.shape):
+        raise ValueError("band align: bad argument shapes")
+    n = len(srcs)
+    rec = np.zeros(n, dtype=HIT_PATH_DTYPE)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+
+    def call(ops, cap, used):
+        rc = fn(*head, n, srcs.ctypes.data_as(ctypes.POINTER(native.GhostmBandSource)),
+                diag.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), lo.ctypes.data_as(u32p), hi.ctypes.data_as(u32p),
+                int(W), int(step), int(band), int(open_gap), int(extend_gap),
+                rec.ctypes.data_as(ctypes.POINTER(native.GhostmHitPath)), ops, cap, ctypes.byref(used))
+        if rc != 0:
+            raise GhostmError(native.last_error())
+
+    used = ctypes.c_size_t(0)
+    call(None, 0, used)  # the size needed
+    ops = np.zeros(used.value, dtype=np.uint32)
+    if used.value:
+        call(ops.ctypes.data_as(u32p), used.value, used)
+    return rec, ops
+
+
+def band_align_host(query_seqs, W, db, score_matrix, src, diagonal, s_lo, s_hi, step, band=31,
+                    open_gap=-11, extend_gap=-1):
+    """The host model of the read-level band pass (GhostmBandAlignHost; no
+    device): query_seqs = uint8 codes of nq tile records of W, db = the uint8
+    codes of a DB chunk, score_matrix = 32x32 int32 M[db*32 + query], src =
+    BAND_SOURCE_DTYPE records, diagonal / s_lo / s_hi per hit. Returns
+    (records[HIT_PATH_DTYPE], ops[uint32])."""
+    lib = native.load()
+    qs = np.ascontiguousarray(query_seqs, dtype=np.uint8).reshape(-1)
+    dbs = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
+    m = np.ascontiguousarray(score_matrix, dtype=np.int32).reshape(-1)
+    if m.size != 32 * 32 or W <= 0 or qs.size % W:
+        raise ValueError("band_align_host: bad argument shapes")
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    head = (qs.ctypes.data_as(u8p), qs.size // W, int(W), dbs.ctypes.data_as(u8p), dbs.size,
+            m.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+    return _band_call(lib.GhostmBandAlignHost, head, src, diagonal, s_lo, s_hi, W, step, band, open_gap, extend_gap)
+
+
+def band_align_gpu(src, diagonal, s_lo, s_hi, W, step, band=31, open_gap=-11, extend_gap=-1):
+    """BandAlignGpu on the chunks of SetQueryGpu / SetDbGpu; arguments and
+    result as band_align_host."""
+    lib = native.load()
+    return _band_call(lib.BandAlignGpu, (), src, diagonal, s_lo, s_hi, W, step, band, open_gap, extend_gap)
+
+
+def stage_band_stats() -> dict:
+    """The band counters behind the stage-level calls (GhostmStageBandStats)."""
+    lib = native.load()
+    st = native.GhostmBandStats()
+    lib.GhostmStageBandStats(ctypes.byref(st), ctypes.sizeof(st))
+    return {n: getattr(st, n) for n, _ in st._fields_}
+
+
 def query_chunk_cuts(lengths, chunk_mb: int = 0, dna: bool = False) -> np.ndarray:
     """`ghostm qry`'s chunk cuts over records of these letter counts
     (GhostmQueryChunkCuts; no device): chunk c is records [cuts[c], cuts[c + 1]).
@@ -596,6 +663,38 @@ class Session:
             lib.GhostmSessionPathOps(self._h, ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), m)
         return rec, ops
 
+    def hits_band(self) -> tuple[np.ndarray, np.ndarray]:
+        """(records, ops): one read-level HIT_PATH_DTYPE record per hit of hits()
+        (GhostmSessionHitsBand) and the run-length words they index
+        (GhostmSessionBandOps), after a run with any -y: the whole read or
+        frame aligned to the whole subject inside a band around the hit's tile
+        path. q_start / q_end are read or frame coordinates; cigar() works on
+        the words."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        n = lib.GhostmSessionHitsBand(self._h, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        rec = np.zeros(n, dtype=HIT_PATH_DTYPE)
+        if n:
+            lib.GhostmSessionHitsBand(self._h, rec.ctypes.data_as(ctypes.POINTER(native.GhostmHitPath)), n)
+        m = lib.GhostmSessionBandOps(self._h, None, 0)
+        if m == bad:
+            raise GhostmError(native.last_error())
+        ops = np.zeros(m, dtype=np.uint32)
+        if m:
+            lib.GhostmSessionBandOps(self._h, ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), m)
+        return rec, ops
+
+    def set_band(self, band: int) -> None:
+        """The half-width of hits_band()'s band, 1..31 (default 31). A refusal
+        leaves the old value; a change drops the kept band results."""
+        b = int(band)
+        if not 0 <= b < 1 << 32:  # beyond the C argument's range
+            raise GhostmError(f"band: half-width {b} outside 1..31")
+        if native.load().GhostmSessionSetBand(self._h, b) != 0:
+            raise GhostmError(native.last_error())
+
     def hits_rows(self) -> tuple[np.ndarray, np.ndarray]:
         """(records, rows): one HIT_ROWS_DTYPE record per hit of hits()
         (GhostmSessionHitsRows) and the row bytes they index
@@ -700,6 +799,10 @@ class Session:
         db = native.GhostmDbSetStats()
         native.load().GhostmSessionDbStats(self._h, ctypes.byref(db), ctypes.sizeof(db))
         out.update({name: getattr(db, name) for name, _ in db._fields_})
+        # the band pass's counters (GhostmSessionBandStats), likewise
+        band = native.GhostmBandStats()
+        native.load().GhostmSessionBandStats(self._h, ctypes.byref(band), ctypes.sizeof(band))
+        out.update({name: getattr(band, name) for name, _ in band._fields_})
         return out
 
     def close(self) -> None:

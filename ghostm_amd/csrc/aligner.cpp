@@ -19,6 +19,7 @@
 #include <stdexcept>
 #include <thread>
 
+#include "band_align.h"
 #include "common.h"
 #include "db_set.h"
 #include "query_set.h"
@@ -224,8 +225,8 @@ AlignerOptions ParseAlignerOptions(int argc, char **argv) {
   // small inputs); the oracle honours the same variable
   if (const char *e = getenv("GHOSTM_MAX_LIST_OVERRIDE")) o.max_list_length = (uint32_t)strtoul(e, nullptr, 10);
   o.matrix = ReadScoreMatrix(matrix_file);
-  // 6 to 9: style 0's E-value and bit score; 10 and 11 (the pile-up) print none, like 1 and 2
-  if (o.output_style == 0 || (o.output_style >= 6 && o.output_style <= 9)) {
+  // 6 to 9 and 12: style 0's E-value and bit score; 10 and 11 (the pile-up) print none, like 1 and 2
+  if (o.output_style == 0 || (o.output_style >= 6 && o.output_style <= 9) || o.output_style == 12) {
     // extension: GHOSTM_KARLIN=ungapped prices combinations the
     // reference's table lacks with the matrix's ungapped ideal parameters
     // (karlin_params.cpp); unset, they throw as the reference does
@@ -1488,7 +1489,7 @@ static size_t StreamPiecesPerWorker() {
 const LineFormat &Session::Format() {
   // -y 6 formats style-0 lines first: FormatTabular takes their identity,
   // E-value and bit-score bytes
-  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 9;
+  const bool tabular = (opt_.output_style >= 6 && opt_.output_style <= 9) || opt_.output_style == 12;
   // -y 10 and -y 11 replace the hit lines after the run: style 1's lines, which need no E-value, stand in
   const bool pileup = opt_.output_style == 10 || opt_.output_style == 11;
   if (!format_) format_.reset(new LineFormat(tabular ? 0 : pileup ? 1 : opt_.output_style, opt_.karlin, 4095));
@@ -1697,14 +1698,24 @@ const std::vector<uint32_t> &Session::PathOps() {
 // a thirteenth column, the extended CIGAR. From the style-0 line: the two
 // names, then the E-value and bit-score bytes; the fields are found from the
 // line's end as in FormatTabular.
-void Session::FormatPathTabular() {
-  const std::vector<GhostmHitPath> &path = HitsPath();
-  const std::vector<uint32_t> &ops = path_ops_;
+//
+// -y 12 (read_level): a hit whose read-level score (HitsBand) is above 0 takes
+// the eight columns and the CIGAR from its read-level path instead, in read or
+// frame coordinates, and its E-value and bit score from the read-level score,
+// priced like any line of the session for a query of the source's m letters
+// (search space m x the database's residues; LineFormat's uncached branches
+// take m > 127 and scores from 4096). A hit of read-level score 0 keeps its
+// -y 7 line.
+void Session::FormatPathTabular(bool read_level) {
+  const std::vector<GhostmHitPath> &tile_path = HitsPath();
+  const std::vector<GhostmHitPath> *band_path = read_level ? &HitsBand() : nullptr;
   const LineFormat &w = Format();
   // tab[7]: the tab after the subject name
   RewriteLines("tabular output", 8, [](size_t, size_t n) { return n * 64; },
                [&](size_t hit, const std::string &in, size_t pos, size_t, const size_t *tab, std::string &out) {
-    const GhostmHitPath &x = path[hit];
+    const bool band = band_path && (*band_path)[hit].score > 0;
+    const GhostmHitPath &x = band ? (*band_path)[hit] : tile_path[hit];
+    const std::vector<uint32_t> &ops = band ? band_ops_ : path_ops_;
     uint32_t count[4] = {0, 0, 0, 0}, gap_runs = 0;
     for (uint32_t r = 0; r < x.n_runs; ++r) {
       const uint32_t word = ops[x.ops_offset + r];
@@ -1718,13 +1729,21 @@ void Session::FormatPathTabular() {
     p = PutU32(p, length); *p++ = '\t';
     p = PutU32(p, count[1]); *p++ = '\t';
     p = PutU32(p, gap_runs); *p++ = '\t';
-    const uint32_t q0 = TileOffset(hit) + 1;  // a tiled set prints read coordinates
+    const uint32_t q0 = (band ? 0u : TileOffset(hit)) + 1;  // a tiled set prints read coordinates
     p = PutU32(p, x.q_start + q0); *p++ = '\t';
     p = PutU32(p, x.q_end + q0); *p++ = '\t';
     p = PutU32(p, x.s_start + 1); *p++ = '\t';
     p = PutU32(p, x.s_end + 1); *p++ = '\t';
-    out.append(num, (size_t)(p - num));
-    out.append(in, tab[2] + 1, tab[0] - tab[2] - 1);
+    if (band) {
+      const uint32_t m = band_letters_[hit];
+      const float scaled = (float)((uint64_t)m * (uint64_t)db_sum_u32_) * w.ev.p.K;
+      p = w.PutEvalue(p, m, x.score, scaled); *p++ = '\t';
+      p = w.PutBits(p, x.score);
+      out.append(num, (size_t)(p - num));
+    } else {
+      out.append(num, (size_t)(p - num));
+      out.append(in, tab[2] + 1, tab[0] - tab[2] - 1);
+    }
     out.push_back('\t');
     for (uint32_t r = 0; r < x.n_runs; ++r) {
       const uint32_t word = ops[x.ops_offset + r];
@@ -1791,6 +1810,99 @@ const std::vector<GhostmHitRows> &Session::HitsRows() {
 const std::vector<uint8_t> &Session::RowBytes() {
   HitsRows();
   return row_bytes_;
+}
+
+void Session::SetBand(uint32_t band) {
+  if (band < 1 || band > kBandMax) throw Error("band: half-width " + std::to_string(band) + " outside 1..31");
+  if (band == band_) return;
+  band_ = band;
+  hits_band_.clear();
+  band_ops_.clear();
+  hits_band_valid_ = false;
+}
+
+// The read-level path of every final hit (HitsBand). The record HitsExt()
+// resolved for a hit is a tile of its source: the tile table gives the source's
+// letters and the tile's offset, from which the tile's index and the source's
+// first record follow (a protein record's tiles are consecutive records, a DNA
+// frame's lie six records apart). On an untiled set every record is its own
+// single-tile source. One BandAlign call per (query chunk, DB chunk).
+const std::vector<GhostmHitPath> &Session::HitsBand() {
+  if (hits_band_valid_) return hits_band_;
+  const std::vector<GhostmHitPath> &path = HitsPath();
+  const std::vector<GhostmHit> &hits = Hits();
+  hits_band_.assign(hits.size(), GhostmHitPath{0, 0, 0, 0, 0, 0, 0});
+  band_letters_.assign(hits.size(), 0);
+  band_ops_.clear();
+  const std::vector<std::vector<size_t>> groups = HitsByChunkPair();
+  DeviceModule &dev = DeviceModule::Get();
+  const DeviceTimes before = dev.times();
+  std::vector<GhostmBandSource> src;
+  std::vector<int32_t> diag;
+  std::vector<uint32_t> lo, hi;
+  std::vector<GhostmHitPath> rec;
+  std::vector<std::vector<uint32_t>> words(groups.size());
+  ForChunkPairs(groups, [&](size_t qi, size_t di, const std::vector<size_t> &items) {
+    const QueryData &q = queries_[qi];
+    const DbData &d = dbs_[di];
+    const uint32_t W = q.chunk.L, step = tile_step_ ? tile_step_ : W;
+    src.clear();
+    diag.clear();
+    lo.clear();
+    hi.clear();
+    for (size_t h : items) {
+      const uint32_t local = hit_source_[h].query;
+      GhostmBandSource s{local, 1, 1, q.qlen[local]};
+      uint32_t offset = 0;
+      if (!tile_table_.empty()) {
+        const GhostmQueryTile &t = tile_table_[q.global_base + local];
+        const uint32_t m = std::max(t.letters, 1u), tiles = TileCount(m, W, step);
+        offset = t.offset;
+        const uint32_t index = offset == TileStart(tiles - 1, tiles, m, W, step) ? tiles - 1 : offset / step;
+        const uint32_t stride = tile_dna_ ? 6u : 1u;
+        if ((uint64_t)index * stride > local) throw Error("band align: a tile before its chunk's first record");
+        s = GhostmBandSource{local - index * stride, stride, tiles, m};
+      }
+      const uint32_t subject = hits[h].db_id - d.global_base, pos = d.chunk.starts[subject];
+      src.push_back(s);
+      // the first cell of the tile path, in source coordinates
+      diag.push_back((int32_t)((int64_t)pos + path[h].s_start - ((int64_t)offset + path[h].q_start)));
+      lo.push_back(pos);
+      hi.push_back(pos + SubjectLength(d, subject) - 1);
+    }
+    const uint32_t n = (uint32_t)items.size();
+    rec.resize(n);
+    dev.BandAlign(q.dev, d.dev, n, src.data(), diag.data(), lo.data(), hi.data(), step, band_, opt_.open_gap,
+                  opt_.extend_gap, rec.data(), &words[qi * dbs_.size() + di]);
+    for (uint32_t k = 0; k < n; ++k) {
+      GhostmHitPath p = rec[k];
+      p.s_start -= lo[k];
+      p.s_end -= lo[k];
+      hits_band_[items[k]] = p;  // ops_offset: still within the chunk pair's words
+      band_letters_[items[k]] = src[k].letters;
+    }
+  });
+  // the words in hit order
+  for (size_t h = 0; h < hits.size(); ++h) {
+    GhostmHitPath &p = hits_band_[h];
+    const std::vector<uint32_t> &w = words[hit_source_[h].qi * dbs_.size() + hit_source_[h].di];
+    const size_t at = band_ops_.size();
+    band_ops_.insert(band_ops_.end(), w.begin() + p.ops_offset, w.begin() + p.ops_offset + p.n_runs);
+    p.ops_offset = at;
+  }
+  const DeviceTimes &after = dev.times();
+  band_stats_.seconds_band += after.band - before.band;
+  band_stats_.band_launches += after.band_launches - before.band_launches;
+  band_stats_.band_hits += after.band_hits - before.band_hits;
+  band_stats_.band_cells += after.band_cells - before.band_cells;
+  band_stats_.band_dir_bytes += after.band_dir_bytes - before.band_dir_bytes;
+  hits_band_valid_ = true;
+  return hits_band_;
+}
+
+const std::vector<uint32_t> &Session::BandOps() {
+  HitsBand();
+  return band_ops_;
 }
 
 // A subject's residues: every subject of a chunk is followed by one END.
@@ -2196,6 +2308,10 @@ void Session::DropResults() {
   row_bytes_.clear();
   row_bytes_.shrink_to_fit();
   hits_rows_valid_ = false;
+  hits_band_.clear();
+  band_letters_.clear();
+  band_ops_.clear();
+  hits_band_valid_ = false;
   pileup_subj_.clear();
   pileup_depth_.clear();
   pileup_depth_.shrink_to_fit();
@@ -2213,8 +2329,8 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  // -y 6 to -y 11 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup), not while the search runs
-  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 11;
+  // -y 6 to -y 12 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup), not while the search runs
+  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 12;
   if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
@@ -2242,6 +2358,7 @@ void Session::Run(bool stream_to_file) {
   } close_stream{this};
   dev.ResetTimes();
   stats_ = GhostmStats{};
+  band_stats_ = GhostmBandStats{};
   QueryStats();
   merge_epoch_ = 0;
   DropResults();
@@ -2281,7 +2398,8 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    if (opt_.output_style >= 10) FormatPileup();
+    if (opt_.output_style == 12) FormatPathTabular(true);
+    else if (opt_.output_style >= 10) FormatPileup();
     else if (opt_.output_style == 6) FormatTabular();
     else FormatPathTabular();
     if (opt_.output_style == 8 || opt_.output_style == 9) FormatRows();
@@ -2460,6 +2578,7 @@ void Session::DropQueries() {
   for (QueryData &q : queries_) dev.Free(q.dev);
   queries_.clear();
   tile_table_.clear();  // a tiled set's table goes with the set
+  tile_step_ = 0;
   shard_begin_ = 0;
   shard_end_ = UINT64_MAX;
   format_seconds_ = 0;
@@ -2692,6 +2811,8 @@ void Session::SetTiledRecords(const QueryRecordView *recs, uint32_t n, const Til
   try {
     for (size_t c = 0; c + 1 < cuts.size(); ++c)
       AddQueryChunkTiled(recs + cuts[c], (uint32_t)(cuts[c + 1] - cuts[c]), (uint32_t)cuts[c], rule);
+    tile_step_ = rule.step;
+    tile_dna_ = rule.dna;
   } catch (...) {
     DropQueries();  // no half-made set
     throw;

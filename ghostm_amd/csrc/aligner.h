@@ -238,6 +238,21 @@ class Session {
   // next query set. With -y 8 and -y 9 Run makes them and the text.
   const std::vector<GhostmHitRows> &HitsRows();
   const std::vector<uint8_t> &RowBytes();
+  // One read-level GhostmHitPath per hit of Hits() and the run-length words
+  // they index (include/ghostm_hip.h, BandAlignGpu): a post-pass of
+  // DeviceModule::BandAlign, one call per (query chunk, DB chunk) that has hits.
+  // A hit's source is the whole read or frame its resolved record is a tile of
+  // (on an untiled set the record itself, with its QueryLengths entry as m), its
+  // subject range the whole subject, its anchor the first cell of its tile path
+  // (HitsPath) in source coordinates; q_* are source coordinates, s_* relative
+  // to the subject. Computed on first use, kept until the next run, query set,
+  // database or SetBand.
+  const std::vector<GhostmHitPath> &HitsBand();
+  const std::vector<uint32_t> &BandOps();
+  // the band's half-width, 1..31 (default 31); a change drops the band results
+  void SetBand(uint32_t band);
+  uint32_t Band() const { return band_; }
+  const GhostmBandStats &BandStats() const { return band_stats_; }
   // The subject pile-up of the last run's hits (include/ghostm_hip.h): one
   // GhostmSubjectPileup per subject over all DB chunks in db_id order, and the
   // subjects' depth, identities and consensus concatenated without the END
@@ -390,7 +405,8 @@ class Session {
   // -y 6: rewrites the parts' style-0 lines as the twelve BLAST-tabular columns
   void FormatTabular();
   // -y 7: the same with columns 3 to 10 taken from the hit's path, and its CIGAR
-  void FormatPathTabular();
+  // -y 12 (read_level): ... from the hit's read-level path where its score is above 0
+  void FormatPathTabular(bool read_level = false);
   // -y 8: the -y 7 line plus positives, the query row and the subject row;
   // -y 9: the pairwise view (a '#' line of the first fourteen columns, the
   // three rows, an empty line). Both rewrite the -y 7 text of FormatPathTabular.
@@ -439,6 +455,13 @@ class Session {
   std::vector<GhostmHitRows> hits_rows_;
   std::vector<uint8_t> row_bytes_;
   bool hits_rows_valid_ = false;
+  std::vector<GhostmHitPath> hits_band_;
+  std::vector<uint32_t> band_ops_, band_letters_;  // band_letters_: per hit, its source's letters m
+  bool hits_band_valid_ = false;
+  uint32_t band_ = 31;
+  uint32_t tile_step_ = 0;  // a tiled set's step; 0 on an untiled set
+  bool tile_dna_ = false;   // ... whether its sources are DNA frames (tiles six records apart)
+  GhostmBandStats band_stats_{};
   std::vector<GhostmSubjectPileup> pileup_subj_;
   std::vector<uint32_t> pileup_depth_, pileup_ident_;
   std::vector<uint8_t> pileup_cons_;

@@ -407,6 +407,52 @@ size_t GhostmSessionPathOps(void *s, uint32_t *ops, size_t cap) {
   }
 }
 
+size_t GhostmSessionHitsBand(void *s, GhostmHitPath *rec, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmHitPath> &h = static_cast<Session *>(s)->HitsBand();
+    if (!rec) return h.size();
+    const size_t n = std::min(cap, h.size());
+    std::memcpy(rec, h.data(), n * sizeof(GhostmHitPath));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionBandOps(void *s, uint32_t *ops, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<uint32_t> &w = static_cast<Session *>(s)->BandOps();
+    if (!ops) return w.size();
+    const size_t n = std::min(cap, w.size());
+    std::memcpy(ops, w.data(), n * sizeof(uint32_t));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+int GhostmSessionSetBand(void *s, uint32_t band) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetBand(band);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionBandStats(void *s, GhostmBandStats *stats, size_t size) {
+  if (!s || !stats) return 0;
+  const GhostmBandStats st = static_cast<Session *>(s)->BandStats();
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmBandStats)));
+  return sizeof(GhostmBandStats);
+}
+
 size_t GhostmSessionHitsRows(void *s, GhostmHitRows *rec, size_t cap) {
   try {
     if (!s) throw Error("null session");
@@ -535,12 +581,12 @@ int GhostmSearchMain(int argc, char **argv) {
   uint32_t width = 75, chunk_mb = 0, tile_step = 0, max_len = 0;
   bool dna = false, have_d = false, tiled = false, have_x = false;
   std::string db_fasta;
-  uint32_t db_k = 4, db_mb = 0;
+  uint32_t db_k = 4, db_mb = 0, band = 0;  // band 0: the session's default
   optind = 1;
   opterr = 1;
   int c;
-  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X
-  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:")) >= 0) {
+  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:")) >= 0) {
     switch (c) {
       case 'T':  // reads longer than the width as overlapping tiles, this many letters apart
         tiled = true;
@@ -550,6 +596,13 @@ int GhostmSearchMain(int argc, char **argv) {
         have_x = true;
         max_len = (uint32_t)atoi(optarg);
         break;
+      case 'B': {  // the half-width of -y 12's band, 1..31
+        char *end = nullptr;
+        const long v = strtol(optarg, &end, 10);
+        if (end == optarg || *end || v < 1 || v > 31) return 1;
+        band = (uint32_t)v;
+        break;
+      }
       case 'f': db_fasta = optarg; break;
       case 'k': db_k = (uint32_t)atoi(optarg); break;
       case 'm': db_mb = (uint32_t)atoi(optarg); break;
@@ -585,6 +638,7 @@ int GhostmSearchMain(int argc, char **argv) {
     std::unique_ptr<Session> made(have_d ? new Session(opt, Session::DbOnly{}) : new Session(opt, Session::NoDb{}));
     Session &session = *made;
     if (!have_d) session.SetDbFasta(db_fasta, db_k, db_mb);
+    if (band) session.SetBand(band);
     for (size_t k = 0; k < pos.size(); k += 2) {
       try {
         { std::ofstream touch(pos[k + 1].c_str()); }

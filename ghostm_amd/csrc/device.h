@@ -107,6 +107,9 @@ struct DeviceTimes {
   double pileup = 0;                              // the subject pile-up (k_pileup + k_pileup_finish): seconds,
   uint64_t pileup_launches = 0, pileup_windows = 0, pileup_parts = 0, pileup_columns = 0;  // k_pileup launches,
                                                   // profile windows, (tile, part) workgroups, columns added
+  double band = 0;                                // the read-level band pass (k_band_fill + k_band_walk + k_band_compact):
+  uint64_t band_launches = 0, band_hits = 0, band_cells = 0, band_dir_bytes = 0;  // seconds, batches, hits,
+                                                  // rows run x (2B + 1), direction bytes
 };
 
 class DeviceModule {
@@ -324,6 +327,21 @@ class DeviceModule {
   void PathPileup(DevDb *d, const PileupGroup *groups, size_t ngroups, const uint32_t *ops, size_t ops_len,
                   uint32_t p0, uint32_t p1, uint32_t *depth, uint32_t *identities, uint8_t *consensus,
                   uint32_t *profile);
+
+  // The read-level banded alignment of n hits (kern::k_band_fill, k_band_walk,
+  // k_band_compact; the contract is in include/ghostm_hip.h): hit i aligns
+  // source src[i] of chunk q (W = q's record width, tile step `step`) to
+  // subject range [s_lo[i], s_hi[i]] of chunk d around diagonal D[i] with
+  // half-width B. Everything is checked first (ValidateBand, band_align.h;
+  // throws with the reason before any upload or launch). rec[n] (may be null)
+  // and the words in hit order (*ops replaced; may be null) as TraceBackPath.
+  // The hits run in the order of their row counts, in CutBatch's batches: the
+  // cost a hit's direction bytes and word slot, the budget
+  // GHOSTM_BAND_SCRATCH_MB (default 1024), the cap GHOSTM_BAND_BATCH_HITS.
+  // Adds its device time, batches, hits, cells and direction bytes to times().
+  void BandAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBandSource *src, const int32_t *D,
+                 const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B, int open, int ext,
+                 GhostmHitPath *rec, std::vector<uint32_t> *ops);
 
   DeviceTimes &times() {
     SettleSeedTime();

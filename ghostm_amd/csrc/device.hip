@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/ghostm_hip.h"
+#include "band_align.h"
 #include "common.h"
 #include "device.h"
 #include "formats.h"
@@ -285,6 +286,8 @@ struct DeviceModule::Impl {
   DevBuf path_rows_hit, path_rows_ops, path_rows_out, path_rows_buf;
   // PathPileup: a batch's hits, words, plan lists and parts; a window's profile and finished arrays; the column counter
   DevBuf pileup_hit, pileup_ops, pileup_list, pileup_part, pileup_prof, pileup_out, pileup_cols;
+  // BandAlign: a batch's slots, its offsets / maxima / records, its direction bytes, its word slots, their packed words
+  DevBuf band_hit, band_meta, band_dir, band_ops, band_cmp;
   DevBuf tb_width, tb_ncols, tb_skey, tb_key, tb_order1, tb_order2, tb_sort, tb_pair_a, tb_pair_b, tb_best;
   int cus = 256;
   // K4 work
@@ -2604,6 +2607,146 @@ size_t DeviceModule::PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t 
   return total;
 }
 
+static_assert(kern::kBandNeg == kBandNegInf, "the kernels' minus infinity is the host model's");
+static_assert(sizeof(kern::BandHit) == 48, "BandHit is uploaded as 48-byte records");
+
+void DeviceModule::BandAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBandSource *src, const int32_t *D,
+                             const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B, int open, int ext,
+                             GhostmHitPath *rec, std::vector<uint32_t> *ops) {
+  Use();
+  Impl &I = *impl_;
+  if (ops) ops->clear();
+  if (n == 0) return;
+  // every index the kernels will use, checked here: nothing is uploaded or launched for a refused call
+  const std::string why = ValidateBand(q->nseq, q->L, d->len, n, src, s_lo, s_hi, step, B, open, ext);
+  if (!why.empty()) throw Error("band align: " + why);
+  // every hit's rows and the launch order by them, a stable sort: hits of about equal rows share a block
+  std::vector<BandRows> rows(n);
+  std::vector<uint32_t> order(n);
+  for (uint32_t k = 0; k < n; ++k) {
+    rows[k] = BandRowRange(src[k].letters, D[k], B, s_lo[k], s_hi[k]);
+    order[k] = k;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return rows[x].rows < rows[y].rows; });
+  const uint32_t stride = BandDirStride(B);
+  const size_t budget = EnvSize("GHOSTM_BAND_SCRATCH_MB", 1024) << 20;
+  const size_t max_hits = EnvSize("GHOSTM_BAND_BATCH_HITS", SIZE_MAX);
+  std::vector<std::vector<uint32_t>> batch_words;
+  std::vector<uint32_t> hit_batch(ops ? n : 0), hit_runs(n), h_rec;
+  std::vector<uint64_t> hit_at(ops ? n : 0);
+  std::vector<kern::BandHit> hh;
+  std::vector<unsigned long long> off;  // ops_off[m], later the packed offsets
+  for (uint32_t b0 = 0; b0 < n;) {
+    // slots [b0, b1) of the sorted order, cut by their direction bytes and word slots (hit_batches.h)
+    size_t bytes = 0;
+    const uint32_t b1 = CutBatch(
+        b0, n, max_hits, budget,
+        [&](uint32_t s) { return BandDirBytes(rows[order[s]].rows, B) + 4 * BandOpsSlot(rows[order[s]].rows, B); }, &bytes);
+    const uint32_t m = b1 - b0;
+    hh.resize(m);
+    off.resize(m);
+    size_t dir_bytes = 0, ops_words = 0;
+    uint64_t cells = 0;
+    for (uint32_t s = 0; s < m; ++s) {
+      const uint32_t k = order[b0 + s];
+      hh[s] = kern::BandHit{src[k].first_record, src[k].stride, src[k].tiles, src[k].letters, D[k], s_lo[k], s_hi[k],
+                            rows[k].i_top,       rows[k].rows,  0,            dir_bytes};
+      off[s] = ops_words;
+      dir_bytes += BandDirBytes(rows[k].rows, B);
+      ops_words += BandOpsSlot(rows[k].rows, B);
+      cells += (uint64_t)rows[k].rows * (2 * B + 1);
+    }
+    // meta: ops_off[m], cmp_off[m] (u64), best[3m], rec[6m]
+    I.band_hit.Reserve((size_t)m * sizeof(kern::BandHit));
+    I.band_meta.Reserve((size_t)m * 16 + (size_t)m * 36);
+    I.band_dir.Reserve(std::max<size_t>(dir_bytes, 1));
+    I.band_ops.Reserve(std::max<size_t>(ops_words, 1) * 4);
+    unsigned long long *d_off = I.band_meta.as<unsigned long long>();
+    uint32_t *d_best = reinterpret_cast<uint32_t *>(d_off + 2 * (size_t)m);
+    uint32_t *d_rec = d_best + 3 * (size_t)m;
+    HIP_CHECK(hipMemcpyAsync(I.band_hit.p, hh.data(), (size_t)m * sizeof(kern::BandHit), hipMemcpyHostToDevice, S(stream_)));
+    HIP_CHECK(hipMemcpyAsync(d_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
+    kern::BandArgs a{};
+    a.qseq = q->seq.as<uint8_t>();
+    a.W = q->L;
+    a.step = step;
+    a.db = d->Residues();
+    a.mat = I.mat_raw.as<int>();
+    a.hit = I.band_hit.as<kern::BandHit>();
+    a.n = m;
+    a.B = B;
+    a.stride = stride;
+    a.open = open;
+    a.ext = ext;
+    a.dir = I.band_dir.as<uint8_t>();
+    a.best = d_best;
+    a.ops_off = d_off;
+    a.ops = I.band_ops.as<uint32_t>();
+    a.rec = d_rec;
+    const dim3 block(kern::kTbBlock);
+    const dim3 wave_grid((m + kern::kTbBlock / 64 - 1) / (kern::kTbBlock / 64));  // one wave per slot
+    const dim3 lane_grid((m + kern::kTbBlock - 1) / kern::kTbBlock);              // one lane per slot
+    TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
+      hipLaunchKernelGGL(kern::k_band_fill, wave_grid, block, 0, S(stream_), a);
+      HIP_CHECK(hipGetLastError());
+      hipLaunchKernelGGL(kern::k_band_walk, lane_grid, block, 0, S(stream_), a);
+    });
+    h_rec.resize((size_t)m * 6);
+    HIP_CHECK(hipMemcpyAsync(h_rec.data(), d_rec, (size_t)m * 24, hipMemcpyDeviceToHost, S(stream_)));
+    HIP_CHECK(hipStreamSynchronize(S(stream_)));
+    times_.band += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+    times_.band_launches += 1;
+    times_.band_hits += m;
+    times_.band_cells += cells;
+    times_.band_dir_bytes += dir_bytes;
+    // the scan of the compaction: every slot's first word in the packed array
+    size_t packed = 0;
+    for (uint32_t s = 0; s < m; ++s) {
+      const uint32_t hit = order[b0 + s];
+      const uint32_t *r = h_rec.data() + (size_t)s * 6;
+      if (r[5] > BandOpsSlot(rows[hit].rows, B)) throw Error("band align: a hit's runs exceed its slot");
+      if (rec) rec[hit] = GhostmHitPath{r[0], r[1], r[2], r[3], r[4], r[5], 0};
+      hit_runs[hit] = r[5];
+      off[s] = packed;
+      if (ops) {
+        hit_batch[hit] = (uint32_t)batch_words.size();
+        hit_at[hit] = packed;
+      }
+      packed += r[5];
+    }
+    if (ops) {
+      batch_words.emplace_back(packed);
+      if (packed) {
+        I.band_cmp.Reserve(packed * 4);
+        HIP_CHECK(hipMemcpyAsync(d_off + m, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
+        a.cmp_off = d_off + m;
+        a.cmp = I.band_cmp.as<uint32_t>();
+        TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
+          hipLaunchKernelGGL(kern::k_band_compact, wave_grid, block, 0, S(stream_), a);
+        });
+        HIP_CHECK(hipMemcpyAsync(batch_words.back().data(), a.cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
+        HIP_CHECK(hipStreamSynchronize(S(stream_)));
+        times_.band += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+      }
+    }
+    b0 = b1;
+  }
+  // the batches' words joined in hit order
+  uint64_t total = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    if (rec) rec[k].ops_offset = total;
+    total += hit_runs[k];
+  }
+  if (ops) {
+    ops->resize(total);
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+      if (hit_runs[k]) memcpy(ops->data() + at, batch_words[hit_batch[k]].data() + hit_at[k], (size_t)hit_runs[k] * 4);
+      at += hit_runs[k];
+    }
+  }
+}
+
 static_assert(kern::kPileupTileMax == kPileupTileMax, "the kernel's LDS histogram holds the plan's largest tile");
 
 void DeviceModule::PathPileup(DevDb *d, const PileupGroup *groups, size_t ngroups, const uint32_t *ops,
@@ -2747,7 +2890,7 @@ const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_pileup/k_pileup_finish, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_pileup/k_pileup_finish/k_band_fill/k_band_walk/k_band_compact, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -3177,6 +3320,45 @@ int PathRowsGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPath 
     SetError(e.what());
     return 1;
   }
+}
+
+int BandAlignGpu(uint32_t nhits, const GhostmBandSource src[], const int32_t diagonal[], const uint32_t s_lo[],
+                 const uint32_t s_hi[], uint32_t query_sequence_length, uint32_t step, uint32_t band, int open_gap,
+                 int extend_gap, GhostmHitPath rec[], uint32_t ops[], size_t ops_cap, size_t *ops_used) {
+  try {
+    if (!ops_used) throw Error("BandAlignGpu: null: ops_used");
+    if (nhits && (!src || !diagonal || !s_lo || !s_hi)) throw Error("BandAlignGpu: null: an input array");
+    if (nhits == 0) {
+      *ops_used = 0;
+      return 0;
+    }
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    if (!r.query || !r.db) throw Error("SetQueryGpu/SetDbGpu not called");
+    if (query_sequence_length != r.query->L) throw Error("BandAlignGpu: source: query shape differs from SetQueryGpu");
+    std::vector<GhostmHitPath> out(nhits);
+    std::vector<uint32_t> words;
+    DeviceModule::Get().BandAlign(r.query, r.db, nhits, src, diagonal, s_lo, s_hi, step, band, open_gap, extend_gap,
+                                  out.data(), &words);
+    if (ops && words.size() > ops_cap) throw Error("BandAlignGpu: ops_cap: the operations do not fit");
+    if (rec) std::copy(out.begin(), out.end(), rec);
+    if (ops) std::copy(words.begin(), words.end(), ops);
+    *ops_used = words.size();
+    return 0;
+  } catch (std::exception &e) {
+    SetError(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmStageBandStats(GhostmBandStats *stats, size_t size) {
+  if (!stats) return 0;
+  RefState &r = Ref();
+  std::lock_guard<std::mutex> lk(r.mu);
+  const DeviceTimes &dt = DeviceModule::Get().times();
+  const GhostmBandStats st{dt.band, dt.band_launches, dt.band_hits, dt.band_cells, dt.band_dir_bytes};
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmBandStats)));
+  return sizeof(GhostmBandStats);
 }
 
 int PathPileupGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPath rec[], const uint32_t ops[],

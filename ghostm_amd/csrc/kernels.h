@@ -4820,5 +4820,225 @@ __global__ __launch_bounds__(kScanBlock) void k_tb_scan(TbScanArgs a) {
     if (s_hist[b]) atomicAdd(&a.hist[b], s_hist[b]);
 }
 
+// ------------------------------------------------------------------ read-level banded alignment
+// k_band_fill + k_band_walk + k_band_compact: the read-level path of every hit
+// (BandAlignGpu, include/ghostm_hip.h; host model band_align_host.cpp). One
+// wave per hit; lane b = j - i - D + B (0..2B, at most 63 lanes) owns one
+// diagonal of the band, so in the reverse DP over rows i = i_top .. i_top -
+// rows + 1
+//   the diagonal term H(i+1, j+1) is the lane's own H of the previous row,
+//   F's terms H(i+1, j), F(i+1, j) are lane b-1's of the previous row (one
+//     DPP wave_shr each),
+//   E(i, j) depends on lane b+1 of the same row: the chain across the lanes is
+//     a max-plus suffix scan over Hh = max(0, s, F):
+//     E(b) = max over b' > b of Hh(b') + open + ext * (b' - b - 1),
+//     log2 steps of shuffle-down. It equals the sequential recurrence because
+//     open <= ext (a cell whose H came from E offers E + open <= E + ext, which
+//     the extension already covers); the host refuses other gap costs.
+// A lane whose cell is no band cell (j outside [s_lo, s_hi], lanes above 2B)
+// carries H = 0 and E = F = kBandNeg, the model's neighbour values. eext and
+// fext are formed from the final values with the recurrence's comparisons, so a
+// tie opens as in the model. Every lane keeps its first strict maximum (value,
+// i); the wave reduces by (value, i, lane), the model's first strict maximum in
+// processing order. The letters: q[i] is wave-uniform and read through the
+// tile table (BandLetter, a restatement of band_align.h / query_tiles.h), db[j]
+// one byte per lane; both are loaded one row ahead of their use.
+// Direction bytes, one per lane and row at dir + dir_off + (i_top - i) *
+// stride + b (consecutive lanes, consecutive bytes): bits 0-1 hsel, bit 2
+// eext, bit 3 fext, bit 4 the two codes are equal (so the walk reads no
+// sequence). k_band_walk follows them with one lane per hit, a separate launch
+// so the bytes are visible, and writes run-length words into the slot's
+// 2 * rows + 2B + 2 words and six record words; k_band_compact packs the
+// slots' words (one wave per slot, consecutive lanes on consecutive words).
+// The host has checked every index (ValidateBand, band_align.h).
+constexpr int kBandNeg = -(1 << 29);  // = ghostm::kBandNegInf (checked in device.hip)
+struct BandHit {                      // 48 bytes, one per batch slot
+  uint32_t first_record, stride, tiles, letters;
+  int32_t D;
+  uint32_t s_lo, s_hi;
+  uint32_t i_top, rows;               // the rows run: i_top down to i_top - rows + 1
+  uint32_t pad;
+  unsigned long long dir_off;         // first direction byte of the slot
+};
+struct BandArgs {
+  const uint8_t *qseq;
+  uint32_t W, step;
+  const uint8_t *db;
+  const int *mat;                     // M[db code * 32 + query code]
+  const BandHit *hit;
+  uint32_t n;                         // slots of the batch
+  uint32_t B, stride;                 // half-width; direction bytes per row
+  int open, ext;
+  uint8_t *dir;
+  uint32_t *best;                     // per slot: i*, j*, score
+  const unsigned long long *ops_off;  // per slot: first of its run-length words
+  uint32_t *ops;
+  uint32_t *rec;                      // per slot: q_start, q_end, s_start, s_end, score, n_runs
+  const unsigned long long *cmp_off;  // per slot: its first word in cmp
+  uint32_t *cmp;
+};
+
+__device__ __forceinline__ uint32_t BandLetter(const uint8_t *qseq, const BandHit &h, uint32_t p, uint32_t W,
+                                               uint32_t step) {
+  const uint32_t t = min(p / step, h.tiles - 1);
+  const uint32_t start = t + 1 < h.tiles ? t * step : (h.letters > W ? h.letters - W : 0u);
+  const uint32_t rec = h.first_record + (h.tiles > 1 ? h.stride * t : 0u);
+  return qseq[(size_t)rec * W + (p - start)];
+}
+
+// lane l receives lane l+d's value, the lanes past the wave's end `fill`
+__device__ __forceinline__ int BandShiftDown(int v, uint32_t d, uint32_t lane, int fill) {
+  const int x = __shfl_down(v, d);
+  return lane + d > 63u ? fill : x;
+}
+
+__global__ __launch_bounds__(kTbBlock) void k_band_fill(BandArgs a) {
+  GHOSTM_POISON_LDS();
+  __shared__ int s_mat[32 * 32];
+  for (uint32_t e = threadIdx.x; e < 32 * 32; e += kTbBlock) s_mat[e] = a.mat[e];
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t slot = blockIdx.x * (kTbBlock / 64) + (threadIdx.x >> 6);
+  if (slot >= a.n) return;  // the whole wave
+  const BandHit hit = a.hit[slot];
+  const int B = (int)a.B;
+  int best = 0;
+  uint32_t best_i = 0;
+  if (hit.rows) {
+    // this lane's column in row i is i + j0; it is a band cell for i in [vlo, vhi]
+    const long long j0 = (long long)hit.D - B + (long long)lane;
+    const long long i_bot = (long long)hit.i_top - (long long)hit.rows + 1;
+    long long vlo = (long long)hit.s_lo - j0, vhi = (long long)hit.s_hi - j0;
+    if (lane > 2u * a.B) vhi = -1, vlo = 0;  // never
+    const int lo = (int)min(max(vlo, i_bot), (long long)hit.i_top + 1);
+    const int hi = (int)max(min(vhi, (long long)hit.i_top), i_bot - 1);
+    const uint8_t *dbp = a.db + j0;  // dbp[i] is the lane's residue in row i (read only where valid)
+    uint8_t *dir = a.dir + hit.dir_off + lane;
+    const bool writes = lane < a.stride;
+    int Hp = 0, Fp = kBandNeg;
+    int i = (int)hit.i_top;
+    uint32_t qn = BandLetter(a.qseq, hit, (uint32_t)i, a.W, a.step) & 31u;
+    uint32_t dn = i >= lo && i <= hi ? dbp[i] & 31u : 0u;
+    for (uint32_t r = 0; r < hit.rows; ++r, --i) {
+      const uint32_t qc = qn, dc = dn;
+      const bool valid = i >= lo && i <= hi;
+      if (r + 1 < hit.rows) {  // the next row's letters
+        qn = BandLetter(a.qseq, hit, (uint32_t)(i - 1), a.W, a.step) & 31u;
+        dn = i - 1 >= lo && i - 1 <= hi ? dbp[i - 1] & 31u : 0u;
+      }
+      int Hb = (int)ShiftUp((uint32_t)Hp), Fb = (int)ShiftUp((uint32_t)Fp);
+      if (lane == 0) Fb = kBandNeg;  // (Hb is 0 there: bound_ctrl)
+      const int s = Hp + s_mat[dc * 32 + qc];
+      const int fe = Fb + a.ext, fo = Hb + a.open;
+      const int F = max(fe, fo);
+      const int Hh = valid ? max(max(s, F), 0) : 0;
+      // the E chain: E(b) = max over b' > b of Hh(b') + open + ext * (b' - b - 1)
+      int E = BandShiftDown(Hh + a.open, 1, lane, kBandNeg);
+      for (uint32_t d = 1; d <= 2u * a.B; d <<= 1) E = max(E, BandShiftDown(E, d, lane, kBandNeg) + a.ext * (int)d);
+      int cell = 0;
+      uint32_t bits = 0;
+      if (s > 0) { cell = s; bits = 1; }
+      if (E > cell) { cell = E; bits = 2; }
+      if (F > cell) { cell = F; bits = 3; }
+      const int Hc = valid ? cell : 0, Ec = valid ? E : kBandNeg;
+      // eext from lane b+1's final values (no band cell: H 0, E minus infinity)
+      const int Er = BandShiftDown(Ec, 1, lane, kBandNeg), Hr = BandShiftDown(Hc, 1, lane, 0);
+      bits |= (Er + a.ext > Hr + a.open ? 4u : 0u) | (fe > fo ? 8u : 0u) | (dc == qc ? 16u : 0u);
+      if (writes) dir[(size_t)r * a.stride] = valid ? (uint8_t)bits : (uint8_t)0;
+      if (Hc > best) {
+        best = Hc;
+        best_i = (uint32_t)i;
+      }
+      Hp = Hc;
+      Fp = valid ? F : kBandNeg;
+    }
+  }
+  // the first strict maximum in processing order: largest value, then largest i, then largest lane
+  uint32_t bl = lane;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const int ov = __shfl_xor(best, d);
+    const uint32_t oi = (uint32_t)__shfl_xor((int)best_i, d), ol = (uint32_t)__shfl_xor((int)bl, d);
+    if (ov > best || (ov == best && (oi > best_i || (oi == best_i && ol > bl)))) {
+      best = ov;
+      best_i = oi;
+      bl = ol;
+    }
+  }
+  if (lane == 0) {
+    uint32_t *o = a.best + 3 * (size_t)slot;
+    o[0] = best > 0 ? best_i : 0u;
+    o[1] = best > 0 ? (uint32_t)((long long)best_i + hit.D - B + (long long)bl) : hit.s_lo;
+    o[2] = (uint32_t)best;
+  }
+}
+
+__global__ __launch_bounds__(kTbBlock) void k_band_walk(BandArgs a) {
+  GHOSTM_POISON_LDS();
+  const uint32_t slot = blockIdx.x * kTbBlock + threadIdx.x;
+  if (slot >= a.n) return;
+  const BandHit hit = a.hit[slot];
+  const uint8_t *dir = a.dir + hit.dir_off;
+  uint32_t *out = a.ops + a.ops_off[slot];
+  const uint32_t cap = hit.rows ? 2 * hit.rows + 2 * a.B + 2 : 0;
+  const uint32_t bi = a.best[3 * (size_t)slot], bj = a.best[3 * (size_t)slot + 1], score = a.best[3 * (size_t)slot + 2];
+  long long i = bi, j = bj;
+  const long long i_bot = (long long)hit.i_top - (long long)hit.rows + 1;
+  uint32_t nruns = 0, cur = 0, len = 0;
+  if (score > 0) {
+    int state = 0;
+    // every operation consumes a query or a subject residue: at most cap of them, and a state change between two
+    for (uint32_t it = 0; it < 2 * cap + 2; ++it) {
+      const long long b = j - i - hit.D + (long long)a.B;
+      // the band cells (inside them the row is one of the rows run)
+      if (i >= (long long)hit.letters || j > (long long)hit.s_hi || b < 0 || b > 2ll * a.B) break;
+      if (i > (long long)hit.i_top || i < i_bot) break;
+      const uint32_t d = dir[(size_t)((long long)hit.i_top - i) * a.stride + (size_t)b];
+      uint32_t op;
+      if (state == 0) {
+        const uint32_t sel = d & 3u;
+        if (sel == 0) break;
+        if (sel != 1) { state = sel == 2 ? 1 : 2; continue; }
+        op = (d & 16u) ? 0u : 1u;
+        ++i;
+        ++j;
+      } else if (state == 1) {
+        op = 3u;
+        state = (d & 4u) ? 1 : 0;
+        ++j;
+      } else {
+        op = 2u;
+        state = (d & 8u) ? 2 : 0;
+        ++i;
+      }
+      if (len && op != cur) {
+        if (nruns < cap) out[nruns++] = len << 4 | cur;
+        len = 0;
+      }
+      cur = op;
+      ++len;
+    }
+    if (len && nruns < cap) out[nruns++] = len << 4 | cur;
+  }
+  uint32_t *r = a.rec + 6 * (size_t)slot;
+  r[0] = bi;
+  r[1] = score > 0 ? (uint32_t)(i - 1) : bi;
+  r[2] = bj;
+  r[3] = score > 0 ? (uint32_t)(j - 1) : bj;
+  r[4] = score;
+  r[5] = nruns;
+}
+
+__global__ __launch_bounds__(kTbBlock) void k_band_compact(BandArgs a) {
+  GHOSTM_POISON_LDS();
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t slot = blockIdx.x * (kTbBlock / 64) + (threadIdx.x >> 6);
+  if (slot >= a.n) return;
+  const uint32_t n = a.rec[6 * (size_t)slot + 5];
+  const uint32_t *src = a.ops + a.ops_off[slot];
+  uint32_t *dst = a.cmp + a.cmp_off[slot];
+  for (uint32_t k = lane; k < n; k += 64) dst[k] = src[k];
+}
+
 }  // namespace kern
 }  // namespace ghostm

@@ -78,6 +78,30 @@ class GhostmHitPath(ctypes.Structure):
     ]
 
 
+class GhostmBandSource(ctypes.Structure):
+    """one source of the read-level band pass (16 bytes): its tile records in the
+    resident query chunk and its letters."""
+
+    _fields_ = [
+        ("first_record", c_uint32),
+        ("stride", c_uint32),
+        ("tiles", c_uint32),
+        ("letters", c_uint32),
+    ]
+
+
+class GhostmBandStats(ctypes.Structure):
+    """the counters of the band pass (GhostmSessionBandStats, GhostmStageBandStats)."""
+
+    _fields_ = [
+        ("seconds_band", ctypes.c_double),
+        ("band_launches", c_uint64),
+        ("band_hits", c_uint64),
+        ("band_cells", c_uint64),
+        ("band_dir_bytes", c_uint64),
+    ]
+
+
 class GhostmHitRows(ctypes.Structure):
     """the aligned rows of one hit (32 bytes): the record the path lies in, its
     counts and its 3 * columns bytes rows[rows_offset:] (query row, midline,
@@ -248,6 +272,14 @@ SIGNATURES = {
     "GhostmPathPileupHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, POINTER(ctypes.c_uint8), c_uint32,
                                      POINTER(c_int), c_uint32, u32p, POINTER(GhostmHitPath), u32p, c_size_t, c_uint32,
                                      u32p, u32p, POINTER(ctypes.c_uint8), u32p]),
+    "BandAlignGpu": (c_int, [c_uint32, POINTER(GhostmBandSource), POINTER(ctypes.c_int32), u32p, u32p, c_uint32,
+                             c_uint32, c_uint32, c_int, c_int, POINTER(GhostmHitPath), u32p, c_size_t,
+                             POINTER(c_size_t)]),
+    "GhostmBandAlignHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, POINTER(ctypes.c_uint8), c_uint32,
+                                    POINTER(c_int), c_uint32, POINTER(GhostmBandSource), POINTER(ctypes.c_int32), u32p,
+                                    u32p, c_uint32, c_uint32, c_uint32, c_int, c_int, POINTER(GhostmHitPath), u32p,
+                                    c_size_t, POINTER(c_size_t)]),
+    "GhostmStageBandStats": (c_size_t, [POINTER(GhostmBandStats), c_size_t]),
     "GhostmBuildIndexGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, u32p, u32p, u32p, c_int,
                                     POINTER(c_float)]),
     "GhostmFormatQueriesGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_uint32,
@@ -294,6 +326,10 @@ SIGNATURES = {
     "GhostmSessionHitsExt": (c_size_t, [c_void_p, POINTER(GhostmHitExt), c_size_t]),
     "GhostmSessionHitsPath": (c_size_t, [c_void_p, POINTER(GhostmHitPath), c_size_t]),
     "GhostmSessionPathOps": (c_size_t, [c_void_p, u32p, c_size_t]),
+    "GhostmSessionHitsBand": (c_size_t, [c_void_p, POINTER(GhostmHitPath), c_size_t]),
+    "GhostmSessionBandOps": (c_size_t, [c_void_p, u32p, c_size_t]),
+    "GhostmSessionSetBand": (c_int, [c_void_p, c_uint32]),
+    "GhostmSessionBandStats": (c_size_t, [c_void_p, POINTER(GhostmBandStats), c_size_t]),
     "GhostmSessionHitsRows": (c_size_t, [c_void_p, POINTER(GhostmHitRows), c_size_t]),
     "GhostmSessionRowBytes": (c_size_t, [c_void_p, POINTER(ctypes.c_uint8), c_size_t]),
     "GhostmSessionPileup": (c_size_t, [c_void_p, POINTER(GhostmSubjectPileup), c_size_t]),

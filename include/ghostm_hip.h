@@ -532,8 +532,10 @@ int64_t GhostmQueryChunkCuts(const uint32_t lengths[], uint64_t n, uint32_t chun
  * window of that frame. A tile is searched, scored and priced as a query of its
  * own (its own length in the E-value), exactly as a frame record is; the name
  * group merges a read's tiles into one result list. An alignment longer than
- * W - step + 1 residues may be reported truncated to a tile: tiles are not
- * stitched.
+ * W - step + 1 residues may be reported truncated to a tile by the hit records
+ * and the per-tile detail passes (-y 6 to 11): tiles are not stitched there.
+ * The read-level alignment of a hit, over the whole read or frame, comes from
+ * GhostmSessionHitsBand / -y 12 (BandAlignGpu below).
  *
  * One entry per output record, in output order. */
 typedef struct GhostmQueryTile {
@@ -580,6 +582,103 @@ size_t GhostmSessionQueryTiles(void *session, GhostmQueryTile *tiles, size_t cap
  * NULL) as above. */
 int64_t GhostmQueryTilePlan(const uint32_t lengths[], uint64_t n, uint32_t width, int dna, uint32_t max_len,
                             uint32_t step, GhostmQueryTile tiles[], uint64_t cap, uint64_t *cut_records);
+
+/* Read-level alignments: a banded Gotoh DP with traceback over a whole source
+ * (a protein record's kept letters, or one frame of a DNA read), however many
+ * tile records it was cut into, against one subject range. This is the step
+ * from "which tile hit which subject where" to "how does the read align to
+ * that subject"; the per-tile paths of TraceBackPathGpu stay as they are.
+ *
+ * Per hit: the source's m letters q[0..m), read through its tile records
+ * (letter p lies in tile t = min(p / step, tiles - 1), record first_record +
+ * stride * t, byte p - start(t) with the tile starts above); the subject range
+ * [s_lo, s_hi], absolute in the resident DB chunk and free of END codes (the
+ * caller gives a subject's own residues); the anchor diagonal D (signed); the
+ * band half-width B, 1..31. The band cells are (i, j) with 0 <= i < m, s_lo <=
+ * j <= s_hi and |j - i - D| <= B. All arithmetic is int32. The DP runs in
+ * reverse like GhostmTraceBackPathHost, rows i = m-1 .. 0 and j descending in a
+ * row, so the walk is forward in both sequences:
+ *   s      = H(i+1,j+1) + M[(db[j] & 31) * 32 + (q[i] & 31)]
+ *   E(i,j) = max(E(i,j+1) + ext, H(i,j+1) + open)    'D': db[j] against a gap
+ *   F(i,j) = max(F(i+1,j) + ext, H(i+1,j) + open)    'I': q[i] against a gap
+ *   H(i,j) = s if s > 0 else 0; then E if E > H; then F if F > H (each strict,
+ *            in that order: hsel 1 / 0, 2, 3)
+ *   eext   = E(i,j+1) + ext > H(i,j+1) + open (a tie opens); fext likewise
+ * A neighbour that is no band cell has H = 0 and E, F = minus infinity (no gap
+ * extends from it). The start cell is the first strict maximum in processing
+ * order: among the cells of maximal H the largest i, then the largest j. From
+ * it the three-state walk of TraceBackPathGpu: H with hsel 1 emits '=' / 'X'
+ * and goes to (i+1, j+1); hsel 2 / 3 enter E / F at the same cell; E emits 'D'
+ * and goes to (i, j+1), F emits 'I' and goes to (i+1, j), staying in the gap
+ * state if eext / fext; hsel 0 or leaving the band cells stops. The result is a
+ * GhostmHitPath and run-length words in its encoding; q_start / q_end are in
+ * source coordinates (they may exceed 127), s_* absolute in the chunk. Score 0
+ * gives an empty path at q_start = 0, s_start = s_lo with the ends equal to the
+ * starts. Limits: B <= 31 (one wave lane per diagonal); open_gap <= extend_gap
+ * <= 0 (the kernel resolves a row's E chain with a max-plus scan, which equals
+ * the sequential recurrence exactly under this condition; the reference's 11/1,
+ * 9/1 and 14/2 meet it). */
+typedef struct GhostmBandSource {          /* 16 bytes */
+  uint32_t first_record;                   /* tile 0 of this source in the resident query chunk */
+  uint32_t stride;                         /* records between consecutive tiles: 1, or 6 for a DNA frame; ignored
+                                              when tiles == 1 */
+  uint32_t tiles;                          /* must equal the tile count of letters, W and step */
+  uint32_t letters;                        /* m, at least 1 */
+} GhostmBandSource;
+
+/* The read-level path of every hit (kernels k_band_fill + k_band_walk), stage
+ * level like TraceBackPathGpu (after SetQueryGpu and SetDbGpu);
+ * query_sequence_length is the records' width W, step the tile step. Record i
+ * belongs to hit i; the hits' words follow each other in hit order. ops ==
+ * NULL: only *ops_used (the words needed) and rec (may be NULL) are written.
+ * Everything is checked on the host before any upload or launch; a refused call
+ * leaves rec, ops and *ops_used untouched and names its reason in
+ * GhostmGetLastError:
+ *   "source"  a record outside the chunk; tiles == 0 or letters == 0; tiles
+ *             disagrees with letters, W and step; step 0 or over W; W differs
+ *             from the resident chunk's
+ *   "band"    band outside 1..31
+ *   "bounds"  s_lo > s_hi or s_hi >= the resident chunk's length
+ *   "gaps"    not open_gap <= extend_gap <= 0
+ *   "ops_cap" the words do not fit ops_cap
+ *   "null"    a null ops_used, or a null input array with nhits > 0
+ * One wave runs one hit, lane b = j - i - D + B owning a diagonal, over the
+ * rows whose band meets [s_lo, s_hi] only: i from min(m-1, s_hi - D + B) down
+ * to max(0, s_lo - D - B). A hit's direction buffer is one byte per lane and
+ * row run: rows x ((2B + 1 + 3) & ~3) bytes. The hits are sorted by rows and
+ * cut into batches that fit GHOSTM_BAND_SCRATCH_MB (default 1024) and hold at
+ * most GHOSTM_BAND_BATCH_HITS hits (default: no limit); a batch holds at least
+ * one hit. */
+int BandAlignGpu(uint32_t nhits, const GhostmBandSource src[], const int32_t diagonal[],
+                 const uint32_t s_lo[], const uint32_t s_hi[], uint32_t query_sequence_length,
+                 uint32_t step, uint32_t band, int open_gap, int extend_gap,
+                 GhostmHitPath rec[], uint32_t ops[], size_t ops_cap, size_t *ops_used);
+
+/* The same on the host, with no device call (the model the kernels are checked
+ * against, run cell by cell) and the same checks and reasons: query_seqs = nq
+ * records of L codes, db = the chunk's db_len residues, score_matrix =
+ * M[db code * 32 + query code]; query_sequence_length must equal L. */
+int GhostmBandAlignHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, const uint8_t *db, uint32_t db_len,
+                        const int score_matrix[], uint32_t nhits, const GhostmBandSource src[],
+                        const int32_t diagonal[], const uint32_t s_lo[], const uint32_t s_hi[],
+                        uint32_t query_sequence_length, uint32_t step, uint32_t band, int open_gap,
+                        int extend_gap, GhostmHitPath rec[], uint32_t ops[], size_t ops_cap, size_t *ops_used);
+
+/* The counters of the band pass. A struct of their own, like GhostmDbSetStats:
+ * GhostmStats keeps its layout. */
+typedef struct GhostmBandStats {
+  double seconds_band;       /* k_band_fill + k_band_walk + k_band_compact, device time */
+  uint64_t band_launches;    /* batches of hits */
+  uint64_t band_hits;
+  uint64_t band_cells;       /* sum over the hits of rows run x (2B + 1) */
+  uint64_t band_dir_bytes;   /* direction-buffer bytes the batches addressed */
+} GhostmBandStats;
+
+/* The band counters behind the stage-level calls, as GhostmStageStats gives the
+ * others: they add up over the process's BandAlignGpu calls and start again at
+ * 0 with every GhostmSessionRun. Copies min(size, sizeof(GhostmBandStats))
+ * bytes and returns the library's sizeof; 0 on a null argument. */
+size_t GhostmStageBandStats(GhostmBandStats *stats, size_t size);
 
 /* A session without a database: `aln`'s options without -d (giving it is an
  * error). With -i the query chunks are loaded as GhostmSessionCreate loads
@@ -754,7 +853,16 @@ int GhostmSessionRun(void *session);
  * identities_sum, max_depth. -y 11 is that line with an eighth column, the
  * subject's consensus as text: the residue letter, '-' where depth > 0 and
  * consensus is 255, '.' where depth is 0. Neither prints an E-value, so like
- * -y 1 and -y 2 they need no Karlin parameters. */
+ * -y 1 and -y 2 they need no Karlin parameters.
+ * -y 12 prints the thirteen -y 7 columns from the hit's read-level path
+ * (GhostmSessionHitsBand): pident, length, mismatch, gapopen, qstart, qend,
+ * sstart, send and the CIGAR describe the whole read or frame against the
+ * subject, one-based and in read or frame coordinates; evalue and bitscore come
+ * from the read-level score, priced like every line of the session for a query
+ * of the source's m letters (search space m x the database's residues, the
+ * reference's float / double steps). A hit whose read-level score is 0 prints
+ * its -y 7 line unchanged. Hits are not re-ranked or re-merged by the new
+ * scores. Written at the end of the run, like -y 7. */
 int GhostmSessionRunToFile(void *session);
 
 /* Formatted output of the last run (reference WriteOutput/V1/V2 text). With
@@ -798,6 +906,37 @@ size_t GhostmSessionPathOps(void *session, uint32_t *ops, size_t cap);
  * its name group instead). */
 size_t GhostmSessionHitsRows(void *session, GhostmHitRows *rec, size_t cap);
 size_t GhostmSessionRowBytes(void *session, uint8_t *rows, size_t cap);
+
+/* The read-level path of every hit of the last run (record i belongs to hit i)
+ * and the run-length words they index, in hit order; both with the NULL/cap
+ * convention of GhostmSessionHitsPath, (size_t)-1 on error. Where the hit's
+ * GhostmHitPath describes at most one tile record, this one aligns the whole
+ * read or frame to the whole subject (the contract above BandAlignGpu):
+ *   source   the read or frame whose tile the hit's resolved record is
+ *            (GhostmHitRows.query_record's tile-table entry: record, frame,
+ *            letters); on an untiled set every record is its own single-tile
+ *            source with m its entry of GhostmSessionQueryLengths
+ *   subject  the whole subject, so no alignment crosses an END
+ *   anchor   the first cell of the hit's tile path: D = s_start (absolute) -
+ *            (tile offset + q_start); the read-level score is therefore at
+ *            least the tile path's whenever every cell of the tile path lies
+ *            within the band of D
+ * q_start / q_end are in read or frame coordinates (they may exceed 127),
+ * s_start / s_end relative to the subject. Works after a run with any -y and on
+ * shard sessions (each rank its own hits): one BandAlignGpu-style call per
+ * (query chunk, DB chunk) that has hits, computed on first use and kept until
+ * the next run, GhostmSessionSetQueries*, GhostmSessionSetDb* or change of
+ * band. Hits are not re-ranked or re-merged by the read-level scores. */
+size_t GhostmSessionHitsBand(void *session, GhostmHitPath *rec, size_t cap);
+size_t GhostmSessionBandOps(void *session, uint32_t *ops, size_t cap);
+
+/* The band's half-width for GhostmSessionHitsBand: 1..31, default 31. A
+ * refusal (non-zero) leaves the old value; a change drops the kept results. */
+int GhostmSessionSetBand(void *session, uint32_t band);
+
+/* The band counters of the session since its last run (all 0 until the band
+ * results are asked for); the size convention of GhostmSessionDbStats. */
+size_t GhostmSessionBandStats(void *session, GhostmBandStats *stats, size_t size);
 
 /* The pile-up of the last run's hits on every subject (the definitions above
  * PathPileupGpu), built on the paths of GhostmSessionHitsPath with the record
@@ -859,15 +998,16 @@ void GhostmSessionDestroy(void *session);
 int GhostmAlignMain(int argc, char **argv);
 
 /* `ghostm search [aln options except -i -o -S -L] [-q d|p] [-w maxLength]
- * [-c chunkSizeMB] (-d database | -f db.fasta [-k kSize] [-m chunkSizeMB])
+ * [-c chunkSizeMB] [-B band] (-d database | -f db.fasta [-k kSize] [-m chunkSizeMB])
  * q1.fasta out1 [q2.fasta out2 ...]`: one session with the database resident,
  * from its formatted files (-d) or formatted on the device from FASTA (-f, with
  * -k and -m as db's -k and -l: GhostmSessionCreateQueries and one
  * GhostmSessionSetDbFasta); for each pair the queries are set from the FASTA
  * file (-q, -w, -c as qry's -t, -l, -L; qry's warnings on stderr) and searched
  * into the output file, which equals [`ghostm db` +] `ghostm qry` + `ghostm
- * aln` on those files. Wrong usage (no pairs, an odd number of positionals,
- * -i, -o, -S or -L, both or neither of -d and -f) returns 1 before any device
+ * aln` on those files. -B sets the half-width of -y 12's band
+ * (GhostmSessionSetBand). Wrong usage (no pairs, an odd number of positionals,
+ * -i, -o, -S or -L, both or neither of -d and -f, -B outside 1..31) returns 1 before any device
  * call; errors are printed and 0 returned, as GhostmAlignMain. */
 int GhostmSearchMain(int argc, char **argv);
 
