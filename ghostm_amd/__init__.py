@@ -7,7 +7,8 @@ from .aligner import (Aligner, GhostmError, HIT_DTYPE, HIT_EXT_DTYPE, HIT_PATH_D
                       SUBJECT_PILEUP_DTYPE, Session, cigar, consensus_text, db_chunk_cuts, format_db, format_queries, path_pileup_host,
                       path_rows_host, query_chunk_cuts, rows_of, run_cli, synth, traceback_ext_host,
                       traceback_path_host, QUERY_TILE_DTYPE, tile_plan, BAND_SOURCE_DTYPE, band_align_host,
-                      band_align_gpu, stage_band_stats)
+                      band_align_gpu, stage_band_stats, HIT_FRAME_INFO_DTYPE, frame_align,
+                      frame_align_host, frame_cigar, stage_frame_stats)
 from .native import BIN_PATH, LIB_PATH, NativeLibraryMissing, load
 
 __all__ = [
@@ -35,6 +36,11 @@ __all__ = [
     "band_align_host",
     "band_align_gpu",
     "stage_band_stats",
+    "HIT_FRAME_INFO_DTYPE",
+    "frame_align",
+    "frame_align_host",
+    "frame_cigar",
+    "stage_frame_stats",
     "db_chunk_cuts",
     "synth",
     "run_cli",

@@ -189,8 +189,9 @@ def traceback_path_host(query_seqs, L, db, score_matrix, query_ids, db_ends, bas
 BAND_SOURCE_DTYPE = np.dtype([("first_record", "<u4"), ("stride", "<u4"), ("tiles", "<u4"), ("letters", "<u4")])
 
 
-def _band_call(fn, head, src, diagonal, s_lo, s_hi, W, step, band, open_gap, extend_gap):
-    """Both band entry points take the same tail: the size call, then the words."""
+def _band_call(fn, head, src, diagonal, s_lo, s_hi, W, step, band, open_gap, extend_gap, *more):
+    """The band and frame entry points take the same tail: the size call, then
+    the words. more: what follows extend_gap (the frame pass's shift cost)."""
     srcs = np.ascontiguousarray(src, dtype=BAND_SOURCE_DTYPE)
     diag = np.ascontiguousarray(diagonal, dtype=np.int32)
     lo = np.ascontiguousarray(s_lo, dtype=np.uint32)
@@ -204,7 +205,7 @@ def _band_call(fn, head, src, diagonal, s_lo, s_hi, W, step, band, open_gap, ext
     def call(ops, cap, used):
         rc = fn(*head, n, srcs.ctypes.data_as(ctypes.POINTER(native.GhostmBandSource)),
                 diag.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), lo.ctypes.data_as(u32p), hi.ctypes.data_as(u32p),
-                int(W), int(step), int(band), int(open_gap), int(extend_gap),
+                int(W), int(step), int(band), int(open_gap), int(extend_gap), *more,
                 rec.ctypes.data_as(ctypes.POINTER(native.GhostmHitPath)), ops, cap, ctypes.byref(used))
         if rc != 0:
             raise GhostmError(native.last_error())
@@ -248,6 +249,54 @@ def stage_band_stats() -> dict:
     lib = native.load()
     st = native.GhostmBandStats()
     lib.GhostmStageBandStats(ctypes.byref(st), ctypes.sizeof(st))
+    return {n: getattr(st, n) for n, _ in st._fields_}
+
+
+# GhostmHitFrameInfo: one per hit beside Session.hits_frame()'s records
+HIT_FRAME_INFO_DTYPE = np.dtype([("strand", "<u4"), ("read_nt", "<u4"), ("letters", "<u4"), ("shifts", "<u4")])
+# the operations of a frame path's words: PATH_OPS and the two shifts
+FRAME_OPS = "=XID\\/"
+
+
+def frame_cigar(ops) -> str:
+    """The CIGAR of one hit's frame-path words as -y 13 prints it, for instance
+    30=1\\29= ('\\': the next codon starts one nucleotide late, '/': early)."""
+    return "".join(f"{int(w) >> 4}{FRAME_OPS[int(w) & 7]}" for w in ops)
+
+
+def frame_align_host(query_seqs, W, db, score_matrix, src, diagonal, s_lo, s_hi, step, band=31,
+                     open_gap=-11, extend_gap=-1, shift_cost=-15):
+    """The host model of the frameshift-aware read-level pass
+    (GhostmFrameAlignHost; no device). Arguments as band_align_host, with src
+    naming frame 0 of each hit's strand (its frames g in records first_record +
+    g + stride * t), and the frameshift cost. Returns (records[HIT_PATH_DTYPE]
+    in strand positions, ops[uint32] with the op codes 0..5)."""
+    lib = native.load()
+    qs = np.ascontiguousarray(query_seqs, dtype=np.uint8).reshape(-1)
+    dbs = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
+    m = np.ascontiguousarray(score_matrix, dtype=np.int32).reshape(-1)
+    if m.size != 32 * 32 or W <= 0 or qs.size % W:
+        raise ValueError("frame_align_host: bad argument shapes")
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    head = (qs.ctypes.data_as(u8p), qs.size // W, int(W), dbs.ctypes.data_as(u8p), dbs.size,
+            m.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+    return _band_call(lib.GhostmFrameAlignHost, head, src, diagonal, s_lo, s_hi, W, step, band, open_gap, extend_gap,
+                      int(shift_cost))
+
+
+def frame_align(src, diagonal, s_lo, s_hi, W, step, band=31, open_gap=-11, extend_gap=-1, shift_cost=-15):
+    """FrameAlignGpu on the chunks of SetQueryGpu / SetDbGpu; arguments and
+    result as frame_align_host."""
+    lib = native.load()
+    return _band_call(lib.FrameAlignGpu, (), src, diagonal, s_lo, s_hi, W, step, band, open_gap, extend_gap,
+                      int(shift_cost))
+
+
+def stage_frame_stats() -> dict:
+    """The frame counters behind the stage-level calls (GhostmStageFrameStats)."""
+    lib = native.load()
+    st = native.GhostmFrameStats()
+    lib.GhostmStageFrameStats(ctypes.byref(st), ctypes.sizeof(st))
     return {n: getattr(st, n) for n, _ in st._fields_}
 
 
@@ -694,6 +743,60 @@ class Session:
             raise GhostmError(f"band: half-width {b} outside 1..31")
         if native.load().GhostmSessionSetBand(self._h, b) != 0:
             raise GhostmError(native.last_error())
+
+    def hits_frame(self) -> tuple[np.ndarray, np.ndarray]:
+        """(records, ops): one frameshift-aware read-level HIT_PATH_DTYPE record
+        per hit of hits() (GhostmSessionHitsFrame) and the run-length words they
+        index (GhostmSessionFrameOps; op codes 0..5, frame_cigar() prints
+        them), after a run with any -y on a DNA set of a tiled setter. q_start
+        / q_end are strand positions in nucleotides."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        n = lib.GhostmSessionHitsFrame(self._h, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        rec = np.zeros(n, dtype=HIT_PATH_DTYPE)
+        if n:
+            lib.GhostmSessionHitsFrame(self._h, rec.ctypes.data_as(ctypes.POINTER(native.GhostmHitPath)), n)
+        return rec, self.frame_ops()
+
+    def frame_ops(self) -> np.ndarray:
+        """The run-length words of hits_frame()'s records (GhostmSessionFrameOps)."""
+        lib = native.load()
+        m = lib.GhostmSessionFrameOps(self._h, None, 0)
+        if m == ctypes.c_size_t(-1).value:
+            raise GhostmError(native.last_error())
+        ops = np.zeros(m, dtype=np.uint32)
+        if m:
+            lib.GhostmSessionFrameOps(self._h, ops.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), m)
+        return ops
+
+    def frame_info(self) -> np.ndarray:
+        """One HIT_FRAME_INFO_DTYPE record per hit (GhostmSessionFrameInfo):
+        strand, the read's kept nucleotides, the frames' letters, the shifts."""
+        lib = native.load()
+        n = lib.GhostmSessionFrameInfo(self._h, None, 0)
+        if n == ctypes.c_size_t(-1).value:
+            raise GhostmError(native.last_error())
+        info = np.zeros(n, dtype=HIT_FRAME_INFO_DTYPE)
+        if n:
+            lib.GhostmSessionFrameInfo(self._h, info.ctypes.data_as(ctypes.POINTER(native.GhostmHitFrameInfo)), n)
+        return info
+
+    def set_frame_shift(self, shift_cost: int) -> None:
+        """The frameshift cost of hits_frame(), -(1 << 20)..0 (default -15). A
+        refusal leaves the old value; a change drops the kept frame results."""
+        v = int(shift_cost)
+        if not -(1 << 31) <= v < 1 << 31:  # beyond the C argument's range
+            raise GhostmError(f"shift: frameshift cost {v} outside -(1 << 20)..0")
+        if native.load().GhostmSessionSetFrameShift(self._h, v) != 0:
+            raise GhostmError(native.last_error())
+
+    def frame_stats(self) -> dict:
+        """The frame pass's counters since the last run (GhostmSessionFrameStats)."""
+        st = native.GhostmFrameStats()
+        native.load().GhostmSessionFrameStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        return {name: getattr(st, name) for name, _ in st._fields_}
 
     def hits_rows(self) -> tuple[np.ndarray, np.ndarray]:
         """(records, rows): one HIT_ROWS_DTYPE record per hit of hits()

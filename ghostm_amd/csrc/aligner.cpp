@@ -20,6 +20,7 @@
 #include <thread>
 
 #include "band_align.h"
+#include "frame_align.h"
 #include "common.h"
 #include "db_set.h"
 #include "query_set.h"
@@ -225,8 +226,9 @@ AlignerOptions ParseAlignerOptions(int argc, char **argv) {
   // small inputs); the oracle honours the same variable
   if (const char *e = getenv("GHOSTM_MAX_LIST_OVERRIDE")) o.max_list_length = (uint32_t)strtoul(e, nullptr, 10);
   o.matrix = ReadScoreMatrix(matrix_file);
-  // 6 to 9 and 12: style 0's E-value and bit score; 10 and 11 (the pile-up) print none, like 1 and 2
-  if (o.output_style == 0 || (o.output_style >= 6 && o.output_style <= 9) || o.output_style == 12) {
+  // 6 to 9, 12 and 13: style 0's E-value and bit score; 10 and 11 (the pile-up) print none, like 1 and 2
+  if (o.output_style == 0 || (o.output_style >= 6 && o.output_style <= 9) || o.output_style == 12 ||
+      o.output_style == 13) {
     // extension: GHOSTM_KARLIN=ungapped prices combinations the
     // reference's table lacks with the matrix's ungapped ideal parameters
     // (karlin_params.cpp); unset, they throw as the reference does
@@ -1489,7 +1491,8 @@ static size_t StreamPiecesPerWorker() {
 const LineFormat &Session::Format() {
   // -y 6 formats style-0 lines first: FormatTabular takes their identity,
   // E-value and bit-score bytes
-  const bool tabular = (opt_.output_style >= 6 && opt_.output_style <= 9) || opt_.output_style == 12;
+  const bool tabular =
+      (opt_.output_style >= 6 && opt_.output_style <= 9) || opt_.output_style == 12 || opt_.output_style == 13;
   // -y 10 and -y 11 replace the hit lines after the run: style 1's lines, which need no E-value, stand in
   const bool pileup = opt_.output_style == 10 || opt_.output_style == 11;
   if (!format_) format_.reset(new LineFormat(tabular ? 0 : pileup ? 1 : opt_.output_style, opt_.karlin, 4095));
@@ -1819,6 +1822,7 @@ void Session::SetBand(uint32_t band) {
   hits_band_.clear();
   band_ops_.clear();
   hits_band_valid_ = false;
+  DropFrameResults();  // the frame pass runs inside the same band
 }
 
 // The read-level path of every final hit (HitsBand). The record HitsExt()
@@ -1903,6 +1907,173 @@ const std::vector<GhostmHitPath> &Session::HitsBand() {
 const std::vector<uint32_t> &Session::BandOps() {
   HitsBand();
   return band_ops_;
+}
+
+void Session::DropFrameResults() {
+  hits_frame_.clear();
+  frame_ops_.clear();
+  frame_info_.clear();
+  hits_frame_valid_ = false;
+}
+
+void Session::SetFrameShift(int shift) {
+  if (shift > 0 || shift < kFrameShiftMin)
+    throw Error("shift: frameshift cost " + std::to_string(shift) + " outside -(1 << 20)..0");
+  if (shift == frame_shift_) return;
+  frame_shift_ = shift;
+  DropFrameResults();
+}
+
+// The frame path of every final hit (HitsFrame). The record HitsExt() resolved
+// for a hit is a tile of frame f of a read: its strand is f / 3, and the strand
+// source begins f % 3 records before the frame's own first record (the six
+// frames of a tile are consecutive records). The anchor is HitsBand's: the
+// first cell of the tile path, a codon diagonal. One FrameAlign call per (query
+// chunk, DB chunk).
+const std::vector<GhostmHitPath> &Session::HitsFrame() {
+  if (hits_frame_valid_) return hits_frame_;
+  if (tile_table_.empty() || !tile_dna_)
+    throw Error("frame align: the query set is not a DNA set made by a tiled setter");
+  const std::vector<GhostmHitPath> &path = HitsPath();
+  const std::vector<GhostmHit> &hits = Hits();
+  hits_frame_.assign(hits.size(), GhostmHitPath{0, 0, 0, 0, 0, 0, 0});
+  frame_info_.assign(hits.size(), GhostmHitFrameInfo{0, 0, 0, 0});
+  frame_ops_.clear();
+  const std::vector<std::vector<size_t>> groups = HitsByChunkPair();
+  DeviceModule &dev = DeviceModule::Get();
+  const DeviceTimes before = dev.times();
+  std::vector<GhostmBandSource> src;
+  std::vector<int32_t> diag;
+  std::vector<uint32_t> lo, hi;
+  std::vector<GhostmHitPath> rec;
+  std::vector<std::vector<uint32_t>> words(groups.size());
+  ForChunkPairs(groups, [&](size_t qi, size_t di, const std::vector<size_t> &items) {
+    const QueryData &q = queries_[qi];
+    const DbData &d = dbs_[di];
+    const uint32_t W = q.chunk.L, step = tile_step_;
+    src.clear();
+    diag.clear();
+    lo.clear();
+    hi.clear();
+    for (size_t h : items) {
+      const uint32_t local = hit_source_[h].query;
+      const GhostmQueryTile &t = tile_table_[q.global_base + local];
+      const uint32_t m = std::max(t.letters, 1u), tiles = TileCount(m, W, step);
+      const uint32_t index = t.offset == TileStart(tiles - 1, tiles, m, W, step) ? tiles - 1 : t.offset / step;
+      const uint32_t back = index * 6 + t.frame % 3;
+      if (back > local) throw Error("frame align: a tile before its chunk's first record");
+      const uint32_t subject = hits[h].db_id - d.global_base, pos = d.chunk.starts[subject];
+      src.push_back(GhostmBandSource{local - back, 6, tiles, m});
+      diag.push_back((int32_t)((int64_t)pos + path[h].s_start - ((int64_t)t.offset + path[h].q_start)));
+      lo.push_back(pos);
+      hi.push_back(pos + SubjectLength(d, subject) - 1);
+      frame_info_[h] = GhostmHitFrameInfo{t.frame / 3, tile_read_nt_[t.record], m, 0};
+    }
+    const uint32_t n = (uint32_t)items.size();
+    rec.resize(n);
+    dev.FrameAlign(q.dev, d.dev, n, src.data(), diag.data(), lo.data(), hi.data(), step, band_, opt_.open_gap,
+                   opt_.extend_gap, frame_shift_, rec.data(), &words[qi * dbs_.size() + di]);
+    for (uint32_t k = 0; k < n; ++k) {
+      GhostmHitPath p = rec[k];
+      p.s_start -= lo[k];
+      p.s_end -= lo[k];
+      hits_frame_[items[k]] = p;  // ops_offset: still within the chunk pair's words
+    }
+  });
+  // the words in hit order, and every path's shifts
+  for (size_t h = 0; h < hits.size(); ++h) {
+    GhostmHitPath &p = hits_frame_[h];
+    const std::vector<uint32_t> &w = words[hit_source_[h].qi * dbs_.size() + hit_source_[h].di];
+    const size_t at = frame_ops_.size();
+    frame_ops_.insert(frame_ops_.end(), w.begin() + p.ops_offset, w.begin() + p.ops_offset + p.n_runs);
+    p.ops_offset = at;
+    for (size_t r = at; r < frame_ops_.size(); ++r)
+      if ((frame_ops_[r] & 15u) >= 4) frame_info_[h].shifts += frame_ops_[r] >> 4;
+  }
+  const DeviceTimes &after = dev.times();
+  frame_stats_.seconds_frame += after.frame - before.frame;
+  frame_stats_.frame_launches += after.frame_launches - before.frame_launches;
+  frame_stats_.frame_hits += after.frame_hits - before.frame_hits;
+  frame_stats_.frame_cells += after.frame_cells - before.frame_cells;
+  frame_stats_.frame_dir_bytes += after.frame_dir_bytes - before.frame_dir_bytes;
+  hits_frame_valid_ = true;
+  return hits_frame_;
+}
+
+const std::vector<uint32_t> &Session::FrameOps() {
+  HitsFrame();
+  return frame_ops_;
+}
+
+const std::vector<GhostmHitFrameInfo> &Session::FrameInfo() {
+  HitsFrame();
+  return frame_info_;
+}
+
+// -y 13: FormatPathTabular's line from the hit's frame path (HitsFrame) in read
+// nucleotide coordinates, then qframe and frameshifts. A hit of frame score 0
+// prints its tile path in the same units, with the style-0 line's E-value and
+// bit score.
+void Session::FormatFrameTabular() {
+  const std::vector<GhostmHitPath> &frame_path = HitsFrame();
+  const std::vector<GhostmHitPath> &tile_path = HitsPath();
+  const LineFormat &w = Format();
+  RewriteLines("frame tabular output", 8, [](size_t, size_t n) { return n * 80; },
+               [&](size_t hit, const std::string &in, size_t pos, size_t, const size_t *tab, std::string &out) {
+    const bool framed = frame_path[hit].score > 0;
+    const GhostmHitPath &x = framed ? frame_path[hit] : tile_path[hit];
+    const std::vector<uint32_t> &ops = framed ? frame_ops_ : path_ops_;
+    const GhostmHitFrameInfo &info = frame_info_[hit];
+    uint32_t count[4] = {0, 0, 0, 0}, gap_runs = 0;
+    for (uint32_t r = 0; r < x.n_runs; ++r) {
+      const uint32_t word = ops[x.ops_offset + r], op = word & 15u;
+      if (op >= 4) continue;  // a shift is no column
+      count[op] += word >> 4;
+      gap_runs += op >= 2;
+    }
+    const uint32_t length = count[0] + count[1] + count[2] + count[3];
+    out.append(in, pos, tab[7] + 1 - pos);
+    char num[200], *p = num;
+    p = w.PutId(p, length, count[0]); *p++ = '\t';
+    p = PutU32(p, length); *p++ = '\t';
+    p = PutU32(p, count[1]); *p++ = '\t';
+    p = PutU32(p, gap_runs); *p++ = '\t';
+    // strand positions of the first and the last nucleotide
+    uint32_t q0 = x.q_start, q1 = x.q_end;
+    if (!framed) {
+      const GhostmQueryTile &t = tile_table_[queries_[hit_source_[hit].qi].global_base + hit_source_[hit].query];
+      q0 = 3 * (t.offset + x.q_start) + t.frame % 3;
+      q1 = 3 * (t.offset + x.q_end) + t.frame % 3 + 2;
+    }
+    p = PutU32(p, info.strand ? info.read_nt - q0 : q0 + 1); *p++ = '\t';
+    p = PutU32(p, info.strand ? info.read_nt - q1 : q1 + 1); *p++ = '\t';
+    p = PutU32(p, x.s_start + 1); *p++ = '\t';
+    p = PutU32(p, x.s_end + 1); *p++ = '\t';
+    if (framed) {
+      const uint32_t m = info.letters;
+      const float scaled = (float)((uint64_t)m * (uint64_t)db_sum_u32_) * w.ev.p.K;
+      p = w.PutEvalue(p, m, x.score, scaled); *p++ = '\t';
+      p = w.PutBits(p, x.score);
+      out.append(num, (size_t)(p - num));
+    } else {
+      out.append(num, (size_t)(p - num));
+      out.append(in, tab[2] + 1, tab[0] - tab[2] - 1);
+    }
+    out.push_back('\t');
+    for (uint32_t r = 0; r < x.n_runs; ++r) {
+      const uint32_t word = ops[x.ops_offset + r];
+      p = PutU32(num, word >> 4);
+      *p++ = "=XID\\/"[word & 7u];
+      out.append(num, (size_t)(p - num));
+    }
+    p = num;
+    *p++ = '\t';
+    if (info.strand) *p++ = '-';
+    p = PutU32(p, q0 % 3 + 1); *p++ = '\t';
+    p = PutU32(p, framed ? info.shifts : 0u);
+    *p++ = '\n';
+    out.append(num, (size_t)(p - num));
+  });
 }
 
 // A subject's residues: every subject of a chunk is followed by one END.
@@ -2312,6 +2483,7 @@ void Session::DropResults() {
   band_letters_.clear();
   band_ops_.clear();
   hits_band_valid_ = false;
+  DropFrameResults();
   pileup_subj_.clear();
   pileup_depth_.clear();
   pileup_depth_.shrink_to_fit();
@@ -2329,8 +2501,8 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  // -y 6 to -y 12 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup), not while the search runs
-  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 12;
+  // -y 6 to -y 13 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup), not while the search runs
+  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 13;
   if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
@@ -2359,6 +2531,7 @@ void Session::Run(bool stream_to_file) {
   dev.ResetTimes();
   stats_ = GhostmStats{};
   band_stats_ = GhostmBandStats{};
+  frame_stats_ = GhostmFrameStats{};
   QueryStats();
   merge_epoch_ = 0;
   DropResults();
@@ -2398,7 +2571,8 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    if (opt_.output_style == 12) FormatPathTabular(true);
+    if (opt_.output_style == 13) FormatFrameTabular();
+    else if (opt_.output_style == 12) FormatPathTabular(true);
     else if (opt_.output_style >= 10) FormatPileup();
     else if (opt_.output_style == 6) FormatTabular();
     else FormatPathTabular();
@@ -2578,6 +2752,7 @@ void Session::DropQueries() {
   for (QueryData &q : queries_) dev.Free(q.dev);
   queries_.clear();
   tile_table_.clear();  // a tiled set's table goes with the set
+  tile_read_nt_.clear();
   tile_step_ = 0;
   shard_begin_ = 0;
   shard_end_ = UINT64_MAX;
@@ -2783,6 +2958,8 @@ void Session::AddQueryChunkTiled(const QueryRecordView *recs, uint32_t n, uint32
   q.global_base = queries_.empty() ? 0 : queries_.back().global_base + queries_.back().chunk.nseq;
   if ((uint64_t)q.global_base + q.chunk.nseq > UINT32_MAX) throw Error("set queries: over 4 G tile records");
   tile_table_.insert(tile_table_.end(), table.begin(), table.end());
+  tile_read_nt_.resize(std::max<size_t>(tile_read_nt_.size(), (size_t)record_base + n));
+  std::copy(len.begin(), len.end(), tile_read_nt_.begin() + record_base);
   format_seconds_ += seconds;
   ++format_launches_;
   queries_.push_back(std::move(q));

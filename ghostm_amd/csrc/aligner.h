@@ -253,6 +253,20 @@ class Session {
   void SetBand(uint32_t band);
   uint32_t Band() const { return band_; }
   const GhostmBandStats &BandStats() const { return band_stats_; }
+  // One frameshift-aware read-level GhostmHitPath per hit of Hits(), the words
+  // they index and a GhostmHitFrameInfo each (include/ghostm_hip.h,
+  // FrameAlignGpu): a post-pass of DeviceModule::FrameAlign, one call per (query
+  // chunk, DB chunk) that has hits. A hit's source is the strand of the frame
+  // its resolved record is a tile of, its subject range the whole subject, its
+  // anchor HitsBand's D; q_* are strand positions, s_* relative to the subject.
+  // Throws on a set that is not a DNA set of a tiled setter. Computed on first
+  // use, kept until the next run, query set, database, SetBand or SetFrameShift.
+  const std::vector<GhostmHitPath> &HitsFrame();
+  const std::vector<uint32_t> &FrameOps();
+  const std::vector<GhostmHitFrameInfo> &FrameInfo();
+  // the frameshift cost, -(1 << 20)..0 (default -15); a change drops the frame results
+  void SetFrameShift(int shift);
+  const GhostmFrameStats &FrameStats() const { return frame_stats_; }
   // The subject pile-up of the last run's hits (include/ghostm_hip.h): one
   // GhostmSubjectPileup per subject over all DB chunks in db_id order, and the
   // subjects' depth, identities and consensus concatenated without the END
@@ -407,6 +421,9 @@ class Session {
   // -y 7: the same with columns 3 to 10 taken from the hit's path, and its CIGAR
   // -y 12 (read_level): ... from the hit's read-level path where its score is above 0
   void FormatPathTabular(bool read_level = false);
+  // -y 13: the -y 7 columns from the hit's frame path in read nucleotide
+  // coordinates, then qframe and frameshifts
+  void FormatFrameTabular();
   // -y 8: the -y 7 line plus positives, the query row and the subject row;
   // -y 9: the pairwise view (a '#' line of the first fourteen columns, the
   // three rows, an empty line). Both rewrite the -y 7 text of FormatPathTabular.
@@ -462,6 +479,14 @@ class Session {
   uint32_t tile_step_ = 0;  // a tiled set's step; 0 on an untiled set
   bool tile_dna_ = false;   // ... whether its sources are DNA frames (tiles six records apart)
   GhostmBandStats band_stats_{};
+  std::vector<uint32_t> tile_read_nt_;  // a tiled set's kept letters (nt for DNA) by source record
+  std::vector<GhostmHitPath> hits_frame_;
+  std::vector<uint32_t> frame_ops_;
+  std::vector<GhostmHitFrameInfo> frame_info_;
+  bool hits_frame_valid_ = false;
+  int frame_shift_ = -15;
+  GhostmFrameStats frame_stats_{};
+  void DropFrameResults();
   std::vector<GhostmSubjectPileup> pileup_subj_;
   std::vector<uint32_t> pileup_depth_, pileup_ident_;
   std::vector<uint8_t> pileup_cons_;

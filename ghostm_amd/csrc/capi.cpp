@@ -453,6 +453,66 @@ size_t GhostmSessionBandStats(void *s, GhostmBandStats *stats, size_t size) {
   return sizeof(GhostmBandStats);
 }
 
+size_t GhostmSessionHitsFrame(void *s, GhostmHitPath *rec, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmHitPath> &h = static_cast<Session *>(s)->HitsFrame();
+    if (!rec) return h.size();
+    const size_t n = std::min(cap, h.size());
+    std::memcpy(rec, h.data(), n * sizeof(GhostmHitPath));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionFrameOps(void *s, uint32_t *ops, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<uint32_t> &w = static_cast<Session *>(s)->FrameOps();
+    if (!ops) return w.size();
+    const size_t n = std::min(cap, w.size());
+    std::memcpy(ops, w.data(), n * sizeof(uint32_t));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionFrameInfo(void *s, GhostmHitFrameInfo *info, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmHitFrameInfo> &h = static_cast<Session *>(s)->FrameInfo();
+    if (!info) return h.size();
+    const size_t n = std::min(cap, h.size());
+    std::memcpy(info, h.data(), n * sizeof(GhostmHitFrameInfo));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+int GhostmSessionSetFrameShift(void *s, int shift_cost) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetFrameShift(shift_cost);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionFrameStats(void *s, GhostmFrameStats *stats, size_t size) {
+  if (!s || !stats) return 0;
+  const GhostmFrameStats st = static_cast<Session *>(s)->FrameStats();
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmFrameStats)));
+  return sizeof(GhostmFrameStats);
+}
+
 size_t GhostmSessionHitsRows(void *s, GhostmHitRows *rec, size_t cap) {
   try {
     if (!s) throw Error("null session");
@@ -582,11 +642,12 @@ int GhostmSearchMain(int argc, char **argv) {
   bool dna = false, have_d = false, tiled = false, have_x = false;
   std::string db_fasta;
   uint32_t db_k = 4, db_mb = 0, band = 0;  // band 0: the session's default
+  long shift_cost = -1;                    // -F; below 0: the session's default
   optind = 1;
   opterr = 1;
   int c;
-  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B
-  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:")) >= 0) {
+  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B, -F
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:")) >= 0) {
     switch (c) {
       case 'T':  // reads longer than the width as overlapping tiles, this many letters apart
         tiled = true;
@@ -601,6 +662,13 @@ int GhostmSearchMain(int argc, char **argv) {
         const long v = strtol(optarg, &end, 10);
         if (end == optarg || *end || v < 1 || v > 31) return 1;
         band = (uint32_t)v;
+        break;
+      }
+      case 'F': {  // the frameshift cost of -y 13, 0..1 << 20
+        char *end = nullptr;
+        const long v = strtol(optarg, &end, 10);
+        if (end == optarg || *end || v < 0 || v > (1 << 20)) return 1;
+        shift_cost = v;
         break;
       }
       case 'f': db_fasta = optarg; break;
@@ -639,6 +707,7 @@ int GhostmSearchMain(int argc, char **argv) {
     Session &session = *made;
     if (!have_d) session.SetDbFasta(db_fasta, db_k, db_mb);
     if (band) session.SetBand(band);
+    if (shift_cost >= 0) session.SetFrameShift(-(int)shift_cost);
     for (size_t k = 0; k < pos.size(); k += 2) {
       try {
         { std::ofstream touch(pos[k + 1].c_str()); }

@@ -110,6 +110,8 @@ struct DeviceTimes {
   double band = 0;                                // the read-level band pass (k_band_fill + k_band_walk + k_band_compact):
   uint64_t band_launches = 0, band_hits = 0, band_cells = 0, band_dir_bytes = 0;  // seconds, batches, hits,
                                                   // rows run x (2B + 1), direction bytes
+  double frame = 0;                               // the frame pass (k_frame_fill + k_frame_walk + k_frame_compact),
+  uint64_t frame_launches = 0, frame_hits = 0, frame_cells = 0, frame_dir_bytes = 0;  // counted as the band pass
 };
 
 class DeviceModule {
@@ -343,6 +345,15 @@ class DeviceModule {
                  const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B, int open, int ext,
                  GhostmHitPath *rec, std::vector<uint32_t> *ops);
 
+  // The frameshift-aware read-level alignment (kern::k_frame_fill,
+  // k_frame_walk, k_frame_compact): BandAlign with strand sources (src[i] names
+  // frame 0 of a strand; ValidateFrame, frame_align.h) and the frameshift cost
+  // `shift`. Buffers of its own, the budget GHOSTM_FRAME_SCRATCH_MB, the cap
+  // GHOSTM_FRAME_BATCH_HITS, and the frame_* fields of times().
+  void FrameAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBandSource *src, const int32_t *D,
+                  const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B, int open, int ext, int shift,
+                  GhostmHitPath *rec, std::vector<uint32_t> *ops);
+
   DeviceTimes &times() {
     SettleSeedTime();
     return times_;
@@ -355,6 +366,10 @@ class DeviceModule {
   DeviceModule() = default;
   // span: runs of slots whose hits may pair (a name group's slots)
   void LaunchTraceback(kern::TbArgs a, DevQuery *q, uint32_t n, const DevDb *d, uint32_t span);
+  // BandAlign (frame false, shift unused) and FrameAlign
+  void BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32_t n, const GhostmBandSource *src, const int32_t *D,
+                const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B, int open, int ext,
+                GhostmHitPath *rec, std::vector<uint32_t> *ops);
   int device_ = -1;
   void *stream_ = nullptr;
   HostCopyFn host_copy_;

@@ -14,6 +14,7 @@
 
 #include "../../include/ghostm_hip.h"
 #include "band_align.h"
+#include "frame_align.h"
 #include "common.h"
 #include "device.h"
 #include "formats.h"
@@ -288,6 +289,8 @@ struct DeviceModule::Impl {
   DevBuf pileup_hit, pileup_ops, pileup_list, pileup_part, pileup_prof, pileup_out, pileup_cols;
   // BandAlign: a batch's slots, its offsets / maxima / records, its direction bytes, its word slots, their packed words
   DevBuf band_hit, band_meta, band_dir, band_ops, band_cmp;
+  // FrameAlign: the same five of its own
+  DevBuf frame_hit, frame_meta, frame_dir, frame_ops, frame_cmp;
   DevBuf tb_width, tb_ncols, tb_skey, tb_key, tb_order1, tb_order2, tb_sort, tb_pair_a, tb_pair_b, tb_best;
   int cus = 256;
   // K4 work
@@ -2613,13 +2616,42 @@ static_assert(sizeof(kern::BandHit) == 48, "BandHit is uploaded as 48-byte recor
 void DeviceModule::BandAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBandSource *src, const int32_t *D,
                              const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B, int open, int ext,
                              GhostmHitPath *rec, std::vector<uint32_t> *ops) {
+  BandPass(false, 0, q, d, n, src, D, s_lo, s_hi, step, B, open, ext, rec, ops);
+}
+
+void DeviceModule::FrameAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBandSource *src, const int32_t *D,
+                              const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B, int open, int ext,
+                              int shift, GhostmHitPath *rec, std::vector<uint32_t> *ops) {
+  BandPass(true, shift, q, d, n, src, D, s_lo, s_hi, step, B, open, ext, rec, ops);
+}
+
+// Both read-level passes: the band pass, and the frame pass (frame: the rows
+// are the three nucleotide rows of every codon row, the kernels k_frame_*, and
+// buffers, limits and counters of its own).
+void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32_t n, const GhostmBandSource *src,
+                            const int32_t *D, const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B,
+                            int open, int ext, GhostmHitPath *rec, std::vector<uint32_t> *ops) {
   Use();
   Impl &I = *impl_;
   if (ops) ops->clear();
   if (n == 0) return;
   // every index the kernels will use, checked here: nothing is uploaded or launched for a refused call
-  const std::string why = ValidateBand(q->nseq, q->L, d->len, n, src, s_lo, s_hi, step, B, open, ext);
-  if (!why.empty()) throw Error("band align: " + why);
+  const std::string why = frame ? ValidateFrame(q->nseq, q->L, d->len, n, src, s_lo, s_hi, step, B, open, ext, shift)
+                                : ValidateBand(q->nseq, q->L, d->len, n, src, s_lo, s_hi, step, B, open, ext);
+  const std::string what = frame ? "frame align: " : "band align: ";
+  if (!why.empty()) throw Error(what + why);
+  DevBuf &b_hit = frame ? I.frame_hit : I.band_hit, &b_meta = frame ? I.frame_meta : I.band_meta;
+  DevBuf &b_dir = frame ? I.frame_dir : I.band_dir, &b_ops = frame ? I.frame_ops : I.band_ops;
+  DevBuf &b_cmp = frame ? I.frame_cmp : I.band_cmp;
+  // a hit's rows run (BandRowRange's codon rows three times in the frame pass), direction bytes and word slot
+  const auto Rows = [&](uint32_t codon_rows) { return frame ? 3 * codon_rows : codon_rows; };
+  const auto DirBytes = [&](uint32_t codon_rows) {
+    return frame ? FrameDirBytes(3 * codon_rows, B) : BandDirBytes(codon_rows, B);
+  };
+  const auto OpsSlot = [&](uint32_t codon_rows) {
+    return frame ? FrameOpsSlot(3 * codon_rows, B) : BandOpsSlot(codon_rows, B);
+  };
+  double &t_seconds = frame ? times_.frame : times_.band;
   // every hit's rows and the launch order by them, a stable sort: hits of about equal rows share a block
   std::vector<BandRows> rows(n);
   std::vector<uint32_t> order(n);
@@ -2629,8 +2661,8 @@ void DeviceModule::BandAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBand
   }
   std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return rows[x].rows < rows[y].rows; });
   const uint32_t stride = BandDirStride(B);
-  const size_t budget = EnvSize("GHOSTM_BAND_SCRATCH_MB", 1024) << 20;
-  const size_t max_hits = EnvSize("GHOSTM_BAND_BATCH_HITS", SIZE_MAX);
+  const size_t budget = EnvSize(frame ? "GHOSTM_FRAME_SCRATCH_MB" : "GHOSTM_BAND_SCRATCH_MB", 1024) << 20;
+  const size_t max_hits = EnvSize(frame ? "GHOSTM_FRAME_BATCH_HITS" : "GHOSTM_BAND_BATCH_HITS", SIZE_MAX);
   std::vector<std::vector<uint32_t>> batch_words;
   std::vector<uint32_t> hit_batch(ops ? n : 0), hit_runs(n), h_rec;
   std::vector<uint64_t> hit_at(ops ? n : 0);
@@ -2641,7 +2673,7 @@ void DeviceModule::BandAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBand
     size_t bytes = 0;
     const uint32_t b1 = CutBatch(
         b0, n, max_hits, budget,
-        [&](uint32_t s) { return BandDirBytes(rows[order[s]].rows, B) + 4 * BandOpsSlot(rows[order[s]].rows, B); }, &bytes);
+        [&](uint32_t s) { return DirBytes(rows[order[s]].rows) + 4 * OpsSlot(rows[order[s]].rows); }, &bytes);
     const uint32_t m = b1 - b0;
     hh.resize(m);
     off.resize(m);
@@ -2652,19 +2684,19 @@ void DeviceModule::BandAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBand
       hh[s] = kern::BandHit{src[k].first_record, src[k].stride, src[k].tiles, src[k].letters, D[k], s_lo[k], s_hi[k],
                             rows[k].i_top,       rows[k].rows,  0,            dir_bytes};
       off[s] = ops_words;
-      dir_bytes += BandDirBytes(rows[k].rows, B);
-      ops_words += BandOpsSlot(rows[k].rows, B);
-      cells += (uint64_t)rows[k].rows * (2 * B + 1);
+      dir_bytes += DirBytes(rows[k].rows);
+      ops_words += OpsSlot(rows[k].rows);
+      cells += (uint64_t)Rows(rows[k].rows) * (2 * B + 1);
     }
     // meta: ops_off[m], cmp_off[m] (u64), best[3m], rec[6m]
-    I.band_hit.Reserve((size_t)m * sizeof(kern::BandHit));
-    I.band_meta.Reserve((size_t)m * 16 + (size_t)m * 36);
-    I.band_dir.Reserve(std::max<size_t>(dir_bytes, 1));
-    I.band_ops.Reserve(std::max<size_t>(ops_words, 1) * 4);
-    unsigned long long *d_off = I.band_meta.as<unsigned long long>();
+    b_hit.Reserve((size_t)m * sizeof(kern::BandHit));
+    b_meta.Reserve((size_t)m * 16 + (size_t)m * 36);
+    b_dir.Reserve(std::max<size_t>(dir_bytes, 1));
+    b_ops.Reserve(std::max<size_t>(ops_words, 1) * 4);
+    unsigned long long *d_off = b_meta.as<unsigned long long>();
     uint32_t *d_best = reinterpret_cast<uint32_t *>(d_off + 2 * (size_t)m);
     uint32_t *d_rec = d_best + 3 * (size_t)m;
-    HIP_CHECK(hipMemcpyAsync(I.band_hit.p, hh.data(), (size_t)m * sizeof(kern::BandHit), hipMemcpyHostToDevice, S(stream_)));
+    HIP_CHECK(hipMemcpyAsync(b_hit.p, hh.data(), (size_t)m * sizeof(kern::BandHit), hipMemcpyHostToDevice, S(stream_)));
     HIP_CHECK(hipMemcpyAsync(d_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
     kern::BandArgs a{};
     a.qseq = q->seq.as<uint8_t>();
@@ -2672,39 +2704,45 @@ void DeviceModule::BandAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBand
     a.step = step;
     a.db = d->Residues();
     a.mat = I.mat_raw.as<int>();
-    a.hit = I.band_hit.as<kern::BandHit>();
+    a.hit = b_hit.as<kern::BandHit>();
     a.n = m;
     a.B = B;
     a.stride = stride;
     a.open = open;
     a.ext = ext;
-    a.dir = I.band_dir.as<uint8_t>();
+    a.dir = b_dir.as<uint8_t>();
     a.best = d_best;
     a.ops_off = d_off;
-    a.ops = I.band_ops.as<uint32_t>();
+    a.ops = b_ops.as<uint32_t>();
     a.rec = d_rec;
     const dim3 block(kern::kTbBlock);
     const dim3 wave_grid((m + kern::kTbBlock / 64 - 1) / (kern::kTbBlock / 64));  // one wave per slot
     const dim3 lane_grid((m + kern::kTbBlock - 1) / kern::kTbBlock);              // one lane per slot
     TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
-      hipLaunchKernelGGL(kern::k_band_fill, wave_grid, block, 0, S(stream_), a);
-      HIP_CHECK(hipGetLastError());
-      hipLaunchKernelGGL(kern::k_band_walk, lane_grid, block, 0, S(stream_), a);
+      if (frame) {
+        hipLaunchKernelGGL(kern::k_frame_fill, wave_grid, block, 0, S(stream_), (kern::FrameArgs{a, shift}));
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(kern::k_frame_walk, lane_grid, block, 0, S(stream_), (kern::FrameArgs{a, shift}));
+      } else {
+        hipLaunchKernelGGL(kern::k_band_fill, wave_grid, block, 0, S(stream_), a);
+        HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(kern::k_band_walk, lane_grid, block, 0, S(stream_), a);
+      }
     });
     h_rec.resize((size_t)m * 6);
     HIP_CHECK(hipMemcpyAsync(h_rec.data(), d_rec, (size_t)m * 24, hipMemcpyDeviceToHost, S(stream_)));
     HIP_CHECK(hipStreamSynchronize(S(stream_)));
-    times_.band += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-    times_.band_launches += 1;
-    times_.band_hits += m;
-    times_.band_cells += cells;
-    times_.band_dir_bytes += dir_bytes;
+    t_seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+    (frame ? times_.frame_launches : times_.band_launches) += 1;
+    (frame ? times_.frame_hits : times_.band_hits) += m;
+    (frame ? times_.frame_cells : times_.band_cells) += cells;
+    (frame ? times_.frame_dir_bytes : times_.band_dir_bytes) += dir_bytes;
     // the scan of the compaction: every slot's first word in the packed array
     size_t packed = 0;
     for (uint32_t s = 0; s < m; ++s) {
       const uint32_t hit = order[b0 + s];
       const uint32_t *r = h_rec.data() + (size_t)s * 6;
-      if (r[5] > BandOpsSlot(rows[hit].rows, B)) throw Error("band align: a hit's runs exceed its slot");
+      if (r[5] > OpsSlot(rows[hit].rows)) throw Error(what + "a hit's runs exceed its slot");
       if (rec) rec[hit] = GhostmHitPath{r[0], r[1], r[2], r[3], r[4], r[5], 0};
       hit_runs[hit] = r[5];
       off[s] = packed;
@@ -2717,16 +2755,19 @@ void DeviceModule::BandAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBand
     if (ops) {
       batch_words.emplace_back(packed);
       if (packed) {
-        I.band_cmp.Reserve(packed * 4);
+        b_cmp.Reserve(packed * 4);
         HIP_CHECK(hipMemcpyAsync(d_off + m, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
         a.cmp_off = d_off + m;
-        a.cmp = I.band_cmp.as<uint32_t>();
+        a.cmp = b_cmp.as<uint32_t>();
         TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
-          hipLaunchKernelGGL(kern::k_band_compact, wave_grid, block, 0, S(stream_), a);
+          if (frame)
+            hipLaunchKernelGGL(kern::k_frame_compact, wave_grid, block, 0, S(stream_), (kern::FrameArgs{a, shift}));
+          else
+            hipLaunchKernelGGL(kern::k_band_compact, wave_grid, block, 0, S(stream_), a);
         });
         HIP_CHECK(hipMemcpyAsync(batch_words.back().data(), a.cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
         HIP_CHECK(hipStreamSynchronize(S(stream_)));
-        times_.band += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+        t_seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
       }
     }
     b0 = b1;
@@ -2890,7 +2931,7 @@ const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_pileup/k_pileup_finish/k_band_fill/k_band_walk/k_band_compact, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_pileup/k_pileup_finish/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -3359,6 +3400,46 @@ size_t GhostmStageBandStats(GhostmBandStats *stats, size_t size) {
   const GhostmBandStats st{dt.band, dt.band_launches, dt.band_hits, dt.band_cells, dt.band_dir_bytes};
   std::memcpy(stats, &st, std::min(size, sizeof(GhostmBandStats)));
   return sizeof(GhostmBandStats);
+}
+
+int FrameAlignGpu(uint32_t nhits, const GhostmBandSource src[], const int32_t diagonal[], const uint32_t s_lo[],
+                  const uint32_t s_hi[], uint32_t query_sequence_length, uint32_t step, uint32_t band, int open_gap,
+                  int extend_gap, int shift_cost, GhostmHitPath rec[], uint32_t ops[], size_t ops_cap,
+                  size_t *ops_used) {
+  try {
+    if (!ops_used) throw Error("FrameAlignGpu: null: ops_used");
+    if (nhits && (!src || !diagonal || !s_lo || !s_hi)) throw Error("FrameAlignGpu: null: an input array");
+    if (nhits == 0) {
+      *ops_used = 0;
+      return 0;
+    }
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    if (!r.query || !r.db) throw Error("SetQueryGpu/SetDbGpu not called");
+    if (query_sequence_length != r.query->L) throw Error("FrameAlignGpu: source: query shape differs from SetQueryGpu");
+    std::vector<GhostmHitPath> out(nhits);
+    std::vector<uint32_t> words;
+    DeviceModule::Get().FrameAlign(r.query, r.db, nhits, src, diagonal, s_lo, s_hi, step, band, open_gap, extend_gap,
+                                   shift_cost, out.data(), &words);
+    if (ops && words.size() > ops_cap) throw Error("FrameAlignGpu: ops_cap: the operations do not fit");
+    if (rec) std::copy(out.begin(), out.end(), rec);
+    if (ops) std::copy(words.begin(), words.end(), ops);
+    *ops_used = words.size();
+    return 0;
+  } catch (std::exception &e) {
+    SetError(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmStageFrameStats(GhostmFrameStats *stats, size_t size) {
+  if (!stats) return 0;
+  RefState &r = Ref();
+  std::lock_guard<std::mutex> lk(r.mu);
+  const DeviceTimes &dt = DeviceModule::Get().times();
+  const GhostmFrameStats st{dt.frame, dt.frame_launches, dt.frame_hits, dt.frame_cells, dt.frame_dir_bytes};
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmFrameStats)));
+  return sizeof(GhostmFrameStats);
 }
 
 int PathPileupGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPath rec[], const uint32_t ops[],

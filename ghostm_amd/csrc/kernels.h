@@ -5040,5 +5040,218 @@ __global__ __launch_bounds__(kTbBlock) void k_band_compact(BandArgs a) {
   for (uint32_t k = lane; k < n; k += 64) dst[k] = src[k];
 }
 
+// ------------------------------------------------------------------ frameshift-aware read-level alignment
+// k_frame_fill + k_frame_walk + k_frame_compact: the frame path of every hit
+// (FrameAlignGpu, include/ghostm_hip.h; host model frame_align_host.cpp). The
+// band kernels' structure with rows that are strand positions p = 3c + g of one
+// strand's three frames: one wave per hit, lane b = j - c - D + B owns one
+// codon diagonal, so a lane's column j = c + D - B + b is the same in the three
+// rows of a codon and moves by one between codons. The lane keeps its H of rows
+// p+1 .. p+4 and its F of rows p+1 .. p+3 in registers. In row p, by g = p % 3
+// (the rows of a codon are unrolled, g is a constant in each):
+//   H(p+3, j+1)             the lane's own H3 (one codon up, same diagonal)
+//   H(p+3, j), F(p+3, j)    lane b-1's H3, F3 (DPP wave_shr)
+//   H(p+2, j+1)             g = 0: row p+2 is in this codon, lane b+1's H2
+//                           (shuffle down, 0 past the wave); else the lane's own
+//   H(p+4, j+1)             g = 2: row p+4 is two codons up, lane b-1's H4
+//                           (DPP wave_shr, lane 0 reads 0); else the lane's own
+// A lane whose cell is no band cell carries H = 0, E = F = kBandNeg, and rows
+// at or past 3m and above the rows run are the registers' initial values: the
+// model's neighbour values. The E chain, eext / fext, the best-cell reduction
+// (value, p, lane) and the direction bytes are k_band_fill's; bits 5-6 of a byte
+// hold fsel. A codon's three letters q(3c), q(3c+1), q(3c+2) are byte c of the
+// frames' records, W bytes apart: the tile arithmetic runs once per codon, and
+// they and db[j] are loaded one codon ahead. BandHit.i_top / rows are the codon
+// rows c_top / codons; the rows run are 3 * codons, p_top = 3 * c_top + 2.
+// k_frame_walk adds the shift ops 5 ('/', to p+2) and 4 ('\', to p+4) after a
+// pair column whose fsel is 1 / 2. The host has checked every index
+// (ValidateFrame, frame_align.h).
+struct FrameArgs {
+  BandArgs band;
+  int shift;  // <= 0
+};
+
+// the letters of codon c of the three frames: g's in bits 8g .. 8g+4
+__device__ __forceinline__ uint32_t FrameLetters(const uint8_t *qseq, const BandHit &h, uint32_t c, uint32_t W,
+                                                 uint32_t step) {
+  const uint32_t t = min(c / step, h.tiles - 1);
+  const uint32_t start = t + 1 < h.tiles ? t * step : (h.letters > W ? h.letters - W : 0u);
+  const uint32_t rec = h.first_record + (h.tiles > 1 ? h.stride * t : 0u);
+  const uint8_t *q = qseq + (size_t)rec * W + (c - start);
+  return (q[0] & 31u) | (q[W] & 31u) << 8 | (q[2 * (size_t)W] & 31u) << 16;
+}
+
+__global__ __launch_bounds__(kTbBlock) void k_frame_fill(FrameArgs fa) {
+  GHOSTM_POISON_LDS();
+  const BandArgs &a = fa.band;
+  __shared__ int s_mat[32 * 32];
+  for (uint32_t e = threadIdx.x; e < 32 * 32; e += kTbBlock) s_mat[e] = a.mat[e];
+  __syncthreads();
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t slot = blockIdx.x * (kTbBlock / 64) + (threadIdx.x >> 6);
+  if (slot >= a.n) return;  // the whole wave
+  const BandHit hit = a.hit[slot];
+  const int B = (int)a.B;
+  int best = 0;
+  uint32_t best_p = 0;
+  if (hit.rows) {
+    // this lane's column in codon row c is c + j0; it is a band cell for c in [vlo, vhi]
+    const long long j0 = (long long)hit.D - B + (long long)lane;
+    const long long c_bot = (long long)hit.i_top - (long long)hit.rows + 1;
+    long long vlo = (long long)hit.s_lo - j0, vhi = (long long)hit.s_hi - j0;
+    if (lane > 2u * a.B) vhi = -1, vlo = 0;  // never
+    const int lo = (int)min(max(vlo, c_bot), (long long)hit.i_top + 1);
+    const int hi = (int)max(min(vhi, (long long)hit.i_top), c_bot - 1);
+    const uint8_t *dbp = a.db + j0;  // dbp[c] is the lane's residue in codon row c (read only where valid)
+    uint8_t *dir = a.dir + hit.dir_off + lane;
+    const bool writes = lane < a.stride;
+    int H1 = 0, H2 = 0, H3 = 0, H4 = 0, F1 = kBandNeg, F2 = kBandNeg, F3 = kBandNeg;
+    int c = (int)hit.i_top;
+    uint32_t qn = FrameLetters(a.qseq, hit, (uint32_t)c, a.W, a.step);
+    uint32_t dn = c >= lo && c <= hi ? dbp[c] & 31u : 0u;
+    size_t row = 0;
+    for (uint32_t k = 0; k < hit.rows; ++k, --c) {
+      const uint32_t q3 = qn;
+      const int *mrow = s_mat + dn * 32;
+      const uint32_t dc = dn;
+      const bool valid = c >= lo && c <= hi;
+      if (k + 1 < hit.rows) {  // the next codon's letters
+        qn = FrameLetters(a.qseq, hit, (uint32_t)(c - 1), a.W, a.step);
+        dn = c - 1 >= lo && c - 1 <= hi ? dbp[c - 1] & 31u : 0u;
+      }
+#pragma unroll
+      for (int g = 2; g >= 0; --g, ++row) {
+        const uint32_t qc = (q3 >> (8 * g)) & 31u;
+        int Hb = (int)ShiftUp((uint32_t)H3), Fb = (int)ShiftUp((uint32_t)F3);
+        if (lane == 0) Fb = kBandNeg;  // (Hb is 0 there: bound_ctrl)
+        const int d1 = (g == 0 ? BandShiftDown(H2, 1, lane, 0) : H2) + fa.shift;
+        const int d2 = (g == 2 ? (int)ShiftUp((uint32_t)H4) : H4) + fa.shift;
+        int diag = H3;
+        uint32_t fsel = 0;
+        if (d1 > diag) { diag = d1; fsel = 1; }
+        if (d2 > diag) { diag = d2; fsel = 2; }
+        const int s = diag + mrow[qc];
+        const int fe = Fb + a.ext, fo = Hb + a.open;
+        const int F = max(fe, fo);
+        const int Hh = valid ? max(max(s, F), 0) : 0;
+        // the E chain: E(b) = max over b' > b of Hh(b') + open + ext * (b' - b - 1)
+        int E = BandShiftDown(Hh + a.open, 1, lane, kBandNeg);
+        for (uint32_t d = 1; d <= 2u * a.B; d <<= 1) E = max(E, BandShiftDown(E, d, lane, kBandNeg) + a.ext * (int)d);
+        int cell = 0;
+        uint32_t bits = 0;
+        if (s > 0) { cell = s; bits = 1; }
+        if (E > cell) { cell = E; bits = 2; }
+        if (F > cell) { cell = F; bits = 3; }
+        const int Hc = valid ? cell : 0, Ec = valid ? E : kBandNeg;
+        const int Er = BandShiftDown(Ec, 1, lane, kBandNeg), Hr = BandShiftDown(Hc, 1, lane, 0);
+        bits |= (Er + a.ext > Hr + a.open ? 4u : 0u) | (fe > fo ? 8u : 0u) | (dc == qc ? 16u : 0u) | fsel << 5;
+        if (writes) dir[row * a.stride] = valid ? (uint8_t)bits : (uint8_t)0;
+        if (Hc > best) {
+          best = Hc;
+          best_p = 3u * (uint32_t)c + (uint32_t)g;
+        }
+        H4 = H3;
+        H3 = H2;
+        H2 = H1;
+        H1 = Hc;
+        F3 = F2;
+        F2 = F1;
+        F1 = valid ? F : kBandNeg;
+      }
+    }
+  }
+  // the first strict maximum in processing order: largest value, then largest p, then largest lane
+  uint32_t bl = lane;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const int ov = __shfl_xor(best, d);
+    const uint32_t op = (uint32_t)__shfl_xor((int)best_p, d), ol = (uint32_t)__shfl_xor((int)bl, d);
+    if (ov > best || (ov == best && (op > best_p || (op == best_p && ol > bl)))) {
+      best = ov;
+      best_p = op;
+      bl = ol;
+    }
+  }
+  if (lane == 0) {
+    uint32_t *o = a.best + 3 * (size_t)slot;
+    o[0] = best > 0 ? best_p : 0u;
+    o[1] = best > 0 ? (uint32_t)((long long)(best_p / 3) + hit.D - B + (long long)bl) : hit.s_lo;
+    o[2] = (uint32_t)best;
+  }
+}
+
+__global__ __launch_bounds__(kTbBlock) void k_frame_walk(FrameArgs fa) {
+  GHOSTM_POISON_LDS();
+  const BandArgs &a = fa.band;
+  const uint32_t slot = blockIdx.x * kTbBlock + threadIdx.x;
+  if (slot >= a.n) return;
+  const BandHit hit = a.hit[slot];
+  const uint8_t *dir = a.dir + hit.dir_off;
+  uint32_t *out = a.ops + a.ops_off[slot];
+  const uint32_t cap = hit.rows ? 3 * hit.rows + 4 * a.B + 4 : 0;
+  const uint32_t bp = a.best[3 * (size_t)slot], bj = a.best[3 * (size_t)slot + 1], score = a.best[3 * (size_t)slot + 2];
+  long long p = bp, j = bj;
+  const long long p_top = 3ll * hit.i_top + 2, p_bot = p_top - 3ll * hit.rows + 1;
+  uint32_t nruns = 0, cur = 0, len = 0;
+  auto emit = [&](uint32_t op) {
+    if (len && op != cur) {
+      if (nruns < cap) out[nruns++] = len << 4 | cur;
+      len = 0;
+    }
+    cur = op;
+    ++len;
+  };
+  if (score > 0) {
+    int state = 0;
+    // every iteration emits an operation or changes to a gap state that emits in the next one
+    for (uint32_t it = 0; it < 2 * cap + 2; ++it) {
+      // the band cells (inside them the row is one of the rows run, so p >= 0)
+      if (p > p_top || p < p_bot || p >= 3ll * hit.letters || j > (long long)hit.s_hi) break;
+      const long long b = j - p / 3 - hit.D + (long long)a.B;
+      if (b < 0 || b > 2ll * a.B) break;
+      const uint32_t d = dir[(size_t)(p_top - p) * a.stride + (size_t)b];
+      if (state == 0) {
+        const uint32_t sel = d & 3u;
+        if (sel == 0) break;
+        if (sel != 1) { state = sel == 2 ? 1 : 2; continue; }
+        emit((d & 16u) ? 0u : 1u);
+        const uint32_t fsel = (d >> 5) & 3u;
+        if (fsel == 1) emit(5u);
+        if (fsel == 2) emit(4u);
+        p += fsel == 1 ? 2 : fsel == 2 ? 4 : 3;
+        ++j;
+      } else if (state == 1) {
+        emit(3u);
+        state = (d & 4u) ? 1 : 0;
+        ++j;
+      } else {
+        emit(2u);
+        state = (d & 8u) ? 2 : 0;
+        p += 3;
+      }
+    }
+    if (len && nruns < cap) out[nruns++] = len << 4 | cur;
+  }
+  uint32_t *r = a.rec + 6 * (size_t)slot;
+  r[0] = bp;
+  r[1] = score > 0 ? (uint32_t)(p - 1) : bp;
+  r[2] = bj;
+  r[3] = score > 0 ? (uint32_t)(j - 1) : bj;
+  r[4] = score;
+  r[5] = nruns;
+}
+
+__global__ __launch_bounds__(kTbBlock) void k_frame_compact(FrameArgs fa) {
+  GHOSTM_POISON_LDS();
+  const BandArgs &a = fa.band;
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t slot = blockIdx.x * (kTbBlock / 64) + (threadIdx.x >> 6);
+  if (slot >= a.n) return;
+  const uint32_t n = a.rec[6 * (size_t)slot + 5];
+  const uint32_t *src = a.ops + a.ops_off[slot];
+  uint32_t *dst = a.cmp + a.cmp_off[slot];
+  for (uint32_t k = lane; k < n; k += 64) dst[k] = src[k];
+}
+
 }  // namespace kern
 }  // namespace ghostm

@@ -38,6 +38,7 @@ static int Usage() {
             << "       [-T tileStep [-X maxReadLength]]: reads longer than the record width searched as\n"
             << "        overlapping tiles tileStep letters apart, each read first cut at maxReadLength\n"
             << "       [-B band]: the half-width of -y 12's band around a hit's diagonal, 1..31 (default 31)\n"
+            << "       [-F cost]: the frameshift cost of -y 13 (tiled DNA reads), 0 or more (default 15)\n"
             << "synth: ghostm synth -d db.fasta -q queries.fasta [-n nq] [-N dbResidues] [-s seed]\n";
   return 1;
 }

@@ -102,6 +102,29 @@ class GhostmBandStats(ctypes.Structure):
     ]
 
 
+class GhostmFrameStats(ctypes.Structure):
+    """the counters of the frame pass (GhostmSessionFrameStats, GhostmStageFrameStats)."""
+
+    _fields_ = [
+        ("seconds_frame", ctypes.c_double),
+        ("frame_launches", c_uint64),
+        ("frame_hits", c_uint64),
+        ("frame_cells", c_uint64),
+        ("frame_dir_bytes", c_uint64),
+    ]
+
+
+class GhostmHitFrameInfo(ctypes.Structure):
+    """what GhostmSessionFrameInfo tells about a hit's frame path (16 bytes)."""
+
+    _fields_ = [
+        ("strand", c_uint32),
+        ("read_nt", c_uint32),
+        ("letters", c_uint32),
+        ("shifts", c_uint32),
+    ]
+
+
 class GhostmHitRows(ctypes.Structure):
     """the aligned rows of one hit (32 bytes): the record the path lies in, its
     counts and its 3 * columns bytes rows[rows_offset:] (query row, midline,
@@ -280,6 +303,14 @@ SIGNATURES = {
                                     u32p, c_uint32, c_uint32, c_uint32, c_int, c_int, POINTER(GhostmHitPath), u32p,
                                     c_size_t, POINTER(c_size_t)]),
     "GhostmStageBandStats": (c_size_t, [POINTER(GhostmBandStats), c_size_t]),
+    "FrameAlignGpu": (c_int, [c_uint32, POINTER(GhostmBandSource), POINTER(ctypes.c_int32), u32p, u32p, c_uint32,
+                              c_uint32, c_uint32, c_int, c_int, c_int, POINTER(GhostmHitPath), u32p, c_size_t,
+                              POINTER(c_size_t)]),
+    "GhostmFrameAlignHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, POINTER(ctypes.c_uint8), c_uint32,
+                                     POINTER(c_int), c_uint32, POINTER(GhostmBandSource), POINTER(ctypes.c_int32),
+                                     u32p, u32p, c_uint32, c_uint32, c_uint32, c_int, c_int, c_int,
+                                     POINTER(GhostmHitPath), u32p, c_size_t, POINTER(c_size_t)]),
+    "GhostmStageFrameStats": (c_size_t, [POINTER(GhostmFrameStats), c_size_t]),
     "GhostmBuildIndexGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, u32p, u32p, u32p, c_int,
                                     POINTER(c_float)]),
     "GhostmFormatQueriesGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_uint32,
@@ -330,6 +361,11 @@ SIGNATURES = {
     "GhostmSessionBandOps": (c_size_t, [c_void_p, u32p, c_size_t]),
     "GhostmSessionSetBand": (c_int, [c_void_p, c_uint32]),
     "GhostmSessionBandStats": (c_size_t, [c_void_p, POINTER(GhostmBandStats), c_size_t]),
+    "GhostmSessionHitsFrame": (c_size_t, [c_void_p, POINTER(GhostmHitPath), c_size_t]),
+    "GhostmSessionFrameOps": (c_size_t, [c_void_p, u32p, c_size_t]),
+    "GhostmSessionFrameInfo": (c_size_t, [c_void_p, POINTER(GhostmHitFrameInfo), c_size_t]),
+    "GhostmSessionSetFrameShift": (c_int, [c_void_p, c_int]),
+    "GhostmSessionFrameStats": (c_size_t, [c_void_p, POINTER(GhostmFrameStats), c_size_t]),
     "GhostmSessionHitsRows": (c_size_t, [c_void_p, POINTER(GhostmHitRows), c_size_t]),
     "GhostmSessionRowBytes": (c_size_t, [c_void_p, POINTER(ctypes.c_uint8), c_size_t]),
     "GhostmSessionPileup": (c_size_t, [c_void_p, POINTER(GhostmSubjectPileup), c_size_t]),

@@ -680,6 +680,112 @@ typedef struct GhostmBandStats {
  * bytes and returns the library's sizeof; 0 on a null argument. */
 size_t GhostmStageBandStats(GhostmBandStats *stats, size_t size);
 
+/* Frameshift-aware read-level alignments of DNA reads. BandAlignGpu aligns one
+ * frame; after a single-nucleotide insertion or deletion the true alignment of
+ * a read continues in another frame of the same strand, and this pass follows
+ * it there for a cost.
+ *
+ * A strand source is one strand of a DNA read: its three frames g = 0, 1, 2
+ * (tile-table frames 3 x strand + g), each of m letters (the tile table's
+ * letters, n / 3). It is described by a GhostmBandSource with one added rule:
+ * first_record is tile 0 of frame g = 0 of that strand, and letter c of frame g
+ * lies in record first_record + g + stride * t, with t, the tile start and the
+ * byte within the tile as in BandAlignGpu; stride is ignored when tiles == 1.
+ * The read's strand position is p = 3c + g, 0 <= p < 3m, and its letter q(p) is
+ * letter p / 3 of frame p % 3: letter t of the frame at offset o covers strand
+ * positions o + 3t .. o + 3t + 2 (the reverse strand counted from the read's
+ * last kept nucleotide), which is how the tiled setters lay the frames out.
+ *
+ * Per hit: the source, the subject range [s_lo, s_hi] (absolute in the chunk,
+ * END-free), the anchor diagonal D in letters, the half-width B (1..31), open,
+ * ext and the frameshift cost shift <= 0. The band cells are (p, j) with
+ * 0 <= p < 3m, s_lo <= j <= s_hi and |j - floor(p / 3) - D| <= B. All
+ * arithmetic is int32. The DP runs in reverse, rows p = 3m-1 .. 0 and j
+ * descending within a row:
+ *   d0 = H(p+3, j+1)            in frame
+ *   d1 = H(p+2, j+1) + shift    the next codon starts one nucleotide early
+ *   d2 = H(p+4, j+1) + shift    the next codon starts one nucleotide late
+ *   diag = d0, fsel = 0; if d1 > diag: diag = d1, fsel = 1; if d2 > diag:
+ *          diag = d2, fsel = 2 (each strict, in that order)
+ *   s      = diag + M[(db[j] & 31) * 32 + (q(p) & 31)]
+ *   E(p,j) = max(E(p,j+1) + ext, H(p,j+1) + open)    'D'
+ *   F(p,j) = max(F(p+3,j) + ext, H(p+3,j) + open)    'I': one codon against a gap
+ *   H(p,j) = s if s > 0 else 0; then E if E > H; then F if F > H (hsel 1 / 0,
+ *            2, 3, as BandAlignGpu)
+ *   eext   = E(p,j+1) + ext > H(p,j+1) + open (a tie opens); fext likewise
+ *            with (p+3, j)
+ * A neighbour that is no band cell has H = 0 and E = F = minus infinity. The
+ * start cell is the first strict maximum in processing order (the largest p,
+ * then the largest j). The walk: in H state with hsel 1 it emits '=' or 'X'
+ * (the two codes masked with 31 are equal or not); if fsel is 1 it then emits
+ * op 5 ('/') and goes to (p+2, j+1), if fsel is 2 op 4 ('\') and goes to
+ * (p+4, j+1), otherwise it goes to (p+3, j+1). hsel 2 / 3 enter E / F at the
+ * same cell; E emits 'D' and goes to (p, j+1), F emits 'I' and goes to
+ * (p+3, j), both staying in the gap state while eext / fext. hsel 0 or leaving
+ * the band cells stops. The run-length words keep the len << 4 | op encoding
+ * with the two new op codes 4 and 5; the paths of every other call never
+ * contain them. The result is a GhostmHitPath: q_start is the strand position
+ * of the first codon's first nucleotide, q_end the last nucleotide consumed,
+ * s_* absolute. Score 0 gives an empty path at q_start = 0, s_start = s_lo.
+ *
+ * Three consequences:
+ *   A shift never ends a path: it is taken only if d1 or d2 beats d0 >= 0, so
+ *   the cell stepped to is a band cell with H > 0 and the walk emits there.
+ *   Two shift ops are never adjacent: a shift follows a pair column only.
+ *   The row's E chain is still exact as a max-plus scan, under open <= ext <=
+ *   0: E depends on the same row only, exactly as in BandAlignGpu.
+ * With shift = -(1 << 20), and scores below 1 << 20, no shift is ever taken
+ * and the score is the maximum over g of BandAlignGpu's on frame g with the
+ * same D, B and range.
+ *
+ * FrameAlignGpu: stage level like BandAlignGpu, whose arguments it takes plus
+ * shift_cost; the NULL / cap convention and the refusals are BandAlignGpu's
+ * (a frame's record outside the chunk is "source"), plus
+ *   "shift"   shift_cost > 0 or shift_cost < -(1 << 20)
+ * A refused call leaves rec, ops and *ops_used untouched. One wave runs one
+ * hit (kernels k_frame_fill + k_frame_walk + k_frame_compact), lane b = j -
+ * floor(p / 3) - D + B, over the nucleotide rows of the codon rows BandAlignGpu
+ * would run: p from 3 x c_top + 2 down to 3 x c_bot. A hit's direction buffer
+ * is rows x ((2B + 1 + 3) & ~3) bytes, bits 5-6 of a byte holding fsel; its
+ * words number at most rows + 4B + 4. The hits are sorted by rows and cut into
+ * batches that fit GHOSTM_FRAME_SCRATCH_MB (default 1024) and hold at most
+ * GHOSTM_FRAME_BATCH_HITS hits (default: no limit). */
+int FrameAlignGpu(uint32_t nhits, const GhostmBandSource src[], const int32_t diagonal[],
+                  const uint32_t s_lo[], const uint32_t s_hi[], uint32_t query_sequence_length,
+                  uint32_t step, uint32_t band, int open_gap, int extend_gap, int shift_cost,
+                  GhostmHitPath rec[], uint32_t ops[], size_t ops_cap, size_t *ops_used);
+
+/* The same on the host, with no device call: the model the kernels equal byte
+ * for byte in records and words, run cell by cell. Arguments as
+ * GhostmBandAlignHost plus shift_cost. */
+int GhostmFrameAlignHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, const uint8_t *db, uint32_t db_len,
+                         const int score_matrix[], uint32_t nhits, const GhostmBandSource src[],
+                         const int32_t diagonal[], const uint32_t s_lo[], const uint32_t s_hi[],
+                         uint32_t query_sequence_length, uint32_t step, uint32_t band, int open_gap,
+                         int extend_gap, int shift_cost, GhostmHitPath rec[], uint32_t ops[], size_t ops_cap,
+                         size_t *ops_used);
+
+/* The counters of the frame pass, a struct of their own like GhostmBandStats. */
+typedef struct GhostmFrameStats {
+  double seconds_frame;      /* k_frame_fill + k_frame_walk + k_frame_compact, device time */
+  uint64_t frame_launches;   /* batches of hits */
+  uint64_t frame_hits;
+  uint64_t frame_cells;      /* sum over the hits of rows run x (2B + 1) */
+  uint64_t frame_dir_bytes;  /* direction-buffer bytes the batches addressed */
+} GhostmFrameStats;
+
+/* The frame counters behind the stage-level calls; GhostmStageBandStats'
+ * conventions. */
+size_t GhostmStageFrameStats(GhostmFrameStats *stats, size_t size);
+
+/* What GhostmSessionFrameInfo tells about a hit's frame path. */
+typedef struct GhostmHitFrameInfo {
+  uint32_t strand;   /* 0 forward, 1 reverse complement */
+  uint32_t read_nt;  /* the read's kept nucleotides n */
+  uint32_t letters;  /* m = n / 3, the letters of each frame */
+  uint32_t shifts;   /* the summed length of the path's shift runs */
+} GhostmHitFrameInfo;
+
 /* A session without a database: `aln`'s options without -d (giving it is an
  * error). With -i the query chunks are loaded as GhostmSessionCreate loads
  * them; without -i the session starts with neither input and the queries come
@@ -862,7 +968,18 @@ int GhostmSessionRun(void *session);
  * of the source's m letters (search space m x the database's residues, the
  * reference's float / double steps). A hit whose read-level score is 0 prints
  * its -y 7 line unchanged. Hits are not re-ranked or re-merged by the new
- * scores. Written at the end of the run, like -y 7. */
+ * scores. Written at the end of the run, like -y 7.
+ * -y 13 (DNA sets of a tiled setter only) prints the thirteen -y 7 columns
+ * from the hit's frame path (GhostmSessionHitsFrame) and two more, qframe and
+ * frameshifts: length counts the '=', 'X', 'I' and 'D' columns, mismatch the
+ * 'X', gapopen the runs of 'I' or 'D'; qstart / qend are one-based read
+ * nucleotide coordinates, q_start + 1 and q_end + 1 on the forward strand,
+ * n - q_start and n - q_end on the reverse strand (so qstart > qend there);
+ * the CIGAR writes '\' and '/' for ops 4 and 5; qframe is +-(q_start % 3 + 1);
+ * frameshifts is the summed length of the shift runs; evalue and bitscore are
+ * priced as -y 12 prices them, for a query of m letters. A hit whose frame
+ * score is 0 prints its tile path in the same units (strand positions
+ * 3 x (offset + q) + g, the end + 2, frameshifts 0). Hits are not re-ranked. */
 int GhostmSessionRunToFile(void *session);
 
 /* Formatted output of the last run (reference WriteOutput/V1/V2 text). With
@@ -938,6 +1055,38 @@ int GhostmSessionSetBand(void *session, uint32_t band);
  * results are asked for); the size convention of GhostmSessionDbStats. */
 size_t GhostmSessionBandStats(void *session, GhostmBandStats *stats, size_t size);
 
+/* The frameshift-aware read-level path of every hit of the last run (record i
+ * belongs to hit i) and the run-length words they index, in hit order (the
+ * contract above FrameAlignGpu); the NULL/cap convention of
+ * GhostmSessionHitsBand, (size_t)-1 on error. The query set must be a DNA set
+ * made by a tiled setter (a read of one tile is fine); any other set is an
+ * error. Per hit:
+ *   source   the strand of the hit's resolved tile: frame f of the tile table
+ *            gives strand f / 3, and first_record is the frame's own first
+ *            record minus f % 3
+ *   subject  the whole subject
+ *   anchor   D as GhostmSessionHitsBand computes it, a codon diagonal
+ * q_start / q_end are strand positions (nucleotides; the reverse strand counted
+ * from the read's last kept nucleotide), s_start / s_end relative to the
+ * subject. One FrameAlignGpu-style call per (query chunk, DB chunk) that has
+ * hits, computed on first use and kept until the next run,
+ * GhostmSessionSetQueries*, GhostmSessionSetDb*, a change of band or of the
+ * frameshift cost. Hits are not re-ranked. */
+size_t GhostmSessionHitsFrame(void *session, GhostmHitPath *rec, size_t cap);
+size_t GhostmSessionFrameOps(void *session, uint32_t *ops, size_t cap);
+
+/* One GhostmHitFrameInfo per hit, beside GhostmSessionHitsFrame's records;
+ * the same conventions. */
+size_t GhostmSessionFrameInfo(void *session, GhostmHitFrameInfo *info, size_t cap);
+
+/* The frameshift cost of GhostmSessionHitsFrame: -(1 << 20)..0, default -15.
+ * A refusal (non-zero) leaves the old value; a change drops the kept results. */
+int GhostmSessionSetFrameShift(void *session, int shift_cost);
+
+/* The frame counters of the session since its last run (all 0 until the frame
+ * results are asked for); the size convention of GhostmSessionBandStats. */
+size_t GhostmSessionFrameStats(void *session, GhostmFrameStats *stats, size_t size);
+
 /* The pile-up of the last run's hits on every subject (the definitions above
  * PathPileupGpu), built on the paths of GhostmSessionHitsPath with the record
  * each hit was traced with, so a DNA hit piles up the frame that reproduced
@@ -998,7 +1147,7 @@ void GhostmSessionDestroy(void *session);
 int GhostmAlignMain(int argc, char **argv);
 
 /* `ghostm search [aln options except -i -o -S -L] [-q d|p] [-w maxLength]
- * [-c chunkSizeMB] [-B band] (-d database | -f db.fasta [-k kSize] [-m chunkSizeMB])
+ * [-c chunkSizeMB] [-B band] [-F cost] (-d database | -f db.fasta [-k kSize] [-m chunkSizeMB])
  * q1.fasta out1 [q2.fasta out2 ...]`: one session with the database resident,
  * from its formatted files (-d) or formatted on the device from FASTA (-f, with
  * -k and -m as db's -k and -l: GhostmSessionCreateQueries and one
@@ -1006,7 +1155,9 @@ int GhostmAlignMain(int argc, char **argv);
  * file (-q, -w, -c as qry's -t, -l, -L; qry's warnings on stderr) and searched
  * into the output file, which equals [`ghostm db` +] `ghostm qry` + `ghostm
  * aln` on those files. -B sets the half-width of -y 12's band
- * (GhostmSessionSetBand). Wrong usage (no pairs, an odd number of positionals,
+ * (GhostmSessionSetBand; it applies to -y 13 too), -F the non-negative
+ * frameshift cost of -y 13 (GhostmSessionSetFrameShift with its negative; a
+ * cost that is negative or over 1 << 20 is wrong usage). Wrong usage (no pairs, an odd number of positionals,
  * -i, -o, -S or -L, both or neither of -d and -f, -B outside 1..31) returns 1 before any device
  * call; errors are printed and 0 returned, as GhostmAlignMain. */
 int GhostmSearchMain(int argc, char **argv);
