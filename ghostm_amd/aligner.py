@@ -300,6 +300,75 @@ def stage_frame_stats() -> dict:
     return {n: getattr(st, n) for n, _ in st._fields_}
 
 
+# GhostmHitReadRows: the rows record of a read-level path; HIT_ROWS_DTYPE's
+# fields, then the shift columns
+READ_ROWS_DTYPE = np.dtype(HIT_ROWS_DTYPE.descr + [("shifts", "<u4"), ("pad", "<u4")])
+
+
+def _read_rows_call(fn, head, src, rec, ops, W, step, frame, open_gap, extend_gap, shift_cost):
+    """ReadRowsGpu and GhostmReadRowsHost take the same tail: the size call,
+    then the rows."""
+    srcs = np.ascontiguousarray(src, dtype=BAND_SOURCE_DTYPE)
+    p = np.ascontiguousarray(rec, dtype=HIT_PATH_DTYPE)
+    w = np.ascontiguousarray(ops, dtype=np.uint32)
+    if srcs.shape != p.shape:
+        raise ValueError("read rows: bad argument shapes")
+    n = len(srcs)
+    out = np.zeros(n, dtype=READ_ROWS_DTYPE)
+    u8p, u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+
+    def call(rows, cap, used):
+        rc = fn(*head, n, srcs.ctypes.data_as(ctypes.POINTER(native.GhostmBandSource)),
+                p.ctypes.data_as(ctypes.POINTER(native.GhostmHitPath)), w.ctypes.data_as(u32p), w.size, int(W),
+                int(step), int(bool(frame)), int(open_gap), int(extend_gap), int(shift_cost),
+                out.ctypes.data_as(ctypes.POINTER(native.GhostmHitReadRows)), rows, cap, ctypes.byref(used))
+        if rc != 0:
+            raise GhostmError(native.last_error())
+
+    used = ctypes.c_size_t(0)
+    call(None, 0, used)  # the size needed
+    rows = np.zeros(used.value, dtype=np.uint8)
+    if used.value:
+        call(rows.ctypes.data_as(u8p), used.value, used)
+    return out, rows
+
+
+def read_rows_host(query_seqs, W, db, score_matrix, src, rec, ops, step, frame=False, open_gap=-11, extend_gap=-1,
+                   shift_cost=-15):
+    """The host model of the read-level rows (GhostmReadRowsHost; no device):
+    query_seqs = the chunk's records of W codes, db = the chunk's residues, src
+    = BAND_SOURCE_DTYPE records, rec = HIT_PATH_DTYPE records of band paths
+    (frame False) or frame paths (frame True) with s_start absolute in the
+    chunk, ops = the words they index. Returns (records[READ_ROWS_DTYPE],
+    rows[uint8]); rows_of(rec, rows, h) is hit h's three rows."""
+    lib = native.load()
+    qs = np.ascontiguousarray(query_seqs, dtype=np.uint8).reshape(-1)
+    dbs = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
+    m = np.ascontiguousarray(score_matrix, dtype=np.int32).reshape(-1)
+    if m.size != 32 * 32 or W <= 0 or qs.size % W:
+        raise ValueError("read_rows_host: bad argument shapes")
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    head = (qs.ctypes.data_as(u8p), qs.size // W, int(W), dbs.ctypes.data_as(u8p), dbs.size,
+            m.ctypes.data_as(ctypes.POINTER(ctypes.c_int)))
+    return _read_rows_call(lib.GhostmReadRowsHost, head, src, rec, ops, W, step, frame, open_gap, extend_gap,
+                           shift_cost)
+
+
+def read_rows(src, rec, ops, W, step, frame=False, open_gap=-11, extend_gap=-1, shift_cost=-15):
+    """ReadRowsGpu on the chunks of SetQueryGpu / SetDbGpu; arguments and
+    result as read_rows_host."""
+    lib = native.load()
+    return _read_rows_call(lib.ReadRowsGpu, (), src, rec, ops, W, step, frame, open_gap, extend_gap, shift_cost)
+
+
+def stage_read_rows_stats() -> dict:
+    """The read-rows counters behind the stage-level calls (GhostmStageReadRowsStats)."""
+    lib = native.load()
+    st = native.GhostmReadRowsStats()
+    lib.GhostmStageReadRowsStats(ctypes.byref(st), ctypes.sizeof(st))
+    return {n: getattr(st, n) for n, _ in st._fields_}
+
+
 def query_chunk_cuts(lengths, chunk_mb: int = 0, dna: bool = False) -> np.ndarray:
     """`ghostm qry`'s chunk cuts over records of these letter counts
     (GhostmQueryChunkCuts; no device): chunk c is records [cuts[c], cuts[c + 1]).
@@ -796,6 +865,43 @@ class Session:
         """The frame pass's counters since the last run (GhostmSessionFrameStats)."""
         st = native.GhostmFrameStats()
         native.load().GhostmSessionFrameStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    def _read_rows(self, hits_fn, bytes_fn) -> tuple[np.ndarray, np.ndarray]:
+        bad = ctypes.c_size_t(-1).value
+        n = hits_fn(self._h, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        rec = np.zeros(n, dtype=READ_ROWS_DTYPE)
+        if n:
+            hits_fn(self._h, rec.ctypes.data_as(ctypes.POINTER(native.GhostmHitReadRows)), n)
+        m = bytes_fn(self._h, None, 0)
+        if m == bad:
+            raise GhostmError(native.last_error())
+        rows = np.zeros(m, dtype=np.uint8)
+        if m:
+            bytes_fn(self._h, rows.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), m)
+        return rec, rows
+
+    def hits_band_rows(self) -> tuple[np.ndarray, np.ndarray]:
+        """(records, rows): one READ_ROWS_DTYPE record per hit of hits() for its
+        read-level path (hits_band()) and the row bytes they index
+        (GhostmSessionHitsBandRows, GhostmSessionBandRowBytes), after a run with
+        any -y. rows_of(rec, rows, h) is hit h's three rows."""
+        lib = native.load()
+        return self._read_rows(lib.GhostmSessionHitsBandRows, lib.GhostmSessionBandRowBytes)
+
+    def hits_frame_rows(self) -> tuple[np.ndarray, np.ndarray]:
+        """The same for the frame paths (hits_frame()): the query row holds '\\'
+        and '/' at the frameshifts (GhostmSessionHitsFrameRows,
+        GhostmSessionFrameRowBytes). Refused where hits_frame() is."""
+        lib = native.load()
+        return self._read_rows(lib.GhostmSessionHitsFrameRows, lib.GhostmSessionFrameRowBytes)
+
+    def read_rows_stats(self) -> dict:
+        """The read-rows counters since the last run (GhostmSessionReadRowsStats)."""
+        st = native.GhostmReadRowsStats()
+        native.load().GhostmSessionReadRowsStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
         return {name: getattr(st, name) for name, _ in st._fields_}
 
     def hits_rows(self) -> tuple[np.ndarray, np.ndarray]:

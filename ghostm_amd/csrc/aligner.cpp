@@ -226,9 +226,9 @@ AlignerOptions ParseAlignerOptions(int argc, char **argv) {
   // small inputs); the oracle honours the same variable
   if (const char *e = getenv("GHOSTM_MAX_LIST_OVERRIDE")) o.max_list_length = (uint32_t)strtoul(e, nullptr, 10);
   o.matrix = ReadScoreMatrix(matrix_file);
-  // 6 to 9, 12 and 13: style 0's E-value and bit score; 10 and 11 (the pile-up) print none, like 1 and 2
-  if (o.output_style == 0 || (o.output_style >= 6 && o.output_style <= 9) || o.output_style == 12 ||
-      o.output_style == 13) {
+  // 6 to 9 and 12 to 15: style 0's E-value and bit score; 10 and 11 (the pile-up) print none, like 1 and 2
+  if (o.output_style == 0 || (o.output_style >= 6 && o.output_style <= 9) ||
+      (o.output_style >= 12 && o.output_style <= 15)) {
     // extension: GHOSTM_KARLIN=ungapped prices combinations the
     // reference's table lacks with the matrix's ungapped ideal parameters
     // (karlin_params.cpp); unset, they throw as the reference does
@@ -1492,7 +1492,7 @@ const LineFormat &Session::Format() {
   // -y 6 formats style-0 lines first: FormatTabular takes their identity,
   // E-value and bit-score bytes
   const bool tabular =
-      (opt_.output_style >= 6 && opt_.output_style <= 9) || opt_.output_style == 12 || opt_.output_style == 13;
+      (opt_.output_style >= 6 && opt_.output_style <= 9) || (opt_.output_style >= 12 && opt_.output_style <= 15);
   // -y 10 and -y 11 replace the hit lines after the run: style 1's lines, which need no E-value, stand in
   const bool pileup = opt_.output_style == 10 || opt_.output_style == 11;
   if (!format_) format_.reset(new LineFormat(tabular ? 0 : pileup ? 1 : opt_.output_style, opt_.karlin, 4095));
@@ -1821,7 +1821,9 @@ void Session::SetBand(uint32_t band) {
   band_ = band;
   hits_band_.clear();
   band_ops_.clear();
+  band_src_.clear();
   hits_band_valid_ = false;
+  read_rows_[0].Drop();
   DropFrameResults();  // the frame pass runs inside the same band
 }
 
@@ -1837,6 +1839,7 @@ const std::vector<GhostmHitPath> &Session::HitsBand() {
   const std::vector<GhostmHit> &hits = Hits();
   hits_band_.assign(hits.size(), GhostmHitPath{0, 0, 0, 0, 0, 0, 0});
   band_letters_.assign(hits.size(), 0);
+  band_src_.assign(hits.size(), GhostmBandSource{0, 0, 0, 0});
   band_ops_.clear();
   const std::vector<std::vector<size_t>> groups = HitsByChunkPair();
   DeviceModule &dev = DeviceModule::Get();
@@ -1884,6 +1887,7 @@ const std::vector<GhostmHitPath> &Session::HitsBand() {
       p.s_end -= lo[k];
       hits_band_[items[k]] = p;  // ops_offset: still within the chunk pair's words
       band_letters_[items[k]] = src[k].letters;
+      band_src_[items[k]] = src[k];
     }
   });
   // the words in hit order
@@ -1913,7 +1917,9 @@ void Session::DropFrameResults() {
   hits_frame_.clear();
   frame_ops_.clear();
   frame_info_.clear();
+  frame_src_.clear();
   hits_frame_valid_ = false;
+  read_rows_[1].Drop();
 }
 
 void Session::SetFrameShift(int shift) {
@@ -1938,6 +1944,7 @@ const std::vector<GhostmHitPath> &Session::HitsFrame() {
   const std::vector<GhostmHit> &hits = Hits();
   hits_frame_.assign(hits.size(), GhostmHitPath{0, 0, 0, 0, 0, 0, 0});
   frame_info_.assign(hits.size(), GhostmHitFrameInfo{0, 0, 0, 0});
+  frame_src_.assign(hits.size(), GhostmBandSource{0, 0, 0, 0});
   frame_ops_.clear();
   const std::vector<std::vector<size_t>> groups = HitsByChunkPair();
   DeviceModule &dev = DeviceModule::Get();
@@ -1978,6 +1985,7 @@ const std::vector<GhostmHitPath> &Session::HitsFrame() {
       p.s_start -= lo[k];
       p.s_end -= lo[k];
       hits_frame_[items[k]] = p;  // ops_offset: still within the chunk pair's words
+      frame_src_[items[k]] = src[k];
     }
   });
   // the words in hit order, and every path's shifts
@@ -2008,6 +2016,102 @@ const std::vector<uint32_t> &Session::FrameOps() {
 const std::vector<GhostmHitFrameInfo> &Session::FrameInfo() {
   HitsFrame();
   return frame_info_;
+}
+
+// The read-level rows of every final hit (HitsReadRows): HitsRows' plan with
+// the read-level paths. The hits' column counts give every hit its place in hit
+// order, then one ReadRows call per (query chunk, DB chunk) writes the bytes
+// there, with the source the path pass aligned and the subject coordinates made
+// absolute in the chunk again.
+const std::vector<GhostmHitReadRows> &Session::HitsReadRows(bool frame) {
+  ReadRowsResult &res = read_rows_[frame ? 1 : 0];
+  if (res.valid) return res.rec;
+  const std::vector<GhostmHitPath> &path = frame ? HitsFrame() : HitsBand();
+  const std::vector<uint32_t> &words = frame ? frame_ops_ : band_ops_;
+  const std::vector<GhostmBandSource> &source = frame ? frame_src_ : band_src_;
+  const std::vector<GhostmHit> &hits = Hits();
+  res.rec.assign(hits.size(), GhostmHitReadRows{0, 0, 0, 0, 0, 0, 0, 0, 0});
+  std::vector<uint64_t> place(hits.size());
+  uint64_t total = 0;
+  for (size_t h = 0; h < hits.size(); ++h) {
+    uint64_t cols = 0;
+    for (uint32_t r = 0; r < path[h].n_runs; ++r) cols += words[path[h].ops_offset + r] >> 4;
+    place[h] = total;
+    total += 3 * cols;
+  }
+  res.bytes.assign(total, 0);
+  DeviceModule &dev = DeviceModule::Get();
+  const DeviceTimes before = dev.times();
+  std::vector<GhostmBandSource> src;
+  std::vector<uint64_t> dst;
+  std::vector<GhostmHitPath> rec;
+  std::vector<GhostmHitReadRows> out;
+  ForChunkPairs(HitsByChunkPair(), [&](size_t qi, size_t di, const std::vector<size_t> &items) {
+    src.clear();
+    dst.clear();
+    rec.clear();
+    for (size_t h : items) {
+      GhostmHitPath p = path[h];
+      const uint32_t pos = dbs_[di].chunk.starts[hits[h].db_id - dbs_[di].global_base];
+      p.s_start += pos;
+      p.s_end += pos;
+      src.push_back(source[h]);
+      dst.push_back(place[h]);
+      rec.push_back(p);
+    }
+    out.resize(items.size());
+    const uint32_t W = queries_[qi].chunk.L, step = tile_step_ ? tile_step_ : W;
+    dev.ReadRows(queries_[qi].dev, dbs_[di].dev, (uint32_t)items.size(), src.data(), rec.data(), words.data(),
+                 words.size(), step, frame, opt_.open_gap, opt_.extend_gap, frame_shift_, queries_[qi].global_base,
+                 out.data(), res.bytes.data(), res.bytes.size(), dst.data());
+    for (size_t k = 0; k < items.size(); ++k) res.rec[items[k]] = out[k];
+  });
+  const DeviceTimes &after = dev.times();
+  read_rows_stats_.seconds_read_rows += after.read_rows - before.read_rows;
+  read_rows_stats_.read_rows_launches += after.read_rows_launches - before.read_rows_launches;
+  read_rows_stats_.read_rows_hits += after.read_rows_hits - before.read_rows_hits;
+  read_rows_stats_.read_rows_columns += after.read_rows_columns - before.read_rows_columns;
+  res.valid = true;
+  return res.rec;
+}
+
+const std::vector<uint8_t> &Session::ReadRowBytes(bool frame) {
+  HitsReadRows(frame);
+  return read_rows_[frame ? 1 : 0].bytes;
+}
+
+// -y 14 / -y 15: the -y 12 / -y 13 line, then positives, qseq and sseq: from
+// the hit's read-level rows where its read-level score is above 0 (the line
+// then describes that path), from its tile rows otherwise (the -y 8 fields of
+// the tile path the line describes).
+void Session::FormatReadRows(bool frame) {
+  const std::vector<GhostmHitReadRows> &read = HitsReadRows(frame);
+  const std::vector<uint8_t> &read_bytes = read_rows_[frame ? 1 : 0].bytes;
+  const std::vector<GhostmHitPath> &level = frame ? hits_frame_ : hits_band_;
+  const std::vector<GhostmHitRows> &tile = HitsRows();
+  const std::vector<uint8_t> &tile_bytes = row_bytes_;
+  const auto extra = [&](size_t first, size_t n) {
+    size_t need = n * 16;
+    for (size_t i = 0; i < n; ++i) need += 2 * (size_t)std::max(read[first + i].columns, tile[first + i].columns);
+    return need;
+  };
+  RewriteLines("read rows output", 0, extra,
+               [&](size_t hit, const std::string &in, size_t pos, size_t nl, const size_t *, std::string &out) {
+    const bool lvl = level[hit].score > 0;
+    const size_t n = lvl ? read[hit].columns : tile[hit].columns;
+    const uint32_t positives = lvl ? read[hit].positives : tile[hit].positives;
+    const char *q = reinterpret_cast<const char *>(lvl ? read_bytes.data() + read[hit].rows_offset
+                                                       : tile_bytes.data() + tile[hit].rows_offset);
+    char num[16], *end = PutU32(num, positives);
+    out.append(in, pos, nl - pos);
+    out.push_back('\t');
+    out.append(num, (size_t)(end - num));
+    out.push_back('\t');
+    out.append(q, n);
+    out.push_back('\t');
+    out.append(q + 2 * n, n);
+    out.push_back('\n');
+  });
 }
 
 // -y 13: FormatPathTabular's line from the hit's frame path (HitsFrame) in read
@@ -2482,7 +2586,9 @@ void Session::DropResults() {
   hits_band_.clear();
   band_letters_.clear();
   band_ops_.clear();
+  band_src_.clear();
   hits_band_valid_ = false;
+  read_rows_[0].Drop();
   DropFrameResults();
   pileup_subj_.clear();
   pileup_depth_.clear();
@@ -2501,8 +2607,8 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  // -y 6 to -y 13 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup), not while the search runs
-  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 13;
+  // -y 6 to -y 15 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup, HitsReadRows), not while the search runs
+  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 15;
   if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
@@ -2532,6 +2638,7 @@ void Session::Run(bool stream_to_file) {
   stats_ = GhostmStats{};
   band_stats_ = GhostmBandStats{};
   frame_stats_ = GhostmFrameStats{};
+  read_rows_stats_ = GhostmReadRowsStats{};
   QueryStats();
   merge_epoch_ = 0;
   DropResults();
@@ -2571,12 +2678,13 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    if (opt_.output_style == 13) FormatFrameTabular();
-    else if (opt_.output_style == 12) FormatPathTabular(true);
+    if (opt_.output_style == 13 || opt_.output_style == 15) FormatFrameTabular();
+    else if (opt_.output_style == 12 || opt_.output_style == 14) FormatPathTabular(true);
     else if (opt_.output_style >= 10) FormatPileup();
     else if (opt_.output_style == 6) FormatTabular();
     else FormatPathTabular();
     if (opt_.output_style == 8 || opt_.output_style == 9) FormatRows();
+    if (opt_.output_style == 14 || opt_.output_style == 15) FormatReadRows(opt_.output_style == 15);
     if (stream_to_file) {
       WriteOutputFile();
       streamed_ = true;

@@ -267,6 +267,16 @@ class Session {
   // the frameshift cost, -(1 << 20)..0 (default -15); a change drops the frame results
   void SetFrameShift(int shift);
   const GhostmFrameStats &FrameStats() const { return frame_stats_; }
+  // One GhostmHitReadRows per hit of Hits() and the row bytes they index, in
+  // hit order, for the read-level paths of HitsBand() (frame false) or
+  // HitsFrame() (frame true, with the session's frameshift cost): a post-pass
+  // of DeviceModule::ReadRows, one call per (query chunk, DB chunk) that has
+  // hits, with the sources the path pass used. query_record is a global record
+  // index. Computed on first use and kept as long as the paths they were made
+  // from. With -y 14 / -y 15 Run makes them and the text.
+  const std::vector<GhostmHitReadRows> &HitsReadRows(bool frame);
+  const std::vector<uint8_t> &ReadRowBytes(bool frame);
+  const GhostmReadRowsStats &ReadRowsStats() const { return read_rows_stats_; }
   // The subject pile-up of the last run's hits (include/ghostm_hip.h): one
   // GhostmSubjectPileup per subject over all DB chunks in db_id order, and the
   // subjects' depth, identities and consensus concatenated without the END
@@ -428,6 +438,10 @@ class Session {
   // -y 9: the pairwise view (a '#' line of the first fourteen columns, the
   // three rows, an empty line). Both rewrite the -y 7 text of FormatPathTabular.
   void FormatRows();
+  // -y 14 (frame false) and -y 15 (frame true): positives, qseq and sseq from
+  // the hit's read-level rows appended to the -y 12 / -y 13 line; a hit of
+  // read-level score 0 takes the three fields from its tile rows (HitsRows).
+  void FormatReadRows(bool frame);
   // -y 10 and -y 11: replaces the parts' text by one line per subject with hits
   void FormatPileup();
   // One PathPileup call on DB chunk di for the hits `items` (indices of Hits()),
@@ -475,6 +489,22 @@ class Session {
   std::vector<GhostmHitPath> hits_band_;
   std::vector<uint32_t> band_ops_, band_letters_;  // band_letters_: per hit, its source's letters m
   bool hits_band_valid_ = false;
+  // per hit, the chunk-local sources HitsBand() / HitsFrame() aligned
+  std::vector<GhostmBandSource> band_src_, frame_src_;
+  // the read-level rows of the band paths [0] and of the frame paths [1]
+  struct ReadRowsResult {
+    std::vector<GhostmHitReadRows> rec;
+    std::vector<uint8_t> bytes;
+    bool valid = false;
+    void Drop() {
+      rec.clear();
+      bytes.clear();
+      bytes.shrink_to_fit();
+      valid = false;
+    }
+  };
+  ReadRowsResult read_rows_[2];
+  GhostmReadRowsStats read_rows_stats_{};
   uint32_t band_ = 31;
   uint32_t tile_step_ = 0;  // a tiled set's step; 0 on an untiled set
   bool tile_dna_ = false;   // ... whether its sources are DNA frames (tiles six records apart)

@@ -513,6 +513,47 @@ size_t GhostmSessionFrameStats(void *s, GhostmFrameStats *stats, size_t size) {
   return sizeof(GhostmFrameStats);
 }
 
+namespace {
+size_t CopyReadRows(void *s, bool frame, GhostmHitReadRows *rec, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmHitReadRows> &h = static_cast<Session *>(s)->HitsReadRows(frame);
+    if (!rec) return h.size();
+    const size_t n = std::min(cap, h.size());
+    std::memcpy(rec, h.data(), n * sizeof(GhostmHitReadRows));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+size_t CopyReadRowBytes(void *s, bool frame, uint8_t *rows, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<uint8_t> &b = static_cast<Session *>(s)->ReadRowBytes(frame);
+    if (!rows) return b.size();
+    const size_t n = std::min(cap, b.size());
+    std::memcpy(rows, b.data(), n);
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+}  // namespace
+
+size_t GhostmSessionHitsBandRows(void *s, GhostmHitReadRows *rec, size_t cap) { return CopyReadRows(s, false, rec, cap); }
+size_t GhostmSessionBandRowBytes(void *s, uint8_t *rows, size_t cap) { return CopyReadRowBytes(s, false, rows, cap); }
+size_t GhostmSessionHitsFrameRows(void *s, GhostmHitReadRows *rec, size_t cap) { return CopyReadRows(s, true, rec, cap); }
+size_t GhostmSessionFrameRowBytes(void *s, uint8_t *rows, size_t cap) { return CopyReadRowBytes(s, true, rows, cap); }
+
+size_t GhostmSessionReadRowsStats(void *s, GhostmReadRowsStats *stats, size_t size) {
+  if (!s || !stats) return 0;
+  const GhostmReadRowsStats st = static_cast<Session *>(s)->ReadRowsStats();
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadRowsStats)));
+  return sizeof(GhostmReadRowsStats);
+}
+
 size_t GhostmSessionHitsRows(void *s, GhostmHitRows *rec, size_t cap) {
   try {
     if (!s) throw Error("null session");

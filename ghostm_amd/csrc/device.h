@@ -112,6 +112,8 @@ struct DeviceTimes {
                                                   // rows run x (2B + 1), direction bytes
   double frame = 0;                               // the frame pass (k_frame_fill + k_frame_walk + k_frame_compact),
   uint64_t frame_launches = 0, frame_hits = 0, frame_cells = 0, frame_dir_bytes = 0;  // counted as the band pass
+  double read_rows = 0;                           // the read-level rows (k_read_rows): seconds,
+  uint64_t read_rows_launches = 0, read_rows_hits = 0, read_rows_columns = 0;  // batches, hits, columns
 };
 
 class DeviceModule {
@@ -353,6 +355,22 @@ class DeviceModule {
   void FrameAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBandSource *src, const int32_t *D,
                   const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B, int open, int ext, int shift,
                   GhostmHitPath *rec, std::vector<uint32_t> *ops);
+
+  // The aligned rows of n read-level hits (kern::k_read_rows<frame>; the
+  // contract is above GhostmHitReadRows in include/ghostm_hip.h): hit i has
+  // source src[i] of chunk q (W = q's record width, tile step `step`), rec[i]
+  // gives q_start, s_start (absolute in chunk d) and its words in ops[ops_len].
+  // Everything is checked first (ValidateReadRows, read_rows.h; throws with the
+  // reason before any upload or launch, the outputs untouched). out, rows,
+  // rows_cap, dst_off, record_base and the return value as PathRows. The hits
+  // run in hit order in CutBatch's batches (hit_batches.h): the cost a hit's row
+  // bytes, the budget GHOSTM_READ_ROWS_SCRATCH_MB (default 1024), the cap
+  // GHOSTM_READ_ROWS_BATCH_HITS. Adds its device time, batches, hits and
+  // columns to times().
+  size_t ReadRows(DevQuery *q, DevDb *d, uint32_t n, const GhostmBandSource *src, const GhostmHitPath *rec,
+                  const uint32_t *ops, size_t ops_len, uint32_t step, bool frame, int open, int ext, int shift,
+                  uint32_t record_base, GhostmHitReadRows *out, uint8_t *rows, size_t rows_cap,
+                  const uint64_t *dst_off);
 
   DeviceTimes &times() {
     SettleSeedTime();

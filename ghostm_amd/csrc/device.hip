@@ -22,6 +22,7 @@
 #include "index.h"
 #include "kernels.h"
 #include "path_rows.h"
+#include "read_rows.h"
 #include "pileup_plan.h"
 #include "qformat.h"
 #include "query_tiles.h"
@@ -285,6 +286,8 @@ struct DeviceModule::Impl {
   DevBuf tb_path_in, tb_path_meta, tb_path_dir, tb_path_ops, tb_path_cmp;
   // PathRows: a batch's per-hit inputs, its words, its counts and its row bytes
   DevBuf path_rows_hit, path_rows_ops, path_rows_out, path_rows_buf;
+  // ReadRows: the same four of its own
+  DevBuf read_rows_hit, read_rows_ops, read_rows_out, read_rows_buf;
   // PathPileup: a batch's hits, words, plan lists and parts; a window's profile and finished arrays; the column counter
   DevBuf pileup_hit, pileup_ops, pileup_list, pileup_part, pileup_prof, pileup_out, pileup_cols;
   // BandAlign: a batch's slots, its offsets / maxima / records, its direction bytes, its word slots, their packed words
@@ -2610,6 +2613,106 @@ size_t DeviceModule::PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t 
   return total;
 }
 
+static_assert(sizeof(kern::ReadRowsHit) == 48, "ReadRowsHit is uploaded as 48-byte records");
+
+size_t DeviceModule::ReadRows(DevQuery *q, DevDb *d, uint32_t n, const GhostmBandSource *src, const GhostmHitPath *rec,
+                              const uint32_t *ops, size_t ops_len, uint32_t step, bool frame, int open, int ext,
+                              int shift, uint32_t record_base, GhostmHitReadRows *out, uint8_t *rows, size_t rows_cap,
+                              const uint64_t *dst_off) {
+  Use();
+  Impl &I = *impl_;
+  if (n == 0) return 0;
+  // every index the kernel will use, checked here: nothing is uploaded or launched for a refused call
+  std::vector<uint32_t> columns;
+  const std::string why = ValidateReadRows(q->nseq, q->L, d->len, n, src, rec, ops, ops_len, step, frame, shift, &columns);
+  if (!why.empty()) throw Error("read rows: " + why);
+  size_t total = 0;
+  for (uint32_t k = 0; k < n; ++k) {
+    const size_t b = 3 * (size_t)columns[k], at = dst_off ? (size_t)dst_off[k] : total;
+    if (rows && (at > rows_cap || b > rows_cap - at)) throw Error("read rows: rows_cap: the rows do not fit");
+    total += b;
+  }
+  if (!out && !rows) return total;
+  const size_t budget = EnvSize("GHOSTM_READ_ROWS_SCRATCH_MB", 1024) << 20;
+  const size_t max_hits = EnvSize("GHOSTM_READ_ROWS_BATCH_HITS", SIZE_MAX);
+  std::vector<kern::ReadRowsHit> hh;
+  std::vector<uint32_t> words, counts;
+  std::vector<uint8_t> stage;  // a batch's bytes on their way to dst_off
+  size_t done_bytes = 0;
+  for (uint32_t b0 = 0; b0 < n;) {
+    // hits [b0, b1) in hit order, cut by their row bytes (hit_batches.h)
+    size_t bytes = 0;
+    const uint32_t b1 = CutBatch(b0, n, max_hits, budget, [&](uint32_t k) { return 3 * (size_t)columns[k]; }, &bytes);
+    const uint32_t m = b1 - b0;
+    hh.resize(m);
+    words.clear();
+    for (size_t s = 0, ra = 0; s < m; ++s) {
+      const GhostmHitPath &p = rec[b0 + s];
+      const GhostmBandSource &bs = src[b0 + s];
+      hh[s] = kern::ReadRowsHit{kern::SourceRef{bs.first_record, bs.stride, bs.tiles, bs.letters}, p.q_start, p.s_start,
+                                p.n_runs, columns[b0 + s], words.size(), ra};
+      if (p.n_runs) words.insert(words.end(), ops + p.ops_offset, ops + p.ops_offset + p.n_runs);
+      ra += 3 * (size_t)columns[b0 + s];
+    }
+    const size_t nwords = words.size();
+    I.read_rows_hit.Reserve((size_t)m * sizeof(kern::ReadRowsHit));
+    I.read_rows_ops.Reserve(std::max<size_t>(nwords, 1) * 4);
+    I.read_rows_out.Reserve((size_t)m * 32);
+    if (rows) I.read_rows_buf.Reserve(std::max<size_t>(bytes, 1));
+    HIP_CHECK(hipMemcpyAsync(I.read_rows_hit.p, hh.data(), (size_t)m * sizeof(kern::ReadRowsHit), hipMemcpyHostToDevice,
+                             S(stream_)));
+    if (nwords) HIP_CHECK(hipMemcpyAsync(I.read_rows_ops.p, words.data(), nwords * 4, hipMemcpyHostToDevice, S(stream_)));
+    kern::ReadRowsArgs a{};
+    a.qseq = q->seq.as<uint8_t>();
+    a.W = q->L;
+    a.step = step;
+    a.db = d->Residues();
+    a.mat = I.mat_raw.as<int>();
+    a.hit = I.read_rows_hit.as<kern::ReadRowsHit>();
+    a.n = m;
+    a.ops = I.read_rows_ops.as<uint32_t>();
+    a.open = open;
+    a.ext = ext;
+    a.shift = shift;
+    a.rows = rows ? I.read_rows_buf.as<uint8_t>() : nullptr;
+    a.out = I.read_rows_out.as<uint32_t>();
+    const dim3 grid((m + kern::kTbBlock / 64 - 1) / (kern::kTbBlock / 64)), block(kern::kTbBlock);  // one wave per hit
+    TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
+      if (frame) hipLaunchKernelGGL(kern::k_read_rows<true>, grid, block, 0, S(stream_), a);
+      else hipLaunchKernelGGL(kern::k_read_rows<false>, grid, block, 0, S(stream_), a);
+    });
+    counts.resize((size_t)m * 8);
+    HIP_CHECK(hipMemcpyAsync(counts.data(), a.out, (size_t)m * 32, hipMemcpyDeviceToHost, S(stream_)));
+    uint8_t *land = nullptr;
+    if (rows && bytes) {
+      if (dst_off) {
+        stage.resize(bytes);
+        land = stage.data();
+      } else {
+        land = rows + done_bytes;  // hit order: the batch's bytes are consecutive
+      }
+      HIP_CHECK(hipMemcpyAsync(land, a.rows, bytes, hipMemcpyDeviceToHost, S(stream_)));
+    }
+    HIP_CHECK(hipStreamSynchronize(S(stream_)));
+    times_.read_rows += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+    times_.read_rows_launches += 1;
+    times_.read_rows_hits += m;
+    times_.read_rows_columns += bytes / 3;
+    for (uint32_t s = 0; s < m; ++s) {
+      const uint32_t k = b0 + s;
+      const uint64_t at = dst_off ? dst_off[k] : done_bytes + hh[s].rows_off;
+      if (land && dst_off && columns[k]) memcpy(rows + at, land + hh[s].rows_off, 3 * (size_t)columns[k]);
+      const uint32_t *c = counts.data() + (size_t)s * 8;
+      if (out)
+        out[k] = GhostmHitReadRows{ReadRowsFirstRecord(src[k], rec[k], q->L, step, frame) + record_base, columns[k], c[0],
+                                   c[1], c[2], (int32_t)c[3], at, c[4], 0};
+    }
+    done_bytes += bytes;
+    b0 = b1;
+  }
+  return total;
+}
+
 static_assert(kern::kBandNeg == kBandNegInf, "the kernels' minus infinity is the host model's");
 static_assert(sizeof(kern::BandHit) == 48, "BandHit is uploaded as 48-byte records");
 
@@ -2931,7 +3034,7 @@ const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_pileup/k_pileup_finish/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_pileup_finish/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -3440,6 +3543,39 @@ size_t GhostmStageFrameStats(GhostmFrameStats *stats, size_t size) {
   const GhostmFrameStats st{dt.frame, dt.frame_launches, dt.frame_hits, dt.frame_cells, dt.frame_dir_bytes};
   std::memcpy(stats, &st, std::min(size, sizeof(GhostmFrameStats)));
   return sizeof(GhostmFrameStats);
+}
+
+int ReadRowsGpu(uint32_t nhits, const GhostmBandSource src[], const GhostmHitPath rec[], const uint32_t ops[],
+                size_t ops_len, uint32_t query_sequence_length, uint32_t step, int frame, int open_gap, int extend_gap,
+                int shift_cost, GhostmHitReadRows out[], uint8_t rows[], size_t rows_cap, size_t *rows_used) {
+  try {
+    if (nhits == 0) {
+      if (rows_used) *rows_used = 0;
+      return 0;
+    }
+    if (!src || !rec) throw Error("ReadRowsGpu: null: an input array");
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    if (!r.query || !r.db) throw Error("SetQueryGpu/SetDbGpu not called");
+    if (query_sequence_length != r.query->L) throw Error("ReadRowsGpu: source: query shape differs from SetQueryGpu");
+    const size_t used = DeviceModule::Get().ReadRows(r.query, r.db, nhits, src, rec, ops, ops_len, step, frame != 0,
+                                                     open_gap, extend_gap, shift_cost, 0, out, rows, rows_cap, nullptr);
+    if (rows_used) *rows_used = used;
+    return 0;
+  } catch (std::exception &e) {
+    SetError(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmStageReadRowsStats(GhostmReadRowsStats *stats, size_t size) {
+  if (!stats) return 0;
+  RefState &r = Ref();
+  std::lock_guard<std::mutex> lk(r.mu);
+  const DeviceTimes &dt = DeviceModule::Get().times();
+  const GhostmReadRowsStats st{dt.read_rows, dt.read_rows_launches, dt.read_rows_hits, dt.read_rows_columns};
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadRowsStats)));
+  return sizeof(GhostmReadRowsStats);
 }
 
 int PathPileupGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPath rec[], const uint32_t ops[],

@@ -3407,6 +3407,154 @@ __global__ __launch_bounds__(kTbBlock) void k_path_rows(PathRowsArgs a) {
   }
 }
 
+// ------------------------------------------------------------------ read-level aligned rows
+// k_read_rows<FRAME>: the rows of every read-level path (GhostmHitReadRows,
+// ReadRowsGpu, include/ghostm_hip.h; host model read_rows_host.cpp), for the
+// band pass's paths (FRAME false) and the frame pass's (FRAME true). One wave
+// per hit with k_path_rows' column machinery: the words 64 at a time, three
+// wave scans with a carry, the six-step run search, consecutive lanes on
+// consecutive bytes of each row, wave sums at the end. Two things differ.
+// The query letter is read through the hit's source (SourceLetter, a
+// restatement of read_rows.h / band_align.h / query_tiles.h): a path runs
+// through several tile records, the last one flush right. And the query scan
+// is over a position's advance per word, in FRAME mode in nucleotides and
+// signed: 3 * len for ops 0-2, +len for op 4, -len for op 5. The scan adds in
+// uint32 modulo 2^32, which is exact wherever the host let a letter be read:
+// it has checked that every letter column's true position lies in
+// [0, 3 * letters) and that this fits 32 bits (ValidateReadRows). A letter
+// column k of a word that begins at position q shows letter (q + 3k) / 3 of
+// frame (q + 3k) % 3, so the lanes of one word read consecutive bytes of one
+// frame's record; a shift moves the following word's lanes to another frame's
+// record, W bytes further (the frames of a tile are consecutive records).
+struct SourceRef {  // GhostmBandSource
+  uint32_t first_record, stride, tiles, letters;
+};
+struct ReadRowsHit {  // 48 bytes
+  SourceRef src;
+  uint32_t q_start, s_start, n_runs, columns;
+  unsigned long long ops_off;   // first word of the hit in ops
+  unsigned long long rows_off;  // first byte of the hit's 3 * columns bytes in rows
+};
+struct ReadRowsArgs {
+  const uint8_t *qseq;
+  uint32_t W, step;
+  const uint8_t *db;
+  const int *mat;  // M[db code * 32 + query code]
+  const ReadRowsHit *hit;
+  uint32_t n;
+  const uint32_t *ops;
+  int open, ext, shift;
+  uint8_t *rows;   // null: the counts only
+  uint32_t *out;   // per hit, 8 words: identities, positives, gap_residues, rescore, shifts
+};
+
+// letter c of frame offset g of a source (band mode: g = 0): its byte in the chunk's records
+__device__ __forceinline__ size_t SourceLetter(const SourceRef &s, uint32_t g, uint32_t c, uint32_t W, uint32_t step) {
+  const uint32_t t = min(c / step, s.tiles - 1);
+  const uint32_t start = t + 1 < s.tiles ? t * step : (s.letters > W ? s.letters - W : 0u);
+  const uint32_t rec = s.first_record + g + (s.tiles > 1 ? s.stride * t : 0u);
+  return (size_t)rec * W + (c - start);
+}
+
+template <bool FRAME>
+__global__ __launch_bounds__(kTbBlock) void k_read_rows(ReadRowsArgs a) {
+  GHOSTM_POISON_LDS();
+  __shared__ int s_mat[32 * 32];
+  __shared__ uint8_t s_let[32];
+  for (uint32_t e = threadIdx.x; e < 32 * 32; e += kTbBlock) s_mat[e] = a.mat[e];
+  if (threadIdx.x < 32) s_let[threadIdx.x] = threadIdx.x < 25 ? (uint8_t)"ARNDCQEGHILKMFPSTWYVBJZX*"[threadIdx.x] : (uint8_t)'?';
+  __syncthreads();
+
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t h = blockIdx.x * (kTbBlock / 64) + (threadIdx.x >> 6);
+  if (h >= a.n) return;  // the whole wave
+  const ReadRowsHit hit = a.hit[h];
+  const uint32_t *words = a.ops + hit.ops_off;
+  uint8_t *row_q = a.rows ? a.rows + hit.rows_off : nullptr;
+  uint32_t col0 = 0, q0 = hit.q_start, s0 = hit.s_start;  // of the group's first run
+  uint32_t ident = 0, posit = 0, gaps = 0, shifts = 0;
+  int score = 0;
+  for (uint32_t r0 = 0; r0 < hit.n_runs; r0 += 64) {
+    const uint32_t w = r0 + lane < hit.n_runs ? words[r0 + lane] : 0u;  // past the last run: length 0
+    const uint32_t len = w >> 4, op = w & 7u;
+    // the position's advance over the word, modulo 2^32
+    uint32_t adv = op <= 2u ? (FRAME ? 3u * len : len) : 0u;
+    if (FRAME && op == 4u) adv = len;
+    if (FRAME && op == 5u) adv = 0u - len;
+    uint32_t tc, tq, ts;
+    const uint32_t c = col0 + WaveExclusiveScan(len, &tc);
+    const uint32_t q = q0 + WaveExclusiveScan(adv, &tq);
+    const uint32_t s = s0 + WaveExclusiveScan(op <= 1u || op == 3u ? len : 0u, &ts);
+    const uint32_t c1 = col0 + tc;
+    for (uint32_t base = col0; base < c1; base += 64) {
+      const bool on = base + lane < c1;
+      const uint32_t col = on ? base + lane : c1 - 1;
+      // the last lane whose run begins at or before col (the lanes past the last run begin at c1)
+      uint32_t r = 0;
+#pragma unroll
+      for (uint32_t stp = 32; stp; stp >>= 1) {
+        const uint32_t v = (uint32_t)__shfl((int)c, (int)(r + stp));
+        if (v <= col) r += stp;
+      }
+      const uint32_t k = col - (uint32_t)__shfl((int)c, (int)r);
+      const uint32_t rq = (uint32_t)__shfl((int)q, (int)r), rs = (uint32_t)__shfl((int)s, (int)r);
+      const uint32_t rop = (uint32_t)__shfl((int)op, (int)r);
+      if (on) {
+        uint32_t qc = 0, sc = 0;
+        uint8_t ql = '-', sl = '-', ml = ' ';
+        if (rop <= 2u) {
+          const uint32_t p = rq + (FRAME ? 3u * k : k);
+          qc = a.qseq[FRAME ? SourceLetter(hit.src, p % 3u, p / 3u, a.W, a.step) : SourceLetter(hit.src, 0u, p, a.W, a.step)];
+          ql = qc < 25u ? s_let[qc] : (uint8_t)'?';
+        }
+        if (rop <= 1u || rop == 3u) {
+          sc = a.db[rs + k];
+          sl = sc < 25u ? s_let[sc] : (uint8_t)'?';
+        }
+        if (rop < 2u) {
+          const int m = s_mat[(sc & 31u) * 32 + (qc & 31u)];
+          score += m;
+          posit += m > 0;
+          ident += rop == 0u;
+          if (rop == 0u) ml = ql;
+          else if (m > 0) ml = '+';
+        } else if (rop < 4u) {
+          ++gaps;
+          score += k == 0 ? a.open : a.ext;
+        } else {
+          ql = rop == 4u ? (uint8_t)'\\' : (uint8_t)'/';
+          ++shifts;
+          score += a.shift;
+        }
+        if (row_q) {
+          row_q[col] = ql;
+          row_q[(size_t)hit.columns + col] = ml;
+          row_q[2 * (size_t)hit.columns + col] = sl;
+        }
+      }
+    }
+    col0 = c1;
+    q0 += tq;
+    s0 += ts;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    ident += __shfl_xor(ident, d);
+    posit += __shfl_xor(posit, d);
+    gaps += __shfl_xor(gaps, d);
+    shifts += __shfl_xor(shifts, d);
+    score += __shfl_xor(score, d);
+  }
+  if (lane == 0) {
+    uint32_t *o = a.out + 8 * (size_t)h;
+    o[0] = ident;
+    o[1] = posit;
+    o[2] = gaps;
+    o[3] = (uint32_t)score;
+    o[4] = shifts;
+  }
+}
+
 // ------------------------------------------------------------------ subject pile-up
 // k_pileup: the hits' columns added into the profile of a window of the DB
 // chunk (32 counters per position: query codes 0..24, 25 for every code from 25

@@ -141,6 +141,29 @@ class GhostmHitRows(ctypes.Structure):
     ]
 
 
+class GhostmHitReadRows(ctypes.Structure):
+    """the aligned rows of one read-level hit (40 bytes): GhostmHitRows' fields
+    (query_record: the record of the path's first query letter), then the shift
+    columns."""
+
+    _fields_ = GhostmHitRows._fields_ + [
+        ("shifts", c_uint32),
+        ("pad", c_uint32),
+    ]
+
+
+class GhostmReadRowsStats(ctypes.Structure):
+    """the counters of the read-level rows pass (GhostmSessionReadRowsStats,
+    GhostmStageReadRowsStats)."""
+
+    _fields_ = [
+        ("seconds_read_rows", ctypes.c_double),
+        ("read_rows_launches", c_uint64),
+        ("read_rows_hits", c_uint64),
+        ("read_rows_columns", c_uint64),
+    ]
+
+
 class GhostmSubjectPileup(ctypes.Structure):
     """one subject's summary of the pile-up (40 bytes); offset is its first
     element in the session-level depth / identities / consensus arrays."""
@@ -311,6 +334,14 @@ SIGNATURES = {
                                      u32p, u32p, c_uint32, c_uint32, c_uint32, c_int, c_int, c_int,
                                      POINTER(GhostmHitPath), u32p, c_size_t, POINTER(c_size_t)]),
     "GhostmStageFrameStats": (c_size_t, [POINTER(GhostmFrameStats), c_size_t]),
+    "ReadRowsGpu": (c_int, [c_uint32, POINTER(GhostmBandSource), POINTER(GhostmHitPath), u32p, c_size_t, c_uint32,
+                            c_uint32, c_int, c_int, c_int, c_int, POINTER(GhostmHitReadRows), POINTER(ctypes.c_uint8),
+                            c_size_t, POINTER(c_size_t)]),
+    "GhostmReadRowsHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, POINTER(ctypes.c_uint8), c_uint32,
+                                   POINTER(c_int), c_uint32, POINTER(GhostmBandSource), POINTER(GhostmHitPath), u32p,
+                                   c_size_t, c_uint32, c_uint32, c_int, c_int, c_int, c_int,
+                                   POINTER(GhostmHitReadRows), POINTER(ctypes.c_uint8), c_size_t, POINTER(c_size_t)]),
+    "GhostmStageReadRowsStats": (c_size_t, [POINTER(GhostmReadRowsStats), c_size_t]),
     "GhostmBuildIndexGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, u32p, u32p, u32p, c_int,
                                     POINTER(c_float)]),
     "GhostmFormatQueriesGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_uint32,
@@ -366,6 +397,11 @@ SIGNATURES = {
     "GhostmSessionFrameInfo": (c_size_t, [c_void_p, POINTER(GhostmHitFrameInfo), c_size_t]),
     "GhostmSessionSetFrameShift": (c_int, [c_void_p, c_int]),
     "GhostmSessionFrameStats": (c_size_t, [c_void_p, POINTER(GhostmFrameStats), c_size_t]),
+    "GhostmSessionHitsBandRows": (c_size_t, [c_void_p, POINTER(GhostmHitReadRows), c_size_t]),
+    "GhostmSessionBandRowBytes": (c_size_t, [c_void_p, POINTER(ctypes.c_uint8), c_size_t]),
+    "GhostmSessionHitsFrameRows": (c_size_t, [c_void_p, POINTER(GhostmHitReadRows), c_size_t]),
+    "GhostmSessionFrameRowBytes": (c_size_t, [c_void_p, POINTER(ctypes.c_uint8), c_size_t]),
+    "GhostmSessionReadRowsStats": (c_size_t, [c_void_p, POINTER(GhostmReadRowsStats), c_size_t]),
     "GhostmSessionHitsRows": (c_size_t, [c_void_p, POINTER(GhostmHitRows), c_size_t]),
     "GhostmSessionRowBytes": (c_size_t, [c_void_p, POINTER(ctypes.c_uint8), c_size_t]),
     "GhostmSessionPileup": (c_size_t, [c_void_p, POINTER(GhostmSubjectPileup), c_size_t]),

@@ -786,6 +786,117 @@ typedef struct GhostmHitFrameInfo {
   uint32_t shifts;   /* the summed length of the path's shift runs */
 } GhostmHitFrameInfo;
 
+/* The aligned rows of a read-level path: what GhostmHitRows and PathRowsGpu are
+ * to a tile path, for the paths of BandAlignGpu (band mode) and FrameAlignGpu
+ * (frame mode). The text layout is GhostmHitRows': 3 * columns bytes at
+ * rows[rows_offset], the query row, the midline and the subject row, letters
+ * "ARNDCQEGHILKMFPSTWYVBJZX*"[c] and '?' from code 25 up, the midline the query
+ * letter in a '=' column, '+' in an 'X' column whose matrix entry
+ * M[(db code & 31) * 32 + (query code & 31)] is > 0 and a space elsewhere.
+ *
+ * The query letters are read through the hit's GhostmBandSource, W and step,
+ * by the rules above BandAlignGpu and FrameAlignGpu: letter c of frame offset
+ * g (band mode: g = 0) lies in tile t = min(c / step, tiles - 1), whose start
+ * is t * step, or max(letters - W, 0) for the last tile; its record is
+ * first_record + g + stride * t (stride ignored when tiles == 1), its byte
+ * c - start(t).
+ *
+ * Every word gives len display columns, and a position runs along the path
+ * from rec.q_start (subject: rec.s_start, absolute in the chunk):
+ *   band mode   the position is a source letter. A column of op 0, 1 or 2
+ *               shows the letter at the position and advances it by 1; op 3
+ *               advances the subject only.
+ *   frame mode  the position p is a strand position in nucleotides. A column
+ *               of op 0, 1 or 2 shows letter p / 3 of frame p % 3 and advances
+ *               p by 3; op 3 leaves p; a column of op 4 ('\') advances p by 1
+ *               and a column of op 5 ('/') takes 1 from it. A shift column
+ *               holds '\' or '/' in the query row, a space in the midline and
+ *               '-' in the subject row, and touches no subject residue.
+ * Ops 0, 1 and 3 advance the subject position by 1 per column. The op of a
+ * pair column is taken as given ('=' or 'X'): a '=' column counts as an
+ * identity and puts the query letter on the midline whatever the codes are.
+ *
+ * query_record is the record of the first query letter, the letter at
+ * rec.q_start (stage level: in the resident chunk; session level: the global
+ * index as in GhostmHitRows); a path without words gives first_record, columns
+ * 0, counts 0 and no bytes. shifts counts the columns of ops 4 and 5; they are
+ * no gap_residues. rescore adds shift_cost per shift column to GhostmHitRows'
+ * sum (band mode never reads shift_cost) and equals GhostmHitPath.score for a
+ * path BandAlignGpu or FrameAlignGpu made with the same costs: a proof of the
+ * DP that walks the sequences only. */
+typedef struct GhostmHitReadRows {   /* 40 bytes; the first 32 are GhostmHitRows' */
+  uint32_t query_record;
+  uint32_t columns;
+  uint32_t identities;
+  uint32_t positives;
+  uint32_t gap_residues;  /* 'I' and 'D' columns only */
+  int32_t rescore;
+  uint64_t rows_offset;
+  uint32_t shifts;        /* columns of ops 4 and 5; 0 in band mode */
+  uint32_t pad;           /* 0 */
+} GhostmHitReadRows;
+
+/* The rows of every read-level hit (kernel k_read_rows), stage level like
+ * PathRowsGpu (after SetQueryGpu and SetDbGpu): hit i has source src[i], and
+ * rec[i] gives q_start, s_start (absolute in the chunk) and its n_runs words
+ * at ops[ops_offset]; q_end, s_end and score are not read.
+ * query_sequence_length is the records' width W, step the tile step, frame 0
+ * for band paths and 1 for frame paths (src[i] then names frame 0 of a strand).
+ * Any well-formed path is accepted, not only one the passes made. Record i
+ * belongs to hit i; the hits' bytes follow each other in hit order. rows ==
+ * NULL: only *rows_used (the bytes needed) and out (may be NULL) are written.
+ * nhits == 0 writes *rows_used = 0 and nothing else. Everything is checked on
+ * the host before any upload or launch; a refused call leaves out, rows and
+ * *rows_used untouched and names its reason in GhostmGetLastError:
+ *   "source"   as BandAlignGpu: a record outside the chunk (frame mode: a
+ *              frame's record); tiles == 0 or letters == 0; tiles disagrees
+ *              with letters, W and step; stride 0 with several tiles; step 0 or
+ *              over W; W differs from the resident chunk's
+ *   "ops"      ops_offset + n_runs > ops_len
+ *   "word"     a zero length or bit 3 set; band mode: an op above 3; frame
+ *              mode: an op of 6 or 7
+ *   "bounds"   a column of op 0, 1 or 2 whose position lies outside [0,
+ *              letters) in band mode or [0, 3 * letters) in frame mode, or the
+ *              q_start of a path with words outside it; subject residues past
+ *              the resident chunk; more than 2^32 - 1 columns or strand
+ *              positions
+ *   "shift"    frame mode: shift_cost > 0 or shift_cost < -(1 << 20)
+ *   "rows_cap" rows_cap smaller than the bytes needed
+ *   "null"     null src or rec with nhits > 0
+ * One wave runs one hit with k_path_rows' column machinery; the row buffer is
+ * cut into batches of hits that fit GHOSTM_READ_ROWS_SCRATCH_MB (default 1024)
+ * and hold at most GHOSTM_READ_ROWS_BATCH_HITS hits (default: no limit); a
+ * batch holds at least one hit. */
+int ReadRowsGpu(uint32_t nhits, const GhostmBandSource src[], const GhostmHitPath rec[],
+                const uint32_t ops[], size_t ops_len, uint32_t query_sequence_length, uint32_t step,
+                int frame, int open_gap, int extend_gap, int shift_cost, GhostmHitReadRows out[],
+                uint8_t rows[], size_t rows_cap, size_t *rows_used);
+
+/* The same on the host, with no device call (the model the kernel equals byte
+ * for byte, written column by column) and the same checks and reasons:
+ * query_seqs = nq records of L codes, db = the chunk's db_len residues,
+ * score_matrix = M[db code * 32 + query code]; query_sequence_length must equal
+ * L ("source"); null query_seqs, db or score_matrix with nhits > 0 is "null". */
+int GhostmReadRowsHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, const uint8_t *db,
+                       uint32_t db_len, const int score_matrix[], uint32_t nhits,
+                       const GhostmBandSource src[], const GhostmHitPath rec[], const uint32_t ops[],
+                       size_t ops_len, uint32_t query_sequence_length, uint32_t step, int frame,
+                       int open_gap, int extend_gap, int shift_cost, GhostmHitReadRows out[],
+                       uint8_t rows[], size_t rows_cap, size_t *rows_used);
+
+/* The counters of the read-level rows pass, a struct of their own like
+ * GhostmBandStats. */
+typedef struct GhostmReadRowsStats {
+  double seconds_read_rows;    /* k_read_rows, device time */
+  uint64_t read_rows_launches; /* batches of hits (one launch each) */
+  uint64_t read_rows_hits;
+  uint64_t read_rows_columns;  /* sum of the hits' columns */
+} GhostmReadRowsStats;
+
+/* The read-rows counters behind the stage-level calls; GhostmStageBandStats'
+ * conventions. */
+size_t GhostmStageReadRowsStats(GhostmReadRowsStats *stats, size_t size);
+
 /* A session without a database: `aln`'s options without -d (giving it is an
  * error). With -i the query chunks are loaded as GhostmSessionCreate loads
  * them; without -i the session starts with neither input and the queries come
@@ -1086,6 +1197,28 @@ int GhostmSessionSetFrameShift(void *session, int shift_cost);
 /* The frame counters of the session since its last run (all 0 until the frame
  * results are asked for); the size convention of GhostmSessionBandStats. */
 size_t GhostmSessionFrameStats(void *session, GhostmFrameStats *stats, size_t size);
+
+/* The GhostmHitReadRows of every hit's read-level path (record i belongs to hit
+ * i) and the row bytes they index, in hit order: the Band pair from the paths
+ * of GhostmSessionHitsBand, the Frame pair from those of GhostmSessionHitsFrame
+ * with the session's frameshift cost. The NULL/cap convention of
+ * GhostmSessionHitsRows, (size_t)-1 on error; the Frame pair is refused where
+ * GhostmSessionHitsFrame is. One ReadRowsGpu-style call per (query chunk, DB
+ * chunk) that has hits, computed on first use and kept as long as the paths
+ * they were made from (until the next run, GhostmSessionSetQueries*,
+ * GhostmSessionSetDb*, a change of band, and for the Frame pair of the
+ * frameshift cost). Works after a run with any -y and on shard sessions.
+ * query_record is the global index of the record holding the path's first
+ * query letter; a hit of read-level score 0 has columns 0. */
+size_t GhostmSessionHitsBandRows(void *session, GhostmHitReadRows *rec, size_t cap);
+size_t GhostmSessionBandRowBytes(void *session, uint8_t *rows, size_t cap);
+size_t GhostmSessionHitsFrameRows(void *session, GhostmHitReadRows *rec, size_t cap);
+size_t GhostmSessionFrameRowBytes(void *session, uint8_t *rows, size_t cap);
+
+/* The read-rows counters of the session since its last run (all 0 until the
+ * read-level rows are asked for); the size convention of
+ * GhostmSessionBandStats. */
+size_t GhostmSessionReadRowsStats(void *session, GhostmReadRowsStats *stats, size_t size);
 
 /* The pile-up of the last run's hits on every subject (the definitions above
  * PathPileupGpu), built on the paths of GhostmSessionHitsPath with the record
