@@ -461,6 +461,66 @@ def path_pileup_host(query_seqs, L, db, query_ids, rec, ops, profile=False):
     return (depth, ident, cons, prof) if profile else (depth, ident, cons)
 
 
+# GhostmSubjectReadPileup: SUBJECT_PILEUP_DTYPE's fields, then the summed shift columns
+READ_PILEUP_DTYPE = np.dtype(SUBJECT_PILEUP_DTYPE.descr + [("shifts_sum", "<u8")])
+
+
+def _read_pileup_call(fn, head, n_db, src, rec, ops, W, step, frame, tail, profile, shifts):
+    """ReadPileupGpu and GhostmReadPileupHost take the same hit arguments and
+    the same outputs."""
+    srcs = np.ascontiguousarray(src, dtype=BAND_SOURCE_DTYPE)
+    p = np.ascontiguousarray(rec, dtype=HIT_PATH_DTYPE)
+    w = np.ascontiguousarray(ops, dtype=np.uint32)
+    if srcs.shape != p.shape:
+        raise ValueError("read pileup: bad argument shapes")
+    depth = np.zeros(n_db, dtype=np.uint32)
+    ident = np.zeros(n_db, dtype=np.uint32)
+    cons = np.zeros(n_db, dtype=np.uint8)
+    shf = np.zeros(n_db, dtype=np.uint32) if shifts else None
+    prof = np.zeros((n_db, 32), dtype=np.uint32) if profile else None
+    u8p, u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+    rc = fn(*head, len(srcs), srcs.ctypes.data_as(ctypes.POINTER(native.GhostmBandSource)),
+            p.ctypes.data_as(ctypes.POINTER(native.GhostmHitPath)), w.ctypes.data_as(u32p), w.size, int(W), int(step),
+            int(bool(frame)), *tail, depth.ctypes.data_as(u32p), ident.ctypes.data_as(u32p), cons.ctypes.data_as(u8p),
+            shf.ctypes.data_as(u32p) if shifts else None, prof.ctypes.data_as(u32p) if profile else None)
+    if rc != 0:
+        raise GhostmError(native.last_error())
+    return (depth, ident, cons, shf, prof)
+
+
+def read_pileup_host(query_seqs, W, db, src, rec, ops, step, frame=False, profile=False, shifts=True):
+    """The host model of the read-level pile-up (GhostmReadPileupHost; no
+    device): query_seqs, db, src, rec, ops, step and frame as read_rows_host.
+    Returns (depth, identities, consensus, shifts, profile), each one element
+    per residue of db, profile of shape (len(db), 32); shifts and profile are
+    None unless asked for."""
+    lib = native.load()
+    qs = np.ascontiguousarray(query_seqs, dtype=np.uint8).reshape(-1)
+    dbs = np.ascontiguousarray(db, dtype=np.uint8).reshape(-1)
+    if W <= 0 or qs.size % W:
+        raise ValueError("read_pileup_host: bad argument shapes")
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    head = (qs.ctypes.data_as(u8p), qs.size // W, int(W), dbs.ctypes.data_as(u8p), dbs.size)
+    return _read_pileup_call(lib.GhostmReadPileupHost, head, dbs.size, src, rec, ops, W, step, frame, (), profile,
+                             shifts)
+
+
+def read_pileup(src, rec, ops, W, step, db_len, frame=False, profile=False, shifts=True):
+    """ReadPileupGpu on the chunks of SetQueryGpu / SetDbGpu; db_len is the
+    resident DB chunk's length; result as read_pileup_host."""
+    lib = native.load()
+    return _read_pileup_call(lib.ReadPileupGpu, (), int(db_len), src, rec, ops, W, step, frame, (int(db_len),),
+                             profile, shifts)
+
+
+def stage_read_pileup_stats() -> dict:
+    """The read-level pile-up counters behind the stage-level calls (GhostmStageReadPileupStats)."""
+    lib = native.load()
+    st = native.GhostmReadPileupStats()
+    lib.GhostmStageReadPileupStats(ctypes.byref(st), ctypes.sizeof(st))
+    return {n: getattr(st, n) for n, _ in st._fields_}
+
+
 class Aligner:
     """reference class Aligner (aligner.h:63-92): Execute(argc, argv)."""
 
@@ -963,6 +1023,58 @@ class Session:
                                                  n) == bad:
             raise GhostmError(native.last_error())
         return prof.reshape(-1, 32)
+
+    def read_pileup(self, frame: bool = False) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """(subjects, depth, identities, consensus, shifts): pileup() from the
+        read-level paths, hits_band()'s (frame False) or hits_frame()'s (frame
+        True): one READ_PILEUP_DTYPE record per subject (GhostmSessionReadPileup)
+        and the subjects' positions concatenated
+        (GhostmSessionReadPileupArrays). frame=True is refused where
+        hits_frame() is."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        f = int(bool(frame))
+        n = lib.GhostmSessionReadPileup(self._h, f, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        subj = np.zeros(n, dtype=READ_PILEUP_DTYPE)
+        if n:
+            lib.GhostmSessionReadPileup(self._h, f, subj.ctypes.data_as(ctypes.POINTER(native.GhostmSubjectReadPileup)), n)
+        m = lib.GhostmSessionReadPileupArrays(self._h, f, None, None, None, None, 0)
+        if m == bad:
+            raise GhostmError(native.last_error())
+        depth = np.zeros(m, dtype=np.uint32)
+        ident = np.zeros(m, dtype=np.uint32)
+        cons = np.full(m, 255, dtype=np.uint8)
+        shifts = np.zeros(m, dtype=np.uint32)
+        if m:
+            u32p = ctypes.POINTER(ctypes.c_uint32)
+            lib.GhostmSessionReadPileupArrays(self._h, f, depth.ctypes.data_as(u32p), ident.ctypes.data_as(u32p),
+                                              cons.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
+                                              shifts.ctypes.data_as(u32p), m)
+        return subj, depth, ident, cons, shifts
+
+    def read_subject_profile(self, frame: bool, db_id: int) -> np.ndarray:
+        """The 32-slot rows of subject db_id from the read-level paths, shape
+        (length, 32) (GhostmSessionReadSubjectProfile): slots 27 and 28 hold
+        the shift columns of a frame pile-up. Made on demand, nothing is kept."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        f = int(bool(frame))
+        n = lib.GhostmSessionReadSubjectProfile(self._h, f, db_id, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        prof = np.zeros(n, dtype=np.uint32)
+        if n and lib.GhostmSessionReadSubjectProfile(self._h, f, db_id,
+                                                     prof.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n) == bad:
+            raise GhostmError(native.last_error())
+        return prof.reshape(-1, 32)
+
+    def read_pileup_stats(self) -> dict:
+        """The read-level pile-up counters since the last run (GhostmSessionReadPileupStats)."""
+        st = native.GhostmReadPileupStats()
+        native.load().GhostmSessionReadPileupStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        return {name: getattr(st, name) for name, _ in st._fields_}
 
     def device_hits(self, device="cuda"):
         """The hit records as a torch uint8 tensor on this session's GPU (32 bytes

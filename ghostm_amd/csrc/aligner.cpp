@@ -226,7 +226,7 @@ AlignerOptions ParseAlignerOptions(int argc, char **argv) {
   // small inputs); the oracle honours the same variable
   if (const char *e = getenv("GHOSTM_MAX_LIST_OVERRIDE")) o.max_list_length = (uint32_t)strtoul(e, nullptr, 10);
   o.matrix = ReadScoreMatrix(matrix_file);
-  // 6 to 9 and 12 to 15: style 0's E-value and bit score; 10 and 11 (the pile-up) print none, like 1 and 2
+  // 6 to 9 and 12 to 15: style 0's E-value and bit score; 10, 11 and 16 to 19 (the pile-ups) print none, like 1 and 2
   if (o.output_style == 0 || (o.output_style >= 6 && o.output_style <= 9) ||
       (o.output_style >= 12 && o.output_style <= 15)) {
     // extension: GHOSTM_KARLIN=ungapped prices combinations the
@@ -1493,8 +1493,8 @@ const LineFormat &Session::Format() {
   // E-value and bit-score bytes
   const bool tabular =
       (opt_.output_style >= 6 && opt_.output_style <= 9) || (opt_.output_style >= 12 && opt_.output_style <= 15);
-  // -y 10 and -y 11 replace the hit lines after the run: style 1's lines, which need no E-value, stand in
-  const bool pileup = opt_.output_style == 10 || opt_.output_style == 11;
+  // -y 10, -y 11 and -y 16 to -y 19 replace the hit lines after the run: style 1's lines, which need no E-value, stand in
+  const bool pileup = opt_.output_style == 10 || opt_.output_style == 11 || (opt_.output_style >= 16 && opt_.output_style <= 19);
   if (!format_) format_.reset(new LineFormat(tabular ? 0 : pileup ? 1 : opt_.output_style, opt_.karlin, 4095));
   return *format_;
 }
@@ -1824,6 +1824,7 @@ void Session::SetBand(uint32_t band) {
   band_src_.clear();
   hits_band_valid_ = false;
   read_rows_[0].Drop();
+  read_pileup_[0].Drop();
   DropFrameResults();  // the frame pass runs inside the same band
 }
 
@@ -1920,6 +1921,7 @@ void Session::DropFrameResults() {
   frame_src_.clear();
   hits_frame_valid_ = false;
   read_rows_[1].Drop();
+  read_pileup_[1].Drop();
 }
 
 void Session::SetFrameShift(int shift) {
@@ -2350,6 +2352,173 @@ void Session::FormatPileup() {
   joined_valid_ = false;
 }
 
+// PileupChunk for the read-level paths: the sources HitsBand() / HitsFrame()
+// aligned, the subject coordinates absolute in the chunk again (as
+// HitsReadRows), one DeviceModule::ReadPileup call.
+void Session::ReadPileupChunk(bool frame, size_t di, const std::vector<size_t> &items, uint32_t p0, uint32_t p1,
+                              uint32_t *depth, uint32_t *identities, uint8_t *consensus, uint32_t *shifts,
+                              uint32_t *profile) {
+  const std::vector<GhostmHitPath> &path = frame ? HitsFrame() : HitsBand();
+  const std::vector<uint32_t> &words = frame ? frame_ops_ : band_ops_;
+  const std::vector<GhostmBandSource> &source = frame ? frame_src_ : band_src_;
+  const std::vector<GhostmHit> &hits = Hits();
+  std::vector<std::vector<GhostmBandSource>> src(queries_.size());
+  std::vector<std::vector<GhostmHitPath>> rec(queries_.size());
+  for (size_t h : items) {
+    GhostmHitPath p = path[h];
+    const uint32_t pos = dbs_[di].chunk.starts[hits[h].db_id - dbs_[di].global_base];
+    p.s_start += pos;
+    p.s_end += pos;
+    src[hit_source_[h].qi].push_back(source[h]);
+    rec[hit_source_[h].qi].push_back(p);
+  }
+  std::vector<DeviceModule::ReadPileupGroup> groups;
+  uint32_t step = 0;
+  for (size_t qi = 0; qi < queries_.size(); ++qi)
+    if (!src[qi].empty()) {
+      groups.push_back(DeviceModule::ReadPileupGroup{queries_[qi].dev, (uint32_t)src[qi].size(), src[qi].data(),
+                                                     rec[qi].data()});
+      step = tile_step_ ? tile_step_ : queries_[qi].chunk.L;  // every chunk of a set has the same width
+    }
+  DeviceModule &dev = DeviceModule::Get();
+  const DeviceTimes before = dev.times();
+  dev.ReadPileup(dbs_[di].dev, groups.data(), groups.size(), words.data(), words.size(), step, frame, p0, p1, depth,
+                 identities, consensus, shifts, profile);
+  const DeviceTimes &after = dev.times();
+  read_pileup_stats_.seconds_read_pileup += after.read_pileup - before.read_pileup;
+  read_pileup_stats_.read_pileup_launches += after.read_pileup_launches - before.read_pileup_launches;
+  read_pileup_stats_.read_pileup_windows += after.read_pileup_windows - before.read_pileup_windows;
+  read_pileup_stats_.read_pileup_parts += after.read_pileup_parts - before.read_pileup_parts;
+  read_pileup_stats_.read_pileup_columns += after.read_pileup_columns - before.read_pileup_columns;
+  read_pileup_stats_.read_pileup_shifts += after.read_pileup_shifts - before.read_pileup_shifts;
+}
+
+// Pileup() on the read-level paths, with the shifts beside the other arrays.
+const Session::ReadPileupResult &Session::ReadPileup(bool frame) {
+  ReadPileupResult &res = read_pileup_[frame ? 1 : 0];
+  if (res.valid) return res;
+  if (frame) HitsFrame();  // refuses what GhostmSessionHitsFrame refuses, before anything is made
+  else HitsBand();
+  const std::vector<GhostmHit> &hits = Hits();
+  size_t nsubj = 0;
+  uint64_t total = 0;
+  for (const DbData &d : dbs_) {
+    nsubj = std::max<size_t>(nsubj, (size_t)d.global_base + d.chunk.nseq);
+    total += d.chunk.len - d.chunk.nseq;
+  }
+  res.subj.assign(nsubj, GhostmSubjectReadPileup{0, 0, 0, 0, 0, 0, 0, 0});
+  res.depth.assign(total, 0);
+  res.ident.assign(total, 0);
+  res.shifts.assign(total, 0);
+  res.cons.assign(total, 255);
+  // every subject's place: db_id order is chunk order, subject order within a chunk
+  std::vector<size_t> order(dbs_.size());
+  for (size_t di = 0; di < dbs_.size(); ++di) order[di] = di;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return dbs_[a].global_base < dbs_[b].global_base; });
+  uint64_t at = 0;
+  for (size_t di : order)
+    for (uint32_t s = 0; s < dbs_[di].chunk.nseq; ++s) {
+      GhostmSubjectReadPileup &x = res.subj[dbs_[di].global_base + s];
+      x.length = SubjectLength(dbs_[di], s);
+      x.offset = at;
+      at += x.length;
+    }
+  std::vector<std::vector<size_t>> by_db(dbs_.size());
+  for (size_t h = 0; h < hits.size(); ++h) {
+    by_db[hit_source_[h].di].push_back(h);
+    ++res.subj[hits[h].db_id].hits;
+  }
+  std::vector<uint32_t> depth, ident, shifts;
+  std::vector<uint8_t> cons;
+  for (size_t di = 0; di < dbs_.size(); ++di) {
+    if (by_db[di].empty()) continue;  // nothing landed on the chunk: zeros and 255s
+    const DbData &d = dbs_[di];
+    depth.assign(d.chunk.len, 0);
+    ident.assign(d.chunk.len, 0);
+    shifts.assign(d.chunk.len, 0);
+    cons.assign(d.chunk.len, 255);
+    ReadPileupChunk(frame, di, by_db[di], 0, d.chunk.len, depth.data(), ident.data(), cons.data(), shifts.data(),
+                    nullptr);
+    for (uint32_t s = 0; s < d.chunk.nseq; ++s) {
+      GhostmSubjectReadPileup &x = res.subj[d.global_base + s];
+      if (!x.hits || !x.length) continue;
+      const uint32_t p = d.chunk.starts[s];
+      std::copy(depth.begin() + p, depth.begin() + p + x.length, res.depth.begin() + x.offset);
+      std::copy(ident.begin() + p, ident.begin() + p + x.length, res.ident.begin() + x.offset);
+      std::copy(shifts.begin() + p, shifts.begin() + p + x.length, res.shifts.begin() + x.offset);
+      std::copy(cons.begin() + p, cons.begin() + p + x.length, res.cons.begin() + x.offset);
+      for (uint32_t k = 0; k < x.length; ++k) {
+        const uint32_t v = depth[p + k];
+        x.covered += v > 0;
+        x.max_depth = std::max(x.max_depth, v);
+        x.depth_sum += v;
+        x.identities_sum += ident[p + k];
+        x.shifts_sum += shifts[p + k];
+      }
+    }
+  }
+  res.valid = true;
+  return res;
+}
+
+std::vector<uint32_t> Session::ReadSubjectProfile(bool frame, uint32_t db_id, bool count_only) {
+  if (!count_only) {
+    if (frame) HitsFrame();
+    else HitsBand();
+  }
+  const std::vector<GhostmHit> &hits = Hits();
+  size_t di = 0;
+  while (di < dbs_.size() && !(db_id >= dbs_[di].global_base && db_id - dbs_[di].global_base < dbs_[di].chunk.nseq))
+    ++di;
+  if (di == dbs_.size()) throw Error("read subject profile: db_id outside the loaded chunks");
+  const uint32_t s = db_id - dbs_[di].global_base, len = SubjectLength(dbs_[di], s);
+  std::vector<uint32_t> profile((size_t)len * 32, 0);
+  std::vector<size_t> items;
+  if (count_only) return profile;
+  for (size_t h = 0; h < hits.size(); ++h)
+    if (hits[h].db_id == db_id) items.push_back(h);
+  if (len && !items.empty()) {
+    const uint32_t p = dbs_[di].chunk.starts[s];
+    ReadPileupChunk(frame, di, items, p, p + len, nullptr, nullptr, nullptr, nullptr, profile.data());
+  }
+  return profile;
+}
+
+// -y 16 to -y 19: FormatPileup's line from the read-level pile-up; the frame
+// pile-up's line (-y 18, -y 19) has shifts_sum after max_depth; the consensus
+// text (-y 17, -y 19) comes last.
+void Session::FormatReadPileup(bool frame, bool consensus) {
+  const ReadPileupResult &res = ReadPileup(frame);
+  static const char kLetters[] = "ARNDCQEGHILKMFPSTWYVBJZX*";  // formats.cpp's order
+  std::string out;
+  for (const DbData &d : dbs_)
+    for (uint32_t s = 0; s < d.chunk.nseq; ++s) {
+      const GhostmSubjectReadPileup &x = res.subj[d.global_base + s];
+      if (!x.hits) continue;
+      out.append(d.chunk.names[s]);
+      const uint64_t cols[7] = {x.length, x.hits, x.covered, x.depth_sum, x.identities_sum, x.max_depth, x.shifts_sum};
+      for (size_t c = 0; c < (frame ? 7u : 6u); ++c) {
+        out.push_back('\t');
+        out.append(std::to_string(cols[c]));
+      }
+      if (consensus) {
+        out.push_back('\t');
+        for (uint32_t k = 0; k < x.length; ++k) {
+          const uint8_t c = res.cons[x.offset + k];
+          out.push_back(res.depth[x.offset + k] == 0 ? '.' : c < 25 ? kLetters[c] : '-');
+        }
+      }
+      out.push_back('\n');
+    }
+  bool placed = false;
+  for (size_t k = 0; k < used_parts_; ++k)
+    for (std::string &t : parts_[k].text) {
+      t.clear();
+      if (!placed) t.swap(out), placed = true;
+    }
+  joined_valid_ = false;
+}
+
 // -y 8 and -y 9, from the -y 7 text FormatPathTabular left in the pieces (one
 // line per hit, thirteen columns) and the hits' rows. -y 8 appends positives,
 // the query row and the subject row to the line. -y 9 writes a block per hit:
@@ -2589,6 +2758,7 @@ void Session::DropResults() {
   band_src_.clear();
   hits_band_valid_ = false;
   read_rows_[0].Drop();
+  read_pileup_[0].Drop();
   DropFrameResults();
   pileup_subj_.clear();
   pileup_depth_.clear();
@@ -2607,8 +2777,8 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  // -y 6 to -y 15 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup, HitsReadRows), not while the search runs
-  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 15;
+  // -y 6 to -y 19 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup, HitsReadRows, ReadPileup), not while the search runs
+  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 19;
   if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
@@ -2639,6 +2809,7 @@ void Session::Run(bool stream_to_file) {
   band_stats_ = GhostmBandStats{};
   frame_stats_ = GhostmFrameStats{};
   read_rows_stats_ = GhostmReadRowsStats{};
+  read_pileup_stats_ = GhostmReadPileupStats{};
   QueryStats();
   merge_epoch_ = 0;
   DropResults();
@@ -2678,7 +2849,8 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    if (opt_.output_style == 13 || opt_.output_style == 15) FormatFrameTabular();
+    if (opt_.output_style >= 16) FormatReadPileup(opt_.output_style >= 18, opt_.output_style == 17 || opt_.output_style == 19);
+    else if (opt_.output_style == 13 || opt_.output_style == 15) FormatFrameTabular();
     else if (opt_.output_style == 12 || opt_.output_style == 14) FormatPathTabular(true);
     else if (opt_.output_style >= 10) FormatPileup();
     else if (opt_.output_style == 6) FormatTabular();

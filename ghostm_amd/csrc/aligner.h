@@ -294,6 +294,21 @@ class Session {
   // kernels on that subject's hits only; nothing is kept.
   // count_only: zeros of that size, no device work.
   std::vector<uint32_t> SubjectProfile(uint32_t db_id, bool count_only = false);
+  // The same from the read-level paths (the contract is above ReadPileupGpu in
+  // include/ghostm_hip.h): HitsBand()'s (frame false) or HitsFrame()'s (frame
+  // true), with the sources those passes aligned; a post-pass of
+  // DeviceModule::ReadPileup, per DB chunk one call. Kept as long as the paths
+  // they were made from. With -y 16 to -y 19 Run makes them and the text.
+  struct ReadPileupResult {
+    std::vector<GhostmSubjectReadPileup> subj;
+    std::vector<uint32_t> depth, ident, shifts;
+    std::vector<uint8_t> cons;
+    bool valid = false;
+    void Drop() { *this = ReadPileupResult(); }
+  };
+  const ReadPileupResult &ReadPileup(bool frame);
+  std::vector<uint32_t> ReadSubjectProfile(bool frame, uint32_t db_id, bool count_only = false);
+  const GhostmReadPileupStats &ReadPileupStats() const { return read_pileup_stats_; }
   // Hit records of the last run in device memory (this session's GPU): copies
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
@@ -449,6 +464,13 @@ class Session {
   // device's counters to stats_.
   void PileupChunk(size_t di, const std::vector<size_t> &items, uint32_t p0, uint32_t p1, uint32_t *depth,
                    uint32_t *identities, uint8_t *consensus, uint32_t *profile);
+  // -y 16 / -y 17 (frame false) and -y 18 / -y 19 (frame true): FormatPileup's
+  // text from ReadPileup(frame), with shifts_sum in frame mode
+  void FormatReadPileup(bool frame, bool consensus);
+  // PileupChunk for the read-level paths; adds the device's counters to read_pileup_stats_
+  void ReadPileupChunk(bool frame, size_t di, const std::vector<size_t> &items, uint32_t p0, uint32_t p1,
+                       uint32_t *depth, uint32_t *identities, uint8_t *consensus, uint32_t *shifts,
+                       uint32_t *profile);
   uint32_t SubjectLength(const DbData &d, uint32_t subject) const;
 
   AlignerOptions opt_;
@@ -521,6 +543,8 @@ class Session {
   std::vector<uint32_t> pileup_depth_, pileup_ident_;
   std::vector<uint8_t> pileup_cons_;
   bool pileup_valid_ = false;
+  ReadPileupResult read_pileup_[2];  // of the band paths [0] and of the frame paths [1]
+  GhostmReadPileupStats read_pileup_stats_{};
   bool records_on_device_ = false;
   GhostmStats stats_{};
   unsigned threads_ = 1;

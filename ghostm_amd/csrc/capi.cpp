@@ -627,6 +627,59 @@ size_t GhostmSessionSubjectProfile(void *s, uint32_t db_id, uint32_t *profile, s
   }
 }
 
+size_t GhostmSessionReadPileup(void *s, int frame, GhostmSubjectReadPileup *subj, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmSubjectReadPileup> &p = static_cast<Session *>(s)->ReadPileup(frame != 0).subj;
+    if (!subj) return p.size();
+    const size_t n = std::min(cap, p.size());
+    std::memcpy(subj, p.data(), n * sizeof(GhostmSubjectReadPileup));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionReadPileupArrays(void *s, int frame, uint32_t *depth, uint32_t *identities, uint8_t *consensus,
+                                     uint32_t *shifts, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const Session::ReadPileupResult &r = static_cast<Session *>(s)->ReadPileup(frame != 0);
+    if (!depth && !identities && !consensus && !shifts) return r.depth.size();
+    const size_t n = std::min(cap, r.depth.size());
+    if (depth && n) std::memcpy(depth, r.depth.data(), n * 4);
+    if (identities && n) std::memcpy(identities, r.ident.data(), n * 4);
+    if (consensus && n) std::memcpy(consensus, r.cons.data(), n);
+    if (shifts && n) std::memcpy(shifts, r.shifts.data(), n * 4);
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionReadSubjectProfile(void *s, int frame, uint32_t db_id, uint32_t *profile, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<uint32_t> p = static_cast<Session *>(s)->ReadSubjectProfile(frame != 0, db_id, !profile);
+    if (!profile) return p.size();
+    const size_t n = std::min(cap, p.size());
+    if (n) std::memcpy(profile, p.data(), n * 4);
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionReadPileupStats(void *s, GhostmReadPileupStats *stats, size_t size) {
+  if (!s || !stats) return 0;
+  const GhostmReadPileupStats st = static_cast<Session *>(s)->ReadPileupStats();
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadPileupStats)));
+  return sizeof(GhostmReadPileupStats);
+}
+
 size_t GhostmSessionDeviceHits(void *s, void *dst_device, size_t cap) {
   try {
     if (!s) throw Error("null session");

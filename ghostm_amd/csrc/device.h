@@ -114,6 +114,9 @@ struct DeviceTimes {
   uint64_t frame_launches = 0, frame_hits = 0, frame_cells = 0, frame_dir_bytes = 0;  // counted as the band pass
   double read_rows = 0;                           // the read-level rows (k_read_rows): seconds,
   uint64_t read_rows_launches = 0, read_rows_hits = 0, read_rows_columns = 0;  // batches, hits, columns
+  double read_pileup = 0;                         // the read-level pile-up (k_read_pileup + k_pileup_finish<true>),
+  uint64_t read_pileup_launches = 0, read_pileup_windows = 0, read_pileup_parts = 0;  // counted as the pile-up;
+  uint64_t read_pileup_columns = 0, read_pileup_shifts = 0;  // '=', 'X', 'D' columns and shift columns charged
 };
 
 class DeviceModule {
@@ -331,6 +334,25 @@ class DeviceModule {
   void PathPileup(DevDb *d, const PileupGroup *groups, size_t ngroups, const uint32_t *ops, size_t ops_len,
                   uint32_t p0, uint32_t p1, uint32_t *depth, uint32_t *identities, uint8_t *consensus,
                   uint32_t *profile);
+
+  // The pile-up of read-level hits on positions [p0, p1) of chunk d
+  // (kern::k_read_pileup<frame>, kern::k_pileup_finish<true>; the contract is
+  // above ReadPileupGpu in include/ghostm_hip.h). PathPileup's shape: group g's
+  // hit i has source src[i] of chunk q (W = q's record width, tile step
+  // `step`) and rec[i] as for ReadRows. Every group is checked first
+  // (ValidateReadRows, ReadPileupSpans; throws with the reason before any
+  // upload or launch). The plan gives a hit to every tile its charged span
+  // meets, a position only a shift charges included. shifts (p1 - p0
+  // elements) may be null like the other outputs. Adds to times().read_pileup*.
+  struct ReadPileupGroup {
+    DevQuery *q;
+    uint32_t n;
+    const GhostmBandSource *src;
+    const GhostmHitPath *rec;
+  };
+  void ReadPileup(DevDb *d, const ReadPileupGroup *groups, size_t ngroups, const uint32_t *ops, size_t ops_len,
+                  uint32_t step, bool frame, uint32_t p0, uint32_t p1, uint32_t *depth, uint32_t *identities,
+                  uint8_t *consensus, uint32_t *shifts, uint32_t *profile);
 
   // The read-level banded alignment of n hits (kern::k_band_fill, k_band_walk,
   // k_band_compact; the contract is in include/ghostm_hip.h): hit i aligns

@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "path_rows.h"
 #include "read_rows.h"
+#include "read_pileup.h"
 #include "pileup_plan.h"
 #include "qformat.h"
 #include "query_tiles.h"
@@ -3007,7 +3008,7 @@ void DeviceModule::PathPileup(DevDb *d, const PileupGroup *groups, size_t ngroup
     f.consensus = reinterpret_cast<uint8_t *>(f.identities + npos);
     const dim3 fgrid((npos + kern::kTbBlock - 1) / kern::kTbBlock), block(kern::kTbBlock);
     TimedLaunch(I.ev0, I.ev1, S(stream_),
-                [&] { hipLaunchKernelGGL(kern::k_pileup_finish, fgrid, block, 0, S(stream_), f); });
+                [&] { hipLaunchKernelGGL(kern::k_pileup_finish<false>, fgrid, block, 0, S(stream_), f); });
     const uint32_t c0 = std::max(win0, p0), c1 = std::min(win1, p1);
     if (c0 < c1) {
       const size_t cn = c1 - c0, from = c0 - win0, to = c0 - p0;
@@ -3029,12 +3030,153 @@ void DeviceModule::PathPileup(DevDb *d, const PileupGroup *groups, size_t ngroup
   times_.pileup_columns += cols;
 }
 
+static_assert(sizeof(kern::ReadPileupHit) == 40, "ReadPileupHit is uploaded as 40-byte records");
+
+// PathPileup's loops with the read-level hit record, the charged span instead
+// of the subject residues, k_read_pileup and the finish kernel's shifts.
+void DeviceModule::ReadPileup(DevDb *d, const ReadPileupGroup *groups, size_t ngroups, const uint32_t *ops,
+                              size_t ops_len, uint32_t step, bool frame, uint32_t p0, uint32_t p1, uint32_t *depth,
+                              uint32_t *identities, uint8_t *consensus, uint32_t *shifts, uint32_t *profile) {
+  Use();
+  Impl &I = *impl_;
+  if (p0 > p1 || p1 > d->len) throw Error("read pileup: positions outside the resident chunk (db_len)");
+  // every index the kernels will use, checked here: nothing is uploaded or launched for a refused call
+  std::vector<std::vector<uint32_t>> span(ngroups);  // per hit: the positions it charges, from s_start
+  for (size_t g = 0; g < ngroups; ++g) {
+    const ReadPileupGroup &G = groups[g];
+    if (G.n == 0) continue;
+    std::string why = ValidateReadRows(G.q->nseq, G.q->L, d->len, G.n, G.src, G.rec, ops, ops_len, step, frame, 0, nullptr);
+    if (why.empty()) why = ReadPileupSpans(d->len, G.n, G.rec, ops, &span[g]);
+    if (!why.empty()) throw Error("read pileup: " + why);
+  }
+  if (p0 == p1) return;
+  const uint32_t T = PileupClampTile(EnvSize("GHOSTM_PILEUP_TILE", kPileupTileDefault));
+  const uint32_t P = (uint32_t)std::min<size_t>(EnvSize("GHOSTM_PILEUP_PART_HITS", kPileupPartDefault), UINT32_MAX);
+  const size_t budget = EnvSize("GHOSTM_PILEUP_SCRATCH_MB", 1024) << 20;
+  const size_t max_hits = EnvSize("GHOSTM_PILEUP_BATCH_HITS", (size_t)1 << 22);
+  const size_t upload_budget = (size_t)256 << 20;  // a batch's hit records, words and plan
+  const uint32_t t_lo = p0 / T, t_hi = (p1 - 1) / T + 1;
+  const std::vector<uint32_t> win =
+      PileupWindows((uint32_t)std::min<uint64_t>((uint64_t)(t_hi - t_lo) * T, UINT32_MAX), T, budget);
+  I.pileup_cols.Reserve(16);
+  unsigned long long *cols_d = I.pileup_cols.as<unsigned long long>();
+  HIP_CHECK(hipMemsetAsync(cols_d, 0, 16, S(stream_)));
+  std::vector<uint32_t> sel, words;
+  std::vector<kern::ReadPileupHit> hh;
+  PileupPlan plan;
+  for (size_t w = 0; w + 1 < win.size(); ++w) {
+    const uint32_t ta = t_lo + win[w], tb = t_lo + win[w + 1];
+    const uint32_t win0 = ta * T, win1 = (uint32_t)std::min<uint64_t>((uint64_t)tb * T, d->len);
+    const uint32_t npos = win1 - win0;
+    I.pileup_prof.Reserve((size_t)npos * kPileupSlots * 4);
+    HIP_CHECK(hipMemsetAsync(I.pileup_prof.p, 0, (size_t)npos * kPileupSlots * 4, S(stream_)));
+    for (size_t g = 0; g < ngroups; ++g) {
+      const ReadPileupGroup &G = groups[g];
+      // the group's hits that meet the window, in hit order
+      sel.clear();
+      for (uint32_t k = 0; k < G.n; ++k)
+        if (span[g][k] && G.rec[k].s_start < win1 && (uint64_t)G.rec[k].s_start + span[g][k] > win0) sel.push_back(k);
+      const uint32_t n = (uint32_t)sel.size();
+      for (uint32_t b0 = 0, b1 = 0; b0 < n; b0 = b1) {
+        // hits sel[b0, b1): an upload batch (hit_batches.h), cut by its records, words and list entries
+        size_t bytes = 0;
+        b1 = CutBatch(b0, n, max_hits, upload_budget, [&](uint32_t s) {
+          return sizeof(kern::ReadPileupHit) + 4 * (size_t)G.rec[sel[s]].n_runs + 4 * ((size_t)span[g][sel[s]] / T + 2);
+        }, &bytes);
+        const uint32_t m = b1 - b0;
+        if (!BuildPileupPlan(m, [&](uint32_t s) { return G.rec[sel[b0 + s]].s_start; },
+                             [&](uint32_t s) { return span[g][sel[b0 + s]]; }, T, ta, tb, P, &plan))
+          throw Error("read pileup: a batch's plan exceeds 2^32 - 1 entries (lower GHOSTM_PILEUP_BATCH_HITS)");
+        if (plan.parts.empty()) continue;
+        hh.resize(m);
+        words.clear();
+        for (uint32_t s = 0; s < m; ++s) {
+          const GhostmHitPath &p = G.rec[sel[b0 + s]];
+          const GhostmBandSource &bs = G.src[sel[b0 + s]];
+          hh[s] = kern::ReadPileupHit{kern::SourceRef{bs.first_record, bs.stride, bs.tiles, bs.letters}, p.q_start,
+                                      p.s_start, p.n_runs, 0, words.size()};
+          words.insert(words.end(), ops + p.ops_offset, ops + p.ops_offset + p.n_runs);
+        }
+        const size_t nparts = plan.parts.size();
+        I.pileup_hit.Reserve((size_t)m * sizeof(kern::ReadPileupHit));
+        I.pileup_ops.Reserve(words.size() * 4);
+        I.pileup_list.Reserve(plan.list.size() * 4);
+        I.pileup_part.Reserve(nparts * sizeof(PileupPart));
+        HIP_CHECK(hipMemcpyAsync(I.pileup_hit.p, hh.data(), (size_t)m * sizeof(kern::ReadPileupHit),
+                                 hipMemcpyHostToDevice, S(stream_)));
+        HIP_CHECK(hipMemcpyAsync(I.pileup_ops.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, S(stream_)));
+        HIP_CHECK(hipMemcpyAsync(I.pileup_list.p, plan.list.data(), plan.list.size() * 4, hipMemcpyHostToDevice,
+                                 S(stream_)));
+        HIP_CHECK(hipMemcpyAsync(I.pileup_part.p, plan.parts.data(), nparts * sizeof(PileupPart), hipMemcpyHostToDevice,
+                                 S(stream_)));
+        kern::ReadPileupArgs a{};
+        a.qseq = G.q->seq.as<uint8_t>();
+        a.W = G.q->L;
+        a.step = step;
+        a.hit = I.pileup_hit.as<kern::ReadPileupHit>();
+        a.ops = I.pileup_ops.as<uint32_t>();
+        a.list = I.pileup_list.as<uint32_t>();
+        a.part = I.pileup_part.as<kern::PileupPartArg>();
+        a.T = T;
+        a.win0 = win0;
+        a.win1 = win1;
+        a.profile = I.pileup_prof.as<uint32_t>();
+        a.counters = cols_d;
+        if (nparts > 0x7FFFFFFFu)
+          throw Error("read pileup: too many parts in one launch (lower GHOSTM_PILEUP_BATCH_HITS)");
+        const dim3 grid((uint32_t)nparts), block(kern::kTbBlock);  // one workgroup per (tile, part)
+        TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
+          if (frame) hipLaunchKernelGGL(kern::k_read_pileup<true>, grid, block, 0, S(stream_), a);
+          else hipLaunchKernelGGL(kern::k_read_pileup<false>, grid, block, 0, S(stream_), a);
+        });
+        HIP_CHECK(hipStreamSynchronize(S(stream_)));
+        times_.read_pileup += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+        times_.read_pileup_launches += 1;
+        times_.read_pileup_parts += nparts;
+      }
+    }
+    // the window's positions finished; those inside [p0, p1) go back
+    I.pileup_out.Reserve((size_t)npos * 13);
+    kern::PileupFinishArgs f{};
+    f.profile = I.pileup_prof.as<uint32_t>();
+    f.db = d->Residues() + win0;
+    f.n = npos;
+    f.depth = I.pileup_out.as<uint32_t>();
+    f.identities = f.depth + npos;
+    f.shifts = f.identities + npos;
+    f.consensus = reinterpret_cast<uint8_t *>(f.shifts + npos);
+    const dim3 fgrid((npos + kern::kTbBlock - 1) / kern::kTbBlock), block(kern::kTbBlock);
+    TimedLaunch(I.ev0, I.ev1, S(stream_),
+                [&] { hipLaunchKernelGGL(kern::k_pileup_finish<true>, fgrid, block, 0, S(stream_), f); });
+    const uint32_t c0 = std::max(win0, p0), c1 = std::min(win1, p1);
+    if (c0 < c1) {
+      const size_t cn = c1 - c0, from = c0 - win0, to = c0 - p0;
+      if (depth) HIP_CHECK(hipMemcpyAsync(depth + to, f.depth + from, cn * 4, hipMemcpyDeviceToHost, S(stream_)));
+      if (identities)
+        HIP_CHECK(hipMemcpyAsync(identities + to, f.identities + from, cn * 4, hipMemcpyDeviceToHost, S(stream_)));
+      if (consensus) HIP_CHECK(hipMemcpyAsync(consensus + to, f.consensus + from, cn, hipMemcpyDeviceToHost, S(stream_)));
+      if (shifts) HIP_CHECK(hipMemcpyAsync(shifts + to, f.shifts + from, cn * 4, hipMemcpyDeviceToHost, S(stream_)));
+      if (profile)
+        HIP_CHECK(hipMemcpyAsync(profile + to * kPileupSlots, f.profile + from * kPileupSlots, cn * kPileupSlots * 4,
+                                 hipMemcpyDeviceToHost, S(stream_)));
+    }
+    HIP_CHECK(hipStreamSynchronize(S(stream_)));
+    times_.read_pileup += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+    times_.read_pileup_windows += 1;
+  }
+  unsigned long long cols[2] = {0, 0};
+  HIP_CHECK(hipMemcpyAsync(cols, cols_d, 16, hipMemcpyDeviceToHost, S(stream_)));
+  HIP_CHECK(hipStreamSynchronize(S(stream_)));
+  times_.read_pileup_columns += cols[0];
+  times_.read_pileup_shifts += cols[1];
+}
+
 const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_amd/srchash.py)
 
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_pileup_finish/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_read_pileup/k_pileup_finish/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -3596,6 +3738,38 @@ int PathPileupGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPat
     SetError(e.what());
     return 1;
   }
+}
+
+int ReadPileupGpu(uint32_t nhits, const GhostmBandSource src[], const GhostmHitPath rec[], const uint32_t ops[],
+                  size_t ops_len, uint32_t query_sequence_length, uint32_t step, int frame, uint32_t db_len,
+                  uint32_t depth[], uint32_t identities[], uint8_t consensus[], uint32_t shifts[], uint32_t profile[]) {
+  try {
+    if (!depth || !identities || !consensus) throw Error("ReadPileupGpu: null: an output array");
+    if (nhits && (!src || !rec)) throw Error("ReadPileupGpu: null: an input array");
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    if (!r.query || !r.db) throw Error("SetQueryGpu/SetDbGpu not called");
+    if (query_sequence_length != r.query->L) throw Error("ReadPileupGpu: source: query shape differs from SetQueryGpu");
+    if (db_len != r.db->len) throw Error("ReadPileupGpu: db_len differs from the resident chunk's");
+    const DeviceModule::ReadPileupGroup g{r.query, nhits, src, rec};
+    DeviceModule::Get().ReadPileup(r.db, &g, 1, ops, ops_len, step, frame != 0, 0, db_len, depth, identities, consensus,
+                                   shifts, profile);
+    return 0;
+  } catch (std::exception &e) {
+    SetError(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmStageReadPileupStats(GhostmReadPileupStats *stats, size_t size) {
+  if (!stats) return 0;
+  RefState &r = Ref();
+  std::lock_guard<std::mutex> lk(r.mu);
+  const DeviceTimes &dt = DeviceModule::Get().times();
+  const GhostmReadPileupStats st{dt.read_pileup,       dt.read_pileup_launches, dt.read_pileup_windows,
+                                 dt.read_pileup_parts, dt.read_pileup_columns,  dt.read_pileup_shifts};
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadPileupStats)));
+  return sizeof(GhostmReadPileupStats);
 }
 
 }  // extern "C"

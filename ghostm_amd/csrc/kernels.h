@@ -3660,26 +3660,138 @@ __global__ __launch_bounds__(kTbBlock) void k_pileup(PileupArgs a) {
   if (lane == 0 && added) atomicAdd(a.columns, (unsigned long long)added);
 }
 
+// k_read_pileup<FRAME>: k_pileup for read-level paths (ReadPileupGpu,
+// include/ghostm_hip.h; host model read_pileup_host.cpp), the band pass's
+// (FRAME false) and the frame pass's (FRAME true). The plan, the histogram and
+// the column machinery are k_pileup's. Three things differ. The query letter
+// is read through the hit's source (SourceLetter), at a position scanned as
+// k_read_rows scans it: in FRAME mode in nucleotides and signed, modulo 2^32.
+// A shift column (ops 4 and 5) touches no subject residue and is charged to the
+// position the path stands at, its word's own scan value, in slot 27 or 28. So
+// a group of 64 words charges positions in [s0, s0 + ts], the upper end only by
+// a shift after its last residue, and is skipped only when s0 + ts < tile0. A
+// read-level path meets several tiles and is walked by one workgroup per tile
+// it meets, each charging its own positions only. The host has checked every
+// index (ValidateReadRows, ReadPileupSpans; the plan's tiles inside the window).
+struct ReadPileupHit {  // 40 bytes
+  SourceRef src;
+  uint32_t q_start, s_start, n_runs, pad;
+  unsigned long long ops_off;  // first word of the hit in ops
+};
+struct ReadPileupArgs {
+  const uint8_t *qseq;
+  uint32_t W, step;
+  const ReadPileupHit *hit;
+  const uint32_t *ops;
+  const uint32_t *list;          // the plan's hit slots, per tile
+  const PileupPartArg *part;     // one per workgroup
+  uint32_t T;                    // positions per tile, 32..kPileupTileMax
+  uint32_t win0, win1;           // the window's positions [win0, win1), win0 a multiple of T
+  uint32_t *profile;             // (win1 - win0) x 32
+  unsigned long long *counters;  // [0] += the '=', 'X' and 'D' columns added, [1] += the shift columns
+};
+
+template <bool FRAME>
+__global__ __launch_bounds__(kTbBlock) void k_read_pileup(ReadPileupArgs a) {
+  GHOSTM_POISON_LDS();
+  __shared__ uint32_t s_cnt[kPileupTileMax * kPileupStride];
+  for (uint32_t e = threadIdx.x; e < a.T * kPileupStride; e += kTbBlock) s_cnt[e] = 0;
+  __syncthreads();
+
+  const uint32_t lane = threadIdx.x & 63;
+  const PileupPartArg part = a.part[blockIdx.x];
+  const uint32_t tile0 = part.tile * a.T;
+  const uint32_t tile1 = a.win1 - tile0 < a.T ? a.win1 : tile0 + a.T;
+  uint32_t added = 0, shifted = 0;
+  for (uint32_t i = threadIdx.x >> 6; i < part.count; i += kTbBlock / 64) {  // wave-uniform
+    const ReadPileupHit hit = a.hit[a.list[part.first + i]];
+    const uint32_t *words = a.ops + hit.ops_off;
+    uint32_t col0 = 0, q0 = hit.q_start, s0 = hit.s_start;  // of the group's first run
+    for (uint32_t r0 = 0; r0 < hit.n_runs && s0 < tile1; r0 += 64) {
+      const uint32_t w = r0 + lane < hit.n_runs ? words[r0 + lane] : 0u;  // past the last run: length 0
+      const uint32_t len = w >> 4, op = w & 7u;
+      // the position's advance over the word, modulo 2^32
+      uint32_t adv = op <= 2u ? (FRAME ? 3u * len : len) : 0u;
+      if (FRAME && op == 4u) adv = len;
+      if (FRAME && op == 5u) adv = 0u - len;
+      uint32_t tc, tq, ts;
+      const uint32_t c = col0 + WaveExclusiveScan(len, &tc);
+      const uint32_t q = q0 + WaveExclusiveScan(adv, &tq);
+      const uint32_t s = s0 + WaveExclusiveScan(op <= 1u || op == 3u ? len : 0u, &ts);
+      const uint32_t c1 = col0 + tc;
+      if (s0 + ts >= tile0) {  // the group's residues, or a shift standing after them, meet the tile
+        for (uint32_t base = col0; base < c1; base += 64) {
+          const bool on = base + lane < c1;
+          const uint32_t col = on ? base + lane : c1 - 1;
+          // the last lane whose run begins at or before col (the lanes past the last run begin at c1)
+          uint32_t r = 0;
+#pragma unroll
+          for (uint32_t stp = 32; stp; stp >>= 1) {
+            const uint32_t v = (uint32_t)__shfl((int)c, (int)(r + stp));
+            if (v <= col) r += stp;
+          }
+          const uint32_t k = col - (uint32_t)__shfl((int)c, (int)r);
+          const uint32_t rq = (uint32_t)__shfl((int)q, (int)r), rs = (uint32_t)__shfl((int)s, (int)r);
+          const uint32_t rop = (uint32_t)__shfl((int)op, (int)r);
+          const bool shift = FRAME && rop >= 4u;
+          const uint32_t p = shift ? rs : rs + k;  // a shift column stands where the path stands
+          if (on && rop != 2u && p >= tile0 && p < tile1) {
+            uint32_t slot = shift ? 23u + rop : 26u;  // op 4: 27, op 5: 28
+            if (rop <= 1u) {
+              const uint32_t pq = rq + (FRAME ? 3u * k : k);
+              const uint32_t qc =
+                  a.qseq[FRAME ? SourceLetter(hit.src, pq % 3u, pq / 3u, a.W, a.step) : SourceLetter(hit.src, 0u, pq, a.W, a.step)];
+              slot = qc < 25u ? qc : 25u;
+            }
+            atomicAdd(&s_cnt[(p - tile0) * kPileupStride + slot], 1u);
+            if (shift) ++shifted;
+            else ++added;
+          }
+        }
+      }
+      col0 = c1;
+      q0 += tq;
+      s0 += ts;
+    }
+  }
+  __syncthreads();
+  uint32_t *out = a.profile + (size_t)(tile0 - a.win0) * 32;
+  for (uint32_t e = threadIdx.x; e < (tile1 - tile0) * 32; e += kTbBlock) {
+    const uint32_t v = s_cnt[(e >> 5) * kPileupStride + (e & 31u)];
+    if (v) atomicAdd(out + e, v);
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    added += __shfl_xor(added, d);
+    shifted += __shfl_xor(shifted, d);
+  }
+  if (lane == 0 && added) atomicAdd(a.counters, (unsigned long long)added);
+  if (lane == 0 && shifted) atomicAdd(a.counters + 1, (unsigned long long)shifted);
+}
+
 // k_pileup_finish: one thread per position of the window reads its counters as
 // 128-bit loads (seven: slots 28..31 are never set) and writes the position's depth (slots 0..26), its
 // identities (the slot of the DB residue) and its consensus (the largest of
 // slots 0..24, the lowest on a tie, 255 when they are all zero). It writes no
-// profile bytes.
+// profile bytes. SHIFTS (the read-level pile-up) reads an eighth load and also
+// writes shifts = slot 27 + slot 28.
 struct PileupFinishArgs {
   const uint32_t *profile;  // n x 32, 16-byte aligned
   const uint8_t *db;        // the window's first residue
   uint32_t n;
   uint32_t *depth, *identities;
   uint8_t *consensus;
+  uint32_t *shifts;         // SHIFTS only
 };
 
+template <bool SHIFTS = false>
 __global__ __launch_bounds__(kTbBlock) void k_pileup_finish(PileupFinishArgs a) {
   GHOSTM_POISON_LDS();
   const uint32_t i = blockIdx.x * kTbBlock + threadIdx.x;
   if (i >= a.n) return;
   const uint4 *row = reinterpret_cast<const uint4 *>(a.profile + (size_t)i * 32);
   const uint32_t code = a.db[i], mine = code < 25u ? code : 25u;
-  uint32_t sum = 0, best = 0, arg = 255, ident = 0;
+  uint32_t sum = 0, best = 0, arg = 255, ident = 0, shifts = 0;
 #pragma unroll
   for (uint32_t v = 0; v < 7; ++v) {
     const uint4 x = row[v];
@@ -3690,11 +3802,13 @@ __global__ __launch_bounds__(kTbBlock) void k_pileup_finish(PileupFinishArgs a) 
       if (slot < 27) sum += c[j];
       if (slot < 25 && c[j] > best) best = c[j], arg = slot;
       if (slot == mine) ident = c[j];
+      if (SHIFTS && slot == 27) shifts = c[j];
     }
   }
   a.depth[i] = sum;
   a.identities[i] = ident;
   a.consensus[i] = (uint8_t)arg;
+  if (SHIFTS) a.shifts[i] = shifts + row[7].x;
 }
 
 // FRAME (FINAL only, round 6): every key of column j is stored with FR_j =

@@ -31,15 +31,17 @@ static int Usage() {
             << "       -i queries -d database -o output\n"
             << "       (-y 6: BLAST-tabular, the twelve -outfmt 6 columns; -y 12: the -y 7 columns from the\n"
             << "        read-level alignment of a read longer than one record; -y 14 and -y 15: the -y 12 and\n"
-            << "        -y 13 lines with positives, qseq and sseq of the read-level alignment)\n"
+            << "        -y 13 lines with positives, qseq and sseq of the read-level alignment; -y 16 and -y 17: the\n"
+            << "        -y 10 and -y 11 subject pile-up from the read-level alignments; -y 18 and -y 19: the same\n"
+            << "        from the frameshift-aware alignments, with the subject's frameshift count)\n"
             << "search: ghostm search [aln options except -i -o -S -L] [-q d|p] [-w maxLength] [-c chunkSizeMB]\n"
             << "       (-d database | -f db.fasta [-k kSize] [-m chunkSizeMB]) q1.fasta out1 [q2.fasta out2 ...]\n"
             << "       (qry + aln per pair on one resident database; -q -w -c as qry's -t -l -L;\n"
             << "        -f: the database formatted on the GPU from FASTA, -k -m as db's -k -l)\n"
             << "       [-T tileStep [-X maxReadLength]]: reads longer than the record width searched as\n"
             << "        overlapping tiles tileStep letters apart, each read first cut at maxReadLength\n"
-            << "       [-B band]: the half-width of -y 12 to 15's band around a hit's diagonal, 1..31 (default 31)\n"
-            << "       [-F cost]: the frameshift cost of -y 13 and -y 15 (tiled DNA reads), 0 or more (default 15)\n"
+            << "       [-B band]: the half-width of -y 12 to 19's band around a hit's diagonal, 1..31 (default 31)\n"
+            << "       [-F cost]: the frameshift cost of -y 13, 15, 18 and 19 (tiled DNA reads), 0 or more (default 15)\n"
             << "synth: ghostm synth -d db.fasta -q queries.fasta [-n nq] [-N dbResidues] [-s seed]\n";
   return 1;
 }

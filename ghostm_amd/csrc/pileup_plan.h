@@ -11,7 +11,7 @@
 
 namespace ghostm {
 
-constexpr uint32_t kPileupSlots = 32;          // dwords of a profile row (slots 27..31 stay 0)
+constexpr uint32_t kPileupSlots = 32;          // dwords of a profile row (27, 28: the read-level pile-up's shifts; 29..31 stay 0)
 constexpr uint32_t kPileupTileMin = 32;        // GHOSTM_PILEUP_TILE's range; the upper end is the
 constexpr uint32_t kPileupTileMax = 256;       // kernel's LDS histogram (256 x 33 dwords = 33 KB)
 // The defaults, from tools/bench_pileup.py --sweep 64,128,256:128,512,2048 on

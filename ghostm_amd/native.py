@@ -179,6 +179,29 @@ class GhostmSubjectPileup(ctypes.Structure):
     ]
 
 
+class GhostmSubjectReadPileup(ctypes.Structure):
+    """one subject's summary of the read-level pile-up (48 bytes):
+    GhostmSubjectPileup's fields, then the summed shift columns."""
+
+    _fields_ = GhostmSubjectPileup._fields_ + [
+        ("shifts_sum", c_uint64),
+    ]
+
+
+class GhostmReadPileupStats(ctypes.Structure):
+    """the counters of the read-level pile-up (GhostmSessionReadPileupStats,
+    GhostmStageReadPileupStats)."""
+
+    _fields_ = [
+        ("seconds_read_pileup", ctypes.c_double),
+        ("read_pileup_launches", c_uint64),
+        ("read_pileup_windows", c_uint64),
+        ("read_pileup_parts", c_uint64),
+        ("read_pileup_columns", c_uint64),
+        ("read_pileup_shifts", c_uint64),
+    ]
+
+
 class GhostmDbChunkInfo(ctypes.Structure):
     """one resident DB chunk: the values of its .inf and .ind headers."""
 
@@ -342,6 +365,12 @@ SIGNATURES = {
                                    c_size_t, c_uint32, c_uint32, c_int, c_int, c_int, c_int,
                                    POINTER(GhostmHitReadRows), POINTER(ctypes.c_uint8), c_size_t, POINTER(c_size_t)]),
     "GhostmStageReadRowsStats": (c_size_t, [POINTER(GhostmReadRowsStats), c_size_t]),
+    "ReadPileupGpu": (c_int, [c_uint32, POINTER(GhostmBandSource), POINTER(GhostmHitPath), u32p, c_size_t, c_uint32,
+                              c_uint32, c_int, c_uint32, u32p, u32p, POINTER(ctypes.c_uint8), u32p, u32p]),
+    "GhostmReadPileupHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, POINTER(ctypes.c_uint8), c_uint32,
+                                     c_uint32, POINTER(GhostmBandSource), POINTER(GhostmHitPath), u32p, c_size_t,
+                                     c_uint32, c_uint32, c_int, u32p, u32p, POINTER(ctypes.c_uint8), u32p, u32p]),
+    "GhostmStageReadPileupStats": (c_size_t, [POINTER(GhostmReadPileupStats), c_size_t]),
     "GhostmBuildIndexGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, u32p, u32p, u32p, c_int,
                                     POINTER(c_float)]),
     "GhostmFormatQueriesGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_uint32,
@@ -407,6 +436,10 @@ SIGNATURES = {
     "GhostmSessionPileup": (c_size_t, [c_void_p, POINTER(GhostmSubjectPileup), c_size_t]),
     "GhostmSessionPileupArrays": (c_size_t, [c_void_p, u32p, u32p, POINTER(ctypes.c_uint8), c_size_t]),
     "GhostmSessionSubjectProfile": (c_size_t, [c_void_p, c_uint32, u32p, c_size_t]),
+    "GhostmSessionReadPileup": (c_size_t, [c_void_p, c_int, POINTER(GhostmSubjectReadPileup), c_size_t]),
+    "GhostmSessionReadPileupArrays": (c_size_t, [c_void_p, c_int, u32p, u32p, POINTER(ctypes.c_uint8), u32p, c_size_t]),
+    "GhostmSessionReadSubjectProfile": (c_size_t, [c_void_p, c_int, c_uint32, u32p, c_size_t]),
+    "GhostmSessionReadPileupStats": (c_size_t, [c_void_p, POINTER(GhostmReadPileupStats), c_size_t]),
     "GhostmSessionDeviceHits": (c_size_t, [c_void_p, c_void_p, c_size_t]),
     "GhostmSessionStats": (c_int, [c_void_p, POINTER(GhostmStats)]),
     "GhostmSessionStatsSized": (c_size_t, [c_void_p, POINTER(GhostmStats), c_size_t]),

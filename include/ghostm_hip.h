@@ -897,6 +897,91 @@ typedef struct GhostmReadRowsStats {
  * conventions. */
 size_t GhostmStageReadRowsStats(GhostmReadRowsStats *stats, size_t size);
 
+/* The read-level subject pile-up: PathPileupGpu's view (its definitions: 32
+ * uint32_t per position, slot(c), depth, identities, consensus, integer sums
+ * only) from read-level paths, so a read adds depth over its whole alignment
+ * and not over one tile's 127 letters. These points differ.
+ *   source letters   a hit is a GhostmBandSource and a GhostmHitPath (q_start,
+ *                    s_start absolute in the chunk, n_runs words at
+ *                    ops[ops_offset]) as for ReadRowsGpu, and its query letters
+ *                    are read through the source by ReadRowsGpu's rules: band
+ *                    mode (frame 0) the letter at the position, advancing by 1;
+ *                    frame mode (frame 1) letter p / 3 of frame p % 3,
+ *                    advancing by 3
+ *   columns          a column of op 0 or 1 at subject position s adds 1 to
+ *                    profile[s][slot(query code)], op 3 adds 1 to
+ *                    profile[s][26], op 2 adds nothing
+ *   shift columns    (frame mode) a column of op 4 moves the strand position
+ *                    by +1, of op 5 by -1, and touches no subject residue. It
+ *                    is charged to the position the path stands at, s =
+ *                    rec.s_start + the subject residues of the columns before
+ *                    it: 1 to profile[s][27] for op 4, to profile[s][28] for op
+ *                    5. In a path FrameAlignGpu made that is the residue of the
+ *                    column after the shift (a shift never ends a path); a
+ *                    hand-made path that ends in a shift charges the position
+ *                    one past its last residue. Slots 27 and 28 are not part of
+ *                    depth. Band mode leaves slots 27..31 at 0, frame mode
+ *                    29..31.
+ *   shifts[s]        = profile[s][27] + profile[s][28]; shifts may be NULL
+ * A hit with an empty path adds nothing.
+ *
+ * ReadPileupGpu (kernels k_read_pileup and k_pileup_finish) is stage level like
+ * PathPileupGpu and ReadRowsGpu (after SetQueryGpu and SetDbGpu).
+ * query_sequence_length is the records' width W, step the tile step. db_len
+ * must be the resident chunk's length; depth, identities, consensus and shifts
+ * hold db_len elements, profile db_len * 32 or is NULL. nhits == 0 gives zeros
+ * and 255s. Everything is checked on the host before any upload or launch; a
+ * refused call leaves every output untouched and names its reason in
+ * GhostmGetLastError: ReadRowsGpu's "source", "ops", "word" and "bounds" by the
+ * same validation ("bounds" also for a shift column whose position is >=
+ * db_len), and PathPileupGpu's "db_len" and "null". The tiles, parts, windows
+ * and upload batches are PathPileupGpu's, under the same GHOSTM_PILEUP_*
+ * variables; a path is walked once by every tile it meets. 9 bytes per
+ * position are read back, 13 with shifts. */
+int ReadPileupGpu(uint32_t nhits, const GhostmBandSource src[], const GhostmHitPath rec[],
+                  const uint32_t ops[], size_t ops_len, uint32_t query_sequence_length, uint32_t step,
+                  int frame, uint32_t db_len, uint32_t depth[], uint32_t identities[],
+                  uint8_t consensus[], uint32_t shifts[], uint32_t profile[]);
+
+/* The same on the host, with no device call (the model the kernels equal
+ * exactly, written column by column) and the same checks and reasons:
+ * query_seqs = nq records of L codes, db = the chunk's db_len residues;
+ * query_sequence_length must equal L ("source"). */
+int GhostmReadPileupHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, const uint8_t *db,
+                         uint32_t db_len, uint32_t nhits, const GhostmBandSource src[],
+                         const GhostmHitPath rec[], const uint32_t ops[], size_t ops_len,
+                         uint32_t query_sequence_length, uint32_t step, int frame, uint32_t depth[],
+                         uint32_t identities[], uint8_t consensus[], uint32_t shifts[],
+                         uint32_t profile[]);
+
+/* The counters of the read-level pile-up, a struct of their own like
+ * GhostmBandStats; GhostmStats' pileup_* fields count PathPileupGpu only. */
+typedef struct GhostmReadPileupStats {
+  double seconds_read_pileup;    /* k_read_pileup + k_pileup_finish, device time */
+  uint64_t read_pileup_launches; /* k_read_pileup launches */
+  uint64_t read_pileup_windows;  /* profile windows */
+  uint64_t read_pileup_parts;    /* (tile, part) workgroups */
+  uint64_t read_pileup_columns;  /* '=', 'X' and 'D' columns charged */
+  uint64_t read_pileup_shifts;   /* shift columns charged */
+} GhostmReadPileupStats;
+
+/* The read-level pile-up counters behind the stage-level calls;
+ * GhostmStageBandStats' conventions. */
+size_t GhostmStageReadPileupStats(GhostmReadPileupStats *stats, size_t size);
+
+/* One subject's summary of the session-level read pile-up
+ * (GhostmSessionReadPileup). */
+typedef struct GhostmSubjectReadPileup {  /* 48 bytes; the first 40 are GhostmSubjectPileup's */
+  uint32_t length;
+  uint32_t hits;
+  uint32_t covered;
+  uint32_t max_depth;
+  uint64_t depth_sum;
+  uint64_t identities_sum;
+  uint64_t offset;
+  uint64_t shifts_sum;      /* the sum of shifts over the subject; 0 in band mode */
+} GhostmSubjectReadPileup;
+
 /* A session without a database: `aln`'s options without -d (giving it is an
  * error). With -i the query chunks are loaded as GhostmSessionCreate loads
  * them; without -i the session starts with neither input and the queries come
@@ -1090,7 +1175,13 @@ int GhostmSessionRun(void *session);
  * frameshifts is the summed length of the shift runs; evalue and bitscore are
  * priced as -y 12 prices them, for a query of m letters. A hit whose frame
  * score is 0 prints its tile path in the same units (strand positions
- * 3 x (offset + q) + g, the end + 2, frameshifts 0). Hits are not re-ranked. */
+ * 3 x (offset + q) + g, the end + 2, frameshifts 0). Hits are not re-ranked.
+ * -y 16 and -y 17 are the -y 10 and -y 11 lines from the read-level pile-up of
+ * the band paths (GhostmSessionReadPileup with frame = 0). -y 18 (DNA sets of a
+ * tiled setter only, as -y 13) is the -y 10 line from the pile-up of the frame
+ * paths with an eighth column, shifts_sum; -y 19 is the -y 18 line and a ninth
+ * column, the consensus text as -y 11 writes it. Like -y 10 they print no
+ * E-value and are written at the end of the run. */
 int GhostmSessionRunToFile(void *session);
 
 /* Formatted output of the last run (reference WriteOutput/V1/V2 text). With
@@ -1244,6 +1335,31 @@ size_t GhostmSessionPileupArrays(void *session, uint32_t *depth, uint32_t *ident
  * count), made on demand by the same kernels on that subject's hits only;
  * nothing is kept. (size_t)-1 on error (a db_id outside the loaded chunks). */
 size_t GhostmSessionSubjectProfile(void *session, uint32_t db_id, uint32_t *profile, size_t cap);
+
+/* The read-level pile-up of the last run's hits (the definitions above
+ * ReadPileupGpu): GhostmSessionPileup's three calls on the read-level paths,
+ * frame = 0 those of GhostmSessionHitsBand, frame = 1 those of
+ * GhostmSessionHitsFrame, with the sources those passes aligned and the subject
+ * coordinates made absolute in the chunk again. The conventions are
+ * GhostmSessionPileup*'s; shifts is a fourth array (NULL is skipped; all 0 with
+ * frame = 0). frame = 1 is refused where GhostmSessionHitsFrame is. A hit of
+ * read-level score 0 counts in hits and adds nothing. Computed on first use and
+ * kept as long as the paths they were made from: until the next run,
+ * GhostmSessionSetQueries*, GhostmSessionSetDb*, a change of band and, for
+ * frame = 1, of the frameshift cost. A shard session piles up its own hits:
+ * depth, identities, shifts, the profile and the sums add up across the ranks;
+ * covered, max_depth and consensus do not. GhostmSessionReadSubjectProfile
+ * keeps nothing, like GhostmSessionSubjectProfile. */
+size_t GhostmSessionReadPileup(void *session, int frame, GhostmSubjectReadPileup *subj, size_t cap);
+size_t GhostmSessionReadPileupArrays(void *session, int frame, uint32_t *depth, uint32_t *identities,
+                                     uint8_t *consensus, uint32_t *shifts, size_t cap);
+size_t GhostmSessionReadSubjectProfile(void *session, int frame, uint32_t db_id, uint32_t *profile,
+                                       size_t cap);
+
+/* The read-level pile-up counters of the session since its last run (all 0
+ * until the read-level pile-up is asked for); the size convention of
+ * GhostmSessionBandStats. */
+size_t GhostmSessionReadPileupStats(void *session, GhostmReadPileupStats *stats, size_t size);
 
 /* The same records resident on the session's GPU, for a device-to-device
  * gather across ranks: copies min(n, cap) records to dst_device
