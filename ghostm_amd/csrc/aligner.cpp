@@ -1499,6 +1499,20 @@ const LineFormat &Session::Format() {
   return *format_;
 }
 
+// What a pass added to the device's counters: dst.*to += after.*from - before.*from
+// for every (to, from) pair of members.
+template <class Dst, class... To, class... From>
+static void AddDeltas(Dst &dst, const DeviceTimes &before, const DeviceTimes &after,
+                      std::pair<To Dst::*, From DeviceTimes::*>... m) {
+  ((dst.*m.first += after.*m.second - before.*m.second), ...);
+}
+
+// The index of the tile at `offset` within its source of m letters and `tiles`
+// tiles (query_tiles.h: the last tile ends with the source).
+static uint32_t TileIndex(uint32_t offset, uint32_t tiles, uint32_t m, uint32_t W, uint32_t step) {
+  return offset == TileStart(tiles - 1, tiles, m, W, step) ? tiles - 1 : offset / step;
+}
+
 uint32_t Session::TbBase(const QueryData &q) const {
   return q.chunk.L + 2 * opt_.extend * 2 * (1u << opt_.log_region);
 }
@@ -1514,6 +1528,53 @@ template <class Item, class F> void Session::ForChunkPairs(const std::vector<std
   for (size_t qi = 0; qi < queries_.size(); ++qi)
     for (size_t di = 0; di < dbs_.size(); ++di)
       if (!groups[qi * dbs_.size() + di].empty()) fn(qi, di, groups[qi * dbs_.size() + di]);
+}
+
+// The words in hit order: hit h's words leave its chunk pair's words[qi *
+// dbs_.size() + di], where (*path)[h].ops_offset still points, for *ops.
+void Session::JoinWords(const std::vector<std::vector<uint32_t>> &words, std::vector<GhostmHitPath> *path,
+                        std::vector<uint32_t> *ops) const {
+  for (size_t h = 0; h < path->size(); ++h) {
+    GhostmHitPath &p = (*path)[h];
+    const std::vector<uint32_t> &w = words[hit_source_[h].qi * dbs_.size() + hit_source_[h].di];
+    const size_t at = ops->size();
+    ops->insert(ops->end(), w.begin() + p.ops_offset, w.begin() + p.ops_offset + p.n_runs);
+    p.ops_offset = at;
+  }
+}
+
+// The rows passes' plan (HitsRows, HitsReadRows): the hits' column counts give
+// every hit its place in hit order and *bytes its size; then per (query chunk,
+// DB chunk) call(qi, di, items, rec, dst) with the items' paths, their subject
+// coordinates absolute in the chunk again, and their places.
+template <class Call>
+void Session::RowsPlan(const std::vector<GhostmHitPath> &path, const std::vector<uint32_t> &words,
+                       std::vector<uint8_t> *bytes, Call call) {
+  const std::vector<GhostmHit> &hits = Hits();
+  std::vector<uint64_t> place(hits.size());
+  uint64_t total = 0;
+  for (size_t h = 0; h < hits.size(); ++h) {
+    uint64_t cols = 0;
+    for (uint32_t r = 0; r < path[h].n_runs; ++r) cols += words[path[h].ops_offset + r] >> 4;
+    place[h] = total;
+    total += 3 * cols;
+  }
+  bytes->assign(total, 0);
+  std::vector<uint64_t> dst;
+  std::vector<GhostmHitPath> rec;
+  ForChunkPairs(HitsByChunkPair(), [&](size_t qi, size_t di, const std::vector<size_t> &items) {
+    dst.clear();
+    rec.clear();
+    for (size_t h : items) {
+      GhostmHitPath p = path[h];
+      const uint32_t pos = dbs_[di].chunk.starts[hits[h].db_id - dbs_[di].global_base];
+      p.s_start += pos;
+      p.s_end += pos;
+      dst.push_back(place[h]);
+      rec.push_back(p);
+    }
+    call(qi, di, items, rec, dst);
+  });
 }
 
 template <class Extra, class Line> void Session::RewriteLines(const char *what, int tabs, Extra extra, Line line) {
@@ -1625,10 +1686,9 @@ const std::vector<GhostmHitExt> &Session::HitsExt() {
       if (!found) throw Error("extended traceback: no query of the hit's name group reproduces its alignment");
     }
   });
-  const DeviceTimes &after = dev.times();
-  stats_.seconds_traceback_ext += after.traceback_ext - before.traceback_ext;
-  stats_.traceback_ext_launches += after.traceback_ext_launches - before.traceback_ext_launches;
-  stats_.traceback_ext_cells += after.traceback_ext_cells - before.traceback_ext_cells;
+  AddDeltas(stats_, before, dev.times(), std::make_pair(&GhostmStats::seconds_traceback_ext, &DeviceTimes::traceback_ext),
+            std::make_pair(&GhostmStats::traceback_ext_launches, &DeviceTimes::traceback_ext_launches),
+            std::make_pair(&GhostmStats::traceback_ext_cells, &DeviceTimes::traceback_ext_cells));
   hits_ext_valid_ = true;
   return hits_ext_;
 }
@@ -1674,19 +1734,12 @@ const std::vector<GhostmHitPath> &Session::HitsPath() {
       hits_path_[items[k]] = p;  // ops_offset: still within the chunk pair's words
     }
   });
-  // the words in hit order
-  for (size_t h = 0; h < hits.size(); ++h) {
-    GhostmHitPath &p = hits_path_[h];
-    const std::vector<uint32_t> &w = words[hit_source_[h].qi * dbs_.size() + hit_source_[h].di];
-    const size_t at = path_ops_.size();
-    path_ops_.insert(path_ops_.end(), w.begin() + p.ops_offset, w.begin() + p.ops_offset + p.n_runs);
-    p.ops_offset = at;
-  }
-  const DeviceTimes &after = dev.times();
-  stats_.seconds_traceback_path += after.traceback_path - before.traceback_path;
-  stats_.traceback_path_launches += after.traceback_path_launches - before.traceback_path_launches;
-  stats_.traceback_path_cells += after.traceback_path_cells - before.traceback_path_cells;
-  stats_.traceback_path_dir_bytes += after.traceback_path_dir_bytes - before.traceback_path_dir_bytes;
+  JoinWords(words, &hits_path_, &path_ops_);
+  AddDeltas(stats_, before, dev.times(),
+            std::make_pair(&GhostmStats::seconds_traceback_path, &DeviceTimes::traceback_path),
+            std::make_pair(&GhostmStats::traceback_path_launches, &DeviceTimes::traceback_path_launches),
+            std::make_pair(&GhostmStats::traceback_path_cells, &DeviceTimes::traceback_path_cells),
+            std::make_pair(&GhostmStats::traceback_path_dir_bytes, &DeviceTimes::traceback_path_dir_bytes));
   hits_path_valid_ = true;
   return hits_path_;
 }
@@ -1765,47 +1818,25 @@ void Session::FormatPathTabular(bool read_level) {
 const std::vector<GhostmHitRows> &Session::HitsRows() {
   if (hits_rows_valid_) return hits_rows_;
   const std::vector<GhostmHitPath> &path = HitsPath();
-  const std::vector<GhostmHit> &hits = Hits();
-  hits_rows_.assign(hits.size(), GhostmHitRows{0, 0, 0, 0, 0, 0, 0});
-  std::vector<uint64_t> place(hits.size());
-  uint64_t total = 0;
-  for (size_t h = 0; h < hits.size(); ++h) {
-    uint64_t cols = 0;
-    for (uint32_t r = 0; r < path[h].n_runs; ++r) cols += path_ops_[path[h].ops_offset + r] >> 4;
-    place[h] = total;
-    total += 3 * cols;
-  }
-  row_bytes_.assign(total, 0);
+  hits_rows_.assign(Hits().size(), GhostmHitRows{0, 0, 0, 0, 0, 0, 0});
   DeviceModule &dev = DeviceModule::Get();
   const DeviceTimes before = dev.times();
   std::vector<uint32_t> qid;
-  std::vector<uint64_t> dst;
-  std::vector<GhostmHitPath> rec;
   std::vector<GhostmHitRows> out;
-  ForChunkPairs(HitsByChunkPair(), [&](size_t qi, size_t di, const std::vector<size_t> &items) {
+  RowsPlan(path, path_ops_, &row_bytes_, [&](size_t qi, size_t di, const std::vector<size_t> &items,
+                                             const std::vector<GhostmHitPath> &rec, const std::vector<uint64_t> &dst) {
     qid.clear();
-    dst.clear();
-    rec.clear();
-    for (size_t h : items) {
-      GhostmHitPath p = path[h];
-      const uint32_t pos = dbs_[di].chunk.starts[hits[h].db_id - dbs_[di].global_base];
-      p.s_start += pos;
-      p.s_end += pos;
-      qid.push_back(hit_source_[h].query);
-      dst.push_back(place[h]);
-      rec.push_back(p);
-    }
+    for (size_t h : items) qid.push_back(hit_source_[h].query);
     out.resize(items.size());
     dev.PathRows(queries_[qi].dev, dbs_[di].dev, (uint32_t)items.size(), qid.data(), rec.data(), path_ops_.data(),
                  path_ops_.size(), opt_.open_gap, opt_.extend_gap, queries_[qi].global_base, out.data(),
                  row_bytes_.data(), row_bytes_.size(), dst.data());
     for (size_t k = 0; k < items.size(); ++k) hits_rows_[items[k]] = out[k];
   });
-  const DeviceTimes &after = dev.times();
-  stats_.seconds_path_rows += after.path_rows - before.path_rows;
-  stats_.path_rows_launches += after.path_rows_launches - before.path_rows_launches;
-  stats_.path_rows_columns += after.path_rows_columns - before.path_rows_columns;
-  stats_.path_rows_bytes += after.path_rows_bytes - before.path_rows_bytes;
+  AddDeltas(stats_, before, dev.times(), std::make_pair(&GhostmStats::seconds_path_rows, &DeviceTimes::path_rows),
+            std::make_pair(&GhostmStats::path_rows_launches, &DeviceTimes::path_rows_launches),
+            std::make_pair(&GhostmStats::path_rows_columns, &DeviceTimes::path_rows_columns),
+            std::make_pair(&GhostmStats::path_rows_bytes, &DeviceTimes::path_rows_bytes));
   hits_rows_valid_ = true;
   return hits_rows_;
 }
@@ -1824,7 +1855,7 @@ void Session::SetBand(uint32_t band) {
   band_src_.clear();
   hits_band_valid_ = false;
   read_rows_[0].Drop();
-  read_pileup_[0].Drop();
+  pileup_[kBandLevel].Drop();
   DropFrameResults();  // the frame pass runs inside the same band
 }
 
@@ -1866,7 +1897,7 @@ const std::vector<GhostmHitPath> &Session::HitsBand() {
         const GhostmQueryTile &t = tile_table_[q.global_base + local];
         const uint32_t m = std::max(t.letters, 1u), tiles = TileCount(m, W, step);
         offset = t.offset;
-        const uint32_t index = offset == TileStart(tiles - 1, tiles, m, W, step) ? tiles - 1 : offset / step;
+        const uint32_t index = TileIndex(offset, tiles, m, W, step);
         const uint32_t stride = tile_dna_ ? 6u : 1u;
         if ((uint64_t)index * stride > local) throw Error("band align: a tile before its chunk's first record");
         s = GhostmBandSource{local - index * stride, stride, tiles, m};
@@ -1891,20 +1922,12 @@ const std::vector<GhostmHitPath> &Session::HitsBand() {
       band_src_[items[k]] = src[k];
     }
   });
-  // the words in hit order
-  for (size_t h = 0; h < hits.size(); ++h) {
-    GhostmHitPath &p = hits_band_[h];
-    const std::vector<uint32_t> &w = words[hit_source_[h].qi * dbs_.size() + hit_source_[h].di];
-    const size_t at = band_ops_.size();
-    band_ops_.insert(band_ops_.end(), w.begin() + p.ops_offset, w.begin() + p.ops_offset + p.n_runs);
-    p.ops_offset = at;
-  }
-  const DeviceTimes &after = dev.times();
-  band_stats_.seconds_band += after.band - before.band;
-  band_stats_.band_launches += after.band_launches - before.band_launches;
-  band_stats_.band_hits += after.band_hits - before.band_hits;
-  band_stats_.band_cells += after.band_cells - before.band_cells;
-  band_stats_.band_dir_bytes += after.band_dir_bytes - before.band_dir_bytes;
+  JoinWords(words, &hits_band_, &band_ops_);
+  AddDeltas(band_stats_, before, dev.times(), std::make_pair(&GhostmBandStats::seconds_band, &DeviceTimes::band),
+            std::make_pair(&GhostmBandStats::band_launches, &DeviceTimes::band_launches),
+            std::make_pair(&GhostmBandStats::band_hits, &DeviceTimes::band_hits),
+            std::make_pair(&GhostmBandStats::band_cells, &DeviceTimes::band_cells),
+            std::make_pair(&GhostmBandStats::band_dir_bytes, &DeviceTimes::band_dir_bytes));
   hits_band_valid_ = true;
   return hits_band_;
 }
@@ -1921,7 +1944,7 @@ void Session::DropFrameResults() {
   frame_src_.clear();
   hits_frame_valid_ = false;
   read_rows_[1].Drop();
-  read_pileup_[1].Drop();
+  pileup_[kFrameLevel].Drop();
 }
 
 void Session::SetFrameShift(int shift) {
@@ -1968,7 +1991,7 @@ const std::vector<GhostmHitPath> &Session::HitsFrame() {
       const uint32_t local = hit_source_[h].query;
       const GhostmQueryTile &t = tile_table_[q.global_base + local];
       const uint32_t m = std::max(t.letters, 1u), tiles = TileCount(m, W, step);
-      const uint32_t index = t.offset == TileStart(tiles - 1, tiles, m, W, step) ? tiles - 1 : t.offset / step;
+      const uint32_t index = TileIndex(t.offset, tiles, m, W, step);
       const uint32_t back = index * 6 + t.frame % 3;
       if (back > local) throw Error("frame align: a tile before its chunk's first record");
       const uint32_t subject = hits[h].db_id - d.global_base, pos = d.chunk.starts[subject];
@@ -1990,22 +2013,18 @@ const std::vector<GhostmHitPath> &Session::HitsFrame() {
       frame_src_[items[k]] = src[k];
     }
   });
-  // the words in hit order, and every path's shifts
-  for (size_t h = 0; h < hits.size(); ++h) {
-    GhostmHitPath &p = hits_frame_[h];
-    const std::vector<uint32_t> &w = words[hit_source_[h].qi * dbs_.size() + hit_source_[h].di];
-    const size_t at = frame_ops_.size();
-    frame_ops_.insert(frame_ops_.end(), w.begin() + p.ops_offset, w.begin() + p.ops_offset + p.n_runs);
-    p.ops_offset = at;
-    for (size_t r = at; r < frame_ops_.size(); ++r)
-      if ((frame_ops_[r] & 15u) >= 4) frame_info_[h].shifts += frame_ops_[r] >> 4;
-  }
-  const DeviceTimes &after = dev.times();
-  frame_stats_.seconds_frame += after.frame - before.frame;
-  frame_stats_.frame_launches += after.frame_launches - before.frame_launches;
-  frame_stats_.frame_hits += after.frame_hits - before.frame_hits;
-  frame_stats_.frame_cells += after.frame_cells - before.frame_cells;
-  frame_stats_.frame_dir_bytes += after.frame_dir_bytes - before.frame_dir_bytes;
+  JoinWords(words, &hits_frame_, &frame_ops_);
+  // every path's shifts
+  for (size_t h = 0; h < hits.size(); ++h)
+    for (uint32_t r = 0; r < hits_frame_[h].n_runs; ++r) {
+      const uint32_t word = frame_ops_[hits_frame_[h].ops_offset + r];
+      if ((word & 15u) >= 4) frame_info_[h].shifts += word >> 4;
+    }
+  AddDeltas(frame_stats_, before, dev.times(), std::make_pair(&GhostmFrameStats::seconds_frame, &DeviceTimes::frame),
+            std::make_pair(&GhostmFrameStats::frame_launches, &DeviceTimes::frame_launches),
+            std::make_pair(&GhostmFrameStats::frame_hits, &DeviceTimes::frame_hits),
+            std::make_pair(&GhostmFrameStats::frame_cells, &DeviceTimes::frame_cells),
+            std::make_pair(&GhostmFrameStats::frame_dir_bytes, &DeviceTimes::frame_dir_bytes));
   hits_frame_valid_ = true;
   return hits_frame_;
 }
@@ -2031,36 +2050,15 @@ const std::vector<GhostmHitReadRows> &Session::HitsReadRows(bool frame) {
   const std::vector<GhostmHitPath> &path = frame ? HitsFrame() : HitsBand();
   const std::vector<uint32_t> &words = frame ? frame_ops_ : band_ops_;
   const std::vector<GhostmBandSource> &source = frame ? frame_src_ : band_src_;
-  const std::vector<GhostmHit> &hits = Hits();
-  res.rec.assign(hits.size(), GhostmHitReadRows{0, 0, 0, 0, 0, 0, 0, 0, 0});
-  std::vector<uint64_t> place(hits.size());
-  uint64_t total = 0;
-  for (size_t h = 0; h < hits.size(); ++h) {
-    uint64_t cols = 0;
-    for (uint32_t r = 0; r < path[h].n_runs; ++r) cols += words[path[h].ops_offset + r] >> 4;
-    place[h] = total;
-    total += 3 * cols;
-  }
-  res.bytes.assign(total, 0);
+  res.rec.assign(Hits().size(), GhostmHitReadRows{0, 0, 0, 0, 0, 0, 0, 0, 0});
   DeviceModule &dev = DeviceModule::Get();
   const DeviceTimes before = dev.times();
   std::vector<GhostmBandSource> src;
-  std::vector<uint64_t> dst;
-  std::vector<GhostmHitPath> rec;
   std::vector<GhostmHitReadRows> out;
-  ForChunkPairs(HitsByChunkPair(), [&](size_t qi, size_t di, const std::vector<size_t> &items) {
+  RowsPlan(path, words, &res.bytes, [&](size_t qi, size_t di, const std::vector<size_t> &items,
+                                        const std::vector<GhostmHitPath> &rec, const std::vector<uint64_t> &dst) {
     src.clear();
-    dst.clear();
-    rec.clear();
-    for (size_t h : items) {
-      GhostmHitPath p = path[h];
-      const uint32_t pos = dbs_[di].chunk.starts[hits[h].db_id - dbs_[di].global_base];
-      p.s_start += pos;
-      p.s_end += pos;
-      src.push_back(source[h]);
-      dst.push_back(place[h]);
-      rec.push_back(p);
-    }
+    for (size_t h : items) src.push_back(source[h]);
     out.resize(items.size());
     const uint32_t W = queries_[qi].chunk.L, step = tile_step_ ? tile_step_ : W;
     dev.ReadRows(queries_[qi].dev, dbs_[di].dev, (uint32_t)items.size(), src.data(), rec.data(), words.data(),
@@ -2068,11 +2066,11 @@ const std::vector<GhostmHitReadRows> &Session::HitsReadRows(bool frame) {
                  out.data(), res.bytes.data(), res.bytes.size(), dst.data());
     for (size_t k = 0; k < items.size(); ++k) res.rec[items[k]] = out[k];
   });
-  const DeviceTimes &after = dev.times();
-  read_rows_stats_.seconds_read_rows += after.read_rows - before.read_rows;
-  read_rows_stats_.read_rows_launches += after.read_rows_launches - before.read_rows_launches;
-  read_rows_stats_.read_rows_hits += after.read_rows_hits - before.read_rows_hits;
-  read_rows_stats_.read_rows_columns += after.read_rows_columns - before.read_rows_columns;
+  AddDeltas(read_rows_stats_, before, dev.times(),
+            std::make_pair(&GhostmReadRowsStats::seconds_read_rows, &DeviceTimes::read_rows),
+            std::make_pair(&GhostmReadRowsStats::read_rows_launches, &DeviceTimes::read_rows_launches),
+            std::make_pair(&GhostmReadRowsStats::read_rows_hits, &DeviceTimes::read_rows_hits),
+            std::make_pair(&GhostmReadRowsStats::read_rows_columns, &DeviceTimes::read_rows_columns));
   res.valid = true;
   return res.rec;
 }
@@ -2188,180 +2186,23 @@ uint32_t Session::SubjectLength(const DbData &d, uint32_t subject) const {
   return next - d.chunk.starts[subject] - 1;
 }
 
-void Session::PileupChunk(size_t di, const std::vector<size_t> &items, uint32_t p0, uint32_t p1, uint32_t *depth,
-                          uint32_t *identities, uint8_t *consensus, uint32_t *profile) {
-  const std::vector<GhostmHitPath> &path = HitsPath();
-  const std::vector<GhostmHit> &hits = Hits();
-  // the hits by query chunk, their subject coordinates absolute in the chunk again
-  std::vector<std::vector<uint32_t>> qid(queries_.size());
-  std::vector<std::vector<GhostmHitPath>> rec(queries_.size());
-  for (size_t h : items) {
-    GhostmHitPath p = path[h];
-    const uint32_t pos = dbs_[di].chunk.starts[hits[h].db_id - dbs_[di].global_base];
-    p.s_start += pos;
-    p.s_end += pos;
-    qid[hit_source_[h].qi].push_back(hit_source_[h].query);
-    rec[hit_source_[h].qi].push_back(p);
-  }
-  std::vector<DeviceModule::PileupGroup> groups;
-  for (size_t qi = 0; qi < queries_.size(); ++qi)
-    if (!qid[qi].empty())
-      groups.push_back(DeviceModule::PileupGroup{queries_[qi].dev, (uint32_t)qid[qi].size(), qid[qi].data(),
-                                                 rec[qi].data()});
-  DeviceModule &dev = DeviceModule::Get();
-  const DeviceTimes before = dev.times();
-  dev.PathPileup(dbs_[di].dev, groups.data(), groups.size(), path_ops_.data(), path_ops_.size(), p0, p1, depth,
-                 identities, consensus, profile);
-  const DeviceTimes &after = dev.times();
-  stats_.seconds_pileup += after.pileup - before.pileup;
-  stats_.pileup_launches += after.pileup_launches - before.pileup_launches;
-  stats_.pileup_windows += after.pileup_windows - before.pileup_windows;
-  stats_.pileup_parts += after.pileup_parts - before.pileup_parts;
-  stats_.pileup_columns += after.pileup_columns - before.pileup_columns;
+const std::vector<GhostmHitPath> &Session::LevelPaths(PathLevel lv) {
+  return lv == kFrameLevel ? HitsFrame() : lv == kBandLevel ? HitsBand() : HitsPath();
 }
 
-const std::vector<GhostmSubjectPileup> &Session::Pileup() {
-  if (pileup_valid_) return pileup_subj_;
-  HitsPath();
-  const std::vector<GhostmHit> &hits = Hits();
-  size_t nsubj = 0;
-  uint64_t total = 0;
-  for (const DbData &d : dbs_) {
-    nsubj = std::max<size_t>(nsubj, (size_t)d.global_base + d.chunk.nseq);
-    total += d.chunk.len - d.chunk.nseq;
-  }
-  pileup_subj_.assign(nsubj, GhostmSubjectPileup{0, 0, 0, 0, 0, 0, 0});
-  pileup_depth_.assign(total, 0);
-  pileup_ident_.assign(total, 0);
-  pileup_cons_.assign(total, 255);
-  // every subject's place: db_id order is chunk order, subject order within a chunk
-  std::vector<size_t> order(dbs_.size());
-  for (size_t di = 0; di < dbs_.size(); ++di) order[di] = di;
-  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return dbs_[a].global_base < dbs_[b].global_base; });
-  uint64_t at = 0;
-  for (size_t di : order)
-    for (uint32_t s = 0; s < dbs_[di].chunk.nseq; ++s) {
-      GhostmSubjectPileup &x = pileup_subj_[dbs_[di].global_base + s];
-      x.length = SubjectLength(dbs_[di], s);
-      x.offset = at;
-      at += x.length;
-    }
-  std::vector<std::vector<size_t>> by_db(dbs_.size());
-  for (size_t h = 0; h < hits.size(); ++h) {
-    by_db[hit_source_[h].di].push_back(h);
-    ++pileup_subj_[hits[h].db_id].hits;
-  }
-  std::vector<uint32_t> depth, ident;
-  std::vector<uint8_t> cons;
-  for (size_t di = 0; di < dbs_.size(); ++di) {
-    if (by_db[di].empty()) continue;  // nothing landed on the chunk: zeros and 255s
-    const DbData &d = dbs_[di];
-    depth.assign(d.chunk.len, 0);
-    ident.assign(d.chunk.len, 0);
-    cons.assign(d.chunk.len, 255);
-    PileupChunk(di, by_db[di], 0, d.chunk.len, depth.data(), ident.data(), cons.data(), nullptr);
-    for (uint32_t s = 0; s < d.chunk.nseq; ++s) {
-      GhostmSubjectPileup &x = pileup_subj_[d.global_base + s];
-      if (!x.hits || !x.length) continue;
-      const uint32_t p = d.chunk.starts[s];
-      std::copy(depth.begin() + p, depth.begin() + p + x.length, pileup_depth_.begin() + x.offset);
-      std::copy(ident.begin() + p, ident.begin() + p + x.length, pileup_ident_.begin() + x.offset);
-      std::copy(cons.begin() + p, cons.begin() + p + x.length, pileup_cons_.begin() + x.offset);
-      for (uint32_t k = 0; k < x.length; ++k) {
-        const uint32_t v = depth[p + k];
-        x.covered += v > 0;
-        x.max_depth = std::max(x.max_depth, v);
-        x.depth_sum += v;
-        x.identities_sum += ident[p + k];
-      }
-    }
-  }
-  pileup_valid_ = true;
-  return pileup_subj_;
-}
-
-const std::vector<uint32_t> &Session::PileupDepth() {
-  Pileup();
-  return pileup_depth_;
-}
-
-const std::vector<uint32_t> &Session::PileupIdentities() {
-  Pileup();
-  return pileup_ident_;
-}
-
-const std::vector<uint8_t> &Session::PileupConsensus() {
-  Pileup();
-  return pileup_cons_;
-}
-
-std::vector<uint32_t> Session::SubjectProfile(uint32_t db_id, bool count_only) {
-  if (!count_only) HitsPath();
-  const std::vector<GhostmHit> &hits = Hits();
-  size_t di = 0;
-  while (di < dbs_.size() && !(db_id >= dbs_[di].global_base && db_id - dbs_[di].global_base < dbs_[di].chunk.nseq))
-    ++di;
-  if (di == dbs_.size()) throw Error("subject profile: db_id outside the loaded chunks");
-  const uint32_t s = db_id - dbs_[di].global_base, len = SubjectLength(dbs_[di], s);
-  std::vector<uint32_t> profile((size_t)len * 32, 0);
-  std::vector<size_t> items;
-  if (count_only) return profile;
-  for (size_t h = 0; h < hits.size(); ++h)
-    if (hits[h].db_id == db_id) items.push_back(h);
-  if (len && !items.empty()) {
-    const uint32_t p = dbs_[di].chunk.starts[s];
-    PileupChunk(di, items, p, p + len, nullptr, nullptr, nullptr, profile.data());
-  }
-  return profile;
-}
-
-// -y 10 and -y 11: one line per subject with at least one hit, in db_id order:
-// name, length, hits, covered, depth_sum, identities_sum, max_depth and, with
-// -y 11, the consensus text (the residue letter, '-' where depth > 0 and no
-// residue was seen, '.' where depth is 0). The text replaces the hit lines: it
-// goes into the first piece, the other pieces are emptied.
-void Session::FormatPileup() {
-  const std::vector<GhostmSubjectPileup> &subj = Pileup();
-  static const char kLetters[] = "ARNDCQEGHILKMFPSTWYVBJZX*";  // formats.cpp's order
-  std::string out;
-  for (const DbData &d : dbs_)
-    for (uint32_t s = 0; s < d.chunk.nseq; ++s) {
-      const GhostmSubjectPileup &x = subj[d.global_base + s];
-      if (!x.hits) continue;
-      out.append(d.chunk.names[s]);
-      const uint64_t cols[6] = {x.length, x.hits, x.covered, x.depth_sum, x.identities_sum, x.max_depth};
-      for (uint64_t v : cols) {
-        out.push_back('\t');
-        out.append(std::to_string(v));
-      }
-      if (opt_.output_style == 11) {
-        out.push_back('\t');
-        for (uint32_t k = 0; k < x.length; ++k) {
-          const uint8_t c = pileup_cons_[x.offset + k];
-          out.push_back(pileup_depth_[x.offset + k] == 0 ? '.' : c < 25 ? kLetters[c] : '-');
-        }
-      }
-      out.push_back('\n');
-    }
-  bool placed = false;
-  for (size_t k = 0; k < used_parts_; ++k)
-    for (std::string &t : parts_[k].text) {
-      t.clear();
-      if (!placed) t.swap(out), placed = true;
-    }
-  joined_valid_ = false;
-}
-
-// PileupChunk for the read-level paths: the sources HitsBand() / HitsFrame()
-// aligned, the subject coordinates absolute in the chunk again (as
-// HitsReadRows), one DeviceModule::ReadPileup call.
-void Session::ReadPileupChunk(bool frame, size_t di, const std::vector<size_t> &items, uint32_t p0, uint32_t p1,
-                              uint32_t *depth, uint32_t *identities, uint8_t *consensus, uint32_t *shifts,
-                              uint32_t *profile) {
-  const std::vector<GhostmHitPath> &path = frame ? HitsFrame() : HitsBand();
-  const std::vector<uint32_t> &words = frame ? frame_ops_ : band_ops_;
+// One pile-up call on DB chunk di for the hits `items`: the hits by query chunk
+// with their subject coordinates absolute in the chunk again, the tile paths'
+// resolved records (PathPileup) or the sources HitsBand() / HitsFrame() aligned
+// (ReadPileup).
+void Session::PileupChunk(PathLevel lv, size_t di, const std::vector<size_t> &items, uint32_t p0, uint32_t p1,
+                          uint32_t *depth, uint32_t *identities, uint8_t *consensus, uint32_t *shifts,
+                          uint32_t *profile) {
+  const bool tile = lv == kTileLevel, frame = lv == kFrameLevel;
+  const std::vector<GhostmHitPath> &path = LevelPaths(lv);
+  const std::vector<uint32_t> &words = frame ? frame_ops_ : tile ? path_ops_ : band_ops_;
   const std::vector<GhostmBandSource> &source = frame ? frame_src_ : band_src_;
   const std::vector<GhostmHit> &hits = Hits();
+  std::vector<std::vector<uint32_t>> qid(queries_.size());
   std::vector<std::vector<GhostmBandSource>> src(queries_.size());
   std::vector<std::vector<GhostmHitPath>> rec(queries_.size());
   for (size_t h : items) {
@@ -2369,36 +2210,51 @@ void Session::ReadPileupChunk(bool frame, size_t di, const std::vector<size_t> &
     const uint32_t pos = dbs_[di].chunk.starts[hits[h].db_id - dbs_[di].global_base];
     p.s_start += pos;
     p.s_end += pos;
-    src[hit_source_[h].qi].push_back(source[h]);
+    if (tile) qid[hit_source_[h].qi].push_back(hit_source_[h].query);
+    else src[hit_source_[h].qi].push_back(source[h]);
     rec[hit_source_[h].qi].push_back(p);
   }
+  std::vector<DeviceModule::PileupGroup> tile_groups;
   std::vector<DeviceModule::ReadPileupGroup> groups;
   uint32_t step = 0;
-  for (size_t qi = 0; qi < queries_.size(); ++qi)
-    if (!src[qi].empty()) {
-      groups.push_back(DeviceModule::ReadPileupGroup{queries_[qi].dev, (uint32_t)src[qi].size(), src[qi].data(),
-                                                     rec[qi].data()});
-      step = tile_step_ ? tile_step_ : queries_[qi].chunk.L;  // every chunk of a set has the same width
-    }
+  for (size_t qi = 0; qi < queries_.size(); ++qi) {
+    if (rec[qi].empty()) continue;
+    const uint32_t n = (uint32_t)rec[qi].size();
+    if (tile) tile_groups.push_back(DeviceModule::PileupGroup{queries_[qi].dev, n, qid[qi].data(), rec[qi].data()});
+    else groups.push_back(DeviceModule::ReadPileupGroup{queries_[qi].dev, n, src[qi].data(), rec[qi].data()});
+    step = tile_step_ ? tile_step_ : queries_[qi].chunk.L;  // every chunk of a set has the same width
+  }
   DeviceModule &dev = DeviceModule::Get();
   const DeviceTimes before = dev.times();
+  if (tile) {
+    dev.PathPileup(dbs_[di].dev, tile_groups.data(), tile_groups.size(), words.data(), words.size(), p0, p1, depth,
+                   identities, consensus, profile);
+    AddDeltas(stats_, before, dev.times(), std::make_pair(&GhostmStats::seconds_pileup, &DeviceTimes::pileup),
+              std::make_pair(&GhostmStats::pileup_launches, &DeviceTimes::pileup_launches),
+              std::make_pair(&GhostmStats::pileup_windows, &DeviceTimes::pileup_windows),
+              std::make_pair(&GhostmStats::pileup_parts, &DeviceTimes::pileup_parts),
+              std::make_pair(&GhostmStats::pileup_columns, &DeviceTimes::pileup_columns));
+    return;
+  }
   dev.ReadPileup(dbs_[di].dev, groups.data(), groups.size(), words.data(), words.size(), step, frame, p0, p1, depth,
                  identities, consensus, shifts, profile);
-  const DeviceTimes &after = dev.times();
-  read_pileup_stats_.seconds_read_pileup += after.read_pileup - before.read_pileup;
-  read_pileup_stats_.read_pileup_launches += after.read_pileup_launches - before.read_pileup_launches;
-  read_pileup_stats_.read_pileup_windows += after.read_pileup_windows - before.read_pileup_windows;
-  read_pileup_stats_.read_pileup_parts += after.read_pileup_parts - before.read_pileup_parts;
-  read_pileup_stats_.read_pileup_columns += after.read_pileup_columns - before.read_pileup_columns;
-  read_pileup_stats_.read_pileup_shifts += after.read_pileup_shifts - before.read_pileup_shifts;
+  AddDeltas(read_pileup_stats_, before, dev.times(),
+            std::make_pair(&GhostmReadPileupStats::seconds_read_pileup, &DeviceTimes::read_pileup),
+            std::make_pair(&GhostmReadPileupStats::read_pileup_launches, &DeviceTimes::read_pileup_launches),
+            std::make_pair(&GhostmReadPileupStats::read_pileup_windows, &DeviceTimes::read_pileup_windows),
+            std::make_pair(&GhostmReadPileupStats::read_pileup_parts, &DeviceTimes::read_pileup_parts),
+            std::make_pair(&GhostmReadPileupStats::read_pileup_columns, &DeviceTimes::read_pileup_columns),
+            std::make_pair(&GhostmReadPileupStats::read_pileup_shifts, &DeviceTimes::read_pileup_shifts));
 }
 
-// Pileup() on the read-level paths, with the shifts beside the other arrays.
-const Session::ReadPileupResult &Session::ReadPileup(bool frame) {
-  ReadPileupResult &res = read_pileup_[frame ? 1 : 0];
+// The pile-up of one level's paths: every subject placed in db_id order, one
+// PileupChunk per DB chunk with hits, the subjects' arrays copied out and
+// summed. The tile pile-up has no shifts.
+const Session::ReadPileupResult &Session::PileupAt(PathLevel lv) {
+  ReadPileupResult &res = pileup_[lv];
   if (res.valid) return res;
-  if (frame) HitsFrame();  // refuses what GhostmSessionHitsFrame refuses, before anything is made
-  else HitsBand();
+  LevelPaths(lv);  // the frame paths refuse what GhostmSessionHitsFrame refuses, before anything is made
+  const bool with_shifts = lv != kTileLevel;
   const std::vector<GhostmHit> &hits = Hits();
   size_t nsubj = 0;
   uint64_t total = 0;
@@ -2409,7 +2265,7 @@ const Session::ReadPileupResult &Session::ReadPileup(bool frame) {
   res.subj.assign(nsubj, GhostmSubjectReadPileup{0, 0, 0, 0, 0, 0, 0, 0});
   res.depth.assign(total, 0);
   res.ident.assign(total, 0);
-  res.shifts.assign(total, 0);
+  res.shifts.assign(with_shifts ? total : 0, 0);
   res.cons.assign(total, 255);
   // every subject's place: db_id order is chunk order, subject order within a chunk
   std::vector<size_t> order(dbs_.size());
@@ -2435,17 +2291,17 @@ const Session::ReadPileupResult &Session::ReadPileup(bool frame) {
     const DbData &d = dbs_[di];
     depth.assign(d.chunk.len, 0);
     ident.assign(d.chunk.len, 0);
-    shifts.assign(d.chunk.len, 0);
+    shifts.assign(with_shifts ? d.chunk.len : 0, 0);
     cons.assign(d.chunk.len, 255);
-    ReadPileupChunk(frame, di, by_db[di], 0, d.chunk.len, depth.data(), ident.data(), cons.data(), shifts.data(),
-                    nullptr);
+    PileupChunk(lv, di, by_db[di], 0, d.chunk.len, depth.data(), ident.data(), cons.data(),
+                with_shifts ? shifts.data() : nullptr, nullptr);
     for (uint32_t s = 0; s < d.chunk.nseq; ++s) {
       GhostmSubjectReadPileup &x = res.subj[d.global_base + s];
       if (!x.hits || !x.length) continue;
       const uint32_t p = d.chunk.starts[s];
       std::copy(depth.begin() + p, depth.begin() + p + x.length, res.depth.begin() + x.offset);
       std::copy(ident.begin() + p, ident.begin() + p + x.length, res.ident.begin() + x.offset);
-      std::copy(shifts.begin() + p, shifts.begin() + p + x.length, res.shifts.begin() + x.offset);
+      if (with_shifts) std::copy(shifts.begin() + p, shifts.begin() + p + x.length, res.shifts.begin() + x.offset);
       std::copy(cons.begin() + p, cons.begin() + p + x.length, res.cons.begin() + x.offset);
       for (uint32_t k = 0; k < x.length; ++k) {
         const uint32_t v = depth[p + k];
@@ -2453,24 +2309,40 @@ const Session::ReadPileupResult &Session::ReadPileup(bool frame) {
         x.max_depth = std::max(x.max_depth, v);
         x.depth_sum += v;
         x.identities_sum += ident[p + k];
-        x.shifts_sum += shifts[p + k];
+        if (with_shifts) x.shifts_sum += shifts[p + k];
       }
     }
+  }
+  // the tile pile-up's records as the C ABI hands them out: the first 40 bytes
+  if (lv == kTileLevel) {
+    pileup_subj_.clear();
+    for (const GhostmSubjectReadPileup &x : res.subj)
+      pileup_subj_.push_back(
+          GhostmSubjectPileup{x.length, x.hits, x.covered, x.max_depth, x.depth_sum, x.identities_sum, x.offset});
   }
   res.valid = true;
   return res;
 }
 
-std::vector<uint32_t> Session::ReadSubjectProfile(bool frame, uint32_t db_id, bool count_only) {
-  if (!count_only) {
-    if (frame) HitsFrame();
-    else HitsBand();
-  }
+const std::vector<GhostmSubjectPileup> &Session::Pileup() {
+  PileupAt(kTileLevel);
+  return pileup_subj_;
+}
+
+const std::vector<uint32_t> &Session::PileupDepth() { return PileupAt(kTileLevel).depth; }
+const std::vector<uint32_t> &Session::PileupIdentities() { return PileupAt(kTileLevel).ident; }
+const std::vector<uint8_t> &Session::PileupConsensus() { return PileupAt(kTileLevel).cons; }
+
+const Session::ReadPileupResult &Session::ReadPileup(bool frame) { return PileupAt(frame ? kFrameLevel : kBandLevel); }
+
+// One subject's profile rows from one level's paths; what: the messages' prefix.
+std::vector<uint32_t> Session::SubjectProfileAt(PathLevel lv, const char *what, uint32_t db_id, bool count_only) {
+  if (!count_only) LevelPaths(lv);
   const std::vector<GhostmHit> &hits = Hits();
   size_t di = 0;
   while (di < dbs_.size() && !(db_id >= dbs_[di].global_base && db_id - dbs_[di].global_base < dbs_[di].chunk.nseq))
     ++di;
-  if (di == dbs_.size()) throw Error("read subject profile: db_id outside the loaded chunks");
+  if (di == dbs_.size()) throw Error(std::string(what) + ": db_id outside the loaded chunks");
   const uint32_t s = db_id - dbs_[di].global_base, len = SubjectLength(dbs_[di], s);
   std::vector<uint32_t> profile((size_t)len * 32, 0);
   std::vector<size_t> items;
@@ -2479,16 +2351,28 @@ std::vector<uint32_t> Session::ReadSubjectProfile(bool frame, uint32_t db_id, bo
     if (hits[h].db_id == db_id) items.push_back(h);
   if (len && !items.empty()) {
     const uint32_t p = dbs_[di].chunk.starts[s];
-    ReadPileupChunk(frame, di, items, p, p + len, nullptr, nullptr, nullptr, nullptr, profile.data());
+    PileupChunk(lv, di, items, p, p + len, nullptr, nullptr, nullptr, nullptr, profile.data());
   }
   return profile;
 }
 
-// -y 16 to -y 19: FormatPileup's line from the read-level pile-up; the frame
-// pile-up's line (-y 18, -y 19) has shifts_sum after max_depth; the consensus
-// text (-y 17, -y 19) comes last.
-void Session::FormatReadPileup(bool frame, bool consensus) {
-  const ReadPileupResult &res = ReadPileup(frame);
+std::vector<uint32_t> Session::SubjectProfile(uint32_t db_id, bool count_only) {
+  return SubjectProfileAt(kTileLevel, "subject profile", db_id, count_only);
+}
+
+std::vector<uint32_t> Session::ReadSubjectProfile(bool frame, uint32_t db_id, bool count_only) {
+  return SubjectProfileAt(frame ? kFrameLevel : kBandLevel, "read subject profile", db_id, count_only);
+}
+
+// -y 10, -y 11 (the tile paths) and -y 16 to -y 19 (the read-level paths): one
+// line per subject with at least one hit, in db_id order: name, length, hits,
+// covered, depth_sum, identities_sum, max_depth, the frame pile-up's line (-y
+// 18, -y 19) shifts_sum too, and last, with consensus, the consensus text (the
+// residue letter, '-' where depth > 0 and no residue was seen, '.' where depth
+// is 0). The text replaces the hit lines: it goes into the first piece, the
+// other pieces are emptied.
+void Session::FormatPileup(PathLevel lv, bool consensus) {
+  const ReadPileupResult &res = PileupAt(lv);
   static const char kLetters[] = "ARNDCQEGHILKMFPSTWYVBJZX*";  // formats.cpp's order
   std::string out;
   for (const DbData &d : dbs_)
@@ -2497,7 +2381,7 @@ void Session::FormatReadPileup(bool frame, bool consensus) {
       if (!x.hits) continue;
       out.append(d.chunk.names[s]);
       const uint64_t cols[7] = {x.length, x.hits, x.covered, x.depth_sum, x.identities_sum, x.max_depth, x.shifts_sum};
-      for (size_t c = 0; c < (frame ? 7u : 6u); ++c) {
+      for (size_t c = 0; c < (lv == kFrameLevel ? 7u : 6u); ++c) {
         out.push_back('\t');
         out.append(std::to_string(cols[c]));
       }
@@ -2758,16 +2642,10 @@ void Session::DropResults() {
   band_src_.clear();
   hits_band_valid_ = false;
   read_rows_[0].Drop();
-  read_pileup_[0].Drop();
+  pileup_[kBandLevel].Drop();
   DropFrameResults();
   pileup_subj_.clear();
-  pileup_depth_.clear();
-  pileup_depth_.shrink_to_fit();
-  pileup_ident_.clear();
-  pileup_ident_.shrink_to_fit();
-  pileup_cons_.clear();
-  pileup_cons_.shrink_to_fit();
-  pileup_valid_ = false;
+  pileup_[kTileLevel].Drop();
 }
 
 void Session::Run(bool stream_to_file) {
@@ -2849,10 +2727,11 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    if (opt_.output_style >= 16) FormatReadPileup(opt_.output_style >= 18, opt_.output_style == 17 || opt_.output_style == 19);
+    if (opt_.output_style >= 16)
+      FormatPileup(opt_.output_style >= 18 ? kFrameLevel : kBandLevel, opt_.output_style == 17 || opt_.output_style == 19);
     else if (opt_.output_style == 13 || opt_.output_style == 15) FormatFrameTabular();
     else if (opt_.output_style == 12 || opt_.output_style == 14) FormatPathTabular(true);
-    else if (opt_.output_style >= 10) FormatPileup();
+    else if (opt_.output_style >= 10) FormatPileup(kTileLevel, opt_.output_style == 11);
     else if (opt_.output_style == 6) FormatTabular();
     else FormatPathTabular();
     if (opt_.output_style == 8 || opt_.output_style == 9) FormatRows();

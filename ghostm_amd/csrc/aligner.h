@@ -457,20 +457,31 @@ class Session {
   // the hit's read-level rows appended to the -y 12 / -y 13 line; a hit of
   // read-level score 0 takes the three fields from its tile rows (HitsRows).
   void FormatReadRows(bool frame);
-  // -y 10 and -y 11: replaces the parts' text by one line per subject with hits
-  void FormatPileup();
-  // One PathPileup call on DB chunk di for the hits `items` (indices of Hits()),
-  // grouped by query chunk, over the chunk's positions [p0, p1); adds the
-  // device's counters to stats_.
-  void PileupChunk(size_t di, const std::vector<size_t> &items, uint32_t p0, uint32_t p1, uint32_t *depth,
-                   uint32_t *identities, uint8_t *consensus, uint32_t *profile);
-  // -y 16 / -y 17 (frame false) and -y 18 / -y 19 (frame true): FormatPileup's
-  // text from ReadPileup(frame), with shifts_sum in frame mode
-  void FormatReadPileup(bool frame, bool consensus);
-  // PileupChunk for the read-level paths; adds the device's counters to read_pileup_stats_
-  void ReadPileupChunk(bool frame, size_t di, const std::vector<size_t> &items, uint32_t p0, uint32_t p1,
-                       uint32_t *depth, uint32_t *identities, uint8_t *consensus, uint32_t *shifts,
-                       uint32_t *profile);
+  // The chunk pairs' words of a path pass joined in hit order (HitsPath, HitsBand, HitsFrame)
+  void JoinWords(const std::vector<std::vector<uint32_t>> &words, std::vector<GhostmHitPath> *path,
+                 std::vector<uint32_t> *ops) const;
+  // The plan HitsRows and HitsReadRows share: places in hit order, *bytes sized,
+  // call(qi, di, items, rec, dst) per chunk pair with absolute subject coordinates
+  template <class Call>
+  void RowsPlan(const std::vector<GhostmHitPath> &path, const std::vector<uint32_t> &words, std::vector<uint8_t> *bytes,
+                Call call);
+  // The paths a pile-up is made from: the tile paths (HitsPath), the band paths
+  // (HitsBand) or the frame paths (HitsFrame); LevelPaths makes them.
+  enum PathLevel { kTileLevel = 0, kBandLevel = 1, kFrameLevel = 2 };
+  const std::vector<GhostmHitPath> &LevelPaths(PathLevel lv);
+  // The pile-up of a level, kept in pileup_[lv]; Pileup() and ReadPileup() return it
+  const ReadPileupResult &PileupAt(PathLevel lv);
+  // One PathPileup (tile level) or ReadPileup call on DB chunk di for the hits
+  // `items` (indices of Hits()), grouped by query chunk, over the chunk's
+  // positions [p0, p1); adds the device's counters to stats_ (tile level) or
+  // read_pileup_stats_.
+  void PileupChunk(PathLevel lv, size_t di, const std::vector<size_t> &items, uint32_t p0, uint32_t p1,
+                   uint32_t *depth, uint32_t *identities, uint8_t *consensus, uint32_t *shifts, uint32_t *profile);
+  std::vector<uint32_t> SubjectProfileAt(PathLevel lv, const char *what, uint32_t db_id, bool count_only);
+  // -y 10 / -y 11 (tile level), -y 16 / -y 17 (band level) and -y 18 / -y 19
+  // (frame level, with shifts_sum): replaces the parts' text by one line per
+  // subject with hits
+  void FormatPileup(PathLevel lv, bool consensus);
   uint32_t SubjectLength(const DbData &d, uint32_t subject) const;
 
   AlignerOptions opt_;
@@ -539,11 +550,8 @@ class Session {
   int frame_shift_ = -15;
   GhostmFrameStats frame_stats_{};
   void DropFrameResults();
-  std::vector<GhostmSubjectPileup> pileup_subj_;
-  std::vector<uint32_t> pileup_depth_, pileup_ident_;
-  std::vector<uint8_t> pileup_cons_;
-  bool pileup_valid_ = false;
-  ReadPileupResult read_pileup_[2];  // of the band paths [0] and of the frame paths [1]
+  ReadPileupResult pileup_[3];                  // by PathLevel; the tile pile-up's shifts stay empty
+  std::vector<GhostmSubjectPileup> pileup_subj_;  // pileup_[kTileLevel].subj as 40-byte records
   GhostmReadPileupStats read_pileup_stats_{};
   bool records_on_device_ = false;
   GhostmStats stats_{};

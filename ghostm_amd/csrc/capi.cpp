@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstring>
 #include <fstream>
+#include <functional>
 #include <iostream>
 #include <memory>
 #include <string>
@@ -21,6 +22,38 @@ using namespace ghostm;
 namespace ghostm {
 void SetLastErrorMessage(const std::string &m);
 }
+
+namespace {
+
+// The vector copy-outs: with dst null the size, else at most cap elements of
+// the vector get(session) returns (by reference or by value) and their count;
+// (size_t)-1 with the message set for a null session or a throw.
+template <class T, class Get>
+size_t CopyOut(void *s, T *dst, size_t cap, Get get) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<T> &v = get(*static_cast<Session *>(s));
+    if (!dst) return v.size();
+    const size_t n = std::min(cap, v.size());
+    if (n) std::memcpy(dst, v.data(), n * sizeof(T));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+// The sized stats structs: the first min(size, sizeof(T)) bytes of what
+// get(session) returns, and sizeof(T); 0 for a null session or struct.
+template <class T, class Get>
+size_t CopyStats(void *s, T *stats, size_t size, Get get) {
+  if (!s || !stats) return 0;
+  const T st = get(*static_cast<Session *>(s));
+  std::memcpy(stats, &st, std::min(size, sizeof(T)));
+  return sizeof(T);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -249,10 +282,7 @@ int GhostmSessionDbIndex(void *s, uint32_t chunk, uint32_t *keys_count, size_t k
 }
 
 size_t GhostmSessionDbStats(void *s, GhostmDbSetStats *stats, size_t size) {
-  if (!s || !stats) return 0;
-  const GhostmDbSetStats st = static_cast<Session *>(s)->DbSetStats();
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmDbSetStats)));
-  return sizeof(GhostmDbSetStats);
+  return CopyStats(s, stats, size, std::mem_fn(&Session::DbSetStats));
 }
 
 int64_t GhostmDbChunkCuts(const uint32_t lengths[], uint64_t n, uint32_t chunk_mb, uint64_t cuts[], uint64_t cap) {
@@ -366,73 +396,23 @@ size_t GhostmSessionHits(void *s, GhostmHit *hits, size_t cap) {
 }
 
 size_t GhostmSessionHitsExt(void *s, GhostmHitExt *ext, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<GhostmHitExt> &h = static_cast<Session *>(s)->HitsExt();
-    if (!ext) return h.size();
-    const size_t n = std::min(cap, h.size());
-    std::memcpy(ext, h.data(), n * sizeof(GhostmHitExt));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, ext, cap, std::mem_fn(&Session::HitsExt));
 }
 
 size_t GhostmSessionHitsPath(void *s, GhostmHitPath *rec, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<GhostmHitPath> &h = static_cast<Session *>(s)->HitsPath();
-    if (!rec) return h.size();
-    const size_t n = std::min(cap, h.size());
-    std::memcpy(rec, h.data(), n * sizeof(GhostmHitPath));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, rec, cap, std::mem_fn(&Session::HitsPath));
 }
 
 size_t GhostmSessionPathOps(void *s, uint32_t *ops, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<uint32_t> &w = static_cast<Session *>(s)->PathOps();
-    if (!ops) return w.size();
-    const size_t n = std::min(cap, w.size());
-    std::memcpy(ops, w.data(), n * sizeof(uint32_t));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, ops, cap, std::mem_fn(&Session::PathOps));
 }
 
 size_t GhostmSessionHitsBand(void *s, GhostmHitPath *rec, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<GhostmHitPath> &h = static_cast<Session *>(s)->HitsBand();
-    if (!rec) return h.size();
-    const size_t n = std::min(cap, h.size());
-    std::memcpy(rec, h.data(), n * sizeof(GhostmHitPath));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, rec, cap, std::mem_fn(&Session::HitsBand));
 }
 
 size_t GhostmSessionBandOps(void *s, uint32_t *ops, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<uint32_t> &w = static_cast<Session *>(s)->BandOps();
-    if (!ops) return w.size();
-    const size_t n = std::min(cap, w.size());
-    std::memcpy(ops, w.data(), n * sizeof(uint32_t));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, ops, cap, std::mem_fn(&Session::BandOps));
 }
 
 int GhostmSessionSetBand(void *s, uint32_t band) {
@@ -447,52 +427,19 @@ int GhostmSessionSetBand(void *s, uint32_t band) {
 }
 
 size_t GhostmSessionBandStats(void *s, GhostmBandStats *stats, size_t size) {
-  if (!s || !stats) return 0;
-  const GhostmBandStats st = static_cast<Session *>(s)->BandStats();
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmBandStats)));
-  return sizeof(GhostmBandStats);
+  return CopyStats(s, stats, size, std::mem_fn(&Session::BandStats));
 }
 
 size_t GhostmSessionHitsFrame(void *s, GhostmHitPath *rec, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<GhostmHitPath> &h = static_cast<Session *>(s)->HitsFrame();
-    if (!rec) return h.size();
-    const size_t n = std::min(cap, h.size());
-    std::memcpy(rec, h.data(), n * sizeof(GhostmHitPath));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, rec, cap, std::mem_fn(&Session::HitsFrame));
 }
 
 size_t GhostmSessionFrameOps(void *s, uint32_t *ops, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<uint32_t> &w = static_cast<Session *>(s)->FrameOps();
-    if (!ops) return w.size();
-    const size_t n = std::min(cap, w.size());
-    std::memcpy(ops, w.data(), n * sizeof(uint32_t));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, ops, cap, std::mem_fn(&Session::FrameOps));
 }
 
 size_t GhostmSessionFrameInfo(void *s, GhostmHitFrameInfo *info, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<GhostmHitFrameInfo> &h = static_cast<Session *>(s)->FrameInfo();
-    if (!info) return h.size();
-    const size_t n = std::min(cap, h.size());
-    std::memcpy(info, h.data(), n * sizeof(GhostmHitFrameInfo));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, info, cap, std::mem_fn(&Session::FrameInfo));
 }
 
 int GhostmSessionSetFrameShift(void *s, int shift_cost) {
@@ -507,93 +454,36 @@ int GhostmSessionSetFrameShift(void *s, int shift_cost) {
 }
 
 size_t GhostmSessionFrameStats(void *s, GhostmFrameStats *stats, size_t size) {
-  if (!s || !stats) return 0;
-  const GhostmFrameStats st = static_cast<Session *>(s)->FrameStats();
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmFrameStats)));
-  return sizeof(GhostmFrameStats);
+  return CopyStats(s, stats, size, std::mem_fn(&Session::FrameStats));
 }
 
-namespace {
-size_t CopyReadRows(void *s, bool frame, GhostmHitReadRows *rec, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<GhostmHitReadRows> &h = static_cast<Session *>(s)->HitsReadRows(frame);
-    if (!rec) return h.size();
-    const size_t n = std::min(cap, h.size());
-    std::memcpy(rec, h.data(), n * sizeof(GhostmHitReadRows));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+size_t GhostmSessionHitsBandRows(void *s, GhostmHitReadRows *rec, size_t cap) {
+  return CopyOut(s, rec, cap, [](Session &x) -> auto & { return x.HitsReadRows(false); });
 }
-size_t CopyReadRowBytes(void *s, bool frame, uint8_t *rows, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<uint8_t> &b = static_cast<Session *>(s)->ReadRowBytes(frame);
-    if (!rows) return b.size();
-    const size_t n = std::min(cap, b.size());
-    std::memcpy(rows, b.data(), n);
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+size_t GhostmSessionBandRowBytes(void *s, uint8_t *rows, size_t cap) {
+  return CopyOut(s, rows, cap, [](Session &x) -> auto & { return x.ReadRowBytes(false); });
 }
-}  // namespace
-
-size_t GhostmSessionHitsBandRows(void *s, GhostmHitReadRows *rec, size_t cap) { return CopyReadRows(s, false, rec, cap); }
-size_t GhostmSessionBandRowBytes(void *s, uint8_t *rows, size_t cap) { return CopyReadRowBytes(s, false, rows, cap); }
-size_t GhostmSessionHitsFrameRows(void *s, GhostmHitReadRows *rec, size_t cap) { return CopyReadRows(s, true, rec, cap); }
-size_t GhostmSessionFrameRowBytes(void *s, uint8_t *rows, size_t cap) { return CopyReadRowBytes(s, true, rows, cap); }
+size_t GhostmSessionHitsFrameRows(void *s, GhostmHitReadRows *rec, size_t cap) {
+  return CopyOut(s, rec, cap, [](Session &x) -> auto & { return x.HitsReadRows(true); });
+}
+size_t GhostmSessionFrameRowBytes(void *s, uint8_t *rows, size_t cap) {
+  return CopyOut(s, rows, cap, [](Session &x) -> auto & { return x.ReadRowBytes(true); });
+}
 
 size_t GhostmSessionReadRowsStats(void *s, GhostmReadRowsStats *stats, size_t size) {
-  if (!s || !stats) return 0;
-  const GhostmReadRowsStats st = static_cast<Session *>(s)->ReadRowsStats();
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadRowsStats)));
-  return sizeof(GhostmReadRowsStats);
+  return CopyStats(s, stats, size, std::mem_fn(&Session::ReadRowsStats));
 }
 
 size_t GhostmSessionHitsRows(void *s, GhostmHitRows *rec, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<GhostmHitRows> &h = static_cast<Session *>(s)->HitsRows();
-    if (!rec) return h.size();
-    const size_t n = std::min(cap, h.size());
-    std::memcpy(rec, h.data(), n * sizeof(GhostmHitRows));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, rec, cap, std::mem_fn(&Session::HitsRows));
 }
 
 size_t GhostmSessionRowBytes(void *s, uint8_t *rows, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<uint8_t> &b = static_cast<Session *>(s)->RowBytes();
-    if (!rows) return b.size();
-    const size_t n = std::min(cap, b.size());
-    std::memcpy(rows, b.data(), n);
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, rows, cap, std::mem_fn(&Session::RowBytes));
 }
 
 size_t GhostmSessionPileup(void *s, GhostmSubjectPileup *subj, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<GhostmSubjectPileup> &p = static_cast<Session *>(s)->Pileup();
-    if (!subj) return p.size();
-    const size_t n = std::min(cap, p.size());
-    std::memcpy(subj, p.data(), n * sizeof(GhostmSubjectPileup));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, subj, cap, std::mem_fn(&Session::Pileup));
 }
 
 size_t GhostmSessionPileupArrays(void *s, uint32_t *depth, uint32_t *identities, uint8_t *consensus, size_t cap) {
@@ -614,31 +504,11 @@ size_t GhostmSessionPileupArrays(void *s, uint32_t *depth, uint32_t *identities,
 }
 
 size_t GhostmSessionSubjectProfile(void *s, uint32_t db_id, uint32_t *profile, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<uint32_t> p = static_cast<Session *>(s)->SubjectProfile(db_id, !profile);
-    if (!profile) return p.size();
-    const size_t n = std::min(cap, p.size());
-    if (n) std::memcpy(profile, p.data(), n * 4);
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, profile, cap, [&](Session &x) { return x.SubjectProfile(db_id, !profile); });
 }
 
 size_t GhostmSessionReadPileup(void *s, int frame, GhostmSubjectReadPileup *subj, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<GhostmSubjectReadPileup> &p = static_cast<Session *>(s)->ReadPileup(frame != 0).subj;
-    if (!subj) return p.size();
-    const size_t n = std::min(cap, p.size());
-    std::memcpy(subj, p.data(), n * sizeof(GhostmSubjectReadPileup));
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, subj, cap, [&](Session &x) -> auto & { return x.ReadPileup(frame != 0).subj; });
 }
 
 size_t GhostmSessionReadPileupArrays(void *s, int frame, uint32_t *depth, uint32_t *identities, uint8_t *consensus,
@@ -660,24 +530,11 @@ size_t GhostmSessionReadPileupArrays(void *s, int frame, uint32_t *depth, uint32
 }
 
 size_t GhostmSessionReadSubjectProfile(void *s, int frame, uint32_t db_id, uint32_t *profile, size_t cap) {
-  try {
-    if (!s) throw Error("null session");
-    const std::vector<uint32_t> p = static_cast<Session *>(s)->ReadSubjectProfile(frame != 0, db_id, !profile);
-    if (!profile) return p.size();
-    const size_t n = std::min(cap, p.size());
-    if (n) std::memcpy(profile, p.data(), n * 4);
-    return n;
-  } catch (std::exception &e) {
-    SetLastErrorMessage(e.what());
-    return (size_t)-1;
-  }
+  return CopyOut(s, profile, cap, [&](Session &x) { return x.ReadSubjectProfile(frame != 0, db_id, !profile); });
 }
 
 size_t GhostmSessionReadPileupStats(void *s, GhostmReadPileupStats *stats, size_t size) {
-  if (!s || !stats) return 0;
-  const GhostmReadPileupStats st = static_cast<Session *>(s)->ReadPileupStats();
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadPileupStats)));
-  return sizeof(GhostmReadPileupStats);
+  return CopyStats(s, stats, size, std::mem_fn(&Session::ReadPileupStats));
 }
 
 size_t GhostmSessionDeviceHits(void *s, void *dst_device, size_t cap) {
@@ -697,10 +554,7 @@ int GhostmSessionStats(void *s, GhostmStats *stats) {
 }
 
 size_t GhostmSessionStatsSized(void *s, GhostmStats *stats, size_t size) {
-  if (!s || !stats) return 0;
-  const GhostmStats &st = static_cast<Session *>(s)->Stats();
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmStats)));
-  return sizeof(GhostmStats);
+  return CopyStats(s, stats, size, std::mem_fn(&Session::Stats));
 }
 
 void GhostmSessionDestroy(void *s) { delete static_cast<Session *>(s); }

@@ -2395,6 +2395,59 @@ static size_t EnvSize(const char *name, size_t def) {
   return v ? (size_t)v : def;
 }
 
+// The run-length words of a batched path pass (TraceBackPath, BandPass): the
+// batches' packed words (slot order) and where each hit's lie: batch, first word.
+struct PackedWords {
+  std::vector<std::vector<uint32_t>> batch_words;
+  std::vector<uint32_t> hit_batch, hit_runs;
+  std::vector<uint64_t> hit_at;
+  const bool keep;  // the words are wanted, not only the records
+  PackedWords(uint32_t n, bool keep_words)
+      : hit_batch(keep_words ? n : 0), hit_runs(n), hit_at(keep_words ? n : 0), keep(keep_words) {}
+
+  // The scan of a batch's compaction over its m downloaded records (6 words a
+  // slot; order[s] is slot s's hit, slot(hit) the words it may hold): rec filled,
+  // off[s] every slot's first word in the packed array. Opens the batch's words
+  // (batch_words.back(), with keep) and returns their count.
+  template <class Slot>
+  size_t Scan(uint32_t m, const uint32_t *order, const uint32_t *h_rec, Slot slot, const std::string &what,
+              GhostmHitPath *rec, unsigned long long *off) {
+    size_t packed = 0;
+    for (uint32_t s = 0; s < m; ++s) {
+      const uint32_t hit = order[s];
+      const uint32_t *r = h_rec + (size_t)s * 6;
+      if (r[5] > slot(hit)) throw Error(what + "a hit's runs exceed its slot");
+      if (rec) rec[hit] = GhostmHitPath{r[0], r[1], r[2], r[3], r[4], r[5], 0};
+      hit_runs[hit] = r[5];
+      off[s] = packed;
+      if (keep) {
+        hit_batch[hit] = (uint32_t)batch_words.size();
+        hit_at[hit] = packed;
+      }
+      packed += r[5];
+    }
+    if (keep) batch_words.emplace_back(packed);
+    return packed;
+  }
+
+  // the batches' words joined in hit order
+  void Join(GhostmHitPath *rec, std::vector<uint32_t> *ops) const {
+    const uint32_t n = (uint32_t)hit_runs.size();
+    uint64_t total = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+      if (rec) rec[k].ops_offset = total;
+      total += hit_runs[k];
+    }
+    if (!ops) return;
+    ops->resize(total);
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+      if (hit_runs[k]) memcpy(ops->data() + at, batch_words[hit_batch[k]].data() + hit_at[k], (size_t)hit_runs[k] * 4);
+      at += hit_runs[k];
+    }
+  }
+};
+
 void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const uint32_t *db_end,
                                  const uint32_t *db_start_in, uint32_t base, int open, int ext, GhostmHitPath *rec,
                                  std::vector<uint32_t> *ops) {
@@ -2417,11 +2470,7 @@ void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32
   const size_t colw = (size_t)lay.G * (size_t)(lay.S / 8);  // direction dwords per hit-column
   const size_t budget = EnvSize("GHOSTM_PATH_SCRATCH_MB", 1024) << 20;
   const size_t max_hits = EnvSize("GHOSTM_PATH_BATCH_HITS", SIZE_MAX);
-  // the batches' packed words (slot order) and where each hit's lie: batch, first word
-  std::vector<std::vector<uint32_t>> batch_words;
-  std::vector<uint32_t> hit_batch(ops ? n : 0);
-  std::vector<uint64_t> hit_at(ops ? n : 0);
-  std::vector<uint32_t> hit_runs(n);
+  PackedWords pw(n, ops != nullptr);
   std::vector<unsigned long long> off;  // dir_off[m], then ops_off[m]; dir_off later the packed offsets
   std::vector<uint32_t> h_rec;
   for (uint32_t b0 = 0; b0 < n;) {
@@ -2479,73 +2528,55 @@ void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32
     times_.traceback_path_launches += 1;
     times_.traceback_path_cells += cells;
     times_.traceback_path_dir_bytes += dir_bytes;
-    // the scan of the compaction: every slot's first word in the packed array
-    size_t packed = 0;
-    for (uint32_t s = 0; s < m; ++s) {
-      const uint32_t hit = order[b0 + s];
-      const uint32_t *r = h_rec.data() + (size_t)s * 6;
-      if (r[5] > ncols[hit] + L) throw Error("path traceback: a hit's runs exceed its slot");
-      if (rec) rec[hit] = GhostmHitPath{r[0], r[1], r[2], r[3], r[4], r[5], 0};
-      hit_runs[hit] = r[5];
-      off[s] = packed;
-      if (ops) {
-        hit_batch[hit] = (uint32_t)batch_words.size();
-        hit_at[hit] = packed;
-      }
-      packed += r[5];
-    }
-    if (ops) {
-      batch_words.emplace_back(packed);
-      if (packed) {
-        I.tb_path_cmp.Reserve(packed * 4);
-        HIP_CHECK(hipMemcpyAsync(d_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
-        a.cmp_off = d_off;
-        a.cmp = I.tb_path_cmp.as<uint32_t>();
-        TimedLaunch(I.ev0, I.ev1, S(stream_),
-                    [&] { hipLaunchKernelGGL(kern::k_tb_path_compact, lane_grid, block, 0, S(stream_), a); });
-        HIP_CHECK(hipMemcpyAsync(batch_words.back().data(), a.cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
-        HIP_CHECK(hipStreamSynchronize(S(stream_)));
-        times_.traceback_path += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-      }
+    const size_t packed = pw.Scan(m, order.data() + b0, h_rec.data(), [&](uint32_t hit) { return ncols[hit] + L; },
+                                  "path traceback: ", rec, off.data());
+    // the batch packed on the device and brought back
+    if (ops && packed) {
+      I.tb_path_cmp.Reserve(packed * 4);
+      HIP_CHECK(hipMemcpyAsync(d_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
+      a.cmp_off = d_off;
+      a.cmp = I.tb_path_cmp.as<uint32_t>();
+      TimedLaunch(I.ev0, I.ev1, S(stream_),
+                  [&] { hipLaunchKernelGGL(kern::k_tb_path_compact, lane_grid, block, 0, S(stream_), a); });
+      HIP_CHECK(hipMemcpyAsync(pw.batch_words.back().data(), a.cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
+      HIP_CHECK(hipStreamSynchronize(S(stream_)));
+      times_.traceback_path += ElapsedMs(I.ev0, I.ev1) * 1e-3;
     }
     b0 = b1;
   }
-  // the batches' words joined in hit order
-  uint64_t total = 0;
-  for (uint32_t k = 0; k < n; ++k) {
-    if (rec) rec[k].ops_offset = total;
-    total += hit_runs[k];
-  }
-  if (ops) {
-    ops->resize(total);
-    uint64_t at = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-      if (hit_runs[k]) memcpy(ops->data() + at, batch_words[hit_batch[k]].data() + hit_at[k], (size_t)hit_runs[k] * 4);
-      at += hit_runs[k];
-    }
-  }
+  pw.Join(rec, ops);
 }
 
-size_t DeviceModule::PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const GhostmHitPath *rec,
-                              const uint32_t *ops, size_t ops_len, int open, int ext, uint32_t record_base,
-                              GhostmHitRows *out, uint8_t *rows, size_t rows_cap, const uint64_t *dst_off) {
-  Use();
-  Impl &I = *impl_;
-  if (n == 0) return 0;
-  // every index the kernel will use, checked here: nothing is uploaded or launched for a refused call
-  std::vector<uint32_t> columns;
-  const std::string why = ValidatePathRows(q->nseq, q->L, d->len, n, qid, rec, ops, ops_len, &columns);
-  if (!why.empty()) throw Error("path rows: " + why);
+// Both rows passes. The callers have validated (columns[n]); what differs comes
+// in kind and the callables: make_hit(k, ops_off, rows_off) the uploaded record,
+// launch(a, grid, block) the kernel once a's own fields are set, charge(m, bytes)
+// the counters past the launch count, make_out(k, c, at) out[k] from the
+// kernel's out_words words (called only with has_out).
+struct RowsKind {
+  const char *refuse_cap;               // the whole message
+  const char *scratch_mb, *batch_hits;  // the limits' names
+  DevBuf &hit, &ops, &out, &buf;
+  uint32_t out_words;
+  double &seconds;
+  uint64_t &launches;
+};
+
+template <class Hit, class Args, class MakeHit, class Launch, class Charge, class MakeOut>
+static size_t RowsPass(const RowsKind &K, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1, const uint8_t *qseq,
+                       const uint8_t *db, const int *mat, int open, int ext, uint32_t n,
+                       const std::vector<uint32_t> &columns, const GhostmHitPath *rec, const uint32_t *ops, bool has_out,
+                       uint8_t *rows, size_t rows_cap, const uint64_t *dst_off, MakeHit make_hit, Launch launch,
+                       Charge charge, MakeOut make_out) {
   size_t total = 0;
   for (uint32_t k = 0; k < n; ++k) {
     const size_t b = 3 * (size_t)columns[k], at = dst_off ? (size_t)dst_off[k] : total;
-    if (rows && (at > rows_cap || b > rows_cap - at)) throw Error("path rows: the rows do not fit rows_cap");
+    if (rows && (at > rows_cap || b > rows_cap - at)) throw Error(K.refuse_cap);
     total += b;
   }
-  if (!out && !rows) return total;
-  const size_t budget = EnvSize("GHOSTM_ROWS_SCRATCH_MB", 1024) << 20;
-  const size_t max_hits = EnvSize("GHOSTM_ROWS_BATCH_HITS", SIZE_MAX);
-  std::vector<kern::PathRowsHit> hh;
+  if (!has_out && !rows) return total;
+  const size_t budget = EnvSize(K.scratch_mb, 1024) << 20;
+  const size_t max_hits = EnvSize(K.batch_hits, SIZE_MAX);
+  std::vector<Hit> hh;
   std::vector<uint32_t> words, counts;
   std::vector<uint8_t> stage;  // a batch's bytes on their way to dst_off
   size_t done_bytes = 0;
@@ -2558,34 +2589,32 @@ size_t DeviceModule::PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t 
     words.clear();
     for (size_t s = 0, ra = 0; s < m; ++s) {
       const GhostmHitPath &p = rec[b0 + s];
-      hh[s] = kern::PathRowsHit{qid[b0 + s], p.q_start, p.s_start, p.n_runs, columns[b0 + s], 0, words.size(), ra};
+      hh[s] = make_hit(b0 + (uint32_t)s, words.size(), ra);
       if (p.n_runs) words.insert(words.end(), ops + p.ops_offset, ops + p.ops_offset + p.n_runs);
       ra += 3 * (size_t)columns[b0 + s];
     }
     const size_t nwords = words.size();
-    I.path_rows_hit.Reserve((size_t)m * sizeof(kern::PathRowsHit));
-    I.path_rows_ops.Reserve(std::max<size_t>(nwords, 1) * 4);
-    I.path_rows_out.Reserve((size_t)m * 16);
-    if (rows) I.path_rows_buf.Reserve(std::max<size_t>(bytes, 1));
-    HIP_CHECK(hipMemcpyAsync(I.path_rows_hit.p, hh.data(), (size_t)m * sizeof(kern::PathRowsHit), hipMemcpyHostToDevice,
-                             S(stream_)));
-    if (nwords) HIP_CHECK(hipMemcpyAsync(I.path_rows_ops.p, words.data(), nwords * 4, hipMemcpyHostToDevice, S(stream_)));
-    kern::PathRowsArgs a{};
-    a.qseq = q->seq.as<uint8_t>();
-    a.L = q->L;
-    a.db = d->Residues();
-    a.mat = I.mat_raw.as<int>();
-    a.hit = I.path_rows_hit.as<kern::PathRowsHit>();
+    K.hit.Reserve((size_t)m * sizeof(Hit));
+    K.ops.Reserve(std::max<size_t>(nwords, 1) * 4);
+    K.out.Reserve((size_t)m * K.out_words * 4);
+    if (rows) K.buf.Reserve(std::max<size_t>(bytes, 1));
+    HIP_CHECK(hipMemcpyAsync(K.hit.p, hh.data(), (size_t)m * sizeof(Hit), hipMemcpyHostToDevice, st));
+    if (nwords) HIP_CHECK(hipMemcpyAsync(K.ops.p, words.data(), nwords * 4, hipMemcpyHostToDevice, st));
+    Args a{};
+    a.qseq = qseq;
+    a.db = db;
+    a.mat = mat;
+    a.hit = K.hit.as<Hit>();
     a.n = m;
-    a.ops = I.path_rows_ops.as<uint32_t>();
+    a.ops = K.ops.as<uint32_t>();
     a.open = open;
     a.ext = ext;
-    a.rows = rows ? I.path_rows_buf.as<uint8_t>() : nullptr;
-    a.out = I.path_rows_out.as<uint32_t>();
+    a.rows = rows ? K.buf.as<uint8_t>() : nullptr;
+    a.out = K.out.as<uint32_t>();
     const dim3 grid((m + kern::kTbBlock / 64 - 1) / (kern::kTbBlock / 64)), block(kern::kTbBlock);  // one wave per hit
-    TimedLaunch(I.ev0, I.ev1, S(stream_), [&] { hipLaunchKernelGGL(kern::k_path_rows, grid, block, 0, S(stream_), a); });
-    counts.resize((size_t)m * 4);
-    HIP_CHECK(hipMemcpyAsync(counts.data(), a.out, (size_t)m * 16, hipMemcpyDeviceToHost, S(stream_)));
+    TimedLaunch(ev0, ev1, st, [&] { launch(a, grid, block); });
+    counts.resize((size_t)m * K.out_words);
+    HIP_CHECK(hipMemcpyAsync(counts.data(), a.out, (size_t)m * K.out_words * 4, hipMemcpyDeviceToHost, st));
     uint8_t *land = nullptr;
     if (rows && bytes) {
       if (dst_off) {
@@ -2594,24 +2623,55 @@ size_t DeviceModule::PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t 
       } else {
         land = rows + done_bytes;  // hit order: the batch's bytes are consecutive
       }
-      HIP_CHECK(hipMemcpyAsync(land, a.rows, bytes, hipMemcpyDeviceToHost, S(stream_)));
+      HIP_CHECK(hipMemcpyAsync(land, a.rows, bytes, hipMemcpyDeviceToHost, st));
     }
-    HIP_CHECK(hipStreamSynchronize(S(stream_)));
-    times_.path_rows += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-    times_.path_rows_launches += 1;
-    times_.path_rows_columns += bytes / 3;
-    times_.path_rows_bytes += rows ? bytes : 0;
+    HIP_CHECK(hipStreamSynchronize(st));
+    K.seconds += ElapsedMs(ev0, ev1) * 1e-3;
+    K.launches += 1;
+    charge(m, bytes);
     for (uint32_t s = 0; s < m; ++s) {
       const uint32_t k = b0 + s;
       const uint64_t at = dst_off ? dst_off[k] : done_bytes + hh[s].rows_off;
       if (land && dst_off && columns[k]) memcpy(rows + at, land + hh[s].rows_off, 3 * (size_t)columns[k]);
-      const uint32_t *c = counts.data() + (size_t)s * 4;
-      if (out) out[k] = GhostmHitRows{qid[k] + record_base, columns[k], c[0], c[1], c[2], (int32_t)c[3], at};
+      if (has_out) make_out(k, counts.data() + (size_t)s * K.out_words, at);
     }
     done_bytes += bytes;
     b0 = b1;
   }
   return total;
+}
+
+size_t DeviceModule::PathRows(DevQuery *q, DevDb *d, uint32_t n, const uint32_t *qid, const GhostmHitPath *rec,
+                              const uint32_t *ops, size_t ops_len, int open, int ext, uint32_t record_base,
+                              GhostmHitRows *out, uint8_t *rows, size_t rows_cap, const uint64_t *dst_off) {
+  Use();
+  Impl &I = *impl_;
+  if (n == 0) return 0;
+  // every index the kernel will use, checked here: nothing is uploaded or launched for a refused call
+  std::vector<uint32_t> columns;
+  const std::string why = ValidatePathRows(q->nseq, q->L, d->len, n, qid, rec, ops, ops_len, &columns);
+  if (!why.empty()) throw Error("path rows: " + why);
+  const RowsKind K{"path rows: the rows do not fit rows_cap", "GHOSTM_ROWS_SCRATCH_MB", "GHOSTM_ROWS_BATCH_HITS",
+                   I.path_rows_hit, I.path_rows_ops, I.path_rows_out, I.path_rows_buf, 4, times_.path_rows,
+                   times_.path_rows_launches};
+  return RowsPass<kern::PathRowsHit, kern::PathRowsArgs>(
+      K, S(stream_), I.ev0, I.ev1, q->seq.as<uint8_t>(), d->Residues(), I.mat_raw.as<int>(), open, ext, n, columns, rec,
+      ops, out != nullptr, rows, rows_cap, dst_off,
+      [&](uint32_t k, size_t ops_off, size_t rows_off) {
+        const GhostmHitPath &p = rec[k];
+        return kern::PathRowsHit{qid[k], p.q_start, p.s_start, p.n_runs, columns[k], 0, ops_off, rows_off};
+      },
+      [&](kern::PathRowsArgs &a, dim3 grid, dim3 block) {
+        a.L = q->L;
+        hipLaunchKernelGGL(kern::k_path_rows, grid, block, 0, S(stream_), a);
+      },
+      [&](uint32_t, size_t bytes) {
+        times_.path_rows_columns += bytes / 3;
+        times_.path_rows_bytes += rows ? bytes : 0;
+      },
+      [&](uint32_t k, const uint32_t *c, uint64_t at) {
+        out[k] = GhostmHitRows{qid[k] + record_base, columns[k], c[0], c[1], c[2], (int32_t)c[3], at};
+      });
 }
 
 static_assert(sizeof(kern::ReadRowsHit) == 48, "ReadRowsHit is uploaded as 48-byte records");
@@ -2627,91 +2687,33 @@ size_t DeviceModule::ReadRows(DevQuery *q, DevDb *d, uint32_t n, const GhostmBan
   std::vector<uint32_t> columns;
   const std::string why = ValidateReadRows(q->nseq, q->L, d->len, n, src, rec, ops, ops_len, step, frame, shift, &columns);
   if (!why.empty()) throw Error("read rows: " + why);
-  size_t total = 0;
-  for (uint32_t k = 0; k < n; ++k) {
-    const size_t b = 3 * (size_t)columns[k], at = dst_off ? (size_t)dst_off[k] : total;
-    if (rows && (at > rows_cap || b > rows_cap - at)) throw Error("read rows: rows_cap: the rows do not fit");
-    total += b;
-  }
-  if (!out && !rows) return total;
-  const size_t budget = EnvSize("GHOSTM_READ_ROWS_SCRATCH_MB", 1024) << 20;
-  const size_t max_hits = EnvSize("GHOSTM_READ_ROWS_BATCH_HITS", SIZE_MAX);
-  std::vector<kern::ReadRowsHit> hh;
-  std::vector<uint32_t> words, counts;
-  std::vector<uint8_t> stage;  // a batch's bytes on their way to dst_off
-  size_t done_bytes = 0;
-  for (uint32_t b0 = 0; b0 < n;) {
-    // hits [b0, b1) in hit order, cut by their row bytes (hit_batches.h)
-    size_t bytes = 0;
-    const uint32_t b1 = CutBatch(b0, n, max_hits, budget, [&](uint32_t k) { return 3 * (size_t)columns[k]; }, &bytes);
-    const uint32_t m = b1 - b0;
-    hh.resize(m);
-    words.clear();
-    for (size_t s = 0, ra = 0; s < m; ++s) {
-      const GhostmHitPath &p = rec[b0 + s];
-      const GhostmBandSource &bs = src[b0 + s];
-      hh[s] = kern::ReadRowsHit{kern::SourceRef{bs.first_record, bs.stride, bs.tiles, bs.letters}, p.q_start, p.s_start,
-                                p.n_runs, columns[b0 + s], words.size(), ra};
-      if (p.n_runs) words.insert(words.end(), ops + p.ops_offset, ops + p.ops_offset + p.n_runs);
-      ra += 3 * (size_t)columns[b0 + s];
-    }
-    const size_t nwords = words.size();
-    I.read_rows_hit.Reserve((size_t)m * sizeof(kern::ReadRowsHit));
-    I.read_rows_ops.Reserve(std::max<size_t>(nwords, 1) * 4);
-    I.read_rows_out.Reserve((size_t)m * 32);
-    if (rows) I.read_rows_buf.Reserve(std::max<size_t>(bytes, 1));
-    HIP_CHECK(hipMemcpyAsync(I.read_rows_hit.p, hh.data(), (size_t)m * sizeof(kern::ReadRowsHit), hipMemcpyHostToDevice,
-                             S(stream_)));
-    if (nwords) HIP_CHECK(hipMemcpyAsync(I.read_rows_ops.p, words.data(), nwords * 4, hipMemcpyHostToDevice, S(stream_)));
-    kern::ReadRowsArgs a{};
-    a.qseq = q->seq.as<uint8_t>();
-    a.W = q->L;
-    a.step = step;
-    a.db = d->Residues();
-    a.mat = I.mat_raw.as<int>();
-    a.hit = I.read_rows_hit.as<kern::ReadRowsHit>();
-    a.n = m;
-    a.ops = I.read_rows_ops.as<uint32_t>();
-    a.open = open;
-    a.ext = ext;
-    a.shift = shift;
-    a.rows = rows ? I.read_rows_buf.as<uint8_t>() : nullptr;
-    a.out = I.read_rows_out.as<uint32_t>();
-    const dim3 grid((m + kern::kTbBlock / 64 - 1) / (kern::kTbBlock / 64)), block(kern::kTbBlock);  // one wave per hit
-    TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
-      if (frame) hipLaunchKernelGGL(kern::k_read_rows<true>, grid, block, 0, S(stream_), a);
-      else hipLaunchKernelGGL(kern::k_read_rows<false>, grid, block, 0, S(stream_), a);
-    });
-    counts.resize((size_t)m * 8);
-    HIP_CHECK(hipMemcpyAsync(counts.data(), a.out, (size_t)m * 32, hipMemcpyDeviceToHost, S(stream_)));
-    uint8_t *land = nullptr;
-    if (rows && bytes) {
-      if (dst_off) {
-        stage.resize(bytes);
-        land = stage.data();
-      } else {
-        land = rows + done_bytes;  // hit order: the batch's bytes are consecutive
-      }
-      HIP_CHECK(hipMemcpyAsync(land, a.rows, bytes, hipMemcpyDeviceToHost, S(stream_)));
-    }
-    HIP_CHECK(hipStreamSynchronize(S(stream_)));
-    times_.read_rows += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-    times_.read_rows_launches += 1;
-    times_.read_rows_hits += m;
-    times_.read_rows_columns += bytes / 3;
-    for (uint32_t s = 0; s < m; ++s) {
-      const uint32_t k = b0 + s;
-      const uint64_t at = dst_off ? dst_off[k] : done_bytes + hh[s].rows_off;
-      if (land && dst_off && columns[k]) memcpy(rows + at, land + hh[s].rows_off, 3 * (size_t)columns[k]);
-      const uint32_t *c = counts.data() + (size_t)s * 8;
-      if (out)
+  const RowsKind K{"read rows: rows_cap: the rows do not fit", "GHOSTM_READ_ROWS_SCRATCH_MB",
+                   "GHOSTM_READ_ROWS_BATCH_HITS", I.read_rows_hit, I.read_rows_ops, I.read_rows_out, I.read_rows_buf, 8,
+                   times_.read_rows, times_.read_rows_launches};
+  return RowsPass<kern::ReadRowsHit, kern::ReadRowsArgs>(
+      K, S(stream_), I.ev0, I.ev1, q->seq.as<uint8_t>(), d->Residues(), I.mat_raw.as<int>(), open, ext, n, columns, rec,
+      ops, out != nullptr, rows, rows_cap, dst_off,
+      [&](uint32_t k, size_t ops_off, size_t rows_off) {
+        const GhostmHitPath &p = rec[k];
+        const GhostmBandSource &bs = src[k];
+        return kern::ReadRowsHit{kern::SourceRef{bs.first_record, bs.stride, bs.tiles, bs.letters}, p.q_start, p.s_start,
+                                 p.n_runs, columns[k], ops_off, rows_off};
+      },
+      [&](kern::ReadRowsArgs &a, dim3 grid, dim3 block) {
+        a.W = q->L;
+        a.step = step;
+        a.shift = shift;
+        if (frame) hipLaunchKernelGGL(kern::k_read_rows<true>, grid, block, 0, S(stream_), a);
+        else hipLaunchKernelGGL(kern::k_read_rows<false>, grid, block, 0, S(stream_), a);
+      },
+      [&](uint32_t m, size_t bytes) {
+        times_.read_rows_hits += m;
+        times_.read_rows_columns += bytes / 3;
+      },
+      [&](uint32_t k, const uint32_t *c, uint64_t at) {
         out[k] = GhostmHitReadRows{ReadRowsFirstRecord(src[k], rec[k], q->L, step, frame) + record_base, columns[k], c[0],
                                    c[1], c[2], (int32_t)c[3], at, c[4], 0};
-    }
-    done_bytes += bytes;
-    b0 = b1;
-  }
-  return total;
+      });
 }
 
 static_assert(kern::kBandNeg == kBandNegInf, "the kernels' minus infinity is the host model's");
@@ -2767,9 +2769,8 @@ void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32
   const uint32_t stride = BandDirStride(B);
   const size_t budget = EnvSize(frame ? "GHOSTM_FRAME_SCRATCH_MB" : "GHOSTM_BAND_SCRATCH_MB", 1024) << 20;
   const size_t max_hits = EnvSize(frame ? "GHOSTM_FRAME_BATCH_HITS" : "GHOSTM_BAND_BATCH_HITS", SIZE_MAX);
-  std::vector<std::vector<uint32_t>> batch_words;
-  std::vector<uint32_t> hit_batch(ops ? n : 0), hit_runs(n), h_rec;
-  std::vector<uint64_t> hit_at(ops ? n : 0);
+  PackedWords pw(n, ops != nullptr);
+  std::vector<uint32_t> h_rec;
   std::vector<kern::BandHit> hh;
   std::vector<unsigned long long> off;  // ops_off[m], later the packed offsets
   for (uint32_t b0 = 0; b0 < n;) {
@@ -2841,64 +2842,169 @@ void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32
     (frame ? times_.frame_hits : times_.band_hits) += m;
     (frame ? times_.frame_cells : times_.band_cells) += cells;
     (frame ? times_.frame_dir_bytes : times_.band_dir_bytes) += dir_bytes;
-    // the scan of the compaction: every slot's first word in the packed array
-    size_t packed = 0;
-    for (uint32_t s = 0; s < m; ++s) {
-      const uint32_t hit = order[b0 + s];
-      const uint32_t *r = h_rec.data() + (size_t)s * 6;
-      if (r[5] > OpsSlot(rows[hit].rows)) throw Error(what + "a hit's runs exceed its slot");
-      if (rec) rec[hit] = GhostmHitPath{r[0], r[1], r[2], r[3], r[4], r[5], 0};
-      hit_runs[hit] = r[5];
-      off[s] = packed;
-      if (ops) {
-        hit_batch[hit] = (uint32_t)batch_words.size();
-        hit_at[hit] = packed;
-      }
-      packed += r[5];
-    }
-    if (ops) {
-      batch_words.emplace_back(packed);
-      if (packed) {
-        b_cmp.Reserve(packed * 4);
-        HIP_CHECK(hipMemcpyAsync(d_off + m, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
-        a.cmp_off = d_off + m;
-        a.cmp = b_cmp.as<uint32_t>();
-        TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
-          if (frame)
-            hipLaunchKernelGGL(kern::k_frame_compact, wave_grid, block, 0, S(stream_), (kern::FrameArgs{a, shift}));
-          else
-            hipLaunchKernelGGL(kern::k_band_compact, wave_grid, block, 0, S(stream_), a);
-        });
-        HIP_CHECK(hipMemcpyAsync(batch_words.back().data(), a.cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
-        HIP_CHECK(hipStreamSynchronize(S(stream_)));
-        t_seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-      }
+    const size_t packed = pw.Scan(m, order.data() + b0, h_rec.data(),
+                                  [&](uint32_t hit) { return OpsSlot(rows[hit].rows); }, what, rec, off.data());
+    // the batch packed on the device and brought back
+    if (ops && packed) {
+      b_cmp.Reserve(packed * 4);
+      HIP_CHECK(hipMemcpyAsync(d_off + m, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
+      a.cmp_off = d_off + m;
+      a.cmp = b_cmp.as<uint32_t>();
+      TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
+        if (frame)
+          hipLaunchKernelGGL(kern::k_frame_compact, wave_grid, block, 0, S(stream_), (kern::FrameArgs{a, shift}));
+        else
+          hipLaunchKernelGGL(kern::k_band_compact, wave_grid, block, 0, S(stream_), a);
+      });
+      HIP_CHECK(hipMemcpyAsync(pw.batch_words.back().data(), a.cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
+      HIP_CHECK(hipStreamSynchronize(S(stream_)));
+      t_seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
     }
     b0 = b1;
   }
-  // the batches' words joined in hit order
-  uint64_t total = 0;
-  for (uint32_t k = 0; k < n; ++k) {
-    if (rec) rec[k].ops_offset = total;
-    total += hit_runs[k];
-  }
-  if (ops) {
-    ops->resize(total);
-    uint64_t at = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-      if (hit_runs[k]) memcpy(ops->data() + at, batch_words[hit_batch[k]].data() + hit_at[k], (size_t)hit_runs[k] * 4);
-      at += hit_runs[k];
-    }
-  }
+  pw.Join(rec, ops);
 }
 
 static_assert(kern::kPileupTileMax == kPileupTileMax, "the kernel's LDS histogram holds the plan's largest tile");
+
+// Both pile-up passes past their checks: span[g][k] is what hit k of group g
+// charges from its s_start. with_shifts (the read-level pass): two column
+// counters, a shifts row in pileup_out and k_pileup_finish<true>; shifts may be
+// null like the other outputs. make_hit(G, k, ops_off) is the uploaded record,
+// launch(G, a, cols, grid, block) the kernel once a's own fields are set (cols:
+// the device counters).
+struct PileupKind {
+  const char *what;  // the messages' prefix
+  bool with_shifts;
+  double &seconds;
+  uint64_t &launches, &windows, &parts, &columns, *shift_columns;
+};
+
+template <class Hit, class Args, class Group, class MakeHit, class Launch>
+static void PileupPass(const PileupKind &K, DeviceModule::Impl &I, hipStream_t st, DevDb *d, const Group *groups,
+                       size_t ngroups, const std::vector<std::vector<uint32_t>> &span, const uint32_t *ops, uint32_t p0,
+                       uint32_t p1, uint32_t *depth, uint32_t *identities, uint8_t *consensus, uint32_t *shifts,
+                       uint32_t *profile, MakeHit make_hit, Launch launch) {
+  if (p0 == p1) return;
+  const std::string what = K.what;
+  const uint32_t T = PileupClampTile(EnvSize("GHOSTM_PILEUP_TILE", kPileupTileDefault));
+  const uint32_t P = (uint32_t)std::min<size_t>(EnvSize("GHOSTM_PILEUP_PART_HITS", kPileupPartDefault), UINT32_MAX);
+  const size_t budget = EnvSize("GHOSTM_PILEUP_SCRATCH_MB", 1024) << 20;
+  const size_t max_hits = EnvSize("GHOSTM_PILEUP_BATCH_HITS", (size_t)1 << 22);
+  const size_t upload_budget = (size_t)256 << 20;  // a batch's hit records, words and plan
+  const uint32_t t_lo = p0 / T, t_hi = (p1 - 1) / T + 1;
+  const std::vector<uint32_t> win =
+      PileupWindows((uint32_t)std::min<uint64_t>((uint64_t)(t_hi - t_lo) * T, UINT32_MAX), T, budget);
+  const size_t cols_bytes = K.with_shifts ? 16 : 8;
+  I.pileup_cols.Reserve(cols_bytes);
+  unsigned long long *cols_d = I.pileup_cols.as<unsigned long long>();
+  HIP_CHECK(hipMemsetAsync(cols_d, 0, cols_bytes, st));
+  std::vector<uint32_t> sel, words;
+  std::vector<Hit> hh;
+  PileupPlan plan;
+  for (size_t w = 0; w + 1 < win.size(); ++w) {
+    const uint32_t ta = t_lo + win[w], tb = t_lo + win[w + 1];
+    const uint32_t win0 = ta * T, win1 = (uint32_t)std::min<uint64_t>((uint64_t)tb * T, d->len);
+    const uint32_t npos = win1 - win0;
+    I.pileup_prof.Reserve((size_t)npos * kPileupSlots * 4);
+    HIP_CHECK(hipMemsetAsync(I.pileup_prof.p, 0, (size_t)npos * kPileupSlots * 4, st));
+    for (size_t g = 0; g < ngroups; ++g) {
+      const Group &G = groups[g];
+      // the group's hits that meet the window, in hit order
+      sel.clear();
+      for (uint32_t k = 0; k < G.n; ++k)
+        if (span[g][k] && G.rec[k].s_start < win1 && (uint64_t)G.rec[k].s_start + span[g][k] > win0) sel.push_back(k);
+      const uint32_t n = (uint32_t)sel.size();
+      for (uint32_t b0 = 0, b1 = 0; b0 < n; b0 = b1) {
+        // hits sel[b0, b1): an upload batch (hit_batches.h), cut by its records, words and list entries
+        size_t bytes = 0;
+        b1 = CutBatch(b0, n, max_hits, upload_budget, [&](uint32_t s) {
+          return sizeof(Hit) + 4 * (size_t)G.rec[sel[s]].n_runs + 4 * ((size_t)span[g][sel[s]] / T + 2);
+        }, &bytes);
+        const uint32_t m = b1 - b0;
+        if (!BuildPileupPlan(m, [&](uint32_t s) { return G.rec[sel[b0 + s]].s_start; },
+                             [&](uint32_t s) { return span[g][sel[b0 + s]]; }, T, ta, tb, P, &plan))
+          throw Error(what + "a batch's plan exceeds 2^32 - 1 entries (lower GHOSTM_PILEUP_BATCH_HITS)");
+        if (plan.parts.empty()) continue;
+        hh.resize(m);
+        words.clear();
+        for (uint32_t s = 0; s < m; ++s) {
+          const GhostmHitPath &p = G.rec[sel[b0 + s]];
+          hh[s] = make_hit(G, sel[b0 + s], words.size());
+          words.insert(words.end(), ops + p.ops_offset, ops + p.ops_offset + p.n_runs);
+        }
+        static_assert(sizeof(kern::PileupPartArg) == sizeof(PileupPart), "the plan's parts are uploaded as they are");
+        const size_t nparts = plan.parts.size();
+        I.pileup_hit.Reserve((size_t)m * sizeof(Hit));
+        I.pileup_ops.Reserve(words.size() * 4);
+        I.pileup_list.Reserve(plan.list.size() * 4);
+        I.pileup_part.Reserve(nparts * sizeof(PileupPart));
+        HIP_CHECK(hipMemcpyAsync(I.pileup_hit.p, hh.data(), (size_t)m * sizeof(Hit), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(I.pileup_ops.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipMemcpyAsync(I.pileup_list.p, plan.list.data(), plan.list.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_CHECK(
+            hipMemcpyAsync(I.pileup_part.p, plan.parts.data(), nparts * sizeof(PileupPart), hipMemcpyHostToDevice, st));
+        Args a{};
+        a.qseq = G.q->seq.template as<uint8_t>();
+        a.hit = I.pileup_hit.as<Hit>();
+        a.ops = I.pileup_ops.as<uint32_t>();
+        a.list = I.pileup_list.as<uint32_t>();
+        a.part = I.pileup_part.as<kern::PileupPartArg>();
+        a.T = T;
+        a.win0 = win0;
+        a.win1 = win1;
+        a.profile = I.pileup_prof.as<uint32_t>();
+        if (nparts > 0x7FFFFFFFu) throw Error(what + "too many parts in one launch (lower GHOSTM_PILEUP_BATCH_HITS)");
+        const dim3 grid((uint32_t)nparts), block(kern::kTbBlock);  // one workgroup per (tile, part)
+        TimedLaunch(I.ev0, I.ev1, st, [&] { launch(G, a, cols_d, grid, block); });
+        HIP_CHECK(hipStreamSynchronize(st));
+        K.seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+        K.launches += 1;
+        K.parts += nparts;
+      }
+    }
+    // the window's positions finished; those inside [p0, p1) go back
+    I.pileup_out.Reserve((size_t)npos * (K.with_shifts ? 13 : 9));
+    kern::PileupFinishArgs f{};
+    f.profile = I.pileup_prof.as<uint32_t>();
+    f.db = d->Residues() + win0;
+    f.n = npos;
+    f.depth = I.pileup_out.as<uint32_t>();
+    f.identities = f.depth + npos;
+    if (K.with_shifts) f.shifts = f.identities + npos;
+    f.consensus = reinterpret_cast<uint8_t *>(f.identities + (K.with_shifts ? 2 : 1) * (size_t)npos);
+    const dim3 fgrid((npos + kern::kTbBlock - 1) / kern::kTbBlock), block(kern::kTbBlock);
+    TimedLaunch(I.ev0, I.ev1, st, [&] {
+      if (K.with_shifts) hipLaunchKernelGGL(kern::k_pileup_finish<true>, fgrid, block, 0, st, f);
+      else hipLaunchKernelGGL(kern::k_pileup_finish<false>, fgrid, block, 0, st, f);
+    });
+    const uint32_t c0 = std::max(win0, p0), c1 = std::min(win1, p1);
+    if (c0 < c1) {
+      const size_t cn = c1 - c0, from = c0 - win0, to = c0 - p0;
+      if (depth) HIP_CHECK(hipMemcpyAsync(depth + to, f.depth + from, cn * 4, hipMemcpyDeviceToHost, st));
+      if (identities)
+        HIP_CHECK(hipMemcpyAsync(identities + to, f.identities + from, cn * 4, hipMemcpyDeviceToHost, st));
+      if (consensus) HIP_CHECK(hipMemcpyAsync(consensus + to, f.consensus + from, cn, hipMemcpyDeviceToHost, st));
+      if (shifts) HIP_CHECK(hipMemcpyAsync(shifts + to, f.shifts + from, cn * 4, hipMemcpyDeviceToHost, st));
+      if (profile)
+        HIP_CHECK(hipMemcpyAsync(profile + to * kPileupSlots, f.profile + from * kPileupSlots, cn * kPileupSlots * 4,
+                                 hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+    K.seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+    K.windows += 1;
+  }
+  unsigned long long cols[2] = {0, 0};
+  HIP_CHECK(hipMemcpyAsync(cols, cols_d, cols_bytes, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  K.columns += cols[0];
+  if (K.shift_columns) *K.shift_columns += cols[1];
+}
 
 void DeviceModule::PathPileup(DevDb *d, const PileupGroup *groups, size_t ngroups, const uint32_t *ops,
                               size_t ops_len, uint32_t p0, uint32_t p1, uint32_t *depth, uint32_t *identities,
                               uint8_t *consensus, uint32_t *profile) {
   Use();
-  Impl &I = *impl_;
   if (p0 > p1 || p1 > d->len) throw Error("pileup: positions outside the resident chunk (db_len)");
   // every index the kernels will use, checked here: nothing is uploaded or launched for a refused call
   std::vector<std::vector<uint32_t>> span(ngroups);  // per hit: its subject residues
@@ -2917,128 +3023,29 @@ void DeviceModule::PathPileup(DevDb *d, const PileupGroup *groups, size_t ngroup
       span[g][k] = s;
     }
   }
-  if (p0 == p1) return;
-  const uint32_t T = PileupClampTile(EnvSize("GHOSTM_PILEUP_TILE", kPileupTileDefault));
-  const uint32_t P = (uint32_t)std::min<size_t>(EnvSize("GHOSTM_PILEUP_PART_HITS", kPileupPartDefault), UINT32_MAX);
-  const size_t budget = EnvSize("GHOSTM_PILEUP_SCRATCH_MB", 1024) << 20;
-  const size_t max_hits = EnvSize("GHOSTM_PILEUP_BATCH_HITS", (size_t)1 << 22);
-  const size_t upload_budget = (size_t)256 << 20;  // a batch's hit records, words and plan
-  const uint32_t t_lo = p0 / T, t_hi = (p1 - 1) / T + 1;
-  const std::vector<uint32_t> win =
-      PileupWindows((uint32_t)std::min<uint64_t>((uint64_t)(t_hi - t_lo) * T, UINT32_MAX), T, budget);
-  I.pileup_cols.Reserve(8);
-  unsigned long long *cols_d = I.pileup_cols.as<unsigned long long>();
-  HIP_CHECK(hipMemsetAsync(cols_d, 0, 8, S(stream_)));
-  std::vector<uint32_t> sel, words;
-  std::vector<kern::PileupHit> hh;
-  PileupPlan plan;
-  for (size_t w = 0; w + 1 < win.size(); ++w) {
-    const uint32_t ta = t_lo + win[w], tb = t_lo + win[w + 1];
-    const uint32_t win0 = ta * T, win1 = (uint32_t)std::min<uint64_t>((uint64_t)tb * T, d->len);
-    const uint32_t npos = win1 - win0;
-    I.pileup_prof.Reserve((size_t)npos * kPileupSlots * 4);
-    HIP_CHECK(hipMemsetAsync(I.pileup_prof.p, 0, (size_t)npos * kPileupSlots * 4, S(stream_)));
-    for (size_t g = 0; g < ngroups; ++g) {
-      const PileupGroup &G = groups[g];
-      // the group's hits that meet the window, in hit order
-      sel.clear();
-      for (uint32_t k = 0; k < G.n; ++k)
-        if (span[g][k] && G.rec[k].s_start < win1 && (uint64_t)G.rec[k].s_start + span[g][k] > win0) sel.push_back(k);
-      const uint32_t n = (uint32_t)sel.size();
-      for (uint32_t b0 = 0, b1 = 0; b0 < n; b0 = b1) {
-        // hits sel[b0, b1): an upload batch (hit_batches.h), cut by its records, words and list entries
-        size_t bytes = 0;
-        b1 = CutBatch(b0, n, max_hits, upload_budget, [&](uint32_t s) {
-          return sizeof(kern::PileupHit) + 4 * (size_t)G.rec[sel[s]].n_runs + 4 * ((size_t)span[g][sel[s]] / T + 2);
-        }, &bytes);
-        const uint32_t m = b1 - b0;
-        if (!BuildPileupPlan(m, [&](uint32_t s) { return G.rec[sel[b0 + s]].s_start; },
-                             [&](uint32_t s) { return span[g][sel[b0 + s]]; }, T, ta, tb, P, &plan))
-          throw Error("pileup: a batch's plan exceeds 2^32 - 1 entries (lower GHOSTM_PILEUP_BATCH_HITS)");
-        if (plan.parts.empty()) continue;
-        hh.resize(m);
-        words.clear();
-        for (uint32_t s = 0; s < m; ++s) {
-          const GhostmHitPath &p = G.rec[sel[b0 + s]];
-          hh[s] = kern::PileupHit{G.qid[sel[b0 + s]], p.q_start, p.s_start, p.n_runs, words.size()};
-          words.insert(words.end(), ops + p.ops_offset, ops + p.ops_offset + p.n_runs);
-        }
-        static_assert(sizeof(kern::PileupPartArg) == sizeof(PileupPart), "the plan's parts are uploaded as they are");
-        const size_t nparts = plan.parts.size();
-        I.pileup_hit.Reserve((size_t)m * sizeof(kern::PileupHit));
-        I.pileup_ops.Reserve(words.size() * 4);
-        I.pileup_list.Reserve(plan.list.size() * 4);
-        I.pileup_part.Reserve(nparts * sizeof(PileupPart));
-        HIP_CHECK(hipMemcpyAsync(I.pileup_hit.p, hh.data(), (size_t)m * sizeof(kern::PileupHit), hipMemcpyHostToDevice,
-                                 S(stream_)));
-        HIP_CHECK(hipMemcpyAsync(I.pileup_ops.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, S(stream_)));
-        HIP_CHECK(hipMemcpyAsync(I.pileup_list.p, plan.list.data(), plan.list.size() * 4, hipMemcpyHostToDevice,
-                                 S(stream_)));
-        HIP_CHECK(hipMemcpyAsync(I.pileup_part.p, plan.parts.data(), nparts * sizeof(PileupPart), hipMemcpyHostToDevice,
-                                 S(stream_)));
-        kern::PileupArgs a{};
-        a.qseq = G.q->seq.as<uint8_t>();
+  const PileupKind K{"pileup: ", false, times_.pileup, times_.pileup_launches, times_.pileup_windows,
+                     times_.pileup_parts, times_.pileup_columns, nullptr};
+  PileupPass<kern::PileupHit, kern::PileupArgs>(
+      K, *impl_, S(stream_), d, groups, ngroups, span, ops, p0, p1, depth, identities, consensus, nullptr, profile,
+      [&](const PileupGroup &G, uint32_t k, size_t ops_off) {
+        const GhostmHitPath &p = G.rec[k];
+        return kern::PileupHit{G.qid[k], p.q_start, p.s_start, p.n_runs, ops_off};
+      },
+      [&](const PileupGroup &G, kern::PileupArgs &a, unsigned long long *cols, dim3 grid, dim3 block) {
         a.L = G.q->L;
-        a.hit = I.pileup_hit.as<kern::PileupHit>();
-        a.ops = I.pileup_ops.as<uint32_t>();
-        a.list = I.pileup_list.as<uint32_t>();
-        a.part = I.pileup_part.as<kern::PileupPartArg>();
-        a.T = T;
-        a.win0 = win0;
-        a.win1 = win1;
-        a.profile = I.pileup_prof.as<uint32_t>();
-        a.columns = cols_d;
-        if (nparts > 0x7FFFFFFFu) throw Error("pileup: too many parts in one launch (lower GHOSTM_PILEUP_BATCH_HITS)");
-        const dim3 grid((uint32_t)nparts), block(kern::kTbBlock);  // one workgroup per (tile, part)
-        TimedLaunch(I.ev0, I.ev1, S(stream_), [&] { hipLaunchKernelGGL(kern::k_pileup, grid, block, 0, S(stream_), a); });
-        HIP_CHECK(hipStreamSynchronize(S(stream_)));
-        times_.pileup += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-        times_.pileup_launches += 1;
-        times_.pileup_parts += nparts;
-      }
-    }
-    // the window's positions finished; those inside [p0, p1) go back
-    I.pileup_out.Reserve((size_t)npos * 9);
-    kern::PileupFinishArgs f{};
-    f.profile = I.pileup_prof.as<uint32_t>();
-    f.db = d->Residues() + win0;
-    f.n = npos;
-    f.depth = I.pileup_out.as<uint32_t>();
-    f.identities = f.depth + npos;
-    f.consensus = reinterpret_cast<uint8_t *>(f.identities + npos);
-    const dim3 fgrid((npos + kern::kTbBlock - 1) / kern::kTbBlock), block(kern::kTbBlock);
-    TimedLaunch(I.ev0, I.ev1, S(stream_),
-                [&] { hipLaunchKernelGGL(kern::k_pileup_finish<false>, fgrid, block, 0, S(stream_), f); });
-    const uint32_t c0 = std::max(win0, p0), c1 = std::min(win1, p1);
-    if (c0 < c1) {
-      const size_t cn = c1 - c0, from = c0 - win0, to = c0 - p0;
-      if (depth) HIP_CHECK(hipMemcpyAsync(depth + to, f.depth + from, cn * 4, hipMemcpyDeviceToHost, S(stream_)));
-      if (identities)
-        HIP_CHECK(hipMemcpyAsync(identities + to, f.identities + from, cn * 4, hipMemcpyDeviceToHost, S(stream_)));
-      if (consensus) HIP_CHECK(hipMemcpyAsync(consensus + to, f.consensus + from, cn, hipMemcpyDeviceToHost, S(stream_)));
-      if (profile)
-        HIP_CHECK(hipMemcpyAsync(profile + to * kPileupSlots, f.profile + from * kPileupSlots, cn * kPileupSlots * 4,
-                                 hipMemcpyDeviceToHost, S(stream_)));
-    }
-    HIP_CHECK(hipStreamSynchronize(S(stream_)));
-    times_.pileup += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-    times_.pileup_windows += 1;
-  }
-  unsigned long long cols = 0;
-  HIP_CHECK(hipMemcpyAsync(&cols, cols_d, 8, hipMemcpyDeviceToHost, S(stream_)));
-  HIP_CHECK(hipStreamSynchronize(S(stream_)));
-  times_.pileup_columns += cols;
+        a.columns = cols;
+        hipLaunchKernelGGL(kern::k_pileup, grid, block, 0, S(stream_), a);
+      });
 }
 
 static_assert(sizeof(kern::ReadPileupHit) == 40, "ReadPileupHit is uploaded as 40-byte records");
 
-// PathPileup's loops with the read-level hit record, the charged span instead
-// of the subject residues, k_read_pileup and the finish kernel's shifts.
+// PathPileup with the read-level hit record, the charged span instead of the
+// subject residues, k_read_pileup and the finish kernel's shifts.
 void DeviceModule::ReadPileup(DevDb *d, const ReadPileupGroup *groups, size_t ngroups, const uint32_t *ops,
                               size_t ops_len, uint32_t step, bool frame, uint32_t p0, uint32_t p1, uint32_t *depth,
                               uint32_t *identities, uint8_t *consensus, uint32_t *shifts, uint32_t *profile) {
   Use();
-  Impl &I = *impl_;
   if (p0 > p1 || p1 > d->len) throw Error("read pileup: positions outside the resident chunk (db_len)");
   // every index the kernels will use, checked here: nothing is uploaded or launched for a refused call
   std::vector<std::vector<uint32_t>> span(ngroups);  // per hit: the positions it charges, from s_start
@@ -3049,126 +3056,23 @@ void DeviceModule::ReadPileup(DevDb *d, const ReadPileupGroup *groups, size_t ng
     if (why.empty()) why = ReadPileupSpans(d->len, G.n, G.rec, ops, &span[g]);
     if (!why.empty()) throw Error("read pileup: " + why);
   }
-  if (p0 == p1) return;
-  const uint32_t T = PileupClampTile(EnvSize("GHOSTM_PILEUP_TILE", kPileupTileDefault));
-  const uint32_t P = (uint32_t)std::min<size_t>(EnvSize("GHOSTM_PILEUP_PART_HITS", kPileupPartDefault), UINT32_MAX);
-  const size_t budget = EnvSize("GHOSTM_PILEUP_SCRATCH_MB", 1024) << 20;
-  const size_t max_hits = EnvSize("GHOSTM_PILEUP_BATCH_HITS", (size_t)1 << 22);
-  const size_t upload_budget = (size_t)256 << 20;  // a batch's hit records, words and plan
-  const uint32_t t_lo = p0 / T, t_hi = (p1 - 1) / T + 1;
-  const std::vector<uint32_t> win =
-      PileupWindows((uint32_t)std::min<uint64_t>((uint64_t)(t_hi - t_lo) * T, UINT32_MAX), T, budget);
-  I.pileup_cols.Reserve(16);
-  unsigned long long *cols_d = I.pileup_cols.as<unsigned long long>();
-  HIP_CHECK(hipMemsetAsync(cols_d, 0, 16, S(stream_)));
-  std::vector<uint32_t> sel, words;
-  std::vector<kern::ReadPileupHit> hh;
-  PileupPlan plan;
-  for (size_t w = 0; w + 1 < win.size(); ++w) {
-    const uint32_t ta = t_lo + win[w], tb = t_lo + win[w + 1];
-    const uint32_t win0 = ta * T, win1 = (uint32_t)std::min<uint64_t>((uint64_t)tb * T, d->len);
-    const uint32_t npos = win1 - win0;
-    I.pileup_prof.Reserve((size_t)npos * kPileupSlots * 4);
-    HIP_CHECK(hipMemsetAsync(I.pileup_prof.p, 0, (size_t)npos * kPileupSlots * 4, S(stream_)));
-    for (size_t g = 0; g < ngroups; ++g) {
-      const ReadPileupGroup &G = groups[g];
-      // the group's hits that meet the window, in hit order
-      sel.clear();
-      for (uint32_t k = 0; k < G.n; ++k)
-        if (span[g][k] && G.rec[k].s_start < win1 && (uint64_t)G.rec[k].s_start + span[g][k] > win0) sel.push_back(k);
-      const uint32_t n = (uint32_t)sel.size();
-      for (uint32_t b0 = 0, b1 = 0; b0 < n; b0 = b1) {
-        // hits sel[b0, b1): an upload batch (hit_batches.h), cut by its records, words and list entries
-        size_t bytes = 0;
-        b1 = CutBatch(b0, n, max_hits, upload_budget, [&](uint32_t s) {
-          return sizeof(kern::ReadPileupHit) + 4 * (size_t)G.rec[sel[s]].n_runs + 4 * ((size_t)span[g][sel[s]] / T + 2);
-        }, &bytes);
-        const uint32_t m = b1 - b0;
-        if (!BuildPileupPlan(m, [&](uint32_t s) { return G.rec[sel[b0 + s]].s_start; },
-                             [&](uint32_t s) { return span[g][sel[b0 + s]]; }, T, ta, tb, P, &plan))
-          throw Error("read pileup: a batch's plan exceeds 2^32 - 1 entries (lower GHOSTM_PILEUP_BATCH_HITS)");
-        if (plan.parts.empty()) continue;
-        hh.resize(m);
-        words.clear();
-        for (uint32_t s = 0; s < m; ++s) {
-          const GhostmHitPath &p = G.rec[sel[b0 + s]];
-          const GhostmBandSource &bs = G.src[sel[b0 + s]];
-          hh[s] = kern::ReadPileupHit{kern::SourceRef{bs.first_record, bs.stride, bs.tiles, bs.letters}, p.q_start,
-                                      p.s_start, p.n_runs, 0, words.size()};
-          words.insert(words.end(), ops + p.ops_offset, ops + p.ops_offset + p.n_runs);
-        }
-        const size_t nparts = plan.parts.size();
-        I.pileup_hit.Reserve((size_t)m * sizeof(kern::ReadPileupHit));
-        I.pileup_ops.Reserve(words.size() * 4);
-        I.pileup_list.Reserve(plan.list.size() * 4);
-        I.pileup_part.Reserve(nparts * sizeof(PileupPart));
-        HIP_CHECK(hipMemcpyAsync(I.pileup_hit.p, hh.data(), (size_t)m * sizeof(kern::ReadPileupHit),
-                                 hipMemcpyHostToDevice, S(stream_)));
-        HIP_CHECK(hipMemcpyAsync(I.pileup_ops.p, words.data(), words.size() * 4, hipMemcpyHostToDevice, S(stream_)));
-        HIP_CHECK(hipMemcpyAsync(I.pileup_list.p, plan.list.data(), plan.list.size() * 4, hipMemcpyHostToDevice,
-                                 S(stream_)));
-        HIP_CHECK(hipMemcpyAsync(I.pileup_part.p, plan.parts.data(), nparts * sizeof(PileupPart), hipMemcpyHostToDevice,
-                                 S(stream_)));
-        kern::ReadPileupArgs a{};
-        a.qseq = G.q->seq.as<uint8_t>();
+  const PileupKind K{"read pileup: ", true, times_.read_pileup, times_.read_pileup_launches, times_.read_pileup_windows,
+                     times_.read_pileup_parts, times_.read_pileup_columns, &times_.read_pileup_shifts};
+  PileupPass<kern::ReadPileupHit, kern::ReadPileupArgs>(
+      K, *impl_, S(stream_), d, groups, ngroups, span, ops, p0, p1, depth, identities, consensus, shifts, profile,
+      [&](const ReadPileupGroup &G, uint32_t k, size_t ops_off) {
+        const GhostmHitPath &p = G.rec[k];
+        const GhostmBandSource &bs = G.src[k];
+        return kern::ReadPileupHit{kern::SourceRef{bs.first_record, bs.stride, bs.tiles, bs.letters}, p.q_start,
+                                   p.s_start, p.n_runs, 0, ops_off};
+      },
+      [&](const ReadPileupGroup &G, kern::ReadPileupArgs &a, unsigned long long *cols, dim3 grid, dim3 block) {
         a.W = G.q->L;
         a.step = step;
-        a.hit = I.pileup_hit.as<kern::ReadPileupHit>();
-        a.ops = I.pileup_ops.as<uint32_t>();
-        a.list = I.pileup_list.as<uint32_t>();
-        a.part = I.pileup_part.as<kern::PileupPartArg>();
-        a.T = T;
-        a.win0 = win0;
-        a.win1 = win1;
-        a.profile = I.pileup_prof.as<uint32_t>();
-        a.counters = cols_d;
-        if (nparts > 0x7FFFFFFFu)
-          throw Error("read pileup: too many parts in one launch (lower GHOSTM_PILEUP_BATCH_HITS)");
-        const dim3 grid((uint32_t)nparts), block(kern::kTbBlock);  // one workgroup per (tile, part)
-        TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
-          if (frame) hipLaunchKernelGGL(kern::k_read_pileup<true>, grid, block, 0, S(stream_), a);
-          else hipLaunchKernelGGL(kern::k_read_pileup<false>, grid, block, 0, S(stream_), a);
-        });
-        HIP_CHECK(hipStreamSynchronize(S(stream_)));
-        times_.read_pileup += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-        times_.read_pileup_launches += 1;
-        times_.read_pileup_parts += nparts;
-      }
-    }
-    // the window's positions finished; those inside [p0, p1) go back
-    I.pileup_out.Reserve((size_t)npos * 13);
-    kern::PileupFinishArgs f{};
-    f.profile = I.pileup_prof.as<uint32_t>();
-    f.db = d->Residues() + win0;
-    f.n = npos;
-    f.depth = I.pileup_out.as<uint32_t>();
-    f.identities = f.depth + npos;
-    f.shifts = f.identities + npos;
-    f.consensus = reinterpret_cast<uint8_t *>(f.shifts + npos);
-    const dim3 fgrid((npos + kern::kTbBlock - 1) / kern::kTbBlock), block(kern::kTbBlock);
-    TimedLaunch(I.ev0, I.ev1, S(stream_),
-                [&] { hipLaunchKernelGGL(kern::k_pileup_finish<true>, fgrid, block, 0, S(stream_), f); });
-    const uint32_t c0 = std::max(win0, p0), c1 = std::min(win1, p1);
-    if (c0 < c1) {
-      const size_t cn = c1 - c0, from = c0 - win0, to = c0 - p0;
-      if (depth) HIP_CHECK(hipMemcpyAsync(depth + to, f.depth + from, cn * 4, hipMemcpyDeviceToHost, S(stream_)));
-      if (identities)
-        HIP_CHECK(hipMemcpyAsync(identities + to, f.identities + from, cn * 4, hipMemcpyDeviceToHost, S(stream_)));
-      if (consensus) HIP_CHECK(hipMemcpyAsync(consensus + to, f.consensus + from, cn, hipMemcpyDeviceToHost, S(stream_)));
-      if (shifts) HIP_CHECK(hipMemcpyAsync(shifts + to, f.shifts + from, cn * 4, hipMemcpyDeviceToHost, S(stream_)));
-      if (profile)
-        HIP_CHECK(hipMemcpyAsync(profile + to * kPileupSlots, f.profile + from * kPileupSlots, cn * kPileupSlots * 4,
-                                 hipMemcpyDeviceToHost, S(stream_)));
-    }
-    HIP_CHECK(hipStreamSynchronize(S(stream_)));
-    times_.read_pileup += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-    times_.read_pileup_windows += 1;
-  }
-  unsigned long long cols[2] = {0, 0};
-  HIP_CHECK(hipMemcpyAsync(cols, cols_d, 16, hipMemcpyDeviceToHost, S(stream_)));
-  HIP_CHECK(hipStreamSynchronize(S(stream_)));
-  times_.read_pileup_columns += cols[0];
-  times_.read_pileup_shifts += cols[1];
+        a.counters = cols;
+        if (frame) hipLaunchKernelGGL(kern::k_read_pileup<true>, grid, block, 0, S(stream_), a);
+        else hipLaunchKernelGGL(kern::k_read_pileup<false>, grid, block, 0, S(stream_), a);
+      });
 }
 
 const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_amd/srchash.py)
