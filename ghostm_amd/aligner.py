@@ -521,6 +521,52 @@ def stage_read_pileup_stats() -> dict:
     return {n: getattr(st, n) for n, _ in st._fields_}
 
 
+# GhostmCullHit and GhostmCullOut (include/ghostm_hip.h)
+CULL_HIT_DTYPE = np.dtype([("subject", "<u4"), ("score", "<u4"), ("q_lo", "<u4"), ("q_hi", "<u4"), ("s_lo", "<u4"),
+                           ("s_hi", "<u4")])
+CULL_OUT_DTYPE = np.dtype([("order", "<u4"), ("status", "<u4"), ("kept_rank", "<u4"), ("detail", "<u4")])
+CULL_KEPT, CULL_DUP, CULL_CULLED, CULL_EMPTY = 0, 1, 2, 3
+
+
+def _read_cull_call(fn, read_begin, hits, top_k, cover_pct, out):
+    """ReadCullGpu and GhostmReadCullHost take the same arguments. out: the
+    array the records go to (the refusal tests pass their own), or None."""
+    rb = np.ascontiguousarray(read_begin, dtype=np.uint32).reshape(-1)
+    h = np.ascontiguousarray(hits, dtype=CULL_HIT_DTYPE).reshape(-1)
+    if out is None:
+        out = np.zeros(len(h), dtype=CULL_OUT_DTYPE)
+    if out.dtype != CULL_OUT_DTYPE or not out.flags.c_contiguous or len(out) < len(h):
+        raise ValueError("read cull: out must be contiguous CULL_OUT_DTYPE records, one per hit")
+    rc = fn(max(len(rb), 1) - 1, rb.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if len(rb) else None, len(h),
+            h.ctypes.data_as(ctypes.POINTER(native.GhostmCullHit)) if len(h) else None, int(top_k), int(cover_pct),
+            out.ctypes.data_as(ctypes.POINTER(native.GhostmCullOut)) if len(out) else None)
+    if rc != 0:
+        raise GhostmError(native.last_error())
+    return out
+
+
+def read_cull_host(read_begin, hits, top_k=1, cover_pct=50, out=None):
+    """The host model of the read-level cull (GhostmReadCullHost; no device):
+    read r's hits are hits[read_begin[r]:read_begin[r + 1]] (CULL_HIT_DTYPE).
+    Returns one CULL_OUT_DTYPE record per hit; hits outside every read keep
+    out's bytes (zeros unless out is given)."""
+    return _read_cull_call(native.load().GhostmReadCullHost, read_begin, hits, top_k, cover_pct, out)
+
+
+def read_cull(read_begin, hits, top_k=1, cover_pct=50, out=None):
+    """ReadCullGpu (k_read_cull); arguments and result as read_cull_host. Needs
+    no resident chunk."""
+    return _read_cull_call(native.load().ReadCullGpu, read_begin, hits, top_k, cover_pct, out)
+
+
+def stage_read_cull_stats() -> dict:
+    """The cull counters behind the stage-level calls (GhostmStageReadCullStats)."""
+    lib = native.load()
+    st = native.GhostmReadCullStats()
+    lib.GhostmStageReadCullStats(ctypes.byref(st), ctypes.sizeof(st))
+    return {n: getattr(st, n) for n, _ in st._fields_}
+
+
 class Aligner:
     """reference class Aligner (aligner.h:63-92): Execute(argc, argv)."""
 
@@ -1053,6 +1099,48 @@ class Session:
                                               cons.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                                               shifts.ctypes.data_as(u32p), m)
         return subj, depth, ident, cons, shifts
+
+    def read_cull(self, frame: bool = False) -> np.ndarray:
+        """One CULL_OUT_DTYPE record per hit of hits() (GhostmSessionReadCull):
+        the hits of every read ranked by the read-level score of hits_band()
+        (frame False) or hits_frame() (frame True), with the hits that repeat a
+        kept alignment (CULL_DUP, detail = the kept hit's index in hits()) and
+        the hits whose stretch of the read kept hits cover (CULL_CULLED) marked.
+        Computed on first use. frame=True is refused where hits_frame() is."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        f = int(bool(frame))
+        n = lib.GhostmSessionReadCull(self._h, f, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        out = np.zeros(n, dtype=CULL_OUT_DTYPE)
+        if n and lib.GhostmSessionReadCull(self._h, f, out.ctypes.data_as(ctypes.POINTER(native.GhostmCullOut)),
+                                           n) == bad:
+            raise GhostmError(native.last_error())
+        return out
+
+    def set_cull(self, top_k: int = 1, cover_pct: int = 50) -> None:
+        """read_cull()'s parameters: a hit is culled when top_k (1..255) kept
+        hits cover cover_pct (1..100) per cent of its stretch of the read. A
+        refusal leaves the old values; a change drops the kept result."""
+        k, pct = int(top_k), int(cover_pct)
+        if not (0 <= k < 1 << 32 and 0 <= pct < 1 << 32):  # beyond the C arguments' range
+            raise GhostmError(f"cull: param: top_k {k}, cover_pct {pct} outside 1..255, 1..100")
+        if native.load().GhostmSessionSetCull(self._h, k, pct) != 0:
+            raise GhostmError(native.last_error())
+
+    def read_cull_stats(self) -> dict:
+        """The cull's counters since the last run (GhostmSessionReadCullStats)."""
+        st = native.GhostmReadCullStats()
+        native.load().GhostmSessionReadCullStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    def set_tile_groups(self, on: bool = True) -> None:
+        """From the next tiled setter on, keep the best -b hits per tile instead
+        of per read (GhostmSessionSetTileGroups). Off by default; refused on a
+        shard session."""
+        if native.load().GhostmSessionSetTileGroups(self._h, int(bool(on))) != 0:
+            raise GhostmError(native.last_error())
 
     def read_subject_profile(self, frame: bool, db_id: int) -> np.ndarray:
         """The 32-slot rows of subject db_id from the read-level paths, shape

@@ -226,9 +226,9 @@ AlignerOptions ParseAlignerOptions(int argc, char **argv) {
   // small inputs); the oracle honours the same variable
   if (const char *e = getenv("GHOSTM_MAX_LIST_OVERRIDE")) o.max_list_length = (uint32_t)strtoul(e, nullptr, 10);
   o.matrix = ReadScoreMatrix(matrix_file);
-  // 6 to 9 and 12 to 15: style 0's E-value and bit score; 10, 11 and 16 to 19 (the pile-ups) print none, like 1 and 2
+  // 6 to 9, 12 to 15, 20 and 21: style 0's E-value and bit score; 10, 11 and 16 to 19 (the pile-ups) print none, like 1 and 2
   if (o.output_style == 0 || (o.output_style >= 6 && o.output_style <= 9) ||
-      (o.output_style >= 12 && o.output_style <= 15)) {
+      (o.output_style >= 12 && o.output_style <= 15) || o.output_style == 20 || o.output_style == 21) {
     // extension: GHOSTM_KARLIN=ungapped prices combinations the
     // reference's table lacks with the matrix's ungapped ideal parameters
     // (karlin_params.cpp); unset, they throw as the reference does
@@ -1492,7 +1492,8 @@ const LineFormat &Session::Format() {
   // -y 6 formats style-0 lines first: FormatTabular takes their identity,
   // E-value and bit-score bytes
   const bool tabular =
-      (opt_.output_style >= 6 && opt_.output_style <= 9) || (opt_.output_style >= 12 && opt_.output_style <= 15);
+      (opt_.output_style >= 6 && opt_.output_style <= 9) || (opt_.output_style >= 12 && opt_.output_style <= 15) ||
+      opt_.output_style == 20 || opt_.output_style == 21;
   // -y 10, -y 11 and -y 16 to -y 19 replace the hit lines after the run: style 1's lines, which need no E-value, stand in
   const bool pileup = opt_.output_style == 10 || opt_.output_style == 11 || (opt_.output_style >= 16 && opt_.output_style <= 19);
   if (!format_) format_.reset(new LineFormat(tabular ? 0 : pileup ? 1 : opt_.output_style, opt_.karlin, 4095));
@@ -1856,6 +1857,7 @@ void Session::SetBand(uint32_t band) {
   hits_band_valid_ = false;
   read_rows_[0].Drop();
   pileup_[kBandLevel].Drop();
+  cull_[0].Drop();
   DropFrameResults();  // the frame pass runs inside the same band
 }
 
@@ -1945,6 +1947,7 @@ void Session::DropFrameResults() {
   hits_frame_valid_ = false;
   read_rows_[1].Drop();
   pileup_[kFrameLevel].Drop();
+  cull_[1].Drop();
 }
 
 void Session::SetFrameShift(int shift) {
@@ -2114,6 +2117,12 @@ void Session::FormatReadRows(bool frame) {
   });
 }
 
+// Strand position p of a read of read_nt nucleotides as a forward-strand
+// position, from 0: what -y 13 prints (plus 1) and what the cull compares.
+static inline uint32_t ForwardNt(uint32_t strand, uint32_t read_nt, uint32_t p) {
+  return strand ? read_nt - 1 - p : p;
+}
+
 // -y 13: FormatPathTabular's line from the hit's frame path (HitsFrame) in read
 // nucleotide coordinates, then qframe and frameshifts. A hit of frame score 0
 // prints its tile path in the same units, with the style-0 line's E-value and
@@ -2149,8 +2158,8 @@ void Session::FormatFrameTabular() {
       q0 = 3 * (t.offset + x.q_start) + t.frame % 3;
       q1 = 3 * (t.offset + x.q_end) + t.frame % 3 + 2;
     }
-    p = PutU32(p, info.strand ? info.read_nt - q0 : q0 + 1); *p++ = '\t';
-    p = PutU32(p, info.strand ? info.read_nt - q1 : q1 + 1); *p++ = '\t';
+    p = PutU32(p, ForwardNt(info.strand, info.read_nt, q0) + 1); *p++ = '\t';
+    p = PutU32(p, ForwardNt(info.strand, info.read_nt, q1) + 1); *p++ = '\t';
     p = PutU32(p, x.s_start + 1); *p++ = '\t';
     p = PutU32(p, x.s_end + 1); *p++ = '\t';
     if (framed) {
@@ -2178,6 +2187,136 @@ void Session::FormatFrameTabular() {
     *p++ = '\n';
     out.append(num, (size_t)(p - num));
   });
+}
+
+void Session::SetCull(uint32_t top_k, uint32_t cover_pct) {
+  if (top_k < 1 || top_k > 255) throw Error("cull: param: top_k " + std::to_string(top_k) + " outside 1..255");
+  if (cover_pct < 1 || cover_pct > 100)
+    throw Error("cull: param: cover_pct " + std::to_string(cover_pct) + " outside 1..100");
+  if (top_k == cull_top_k_ && cover_pct == cull_cover_pct_) return;
+  cull_top_k_ = top_k;
+  cull_cover_pct_ = cover_pct;
+  cull_[0].Drop();
+  cull_[1].Drop();
+}
+
+void Session::SetTileGroups(bool on) {
+  if (shard_world_ > 1) throw Error("a shard session's query set cannot be replaced");
+  tile_groups_ = on;
+}
+
+// The cull of every final hit (ReadCull). The reads: consecutive hits of one
+// source record (tiled set) or of one name group (untiled set). A hit's record
+// is its read-level path's: the q interval in forward-strand read units
+// (nucleotides on a tiled DNA set: a band path's frame letters c of frame f
+// cover strand positions 3c + f % 3 to 3c + f % 3 + 2, a frame path's q_* are
+// strand positions already; ForwardNt turns the reverse strand's round).
+const Session::ReadCullResult &Session::ReadCull(bool frame) {
+  ReadCullResult &res = cull_[frame ? 1 : 0];
+  if (res.valid) return res;
+  const std::vector<GhostmHitPath> &path = frame ? HitsFrame() : HitsBand();
+  const std::vector<GhostmHit> &hits = Hits();
+  const size_t n = hits.size();
+  if (n > UINT32_MAX) throw Error("read cull: over 4 G hits");
+  std::vector<GhostmCullHit> in(n);
+  res.read_begin.assign(1, 0);
+  uint64_t prev = UINT64_MAX;
+  for (size_t h = 0; h < n; ++h) {
+    const HitSource &hs = hit_source_[h];
+    const QueryData &q = queries_[hs.qi];
+    const bool tiled = !tile_table_.empty();
+    const GhostmQueryTile *t = tiled ? &tile_table_[q.global_base + hs.query] : nullptr;
+    // the read's key: the source record, or the name group's end over all chunks
+    const uint64_t key = tiled ? t->record : (uint64_t)q.global_base + q.group_end[hs.query];
+    if (h && key != prev) res.read_begin.push_back((uint32_t)h);
+    prev = key;
+    const GhostmHitPath &x = path[h];
+    GhostmCullHit c{hits[h].db_id, x.score, 0, 0, x.s_start, x.s_end};
+    if (x.score) {
+      if (tiled && tile_dna_) {
+        const uint32_t g = t->frame % 3, strand = t->frame / 3, nt = tile_read_nt_[t->record];
+        const uint32_t p0 = frame ? x.q_start : 3 * x.q_start + g, p1 = frame ? x.q_end : 3 * x.q_end + g + 2;
+        const uint32_t a = ForwardNt(strand, nt, p0), b = ForwardNt(strand, nt, p1);
+        c.q_lo = std::min(a, b);
+        c.q_hi = std::max(a, b);
+      } else {
+        c.q_lo = x.q_start;
+        c.q_hi = x.q_end;
+      }
+    } else {
+      c.s_lo = c.s_hi = 0;  // an EMPTY hit: its ranges say nothing
+    }
+    in[h] = c;
+  }
+  res.read_begin.push_back((uint32_t)n);
+  res.out.assign(n, GhostmCullOut{0, GHOSTM_CULL_EMPTY, 0xFFFFFFFFu, 0});
+  DeviceModule &dev = DeviceModule::Get();
+  const DeviceTimes before = dev.times();
+  dev.ReadCull((uint32_t)res.read_begin.size() - 1, res.read_begin.data(), (uint32_t)n, in.data(), cull_top_k_,
+               cull_cover_pct_, res.out.data());
+  AddDeltas(cull_stats_, before, dev.times(), std::make_pair(&GhostmReadCullStats::seconds_cull, &DeviceTimes::cull),
+            std::make_pair(&GhostmReadCullStats::cull_launches, &DeviceTimes::cull_launches),
+            std::make_pair(&GhostmReadCullStats::cull_reads, &DeviceTimes::cull_reads),
+            std::make_pair(&GhostmReadCullStats::cull_hits, &DeviceTimes::cull_hits),
+            std::make_pair(&GhostmReadCullStats::cull_kept, &DeviceTimes::cull_kept),
+            std::make_pair(&GhostmReadCullStats::cull_dups, &DeviceTimes::cull_dups),
+            std::make_pair(&GhostmReadCullStats::cull_culled, &DeviceTimes::cull_culled));
+  res.valid = true;
+  return res;
+}
+
+// -y 20 / -y 21: the -y 12 / -y 13 lines are in the parts, one per hit in hit
+// order. A read's hits may lie in several parts (tile groups), so the lines are
+// found over all the parts' text and the new text is assembled per read: the
+// KEPT hits in kept_rank order, each line with its rank and its covered count.
+void Session::FormatCull(bool frame) {
+  const ReadCullResult &res = ReadCull(frame);
+  struct LineAt {
+    const std::string *text;
+    size_t pos, len;  // without the newline
+  };
+  std::vector<LineAt> line;
+  line.reserve(res.out.size());
+  size_t bytes = 0;
+  for (size_t k = 0; k < used_parts_; ++k)
+    for (size_t t = 0; t < parts_[k].text.size(); ++t) {
+      const std::string &in = parts_[k].text[t];
+      size_t pos = 0;
+      for (size_t i = 0; i < parts_[k].hits[t].size(); ++i) {
+        const size_t nl = in.find('\n', pos);
+        if (nl == std::string::npos) throw Error("cull output: fewer lines than hits");
+        line.push_back(LineAt{&in, pos, nl - pos});
+        pos = nl + 1;
+      }
+      bytes += in.size();
+    }
+  if (line.size() != res.out.size()) throw Error("cull output: the lines are not the hits'");
+  std::string out;
+  out.reserve(bytes);
+  std::vector<uint32_t> by_rank;
+  for (size_t r = 0; r + 1 < res.read_begin.size(); ++r) {
+    const uint32_t b = res.read_begin[r], e = res.read_begin[r + 1];
+    by_rank.clear();
+    for (uint32_t h = b; h < e; ++h)
+      if (res.out[h].status == GHOSTM_CULL_KEPT) by_rank.push_back(h);
+    std::sort(by_rank.begin(), by_rank.end(),
+              [&](uint32_t x, uint32_t y) { return res.out[x].kept_rank < res.out[y].kept_rank; });
+    for (uint32_t h : by_rank) {
+      out.append(*line[h].text, line[h].pos, line[h].len);
+      char num[32], *p = num;
+      *p++ = '\t';
+      p = PutU32(p, res.out[h].kept_rank); *p++ = '\t';
+      p = PutU32(p, res.out[h].detail); *p++ = '\n';
+      out.append(num, (size_t)(p - num));
+    }
+  }
+  bool placed = false;
+  for (size_t k = 0; k < used_parts_; ++k)
+    for (std::string &t : parts_[k].text) {
+      t.clear();
+      if (!placed) t.swap(out), placed = true;
+    }
+  joined_valid_ = false;
 }
 
 // A subject's residues: every subject of a chunk is followed by one END.
@@ -2643,6 +2782,7 @@ void Session::DropResults() {
   hits_band_valid_ = false;
   read_rows_[0].Drop();
   pileup_[kBandLevel].Drop();
+  cull_[0].Drop();
   DropFrameResults();
   pileup_subj_.clear();
   pileup_[kTileLevel].Drop();
@@ -2655,8 +2795,9 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  // -y 6 to -y 19 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup, HitsReadRows, ReadPileup), not while the search runs
-  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 19;
+  // -y 6 to -y 21 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup, HitsReadRows, ReadPileup,
+  // ReadCull), not while the search runs
+  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 21;
   if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
@@ -2688,6 +2829,7 @@ void Session::Run(bool stream_to_file) {
   frame_stats_ = GhostmFrameStats{};
   read_rows_stats_ = GhostmReadRowsStats{};
   read_pileup_stats_ = GhostmReadPileupStats{};
+  cull_stats_ = GhostmReadCullStats{};
   QueryStats();
   merge_epoch_ = 0;
   DropResults();
@@ -2727,7 +2869,11 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    if (opt_.output_style >= 16)
+    if (opt_.output_style == 20 || opt_.output_style == 21) {
+      if (opt_.output_style == 21) FormatFrameTabular();
+      else FormatPathTabular(true);
+      FormatCull(opt_.output_style == 21);
+    } else if (opt_.output_style >= 16)
       FormatPileup(opt_.output_style >= 18 ? kFrameLevel : kBandLevel, opt_.output_style == 17 || opt_.output_style == 19);
     else if (opt_.output_style == 13 || opt_.output_style == 15) FormatFrameTabular();
     else if (opt_.output_style == 12 || opt_.output_style == 14) FormatPathTabular(true);
@@ -3103,6 +3249,20 @@ void Session::AddQueryChunkTiled(const QueryRecordView *recs, uint32_t n, uint32
   for (uint32_t r = 0; r < n; ++r)
     for (uint32_t k = first[r]; k < first[r + 1]; ++k) q.chunk.names.push_back(recs[r].name);
   PrepareQueryChunk(&q, false);
+  if (tile_groups_) {  // a name group also ends where a tile begins: every record, or every six of a DNA set
+    const uint32_t nrec = q.chunk.nseq;
+    q.group_first.clear();
+    q.group_last.clear();
+    for (uint32_t i = nrec; i-- > 0;) {
+      const bool tile_begins = i + 1 < nrec && (!rule.dna || table[i + 1].frame == 0);
+      if (tile_begins) q.group_end[i] = i + 1;
+      else if (i + 1 < nrec && q.group_end[i] != i + 1) q.group_end[i] = q.group_end[i + 1];
+    }
+    for (uint32_t i = 0; i < nrec; i = q.group_end[i]) {
+      q.group_first.push_back(i);
+      q.group_last.push_back(q.group_end[i] - 1);
+    }
+  }
   q.qlen.assign(q.chunk.nseq, 1);
   double seconds = 0;
   q.dev = dev.FormatQueryTiled(raw.data(), total, off.data(), len.data(), first.data(), n, rule.width, rule.dna,

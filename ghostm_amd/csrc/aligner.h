@@ -309,6 +309,34 @@ class Session {
   const ReadPileupResult &ReadPileup(bool frame);
   std::vector<uint32_t> ReadSubjectProfile(bool frame, uint32_t db_id, bool count_only = false);
   const GhostmReadPileupStats &ReadPileupStats() const { return read_pileup_stats_; }
+  // The cull of the last run's hits by their read-level alignments (the
+  // contract is above ReadCullGpu in include/ghostm_hip.h): one GhostmCullOut
+  // per hit of Hits(), from HitsBand()'s records (frame false) or HitsFrame()'s
+  // (frame true). A read is a maximal run of consecutive hits whose resolved
+  // records have one source record in the tile table (on an untiled set: one
+  // name group); dup_of is an index of Hits(). subject is the hit's db_id, the
+  // s range the path's, the q range the path's interval in forward-strand read
+  // units: letters on a protein set, nucleotides on a DNA set of a tiled setter
+  // at both levels (CullInterval), so that the two strands' hits meet. One
+  // DeviceModule::ReadCull call. Computed on first use and kept as long as the
+  // paths it was made from and the parameters. With -y 20 / -y 21 Run makes it
+  // and the text.
+  struct ReadCullResult {
+    std::vector<GhostmCullOut> out;
+    std::vector<uint32_t> read_begin;
+    bool valid = false;
+    void Drop() { *this = ReadCullResult(); }
+  };
+  const ReadCullResult &ReadCull(bool frame);
+  // top_k 1..255 (default 1), cover_pct 1..100 (default 50); a change drops the kept results
+  void SetCull(uint32_t top_k, uint32_t cover_pct);
+  const GhostmReadCullStats &ReadCullStats() const { return cull_stats_; }
+  // Tile groups: from the next tiled setter on, a name group also ends where
+  // the tile table begins a new tile (every record of a protein set, every six
+  // of a DNA set), so -b is kept per tile and not per read. Off by default;
+  // refused on a shard session.
+  void SetTileGroups(bool on);
+  bool TileGroups() const { return tile_groups_; }
   // Hit records of the last run in device memory (this session's GPU): copies
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
@@ -482,6 +510,12 @@ class Session {
   // (frame level, with shifts_sum): replaces the parts' text by one line per
   // subject with hits
   void FormatPileup(PathLevel lv, bool consensus);
+  // -y 20 (frame false) and -y 21 (frame true): from the -y 12 / -y 13 text
+  // already in the parts, per read the lines of its KEPT hits in kept_rank
+  // order with two more columns, rank and covered; a read may span several
+  // parts, so the text is assembled over the joined lines and replaces the
+  // parts' text as FormatPileup's does
+  void FormatCull(bool frame);
   uint32_t SubjectLength(const DbData &d, uint32_t subject) const;
 
   AlignerOptions opt_;
@@ -553,6 +587,10 @@ class Session {
   ReadPileupResult pileup_[3];                  // by PathLevel; the tile pile-up's shifts stay empty
   std::vector<GhostmSubjectPileup> pileup_subj_;  // pileup_[kTileLevel].subj as 40-byte records
   GhostmReadPileupStats read_pileup_stats_{};
+  ReadCullResult cull_[2];  // of the band paths [0] and of the frame paths [1]
+  uint32_t cull_top_k_ = 1, cull_cover_pct_ = 50;
+  GhostmReadCullStats cull_stats_{};
+  bool tile_groups_ = false;
   bool records_on_device_ = false;
   GhostmStats stats_{};
   unsigned threads_ = 1;

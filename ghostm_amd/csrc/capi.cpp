@@ -537,6 +537,49 @@ size_t GhostmSessionReadPileupStats(void *s, GhostmReadPileupStats *stats, size_
   return CopyStats(s, stats, size, std::mem_fn(&Session::ReadPileupStats));
 }
 
+size_t GhostmSessionReadCull(void *s, int frame, GhostmCullOut *out, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmCullOut> &r = static_cast<Session *>(s)->ReadCull(frame != 0).out;
+    if (!out) return r.size();
+    const size_t n = std::min(cap, r.size());
+    if (n) std::memcpy(out, r.data(), n * sizeof(GhostmCullOut));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+int GhostmSessionSetCull(void *s, uint32_t top_k, uint32_t cover_pct) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetCull(top_k, cover_pct);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+int GhostmSessionSetTileGroups(void *s, int on) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetTileGroups(on != 0);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionReadCullStats(void *s, GhostmReadCullStats *stats, size_t size) {
+  if (!s || !stats) return 0;
+  const GhostmReadCullStats st = static_cast<Session *>(s)->ReadCullStats();
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadCullStats)));
+  return sizeof(GhostmReadCullStats);
+}
+
 size_t GhostmSessionDeviceHits(void *s, void *dst_device, size_t cap) {
   try {
     if (!s) throw Error("null session");
@@ -591,12 +634,23 @@ int GhostmSearchMain(int argc, char **argv) {
   std::string db_fasta;
   uint32_t db_k = 4, db_mb = 0, band = 0;  // band 0: the session's default
   long shift_cost = -1;                    // -F; below 0: the session's default
+  long cull_k = -1, cull_pct = -1;         // -K, -C; below 0: the session's defaults
+  bool tile_groups = false;                // -g
   optind = 1;
   opterr = 1;
   int c;
-  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B, -F
-  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:")) >= 0) {
+  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B, -F, -g, -K, -C
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:")) >= 0) {
     switch (c) {
+      case 'g': tile_groups = true; break;  // with -T: -b per tile, not per read
+      case 'K':    // the cull's top_k, 1..255
+      case 'C': {  // the cull's cover_pct, 1..100
+        char *end = nullptr;
+        const long v = strtol(optarg, &end, 10);
+        if (end == optarg || *end || v < 1 || v > (c == 'K' ? 255 : 100)) return 1;
+        (c == 'K' ? cull_k : cull_pct) = v;
+        break;
+      }
       case 'T':  // reads longer than the width as overlapping tiles, this many letters apart
         tiled = true;
         tile_step = (uint32_t)atoi(optarg);
@@ -648,6 +702,7 @@ int GhostmSearchMain(int argc, char **argv) {
   if (pos.empty() || pos.size() % 2) return 1;
   if (have_d == !db_fasta.empty()) return 1;  // -d or -f, not both
   if (have_x && !tiled) return 1;             // -X cuts a tiled set only
+  if (tile_groups && !tiled) return 1;        // -g groups a tiled set only
   try {
     aln_argv.push_back(nullptr);
     AlignerOptions opt = ParseAlignerOptions((int)aln_argv.size() - 1, aln_argv.data());
@@ -656,6 +711,8 @@ int GhostmSearchMain(int argc, char **argv) {
     if (!have_d) session.SetDbFasta(db_fasta, db_k, db_mb);
     if (band) session.SetBand(band);
     if (shift_cost >= 0) session.SetFrameShift(-(int)shift_cost);
+    if (cull_k >= 0 || cull_pct >= 0) session.SetCull(cull_k >= 0 ? (uint32_t)cull_k : 1u, cull_pct >= 0 ? (uint32_t)cull_pct : 50u);
+    if (tile_groups) session.SetTileGroups(true);
     for (size_t k = 0; k < pos.size(); k += 2) {
       try {
         { std::ofstream touch(pos[k + 1].c_str()); }

@@ -117,6 +117,9 @@ struct DeviceTimes {
   double read_pileup = 0;                         // the read-level pile-up (k_read_pileup + k_pileup_finish<true>),
   uint64_t read_pileup_launches = 0, read_pileup_windows = 0, read_pileup_parts = 0;  // counted as the pile-up;
   uint64_t read_pileup_columns = 0, read_pileup_shifts = 0;  // '=', 'X', 'D' columns and shift columns charged
+  double cull = 0;                                // the read-level cull (k_read_cull): seconds, batches,
+  uint64_t cull_launches = 0, cull_reads = 0, cull_hits = 0;  // reads with a hit, hits,
+  uint64_t cull_kept = 0, cull_dups = 0, cull_culled = 0;     // and the hits by status
 };
 
 class DeviceModule {
@@ -353,6 +356,14 @@ class DeviceModule {
   void ReadPileup(DevDb *d, const ReadPileupGroup *groups, size_t ngroups, const uint32_t *ops, size_t ops_len,
                   uint32_t step, bool frame, uint32_t p0, uint32_t p1, uint32_t *depth, uint32_t *identities,
                   uint8_t *consensus, uint32_t *shifts, uint32_t *profile);
+
+  // The cull of nreads reads' hits (kern::k_read_cull; the contract is above
+  // ReadCullGpu in include/ghostm_hip.h): read r's hits are hit[read_begin[r],
+  // read_begin[r + 1]), out[i] hit i's record. Everything is checked first
+  // (ValidateReadCull, read_cull.h; throws with the reason before any upload or
+  // launch, out untouched). Needs no resident chunk. Adds to times().cull*.
+  void ReadCull(uint32_t nreads, const uint32_t *read_begin, uint32_t nhits, const GhostmCullHit *hit, uint32_t top_k,
+                uint32_t cover_pct, GhostmCullOut *out);
 
   // The read-level banded alignment of n hits (kern::k_band_fill, k_band_walk,
   // k_band_compact; the contract is in include/ghostm_hip.h): hit i aligns

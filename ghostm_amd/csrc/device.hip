@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "path_rows.h"
 #include "read_rows.h"
+#include "read_cull.h"
 #include "read_pileup.h"
 #include "pileup_plan.h"
 #include "qformat.h"
@@ -291,6 +292,8 @@ struct DeviceModule::Impl {
   DevBuf read_rows_hit, read_rows_ops, read_rows_out, read_rows_buf;
   // PathPileup: a batch's hits, words, plan lists and parts; a window's profile and finished arrays; the column counter
   DevBuf pileup_hit, pileup_ops, pileup_list, pileup_part, pileup_prof, pileup_out, pileup_cols;
+  // ReadCull: a batch's hits, its read table with the class lists and table offsets, its tables, its records
+  DevBuf cull_hit, cull_meta, cull_scratch, cull_out;
   // BandAlign: a batch's slots, its offsets / maxima / records, its direction bytes, its word slots, their packed words
   DevBuf band_hit, band_meta, band_dir, band_ops, band_cmp;
   // FrameAlign: the same five of its own
@@ -3075,12 +3078,112 @@ void DeviceModule::ReadPileup(DevDb *d, const ReadPileupGroup *groups, size_t ng
       });
 }
 
+static_assert(sizeof(kern::CullHit) == sizeof(GhostmCullHit) && sizeof(GhostmCullHit) == 24,
+              "GhostmCullHit is uploaded as it is");
+static_assert(sizeof(GhostmCullOut) == 16, "k_read_cull writes 4 words per hit");
+static_assert(kern::kCullArrays == kCullTableArrays, "read_cull.h sizes the tables");
+
+// The cull of nreads reads (kern::k_read_cull; the contract is above ReadCullGpu
+// in include/ghostm_hip.h). The reads go in batches cut by their bytes (hits,
+// records and, for a read above kCullCap hits, its table); a batch's reads are
+// listed by size class and every class with a read is one launch.
+void DeviceModule::ReadCull(uint32_t nreads, const uint32_t *read_begin, uint32_t nhits, const GhostmCullHit *hit,
+                            uint32_t top_k, uint32_t cover_pct, GhostmCullOut *out) {
+  if (!impl_) throw Error("read cull: the device module is not bound to a device");
+  Use();
+  Impl &I = *impl_;
+  std::string why = ValidateReadCull(nreads, read_begin, nhits, hit, top_k, cover_pct);
+  if (why.empty() && !out && nreads && read_begin[nreads] > read_begin[0]) why = "null: out";
+  if (!why.empty()) throw Error("read cull: " + why);
+  const size_t budget = EnvSize("GHOSTM_CULL_SCRATCH_MB", 1024) << 20;
+  const size_t max_reads = EnvSize("GHOSTM_CULL_BATCH_READS", SIZE_MAX);
+  const auto hits_of = [&](uint32_t r) { return read_begin[r + 1] - read_begin[r]; };
+  const auto table_words = [&](uint32_t r) {
+    return hits_of(r) > kern::kCullCap ? (size_t)kCullTableArrays * CullPow2(hits_of(r)) : (size_t)0;
+  };
+  std::vector<uint32_t> meta;  // read_begin[m + 1], the four lists, then (8-byte aligned) the table offsets
+  std::vector<unsigned long long> offs;
+  for (uint32_t b0 = 0; b0 < nreads;) {
+    size_t bytes = 0;
+    const uint32_t b1 = CutBatch(b0, nreads, max_reads, budget,
+                                 [&](uint32_t r) { return (size_t)hits_of(r) * 40 + table_words(r) * 4 + 8; }, &bytes);
+    const uint32_t m = b1 - b0, h0 = read_begin[b0], nh = read_begin[b1] - h0;
+    b0 = b1;
+    if (nh == 0) continue;
+    // the lists by class: wave, kCullMid, kCullCap, device memory
+    std::vector<uint32_t> list[4];
+    offs.clear();
+    size_t words = 0;
+    for (uint32_t r = 0; r < m; ++r) {
+      const uint32_t n = hits_of(b1 - m + r);
+      if (n == 0) continue;
+      list[n <= kern::kCullWave ? 0 : n <= kern::kCullMid ? 1 : n <= kern::kCullCap ? 2 : 3].push_back(r);
+      if (n > kern::kCullCap) {
+        offs.push_back(words);
+        words += table_words(b1 - m + r);
+      }
+    }
+    meta.assign(read_begin + (b1 - m), read_begin + b1 + 1);
+    size_t list_at[4];
+    for (int c = 0; c < 4; ++c) {
+      list_at[c] = meta.size();
+      meta.insert(meta.end(), list[c].begin(), list[c].end());
+    }
+    if (meta.size() & 1) meta.push_back(0);
+    const size_t offs_at = meta.size();
+    meta.resize(offs_at + 2 * offs.size());
+    if (!offs.empty()) memcpy(meta.data() + offs_at, offs.data(), offs.size() * 8);
+    I.cull_hit.Reserve((size_t)nh * sizeof(GhostmCullHit));
+    I.cull_meta.Reserve(meta.size() * 4);
+    I.cull_out.Reserve((size_t)nh * sizeof(GhostmCullOut));
+    if (words) I.cull_scratch.Reserve(words * 4);
+    hipStream_t st = S(stream_);
+    HIP_CHECK(hipMemcpyAsync(I.cull_hit.p, hit + h0, (size_t)nh * sizeof(GhostmCullHit), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(I.cull_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, st));
+    kern::CullArgs a{};
+    a.hit = I.cull_hit.as<kern::CullHit>();
+    a.hit_base = h0;
+    a.read_begin = I.cull_meta.as<uint32_t>();
+    a.top_k = top_k;
+    a.cover_pct = cover_pct;
+    a.scratch = I.cull_scratch.as<uint32_t>();
+    a.scratch_off = reinterpret_cast<const unsigned long long *>(I.cull_meta.as<uint32_t>() + offs_at);
+    a.out = I.cull_out.as<uint32_t>();
+    TimedLaunch(I.ev0, I.ev1, st, [&] {
+      for (int c = 0; c < 4; ++c) {
+        if (list[c].empty()) continue;
+        a.list = I.cull_meta.as<uint32_t>() + list_at[c];
+        a.nlist = (uint32_t)list[c].size();
+        const uint32_t per = c == 0 ? kern::kCullBlock / 64 : 1;
+        const dim3 grid((a.nlist + per - 1) / per), block(kern::kCullBlock);
+        if (c == 0) hipLaunchKernelGGL((kern::k_read_cull<kern::kCullWave, true, false>), grid, block, 0, st, a);
+        else if (c == 1) hipLaunchKernelGGL((kern::k_read_cull<kern::kCullMid, false, false>), grid, block, 0, st, a);
+        else if (c == 2) hipLaunchKernelGGL((kern::k_read_cull<kern::kCullCap, false, false>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((kern::k_read_cull<kern::kCullCap, false, true>), grid, block, 0, st, a);
+        HIP_CHECK(hipGetLastError());
+      }
+    });
+    HIP_CHECK(hipMemcpyAsync(out + h0, a.out, (size_t)nh * sizeof(GhostmCullOut), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    times_.cull += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+    times_.cull_launches += 1;
+    times_.cull_hits += nh;
+    for (uint32_t r = 0; r < m; ++r) times_.cull_reads += hits_of(b1 - m + r) != 0;
+    for (uint32_t k = 0; k < nh; ++k) {
+      const uint32_t s = out[h0 + k].status;
+      times_.cull_kept += s == GHOSTM_CULL_KEPT;
+      times_.cull_dups += s == GHOSTM_CULL_DUP;
+      times_.cull_culled += s == GHOSTM_CULL_CULLED;
+    }
+  }
+}
+
 const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_amd/srchash.py)
 
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_read_pileup/k_pileup_finish/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_read_pileup/k_pileup_finish/k_read_cull/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -3674,6 +3777,32 @@ size_t GhostmStageReadPileupStats(GhostmReadPileupStats *stats, size_t size) {
                                  dt.read_pileup_parts, dt.read_pileup_columns,  dt.read_pileup_shifts};
   std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadPileupStats)));
   return sizeof(GhostmReadPileupStats);
+}
+
+int ReadCullGpu(uint32_t nreads, const uint32_t read_begin[], uint32_t nhits, const GhostmCullHit hit[],
+                uint32_t top_k, uint32_t cover_pct, GhostmCullOut out[]) {
+  try {
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    DeviceModule &m = DeviceModule::Get();
+    if (m.device() < 0) m.Bind(0);  // no SetOptionGpu yet: the first device
+    m.ReadCull(nreads, read_begin, nhits, hit, top_k, cover_pct, out);
+    return 0;
+  } catch (std::exception &e) {
+    SetError(std::string("ReadCullGpu: ") + e.what());
+    return 1;
+  }
+}
+
+size_t GhostmStageReadCullStats(GhostmReadCullStats *stats, size_t size) {
+  if (!stats) return 0;
+  RefState &r = Ref();
+  std::lock_guard<std::mutex> lk(r.mu);
+  const DeviceTimes &dt = DeviceModule::Get().times();
+  const GhostmReadCullStats st{dt.cull,      dt.cull_launches, dt.cull_reads, dt.cull_hits,
+                               dt.cull_kept, dt.cull_dups,     dt.cull_culled};
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadCullStats)));
+  return sizeof(GhostmReadCullStats);
 }
 
 }  // extern "C"

@@ -5515,5 +5515,207 @@ __global__ __launch_bounds__(kTbBlock) void k_frame_compact(FrameArgs fa) {
   for (uint32_t k = lane; k < n; k += 64) dst[k] = src[k];
 }
 
+// ------------------------------------------------------------ read-level cull
+// k_read_cull<P, WAVE, GLOBAL>: the cull of one read by one team (the contract
+// is above ReadCullGpu in include/ghostm_hip.h; read_cull.h has the same steps
+// on the host). The team is a wave (WAVE: reads of at most 64 hits, kCullBlock
+// / 64 reads per workgroup) or the workgroup (tables of P hits in LDS, or, with
+// GLOBAL, in the read's slice of a.scratch for any size). No per-position
+// array: the read's 2 * nz endpoints (q_lo, q_hi + 1 of its nz hits with a
+// score) are sorted once, and one counter per segment between consecutive
+// endpoints holds the coverage (equal endpoints stay: a segment of length 0
+// adds nothing). The hits are ranked by a sort of (~score, index) keys; both
+// sorts are bitonic over the power of two p at or above n, padded with the
+// largest key. Then the hits are taken one by one in rank order, which is the
+// only serial dimension: the lanes run over the kept hits for the duplicate
+// test (a ballot gives the wave's first, the waves meet in an LDS minimum) and
+// over the hit's segments for d (wave reduction, then an LDS sum), and a kept
+// hit's lanes add 1 to its segments' counters. A workgroup step costs two
+// barriers; the LDS minimum and sum are double-buffered by the step's parity
+// so that clearing them needs no third.
+//
+// Table of a read, words: ep[2p], count[2p] (first the p 64-bit keys), order[p],
+// seg_lo[p], seg_hi[p], and the kept hits' index, subject, q_lo, q_hi, s_lo,
+// s_hi [p each]: 13 p words.
+struct CullHit {
+  uint32_t subject, score, q_lo, q_hi, s_lo, s_hi;
+};
+
+struct CullArgs {
+  const CullHit *hit;          // the batch's hits
+  uint32_t hit_base;           // hit[0]'s index in the call: read_begin counts from the call's first hit
+  const uint32_t *read_begin;  // the batch's reads, one more entry than reads
+  const uint32_t *list;        // this launch's reads: indices into read_begin
+  uint32_t nlist;
+  uint32_t top_k, cover_pct;
+  uint32_t *scratch;                      // GLOBAL: the tables,
+  const unsigned long long *scratch_off;  // list entry k's first word
+  uint32_t *out;                          // 4 words per hit of the batch
+};
+
+constexpr uint32_t kCullBlock = 256;
+constexpr uint32_t kCullArrays = 13;
+constexpr uint32_t kCullWave = 64, kCullMid = 256, kCullCap = 1024;  // the classes' largest reads
+constexpr uint32_t kCullNone = 0xFFFFFFFFu;
+
+template <bool WAVE> __device__ __forceinline__ void CullSync() {
+  if (WAVE) WaveSync();
+  else __syncthreads();
+}
+
+// a[0, p) ascending, p a power of two: every team thread calls it
+template <bool WAVE, class T>
+__device__ __forceinline__ void CullBitonic(T *a, uint32_t p, uint32_t tid, uint32_t nt) {
+  for (uint32_t k = 2; k <= p; k <<= 1)
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t t = tid; t < p / 2; t += nt) {
+        const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+        const T x = a[i], y = a[l];
+        if (((i & k) == 0) == (x > y)) {
+          a[i] = y;
+          a[l] = x;
+        }
+      }
+      CullSync<WAVE>();
+    }
+}
+
+// the first index of ep[0, e) whose value is not below v
+__device__ __forceinline__ uint32_t CullLower(const uint32_t *ep, uint32_t e, uint32_t v) {
+  uint32_t lo = 0, hi = e;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (ep[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// hdr: 6 LDS words of the team (nz; the step's first duplicate and d, twice)
+template <bool WAVE>
+__device__ __forceinline__ void CullRead(const CullArgs &a, uint32_t rd, uint32_t *T, uint32_t *hdr, uint32_t tid,
+                                         uint32_t nt) {
+  const uint32_t b = a.read_begin[rd], n = a.read_begin[rd + 1] - b;
+  if (n == 0) return;
+  const CullHit *hit = a.hit + (b - a.hit_base);
+  uint4 *out = reinterpret_cast<uint4 *>(a.out) + (b - a.hit_base);
+  uint32_t p = 2;
+  while (p < n) p <<= 1;
+  uint32_t *ep = T, *cnt = T + 2 * p, *ord = T + 4 * p, *slo = T + 5 * p, *shi = T + 6 * p, *kidx = T + 7 * p;
+  uint32_t *ksub = T + 8 * p, *kqlo = T + 9 * p, *kqhi = T + 10 * p, *kslo = T + 11 * p, *kshi = T + 12 * p;
+  unsigned long long *key = reinterpret_cast<unsigned long long *>(cnt);
+
+  for (uint32_t i = tid; i < p; i += nt) {
+    CullHit h{};
+    if (i < n) h = hit[i];
+    key[i] = i < n ? ((unsigned long long)(~h.score) << 32 | i) : ~0ull;
+    ep[2 * i] = h.score ? h.q_lo : kCullNone;
+    ep[2 * i + 1] = h.score ? h.q_hi + 1 : kCullNone;
+  }
+  if (tid == 0) {
+    hdr[0] = 0;
+    hdr[2] = hdr[3] = kCullNone;
+    hdr[4] = hdr[5] = 0;
+  }
+  CullSync<WAVE>();
+  CullBitonic<WAVE>(key, p, tid, nt);
+  CullBitonic<WAVE>(ep, 2 * p, tid, nt);
+  // the ranking, and nz: the hits with a score come first
+  for (uint32_t r = tid; r < n; r += nt) {
+    const unsigned long long kx = key[r];
+    ord[r] = (uint32_t)kx;
+    const bool has = (uint32_t)(kx >> 32) != kCullNone;
+    const bool next_has = r + 1 < n && (uint32_t)(key[r + 1] >> 32) != kCullNone;
+    if (has && !next_has) hdr[0] = r + 1;
+  }
+  CullSync<WAVE>();  // the keys are done with: their words become the counters
+  const uint32_t nz = hdr[0], e = 2 * nz;
+  for (uint32_t i = tid; i < n; i += nt) {
+    const CullHit h = hit[i];
+    if (h.score) {
+      slo[i] = CullLower(ep, e, h.q_lo);
+      shi[i] = CullLower(ep, e, h.q_hi + 1);
+    }
+  }
+  for (uint32_t j = tid; j < e; j += nt) cnt[j] = 0;
+  for (uint32_t r = nz + tid; r < n; r += nt) out[ord[r]] = make_uint4(r, 3u, kCullNone, 0u);  // EMPTY
+  CullSync<WAVE>();
+
+  uint32_t nk = 0;
+  for (uint32_t r = 0; r < nz; ++r) {
+    const uint32_t i = (uint32_t)__builtin_amdgcn_readfirstlane((int)ord[r]);
+    const CullHit h = hit[i];
+    const uint32_t lo = slo[i], hi = shi[i];
+    // the first kept hit with this subject whose ranges both meet this hit's
+    uint32_t first = kCullNone;
+    for (uint32_t k0 = 0; k0 < nk; k0 += nt) {
+      const uint32_t k = k0 + tid;
+      const bool m = k < nk && ksub[k] == h.subject && kqlo[k] <= h.q_hi && h.q_lo <= kqhi[k] &&
+                     kslo[k] <= h.s_hi && h.s_lo <= kshi[k];
+      const unsigned long long bal = __ballot(m);
+      if (bal) {
+        first = k0 + (tid & ~63u) + (uint32_t)__ffsll((long long)bal) - 1;
+        break;
+      }
+    }
+    uint32_t d = 0;
+    for (uint32_t j = lo + tid; j < hi; j += nt)
+      if (cnt[j] >= a.top_k) d += ep[j + 1] - ep[j];
+    for (int s = 32; s > 0; s >>= 1) d += (uint32_t)__shfl_xor((int)d, s);
+    if (!WAVE) {
+      const uint32_t par = r & 1;
+      if ((tid & 63) == 0) {
+        if (first != kCullNone) atomicMin(&hdr[2 + par], first);
+        if (d) atomicAdd(&hdr[4 + par], d);
+      }
+      __syncthreads();
+      first = hdr[2 + par];
+      d = hdr[4 + par];
+      if (tid == 0) {  // the next step's pair: last read before the previous step's second barrier
+        hdr[2 + (par ^ 1)] = kCullNone;
+        hdr[4 + (par ^ 1)] = 0;
+      }
+    }
+    uint32_t status, detail, rank = kCullNone;
+    if (first != kCullNone) {
+      status = 1;  // DUP
+      detail = b + kidx[first];
+    } else if (d * 100u >= a.cover_pct * (h.q_hi - h.q_lo + 1)) {
+      status = 2;  // CULLED
+      detail = d;
+    } else {
+      status = 0;  // KEPT
+      detail = d;
+      rank = nk;
+    }
+    if (tid == 0) out[i] = make_uint4(r, status, rank, detail);
+    if (status == 0) {
+      for (uint32_t j = lo + tid; j < hi; j += nt) cnt[j] += 1;
+      if (tid == 0) {
+        kidx[nk] = i;
+        ksub[nk] = h.subject;
+        kqlo[nk] = h.q_lo;
+        kqhi[nk] = h.q_hi;
+        kslo[nk] = h.s_lo;
+        kshi[nk] = h.s_hi;
+      }
+      ++nk;
+    }
+    CullSync<WAVE>();
+  }
+}
+
+template <uint32_t P, bool WAVE, bool GLOBAL> __global__ __launch_bounds__(kCullBlock) void k_read_cull(CullArgs a) {
+  GHOSTM_POISON_LDS();
+  constexpr uint32_t kTeams = WAVE ? kCullBlock / 64 : 1;
+  __shared__ __attribute__((aligned(16))) uint32_t tab[GLOBAL ? 2 : kTeams * kCullArrays * P];
+  __shared__ uint32_t hdrs[kTeams][6];
+  const uint32_t team = WAVE ? threadIdx.x >> 6 : 0;
+  const uint32_t k = blockIdx.x * kTeams + team;
+  if (k >= a.nlist) return;  // WAVE: the whole wave; otherwise the whole workgroup
+  uint32_t *T = GLOBAL ? a.scratch + a.scratch_off[k] : tab + team * kCullArrays * P;
+  CullRead<WAVE>(a, a.list[k], T, hdrs[team], WAVE ? threadIdx.x & 63 : threadIdx.x, WAVE ? 64 : kCullBlock);
+}
+
 }  // namespace kern
 }  // namespace ghostm

@@ -42,6 +42,11 @@ static int Usage() {
             << "        overlapping tiles tileStep letters apart, each read first cut at maxReadLength\n"
             << "       [-B band]: the half-width of -y 12 to 19's band around a hit's diagonal, 1..31 (default 31)\n"
             << "       [-F cost]: the frameshift cost of -y 13, 15, 18 and 19 (tiled DNA reads), 0 or more (default 15)\n"
+            << "       [-g]: with -T, the best -b hits kept per tile and not per read (tile groups)\n"
+            << "       [-K topK] [-C coverPct]: -y 20 and -y 21, the -y 12 and -y 13 lines of the hits the read-level\n"
+            << "        cull keeps, per read by read-level score, with their rank and covered count; a hit is dropped\n"
+            << "        when it repeats a kept alignment, or when topK (1..255, default 1) kept hits already cover\n"
+            << "        coverPct (1..100, default 50) per cent of its stretch of the read\n"
             << "synth: ghostm synth -d db.fasta -q queries.fasta [-n nq] [-N dbResidues] [-s seed]\n";
   return 1;
 }

@@ -202,6 +202,46 @@ class GhostmReadPileupStats(ctypes.Structure):
     ]
 
 
+class GhostmCullHit(ctypes.Structure):
+    """one hit of the read-level cull (24 bytes): subject, score, the inclusive
+    ranges on the read and on the subject."""
+
+    _fields_ = [
+        ("subject", c_uint32),
+        ("score", c_uint32),
+        ("q_lo", c_uint32),
+        ("q_hi", c_uint32),
+        ("s_lo", c_uint32),
+        ("s_hi", c_uint32),
+    ]
+
+
+class GhostmCullOut(ctypes.Structure):
+    """one hit's record of the read-level cull (16 bytes)."""
+
+    _fields_ = [
+        ("order", c_uint32),
+        ("status", c_uint32),
+        ("kept_rank", c_uint32),
+        ("detail", c_uint32),
+    ]
+
+
+class GhostmReadCullStats(ctypes.Structure):
+    """the counters of the read-level cull (GhostmSessionReadCullStats,
+    GhostmStageReadCullStats)."""
+
+    _fields_ = [
+        ("seconds_cull", ctypes.c_double),
+        ("cull_launches", c_uint64),
+        ("cull_reads", c_uint64),
+        ("cull_hits", c_uint64),
+        ("cull_kept", c_uint64),
+        ("cull_dups", c_uint64),
+        ("cull_culled", c_uint64),
+    ]
+
+
 class GhostmDbChunkInfo(ctypes.Structure):
     """one resident DB chunk: the values of its .inf and .ind headers."""
 
@@ -371,6 +411,11 @@ SIGNATURES = {
                                      c_uint32, POINTER(GhostmBandSource), POINTER(GhostmHitPath), u32p, c_size_t,
                                      c_uint32, c_uint32, c_int, u32p, u32p, POINTER(ctypes.c_uint8), u32p, u32p]),
     "GhostmStageReadPileupStats": (c_size_t, [POINTER(GhostmReadPileupStats), c_size_t]),
+    "ReadCullGpu": (c_int, [c_uint32, u32p, c_uint32, POINTER(GhostmCullHit), c_uint32, c_uint32,
+                            POINTER(GhostmCullOut)]),
+    "GhostmReadCullHost": (c_int, [c_uint32, u32p, c_uint32, POINTER(GhostmCullHit), c_uint32, c_uint32,
+                                   POINTER(GhostmCullOut)]),
+    "GhostmStageReadCullStats": (c_size_t, [POINTER(GhostmReadCullStats), c_size_t]),
     "GhostmBuildIndexGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, u32p, u32p, u32p, c_int,
                                     POINTER(c_float)]),
     "GhostmFormatQueriesGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_uint32,
@@ -440,6 +485,10 @@ SIGNATURES = {
     "GhostmSessionReadPileupArrays": (c_size_t, [c_void_p, c_int, u32p, u32p, POINTER(ctypes.c_uint8), u32p, c_size_t]),
     "GhostmSessionReadSubjectProfile": (c_size_t, [c_void_p, c_int, c_uint32, u32p, c_size_t]),
     "GhostmSessionReadPileupStats": (c_size_t, [c_void_p, POINTER(GhostmReadPileupStats), c_size_t]),
+    "GhostmSessionReadCull": (c_size_t, [c_void_p, c_int, POINTER(GhostmCullOut), c_size_t]),
+    "GhostmSessionSetCull": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "GhostmSessionSetTileGroups": (c_int, [c_void_p, c_int]),
+    "GhostmSessionReadCullStats": (c_size_t, [c_void_p, POINTER(GhostmReadCullStats), c_size_t]),
     "GhostmSessionDeviceHits": (c_size_t, [c_void_p, c_void_p, c_size_t]),
     "GhostmSessionStats": (c_int, [c_void_p, POINTER(GhostmStats)]),
     "GhostmSessionStatsSized": (c_size_t, [c_void_p, POINTER(GhostmStats), c_size_t]),

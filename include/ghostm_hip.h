@@ -982,6 +982,95 @@ typedef struct GhostmSubjectReadPileup {  /* 48 bytes; the first 40 are GhostmSu
   uint64_t shifts_sum;      /* the sum of shifts over the subject; 0 in band mode */
 } GhostmSubjectReadPileup;
 
+/* The read-level cull: per read, its hits ranked by read-level score, the hits
+ * that find one alignment twice marked, and the hits marked whose stretch of
+ * the read better hits already cover. All arithmetic is on integers; the
+ * kernel equals the host model exactly.
+ *
+ * Input: nreads reads; read r's hits are hit[read_begin[r] ..
+ * read_begin[r + 1]) (read_begin has nreads + 1 entries, monotone, the last at
+ * most nhits; hits outside every read get no output). A hit is its subject,
+ * its score and two inclusive ranges, q on the read and s on the subject, lo
+ * <= hi, every coordinate below 2^25 (so that d * 100 fits 32 bits).
+ *
+ * Per read:
+ *   1. The hits are ordered by score descending, then input index ascending.
+ *   2. In that order every hit gets its status:
+ *        EMPTY   its score is 0. Such a hit covers nothing.
+ *        DUP     an earlier KEPT hit has the same subject, a q range that
+ *                meets this one's and an s range that meets this one's (ranges
+ *                meet when they share a position; q_hi + 1 == the other's q_lo
+ *                does not). detail names the first such hit in rank order, as
+ *                its index in the call's hit array.
+ *        CULLED  otherwise, with d = the positions p of [q_lo, q_hi] that at
+ *                least top_k earlier KEPT hits contain in their q range, when
+ *                d * 100 >= cover_pct * (q_hi - q_lo + 1). detail = d.
+ *        KEPT    otherwise. kept_rank is the count of the read's hits kept
+ *                before it; detail = d.
+ *   3. out[i] is hit i's record: order (its place in the ranking, from 0),
+ *      status, kept_rank (0xFFFFFFFF unless KEPT) and detail (0 for EMPTY).
+ *
+ * top_k is 1..255, cover_pct 1..100. */
+typedef struct GhostmCullHit {  /* 24 bytes */
+  uint32_t subject;
+  uint32_t score;
+  uint32_t q_lo, q_hi;  /* inclusive, on the read */
+  uint32_t s_lo, s_hi;  /* inclusive, on the subject */
+} GhostmCullHit;
+
+enum { GHOSTM_CULL_KEPT = 0, GHOSTM_CULL_DUP = 1, GHOSTM_CULL_CULLED = 2, GHOSTM_CULL_EMPTY = 3 };
+
+typedef struct GhostmCullOut {  /* 16 bytes */
+  uint32_t order;      /* the hit's place in its read's ranking */
+  uint32_t status;     /* GHOSTM_CULL_* */
+  uint32_t kept_rank;  /* 0xFFFFFFFF unless KEPT */
+  uint32_t detail;     /* d; DUP: the index of the kept hit it repeats; EMPTY: 0 */
+} GhostmCullOut;
+
+/* ReadCullGpu (kernel k_read_cull) is stage level, but needs neither
+ * SetQueryGpu nor SetDbGpu: the records are all it reads. It runs on
+ * SetOptionGpu's device, or on device 0 when that was not called. Everything is checked
+ * on the host before any upload or launch; a refused call returns 1, leaves
+ * out untouched and names its reason in GhostmGetLastError:
+ *   "null"    a null pointer where one is needed (hit with nhits > 0,
+ *             read_begin with nreads > 0, out when a read has a hit)
+ *   "reads"   read_begin not monotone or ending past nhits; a read of more
+ *             than 2^24 hits
+ *   "range"   lo > hi
+ *   "bounds"  a coordinate at or over 2^25
+ *   "param"   top_k or cover_pct out of range
+ * Reads of at most 64 hits take one wave each, reads of at most 256 and of at
+ * most 1024 one workgroup with the tables in LDS, larger reads one workgroup
+ * with the tables in device memory; no read is too large for the device path
+ * and none is done on the host. The reads go in batches of at most
+ * GHOSTM_CULL_BATCH_READS reads (default: no limit) and GHOSTM_CULL_SCRATCH_MB
+ * megabytes of records and tables (default 1024); 16 bytes per hit are read
+ * back. */
+int ReadCullGpu(uint32_t nreads, const uint32_t read_begin[], uint32_t nhits, const GhostmCullHit hit[],
+                uint32_t top_k, uint32_t cover_pct, GhostmCullOut out[]);
+
+/* The same on the host, with no device call: the model the kernel equals
+ * exactly, with the same checks and reasons. */
+int GhostmReadCullHost(uint32_t nreads, const uint32_t read_begin[], uint32_t nhits,
+                       const GhostmCullHit hit[], uint32_t top_k, uint32_t cover_pct,
+                       GhostmCullOut out[]);
+
+/* The counters of the read-level cull, a struct of their own like
+ * GhostmBandStats; GhostmStats keeps its layout. */
+typedef struct GhostmReadCullStats {
+  double seconds_cull;     /* k_read_cull, device time */
+  uint64_t cull_launches;  /* batches of reads */
+  uint64_t cull_reads;
+  uint64_t cull_hits;
+  uint64_t cull_kept;
+  uint64_t cull_dups;
+  uint64_t cull_culled;
+} GhostmReadCullStats;
+
+/* The cull counters behind the stage-level calls; GhostmStageBandStats'
+ * conventions. */
+size_t GhostmStageReadCullStats(GhostmReadCullStats *stats, size_t size);
+
 /* A session without a database: `aln`'s options without -d (giving it is an
  * error). With -i the query chunks are loaded as GhostmSessionCreate loads
  * them; without -i the session starts with neither input and the queries come
@@ -1163,8 +1252,8 @@ int GhostmSessionRun(void *session);
  * from the read-level score, priced like every line of the session for a query
  * of the source's m letters (search space m x the database's residues, the
  * reference's float / double steps). A hit whose read-level score is 0 prints
- * its -y 7 line unchanged. Hits are not re-ranked or re-merged by the new
- * scores. Written at the end of the run, like -y 7.
+ * its -y 7 line unchanged. The lines keep the order of the hits (-y 20 ranks and
+ * culls them by the new scores). Written at the end of the run, like -y 7.
  * -y 13 (DNA sets of a tiled setter only) prints the thirteen -y 7 columns
  * from the hit's frame path (GhostmSessionHitsFrame) and two more, qframe and
  * frameshifts: length counts the '=', 'X', 'I' and 'D' columns, mismatch the
@@ -1175,7 +1264,8 @@ int GhostmSessionRun(void *session);
  * frameshifts is the summed length of the shift runs; evalue and bitscore are
  * priced as -y 12 prices them, for a query of m letters. A hit whose frame
  * score is 0 prints its tile path in the same units (strand positions
- * 3 x (offset + q) + g, the end + 2, frameshifts 0). Hits are not re-ranked.
+ * 3 x (offset + q) + g, the end + 2, frameshifts 0). The lines keep the order
+ * of the hits (-y 21 ranks and culls them).
  * -y 16 and -y 17 are the -y 10 and -y 11 lines from the read-level pile-up of
  * the band paths (GhostmSessionReadPileup with frame = 0). -y 18 (DNA sets of a
  * tiled setter only, as -y 13) is the -y 10 line from the pile-up of the frame
@@ -1245,7 +1335,8 @@ size_t GhostmSessionRowBytes(void *session, uint8_t *rows, size_t cap);
  * shard sessions (each rank its own hits): one BandAlignGpu-style call per
  * (query chunk, DB chunk) that has hits, computed on first use and kept until
  * the next run, GhostmSessionSetQueries*, GhostmSessionSetDb* or change of
- * band. Hits are not re-ranked or re-merged by the read-level scores. */
+ * band. The records come in the order of GhostmSessionHits; ranking and
+ * culling a read's hits by these scores is GhostmSessionReadCull's (-y 20). */
 size_t GhostmSessionHitsBand(void *session, GhostmHitPath *rec, size_t cap);
 size_t GhostmSessionBandOps(void *session, uint32_t *ops, size_t cap);
 
@@ -1273,7 +1364,8 @@ size_t GhostmSessionBandStats(void *session, GhostmBandStats *stats, size_t size
  * subject. One FrameAlignGpu-style call per (query chunk, DB chunk) that has
  * hits, computed on first use and kept until the next run,
  * GhostmSessionSetQueries*, GhostmSessionSetDb*, a change of band or of the
- * frameshift cost. Hits are not re-ranked. */
+ * frameshift cost. The records come in the order of GhostmSessionHits; ranking
+ * and culling by these scores is GhostmSessionReadCull's with frame = 1 (-y 21). */
 size_t GhostmSessionHitsFrame(void *session, GhostmHitPath *rec, size_t cap);
 size_t GhostmSessionFrameOps(void *session, uint32_t *ops, size_t cap);
 
@@ -1360,6 +1452,45 @@ size_t GhostmSessionReadSubjectProfile(void *session, int frame, uint32_t db_id,
  * until the read-level pile-up is asked for); the size convention of
  * GhostmSessionBandStats. */
 size_t GhostmSessionReadPileupStats(void *session, GhostmReadPileupStats *stats, size_t size);
+
+/* The cull of the last run's hits by their read-level alignments (the contract
+ * is above ReadCullGpu): one GhostmCullOut per hit of GhostmSessionHits, from
+ * the records of GhostmSessionHitsBand (frame = 0) or GhostmSessionHitsFrame
+ * (frame = 1, a DNA set of a tiled setter). With out NULL returns the count,
+ * else copies min(cap, count) records and returns that; (size_t)-1 on error.
+ *   reads     a read is a maximal run of consecutive hits whose resolved
+ *             records have the same source record in the tile table; on an
+ *             untiled set a read is the name group. detail of a DUP is an index
+ *             of GhostmSessionHits.
+ *   subject   GhostmHit.db_id; s_lo, s_hi: the path's subject range
+ *   score     the path's score; a hit whose read-level score is 0 is EMPTY
+ *   q_lo, q_hi  the path's interval in forward-strand read units: letters on a
+ *             protein set; on a DNA set of a tiled setter nucleotides from 0 at
+ *             both levels: the frame path's interval as -y 13 prints it (less
+ *             1, sorted), the band path's frame letters c of frame f as 3c + f
+ *             % 3 to 3c + f % 3 + 2 on the strand, turned round on the reverse
+ *             strand with the read's kept n. Hits of the two strands land on
+ *             the same coordinates, so they cull each other.
+ * One ReadCullGpu-style pass over all hits (its batches and variables).
+ * Computed on first use; kept until the next run, query set, database, SetBand
+ * (and SetFrameShift for frame = 1) or SetCull. -y 20 prints, per read, the
+ * -y 12 line of every KEPT hit in kept_rank order with two more columns, rank
+ * (kept_rank) and covered (d); -y 21 the same from the -y 13 line. */
+size_t GhostmSessionReadCull(void *session, int frame, GhostmCullOut *out, size_t cap);
+/* top_k 1..255 (default 1) and cover_pct 1..100 (default 50) of the session's
+ * cull; a change drops the kept result. Returns 0, or 1 ("param"). */
+int GhostmSessionSetCull(void *session, uint32_t top_k, uint32_t cover_pct);
+/* The cull's counters since the last run began; GhostmSessionBandStats'
+ * conventions. */
+size_t GhostmSessionReadCullStats(void *session, GhostmReadCullStats *stats, size_t size);
+/* Tile groups: with on != 0, from the next tiled setter on a name group also
+ * ends where the tile table begins a new tile (every record of a protein set,
+ * every six records of a DNA set), so the search keeps the best -b hits per
+ * tile and not per read, and a read that carries two genes keeps hits of both.
+ * The hit capacity grows with the group count. Off by default: then nothing
+ * differs. A shard session refuses it as it refuses a tiled set. Returns 0, or
+ * 1 on error. */
+int GhostmSessionSetTileGroups(void *session, int on);
 
 /* The same records resident on the session's GPU, for a device-to-device
  * gather across ranks: copies min(n, cap) records to dst_device
