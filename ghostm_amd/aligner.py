@@ -24,6 +24,7 @@ module only marshals arguments.
 from __future__ import annotations
 
 import ctypes
+import os
 import subprocess
 from typing import Sequence
 
@@ -564,6 +565,76 @@ def stage_read_cull_stats() -> dict:
     lib = native.load()
     st = native.GhostmReadCullStats()
     lib.GhostmStageReadCullStats(ctypes.byref(st), ctypes.sizeof(st))
+    return {n: getattr(st, n) for n, _ in st._fields_}
+
+
+# GhostmLcaHit and GhostmLcaOut (include/ghostm_hip.h)
+LCA_HIT_DTYPE = np.dtype([("node", "<u4"), ("score", "<u4"), ("q_lo", "<u4"), ("q_hi", "<u4")])
+LCA_OUT_DTYPE = np.dtype([("node", "<u4"), ("depth", "<u4"), ("votes", "<u4"), ("support", "<u4"), ("lca", "<u4"),
+                          ("candidates", "<u4"), ("unmapped", "<u4"), ("best_score", "<u4")])
+_U32P = ctypes.POINTER(ctypes.c_uint32)
+
+
+def taxonomy_depths(parent) -> np.ndarray:
+    """The depths of a taxonomy given as parent indices (GhostmTaxonomyDepths;
+    no device): checked as SetTaxonomyGpu checks it."""
+    par = np.ascontiguousarray(parent, dtype=np.uint32).reshape(-1)
+    depth = np.zeros(len(par), dtype=np.uint32)
+    if native.load().GhostmTaxonomyDepths(len(par), par.ctypes.data_as(_U32P) if len(par) else None,
+                                          depth.ctypes.data_as(_U32P) if len(par) else None) != 0:
+        raise GhostmError(native.last_error())
+    return depth
+
+
+def set_taxonomy_gpu(parent) -> None:
+    """Makes the taxonomy resident for read_lca() (SetTaxonomyGpu); it stays
+    until the next call or FreeGpu. A refused call keeps the previous one."""
+    par = np.ascontiguousarray(parent, dtype=np.uint32).reshape(-1)
+    if native.load().SetTaxonomyGpu(len(par), par.ctypes.data_as(_U32P) if len(par) else None) != 0:
+        raise GhostmError(native.last_error())
+
+
+def _read_lca_args(read_begin, hits, top_pct, support_pct, out):
+    rb = np.ascontiguousarray(read_begin, dtype=np.uint32).reshape(-1)
+    h = np.ascontiguousarray(hits, dtype=LCA_HIT_DTYPE).reshape(-1)
+    nreads = max(len(rb), 1) - 1
+    if out is None:
+        out = np.zeros(nreads, dtype=LCA_OUT_DTYPE)
+    if out.dtype != LCA_OUT_DTYPE or not out.flags.c_contiguous or len(out) < nreads:
+        raise ValueError("read lca: out must be contiguous LCA_OUT_DTYPE records, one per read")
+    args = (nreads, rb.ctypes.data_as(_U32P) if len(rb) else None, len(h),
+            h.ctypes.data_as(ctypes.POINTER(native.GhostmLcaHit)) if len(h) else None, int(top_pct), int(support_pct),
+            out.ctypes.data_as(ctypes.POINTER(native.GhostmLcaOut)) if len(out) else None)
+    return args, out, (rb, h)
+
+
+def read_lca_host(parent, read_begin, hits, top_pct=10, support_pct=100, out=None):
+    """The host model of the per-read taxonomic assignment (GhostmReadLcaHost;
+    no device) over the taxonomy `parent`: read r's hits are
+    hits[read_begin[r]:read_begin[r + 1]] (LCA_HIT_DTYPE). Returns one
+    LCA_OUT_DTYPE record per read."""
+    par = np.ascontiguousarray(parent, dtype=np.uint32).reshape(-1)
+    args, out, _keep = _read_lca_args(read_begin, hits, top_pct, support_pct, out)
+    if native.load().GhostmReadLcaHost(len(par), par.ctypes.data_as(_U32P) if len(par) else None, *args) != 0:
+        raise GhostmError(native.last_error())
+    return out
+
+
+def read_lca(read_begin, hits, top_pct=10, support_pct=100, out=None):
+    """ReadLcaGpu (k_read_lca_wave, k_read_lca) over the taxonomy of
+    set_taxonomy_gpu(); arguments and result as read_lca_host. Needs no
+    resident chunk."""
+    args, out, _keep = _read_lca_args(read_begin, hits, top_pct, support_pct, out)
+    if native.load().ReadLcaGpu(*args) != 0:
+        raise GhostmError(native.last_error())
+    return out
+
+
+def stage_read_lca_stats() -> dict:
+    """The assignment's counters behind the stage-level calls (GhostmStageReadLcaStats)."""
+    lib = native.load()
+    st = native.GhostmReadLcaStats()
+    lib.GhostmStageReadLcaStats(ctypes.byref(st), ctypes.sizeof(st))
     return {n: getattr(st, n) for n, _ in st._fields_}
 
 
@@ -1141,6 +1212,73 @@ class Session:
         shard session."""
         if native.load().GhostmSessionSetTileGroups(self._h, int(bool(on))) != 0:
             raise GhostmError(native.last_error())
+
+    def set_taxonomy(self, taxid, parent, subject_node) -> None:
+        """A taxonomy for the resident database (GhostmSessionSetTaxonomy):
+        taxid[i] labels node i (distinct, at least 1), parent[i] is its parent's
+        index (the root its own), subject_node[db_id] a node or 0xFFFFFFFF. A
+        refusal leaves the session as it was; set_db* drop the taxonomy."""
+        tid = np.ascontiguousarray(taxid, dtype=np.uint32).reshape(-1)
+        par = np.ascontiguousarray(parent, dtype=np.uint32).reshape(-1)
+        sub = np.ascontiguousarray(subject_node, dtype=np.uint32).reshape(-1)
+        if len(tid) != len(par):
+            raise GhostmError("set taxonomy: taxonomy: taxid and parent differ in length")
+        if native.load().GhostmSessionSetTaxonomy(self._h, len(par), tid.ctypes.data_as(_U32P) if len(tid) else None,
+                                                  par.ctypes.data_as(_U32P) if len(par) else None, len(sub),
+                                                  sub.ctypes.data_as(_U32P) if len(sub) else None) != 0:
+            raise GhostmError(native.last_error())
+
+    def set_taxonomy_files(self, nodes_path: str, map_path: str) -> None:
+        """The same from a nodes file (taxid, parent taxid per line; NCBI's
+        nodes.dmp reads as it is) and a map file (subject name, taxid)
+        (GhostmSessionSetTaxonomyFiles)."""
+        if native.load().GhostmSessionSetTaxonomyFiles(self._h, os.fsencode(nodes_path), os.fsencode(map_path)) != 0:
+            raise GhostmError(native.last_error())
+
+    def taxonomy_info(self) -> dict:
+        """nodes (0: no taxonomy), subjects_mapped, subjects_unmapped and the
+        map lines that matched no subject (GhostmSessionTaxonomyInfo)."""
+        st = native.GhostmTaxonomyInfo()
+        native.load().GhostmSessionTaxonomyInfo(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    def set_lca(self, top_pct: int = 10, support_pct: int = 100) -> None:
+        """read_lca()'s parameters: a kept hit votes when its score is within
+        top_pct (0..100) per cent of the best on its stretch of the read; the
+        taxon is the deepest node with support_pct (51..100) per cent of the
+        votes. A refusal leaves the old values; a change drops the kept result."""
+        top, sup = int(top_pct), int(support_pct)
+        if not (0 <= top <= 100 and 51 <= sup <= 100):  # GhostmSessionSetLca's ranges; an int beyond uint32 would wrap
+            raise GhostmError(f"lca: param: top_pct {top}, support_pct {sup} outside 0..100, 51..100")
+        if native.load().GhostmSessionSetLca(self._h, top, sup) != 0:
+            raise GhostmError(native.last_error())
+
+    def read_lca(self, frame: bool = False, with_begin: bool = False):
+        """One LCA_OUT_DTYPE record per read of read_cull(frame)
+        (GhostmSessionReadLca): the taxon of the read from the hits the cull
+        keeps. node and lca are node indices. with_begin: also every read's
+        first hit as an index of hits(), plus the end. Computed on first use."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        f = int(bool(frame))
+        n = lib.GhostmSessionReadLca(self._h, f, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        out = np.zeros(n, dtype=LCA_OUT_DTYPE)
+        if n and lib.GhostmSessionReadLca(self._h, f, out.ctypes.data_as(ctypes.POINTER(native.GhostmLcaOut)), n) == bad:
+            raise GhostmError(native.last_error())
+        if not with_begin:
+            return out
+        begin = np.zeros(n + 1, dtype=np.uint32)
+        if lib.GhostmSessionReadLcaBegin(self._h, f, begin.ctypes.data_as(_U32P), n + 1) == bad:
+            raise GhostmError(native.last_error())
+        return out, begin
+
+    def read_lca_stats(self) -> dict:
+        """The assignment's counters since the last run (GhostmSessionReadLcaStats)."""
+        st = native.GhostmReadLcaStats()
+        native.load().GhostmSessionReadLcaStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        return {name: getattr(st, name) for name, _ in st._fields_}
 
     def read_subject_profile(self, frame: bool, db_id: int) -> np.ndarray:
         """The 32-slot rows of subject db_id from the read-level paths, shape

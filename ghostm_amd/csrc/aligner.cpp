@@ -16,8 +16,11 @@
 #include <exception>
 #include <fstream>
 #include <iostream>
+#include <sstream>
 #include <stdexcept>
 #include <thread>
+#include <unordered_map>
+#include <unordered_set>
 
 #include "band_align.h"
 #include "frame_align.h"
@@ -25,6 +28,7 @@
 #include "db_set.h"
 #include "query_set.h"
 #include "query_tiles.h"
+#include "read_lca.h"
 #include "worker_pool.h"
 
 namespace ghostm {
@@ -1495,7 +1499,8 @@ const LineFormat &Session::Format() {
       (opt_.output_style >= 6 && opt_.output_style <= 9) || (opt_.output_style >= 12 && opt_.output_style <= 15) ||
       opt_.output_style == 20 || opt_.output_style == 21;
   // -y 10, -y 11 and -y 16 to -y 19 replace the hit lines after the run: style 1's lines, which need no E-value, stand in
-  const bool pileup = opt_.output_style == 10 || opt_.output_style == 11 || (opt_.output_style >= 16 && opt_.output_style <= 19);
+  const bool pileup = opt_.output_style == 10 || opt_.output_style == 11 || (opt_.output_style >= 16 && opt_.output_style <= 19) ||
+                      opt_.output_style == 22 || opt_.output_style == 23;  // and the taxon lines
   if (!format_) format_.reset(new LineFormat(tabular ? 0 : pileup ? 1 : opt_.output_style, opt_.karlin, 4095));
   return *format_;
 }
@@ -1858,6 +1863,7 @@ void Session::SetBand(uint32_t band) {
   read_rows_[0].Drop();
   pileup_[kBandLevel].Drop();
   cull_[0].Drop();
+  lca_[0].Drop();
   DropFrameResults();  // the frame pass runs inside the same band
 }
 
@@ -1948,6 +1954,7 @@ void Session::DropFrameResults() {
   read_rows_[1].Drop();
   pileup_[kFrameLevel].Drop();
   cull_[1].Drop();
+  lca_[1].Drop();
 }
 
 void Session::SetFrameShift(int shift) {
@@ -2197,7 +2204,9 @@ void Session::SetCull(uint32_t top_k, uint32_t cover_pct) {
   cull_top_k_ = top_k;
   cull_cover_pct_ = cover_pct;
   cull_[0].Drop();
+  lca_[0].Drop();
   cull_[1].Drop();
+  lca_[1].Drop();
 }
 
 void Session::SetTileGroups(bool on) {
@@ -2205,12 +2214,38 @@ void Session::SetTileGroups(bool on) {
   tile_groups_ = on;
 }
 
-// The cull of every final hit (ReadCull). The reads: consecutive hits of one
+// The cull's input record of final hit h (ReadCull; ReadLca for the hits the
+// cull kept). The reads: consecutive hits of one
 // source record (tiled set) or of one name group (untiled set). A hit's record
 // is its read-level path's: the q interval in forward-strand read units
 // (nucleotides on a tiled DNA set: a band path's frame letters c of frame f
 // cover strand positions 3c + f % 3 to 3c + f % 3 + 2, a frame path's q_* are
 // strand positions already; ForwardNt turns the reverse strand's round).
+GhostmCullHit Session::CullRecord(bool frame, size_t h, const GhostmHit &hit, const GhostmHitPath &x, uint64_t *key) const {
+  const HitSource &hs = hit_source_[h];
+  const QueryData &q = queries_[hs.qi];
+  const bool tiled = !tile_table_.empty();
+  const GhostmQueryTile *t = tiled ? &tile_table_[q.global_base + hs.query] : nullptr;
+  // the read's key: the source record, or the name group's end over all chunks
+  if (key) *key = tiled ? t->record : (uint64_t)q.global_base + q.group_end[hs.query];
+  GhostmCullHit c{hit.db_id, x.score, 0, 0, x.s_start, x.s_end};
+  if (x.score) {
+    if (tiled && tile_dna_) {
+      const uint32_t g = t->frame % 3, strand = t->frame / 3, nt = tile_read_nt_[t->record];
+      const uint32_t p0 = frame ? x.q_start : 3 * x.q_start + g, p1 = frame ? x.q_end : 3 * x.q_end + g + 2;
+      const uint32_t a = ForwardNt(strand, nt, p0), b = ForwardNt(strand, nt, p1);
+      c.q_lo = std::min(a, b);
+      c.q_hi = std::max(a, b);
+    } else {
+      c.q_lo = x.q_start;
+      c.q_hi = x.q_end;
+    }
+  } else {
+    c.s_lo = c.s_hi = 0;  // an EMPTY hit: its ranges say nothing
+  }
+  return c;
+}
+
 const Session::ReadCullResult &Session::ReadCull(bool frame) {
   ReadCullResult &res = cull_[frame ? 1 : 0];
   if (res.valid) return res;
@@ -2222,31 +2257,10 @@ const Session::ReadCullResult &Session::ReadCull(bool frame) {
   res.read_begin.assign(1, 0);
   uint64_t prev = UINT64_MAX;
   for (size_t h = 0; h < n; ++h) {
-    const HitSource &hs = hit_source_[h];
-    const QueryData &q = queries_[hs.qi];
-    const bool tiled = !tile_table_.empty();
-    const GhostmQueryTile *t = tiled ? &tile_table_[q.global_base + hs.query] : nullptr;
-    // the read's key: the source record, or the name group's end over all chunks
-    const uint64_t key = tiled ? t->record : (uint64_t)q.global_base + q.group_end[hs.query];
+    uint64_t key = 0;
+    in[h] = CullRecord(frame, h, hits[h], path[h], &key);
     if (h && key != prev) res.read_begin.push_back((uint32_t)h);
     prev = key;
-    const GhostmHitPath &x = path[h];
-    GhostmCullHit c{hits[h].db_id, x.score, 0, 0, x.s_start, x.s_end};
-    if (x.score) {
-      if (tiled && tile_dna_) {
-        const uint32_t g = t->frame % 3, strand = t->frame / 3, nt = tile_read_nt_[t->record];
-        const uint32_t p0 = frame ? x.q_start : 3 * x.q_start + g, p1 = frame ? x.q_end : 3 * x.q_end + g + 2;
-        const uint32_t a = ForwardNt(strand, nt, p0), b = ForwardNt(strand, nt, p1);
-        c.q_lo = std::min(a, b);
-        c.q_hi = std::max(a, b);
-      } else {
-        c.q_lo = x.q_start;
-        c.q_hi = x.q_end;
-      }
-    } else {
-      c.s_lo = c.s_hi = 0;  // an EMPTY hit: its ranges say nothing
-    }
-    in[h] = c;
   }
   res.read_begin.push_back((uint32_t)n);
   res.out.assign(n, GhostmCullOut{0, GHOSTM_CULL_EMPTY, 0xFFFFFFFFu, 0});
@@ -2309,6 +2323,175 @@ void Session::FormatCull(bool frame) {
       p = PutU32(p, res.out[h].detail); *p++ = '\n';
       out.append(num, (size_t)(p - num));
     }
+  }
+  bool placed = false;
+  for (size_t k = 0; k < used_parts_; ++k)
+    for (std::string &t : parts_[k].text) {
+      t.clear();
+      if (!placed) t.swap(out), placed = true;
+    }
+  joined_valid_ = false;
+}
+
+static std::string ReadTextFile(const std::string &path, const char *what) {
+  std::ifstream f(path.c_str(), std::ios::binary);
+  if (!f) throw Error(std::string("set taxonomy: cannot open the ") + what + " file " + path);
+  std::ostringstream ss;
+  ss << f.rdbuf();
+  return ss.str();
+}
+
+void Session::SetTaxonomy(uint32_t nnodes, const uint32_t *taxid, const uint32_t *parent, size_t nsubjects,
+                          const uint32_t *subject_node, uint64_t map_unmatched) {
+  if (!taxid || !parent) throw Error("set taxonomy: null: taxid or parent");
+  if (nsubjects && !subject_node) throw Error("set taxonomy: null: subject_node");
+  std::vector<uint32_t> depth;
+  const std::string why = TaxonomyDepths(nnodes, parent, &depth);
+  if (!why.empty()) throw Error("set taxonomy: " + why);
+  std::unordered_set<uint32_t> seen;
+  for (uint32_t i = 0; i < nnodes; ++i) {
+    if (taxid[i] == 0) throw Error("set taxonomy: taxonomy: node " + std::to_string(i) + ": taxid 0");
+    if (!seen.insert(taxid[i]).second)
+      throw Error("set taxonomy: taxonomy: node " + std::to_string(i) + ": taxid " + std::to_string(taxid[i]) + " repeated");
+  }
+  const size_t have = dbs_.empty() ? 0 : (size_t)dbs_.back().global_base + dbs_.back().chunk.nseq;
+  if (nsubjects != have)
+    throw Error("set taxonomy: subjects: " + std::to_string(nsubjects) + " given, the database has " + std::to_string(have));
+  uint64_t mapped = 0;
+  for (size_t k = 0; k < nsubjects; ++k) {
+    if (subject_node[k] != kLcaNone && subject_node[k] >= nnodes)
+      throw Error("set taxonomy: node: subject " + std::to_string(k) + ": no such node");
+    mapped += subject_node[k] != kLcaNone;
+  }
+  DeviceModule &dev = DeviceModule::Get();
+  dev.SetTaxonomy(nnodes, parent);
+  tax_.taxid.assign(taxid, taxid + nnodes);
+  tax_.parent.assign(parent, parent + nnodes);
+  tax_.subject_node.assign(subject_node, subject_node + nsubjects);
+  tax_.mapped = mapped;
+  tax_.map_unmatched = map_unmatched;
+  tax_.serial = dev.taxonomy_serial();
+  tax_.set = true;
+  lca_[0].Drop();
+  lca_[1].Drop();
+}
+
+void Session::SetTaxonomyFiles(const std::string &nodes_path, const std::string &map_path) {
+  TaxonomyFile nodes;
+  std::string why = ParseTaxonomyNodes(ReadTextFile(nodes_path, "nodes"), &nodes);
+  if (!why.empty()) throw Error("set taxonomy: " + why);
+  std::vector<std::pair<std::string, uint32_t>> lines;
+  std::vector<uint32_t> line_of;
+  why = ParseTaxonomyMap(ReadTextFile(map_path, "map"), &lines, &line_of);
+  if (!why.empty()) throw Error("set taxonomy: " + why);
+  std::unordered_map<uint32_t, uint32_t> node_of;
+  for (size_t i = 0; i < nodes.taxid.size(); ++i) node_of.emplace(nodes.taxid[i], (uint32_t)i);
+  std::unordered_map<std::string, uint32_t> name_node;  // a later line wins
+  for (size_t k = 0; k < lines.size(); ++k) {
+    const auto it = node_of.find(lines[k].second);
+    if (it == node_of.end())
+      throw Error("set taxonomy: map: line " + std::to_string(line_of[k]) + ": taxid " + std::to_string(lines[k].second) +
+                  " is not in the nodes file");
+    name_node[lines[k].first] = it->second;
+  }
+  std::vector<uint32_t> subject_node;
+  std::unordered_set<std::string> names;
+  for (const DbData &d : dbs_)
+    for (uint32_t s = 0; s < d.chunk.nseq; ++s) {
+      const std::string key = LcaNameKey(std::string(d.chunk.names[s]));
+      const auto it = name_node.find(key);
+      subject_node.push_back(it == name_node.end() ? kLcaNone : it->second);
+      names.insert(key);
+    }
+  uint64_t unmatched = 0;
+  for (const auto &l : lines) unmatched += names.count(l.first) == 0;
+  SetTaxonomy((uint32_t)std::min<size_t>(nodes.taxid.size(), UINT32_MAX), nodes.taxid.data(), nodes.parent.data(),
+              subject_node.size(), subject_node.data(), unmatched);
+}
+
+GhostmTaxonomyInfo Session::TaxonomyInfo() const {
+  GhostmTaxonomyInfo info{};
+  if (!tax_.set) return info;
+  info.nodes = tax_.taxid.size();
+  info.subjects_mapped = tax_.mapped;
+  info.subjects_unmapped = tax_.subject_node.size() - tax_.mapped;
+  info.map_unmatched = tax_.map_unmatched;
+  return info;
+}
+
+void Session::SetLca(uint32_t top_pct, uint32_t support_pct) {
+  if (top_pct > 100) throw Error("lca: param: top_pct " + std::to_string(top_pct) + " outside 0..100");
+  if (support_pct < 51 || support_pct > 100)
+    throw Error("lca: param: support_pct " + std::to_string(support_pct) + " outside 51..100");
+  if (top_pct == lca_top_pct_ && support_pct == lca_support_pct_) return;
+  lca_top_pct_ = top_pct;
+  lca_support_pct_ = support_pct;
+  lca_[0].Drop();
+  lca_[1].Drop();
+}
+
+// The taxon of every read (ReadLca): the cull's reads and records, a KEPT hit
+// a candidate with its read-level score, every other hit score 0.
+const Session::ReadLcaResult &Session::ReadLca(bool frame) {
+  if (!tax_.set) throw Error("read lca: taxonomy: none is set (GhostmSessionSetTaxonomy)");
+  ReadLcaResult &res = lca_[frame ? 1 : 0];
+  if (res.valid) return res;
+  const ReadCullResult &cull = ReadCull(frame);
+  const std::vector<GhostmHitPath> &path = frame ? HitsFrame() : HitsBand();
+  const std::vector<GhostmHit> &hits = Hits();
+  const size_t n = hits.size();
+  res.read_begin = cull.read_begin;
+  if (n == 0) res.read_begin.assign(1, 0);  // no hit, no read
+  // Only the KEPT hits go to the stage call: every other hit has score 0 there,
+  // is no candidate and changes no field of the record. begin: the reads in
+  // the compacted array.
+  std::vector<GhostmLcaHit> rec;
+  std::vector<uint32_t> begin(res.read_begin.size());
+  for (size_t r = 0; r + 1 < res.read_begin.size(); ++r) {
+    begin[r] = (uint32_t)rec.size();
+    for (uint32_t h = res.read_begin[r]; h < res.read_begin[r + 1]; ++h) {
+      if (cull.out[h].status != GHOSTM_CULL_KEPT) continue;
+      const GhostmCullHit c = CullRecord(frame, h, hits[h], path[h], nullptr);
+      rec.push_back(GhostmLcaHit{tax_.subject_node[hits[h].db_id], c.score, c.q_lo, c.q_hi});
+    }
+  }
+  begin.back() = (uint32_t)rec.size();
+  DeviceModule &dev = DeviceModule::Get();
+  if (dev.taxonomy_serial() != tax_.serial) {  // SetTaxonomyGpu, FreeGpu or another session since: ours again
+    dev.SetTaxonomy((uint32_t)tax_.parent.size(), tax_.parent.data());
+    tax_.serial = dev.taxonomy_serial();
+  }
+  const uint32_t nreads = (uint32_t)res.read_begin.size() - 1;
+  res.out.assign(nreads, GhostmLcaOut{});
+  const DeviceTimes before = dev.times();
+  dev.ReadLca(nreads, begin.data(), (uint32_t)rec.size(), rec.data(), lca_top_pct_, lca_support_pct_, res.out.data());
+  AddDeltas(lca_stats_, before, dev.times(), std::make_pair(&GhostmReadLcaStats::seconds_lca, &DeviceTimes::lca),
+            std::make_pair(&GhostmReadLcaStats::lca_launches, &DeviceTimes::lca_launches),
+            std::make_pair(&GhostmReadLcaStats::lca_votes, &DeviceTimes::lca_votes),
+            std::make_pair(&GhostmReadLcaStats::lca_assigned, &DeviceTimes::lca_assigned));
+  lca_stats_.lca_reads += nreads;  // the session's reads and hits, not the compacted call's
+  lca_stats_.lca_hits += n;
+  res.valid = true;
+  return res;
+}
+
+// -y 22 / -y 23: one line per read, named by its first hit's query record.
+void Session::FormatLca(bool frame) {
+  const ReadLcaResult &res = ReadLca(frame);
+  std::string out;
+  for (size_t r = 0; r + 1 < res.read_begin.size(); ++r) {
+    const HitSource &hs = hit_source_[res.read_begin[r]];
+    const GhostmLcaOut &o = res.out[r];
+    out.append(queries_[hs.qi].chunk.names[hs.query]);
+    const uint32_t cols[8] = {o.node == kLcaNone ? 0u : tax_.taxid[o.node], o.depth, o.votes, o.support,
+                              o.lca == kLcaNone ? 0u : tax_.taxid[o.lca], o.candidates, o.unmapped, o.best_score};
+    for (uint32_t c : cols) {
+      char num[16], *p = num;
+      *p++ = '\t';
+      p = PutU32(p, c);
+      out.append(num, (size_t)(p - num));
+    }
+    out.push_back('\n');
   }
   bool placed = false;
   for (size_t k = 0; k < used_parts_; ++k)
@@ -2783,6 +2966,7 @@ void Session::DropResults() {
   read_rows_[0].Drop();
   pileup_[kBandLevel].Drop();
   cull_[0].Drop();
+  lca_[0].Drop();
   DropFrameResults();
   pileup_subj_.clear();
   pileup_[kTileLevel].Drop();
@@ -2795,9 +2979,9 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  // -y 6 to -y 21 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup, HitsReadRows, ReadPileup,
-  // ReadCull), not while the search runs
-  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 21;
+  // -y 6 to -y 23 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup, HitsReadRows, ReadPileup,
+  // ReadCull, ReadLca), not while the search runs
+  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 23;
   if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
@@ -2830,6 +3014,7 @@ void Session::Run(bool stream_to_file) {
   read_rows_stats_ = GhostmReadRowsStats{};
   read_pileup_stats_ = GhostmReadPileupStats{};
   cull_stats_ = GhostmReadCullStats{};
+  lca_stats_ = GhostmReadLcaStats{};
   QueryStats();
   merge_epoch_ = 0;
   DropResults();
@@ -2869,7 +3054,9 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    if (opt_.output_style == 20 || opt_.output_style == 21) {
+    if (opt_.output_style == 22 || opt_.output_style == 23) {
+      FormatLca(opt_.output_style == 23);
+    } else if (opt_.output_style == 20 || opt_.output_style == 21) {
       if (opt_.output_style == 21) FormatFrameTabular();
       else FormatPathTabular(true);
       FormatCull(opt_.output_style == 21);
@@ -3395,6 +3582,7 @@ void Session::DropDb() {
   // the old chunks' device blocks go back to the pool
   for (DbData &d : dbs_) dev.Free(d.dev);
   dbs_.clear();
+  tax_ = Taxonomy();  // its subjects are gone
   db_sum_u32_ = 0;
   // the E-value text cache is keyed by (query length, score) and was priced
   // with the old database's residue sum

@@ -337,6 +337,30 @@ class Session {
   // refused on a shard session.
   void SetTileGroups(bool on);
   bool TileGroups() const { return tile_groups_; }
+  // A taxonomy for the resident database and the taxon of every read (the
+  // contract is above ReadLcaGpu in include/ghostm_hip.h; the session calls
+  // are described at GhostmSessionSetTaxonomy). SetTaxonomy checks everything,
+  // makes the words resident (DeviceModule::SetTaxonomy) and only then takes
+  // the arrays; DropDb forgets them.
+  void SetTaxonomy(uint32_t nnodes, const uint32_t *taxid, const uint32_t *parent, size_t nsubjects,
+                   const uint32_t *subject_node, uint64_t map_unmatched = 0);
+  void SetTaxonomyFiles(const std::string &nodes_path, const std::string &map_path);
+  GhostmTaxonomyInfo TaxonomyInfo() const;
+  // top_pct 0..100 (default 10), support_pct 51..100 (default 100); a change drops the kept results
+  void SetLca(uint32_t top_pct, uint32_t support_pct);
+  // One record per read of ReadCull(frame), from its records: a KEPT hit votes
+  // with its read-level score and the cull's stretch, node =
+  // subject_node[db_id]. One DeviceModule::ReadLca call over the KEPT hits
+  // alone (a hit of score 0 is no candidate and changes nothing). Computed on first use;
+  // kept as long as the cull's result, the parameters and the taxonomy.
+  struct ReadLcaResult {
+    std::vector<GhostmLcaOut> out;
+    std::vector<uint32_t> read_begin;
+    bool valid = false;
+    void Drop() { *this = ReadLcaResult(); }
+  };
+  const ReadLcaResult &ReadLca(bool frame);
+  const GhostmReadLcaStats &ReadLcaStats() const { return lca_stats_; }
   // Hit records of the last run in device memory (this session's GPU): copies
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
@@ -516,6 +540,13 @@ class Session {
   // parts, so the text is assembled over the joined lines and replaces the
   // parts' text as FormatPileup's does
   void FormatCull(bool frame);
+  // the cull's input record of final hit h from its read-level path x, and (key not null) the key of its read:
+  // consecutive hits with one key are one read (ReadCull; ReadLca for the kept hits)
+  GhostmCullHit CullRecord(bool frame, size_t h, const GhostmHit &hit, const GhostmHitPath &x, uint64_t *key) const;
+  // -y 22 (frame false) and -y 23 (frame true): one line per read with hits, in
+  // read order: qname, taxid, depth, votes, support, lca_taxid, candidates,
+  // unmapped, best_score; replaces the parts' text as FormatPileup's does
+  void FormatLca(bool frame);
   uint32_t SubjectLength(const DbData &d, uint32_t subject) const;
 
   AlignerOptions opt_;
@@ -591,6 +622,16 @@ class Session {
   uint32_t cull_top_k_ = 1, cull_cover_pct_ = 50;
   GhostmReadCullStats cull_stats_{};
   bool tile_groups_ = false;
+  struct Taxonomy {
+    std::vector<uint32_t> taxid, parent, subject_node;
+    uint64_t mapped = 0, map_unmatched = 0;
+    uint64_t serial = 0;  // DeviceModule::taxonomy_serial() after this taxonomy's upload
+    bool set = false;
+  };
+  Taxonomy tax_;
+  ReadLcaResult lca_[2];  // of the band paths [0] and of the frame paths [1]
+  uint32_t lca_top_pct_ = 10, lca_support_pct_ = 100;
+  GhostmReadLcaStats lca_stats_{};
   bool records_on_device_ = false;
   GhostmStats stats_{};
   unsigned threads_ = 1;

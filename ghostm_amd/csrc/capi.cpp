@@ -580,6 +580,83 @@ size_t GhostmSessionReadCullStats(void *s, GhostmReadCullStats *stats, size_t si
   return sizeof(GhostmReadCullStats);
 }
 
+int GhostmSessionSetTaxonomy(void *s, uint32_t nnodes, const uint32_t taxid[], const uint32_t parent[],
+                             size_t nsubjects, const uint32_t subject_node[]) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetTaxonomy(nnodes, taxid, parent, nsubjects, subject_node);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+int GhostmSessionSetTaxonomyFiles(void *s, const char *nodes_path, const char *map_path) {
+  try {
+    if (!s) throw Error("null session");
+    if (!nodes_path || !map_path) throw Error("set taxonomy: null: a path");
+    static_cast<Session *>(s)->SetTaxonomyFiles(nodes_path, map_path);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionTaxonomyInfo(void *s, GhostmTaxonomyInfo *info, size_t size) {
+  if (!s || !info) return 0;
+  const GhostmTaxonomyInfo t = static_cast<Session *>(s)->TaxonomyInfo();
+  std::memcpy(info, &t, std::min(size, sizeof(GhostmTaxonomyInfo)));
+  return sizeof(GhostmTaxonomyInfo);
+}
+
+int GhostmSessionSetLca(void *s, uint32_t top_pct, uint32_t support_pct) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetLca(top_pct, support_pct);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionReadLca(void *s, int frame, GhostmLcaOut *out, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmLcaOut> &r = static_cast<Session *>(s)->ReadLca(frame != 0).out;
+    if (!out) return r.size();
+    const size_t n = std::min(cap, r.size());
+    if (n) std::memcpy(out, r.data(), n * sizeof(GhostmLcaOut));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionReadLcaBegin(void *s, int frame, uint32_t *read_begin, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<uint32_t> &r = static_cast<Session *>(s)->ReadLca(frame != 0).read_begin;
+    if (!read_begin) return r.size();
+    const size_t n = std::min(cap, r.size());
+    if (n) std::memcpy(read_begin, r.data(), n * sizeof(uint32_t));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionReadLcaStats(void *s, GhostmReadLcaStats *stats, size_t size) {
+  if (!s || !stats) return 0;
+  const GhostmReadLcaStats st = static_cast<Session *>(s)->ReadLcaStats();
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadLcaStats)));
+  return sizeof(GhostmReadLcaStats);
+}
+
 size_t GhostmSessionDeviceHits(void *s, void *dst_device, size_t cap) {
   try {
     if (!s) throw Error("null session");
@@ -607,6 +684,8 @@ void GhostmSessionDestroy(void *s) { delete static_cast<Session *>(s); }
 int GhostmAlignMain(int argc, char **argv) {
   try {
     AlignerOptions opt = ParseAlignerOptions(argc, argv);
+    if (opt.output_style == 22 || opt.output_style == 23)
+      throw Error("-y 22 and -y 23 need a taxonomy: use `ghostm search` with -n nodes.tsv -a map.tsv");
     { std::ofstream touch(opt.output_file.c_str()); }
     Session session(opt);
     session.Run(true);       // the output file is written while the search runs
@@ -636,12 +715,26 @@ int GhostmSearchMain(int argc, char **argv) {
   long shift_cost = -1;                    // -F; below 0: the session's default
   long cull_k = -1, cull_pct = -1;         // -K, -C; below 0: the session's defaults
   bool tile_groups = false;                // -g
+  std::string tax_nodes, tax_map;          // -n, -a
+  long lca_top = -1, lca_support = -1;     // -p, -P; below 0: the session's defaults
+  int style = 0;                           // -y, as aln reads it
   optind = 1;
   opterr = 1;
   int c;
-  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B, -F, -g, -K, -C
-  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:")) >= 0) {
+  // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B, -F, -g, -K, -C, -n, -a,
+  // -p, -P
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:n:a:p:P:")) >= 0) {
     switch (c) {
+      case 'n': tax_nodes = optarg; break;  // the taxonomy's nodes file
+      case 'a': tax_map = optarg; break;    // and the subjects' taxids
+      case 'p':    // the assignment's top_pct, 0..100
+      case 'P': {  // and support_pct, 51..100
+        char *end = nullptr;
+        const long v = strtol(optarg, &end, 10);
+        if (end == optarg || *end || v < (c == 'p' ? 0 : 51) || v > 100) return 1;
+        (c == 'p' ? lca_top : lca_support) = v;
+        break;
+      }
       case 'g': tile_groups = true; break;  // with -T: -b per tile, not per read
       case 'K':    // the cull's top_k, 1..255
       case 'C': {  // the cull's cover_pct, 1..100
@@ -691,6 +784,7 @@ int GhostmSearchMain(int argc, char **argv) {
       case 'v': aln_argv.push_back(const_cast<char *>("-v")); break;
       default: {
         if (c == 'd') have_d = true;
+        if (c == 'y') style = atoi(optarg);
         static const char *const kFlags[] = {"-b", "-d", "-D", "-e", "-E", "-G", "-l", "-M", "-r", "-s", "-t", "-y"};
         for (const char *f : kFlags)
           if (f[1] == c) aln_argv.push_back(const_cast<char *>(f));
@@ -703,6 +797,8 @@ int GhostmSearchMain(int argc, char **argv) {
   if (have_d == !db_fasta.empty()) return 1;  // -d or -f, not both
   if (have_x && !tiled) return 1;             // -X cuts a tiled set only
   if (tile_groups && !tiled) return 1;        // -g groups a tiled set only
+  if (tax_nodes.empty() != tax_map.empty()) return 1;                // -n and -a come together
+  if ((style == 22 || style == 23) && tax_nodes.empty()) return 1;  // the taxon lines need them
   try {
     aln_argv.push_back(nullptr);
     AlignerOptions opt = ParseAlignerOptions((int)aln_argv.size() - 1, aln_argv.data());
@@ -713,6 +809,9 @@ int GhostmSearchMain(int argc, char **argv) {
     if (shift_cost >= 0) session.SetFrameShift(-(int)shift_cost);
     if (cull_k >= 0 || cull_pct >= 0) session.SetCull(cull_k >= 0 ? (uint32_t)cull_k : 1u, cull_pct >= 0 ? (uint32_t)cull_pct : 50u);
     if (tile_groups) session.SetTileGroups(true);
+    if (!tax_nodes.empty()) session.SetTaxonomyFiles(tax_nodes, tax_map);  // after the database
+    if (lca_top >= 0 || lca_support >= 0)
+      session.SetLca(lca_top >= 0 ? (uint32_t)lca_top : 10u, lca_support >= 0 ? (uint32_t)lca_support : 100u);
     for (size_t k = 0; k < pos.size(); k += 2) {
       try {
         { std::ofstream touch(pos[k + 1].c_str()); }

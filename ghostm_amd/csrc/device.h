@@ -120,6 +120,9 @@ struct DeviceTimes {
   double cull = 0;                                // the read-level cull (k_read_cull): seconds, batches,
   uint64_t cull_launches = 0, cull_reads = 0, cull_hits = 0;  // reads with a hit, hits,
   uint64_t cull_kept = 0, cull_dups = 0, cull_culled = 0;     // and the hits by status
+  double lca = 0;                                  // the taxon per read (k_read_lca*): seconds, batches,
+  uint64_t lca_launches = 0, lca_reads = 0, lca_hits = 0;  // reads with a hit, their hits,
+  uint64_t lca_votes = 0, lca_assigned = 0;                // votes, reads with a node
 };
 
 class DeviceModule {
@@ -365,6 +368,23 @@ class DeviceModule {
   void ReadCull(uint32_t nreads, const uint32_t *read_begin, uint32_t nhits, const GhostmCullHit *hit, uint32_t top_k,
                 uint32_t cover_pct, GhostmCullOut *out);
 
+  // The taxonomy of ReadLca (the contract is above ReadLcaGpu in
+  // include/ghostm_hip.h): checked (TaxonomyDepths, read_lca.h; throws with the
+  // reason, the resident one stays), packed and uploaded. Resident until the
+  // next SetTaxonomy or DropTaxonomy. taxonomy_serial() changes with both, so
+  // a session can tell whether the resident words are still its own.
+  void SetTaxonomy(uint32_t nnodes, const uint32_t *parent);
+  void DropTaxonomy();
+  uint32_t taxonomy_nodes() const { return tax_nodes_; }
+  uint64_t taxonomy_serial() const { return tax_serial_; }
+  // The taxon of nreads reads (kern::k_read_lca_wave, kern::k_read_lca): read
+  // r's hits are hit[read_begin[r], read_begin[r + 1]), out[r] its record.
+  // Everything is checked first (ValidateReadLca, read_lca.h; throws with the
+  // reason before any upload or launch, out untouched). Needs no resident
+  // chunk. Adds to times().lca*.
+  void ReadLca(uint32_t nreads, const uint32_t *read_begin, uint32_t nhits, const GhostmLcaHit *hit, uint32_t top_pct,
+               uint32_t support_pct, GhostmLcaOut *out);
+
   // The read-level banded alignment of n hits (kern::k_band_fill, k_band_walk,
   // k_band_compact; the contract is in include/ghostm_hip.h): hit i aligns
   // source src[i] of chunk q (W = q's record width, tile step `step`) to
@@ -422,6 +442,8 @@ class DeviceModule {
                 const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B, int open, int ext,
                 GhostmHitPath *rec, std::vector<uint32_t> *ops);
   int device_ = -1;
+  uint32_t tax_nodes_ = 0;   // the resident taxonomy's nodes; 0: none
+  uint64_t tax_serial_ = 0;  // counts SetTaxonomy and DropTaxonomy
   void *stream_ = nullptr;
   HostCopyFn host_copy_;
   HostParallelFn host_par_;

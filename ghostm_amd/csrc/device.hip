@@ -24,6 +24,7 @@
 #include "path_rows.h"
 #include "read_rows.h"
 #include "read_cull.h"
+#include "read_lca.h"
 #include "read_pileup.h"
 #include "pileup_plan.h"
 #include "qformat.h"
@@ -294,6 +295,9 @@ struct DeviceModule::Impl {
   DevBuf pileup_hit, pileup_ops, pileup_list, pileup_part, pileup_prof, pileup_out, pileup_cols;
   // ReadCull: a batch's hits, its read table with the class lists and table offsets, its tables, its records
   DevBuf cull_hit, cull_meta, cull_scratch, cull_out;
+  // ReadLca: the taxonomy's words; a batch's hits, its read table with the class lists, counts and table offsets, its
+  // tables, its records
+  DevBuf lca_tax, lca_hit, lca_meta, lca_scratch, lca_out;
   // BandAlign: a batch's slots, its offsets / maxima / records, its direction bytes, its word slots, their packed words
   DevBuf band_hit, band_meta, band_dir, band_ops, band_cmp;
   // FrameAlign: the same five of its own
@@ -3178,12 +3182,150 @@ void DeviceModule::ReadCull(uint32_t nreads, const uint32_t *read_begin, uint32_
   }
 }
 
+static_assert(sizeof(kern::LcaHit) == sizeof(GhostmLcaHit) && sizeof(GhostmLcaHit) == 16,
+              "GhostmLcaHit is uploaded as it is");
+static_assert(sizeof(GhostmLcaOut) == 32, "k_read_lca writes 8 words per read");
+static_assert(kern::kLcaArrays == kLcaTableArrays && kern::kLcaWave == kLcaWave && kern::kLcaCap == kLcaCap &&
+                  kern::kLcaLimit == kLcaReadLimit,
+              "read_lca.h sizes the tables and the classes");
+
+void DeviceModule::SetTaxonomy(uint32_t nnodes, const uint32_t *parent) {
+  if (!impl_) throw Error("taxonomy: the device module is not bound to a device");
+  Use();
+  std::vector<uint32_t> depth;
+  const std::string why = TaxonomyDepths(nnodes, parent, &depth);
+  if (!why.empty()) throw Error(why);
+  const std::vector<uint32_t> words = TaxonomyWords(nnodes, parent, depth);
+  Impl &I = *impl_;
+  hipStream_t st = S(stream_);
+  I.lca_tax.Reserve((size_t)nnodes * 4);
+  HIP_CHECK(hipMemcpyAsync(I.lca_tax.p, words.data(), (size_t)nnodes * 4, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  tax_nodes_ = nnodes;
+  ++tax_serial_;
+}
+
+void DeviceModule::DropTaxonomy() {
+  if (impl_ && tax_nodes_) impl_->lca_tax.Release();
+  tax_nodes_ = 0;
+  ++tax_serial_;
+}
+
+// The taxon of nreads reads (kern::k_read_lca_wave, kern::k_read_lca; the
+// contract is above ReadLcaGpu in include/ghostm_hip.h). The reads go in
+// batches cut by their bytes (hits, the record and, for a read above kLcaCap
+// candidates, its table); a batch's reads with a candidate are listed by size
+// class and every class with a read is one launch. A read without a candidate
+// gets its record here.
+void DeviceModule::ReadLca(uint32_t nreads, const uint32_t *read_begin, uint32_t nhits, const GhostmLcaHit *hit,
+                           uint32_t top_pct, uint32_t support_pct, GhostmLcaOut *out) {
+  if (!impl_) throw Error("read lca: the device module is not bound to a device");
+  Use();
+  Impl &I = *impl_;
+  std::vector<uint32_t> ncand;
+  std::string why = ValidateReadLca(tax_nodes_, nreads, read_begin, nhits, hit, top_pct, support_pct, &ncand);
+  if (why.empty() && !out && nreads) why = "null: out";
+  if (!why.empty()) throw Error("read lca: " + why);
+  const size_t budget = EnvSize("GHOSTM_LCA_SCRATCH_MB", 1024) << 20;
+  const size_t max_reads = EnvSize("GHOSTM_LCA_BATCH_READS", SIZE_MAX);
+  const auto hits_of = [&](uint32_t r) { return read_begin[r + 1] - read_begin[r]; };
+  const auto table_words = [&](uint32_t r) {
+    return ncand[r] > kLcaCap ? (size_t)kLcaTableArrays * LcaPow2(ncand[r]) : (size_t)0;
+  };
+  std::vector<uint32_t> meta;  // read_begin[m + 1], per class the list and its counts, then (8-byte aligned) the offsets
+  std::vector<unsigned long long> offs;
+  std::vector<GhostmLcaOut> got;  // a batch's records as read back
+  for (uint32_t b0 = 0; b0 < nreads;) {
+    size_t bytes = 0;
+    const uint32_t b1 = CutBatch(b0, nreads, max_reads, budget,
+                                 [&](uint32_t r) { return (size_t)hits_of(r) * 16 + table_words(r) * 4 + 48; }, &bytes);
+    const uint32_t m = b1 - b0, r0 = b0, h0 = read_begin[b0], nh = read_begin[b1] - h0;
+    b0 = b1;
+    // the lists by class: wave, LDS, device memory
+    std::vector<uint32_t> list[3];
+    offs.clear();
+    size_t words = 0;
+    for (uint32_t r = 0; r < m; ++r) {
+      const uint32_t c = ncand[r0 + r];
+      times_.lca_reads += hits_of(r0 + r) != 0;
+      if (c == 0) {
+        out[r0 + r] = LcaNoVote(0, 0, 0);
+        continue;
+      }
+      list[c <= kLcaWave ? 0 : c <= kLcaCap ? 1 : 2].push_back(r);
+      if (c > kLcaCap) {
+        offs.push_back(words);
+        words += table_words(r0 + r);
+      }
+    }
+    times_.lca_hits += nh;
+    if (list[0].empty() && list[1].empty() && list[2].empty()) continue;
+    meta.assign(read_begin + r0, read_begin + b1 + 1);
+    size_t list_at[3];
+    for (int c = 0; c < 3; ++c) {
+      list_at[c] = meta.size();
+      meta.insert(meta.end(), list[c].begin(), list[c].end());
+      for (uint32_t r : list[c]) meta.push_back(ncand[r0 + r]);
+    }
+    if (meta.size() & 1) meta.push_back(0);
+    const size_t offs_at = meta.size();
+    meta.resize(offs_at + 2 * offs.size());
+    if (!offs.empty()) memcpy(meta.data() + offs_at, offs.data(), offs.size() * 8);
+    I.lca_hit.Reserve((size_t)nh * sizeof(GhostmLcaHit));
+    I.lca_meta.Reserve(meta.size() * 4);
+    I.lca_out.Reserve((size_t)m * sizeof(GhostmLcaOut));
+    if (words) I.lca_scratch.Reserve(words * 4);
+    hipStream_t st = S(stream_);
+    HIP_CHECK(hipMemcpyAsync(I.lca_hit.p, hit + h0, (size_t)nh * sizeof(GhostmLcaHit), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(I.lca_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, st));
+    kern::LcaArgs a{};
+    a.hit = I.lca_hit.as<kern::LcaHit>();
+    a.hit_base = h0;
+    a.read_begin = I.lca_meta.as<uint32_t>();
+    a.tax = I.lca_tax.as<uint32_t>();
+    a.nnodes = tax_nodes_;
+    a.top_pct = top_pct;
+    a.support_pct = support_pct;
+    a.scratch = I.lca_scratch.as<uint32_t>();
+    a.scratch_off = reinterpret_cast<const unsigned long long *>(I.lca_meta.as<uint32_t>() + offs_at);
+    a.out = I.lca_out.as<uint32_t>();
+    TimedLaunch(I.ev0, I.ev1, st, [&] {
+      for (int c = 0; c < 3; ++c) {
+        if (list[c].empty()) continue;
+        a.list = I.lca_meta.as<uint32_t>() + list_at[c];
+        a.nlist = (uint32_t)list[c].size();
+        a.ncand = a.list + a.nlist;
+        if (c == 0) {
+          const uint32_t per = kern::kLcaWaveBlock / 64;
+          hipLaunchKernelGGL(kern::k_read_lca_wave, dim3((a.nlist + per - 1) / per), dim3(kern::kLcaWaveBlock), 0, st, a);
+        } else if (c == 1) {
+          hipLaunchKernelGGL(kern::k_read_lca<false>, dim3(a.nlist), dim3(kern::kLcaBlock), 0, st, a);
+        } else {
+          hipLaunchKernelGGL(kern::k_read_lca<true>, dim3(a.nlist), dim3(kern::kLcaBlock), 0, st, a);
+        }
+        HIP_CHECK(hipGetLastError());
+      }
+    });
+    got.resize(m);
+    HIP_CHECK(hipMemcpyAsync(got.data(), a.out, (size_t)m * sizeof(GhostmLcaOut), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    times_.lca += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+    times_.lca_launches += 1;
+    for (int c = 0; c < 3; ++c)
+      for (uint32_t r : list[c]) {
+        out[r0 + r] = got[r];
+        times_.lca_votes += got[r].votes;
+        times_.lca_assigned += got[r].node != kLcaNone;
+      }
+  }
+}
+
 const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_amd/srchash.py)
 
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_read_pileup/k_pileup_finish/k_read_cull/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_read_pileup/k_pileup_finish/k_read_cull/k_read_lca_wave/k_read_lca/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -3469,6 +3611,7 @@ int FreeGpu(void) {
     r.query = nullptr;
     r.db = nullptr;
     r.seeded = false;
+    m.DropTaxonomy();  // SetTaxonomyGpu's
     return 0;
   } catch (std::exception &e) {
     SetError(e.what());
@@ -3803,6 +3946,45 @@ size_t GhostmStageReadCullStats(GhostmReadCullStats *stats, size_t size) {
                                dt.cull_kept, dt.cull_dups,     dt.cull_culled};
   std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadCullStats)));
   return sizeof(GhostmReadCullStats);
+}
+
+int SetTaxonomyGpu(uint32_t nnodes, const uint32_t parent[]) {
+  try {
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    DeviceModule &m = DeviceModule::Get();
+    if (m.device() < 0) m.Bind(0);  // no SetOptionGpu yet: the first device
+    m.SetTaxonomy(nnodes, parent);
+    return 0;
+  } catch (std::exception &e) {
+    SetError(std::string("SetTaxonomyGpu: ") + e.what());
+    return 1;
+  }
+}
+
+int ReadLcaGpu(uint32_t nreads, const uint32_t read_begin[], uint32_t nhits, const GhostmLcaHit hit[],
+               uint32_t top_pct, uint32_t support_pct, GhostmLcaOut out[]) {
+  try {
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    DeviceModule &m = DeviceModule::Get();
+    if (m.device() < 0) m.Bind(0);  // no SetOptionGpu yet: the first device
+    m.ReadLca(nreads, read_begin, nhits, hit, top_pct, support_pct, out);
+    return 0;
+  } catch (std::exception &e) {
+    SetError(std::string("ReadLcaGpu: ") + e.what());
+    return 1;
+  }
+}
+
+size_t GhostmStageReadLcaStats(GhostmReadLcaStats *stats, size_t size) {
+  if (!stats) return 0;
+  RefState &r = Ref();
+  std::lock_guard<std::mutex> lk(r.mu);
+  const DeviceTimes &dt = DeviceModule::Get().times();
+  const GhostmReadLcaStats st{dt.lca, dt.lca_launches, dt.lca_reads, dt.lca_hits, dt.lca_votes, dt.lca_assigned};
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadLcaStats)));
+  return sizeof(GhostmReadLcaStats);
 }
 
 }  // extern "C"

@@ -5717,5 +5717,262 @@ template <uint32_t P, bool WAVE, bool GLOBAL> __global__ __launch_bounds__(kCull
   CullRead<WAVE>(a, a.list[k], T, hdrs[team], WAVE ? threadIdx.x & 63 : threadIdx.x, WAVE ? 64 : kCullBlock);
 }
 
+// ------------------------------------------------- taxon per read (LCA)
+// k_read_lca_wave and k_read_lca<GLOBAL>: the assignment of one read by one
+// team (the contract is above ReadLcaGpu in include/ghostm_hip.h; read_lca.h has
+// the same phases on the host). The class is the read's candidate count nc (its
+// hits with a score), which the host counted and passes in a.ncand: a wave for
+// nc <= 64 (kLcaWaveBlock / 64 reads per workgroup), a workgroup of kLcaBlock
+// lanes with the tables in LDS for nc <= kLcaCap, or in the read's slice of
+// a.scratch above (GLOBAL).
+//   compact    the candidates, in any order: the record does not depend on it
+//   score test candidate i against every j: ref = the largest score whose
+//              stretch shares a position with i's. Wave: lane i holds candidate
+//              i and reads lane j's three values. Workgroup: the tables.
+//   climb      every vote holds cur (its node, then an ancestor) and that
+//              node's depth. Levels run from the read's largest depth down;
+//              at a level the votes there count the votes with an equal cur
+//              (equal nodes have equal depths, so every vote under cur has
+//              arrived). Wave: one ballot per distinct cur. Workgroup: a table
+//              of 2 P slots keyed by cur, linear probing. The first level
+//              where a count reaches thr gives node, the first where one
+//              reaches V gives lca and ends the climb; otherwise the level's
+//              votes step to their parents (one gather of depth << 24 | parent).
+// Every loop ends at a bound the host validated or a constant: nc, the table
+// size, 255 levels (the depth is 8 bits of a word). What LDS or a gather holds
+// can shorten a loop, never lengthen it. Node indices are clamped below nnodes
+// before they index a.tax.
+//
+// Table of a read, words: score[P], q_lo[P], q_hi[P], cur[P], depth[P], slot[P],
+// key[2P], count[2P]: 10 P words, P = kLcaCap in LDS (40 KB).
+struct LcaHit {
+  uint32_t node, score, q_lo, q_hi;
+};
+
+struct LcaArgs {
+  const LcaHit *hit;           // the batch's hits
+  uint32_t hit_base;           // hit[0]'s index in the call
+  const uint32_t *read_begin;  // the batch's reads, one more entry than reads
+  const uint32_t *list;        // this launch's reads: indices into read_begin,
+  const uint32_t *ncand;       // and their candidate counts
+  uint32_t nlist;
+  const uint32_t *tax;  // depth << 24 | parent, nnodes words
+  uint32_t nnodes;
+  uint32_t top_pct, support_pct;
+  uint32_t *scratch;                      // GLOBAL: the tables,
+  const unsigned long long *scratch_off;  // list entry k's first word
+  uint32_t *out;                          // 8 words per read of the batch
+};
+
+constexpr uint32_t kLcaWaveBlock = 256, kLcaBlock = 1024;
+constexpr uint32_t kLcaArrays = 10;
+constexpr uint32_t kLcaWave = 64, kLcaCap = 1024, kLcaLimit = 16384;  // the classes' largest reads; the largest read
+constexpr uint32_t kLcaNone = 0xFFFFFFFFu;
+
+__device__ __forceinline__ void LcaStore(const LcaArgs &a, uint32_t rd, uint32_t node, uint32_t depth, uint32_t votes,
+                                         uint32_t support, uint32_t lca, uint32_t cand, uint32_t unmapped,
+                                         uint32_t best) {
+  uint4 *o = reinterpret_cast<uint4 *>(a.out) + 2 * (size_t)rd;
+  o[0] = make_uint4(node, depth, votes, support);
+  o[1] = make_uint4(lca, cand, unmapped, best);
+}
+
+__device__ __forceinline__ uint32_t LcaWaveMax(uint32_t v) {
+  for (int s = 32; s > 0; s >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, s));
+  return v;
+}
+
+__global__ __launch_bounds__(kLcaWaveBlock) void k_read_lca_wave(LcaArgs a) {
+  GHOSTM_POISON_LDS();
+  __shared__ uint32_t stage[kLcaWaveBlock / 64][4][64];
+  const uint32_t team = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t k = blockIdx.x * (kLcaWaveBlock / 64) + team;
+  if (k >= a.nlist) return;  // the whole wave
+  const uint32_t rd = a.list[k], nc = min(a.ncand[k], kLcaWave);
+  const uint32_t b = a.read_begin[rd], n = a.read_begin[rd + 1] - b;
+  const LcaHit *hit = a.hit + (b - a.hit_base);
+  // compact: a ballot per 64 hits
+  uint32_t at = 0;
+  for (uint32_t i0 = 0; i0 < n; i0 += 64) {
+    const uint32_t i = i0 + lane;
+    LcaHit h{};
+    if (i < n) h = hit[i];
+    const bool c = h.score != 0;
+    const unsigned long long bal = __ballot(c);
+    const uint32_t pos = at + (uint32_t)__popcll(bal & ((1ull << lane) - 1));
+    if (c && pos < nc) {
+      stage[team][0][pos] = h.node;
+      stage[team][1][pos] = h.score;
+      stage[team][2][pos] = h.q_lo;
+      stage[team][3][pos] = h.q_hi;
+    }
+    at += (uint32_t)__popcll(bal);
+  }
+  WaveSync();
+  const bool has = lane < nc;
+  uint32_t node = has ? stage[team][0][lane] : kLcaNone;
+  const uint32_t score = has ? stage[team][1][lane] : 0u;
+  const uint32_t lo = has ? stage[team][2][lane] : 1u, hi = has ? stage[team][3][lane] : 0u;
+  if (node != kLcaNone && node >= a.nnodes) node = kLcaNone;
+  // the score test: lane j's values, one after the other
+  uint32_t ref = 0;
+  for (uint32_t j = 0; j < nc; ++j) {
+    const uint32_t sj = (uint32_t)__shfl((int)score, (int)j), lj = (uint32_t)__shfl((int)lo, (int)j),
+                   hj = (uint32_t)__shfl((int)hi, (int)j);
+    if (lj <= hi && lo <= hj) ref = max(ref, sj);
+  }
+  const bool pass = has && score * 100u >= (100u - a.top_pct) * ref;
+  const bool vote = pass && node != kLcaNone;
+  const uint32_t V = (uint32_t)__popcll(__ballot(vote)), unmapped = (uint32_t)__popcll(__ballot(pass && !vote));
+  const uint32_t best = LcaWaveMax(score);
+  if (V == 0) {
+    if (lane == 0) LcaStore(a, rd, kLcaNone, 0, 0, 0, kLcaNone, nc, unmapped, best);
+    return;
+  }
+  uint32_t cur = vote ? node : 0u, d = vote ? a.tax[node] >> 24 : 0u;
+  const uint32_t maxd = LcaWaveMax(d), thr = (a.support_pct * V + 99u) / 100u;
+  uint32_t r_node = kLcaNone, r_depth = 0, r_support = 0, r_lca = kLcaNone;
+  for (uint32_t level = maxd;; --level) {  // at most 256 levels: d is 8 bits of a word
+    const bool here = vote && d == level;
+    unsigned long long rem = __ballot(here);
+    for (uint32_t it = 0; it < nc && rem; ++it) {  // one distinct cur per turn
+      const uint32_t v = (uint32_t)__shfl((int)cur, __ffsll((long long)rem) - 1);
+      const unsigned long long m = __ballot(here && cur == v);
+      const uint32_t c = (uint32_t)__popcll(m);
+      if (r_node == kLcaNone && c >= thr) {
+        r_node = v;
+        r_depth = level;
+        r_support = c;
+      }
+      if (c == V) r_lca = v;
+      rem &= ~m & (rem - 1);  // the lanes counted leave, the first one in any case
+    }
+    if (r_lca != kLcaNone || level == 0) break;
+    if (here) {
+      cur = min(a.tax[cur] & 0xFFFFFFu, a.nnodes - 1);
+      d = level - 1;
+    }
+  }
+  if (lane == 0) LcaStore(a, rd, r_node, r_depth, V, r_support, r_lca, nc, unmapped, best);
+}
+
+template <bool GLOBAL> __global__ __launch_bounds__(kLcaBlock) void k_read_lca(LcaArgs a) {
+  GHOSTM_POISON_LDS();
+  __shared__ __attribute__((aligned(16))) uint32_t tab[GLOBAL ? 2 : kLcaArrays * kLcaCap];
+  __shared__ uint32_t hdr[9];  // slots taken, V, unmapped, best, the largest depth; node, support, depth, lca
+  const uint32_t tid = threadIdx.x, nt = kLcaBlock, k = blockIdx.x;
+  if (k >= a.nlist) return;  // the whole workgroup
+  const uint32_t rd = a.list[k], nc = min(a.ncand[k], GLOBAL ? kLcaLimit : kLcaCap);
+  uint32_t P = kLcaCap;
+  if (GLOBAL) {
+    P = 2;
+    while (P < nc) P <<= 1;  // nc <= kLcaLimit
+  }
+  const uint32_t H = 2 * P, shift = (uint32_t)__clz((int)H) + 1;  // a product's top log2(H) bits
+  uint32_t *T = GLOBAL ? a.scratch + a.scratch_off[k] : tab;
+  uint32_t *sc = T, *qlo = T + P, *qhi = T + 2 * P, *cur = T + 3 * P, *dep = T + 4 * P, *slot = T + 5 * P;
+  uint32_t *key = T + 6 * P, *cnt = T + 8 * P;
+  const uint32_t b = a.read_begin[rd], n = a.read_begin[rd + 1] - b;
+  const LcaHit *hit = a.hit + (b - a.hit_base);
+  // the votes of a level count themselves into key and cnt with atomicCAS and
+  // atomicAdd; everything else on the table is plain loads and stores between
+  // barriers, which one workgroup's waves see as they see LDS
+  if (tid == 0) {
+    hdr[0] = hdr[1] = hdr[2] = hdr[3] = hdr[4] = 0;
+    hdr[5] = hdr[8] = kLcaNone;
+    hdr[6] = hdr[7] = 0;
+  }
+  for (uint32_t j = tid; j < H; j += nt) {
+    key[j] = kLcaNone;
+    cnt[j] = 0;
+  }
+  __syncthreads();
+  // compact
+  for (uint32_t i = tid; i < n; i += nt) {
+    const LcaHit h = hit[i];
+    if (h.score == 0) continue;
+    const uint32_t pos = atomicAdd(&hdr[0], 1u);
+    if (pos < nc) {
+      sc[pos] = h.score;
+      qlo[pos] = h.q_lo;
+      qhi[pos] = h.q_hi;
+      cur[pos] = h.node != kLcaNone && h.node >= a.nnodes ? kLcaNone : h.node;
+    }
+  }
+  __syncthreads();
+  // the score test; a vote keeps cur and gets its depth, every other candidate loses cur
+  for (uint32_t i = tid; i < nc; i += nt) {
+    const uint32_t s = sc[i], l = qlo[i], h = qhi[i], node = cur[i];
+    uint32_t ref = 0;
+    for (uint32_t j = 0; j < nc; ++j)
+      if (qlo[j] <= h && l <= qhi[j]) ref = max(ref, sc[j]);
+    atomicMax(&hdr[3], s);
+    const bool pass = s * 100u >= (100u - a.top_pct) * ref;
+    uint32_t d = 0;
+    if (pass && node != kLcaNone) {
+      d = a.tax[node] >> 24;
+      atomicAdd(&hdr[1], 1u);
+      atomicMax(&hdr[4], d);
+    } else {
+      if (pass) atomicAdd(&hdr[2], 1u);
+      cur[i] = kLcaNone;
+    }
+    dep[i] = d;
+  }
+  __syncthreads();
+  const uint32_t V = hdr[1], unmapped = hdr[2], best = hdr[3];
+  if (V == 0) {  // the whole workgroup
+    if (tid == 0) LcaStore(a, rd, kLcaNone, 0, 0, 0, kLcaNone, nc, unmapped, best);
+    return;
+  }
+  const uint32_t thr = (a.support_pct * V + 99u) / 100u, maxd = min(hdr[4], 255u);
+  bool found = false;
+  for (uint32_t level = maxd;; --level) {
+    // the level's votes enter the table: at most H probes, and H slots hold every vote
+    for (uint32_t i = tid; i < nc; i += nt) {
+      const uint32_t c = cur[i];
+      if (c == kLcaNone || dep[i] != level) continue;
+      uint32_t s = (c * 2654435761u) >> shift, got = kLcaNone;
+      for (uint32_t probe = 0; probe < H; ++probe) {
+        const uint32_t old = atomicCAS(&key[s], kLcaNone, c);
+        if (old == kLcaNone || old == c) {
+          atomicAdd(&cnt[s], 1u);
+          got = s;
+          break;
+        }
+        s = (s + 1) & (H - 1);
+      }
+      slot[i] = got;
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < nc; i += nt) {
+      const uint32_t c = cur[i];
+      if (c == kLcaNone || dep[i] != level || slot[i] == kLcaNone) continue;
+      const uint32_t m = cnt[slot[i] & (H - 1)];
+      if (!found && m >= thr) {  // one node at most: thr is above V / 2
+        hdr[5] = c;
+        hdr[6] = m;
+        hdr[7] = level;
+      }
+      if (m == V) hdr[8] = c;
+    }
+    __syncthreads();
+    found = hdr[5] != kLcaNone;
+    if (hdr[8] != kLcaNone || level == 0) break;  // the whole workgroup
+    for (uint32_t i = tid; i < nc; i += nt) {
+      const uint32_t c = cur[i];
+      if (c == kLcaNone || dep[i] != level) continue;
+      if (slot[i] != kLcaNone) {
+        key[slot[i] & (H - 1)] = kLcaNone;
+        cnt[slot[i] & (H - 1)] = 0;
+      }
+      cur[i] = min(a.tax[min(c, a.nnodes - 1)] & 0xFFFFFFu, a.nnodes - 1);
+      dep[i] = level - 1;
+    }
+    __syncthreads();
+  }
+  if (tid == 0) LcaStore(a, rd, hdr[5], hdr[7], V, hdr[6], hdr[8], nc, unmapped, best);
+}
+
 }  // namespace kern
 }  // namespace ghostm

@@ -47,6 +47,12 @@ static int Usage() {
             << "        cull keeps, per read by read-level score, with their rank and covered count; a hit is dropped\n"
             << "        when it repeats a kept alignment, or when topK (1..255, default 1) kept hits already cover\n"
             << "        coverPct (1..100, default 50) per cent of its stretch of the read\n"
+            << "       [-n nodes.tsv -a map.tsv] [-p topPct] [-P supportPct]: -y 22 and -y 23, one line per read with\n"
+            << "        hits: the taxon of the read from the hits the cull keeps (band paths, frame paths): qname taxid\n"
+            << "        depth votes support lca_taxid candidates unmapped best_score. nodes.tsv: taxid, parent taxid per\n"
+            << "        line (NCBI nodes.dmp reads as it is); map.tsv: subject name, taxid. A hit votes when its score is\n"
+            << "        within topPct (0..100, default 10) per cent of the best on its stretch of the read; the taxon is\n"
+            << "        the deepest node with supportPct (51..100, default 100) per cent of the votes\n"
             << "synth: ghostm synth -d db.fasta -q queries.fasta [-n nq] [-N dbResidues] [-s seed]\n";
   return 1;
 }

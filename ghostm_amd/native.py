@@ -242,6 +242,59 @@ class GhostmReadCullStats(ctypes.Structure):
     ]
 
 
+class GhostmLcaHit(ctypes.Structure):
+    """one hit of the per-read taxonomic assignment (16 bytes): the subject's
+    node or 0xFFFFFFFF, the score (0: not a candidate), the inclusive stretch
+    of the read."""
+
+    _fields_ = [
+        ("node", c_uint32),
+        ("score", c_uint32),
+        ("q_lo", c_uint32),
+        ("q_hi", c_uint32),
+    ]
+
+
+class GhostmLcaOut(ctypes.Structure):
+    """one read's record of the assignment (32 bytes)."""
+
+    _fields_ = [
+        ("node", c_uint32),
+        ("depth", c_uint32),
+        ("votes", c_uint32),
+        ("support", c_uint32),
+        ("lca", c_uint32),
+        ("candidates", c_uint32),
+        ("unmapped", c_uint32),
+        ("best_score", c_uint32),
+    ]
+
+
+class GhostmReadLcaStats(ctypes.Structure):
+    """the counters of the assignment (GhostmSessionReadLcaStats,
+    GhostmStageReadLcaStats)."""
+
+    _fields_ = [
+        ("seconds_lca", ctypes.c_double),
+        ("lca_launches", c_uint64),
+        ("lca_reads", c_uint64),
+        ("lca_hits", c_uint64),
+        ("lca_votes", c_uint64),
+        ("lca_assigned", c_uint64),
+    ]
+
+
+class GhostmTaxonomyInfo(ctypes.Structure):
+    """a session's taxonomy (GhostmSessionTaxonomyInfo)."""
+
+    _fields_ = [
+        ("nodes", c_uint64),
+        ("subjects_mapped", c_uint64),
+        ("subjects_unmapped", c_uint64),
+        ("map_unmatched", c_uint64),
+    ]
+
+
 class GhostmDbChunkInfo(ctypes.Structure):
     """one resident DB chunk: the values of its .inf and .ind headers."""
 
@@ -416,6 +469,12 @@ SIGNATURES = {
     "GhostmReadCullHost": (c_int, [c_uint32, u32p, c_uint32, POINTER(GhostmCullHit), c_uint32, c_uint32,
                                    POINTER(GhostmCullOut)]),
     "GhostmStageReadCullStats": (c_size_t, [POINTER(GhostmReadCullStats), c_size_t]),
+    "SetTaxonomyGpu": (c_int, [c_uint32, u32p]),
+    "GhostmTaxonomyDepths": (c_int, [c_uint32, u32p, u32p]),
+    "ReadLcaGpu": (c_int, [c_uint32, u32p, c_uint32, POINTER(GhostmLcaHit), c_uint32, c_uint32, POINTER(GhostmLcaOut)]),
+    "GhostmReadLcaHost": (c_int, [c_uint32, u32p, c_uint32, u32p, c_uint32, POINTER(GhostmLcaHit), c_uint32, c_uint32,
+                                  POINTER(GhostmLcaOut)]),
+    "GhostmStageReadLcaStats": (c_size_t, [POINTER(GhostmReadLcaStats), c_size_t]),
     "GhostmBuildIndexGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, u32p, u32p, u32p, c_int,
                                     POINTER(c_float)]),
     "GhostmFormatQueriesGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_uint32,
@@ -489,6 +548,13 @@ SIGNATURES = {
     "GhostmSessionSetCull": (c_int, [c_void_p, c_uint32, c_uint32]),
     "GhostmSessionSetTileGroups": (c_int, [c_void_p, c_int]),
     "GhostmSessionReadCullStats": (c_size_t, [c_void_p, POINTER(GhostmReadCullStats), c_size_t]),
+    "GhostmSessionSetTaxonomy": (c_int, [c_void_p, c_uint32, u32p, u32p, c_size_t, u32p]),
+    "GhostmSessionSetTaxonomyFiles": (c_int, [c_void_p, c_char_p, c_char_p]),
+    "GhostmSessionTaxonomyInfo": (c_size_t, [c_void_p, POINTER(GhostmTaxonomyInfo), c_size_t]),
+    "GhostmSessionSetLca": (c_int, [c_void_p, c_uint32, c_uint32]),
+    "GhostmSessionReadLca": (c_size_t, [c_void_p, c_int, POINTER(GhostmLcaOut), c_size_t]),
+    "GhostmSessionReadLcaBegin": (c_size_t, [c_void_p, c_int, u32p, c_size_t]),
+    "GhostmSessionReadLcaStats": (c_size_t, [c_void_p, POINTER(GhostmReadLcaStats), c_size_t]),
     "GhostmSessionDeviceHits": (c_size_t, [c_void_p, c_void_p, c_size_t]),
     "GhostmSessionStats": (c_int, [c_void_p, POINTER(GhostmStats)]),
     "GhostmSessionStatsSized": (c_size_t, [c_void_p, POINTER(GhostmStats), c_size_t]),

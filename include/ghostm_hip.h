@@ -1071,6 +1071,120 @@ typedef struct GhostmReadCullStats {
  * conventions. */
 size_t GhostmStageReadCullStats(GhostmReadCullStats *stats, size_t size);
 
+/* The taxon of a read: the lowest common ancestor (LCA) of the subjects its
+ * best hits name, with a support threshold. All arithmetic is on integers; the
+ * kernel equals the host model exactly.
+ *
+ * Taxonomy: nnodes nodes, indexed 0 .. nnodes - 1, parent[i] < nnodes. Exactly
+ * one node is its own parent, the root; every node reaches the root;
+ * depth[root] = 0 and depth[i] = depth[parent[i]] + 1. 1 <= nnodes <= 2^24 and
+ * depth <= 255: one 32-bit word depth << 24 | parent holds a node, so a step up
+ * the tree is one gather.
+ *
+ * Input: nreads reads; read r's hits are hit[read_begin[r] ..
+ * read_begin[r + 1]) (read_begin has nreads + 1 entries, monotone, the last at
+ * most nhits). A hit is the node of its subject (0xFFFFFFFF: the subject has no
+ * taxon), its score (0: not a candidate; it was culled, a duplicate, or empty)
+ * and its inclusive stretch q_lo <= q_hi of the read. Scores and coordinates
+ * are below 2^25, so that score * 100 fits 32 bits.
+ *
+ * Per read:
+ *   1. The candidates are the read's hits with score > 0; `candidates` is their
+ *      number and best_score their largest score.
+ *   2. Score test. For a candidate h, ref(h) is the largest score among the
+ *      candidates g, h included, whose [q_lo, q_hi] shares a position with h's
+ *      (q_hi + 1 == the other's q_lo does not). h passes when score(h) * 100 >=
+ *      (100 - top_pct) * ref(h). The test is relative to the hits on the same
+ *      stretch: a read that carries a strong and a weak gene lets both vote.
+ *   3. The votes are the passing candidates with a node; `votes` is their
+ *      number V, `unmapped` the number of passing candidates without a node.
+ *   4. V == 0: node = lca = 0xFFFFFFFF, depth = support = 0.
+ *   5. Otherwise count(n) is the number of votes whose node has n on its path
+ *      to the root, ends included, and thr = (support_pct * V + 99) / 100.
+ *      node is the deepest n with count(n) >= thr (unique: support_pct >= 51
+ *      puts thr above V / 2, so two such nodes lie on one path), support =
+ *      count(node), depth = depth[node]; lca is the deepest n with count(n) ==
+ *      V. With support_pct == 100, node == lca.
+ * A read without hits gets the record of 4 with all counts 0. The record does
+ * not depend on the order of the hits. top_pct is 0..100, support_pct 51..100. */
+typedef struct GhostmLcaHit {  /* 16 bytes */
+  uint32_t node;        /* the subject's node, or 0xFFFFFFFF */
+  uint32_t score;       /* 0: not a candidate */
+  uint32_t q_lo, q_hi;  /* inclusive, on the read */
+} GhostmLcaHit;
+
+typedef struct GhostmLcaOut {  /* 32 bytes */
+  uint32_t node;        /* the assignment, or 0xFFFFFFFF */
+  uint32_t depth;       /* depth[node] */
+  uint32_t votes;       /* V */
+  uint32_t support;     /* count(node) */
+  uint32_t lca;         /* the deepest node on every vote's path, or 0xFFFFFFFF */
+  uint32_t candidates;
+  uint32_t unmapped;
+  uint32_t best_score;
+} GhostmLcaOut;
+
+/* The taxonomy of the stage-level calls: checked on the host, packed and made
+ * resident on SetOptionGpu's device, or on device 0 when that was not called.
+ * It stays until the next SetTaxonomyGpu or FreeGpu. Refusals (return 1, the
+ * reason in GhostmGetLastError; the previous taxonomy stays):
+ *   "taxonomy"  no root, a second root, a cycle, a parent out of range, nnodes
+ *               outside 1..2^24, a node deeper than 255; the first offending
+ *               node is named
+ *   "null"      parent is null */
+int SetTaxonomyGpu(uint32_t nnodes, const uint32_t parent[]);
+
+/* The same checks and the depths on the host, without a device:
+ * depth_out[nnodes]. */
+int GhostmTaxonomyDepths(uint32_t nnodes, const uint32_t parent[], uint32_t depth_out[]);
+
+/* ReadLcaGpu (kernels k_read_lca_wave, k_read_lca) needs neither SetQueryGpu
+ * nor SetDbGpu: the records and the resident taxonomy are all it reads.
+ * Everything is checked on the host before any upload or launch; a refused
+ * call returns 1, leaves out untouched, launches nothing and names its reason:
+ *   "param"     top_pct or support_pct out of range
+ *   "null"      a null pointer where one is needed (hit with nhits > 0,
+ *               read_begin with nreads > 0, out with nreads > 0)
+ *   "taxonomy"  no taxonomy is resident
+ *   "reads"     read_begin not monotone or ending past nhits; a read of more
+ *               than 16384 candidates (the score test is quadratic in a read's
+ *               candidates: 16384^2 pair tests over 1024 lanes is 262144
+ *               iterations per lane, which stays in the milliseconds)
+ *   "range"     q_lo > q_hi
+ *   "bounds"    a score or coordinate at or over 2^25
+ *   "node"      a node that is neither 0xFFFFFFFF nor below nnodes
+ * A read of at most 64 candidates takes one wave, a read of at most 1024 one
+ * workgroup with its tables in LDS, a larger read one workgroup with its
+ * tables in device memory; none is done on the host (a read without a
+ * candidate needs no kernel: its record is 4's). The reads go in batches of at
+ * most GHOSTM_LCA_BATCH_READS reads (default: no limit) and
+ * GHOSTM_LCA_SCRATCH_MB megabytes of hits, records and tables (default 1024);
+ * 32 bytes per read are read back. out has nreads records. */
+int ReadLcaGpu(uint32_t nreads, const uint32_t read_begin[], uint32_t nhits, const GhostmLcaHit hit[],
+               uint32_t top_pct, uint32_t support_pct, GhostmLcaOut out[]);
+
+/* The same on the host over the taxonomy given, with no device call: the model
+ * the kernel equals exactly, with the same checks and reasons (and
+ * SetTaxonomyGpu's for the taxonomy). */
+int GhostmReadLcaHost(uint32_t nnodes, const uint32_t parent[], uint32_t nreads, const uint32_t read_begin[],
+                      uint32_t nhits, const GhostmLcaHit hit[], uint32_t top_pct, uint32_t support_pct,
+                      GhostmLcaOut out[]);
+
+/* The counters of the assignment, a struct of their own like
+ * GhostmReadCullStats; GhostmStats keeps its layout. */
+typedef struct GhostmReadLcaStats {
+  double seconds_lca;     /* k_read_lca*, device time */
+  uint64_t lca_launches;  /* batches of reads with a candidate */
+  uint64_t lca_reads;     /* reads with a hit */
+  uint64_t lca_hits;
+  uint64_t lca_votes;     /* V summed over the reads */
+  uint64_t lca_assigned;  /* reads with a node */
+} GhostmReadLcaStats;
+
+/* The counters behind the stage-level calls; GhostmStageReadCullStats'
+ * conventions. */
+size_t GhostmStageReadLcaStats(GhostmReadLcaStats *stats, size_t size);
+
 /* A session without a database: `aln`'s options without -d (giving it is an
  * error). With -i the query chunks are loaded as GhostmSessionCreate loads
  * them; without -i the session starts with neither input and the queries come
@@ -1491,6 +1605,60 @@ size_t GhostmSessionReadCullStats(void *session, GhostmReadCullStats *stats, siz
  * differs. A shard session refuses it as it refuses a tiled set. Returns 0, or
  * 1 on error. */
 int GhostmSessionSetTileGroups(void *session, int on);
+
+/* A taxonomy for the session's resident database (the contract is above
+ * ReadLcaGpu). taxid[nnodes] are the printed labels, distinct and at least 1 (0
+ * is printed for "unclassified"); parent[nnodes] as SetTaxonomyGpu takes it;
+ * subject_node[nsubjects] is indexed by GhostmHit.db_id and holds a node or
+ * 0xFFFFFFFF. nsubjects must equal the resident database's subject count over
+ * all chunks, else the call is refused with "subjects"; "taxonomy" and "null" as
+ * SetTaxonomyGpu, "taxonomy" also for a taxid of 0 or a repeated one, "node"
+ * for a subject_node that is neither. The call also makes the stage-level
+ * taxonomy resident. GhostmSessionSetDb* drop the taxonomy; a refused call
+ * leaves the session as it was. Returns 0, or 1 on error. */
+int GhostmSessionSetTaxonomy(void *session, uint32_t nnodes, const uint32_t taxid[], const uint32_t parent[],
+                             size_t nsubjects, const uint32_t subject_node[]);
+/* The same from two text files.
+ * Nodes file: per line two unsigned integers, taxid and parent taxid, separated
+ * by any run of tabs, spaces and '|'; further fields are ignored, so NCBI's
+ * nodes.dmp reads as it is; blank lines are skipped. The root has itself as
+ * parent. A parent that no line defines or a repeated taxid is refused with
+ * "taxonomy" and the line number.
+ * Map file: per line name, whitespace, taxid. name is compared with each
+ * subject's name up to its first space or tab; a later line for the same name
+ * wins; a taxid the nodes lack is refused with "map"; a name the database lacks
+ * is counted, not refused; a subject without a line is unmapped. */
+int GhostmSessionSetTaxonomyFiles(void *session, const char *nodes_path, const char *map_path);
+typedef struct GhostmTaxonomyInfo {
+  uint64_t nodes;             /* 0: no taxonomy */
+  uint64_t subjects_mapped;
+  uint64_t subjects_unmapped;
+  uint64_t map_unmatched;     /* map lines whose name no subject has (file form) */
+} GhostmTaxonomyInfo;
+size_t GhostmSessionTaxonomyInfo(void *session, GhostmTaxonomyInfo *info, size_t size);
+/* top_pct 0..100 (default 10) and support_pct 51..100 (default 100) of the
+ * session's assignment; a change drops the kept result. Returns 0, or 1
+ * ("param"). */
+int GhostmSessionSetLca(void *session, uint32_t top_pct, uint32_t support_pct);
+/* One GhostmLcaOut per read of GhostmSessionReadCull(session, frame, ...), with
+ * the same definition of a read, built from that result: score is the
+ * read-level score of a KEPT hit, else 0; q_lo, q_hi are the cull's; node =
+ * subject_node[db_id]. node and lca are node indices (taxid[] labels them).
+ * With out NULL returns the count of reads, else copies min(cap, count) records
+ * and returns that; (size_t)-1 on error: "taxonomy" without one, and
+ * GhostmSessionReadCull's errors. Computed on first use; dropped by everything
+ * that drops the cull's result, by SetLca and by SetTaxonomy*. -y 22 (band
+ * paths) and -y 23 (frame paths) print one line per read with hits, in read
+ * order, tab separated:
+ *   qname taxid depth votes support lca_taxid candidates unmapped best_score
+ * taxid and lca_taxid are 0 when the read has no vote. */
+size_t GhostmSessionReadLca(void *session, int frame, GhostmLcaOut *out, size_t cap);
+/* Each read's first hit as an index of GhostmSessionHits, plus the end: one
+ * more entry than GhostmSessionReadLca has records. */
+size_t GhostmSessionReadLcaBegin(void *session, int frame, uint32_t *read_begin, size_t cap);
+/* The assignment's counters since the last run began; GhostmSessionBandStats'
+ * conventions. */
+size_t GhostmSessionReadLcaStats(void *session, GhostmReadLcaStats *stats, size_t size);
 
 /* The same records resident on the session's GPU, for a device-to-device
  * gather across ranks: copies min(n, cap) records to dst_device
