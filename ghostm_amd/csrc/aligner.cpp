@@ -11,6 +11,7 @@
 #include <charconv>
 #include <climits>
 #include <cmath>
+#include <cstddef>
 #include <cstdlib>
 #include <cstring>
 #include <exception>
@@ -19,6 +20,7 @@
 #include <sstream>
 #include <stdexcept>
 #include <thread>
+#include <type_traits>
 #include <unordered_map>
 #include <unordered_set>
 
@@ -1513,6 +1515,49 @@ static void AddDeltas(Dst &dst, const DeviceTimes &before, const DeviceTimes &af
   ((dst.*m.first += after.*m.second - before.*m.second), ...);
 }
 
+// The read-level passes' counters (DeviceTimes holds them as the public structs)
+// are added whole: every one of the six structs is one double, the seconds,
+// followed by uint64_t counters only.
+template <class Stats, size_t kFields>
+constexpr bool SecondsThenCounters(double Stats::*) {
+  return std::is_trivially_copyable<Stats>::value && sizeof(Stats) == 8 * kFields;
+}
+static_assert(SecondsThenCounters<GhostmBandStats, 5>(&GhostmBandStats::seconds_band) &&
+                  SecondsThenCounters<GhostmFrameStats, 5>(&GhostmFrameStats::seconds_frame) &&
+                  SecondsThenCounters<GhostmReadRowsStats, 4>(&GhostmReadRowsStats::seconds_read_rows) &&
+                  SecondsThenCounters<GhostmReadPileupStats, 6>(&GhostmReadPileupStats::seconds_read_pileup) &&
+                  SecondsThenCounters<GhostmReadCullStats, 7>(&GhostmReadCullStats::seconds_cull) &&
+                  SecondsThenCounters<GhostmReadLcaStats, 6>(&GhostmReadLcaStats::seconds_lca),
+              "a pass's counters: a double, then 8-byte counters");
+static_assert(offsetof(GhostmBandStats, seconds_band) == 0 && offsetof(GhostmFrameStats, seconds_frame) == 0 &&
+                  offsetof(GhostmReadRowsStats, seconds_read_rows) == 0 &&
+                  offsetof(GhostmReadPileupStats, seconds_read_pileup) == 0 &&
+                  offsetof(GhostmReadCullStats, seconds_cull) == 0 && offsetof(GhostmReadLcaStats, seconds_lca) == 0,
+              "a pass's counters begin with the seconds");
+
+// dst += x (or dst -= x), field by field
+template <class Stats>
+static void AddStats(Stats &dst, const Stats &x, bool subtract = false) {
+  constexpr size_t n = sizeof(Stats) / 8;
+  uint64_t d[n], v[n];
+  double ds, vs;
+  memcpy(d, &dst, sizeof(Stats));
+  memcpy(v, &x, sizeof(Stats));
+  memcpy(&ds, d, 8);
+  memcpy(&vs, v, 8);
+  ds = subtract ? ds - vs : ds + vs;
+  memcpy(d, &ds, 8);
+  for (size_t k = 1; k < n; ++k) d[k] = subtract ? d[k] - v[k] : d[k] + v[k];
+  memcpy(&dst, d, sizeof(Stats));
+}
+
+// What a pass added to its counters: after - before
+template <class Stats>
+static Stats StatsDelta(Stats after, const Stats &before) {
+  AddStats(after, before, true);
+  return after;
+}
+
 // The index of the tile at `offset` within its source of m letters and `tiles`
 // tiles (query_tiles.h: the last tile ends with the source).
 static uint32_t TileIndex(uint32_t offset, uint32_t tiles, uint32_t m, uint32_t W, uint32_t step) {
@@ -1770,14 +1815,14 @@ const std::vector<uint32_t> &Session::PathOps() {
 // -y 7 line.
 void Session::FormatPathTabular(bool read_level) {
   const std::vector<GhostmHitPath> &tile_path = HitsPath();
-  const std::vector<GhostmHitPath> *band_path = read_level ? &HitsBand() : nullptr;
+  const ReadLevelResult *lvl = read_level ? &ReadLevel(false) : nullptr;
   const LineFormat &w = Format();
   // tab[7]: the tab after the subject name
   RewriteLines("tabular output", 8, [](size_t, size_t n) { return n * 64; },
                [&](size_t hit, const std::string &in, size_t pos, size_t, const size_t *tab, std::string &out) {
-    const bool band = band_path && (*band_path)[hit].score > 0;
-    const GhostmHitPath &x = band ? (*band_path)[hit] : tile_path[hit];
-    const std::vector<uint32_t> &ops = band ? band_ops_ : path_ops_;
+    const bool band = lvl && lvl->rec[hit].score > 0;
+    const GhostmHitPath &x = band ? lvl->rec[hit] : tile_path[hit];
+    const std::vector<uint32_t> &ops = band ? lvl->ops : path_ops_;
     uint32_t count[4] = {0, 0, 0, 0}, gap_runs = 0;
     for (uint32_t r = 0; r < x.n_runs; ++r) {
       const uint32_t word = ops[x.ops_offset + r];
@@ -1797,7 +1842,7 @@ void Session::FormatPathTabular(bool read_level) {
     p = PutU32(p, x.s_start + 1); *p++ = '\t';
     p = PutU32(p, x.s_end + 1); *p++ = '\t';
     if (band) {
-      const uint32_t m = band_letters_[hit];
+      const uint32_t m = lvl->src[hit].letters;
       const float scaled = (float)((uint64_t)m * (uint64_t)db_sum_u32_) * w.ev.p.K;
       p = w.PutEvalue(p, m, x.score, scaled); *p++ = '\t';
       p = w.PutBits(p, x.score);
@@ -1856,31 +1901,53 @@ void Session::SetBand(uint32_t band) {
   if (band < 1 || band > kBandMax) throw Error("band: half-width " + std::to_string(band) + " outside 1..31");
   if (band == band_) return;
   band_ = band;
-  hits_band_.clear();
-  band_ops_.clear();
-  band_src_.clear();
-  hits_band_valid_ = false;
-  read_rows_[0].Drop();
-  pileup_[kBandLevel].Drop();
-  cull_[0].Drop();
-  lca_[0].Drop();
-  DropFrameResults();  // the frame pass runs inside the same band
+  DropLevel(0);
+  DropLevel(1);  // the frame pass runs inside the same band
 }
 
-// The read-level path of every final hit (HitsBand). The record HitsExt()
-// resolved for a hit is a tile of its source: the tile table gives the source's
-// letters and the tile's offset, from which the tile's index and the source's
-// first record follow (a protein record's tiles are consecutive records, a DNA
-// frame's lie six records apart). On an untiled set every record is its own
-// single-tile source. One BandAlign call per (query chunk, DB chunk).
-const std::vector<GhostmHitPath> &Session::HitsBand() {
-  if (hits_band_valid_) return hits_band_;
+void Session::SetFrameShift(int shift) {
+  if (shift > 0 || shift < kFrameShiftMin)
+    throw Error("shift: frameshift cost " + std::to_string(shift) + " outside -(1 << 20)..0");
+  if (shift == frame_shift_) return;
+  frame_shift_ = shift;
+  DropLevel(1);
+}
+
+// A level's paths, or from its cull or its LCA on, and everything made from them
+void Session::DropLevel(int lv, LevelStage from) {
+  if (from == kFromPaths) {
+    level_[lv].Drop();
+    if (lv == 1) frame_info_.clear();
+    read_rows_[lv].Drop();
+    pileup_[kBandLevel + lv].Drop();
+  }
+  if (from != kFromLca) cull_[lv].Drop();
+  lca_[lv].Drop();
+}
+
+// The read-level path of every final hit: the band paths (HitsBand) or the
+// frame paths (HitsFrame). The record HitsExt() resolved for a hit is a tile of
+// its source: the tile table gives the source's letters and the tile's offset,
+// from which the tile's index and the source's first record follow (a protein
+// record's tiles are consecutive records, a DNA frame's lie six records apart).
+// On an untiled set every record is its own single-tile source. The frame
+// pass's source is the strand of the tile's frame f: strand f / 3, beginning
+// f % 3 records before the frame's own first record (the six frames of a tile
+// are consecutive records). Both passes' anchor is the first cell of the tile
+// path, on the frame level a codon diagonal. One BandAlign or FrameAlign call
+// per (query chunk, DB chunk).
+const Session::ReadLevelResult &Session::ReadLevel(bool frame) {
+  ReadLevelResult &res = level_[frame ? 1 : 0];
+  if (res.valid) return res;
+  const std::string what = frame ? "frame align: " : "band align: ";
+  if (frame && (tile_table_.empty() || !tile_dna_))
+    throw Error(what + "the query set is not a DNA set made by a tiled setter");
   const std::vector<GhostmHitPath> &path = HitsPath();
   const std::vector<GhostmHit> &hits = Hits();
-  hits_band_.assign(hits.size(), GhostmHitPath{0, 0, 0, 0, 0, 0, 0});
-  band_letters_.assign(hits.size(), 0);
-  band_src_.assign(hits.size(), GhostmBandSource{0, 0, 0, 0});
-  band_ops_.clear();
+  res.rec.assign(hits.size(), GhostmHitPath{0, 0, 0, 0, 0, 0, 0});
+  res.src.assign(hits.size(), GhostmBandSource{0, 0, 0, 0});
+  res.ops.clear();
+  if (frame) frame_info_.assign(hits.size(), GhostmHitFrameInfo{0, 0, 0, 0});
   const std::vector<std::vector<size_t>> groups = HitsByChunkPair();
   DeviceModule &dev = DeviceModule::Get();
   const DeviceTimes before = dev.times();
@@ -1907,8 +1974,10 @@ const std::vector<GhostmHitPath> &Session::HitsBand() {
         offset = t.offset;
         const uint32_t index = TileIndex(offset, tiles, m, W, step);
         const uint32_t stride = tile_dna_ ? 6u : 1u;
-        if ((uint64_t)index * stride > local) throw Error("band align: a tile before its chunk's first record");
-        s = GhostmBandSource{local - index * stride, stride, tiles, m};
+        const uint64_t back = (uint64_t)index * stride + (frame ? t.frame % 3 : 0u);
+        if (back > local) throw Error(what + "a tile before its chunk's first record");
+        s = GhostmBandSource{local - (uint32_t)back, stride, tiles, m};
+        if (frame) frame_info_[h] = GhostmHitFrameInfo{t.frame / 3, tile_read_nt_[t.record], m, 0};
       }
       const uint32_t subject = hits[h].db_id - d.global_base, pos = d.chunk.starts[subject];
       src.push_back(s);
@@ -1919,133 +1988,39 @@ const std::vector<GhostmHitPath> &Session::HitsBand() {
     }
     const uint32_t n = (uint32_t)items.size();
     rec.resize(n);
-    dev.BandAlign(q.dev, d.dev, n, src.data(), diag.data(), lo.data(), hi.data(), step, band_, opt_.open_gap,
-                  opt_.extend_gap, rec.data(), &words[qi * dbs_.size() + di]);
+    std::vector<uint32_t> *ops = &words[qi * dbs_.size() + di];
+    if (frame)
+      dev.FrameAlign(q.dev, d.dev, n, src.data(), diag.data(), lo.data(), hi.data(), step, band_, opt_.open_gap,
+                     opt_.extend_gap, frame_shift_, rec.data(), ops);
+    else
+      dev.BandAlign(q.dev, d.dev, n, src.data(), diag.data(), lo.data(), hi.data(), step, band_, opt_.open_gap,
+                    opt_.extend_gap, rec.data(), ops);
     for (uint32_t k = 0; k < n; ++k) {
       GhostmHitPath p = rec[k];
       p.s_start -= lo[k];
       p.s_end -= lo[k];
-      hits_band_[items[k]] = p;  // ops_offset: still within the chunk pair's words
-      band_letters_[items[k]] = src[k].letters;
-      band_src_[items[k]] = src[k];
+      res.rec[items[k]] = p;  // ops_offset: still within the chunk pair's words
+      res.src[items[k]] = src[k];
     }
   });
-  JoinWords(words, &hits_band_, &band_ops_);
-  AddDeltas(band_stats_, before, dev.times(), std::make_pair(&GhostmBandStats::seconds_band, &DeviceTimes::band),
-            std::make_pair(&GhostmBandStats::band_launches, &DeviceTimes::band_launches),
-            std::make_pair(&GhostmBandStats::band_hits, &DeviceTimes::band_hits),
-            std::make_pair(&GhostmBandStats::band_cells, &DeviceTimes::band_cells),
-            std::make_pair(&GhostmBandStats::band_dir_bytes, &DeviceTimes::band_dir_bytes));
-  hits_band_valid_ = true;
-  return hits_band_;
-}
-
-const std::vector<uint32_t> &Session::BandOps() {
-  HitsBand();
-  return band_ops_;
-}
-
-void Session::DropFrameResults() {
-  hits_frame_.clear();
-  frame_ops_.clear();
-  frame_info_.clear();
-  frame_src_.clear();
-  hits_frame_valid_ = false;
-  read_rows_[1].Drop();
-  pileup_[kFrameLevel].Drop();
-  cull_[1].Drop();
-  lca_[1].Drop();
-}
-
-void Session::SetFrameShift(int shift) {
-  if (shift > 0 || shift < kFrameShiftMin)
-    throw Error("shift: frameshift cost " + std::to_string(shift) + " outside -(1 << 20)..0");
-  if (shift == frame_shift_) return;
-  frame_shift_ = shift;
-  DropFrameResults();
-}
-
-// The frame path of every final hit (HitsFrame). The record HitsExt() resolved
-// for a hit is a tile of frame f of a read: its strand is f / 3, and the strand
-// source begins f % 3 records before the frame's own first record (the six
-// frames of a tile are consecutive records). The anchor is HitsBand's: the
-// first cell of the tile path, a codon diagonal. One FrameAlign call per (query
-// chunk, DB chunk).
-const std::vector<GhostmHitPath> &Session::HitsFrame() {
-  if (hits_frame_valid_) return hits_frame_;
-  if (tile_table_.empty() || !tile_dna_)
-    throw Error("frame align: the query set is not a DNA set made by a tiled setter");
-  const std::vector<GhostmHitPath> &path = HitsPath();
-  const std::vector<GhostmHit> &hits = Hits();
-  hits_frame_.assign(hits.size(), GhostmHitPath{0, 0, 0, 0, 0, 0, 0});
-  frame_info_.assign(hits.size(), GhostmHitFrameInfo{0, 0, 0, 0});
-  frame_src_.assign(hits.size(), GhostmBandSource{0, 0, 0, 0});
-  frame_ops_.clear();
-  const std::vector<std::vector<size_t>> groups = HitsByChunkPair();
-  DeviceModule &dev = DeviceModule::Get();
-  const DeviceTimes before = dev.times();
-  std::vector<GhostmBandSource> src;
-  std::vector<int32_t> diag;
-  std::vector<uint32_t> lo, hi;
-  std::vector<GhostmHitPath> rec;
-  std::vector<std::vector<uint32_t>> words(groups.size());
-  ForChunkPairs(groups, [&](size_t qi, size_t di, const std::vector<size_t> &items) {
-    const QueryData &q = queries_[qi];
-    const DbData &d = dbs_[di];
-    const uint32_t W = q.chunk.L, step = tile_step_;
-    src.clear();
-    diag.clear();
-    lo.clear();
-    hi.clear();
-    for (size_t h : items) {
-      const uint32_t local = hit_source_[h].query;
-      const GhostmQueryTile &t = tile_table_[q.global_base + local];
-      const uint32_t m = std::max(t.letters, 1u), tiles = TileCount(m, W, step);
-      const uint32_t index = TileIndex(t.offset, tiles, m, W, step);
-      const uint32_t back = index * 6 + t.frame % 3;
-      if (back > local) throw Error("frame align: a tile before its chunk's first record");
-      const uint32_t subject = hits[h].db_id - d.global_base, pos = d.chunk.starts[subject];
-      src.push_back(GhostmBandSource{local - back, 6, tiles, m});
-      diag.push_back((int32_t)((int64_t)pos + path[h].s_start - ((int64_t)t.offset + path[h].q_start)));
-      lo.push_back(pos);
-      hi.push_back(pos + SubjectLength(d, subject) - 1);
-      frame_info_[h] = GhostmHitFrameInfo{t.frame / 3, tile_read_nt_[t.record], m, 0};
-    }
-    const uint32_t n = (uint32_t)items.size();
-    rec.resize(n);
-    dev.FrameAlign(q.dev, d.dev, n, src.data(), diag.data(), lo.data(), hi.data(), step, band_, opt_.open_gap,
-                   opt_.extend_gap, frame_shift_, rec.data(), &words[qi * dbs_.size() + di]);
-    for (uint32_t k = 0; k < n; ++k) {
-      GhostmHitPath p = rec[k];
-      p.s_start -= lo[k];
-      p.s_end -= lo[k];
-      hits_frame_[items[k]] = p;  // ops_offset: still within the chunk pair's words
-      frame_src_[items[k]] = src[k];
-    }
-  });
-  JoinWords(words, &hits_frame_, &frame_ops_);
-  // every path's shifts
-  for (size_t h = 0; h < hits.size(); ++h)
-    for (uint32_t r = 0; r < hits_frame_[h].n_runs; ++r) {
-      const uint32_t word = frame_ops_[hits_frame_[h].ops_offset + r];
-      if ((word & 15u) >= 4) frame_info_[h].shifts += word >> 4;
-    }
-  AddDeltas(frame_stats_, before, dev.times(), std::make_pair(&GhostmFrameStats::seconds_frame, &DeviceTimes::frame),
-            std::make_pair(&GhostmFrameStats::frame_launches, &DeviceTimes::frame_launches),
-            std::make_pair(&GhostmFrameStats::frame_hits, &DeviceTimes::frame_hits),
-            std::make_pair(&GhostmFrameStats::frame_cells, &DeviceTimes::frame_cells),
-            std::make_pair(&GhostmFrameStats::frame_dir_bytes, &DeviceTimes::frame_dir_bytes));
-  hits_frame_valid_ = true;
-  return hits_frame_;
-}
-
-const std::vector<uint32_t> &Session::FrameOps() {
-  HitsFrame();
-  return frame_ops_;
+  JoinWords(words, &res.rec, &res.ops);
+  if (frame) {
+    // every path's shifts
+    for (size_t h = 0; h < hits.size(); ++h)
+      for (uint32_t r = 0; r < res.rec[h].n_runs; ++r) {
+        const uint32_t word = res.ops[res.rec[h].ops_offset + r];
+        if ((word & 15u) >= 4) frame_info_[h].shifts += word >> 4;
+      }
+    AddStats(frame_stats_, StatsDelta(dev.times().frame, before.frame));
+  } else {
+    AddStats(band_stats_, StatsDelta(dev.times().band, before.band));
+  }
+  res.valid = true;
+  return res;
 }
 
 const std::vector<GhostmHitFrameInfo> &Session::FrameInfo() {
-  HitsFrame();
+  ReadLevel(true);
   return frame_info_;
 }
 
@@ -2057,18 +2032,17 @@ const std::vector<GhostmHitFrameInfo> &Session::FrameInfo() {
 const std::vector<GhostmHitReadRows> &Session::HitsReadRows(bool frame) {
   ReadRowsResult &res = read_rows_[frame ? 1 : 0];
   if (res.valid) return res.rec;
-  const std::vector<GhostmHitPath> &path = frame ? HitsFrame() : HitsBand();
-  const std::vector<uint32_t> &words = frame ? frame_ops_ : band_ops_;
-  const std::vector<GhostmBandSource> &source = frame ? frame_src_ : band_src_;
+  const ReadLevelResult &lvl = ReadLevel(frame);
+  const std::vector<uint32_t> &words = lvl.ops;
   res.rec.assign(Hits().size(), GhostmHitReadRows{0, 0, 0, 0, 0, 0, 0, 0, 0});
   DeviceModule &dev = DeviceModule::Get();
   const DeviceTimes before = dev.times();
   std::vector<GhostmBandSource> src;
   std::vector<GhostmHitReadRows> out;
-  RowsPlan(path, words, &res.bytes, [&](size_t qi, size_t di, const std::vector<size_t> &items,
+  RowsPlan(lvl.rec, words, &res.bytes, [&](size_t qi, size_t di, const std::vector<size_t> &items,
                                         const std::vector<GhostmHitPath> &rec, const std::vector<uint64_t> &dst) {
     src.clear();
-    for (size_t h : items) src.push_back(source[h]);
+    for (size_t h : items) src.push_back(lvl.src[h]);
     out.resize(items.size());
     const uint32_t W = queries_[qi].chunk.L, step = tile_step_ ? tile_step_ : W;
     dev.ReadRows(queries_[qi].dev, dbs_[di].dev, (uint32_t)items.size(), src.data(), rec.data(), words.data(),
@@ -2076,11 +2050,7 @@ const std::vector<GhostmHitReadRows> &Session::HitsReadRows(bool frame) {
                  out.data(), res.bytes.data(), res.bytes.size(), dst.data());
     for (size_t k = 0; k < items.size(); ++k) res.rec[items[k]] = out[k];
   });
-  AddDeltas(read_rows_stats_, before, dev.times(),
-            std::make_pair(&GhostmReadRowsStats::seconds_read_rows, &DeviceTimes::read_rows),
-            std::make_pair(&GhostmReadRowsStats::read_rows_launches, &DeviceTimes::read_rows_launches),
-            std::make_pair(&GhostmReadRowsStats::read_rows_hits, &DeviceTimes::read_rows_hits),
-            std::make_pair(&GhostmReadRowsStats::read_rows_columns, &DeviceTimes::read_rows_columns));
+  AddStats(read_rows_stats_, StatsDelta(dev.times().read_rows, before.read_rows));
   res.valid = true;
   return res.rec;
 }
@@ -2097,7 +2067,7 @@ const std::vector<uint8_t> &Session::ReadRowBytes(bool frame) {
 void Session::FormatReadRows(bool frame) {
   const std::vector<GhostmHitReadRows> &read = HitsReadRows(frame);
   const std::vector<uint8_t> &read_bytes = read_rows_[frame ? 1 : 0].bytes;
-  const std::vector<GhostmHitPath> &level = frame ? hits_frame_ : hits_band_;
+  const std::vector<GhostmHitPath> &level = level_[frame ? 1 : 0].rec;
   const std::vector<GhostmHitRows> &tile = HitsRows();
   const std::vector<uint8_t> &tile_bytes = row_bytes_;
   const auto extra = [&](size_t first, size_t n) {
@@ -2135,14 +2105,15 @@ static inline uint32_t ForwardNt(uint32_t strand, uint32_t read_nt, uint32_t p) 
 // prints its tile path in the same units, with the style-0 line's E-value and
 // bit score.
 void Session::FormatFrameTabular() {
-  const std::vector<GhostmHitPath> &frame_path = HitsFrame();
+  const ReadLevelResult &lvl = ReadLevel(true);
+  const std::vector<GhostmHitPath> &frame_path = lvl.rec;
   const std::vector<GhostmHitPath> &tile_path = HitsPath();
   const LineFormat &w = Format();
   RewriteLines("frame tabular output", 8, [](size_t, size_t n) { return n * 80; },
                [&](size_t hit, const std::string &in, size_t pos, size_t, const size_t *tab, std::string &out) {
     const bool framed = frame_path[hit].score > 0;
     const GhostmHitPath &x = framed ? frame_path[hit] : tile_path[hit];
-    const std::vector<uint32_t> &ops = framed ? frame_ops_ : path_ops_;
+    const std::vector<uint32_t> &ops = framed ? lvl.ops : path_ops_;
     const GhostmHitFrameInfo &info = frame_info_[hit];
     uint32_t count[4] = {0, 0, 0, 0}, gap_runs = 0;
     for (uint32_t r = 0; r < x.n_runs; ++r) {
@@ -2203,10 +2174,8 @@ void Session::SetCull(uint32_t top_k, uint32_t cover_pct) {
   if (top_k == cull_top_k_ && cover_pct == cull_cover_pct_) return;
   cull_top_k_ = top_k;
   cull_cover_pct_ = cover_pct;
-  cull_[0].Drop();
-  lca_[0].Drop();
-  cull_[1].Drop();
-  lca_[1].Drop();
+  DropLevel(0, kFromCull);
+  DropLevel(1, kFromCull);
 }
 
 void Session::SetTileGroups(bool on) {
@@ -2249,7 +2218,7 @@ GhostmCullHit Session::CullRecord(bool frame, size_t h, const GhostmHit &hit, co
 const Session::ReadCullResult &Session::ReadCull(bool frame) {
   ReadCullResult &res = cull_[frame ? 1 : 0];
   if (res.valid) return res;
-  const std::vector<GhostmHitPath> &path = frame ? HitsFrame() : HitsBand();
+  const std::vector<GhostmHitPath> &path = ReadLevel(frame).rec;
   const std::vector<GhostmHit> &hits = Hits();
   const size_t n = hits.size();
   if (n > UINT32_MAX) throw Error("read cull: over 4 G hits");
@@ -2268,13 +2237,7 @@ const Session::ReadCullResult &Session::ReadCull(bool frame) {
   const DeviceTimes before = dev.times();
   dev.ReadCull((uint32_t)res.read_begin.size() - 1, res.read_begin.data(), (uint32_t)n, in.data(), cull_top_k_,
                cull_cover_pct_, res.out.data());
-  AddDeltas(cull_stats_, before, dev.times(), std::make_pair(&GhostmReadCullStats::seconds_cull, &DeviceTimes::cull),
-            std::make_pair(&GhostmReadCullStats::cull_launches, &DeviceTimes::cull_launches),
-            std::make_pair(&GhostmReadCullStats::cull_reads, &DeviceTimes::cull_reads),
-            std::make_pair(&GhostmReadCullStats::cull_hits, &DeviceTimes::cull_hits),
-            std::make_pair(&GhostmReadCullStats::cull_kept, &DeviceTimes::cull_kept),
-            std::make_pair(&GhostmReadCullStats::cull_dups, &DeviceTimes::cull_dups),
-            std::make_pair(&GhostmReadCullStats::cull_culled, &DeviceTimes::cull_culled));
+  AddStats(cull_stats_, StatsDelta(dev.times().cull, before.cull));
   res.valid = true;
   return res;
 }
@@ -2324,11 +2287,18 @@ void Session::FormatCull(bool frame) {
       out.append(num, (size_t)(p - num));
     }
   }
+  ReplaceText(&out);
+}
+
+// The text of a view that is not one line per hit (the culled lines, the taxon
+// lines, the pile-up lines) replaces the hit lines: it goes into the first
+// part's first piece, every other piece is emptied.
+void Session::ReplaceText(std::string *out) {
   bool placed = false;
   for (size_t k = 0; k < used_parts_; ++k)
     for (std::string &t : parts_[k].text) {
       t.clear();
-      if (!placed) t.swap(out), placed = true;
+      if (!placed) t.swap(*out), placed = true;
     }
   joined_valid_ = false;
 }
@@ -2372,8 +2342,8 @@ void Session::SetTaxonomy(uint32_t nnodes, const uint32_t *taxid, const uint32_t
   tax_.map_unmatched = map_unmatched;
   tax_.serial = dev.taxonomy_serial();
   tax_.set = true;
-  lca_[0].Drop();
-  lca_[1].Drop();
+  DropLevel(0, kFromLca);
+  DropLevel(1, kFromLca);
 }
 
 void Session::SetTaxonomyFiles(const std::string &nodes_path, const std::string &map_path) {
@@ -2426,8 +2396,8 @@ void Session::SetLca(uint32_t top_pct, uint32_t support_pct) {
   if (top_pct == lca_top_pct_ && support_pct == lca_support_pct_) return;
   lca_top_pct_ = top_pct;
   lca_support_pct_ = support_pct;
-  lca_[0].Drop();
-  lca_[1].Drop();
+  DropLevel(0, kFromLca);
+  DropLevel(1, kFromLca);
 }
 
 // The taxon of every read (ReadLca): the cull's reads and records, a KEPT hit
@@ -2437,7 +2407,7 @@ const Session::ReadLcaResult &Session::ReadLca(bool frame) {
   ReadLcaResult &res = lca_[frame ? 1 : 0];
   if (res.valid) return res;
   const ReadCullResult &cull = ReadCull(frame);
-  const std::vector<GhostmHitPath> &path = frame ? HitsFrame() : HitsBand();
+  const std::vector<GhostmHitPath> &path = ReadLevel(frame).rec;
   const std::vector<GhostmHit> &hits = Hits();
   const size_t n = hits.size();
   res.read_begin = cull.read_begin;
@@ -2463,14 +2433,12 @@ const Session::ReadLcaResult &Session::ReadLca(bool frame) {
   }
   const uint32_t nreads = (uint32_t)res.read_begin.size() - 1;
   res.out.assign(nreads, GhostmLcaOut{});
-  const DeviceTimes before = dev.times();
+  const GhostmReadLcaStats before = dev.times().lca;
   dev.ReadLca(nreads, begin.data(), (uint32_t)rec.size(), rec.data(), lca_top_pct_, lca_support_pct_, res.out.data());
-  AddDeltas(lca_stats_, before, dev.times(), std::make_pair(&GhostmReadLcaStats::seconds_lca, &DeviceTimes::lca),
-            std::make_pair(&GhostmReadLcaStats::lca_launches, &DeviceTimes::lca_launches),
-            std::make_pair(&GhostmReadLcaStats::lca_votes, &DeviceTimes::lca_votes),
-            std::make_pair(&GhostmReadLcaStats::lca_assigned, &DeviceTimes::lca_assigned));
-  lca_stats_.lca_reads += nreads;  // the session's reads and hits, not the compacted call's
-  lca_stats_.lca_hits += n;
+  GhostmReadLcaStats added = StatsDelta(dev.times().lca, before);
+  added.lca_reads = nreads;  // the session's reads and hits, not the compacted call's
+  added.lca_hits = n;
+  AddStats(lca_stats_, added);
   res.valid = true;
   return res;
 }
@@ -2493,13 +2461,7 @@ void Session::FormatLca(bool frame) {
     }
     out.push_back('\n');
   }
-  bool placed = false;
-  for (size_t k = 0; k < used_parts_; ++k)
-    for (std::string &t : parts_[k].text) {
-      t.clear();
-      if (!placed) t.swap(out), placed = true;
-    }
-  joined_valid_ = false;
+  ReplaceText(&out);
 }
 
 // A subject's residues: every subject of a chunk is followed by one END.
@@ -2509,7 +2471,7 @@ uint32_t Session::SubjectLength(const DbData &d, uint32_t subject) const {
 }
 
 const std::vector<GhostmHitPath> &Session::LevelPaths(PathLevel lv) {
-  return lv == kFrameLevel ? HitsFrame() : lv == kBandLevel ? HitsBand() : HitsPath();
+  return lv == kTileLevel ? HitsPath() : ReadLevel(lv == kFrameLevel).rec;
 }
 
 // One pile-up call on DB chunk di for the hits `items`: the hits by query chunk
@@ -2521,8 +2483,8 @@ void Session::PileupChunk(PathLevel lv, size_t di, const std::vector<size_t> &it
                           uint32_t *profile) {
   const bool tile = lv == kTileLevel, frame = lv == kFrameLevel;
   const std::vector<GhostmHitPath> &path = LevelPaths(lv);
-  const std::vector<uint32_t> &words = frame ? frame_ops_ : tile ? path_ops_ : band_ops_;
-  const std::vector<GhostmBandSource> &source = frame ? frame_src_ : band_src_;
+  const ReadLevelResult &lvl = level_[frame ? 1 : 0];  // made by LevelPaths; unused on the tile level
+  const std::vector<uint32_t> &words = tile ? path_ops_ : lvl.ops;
   const std::vector<GhostmHit> &hits = Hits();
   std::vector<std::vector<uint32_t>> qid(queries_.size());
   std::vector<std::vector<GhostmBandSource>> src(queries_.size());
@@ -2533,7 +2495,7 @@ void Session::PileupChunk(PathLevel lv, size_t di, const std::vector<size_t> &it
     p.s_start += pos;
     p.s_end += pos;
     if (tile) qid[hit_source_[h].qi].push_back(hit_source_[h].query);
-    else src[hit_source_[h].qi].push_back(source[h]);
+    else src[hit_source_[h].qi].push_back(lvl.src[h]);
     rec[hit_source_[h].qi].push_back(p);
   }
   std::vector<DeviceModule::PileupGroup> tile_groups;
@@ -2560,13 +2522,7 @@ void Session::PileupChunk(PathLevel lv, size_t di, const std::vector<size_t> &it
   }
   dev.ReadPileup(dbs_[di].dev, groups.data(), groups.size(), words.data(), words.size(), step, frame, p0, p1, depth,
                  identities, consensus, shifts, profile);
-  AddDeltas(read_pileup_stats_, before, dev.times(),
-            std::make_pair(&GhostmReadPileupStats::seconds_read_pileup, &DeviceTimes::read_pileup),
-            std::make_pair(&GhostmReadPileupStats::read_pileup_launches, &DeviceTimes::read_pileup_launches),
-            std::make_pair(&GhostmReadPileupStats::read_pileup_windows, &DeviceTimes::read_pileup_windows),
-            std::make_pair(&GhostmReadPileupStats::read_pileup_parts, &DeviceTimes::read_pileup_parts),
-            std::make_pair(&GhostmReadPileupStats::read_pileup_columns, &DeviceTimes::read_pileup_columns),
-            std::make_pair(&GhostmReadPileupStats::read_pileup_shifts, &DeviceTimes::read_pileup_shifts));
+  AddStats(read_pileup_stats_, StatsDelta(dev.times().read_pileup, before.read_pileup));
 }
 
 // The pile-up of one level's paths: every subject placed in db_id order, one
@@ -2716,13 +2672,7 @@ void Session::FormatPileup(PathLevel lv, bool consensus) {
       }
       out.push_back('\n');
     }
-  bool placed = false;
-  for (size_t k = 0; k < used_parts_; ++k)
-    for (std::string &t : parts_[k].text) {
-      t.clear();
-      if (!placed) t.swap(out), placed = true;
-    }
-  joined_valid_ = false;
+  ReplaceText(&out);
 }
 
 // -y 8 and -y 9, from the -y 7 text FormatPathTabular left in the pieces (one
@@ -2958,16 +2908,8 @@ void Session::DropResults() {
   row_bytes_.clear();
   row_bytes_.shrink_to_fit();
   hits_rows_valid_ = false;
-  hits_band_.clear();
-  band_letters_.clear();
-  band_ops_.clear();
-  band_src_.clear();
-  hits_band_valid_ = false;
-  read_rows_[0].Drop();
-  pileup_[kBandLevel].Drop();
-  cull_[0].Drop();
-  lca_[0].Drop();
-  DropFrameResults();
+  DropLevel(0);
+  DropLevel(1);
   pileup_subj_.clear();
   pileup_[kTileLevel].Drop();
 }

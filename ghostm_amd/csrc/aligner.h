@@ -247,8 +247,8 @@ class Session {
   // (HitsPath) in source coordinates; q_* are source coordinates, s_* relative
   // to the subject. Computed on first use, kept until the next run, query set,
   // database or SetBand.
-  const std::vector<GhostmHitPath> &HitsBand();
-  const std::vector<uint32_t> &BandOps();
+  const std::vector<GhostmHitPath> &HitsBand() { return ReadLevel(false).rec; }
+  const std::vector<uint32_t> &BandOps() { return ReadLevel(false).ops; }
   // the band's half-width, 1..31 (default 31); a change drops the band results
   void SetBand(uint32_t band);
   uint32_t Band() const { return band_; }
@@ -261,12 +261,29 @@ class Session {
   // anchor HitsBand's D; q_* are strand positions, s_* relative to the subject.
   // Throws on a set that is not a DNA set of a tiled setter. Computed on first
   // use, kept until the next run, query set, database, SetBand or SetFrameShift.
-  const std::vector<GhostmHitPath> &HitsFrame();
-  const std::vector<uint32_t> &FrameOps();
+  const std::vector<GhostmHitPath> &HitsFrame() { return ReadLevel(true).rec; }
+  const std::vector<uint32_t> &FrameOps() { return ReadLevel(true).ops; }
   const std::vector<GhostmHitFrameInfo> &FrameInfo();
   // the frameshift cost, -(1 << 20)..0 (default -15); a change drops the frame results
   void SetFrameShift(int shift);
   const GhostmFrameStats &FrameStats() const { return frame_stats_; }
+  // One level's read-level paths, band [0] or frame [1]: per hit its record,
+  // the words the records index, and the chunk-local source the pass aligned
+  // (src[h].letters is the m a read-level line is priced with). HitsBand(),
+  // HitsFrame() and every pass built on them read it through ReadLevel.
+  struct ReadLevelResult {
+    bool valid = false;
+    std::vector<GhostmHitPath> rec;
+    std::vector<uint32_t> ops;
+    std::vector<GhostmBandSource> src;
+    void Drop() {
+      rec.clear();
+      ops.clear();
+      src.clear();
+      valid = false;
+    }
+  };
+  const ReadLevelResult &ReadLevel(bool frame);
   // One GhostmHitReadRows per hit of Hits() and the row bytes they index, in
   // hit order, for the read-level paths of HitsBand() (frame false) or
   // HitsFrame() (frame true, with the session's frameshift cost): a post-pass
@@ -509,7 +526,7 @@ class Session {
   // the hit's read-level rows appended to the -y 12 / -y 13 line; a hit of
   // read-level score 0 takes the three fields from its tile rows (HitsRows).
   void FormatReadRows(bool frame);
-  // The chunk pairs' words of a path pass joined in hit order (HitsPath, HitsBand, HitsFrame)
+  // The chunk pairs' words of a path pass joined in hit order (HitsPath, ReadLevel)
   void JoinWords(const std::vector<std::vector<uint32_t>> &words, std::vector<GhostmHitPath> *path,
                  std::vector<uint32_t> *ops) const;
   // The plan HitsRows and HitsReadRows share: places in hit order, *bytes sized,
@@ -518,7 +535,7 @@ class Session {
   void RowsPlan(const std::vector<GhostmHitPath> &path, const std::vector<uint32_t> &words, std::vector<uint8_t> *bytes,
                 Call call);
   // The paths a pile-up is made from: the tile paths (HitsPath), the band paths
-  // (HitsBand) or the frame paths (HitsFrame); LevelPaths makes them.
+  // (ReadLevel(false)) or the frame paths (ReadLevel(true)); LevelPaths makes them.
   enum PathLevel { kTileLevel = 0, kBandLevel = 1, kFrameLevel = 2 };
   const std::vector<GhostmHitPath> &LevelPaths(PathLevel lv);
   // The pile-up of a level, kept in pileup_[lv]; Pileup() and ReadPileup() return it
@@ -547,6 +564,8 @@ class Session {
   // read order: qname, taxid, depth, votes, support, lca_taxid, candidates,
   // unmapped, best_score; replaces the parts' text as FormatPileup's does
   void FormatLca(bool frame);
+  // the common end of FormatPileup, FormatCull and FormatLca: *out (taken) becomes the parts' whole text
+  void ReplaceText(std::string *out);
   uint32_t SubjectLength(const DbData &d, uint32_t subject) const;
 
   AlignerOptions opt_;
@@ -584,11 +603,13 @@ class Session {
   std::vector<GhostmHitRows> hits_rows_;
   std::vector<uint8_t> row_bytes_;
   bool hits_rows_valid_ = false;
-  std::vector<GhostmHitPath> hits_band_;
-  std::vector<uint32_t> band_ops_, band_letters_;  // band_letters_: per hit, its source's letters m
-  bool hits_band_valid_ = false;
-  // per hit, the chunk-local sources HitsBand() / HitsFrame() aligned
-  std::vector<GhostmBandSource> band_src_, frame_src_;
+  ReadLevelResult level_[2];  // the band paths [0] and the frame paths [1]
+  std::vector<GhostmHitFrameInfo> frame_info_;  // beside level_[1]
+  // Drops a level's results from a stage on: its paths with the rows, the
+  // pile-up, the cull and the LCA made from them; or the cull and its LCA; or
+  // the LCA alone. A new per-level result joins this one list.
+  enum LevelStage { kFromPaths, kFromCull, kFromLca };
+  void DropLevel(int lv, LevelStage from = kFromPaths);
   // the read-level rows of the band paths [0] and of the frame paths [1]
   struct ReadRowsResult {
     std::vector<GhostmHitReadRows> rec;
@@ -608,13 +629,8 @@ class Session {
   bool tile_dna_ = false;   // ... whether its sources are DNA frames (tiles six records apart)
   GhostmBandStats band_stats_{};
   std::vector<uint32_t> tile_read_nt_;  // a tiled set's kept letters (nt for DNA) by source record
-  std::vector<GhostmHitPath> hits_frame_;
-  std::vector<uint32_t> frame_ops_;
-  std::vector<GhostmHitFrameInfo> frame_info_;
-  bool hits_frame_valid_ = false;
   int frame_shift_ = -15;
   GhostmFrameStats frame_stats_{};
-  void DropFrameResults();
   ReadPileupResult pileup_[3];                  // by PathLevel; the tile pile-up's shifts stay empty
   std::vector<GhostmSubjectPileup> pileup_subj_;  // pileup_[kTileLevel].subj as 40-byte records
   GhostmReadPileupStats read_pileup_stats_{};

@@ -16,10 +16,7 @@
 #include <string>
 #include <vector>
 
-struct GhostmHitExt;  // include/ghostm_hip.h
-struct GhostmHitPath;
-struct GhostmHitRows;
-struct GhostmStats;
+#include "../../include/ghostm_hip.h"
 
 namespace ghostm {
 
@@ -107,22 +104,13 @@ struct DeviceTimes {
   double pileup = 0;                              // the subject pile-up (k_pileup + k_pileup_finish): seconds,
   uint64_t pileup_launches = 0, pileup_windows = 0, pileup_parts = 0, pileup_columns = 0;  // k_pileup launches,
                                                   // profile windows, (tile, part) workgroups, columns added
-  double band = 0;                                // the read-level band pass (k_band_fill + k_band_walk + k_band_compact):
-  uint64_t band_launches = 0, band_hits = 0, band_cells = 0, band_dir_bytes = 0;  // seconds, batches, hits,
-                                                  // rows run x (2B + 1), direction bytes
-  double frame = 0;                               // the frame pass (k_frame_fill + k_frame_walk + k_frame_compact),
-  uint64_t frame_launches = 0, frame_hits = 0, frame_cells = 0, frame_dir_bytes = 0;  // counted as the band pass
-  double read_rows = 0;                           // the read-level rows (k_read_rows): seconds,
-  uint64_t read_rows_launches = 0, read_rows_hits = 0, read_rows_columns = 0;  // batches, hits, columns
-  double read_pileup = 0;                         // the read-level pile-up (k_read_pileup + k_pileup_finish<true>),
-  uint64_t read_pileup_launches = 0, read_pileup_windows = 0, read_pileup_parts = 0;  // counted as the pile-up;
-  uint64_t read_pileup_columns = 0, read_pileup_shifts = 0;  // '=', 'X', 'D' columns and shift columns charged
-  double cull = 0;                                // the read-level cull (k_read_cull): seconds, batches,
-  uint64_t cull_launches = 0, cull_reads = 0, cull_hits = 0;  // reads with a hit, hits,
-  uint64_t cull_kept = 0, cull_dups = 0, cull_culled = 0;     // and the hits by status
-  double lca = 0;                                  // the taxon per read (k_read_lca*): seconds, batches,
-  uint64_t lca_launches = 0, lca_reads = 0, lca_hits = 0;  // reads with a hit, their hits,
-  uint64_t lca_votes = 0, lca_assigned = 0;                // votes, reads with a node
+  // the read-level passes' counters as the public structs hand them out (include/ghostm_hip.h)
+  GhostmBandStats band{};                // k_band_fill + k_band_walk + k_band_compact
+  GhostmFrameStats frame{};              // k_frame_fill + k_frame_walk + k_frame_compact, counted as the band pass
+  GhostmReadRowsStats read_rows{};       // k_read_rows
+  GhostmReadPileupStats read_pileup{};   // k_read_pileup + k_pileup_finish<true>, counted as the pile-up
+  GhostmReadCullStats cull{};            // k_read_cull
+  GhostmReadLcaStats lca{};              // k_read_lca*
 };
 
 class DeviceModule {

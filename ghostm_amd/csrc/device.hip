@@ -23,6 +23,7 @@
 #include "kernels.h"
 #include "path_rows.h"
 #include "read_rows.h"
+#include "read_classes.h"
 #include "read_cull.h"
 #include "read_lca.h"
 #include "read_pileup.h"
@@ -293,15 +294,16 @@ struct DeviceModule::Impl {
   DevBuf read_rows_hit, read_rows_ops, read_rows_out, read_rows_buf;
   // PathPileup: a batch's hits, words, plan lists and parts; a window's profile and finished arrays; the column counter
   DevBuf pileup_hit, pileup_ops, pileup_list, pileup_part, pileup_prof, pileup_out, pileup_cols;
-  // ReadCull: a batch's hits, its read table with the class lists and table offsets, its tables, its records
-  DevBuf cull_hit, cull_meta, cull_scratch, cull_out;
-  // ReadLca: the taxonomy's words; a batch's hits, its read table with the class lists, counts and table offsets, its
-  // tables, its records
-  DevBuf lca_tax, lca_hit, lca_meta, lca_scratch, lca_out;
-  // BandAlign: a batch's slots, its offsets / maxima / records, its direction bytes, its word slots, their packed words
-  DevBuf band_hit, band_meta, band_dir, band_ops, band_cmp;
-  // FrameAlign: the same five of its own
-  DevBuf frame_hit, frame_meta, frame_dir, frame_ops, frame_cmp;
+  // ReadCull, ReadLca: a batch's hits, its meta words (read_classes.h), its tables, its records
+  struct ReadBufs {
+    DevBuf hit, meta, scratch, out;
+  } cull, lca;
+  DevBuf lca_tax;  // the taxonomy's words
+  // BandAlign [0], FrameAlign [1]: a batch's slots, its offsets / maxima / records, its direction bytes, its word
+  // slots, their packed words
+  struct PathBufs {
+    DevBuf hit, meta, dir, ops, cmp;
+  } read_level[2];
   DevBuf tb_width, tb_ncols, tb_skey, tb_key, tb_order1, tb_order2, tb_sort, tb_pair_a, tb_pair_b, tb_best;
   int cus = 256;
   // K4 work
@@ -2696,7 +2698,7 @@ size_t DeviceModule::ReadRows(DevQuery *q, DevDb *d, uint32_t n, const GhostmBan
   if (!why.empty()) throw Error("read rows: " + why);
   const RowsKind K{"read rows: rows_cap: the rows do not fit", "GHOSTM_READ_ROWS_SCRATCH_MB",
                    "GHOSTM_READ_ROWS_BATCH_HITS", I.read_rows_hit, I.read_rows_ops, I.read_rows_out, I.read_rows_buf, 8,
-                   times_.read_rows, times_.read_rows_launches};
+                   times_.read_rows.seconds_read_rows, times_.read_rows.read_rows_launches};
   return RowsPass<kern::ReadRowsHit, kern::ReadRowsArgs>(
       K, S(stream_), I.ev0, I.ev1, q->seq.as<uint8_t>(), d->Residues(), I.mat_raw.as<int>(), open, ext, n, columns, rec,
       ops, out != nullptr, rows, rows_cap, dst_off,
@@ -2714,8 +2716,8 @@ size_t DeviceModule::ReadRows(DevQuery *q, DevDb *d, uint32_t n, const GhostmBan
         else hipLaunchKernelGGL(kern::k_read_rows<false>, grid, block, 0, S(stream_), a);
       },
       [&](uint32_t m, size_t bytes) {
-        times_.read_rows_hits += m;
-        times_.read_rows_columns += bytes / 3;
+        times_.read_rows.read_rows_hits += m;
+        times_.read_rows.read_rows_columns += bytes / 3;
       },
       [&](uint32_t k, const uint32_t *c, uint64_t at) {
         out[k] = GhostmHitReadRows{ReadRowsFirstRecord(src[k], rec[k], q->L, step, frame) + record_base, columns[k], c[0],
@@ -2751,20 +2753,29 @@ void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32
   // every index the kernels will use, checked here: nothing is uploaded or launched for a refused call
   const std::string why = frame ? ValidateFrame(q->nseq, q->L, d->len, n, src, s_lo, s_hi, step, B, open, ext, shift)
                                 : ValidateBand(q->nseq, q->L, d->len, n, src, s_lo, s_hi, step, B, open, ext);
-  const std::string what = frame ? "frame align: " : "band align: ";
+  // what the level has of its own: the messages' prefix, its limits, a hit's rows run per codon row of BandRowRange,
+  // its direction bytes and word slot by those rows, and its counters
+  struct Level {
+    const char *what, *env_scratch_mb, *env_batch_hits;
+    uint32_t rows_per_codon;
+    size_t (*dir_bytes_of)(uint32_t rows, uint32_t B);
+    size_t (*ops_slot_of)(uint32_t rows, uint32_t B);
+    double &seconds;
+    uint64_t &launches, &hits, &cells, &dir_bytes;
+  };
+  GhostmBandStats &tb = times_.band;
+  GhostmFrameStats &tf = times_.frame;
+  const Level lv =
+      frame ? Level{"frame align: ", "GHOSTM_FRAME_SCRATCH_MB", "GHOSTM_FRAME_BATCH_HITS", 3, FrameDirBytes, FrameOpsSlot,
+                    tf.seconds_frame, tf.frame_launches, tf.frame_hits, tf.frame_cells, tf.frame_dir_bytes}
+            : Level{"band align: ", "GHOSTM_BAND_SCRATCH_MB", "GHOSTM_BAND_BATCH_HITS", 1, BandDirBytes, BandOpsSlot,
+                    tb.seconds_band, tb.band_launches, tb.band_hits, tb.band_cells, tb.band_dir_bytes};
+  const std::string what = lv.what;
   if (!why.empty()) throw Error(what + why);
-  DevBuf &b_hit = frame ? I.frame_hit : I.band_hit, &b_meta = frame ? I.frame_meta : I.band_meta;
-  DevBuf &b_dir = frame ? I.frame_dir : I.band_dir, &b_ops = frame ? I.frame_ops : I.band_ops;
-  DevBuf &b_cmp = frame ? I.frame_cmp : I.band_cmp;
-  // a hit's rows run (BandRowRange's codon rows three times in the frame pass), direction bytes and word slot
-  const auto Rows = [&](uint32_t codon_rows) { return frame ? 3 * codon_rows : codon_rows; };
-  const auto DirBytes = [&](uint32_t codon_rows) {
-    return frame ? FrameDirBytes(3 * codon_rows, B) : BandDirBytes(codon_rows, B);
-  };
-  const auto OpsSlot = [&](uint32_t codon_rows) {
-    return frame ? FrameOpsSlot(3 * codon_rows, B) : BandOpsSlot(codon_rows, B);
-  };
-  double &t_seconds = frame ? times_.frame : times_.band;
+  Impl::PathBufs &buf = I.read_level[frame];
+  const auto Rows = [&](uint32_t codon_rows) { return lv.rows_per_codon * codon_rows; };
+  const auto DirBytes = [&](uint32_t codon_rows) { return lv.dir_bytes_of(Rows(codon_rows), B); };
+  const auto OpsSlot = [&](uint32_t codon_rows) { return lv.ops_slot_of(Rows(codon_rows), B); };
   // every hit's rows and the launch order by them, a stable sort: hits of about equal rows share a block
   std::vector<BandRows> rows(n);
   std::vector<uint32_t> order(n);
@@ -2774,8 +2785,8 @@ void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32
   }
   std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return rows[x].rows < rows[y].rows; });
   const uint32_t stride = BandDirStride(B);
-  const size_t budget = EnvSize(frame ? "GHOSTM_FRAME_SCRATCH_MB" : "GHOSTM_BAND_SCRATCH_MB", 1024) << 20;
-  const size_t max_hits = EnvSize(frame ? "GHOSTM_FRAME_BATCH_HITS" : "GHOSTM_BAND_BATCH_HITS", SIZE_MAX);
+  const size_t budget = EnvSize(lv.env_scratch_mb, 1024) << 20;
+  const size_t max_hits = EnvSize(lv.env_batch_hits, SIZE_MAX);
   PackedWords pw(n, ops != nullptr);
   std::vector<uint32_t> h_rec;
   std::vector<kern::BandHit> hh;
@@ -2801,14 +2812,14 @@ void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32
       cells += (uint64_t)Rows(rows[k].rows) * (2 * B + 1);
     }
     // meta: ops_off[m], cmp_off[m] (u64), best[3m], rec[6m]
-    b_hit.Reserve((size_t)m * sizeof(kern::BandHit));
-    b_meta.Reserve((size_t)m * 16 + (size_t)m * 36);
-    b_dir.Reserve(std::max<size_t>(dir_bytes, 1));
-    b_ops.Reserve(std::max<size_t>(ops_words, 1) * 4);
-    unsigned long long *d_off = b_meta.as<unsigned long long>();
+    buf.hit.Reserve((size_t)m * sizeof(kern::BandHit));
+    buf.meta.Reserve((size_t)m * 16 + (size_t)m * 36);
+    buf.dir.Reserve(std::max<size_t>(dir_bytes, 1));
+    buf.ops.Reserve(std::max<size_t>(ops_words, 1) * 4);
+    unsigned long long *d_off = buf.meta.as<unsigned long long>();
     uint32_t *d_best = reinterpret_cast<uint32_t *>(d_off + 2 * (size_t)m);
     uint32_t *d_rec = d_best + 3 * (size_t)m;
-    HIP_CHECK(hipMemcpyAsync(b_hit.p, hh.data(), (size_t)m * sizeof(kern::BandHit), hipMemcpyHostToDevice, S(stream_)));
+    HIP_CHECK(hipMemcpyAsync(buf.hit.p, hh.data(), (size_t)m * sizeof(kern::BandHit), hipMemcpyHostToDevice, S(stream_)));
     HIP_CHECK(hipMemcpyAsync(d_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
     kern::BandArgs a{};
     a.qseq = q->seq.as<uint8_t>();
@@ -2816,16 +2827,16 @@ void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32
     a.step = step;
     a.db = d->Residues();
     a.mat = I.mat_raw.as<int>();
-    a.hit = b_hit.as<kern::BandHit>();
+    a.hit = buf.hit.as<kern::BandHit>();
     a.n = m;
     a.B = B;
     a.stride = stride;
     a.open = open;
     a.ext = ext;
-    a.dir = b_dir.as<uint8_t>();
+    a.dir = buf.dir.as<uint8_t>();
     a.best = d_best;
     a.ops_off = d_off;
-    a.ops = b_ops.as<uint32_t>();
+    a.ops = buf.ops.as<uint32_t>();
     a.rec = d_rec;
     const dim3 block(kern::kTbBlock);
     const dim3 wave_grid((m + kern::kTbBlock / 64 - 1) / (kern::kTbBlock / 64));  // one wave per slot
@@ -2844,19 +2855,19 @@ void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32
     h_rec.resize((size_t)m * 6);
     HIP_CHECK(hipMemcpyAsync(h_rec.data(), d_rec, (size_t)m * 24, hipMemcpyDeviceToHost, S(stream_)));
     HIP_CHECK(hipStreamSynchronize(S(stream_)));
-    t_seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-    (frame ? times_.frame_launches : times_.band_launches) += 1;
-    (frame ? times_.frame_hits : times_.band_hits) += m;
-    (frame ? times_.frame_cells : times_.band_cells) += cells;
-    (frame ? times_.frame_dir_bytes : times_.band_dir_bytes) += dir_bytes;
+    lv.seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+    lv.launches += 1;
+    lv.hits += m;
+    lv.cells += cells;
+    lv.dir_bytes += dir_bytes;
     const size_t packed = pw.Scan(m, order.data() + b0, h_rec.data(),
                                   [&](uint32_t hit) { return OpsSlot(rows[hit].rows); }, what, rec, off.data());
     // the batch packed on the device and brought back
     if (ops && packed) {
-      b_cmp.Reserve(packed * 4);
+      buf.cmp.Reserve(packed * 4);
       HIP_CHECK(hipMemcpyAsync(d_off + m, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
       a.cmp_off = d_off + m;
-      a.cmp = b_cmp.as<uint32_t>();
+      a.cmp = buf.cmp.as<uint32_t>();
       TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
         if (frame)
           hipLaunchKernelGGL(kern::k_frame_compact, wave_grid, block, 0, S(stream_), (kern::FrameArgs{a, shift}));
@@ -2865,7 +2876,7 @@ void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32
       });
       HIP_CHECK(hipMemcpyAsync(pw.batch_words.back().data(), a.cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
       HIP_CHECK(hipStreamSynchronize(S(stream_)));
-      t_seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+      lv.seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
     }
     b0 = b1;
   }
@@ -3063,8 +3074,9 @@ void DeviceModule::ReadPileup(DevDb *d, const ReadPileupGroup *groups, size_t ng
     if (why.empty()) why = ReadPileupSpans(d->len, G.n, G.rec, ops, &span[g]);
     if (!why.empty()) throw Error("read pileup: " + why);
   }
-  const PileupKind K{"read pileup: ", true, times_.read_pileup, times_.read_pileup_launches, times_.read_pileup_windows,
-                     times_.read_pileup_parts, times_.read_pileup_columns, &times_.read_pileup_shifts};
+  GhostmReadPileupStats &t = times_.read_pileup;
+  const PileupKind K{"read pileup: ", true, t.seconds_read_pileup, t.read_pileup_launches, t.read_pileup_windows,
+                     t.read_pileup_parts, t.read_pileup_columns, &t.read_pileup_shifts};
   PileupPass<kern::ReadPileupHit, kern::ReadPileupArgs>(
       K, *impl_, S(stream_), d, groups, ngroups, span, ops, p0, p1, depth, identities, consensus, shifts, profile,
       [&](const ReadPileupGroup &G, uint32_t k, size_t ops_off) {
@@ -3087,10 +3099,38 @@ static_assert(sizeof(kern::CullHit) == sizeof(GhostmCullHit) && sizeof(GhostmCul
 static_assert(sizeof(GhostmCullOut) == 16, "k_read_cull writes 4 words per hit");
 static_assert(kern::kCullArrays == kCullTableArrays, "read_cull.h sizes the tables");
 
+// One batch of a per-read pass (ReadCull, ReadLca) past its plan (read_classes.h): the
+// batch's hits and meta words go up, every class with a read is launched inside
+// one timed span by launch(class, its list on the device, its reads), called
+// once the buffers are in place, and the batch's records come back. Returns the
+// span's seconds.
+template <class Launch>
+static double ReadClassBatch(DeviceModule::Impl &I, DeviceModule::Impl::ReadBufs &buf, hipStream_t st,
+                             const ReadClassPlan &plan, const void *hit, size_t hit_bytes, void *out, size_t out_bytes,
+                             Launch launch) {
+  buf.hit.Reserve(hit_bytes);
+  buf.meta.Reserve(plan.meta.size() * 4);
+  buf.out.Reserve(out_bytes);
+  if (plan.table_words) buf.scratch.Reserve(plan.table_words * 4);
+  HIP_CHECK(hipMemcpyAsync(buf.hit.p, hit, hit_bytes, hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(buf.meta.p, plan.meta.data(), plan.meta.size() * 4, hipMemcpyHostToDevice, st));
+  TimedLaunch(I.ev0, I.ev1, st, [&] {
+    for (size_t c = 0; c < plan.list_len.size(); ++c) {
+      if (!plan.list_len[c]) continue;
+      launch((int)c, buf.meta.as<uint32_t>() + plan.list_at[c], (uint32_t)plan.list_len[c]);
+      HIP_CHECK(hipGetLastError());
+    }
+  });
+  HIP_CHECK(hipMemcpyAsync(out, buf.out.p, out_bytes, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  return ElapsedMs(I.ev0, I.ev1) * 1e-3;
+}
+
 // The cull of nreads reads (kern::k_read_cull; the contract is above ReadCullGpu
 // in include/ghostm_hip.h). The reads go in batches cut by their bytes (hits,
 // records and, for a read above kCullCap hits, its table); a batch's reads are
-// listed by size class and every class with a read is one launch.
+// listed by size class (wave, kCullMid, kCullCap, device memory) and every class
+// with a read is one launch.
 void DeviceModule::ReadCull(uint32_t nreads, const uint32_t *read_begin, uint32_t nhits, const GhostmCullHit *hit,
                             uint32_t top_k, uint32_t cover_pct, GhostmCullOut *out) {
   if (!impl_) throw Error("read cull: the device module is not bound to a device");
@@ -3101,83 +3141,52 @@ void DeviceModule::ReadCull(uint32_t nreads, const uint32_t *read_begin, uint32_
   if (!why.empty()) throw Error("read cull: " + why);
   const size_t budget = EnvSize("GHOSTM_CULL_SCRATCH_MB", 1024) << 20;
   const size_t max_reads = EnvSize("GHOSTM_CULL_BATCH_READS", SIZE_MAX);
-  const auto hits_of = [&](uint32_t r) { return read_begin[r + 1] - read_begin[r]; };
+  static const uint32_t kBounds[3] = {kern::kCullWave, kern::kCullMid, kern::kCullCap};
+  std::vector<uint32_t> nhit(nreads);  // a read's size: its hits
+  for (uint32_t r = 0; r < nreads; ++r) nhit[r] = read_begin[r + 1] - read_begin[r];
   const auto table_words = [&](uint32_t r) {
-    return hits_of(r) > kern::kCullCap ? (size_t)kCullTableArrays * CullPow2(hits_of(r)) : (size_t)0;
+    return nhit[r] > kern::kCullCap ? (size_t)kCullTableArrays * CullPow2(nhit[r]) : (size_t)0;
   };
-  std::vector<uint32_t> meta;  // read_begin[m + 1], the four lists, then (8-byte aligned) the table offsets
-  std::vector<unsigned long long> offs;
+  ReadClassPlan plan;
+  GhostmReadCullStats &t = times_.cull;
   for (uint32_t b0 = 0; b0 < nreads;) {
     size_t bytes = 0;
     const uint32_t b1 = CutBatch(b0, nreads, max_reads, budget,
-                                 [&](uint32_t r) { return (size_t)hits_of(r) * 40 + table_words(r) * 4 + 8; }, &bytes);
-    const uint32_t m = b1 - b0, h0 = read_begin[b0], nh = read_begin[b1] - h0;
+                                 [&](uint32_t r) { return (size_t)nhit[r] * 40 + table_words(r) * 4 + 8; }, &bytes);
+    const uint32_t m = b1 - b0, r0 = b0, h0 = read_begin[b0], nh = read_begin[b1] - h0;
     b0 = b1;
-    if (nh == 0) continue;
-    // the lists by class: wave, kCullMid, kCullCap, device memory
-    std::vector<uint32_t> list[4];
-    offs.clear();
-    size_t words = 0;
-    for (uint32_t r = 0; r < m; ++r) {
-      const uint32_t n = hits_of(b1 - m + r);
-      if (n == 0) continue;
-      list[n <= kern::kCullWave ? 0 : n <= kern::kCullMid ? 1 : n <= kern::kCullCap ? 2 : 3].push_back(r);
-      if (n > kern::kCullCap) {
-        offs.push_back(words);
-        words += table_words(b1 - m + r);
-      }
-    }
-    meta.assign(read_begin + (b1 - m), read_begin + b1 + 1);
-    size_t list_at[4];
-    for (int c = 0; c < 4; ++c) {
-      list_at[c] = meta.size();
-      meta.insert(meta.end(), list[c].begin(), list[c].end());
-    }
-    if (meta.size() & 1) meta.push_back(0);
-    const size_t offs_at = meta.size();
-    meta.resize(offs_at + 2 * offs.size());
-    if (!offs.empty()) memcpy(meta.data() + offs_at, offs.data(), offs.size() * 8);
-    I.cull_hit.Reserve((size_t)nh * sizeof(GhostmCullHit));
-    I.cull_meta.Reserve(meta.size() * 4);
-    I.cull_out.Reserve((size_t)nh * sizeof(GhostmCullOut));
-    if (words) I.cull_scratch.Reserve(words * 4);
+    plan.Build(read_begin + r0, m, nhit.data() + r0, kBounds, 3, false, [&](uint32_t r) { return table_words(r0 + r); });
+    if (!plan.launched) continue;
     hipStream_t st = S(stream_);
-    HIP_CHECK(hipMemcpyAsync(I.cull_hit.p, hit + h0, (size_t)nh * sizeof(GhostmCullHit), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(I.cull_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, st));
     kern::CullArgs a{};
-    a.hit = I.cull_hit.as<kern::CullHit>();
     a.hit_base = h0;
-    a.read_begin = I.cull_meta.as<uint32_t>();
     a.top_k = top_k;
     a.cover_pct = cover_pct;
-    a.scratch = I.cull_scratch.as<uint32_t>();
-    a.scratch_off = reinterpret_cast<const unsigned long long *>(I.cull_meta.as<uint32_t>() + offs_at);
-    a.out = I.cull_out.as<uint32_t>();
-    TimedLaunch(I.ev0, I.ev1, st, [&] {
-      for (int c = 0; c < 4; ++c) {
-        if (list[c].empty()) continue;
-        a.list = I.cull_meta.as<uint32_t>() + list_at[c];
-        a.nlist = (uint32_t)list[c].size();
-        const uint32_t per = c == 0 ? kern::kCullBlock / 64 : 1;
-        const dim3 grid((a.nlist + per - 1) / per), block(kern::kCullBlock);
-        if (c == 0) hipLaunchKernelGGL((kern::k_read_cull<kern::kCullWave, true, false>), grid, block, 0, st, a);
-        else if (c == 1) hipLaunchKernelGGL((kern::k_read_cull<kern::kCullMid, false, false>), grid, block, 0, st, a);
-        else if (c == 2) hipLaunchKernelGGL((kern::k_read_cull<kern::kCullCap, false, false>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((kern::k_read_cull<kern::kCullCap, false, true>), grid, block, 0, st, a);
-        HIP_CHECK(hipGetLastError());
-      }
-    });
-    HIP_CHECK(hipMemcpyAsync(out + h0, a.out, (size_t)nh * sizeof(GhostmCullOut), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    times_.cull += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-    times_.cull_launches += 1;
-    times_.cull_hits += nh;
-    for (uint32_t r = 0; r < m; ++r) times_.cull_reads += hits_of(b1 - m + r) != 0;
+    t.seconds_cull += ReadClassBatch(
+        I, I.cull, st, plan, hit + h0, (size_t)nh * sizeof(GhostmCullHit), out + h0, (size_t)nh * sizeof(GhostmCullOut),
+        [&](int c, const uint32_t *list, uint32_t nlist) {
+          a.hit = I.cull.hit.as<kern::CullHit>();
+          a.read_begin = I.cull.meta.as<uint32_t>();
+          a.scratch = I.cull.scratch.as<uint32_t>();
+          a.scratch_off = reinterpret_cast<const unsigned long long *>(I.cull.meta.as<uint32_t>() + plan.offs_at);
+          a.out = I.cull.out.as<uint32_t>();
+          a.list = list;
+          a.nlist = nlist;
+          const uint32_t per = c == 0 ? kern::kCullBlock / 64 : 1;
+          const dim3 grid((nlist + per - 1) / per), block(kern::kCullBlock);
+          if (c == 0) hipLaunchKernelGGL((kern::k_read_cull<kern::kCullWave, true, false>), grid, block, 0, st, a);
+          else if (c == 1) hipLaunchKernelGGL((kern::k_read_cull<kern::kCullMid, false, false>), grid, block, 0, st, a);
+          else if (c == 2) hipLaunchKernelGGL((kern::k_read_cull<kern::kCullCap, false, false>), grid, block, 0, st, a);
+          else hipLaunchKernelGGL((kern::k_read_cull<kern::kCullCap, false, true>), grid, block, 0, st, a);
+        });
+    t.cull_launches += 1;
+    t.cull_hits += nh;
+    t.cull_reads += plan.launched;
     for (uint32_t k = 0; k < nh; ++k) {
       const uint32_t s = out[h0 + k].status;
-      times_.cull_kept += s == GHOSTM_CULL_KEPT;
-      times_.cull_dups += s == GHOSTM_CULL_DUP;
-      times_.cull_culled += s == GHOSTM_CULL_CULLED;
+      t.cull_kept += s == GHOSTM_CULL_KEPT;
+      t.cull_dups += s == GHOSTM_CULL_DUP;
+      t.cull_culled += s == GHOSTM_CULL_CULLED;
     }
   }
 }
@@ -3215,25 +3224,27 @@ void DeviceModule::DropTaxonomy() {
 // contract is above ReadLcaGpu in include/ghostm_hip.h). The reads go in
 // batches cut by their bytes (hits, the record and, for a read above kLcaCap
 // candidates, its table); a batch's reads with a candidate are listed by size
-// class and every class with a read is one launch. A read without a candidate
-// gets its record here.
+// class (wave, LDS, device memory), each list followed by its reads' candidate
+// counts, and every class with a read is one launch. A read without a
+// candidate gets its record here.
 void DeviceModule::ReadLca(uint32_t nreads, const uint32_t *read_begin, uint32_t nhits, const GhostmLcaHit *hit,
                            uint32_t top_pct, uint32_t support_pct, GhostmLcaOut *out) {
   if (!impl_) throw Error("read lca: the device module is not bound to a device");
   Use();
   Impl &I = *impl_;
-  std::vector<uint32_t> ncand;
+  std::vector<uint32_t> ncand;  // a read's size: its candidates
   std::string why = ValidateReadLca(tax_nodes_, nreads, read_begin, nhits, hit, top_pct, support_pct, &ncand);
   if (why.empty() && !out && nreads) why = "null: out";
   if (!why.empty()) throw Error("read lca: " + why);
   const size_t budget = EnvSize("GHOSTM_LCA_SCRATCH_MB", 1024) << 20;
   const size_t max_reads = EnvSize("GHOSTM_LCA_BATCH_READS", SIZE_MAX);
+  static const uint32_t kBounds[2] = {kLcaWave, kLcaCap};
   const auto hits_of = [&](uint32_t r) { return read_begin[r + 1] - read_begin[r]; };
   const auto table_words = [&](uint32_t r) {
     return ncand[r] > kLcaCap ? (size_t)kLcaTableArrays * LcaPow2(ncand[r]) : (size_t)0;
   };
-  std::vector<uint32_t> meta;  // read_begin[m + 1], per class the list and its counts, then (8-byte aligned) the offsets
-  std::vector<unsigned long long> offs;
+  ReadClassPlan plan;
+  GhostmReadLcaStats &t = times_.lca;
   std::vector<GhostmLcaOut> got;  // a batch's records as read back
   for (uint32_t b0 = 0; b0 < nreads;) {
     size_t bytes = 0;
@@ -3241,82 +3252,48 @@ void DeviceModule::ReadLca(uint32_t nreads, const uint32_t *read_begin, uint32_t
                                  [&](uint32_t r) { return (size_t)hits_of(r) * 16 + table_words(r) * 4 + 48; }, &bytes);
     const uint32_t m = b1 - b0, r0 = b0, h0 = read_begin[b0], nh = read_begin[b1] - h0;
     b0 = b1;
-    // the lists by class: wave, LDS, device memory
-    std::vector<uint32_t> list[3];
-    offs.clear();
-    size_t words = 0;
     for (uint32_t r = 0; r < m; ++r) {
-      const uint32_t c = ncand[r0 + r];
-      times_.lca_reads += hits_of(r0 + r) != 0;
-      if (c == 0) {
-        out[r0 + r] = LcaNoVote(0, 0, 0);
-        continue;
-      }
-      list[c <= kLcaWave ? 0 : c <= kLcaCap ? 1 : 2].push_back(r);
-      if (c > kLcaCap) {
-        offs.push_back(words);
-        words += table_words(r0 + r);
-      }
+      t.lca_reads += hits_of(r0 + r) != 0;
+      if (ncand[r0 + r] == 0) out[r0 + r] = LcaNoVote(0, 0, 0);
     }
-    times_.lca_hits += nh;
-    if (list[0].empty() && list[1].empty() && list[2].empty()) continue;
-    meta.assign(read_begin + r0, read_begin + b1 + 1);
-    size_t list_at[3];
-    for (int c = 0; c < 3; ++c) {
-      list_at[c] = meta.size();
-      meta.insert(meta.end(), list[c].begin(), list[c].end());
-      for (uint32_t r : list[c]) meta.push_back(ncand[r0 + r]);
-    }
-    if (meta.size() & 1) meta.push_back(0);
-    const size_t offs_at = meta.size();
-    meta.resize(offs_at + 2 * offs.size());
-    if (!offs.empty()) memcpy(meta.data() + offs_at, offs.data(), offs.size() * 8);
-    I.lca_hit.Reserve((size_t)nh * sizeof(GhostmLcaHit));
-    I.lca_meta.Reserve(meta.size() * 4);
-    I.lca_out.Reserve((size_t)m * sizeof(GhostmLcaOut));
-    if (words) I.lca_scratch.Reserve(words * 4);
+    t.lca_hits += nh;
+    plan.Build(read_begin + r0, m, ncand.data() + r0, kBounds, 2, true, [&](uint32_t r) { return table_words(r0 + r); });
+    if (!plan.launched) continue;
     hipStream_t st = S(stream_);
-    HIP_CHECK(hipMemcpyAsync(I.lca_hit.p, hit + h0, (size_t)nh * sizeof(GhostmLcaHit), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(I.lca_meta.p, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, st));
     kern::LcaArgs a{};
-    a.hit = I.lca_hit.as<kern::LcaHit>();
     a.hit_base = h0;
-    a.read_begin = I.lca_meta.as<uint32_t>();
-    a.tax = I.lca_tax.as<uint32_t>();
     a.nnodes = tax_nodes_;
     a.top_pct = top_pct;
     a.support_pct = support_pct;
-    a.scratch = I.lca_scratch.as<uint32_t>();
-    a.scratch_off = reinterpret_cast<const unsigned long long *>(I.lca_meta.as<uint32_t>() + offs_at);
-    a.out = I.lca_out.as<uint32_t>();
-    TimedLaunch(I.ev0, I.ev1, st, [&] {
-      for (int c = 0; c < 3; ++c) {
-        if (list[c].empty()) continue;
-        a.list = I.lca_meta.as<uint32_t>() + list_at[c];
-        a.nlist = (uint32_t)list[c].size();
-        a.ncand = a.list + a.nlist;
-        if (c == 0) {
-          const uint32_t per = kern::kLcaWaveBlock / 64;
-          hipLaunchKernelGGL(kern::k_read_lca_wave, dim3((a.nlist + per - 1) / per), dim3(kern::kLcaWaveBlock), 0, st, a);
-        } else if (c == 1) {
-          hipLaunchKernelGGL(kern::k_read_lca<false>, dim3(a.nlist), dim3(kern::kLcaBlock), 0, st, a);
-        } else {
-          hipLaunchKernelGGL(kern::k_read_lca<true>, dim3(a.nlist), dim3(kern::kLcaBlock), 0, st, a);
-        }
-        HIP_CHECK(hipGetLastError());
-      }
-    });
     got.resize(m);
-    HIP_CHECK(hipMemcpyAsync(got.data(), a.out, (size_t)m * sizeof(GhostmLcaOut), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    times_.lca += ElapsedMs(I.ev0, I.ev1) * 1e-3;
-    times_.lca_launches += 1;
-    for (int c = 0; c < 3; ++c)
-      for (uint32_t r : list[c]) {
-        out[r0 + r] = got[r];
-        times_.lca_votes += got[r].votes;
-        times_.lca_assigned += got[r].node != kLcaNone;
-      }
+    t.seconds_lca += ReadClassBatch(
+        I, I.lca, st, plan, hit + h0, (size_t)nh * sizeof(GhostmLcaHit), got.data(), (size_t)m * sizeof(GhostmLcaOut),
+        [&](int c, const uint32_t *list, uint32_t nlist) {
+          a.hit = I.lca.hit.as<kern::LcaHit>();
+          a.read_begin = I.lca.meta.as<uint32_t>();
+          a.tax = I.lca_tax.as<uint32_t>();
+          a.scratch = I.lca.scratch.as<uint32_t>();
+          a.scratch_off = reinterpret_cast<const unsigned long long *>(I.lca.meta.as<uint32_t>() + plan.offs_at);
+          a.out = I.lca.out.as<uint32_t>();
+          a.list = list;
+          a.nlist = nlist;
+          a.ncand = list + nlist;
+          if (c == 0) {
+            const uint32_t per = kern::kLcaWaveBlock / 64;
+            hipLaunchKernelGGL(kern::k_read_lca_wave, dim3((nlist + per - 1) / per), dim3(kern::kLcaWaveBlock), 0, st, a);
+          } else if (c == 1) {
+            hipLaunchKernelGGL(kern::k_read_lca<false>, dim3(nlist), dim3(kern::kLcaBlock), 0, st, a);
+          } else {
+            hipLaunchKernelGGL(kern::k_read_lca<true>, dim3(nlist), dim3(kern::kLcaBlock), 0, st, a);
+          }
+        });
+    t.lca_launches += 1;
+    for (uint32_t r = 0; r < m; ++r) {
+      if (ncand[r0 + r] == 0) continue;
+      out[r0 + r] = got[r];
+      t.lca_votes += got[r].votes;
+      t.lca_assigned += got[r].node != kLcaNone;
+    }
   }
 }
 
@@ -3399,6 +3376,69 @@ RefState &Ref() {
 }
 
 void SetError(const std::string &m) { g_last_error = m; }
+
+// A pass's counters behind the stage-level calls (GhostmStageBandStats' conventions)
+template <class Stats>
+size_t StageStats(Stats DeviceTimes::*field, Stats *stats, size_t size) {
+  if (!stats) return 0;
+  RefState &r = Ref();
+  std::lock_guard<std::mutex> lk(r.mu);
+  std::memcpy(stats, &(DeviceModule::Get().times().*field), std::min(size, sizeof(Stats)));
+  return sizeof(Stats);
+}
+
+// BandAlignGpu (frame false, shift_cost unused) and FrameAlignGpu; name: the call's, for its messages
+int ReadLevelAlignGpu(const char *name, bool frame, uint32_t nhits, const GhostmBandSource src[], const int32_t diagonal[],
+                      const uint32_t s_lo[], const uint32_t s_hi[], uint32_t query_sequence_length, uint32_t step,
+                      uint32_t band, int open_gap, int extend_gap, int shift_cost, GhostmHitPath rec[], uint32_t ops[],
+                      size_t ops_cap, size_t *ops_used) {
+  const std::string what = name;
+  try {
+    if (!ops_used) throw Error(what + ": null: ops_used");
+    if (nhits && (!src || !diagonal || !s_lo || !s_hi)) throw Error(what + ": null: an input array");
+    if (nhits == 0) {
+      *ops_used = 0;
+      return 0;
+    }
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    if (!r.query || !r.db) throw Error("SetQueryGpu/SetDbGpu not called");
+    if (query_sequence_length != r.query->L) throw Error(what + ": source: query shape differs from SetQueryGpu");
+    std::vector<GhostmHitPath> out(nhits);
+    std::vector<uint32_t> words;
+    DeviceModule &m = DeviceModule::Get();
+    if (frame)
+      m.FrameAlign(r.query, r.db, nhits, src, diagonal, s_lo, s_hi, step, band, open_gap, extend_gap, shift_cost,
+                   out.data(), &words);
+    else
+      m.BandAlign(r.query, r.db, nhits, src, diagonal, s_lo, s_hi, step, band, open_gap, extend_gap, out.data(), &words);
+    if (ops && words.size() > ops_cap) throw Error(what + ": ops_cap: the operations do not fit");
+    if (rec) std::copy(out.begin(), out.end(), rec);
+    if (ops) std::copy(words.begin(), words.end(), ops);
+    *ops_used = words.size();
+    return 0;
+  } catch (std::exception &e) {
+    SetError(e.what());
+    return 1;
+  }
+}
+
+// A stage call that needs no resident chunk (ReadCullGpu, SetTaxonomyGpu, ReadLcaGpu): under the lock, on the first
+// device when no SetOptionGpu bound one, call(module); an error's text after the call's name
+template <class Call>
+int UnboundStageCall(const char *name, Call call) {
+  try {
+    RefState &r = Ref();
+    std::lock_guard<std::mutex> lk(r.mu);
+    DeviceModule &m = DeviceModule::Get();
+    if (m.device() < 0) m.Bind(0);
+    call(m);
+    return 0;
+  } catch (std::exception &e) {
+    SetError(std::string(name) + ": " + e.what());
+    return 1;
+  }
+}
 
 }  // namespace
 
@@ -3761,80 +3801,24 @@ int PathRowsGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPath 
 int BandAlignGpu(uint32_t nhits, const GhostmBandSource src[], const int32_t diagonal[], const uint32_t s_lo[],
                  const uint32_t s_hi[], uint32_t query_sequence_length, uint32_t step, uint32_t band, int open_gap,
                  int extend_gap, GhostmHitPath rec[], uint32_t ops[], size_t ops_cap, size_t *ops_used) {
-  try {
-    if (!ops_used) throw Error("BandAlignGpu: null: ops_used");
-    if (nhits && (!src || !diagonal || !s_lo || !s_hi)) throw Error("BandAlignGpu: null: an input array");
-    if (nhits == 0) {
-      *ops_used = 0;
-      return 0;
-    }
-    RefState &r = Ref();
-    std::lock_guard<std::mutex> lk(r.mu);
-    if (!r.query || !r.db) throw Error("SetQueryGpu/SetDbGpu not called");
-    if (query_sequence_length != r.query->L) throw Error("BandAlignGpu: source: query shape differs from SetQueryGpu");
-    std::vector<GhostmHitPath> out(nhits);
-    std::vector<uint32_t> words;
-    DeviceModule::Get().BandAlign(r.query, r.db, nhits, src, diagonal, s_lo, s_hi, step, band, open_gap, extend_gap,
-                                  out.data(), &words);
-    if (ops && words.size() > ops_cap) throw Error("BandAlignGpu: ops_cap: the operations do not fit");
-    if (rec) std::copy(out.begin(), out.end(), rec);
-    if (ops) std::copy(words.begin(), words.end(), ops);
-    *ops_used = words.size();
-    return 0;
-  } catch (std::exception &e) {
-    SetError(e.what());
-    return 1;
-  }
+  return ReadLevelAlignGpu("BandAlignGpu", false, nhits, src, diagonal, s_lo, s_hi, query_sequence_length, step, band,
+                           open_gap, extend_gap, 0, rec, ops, ops_cap, ops_used);
 }
 
 size_t GhostmStageBandStats(GhostmBandStats *stats, size_t size) {
-  if (!stats) return 0;
-  RefState &r = Ref();
-  std::lock_guard<std::mutex> lk(r.mu);
-  const DeviceTimes &dt = DeviceModule::Get().times();
-  const GhostmBandStats st{dt.band, dt.band_launches, dt.band_hits, dt.band_cells, dt.band_dir_bytes};
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmBandStats)));
-  return sizeof(GhostmBandStats);
+  return StageStats(&DeviceTimes::band, stats, size);
 }
 
 int FrameAlignGpu(uint32_t nhits, const GhostmBandSource src[], const int32_t diagonal[], const uint32_t s_lo[],
                   const uint32_t s_hi[], uint32_t query_sequence_length, uint32_t step, uint32_t band, int open_gap,
                   int extend_gap, int shift_cost, GhostmHitPath rec[], uint32_t ops[], size_t ops_cap,
                   size_t *ops_used) {
-  try {
-    if (!ops_used) throw Error("FrameAlignGpu: null: ops_used");
-    if (nhits && (!src || !diagonal || !s_lo || !s_hi)) throw Error("FrameAlignGpu: null: an input array");
-    if (nhits == 0) {
-      *ops_used = 0;
-      return 0;
-    }
-    RefState &r = Ref();
-    std::lock_guard<std::mutex> lk(r.mu);
-    if (!r.query || !r.db) throw Error("SetQueryGpu/SetDbGpu not called");
-    if (query_sequence_length != r.query->L) throw Error("FrameAlignGpu: source: query shape differs from SetQueryGpu");
-    std::vector<GhostmHitPath> out(nhits);
-    std::vector<uint32_t> words;
-    DeviceModule::Get().FrameAlign(r.query, r.db, nhits, src, diagonal, s_lo, s_hi, step, band, open_gap, extend_gap,
-                                   shift_cost, out.data(), &words);
-    if (ops && words.size() > ops_cap) throw Error("FrameAlignGpu: ops_cap: the operations do not fit");
-    if (rec) std::copy(out.begin(), out.end(), rec);
-    if (ops) std::copy(words.begin(), words.end(), ops);
-    *ops_used = words.size();
-    return 0;
-  } catch (std::exception &e) {
-    SetError(e.what());
-    return 1;
-  }
+  return ReadLevelAlignGpu("FrameAlignGpu", true, nhits, src, diagonal, s_lo, s_hi, query_sequence_length, step, band,
+                           open_gap, extend_gap, shift_cost, rec, ops, ops_cap, ops_used);
 }
 
 size_t GhostmStageFrameStats(GhostmFrameStats *stats, size_t size) {
-  if (!stats) return 0;
-  RefState &r = Ref();
-  std::lock_guard<std::mutex> lk(r.mu);
-  const DeviceTimes &dt = DeviceModule::Get().times();
-  const GhostmFrameStats st{dt.frame, dt.frame_launches, dt.frame_hits, dt.frame_cells, dt.frame_dir_bytes};
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmFrameStats)));
-  return sizeof(GhostmFrameStats);
+  return StageStats(&DeviceTimes::frame, stats, size);
 }
 
 int ReadRowsGpu(uint32_t nhits, const GhostmBandSource src[], const GhostmHitPath rec[], const uint32_t ops[],
@@ -3861,13 +3845,7 @@ int ReadRowsGpu(uint32_t nhits, const GhostmBandSource src[], const GhostmHitPat
 }
 
 size_t GhostmStageReadRowsStats(GhostmReadRowsStats *stats, size_t size) {
-  if (!stats) return 0;
-  RefState &r = Ref();
-  std::lock_guard<std::mutex> lk(r.mu);
-  const DeviceTimes &dt = DeviceModule::Get().times();
-  const GhostmReadRowsStats st{dt.read_rows, dt.read_rows_launches, dt.read_rows_hits, dt.read_rows_columns};
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadRowsStats)));
-  return sizeof(GhostmReadRowsStats);
+  return StageStats(&DeviceTimes::read_rows, stats, size);
 }
 
 int PathPileupGpu(uint32_t nhits, const uint32_t query_ids[], const GhostmHitPath rec[], const uint32_t ops[],
@@ -3912,79 +3890,29 @@ int ReadPileupGpu(uint32_t nhits, const GhostmBandSource src[], const GhostmHitP
 }
 
 size_t GhostmStageReadPileupStats(GhostmReadPileupStats *stats, size_t size) {
-  if (!stats) return 0;
-  RefState &r = Ref();
-  std::lock_guard<std::mutex> lk(r.mu);
-  const DeviceTimes &dt = DeviceModule::Get().times();
-  const GhostmReadPileupStats st{dt.read_pileup,       dt.read_pileup_launches, dt.read_pileup_windows,
-                                 dt.read_pileup_parts, dt.read_pileup_columns,  dt.read_pileup_shifts};
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadPileupStats)));
-  return sizeof(GhostmReadPileupStats);
+  return StageStats(&DeviceTimes::read_pileup, stats, size);
 }
 
 int ReadCullGpu(uint32_t nreads, const uint32_t read_begin[], uint32_t nhits, const GhostmCullHit hit[],
                 uint32_t top_k, uint32_t cover_pct, GhostmCullOut out[]) {
-  try {
-    RefState &r = Ref();
-    std::lock_guard<std::mutex> lk(r.mu);
-    DeviceModule &m = DeviceModule::Get();
-    if (m.device() < 0) m.Bind(0);  // no SetOptionGpu yet: the first device
-    m.ReadCull(nreads, read_begin, nhits, hit, top_k, cover_pct, out);
-    return 0;
-  } catch (std::exception &e) {
-    SetError(std::string("ReadCullGpu: ") + e.what());
-    return 1;
-  }
+  return UnboundStageCall("ReadCullGpu", [&](DeviceModule &m) { m.ReadCull(nreads, read_begin, nhits, hit, top_k, cover_pct, out); });
 }
 
 size_t GhostmStageReadCullStats(GhostmReadCullStats *stats, size_t size) {
-  if (!stats) return 0;
-  RefState &r = Ref();
-  std::lock_guard<std::mutex> lk(r.mu);
-  const DeviceTimes &dt = DeviceModule::Get().times();
-  const GhostmReadCullStats st{dt.cull,      dt.cull_launches, dt.cull_reads, dt.cull_hits,
-                               dt.cull_kept, dt.cull_dups,     dt.cull_culled};
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadCullStats)));
-  return sizeof(GhostmReadCullStats);
+  return StageStats(&DeviceTimes::cull, stats, size);
 }
 
 int SetTaxonomyGpu(uint32_t nnodes, const uint32_t parent[]) {
-  try {
-    RefState &r = Ref();
-    std::lock_guard<std::mutex> lk(r.mu);
-    DeviceModule &m = DeviceModule::Get();
-    if (m.device() < 0) m.Bind(0);  // no SetOptionGpu yet: the first device
-    m.SetTaxonomy(nnodes, parent);
-    return 0;
-  } catch (std::exception &e) {
-    SetError(std::string("SetTaxonomyGpu: ") + e.what());
-    return 1;
-  }
+  return UnboundStageCall("SetTaxonomyGpu", [&](DeviceModule &m) { m.SetTaxonomy(nnodes, parent); });
 }
 
 int ReadLcaGpu(uint32_t nreads, const uint32_t read_begin[], uint32_t nhits, const GhostmLcaHit hit[],
                uint32_t top_pct, uint32_t support_pct, GhostmLcaOut out[]) {
-  try {
-    RefState &r = Ref();
-    std::lock_guard<std::mutex> lk(r.mu);
-    DeviceModule &m = DeviceModule::Get();
-    if (m.device() < 0) m.Bind(0);  // no SetOptionGpu yet: the first device
-    m.ReadLca(nreads, read_begin, nhits, hit, top_pct, support_pct, out);
-    return 0;
-  } catch (std::exception &e) {
-    SetError(std::string("ReadLcaGpu: ") + e.what());
-    return 1;
-  }
+  return UnboundStageCall("ReadLcaGpu", [&](DeviceModule &m) { m.ReadLca(nreads, read_begin, nhits, hit, top_pct, support_pct, out); });
 }
 
 size_t GhostmStageReadLcaStats(GhostmReadLcaStats *stats, size_t size) {
-  if (!stats) return 0;
-  RefState &r = Ref();
-  std::lock_guard<std::mutex> lk(r.mu);
-  const DeviceTimes &dt = DeviceModule::Get().times();
-  const GhostmReadLcaStats st{dt.lca, dt.lca_launches, dt.lca_reads, dt.lca_hits, dt.lca_votes, dt.lca_assigned};
-  std::memcpy(stats, &st, std::min(size, sizeof(GhostmReadLcaStats)));
-  return sizeof(GhostmReadLcaStats);
+  return StageStats(&DeviceTimes::lca, stats, size);
 }
 
 }  // extern "C"
