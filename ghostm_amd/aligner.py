@@ -638,6 +638,63 @@ def stage_read_lca_stats() -> dict:
     return {n: getattr(st, n) for n, _ in st._fields_}
 
 
+# GhostmTaxonCount (include/ghostm_hip.h)
+TAXON_COUNT_DTYPE = np.dtype([("node", "<u4"), ("clade_reads", "<u4"), ("direct_reads", "<u4"), ("kept_reads", "<u4")])
+
+
+def _taxon_profile(call, name, nreads, node, min_reads, cap, with_final):
+    """One profile call: the count first (cap 0, out NULL) unless cap is given,
+    then the records. Returns (records, final nodes or None, summary dict)."""
+    lib = native.load()
+    min_reads = int(min_reads)
+    if not 0 <= min_reads <= 0xFFFFFFFF:
+        raise GhostmError(f"{name}: param: min_reads {min_reads} outside 1..2^32 - 1")
+    nodep = node.ctypes.data_as(_U32P) if nreads else None
+    nout = ctypes.c_size_t(0)
+    if cap is None:
+        if call(nreads, nodep, min_reads, 0, None, ctypes.byref(nout), None, None) != 0:
+            raise GhostmError(native.last_error())
+        cap = nout.value
+    out = np.zeros(cap, dtype=TAXON_COUNT_DTYPE)
+    final = np.zeros(nreads, dtype=np.uint32) if with_final else None
+    summary = native.GhostmTaxonSummary()
+    # a cap of 0 with a null out only counts: hand over a record's room then
+    room = out if cap else np.zeros(1, dtype=TAXON_COUNT_DTYPE)
+    if call(nreads, nodep, min_reads, cap, room.ctypes.data_as(ctypes.POINTER(native.GhostmTaxonCount)), ctypes.byref(nout),
+            final.ctypes.data_as(_U32P) if with_final and nreads else None, ctypes.byref(summary)) != 0:
+        raise GhostmError(native.last_error())
+    return out[:nout.value], final, {n: getattr(summary, n) for n, _ in summary._fields_}
+
+
+def taxon_profile_host(parent, node, min_reads=1, cap=None, with_final=True):
+    """The host model of a sample's taxon profile (GhostmTaxonProfileHost; no
+    device) over the taxonomy `parent`: node[r] is read r's node index or
+    0xFFFFFFFF. Returns (TAXON_COUNT_DTYPE records in ascending node index,
+    every read's final node, the summary as a dict). cap None asks for the
+    count first; a cap below the count is refused with "cap"."""
+    par = np.ascontiguousarray(parent, dtype=np.uint32).reshape(-1)
+    nd = np.ascontiguousarray(node, dtype=np.uint32).reshape(-1)
+    fn = native.load().GhostmTaxonProfileHost
+    parp = par.ctypes.data_as(_U32P) if len(par) else None
+    return _taxon_profile(lambda *a: fn(len(par), parp, *a), "taxon profile", len(nd), nd, min_reads, cap, with_final)
+
+
+def taxon_profile(node, min_reads=1, cap=None, with_final=True):
+    """TaxonProfileGpu (k_taxon_count, k_taxon_climb, k_taxon_floor,
+    k_taxon_final, k_taxon_sort_*, k_taxon_emit) over the taxonomy of set_taxonomy_gpu();
+    arguments and result as taxon_profile_host. Needs no resident chunk."""
+    nd = np.ascontiguousarray(node, dtype=np.uint32).reshape(-1)
+    return _taxon_profile(native.load().TaxonProfileGpu, "taxon profile", len(nd), nd, min_reads, cap, with_final)
+
+
+def stage_taxon_profile_stats() -> dict:
+    """The profile's counters behind the stage-level calls (GhostmStageTaxonProfileStats)."""
+    lib = native.load()
+    st = native.GhostmTaxonProfileStats()
+    lib.GhostmStageTaxonProfileStats(ctypes.byref(st), ctypes.sizeof(st))
+    return {n: getattr(st, n) for n, _ in st._fields_}
+
+
 class Aligner:
     """reference class Aligner (aligner.h:63-92): Execute(argc, argv)."""
 
@@ -1278,6 +1335,47 @@ class Session:
         """The assignment's counters since the last run (GhostmSessionReadLcaStats)."""
         st = native.GhostmReadLcaStats()
         native.load().GhostmSessionReadLcaStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    def set_profile(self, min_reads: int = 1) -> None:
+        """taxon_profile()'s floor (GhostmSessionSetProfile): a clade with fewer
+        reads hands them to its first ancestor with min_reads. A change drops
+        only the profile; the assignment under it stays."""
+        m = int(min_reads)
+        if not 1 <= m <= 0xFFFFFFFF:  # an int beyond uint32 would wrap
+            raise GhostmError(f"profile: param: min_reads {m} outside 1..2^32 - 1")
+        if native.load().GhostmSessionSetProfile(self._h, m) != 0:
+            raise GhostmError(native.last_error())
+
+    def taxon_profile(self, frame: bool = False):
+        """The sample's taxon profile from read_lca(frame)'s nodes
+        (GhostmSessionTaxonProfile, ...Final, ...Summary): (TAXON_COUNT_DTYPE
+        records in ascending node index, one final node per read_lca record,
+        the summary as a dict). Computed on first use."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        f = int(bool(frame))
+        n = lib.GhostmSessionTaxonProfile(self._h, f, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        rec = np.zeros(n, dtype=TAXON_COUNT_DTYPE)
+        if n and lib.GhostmSessionTaxonProfile(self._h, f, rec.ctypes.data_as(ctypes.POINTER(native.GhostmTaxonCount)), n) == bad:
+            raise GhostmError(native.last_error())
+        m = lib.GhostmSessionTaxonProfileFinal(self._h, f, None, 0)
+        if m == bad:
+            raise GhostmError(native.last_error())
+        final = np.zeros(m, dtype=np.uint32)
+        if m and lib.GhostmSessionTaxonProfileFinal(self._h, f, final.ctypes.data_as(_U32P), m) == bad:
+            raise GhostmError(native.last_error())
+        st = native.GhostmTaxonSummary()
+        if lib.GhostmSessionTaxonProfileSummary(self._h, f, ctypes.byref(st), ctypes.sizeof(st)) == bad:
+            raise GhostmError(native.last_error())
+        return rec, final, {name: getattr(st, name) for name, _ in st._fields_}
+
+    def taxon_profile_stats(self) -> dict:
+        """The profile's counters since the last run (GhostmSessionTaxonProfileStats)."""
+        st = native.GhostmTaxonProfileStats()
+        native.load().GhostmSessionTaxonProfileStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
         return {name: getattr(st, name) for name, _ in st._fields_}
 
     def read_subject_profile(self, frame: bool, db_id: int) -> np.ndarray:

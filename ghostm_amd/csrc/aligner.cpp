@@ -31,6 +31,7 @@
 #include "query_set.h"
 #include "query_tiles.h"
 #include "read_lca.h"
+#include "taxon_profile.h"
 #include "worker_pool.h"
 
 namespace ghostm {
@@ -1502,7 +1503,7 @@ const LineFormat &Session::Format() {
       opt_.output_style == 20 || opt_.output_style == 21;
   // -y 10, -y 11 and -y 16 to -y 19 replace the hit lines after the run: style 1's lines, which need no E-value, stand in
   const bool pileup = opt_.output_style == 10 || opt_.output_style == 11 || (opt_.output_style >= 16 && opt_.output_style <= 19) ||
-                      opt_.output_style == 22 || opt_.output_style == 23;  // and the taxon lines
+                      (opt_.output_style >= 22 && opt_.output_style <= 25);  // and the taxon lines, the profile
   if (!format_) format_.reset(new LineFormat(tabular ? 0 : pileup ? 1 : opt_.output_style, opt_.karlin, 4095));
   return *format_;
 }
@@ -1516,7 +1517,7 @@ static void AddDeltas(Dst &dst, const DeviceTimes &before, const DeviceTimes &af
 }
 
 // The read-level passes' counters (DeviceTimes holds them as the public structs)
-// are added whole: every one of the six structs is one double, the seconds,
+// are added whole: every one of the seven structs is one double, the seconds,
 // followed by uint64_t counters only.
 template <class Stats, size_t kFields>
 constexpr bool SecondsThenCounters(double Stats::*) {
@@ -1527,12 +1528,14 @@ static_assert(SecondsThenCounters<GhostmBandStats, 5>(&GhostmBandStats::seconds_
                   SecondsThenCounters<GhostmReadRowsStats, 4>(&GhostmReadRowsStats::seconds_read_rows) &&
                   SecondsThenCounters<GhostmReadPileupStats, 6>(&GhostmReadPileupStats::seconds_read_pileup) &&
                   SecondsThenCounters<GhostmReadCullStats, 7>(&GhostmReadCullStats::seconds_cull) &&
-                  SecondsThenCounters<GhostmReadLcaStats, 6>(&GhostmReadLcaStats::seconds_lca),
+                  SecondsThenCounters<GhostmReadLcaStats, 6>(&GhostmReadLcaStats::seconds_lca) &&
+                  SecondsThenCounters<GhostmTaxonProfileStats, 4>(&GhostmTaxonProfileStats::seconds_profile),
               "a pass's counters: a double, then 8-byte counters");
 static_assert(offsetof(GhostmBandStats, seconds_band) == 0 && offsetof(GhostmFrameStats, seconds_frame) == 0 &&
                   offsetof(GhostmReadRowsStats, seconds_read_rows) == 0 &&
                   offsetof(GhostmReadPileupStats, seconds_read_pileup) == 0 &&
-                  offsetof(GhostmReadCullStats, seconds_cull) == 0 && offsetof(GhostmReadLcaStats, seconds_lca) == 0,
+                  offsetof(GhostmReadCullStats, seconds_cull) == 0 && offsetof(GhostmReadLcaStats, seconds_lca) == 0 &&
+                  offsetof(GhostmTaxonProfileStats, seconds_profile) == 0,
               "a pass's counters begin with the seconds");
 
 // dst += x (or dst -= x), field by field
@@ -1923,6 +1926,7 @@ void Session::DropLevel(int lv, LevelStage from) {
   }
   if (from != kFromLca) cull_[lv].Drop();
   lca_[lv].Drop();
+  profile_[lv].Drop();
 }
 
 // The read-level path of every final hit: the band paths (HitsBand) or the
@@ -2341,6 +2345,7 @@ void Session::SetTaxonomy(uint32_t nnodes, const uint32_t *taxid, const uint32_t
   tax_.mapped = mapped;
   tax_.map_unmatched = map_unmatched;
   tax_.serial = dev.taxonomy_serial();
+  tax_.depth = depth;
   tax_.set = true;
   DropLevel(0, kFromLca);
   DropLevel(1, kFromLca);
@@ -2461,6 +2466,45 @@ void Session::FormatLca(bool frame) {
     }
     out.push_back('\n');
   }
+  ReplaceText(&out);
+}
+
+void Session::SetProfile(uint32_t min_reads) {
+  if (min_reads < 1) throw Error("profile: param: min_reads 0");
+  if (min_reads == profile_min_reads_) return;
+  profile_min_reads_ = min_reads;
+  profile_[0].Drop();  // the assignments under them stay
+  profile_[1].Drop();
+}
+
+// The sample's profile (TaxonProfile): every ReadLca record is a read, its node the read's.
+const Session::TaxonProfileResult &Session::TaxonProfile(bool frame) {
+  const ReadLcaResult &lca = ReadLca(frame);  // throws without a taxonomy
+  TaxonProfileResult &res = profile_[frame ? 1 : 0];
+  if (res.valid) return res;
+  const uint32_t nreads = (uint32_t)lca.out.size();
+  std::vector<uint32_t> node(nreads);
+  for (uint32_t r = 0; r < nreads; ++r) node[r] = lca.out[r].node;
+  DeviceModule &dev = DeviceModule::Get();
+  if (dev.taxonomy_serial() != tax_.serial) {  // SetTaxonomyGpu, FreeGpu or another session since: ours again
+    dev.SetTaxonomy((uint32_t)tax_.parent.size(), tax_.parent.data());
+    tax_.serial = dev.taxonomy_serial();
+  }
+  const GhostmTaxonProfileStats before = dev.times().profile;
+  size_t n = 0;
+  res.final_node.assign(nreads, kLcaNone);
+  res.summary = GhostmTaxonSummary{};
+  dev.TaxonProfile(nreads, node.data(), profile_min_reads_, 0, nullptr, &n, res.final_node.data(), &res.summary, &res.rec);
+  AddStats(profile_stats_, StatsDelta(dev.times().profile, before));
+  res.valid = true;
+  return res;
+}
+
+// -y 24 / -y 25: the report of the whole sample.
+void Session::FormatProfile(bool frame) {
+  const TaxonProfileResult &res = TaxonProfile(frame);
+  std::string out = TaxonReport(res.rec.data(), res.rec.size(), profile_min_reads_, res.summary.reads, tax_.parent.data(),
+                                tax_.depth.data(), tax_.taxid.data());
   ReplaceText(&out);
 }
 
@@ -2921,9 +2965,9 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  // -y 6 to -y 23 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup, HitsReadRows, ReadPileup,
-  // ReadCull, ReadLca), not while the search runs
-  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 23;
+  // -y 6 to -y 25 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup, HitsReadRows, ReadPileup,
+  // ReadCull, ReadLca, TaxonProfile), not while the search runs
+  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 25;
   if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
@@ -2957,6 +3001,7 @@ void Session::Run(bool stream_to_file) {
   read_pileup_stats_ = GhostmReadPileupStats{};
   cull_stats_ = GhostmReadCullStats{};
   lca_stats_ = GhostmReadLcaStats{};
+  profile_stats_ = GhostmTaxonProfileStats{};
   QueryStats();
   merge_epoch_ = 0;
   DropResults();
@@ -2996,7 +3041,9 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    if (opt_.output_style == 22 || opt_.output_style == 23) {
+    if (opt_.output_style == 24 || opt_.output_style == 25) {
+      FormatProfile(opt_.output_style == 25);
+    } else if (opt_.output_style == 22 || opt_.output_style == 23) {
       FormatLca(opt_.output_style == 23);
     } else if (opt_.output_style == 20 || opt_.output_style == 21) {
       if (opt_.output_style == 21) FormatFrameTabular();

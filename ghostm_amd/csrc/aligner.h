@@ -378,6 +378,22 @@ class Session {
   };
   const ReadLcaResult &ReadLca(bool frame);
   const GhostmReadLcaStats &ReadLcaStats() const { return lca_stats_; }
+  // The sample's taxon profile (the contract is above TaxonProfileGpu in
+  // include/ghostm_hip.h; the session calls are described at
+  // GhostmSessionSetProfile): one DeviceModule::TaxonProfile call over the
+  // node field of ReadLca(frame)'s records. Computed on first use; kept as
+  // long as the assignment under it and the floor. min_reads >= 1 (default 1);
+  // a change drops only the profile.
+  void SetProfile(uint32_t min_reads);
+  struct TaxonProfileResult {
+    std::vector<GhostmTaxonCount> rec;
+    std::vector<uint32_t> final_node;
+    GhostmTaxonSummary summary{};
+    bool valid = false;
+    void Drop() { *this = TaxonProfileResult(); }
+  };
+  const TaxonProfileResult &TaxonProfile(bool frame);
+  const GhostmTaxonProfileStats &TaxonProfileStats() const { return profile_stats_; }
   // Hit records of the last run in device memory (this session's GPU): copies
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
@@ -564,7 +580,10 @@ class Session {
   // read order: qname, taxid, depth, votes, support, lca_taxid, candidates,
   // unmapped, best_score; replaces the parts' text as FormatPileup's does
   void FormatLca(bool frame);
-  // the common end of FormatPileup, FormatCull and FormatLca: *out (taken) becomes the parts' whole text
+  // -y 24 (frame false) and -y 25 (frame true): the sample's report (TaxonReport, taxon_profile.h); replaces the
+  // parts' text as FormatLca does
+  void FormatProfile(bool frame);
+  // the common end of FormatPileup, FormatCull, FormatLca and FormatProfile: *out (taken) becomes the parts' whole text
   void ReplaceText(std::string *out);
   uint32_t SubjectLength(const DbData &d, uint32_t subject) const;
 
@@ -606,8 +625,9 @@ class Session {
   ReadLevelResult level_[2];  // the band paths [0] and the frame paths [1]
   std::vector<GhostmHitFrameInfo> frame_info_;  // beside level_[1]
   // Drops a level's results from a stage on: its paths with the rows, the
-  // pile-up, the cull and the LCA made from them; or the cull and its LCA; or
-  // the LCA alone. A new per-level result joins this one list.
+  // pile-up, the cull, the LCA and the profile made from them; or the cull,
+  // its LCA and the profile; or the LCA and the profile. A new per-level result
+  // joins this one list.
   enum LevelStage { kFromPaths, kFromCull, kFromLca };
   void DropLevel(int lv, LevelStage from = kFromPaths);
   // the read-level rows of the band paths [0] and of the frame paths [1]
@@ -640,6 +660,7 @@ class Session {
   bool tile_groups_ = false;
   struct Taxonomy {
     std::vector<uint32_t> taxid, parent, subject_node;
+    std::vector<uint32_t> depth;  // per node (the report's column)
     uint64_t mapped = 0, map_unmatched = 0;
     uint64_t serial = 0;  // DeviceModule::taxonomy_serial() after this taxonomy's upload
     bool set = false;
@@ -648,6 +669,9 @@ class Session {
   ReadLcaResult lca_[2];  // of the band paths [0] and of the frame paths [1]
   uint32_t lca_top_pct_ = 10, lca_support_pct_ = 100;
   GhostmReadLcaStats lca_stats_{};
+  TaxonProfileResult profile_[2];  // of lca_[0] and of lca_[1]
+  uint32_t profile_min_reads_ = 1;
+  GhostmTaxonProfileStats profile_stats_{};
   bool records_on_device_ = false;
   GhostmStats stats_{};
   unsigned threads_ = 1;

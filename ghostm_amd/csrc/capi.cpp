@@ -657,6 +657,64 @@ size_t GhostmSessionReadLcaStats(void *s, GhostmReadLcaStats *stats, size_t size
   return sizeof(GhostmReadLcaStats);
 }
 
+int GhostmSessionSetProfile(void *s, uint32_t min_reads) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetProfile(min_reads);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionTaxonProfile(void *s, int frame, GhostmTaxonCount *out, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmTaxonCount> &r = static_cast<Session *>(s)->TaxonProfile(frame != 0).rec;
+    if (!out) return r.size();
+    const size_t n = std::min(cap, r.size());
+    if (n) std::memcpy(out, r.data(), n * sizeof(GhostmTaxonCount));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionTaxonProfileFinal(void *s, int frame, uint32_t *final_node, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<uint32_t> &r = static_cast<Session *>(s)->TaxonProfile(frame != 0).final_node;
+    if (!final_node) return r.size();
+    const size_t n = std::min(cap, r.size());
+    if (n) std::memcpy(final_node, r.data(), n * sizeof(uint32_t));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionTaxonProfileSummary(void *s, int frame, GhostmTaxonSummary *summary, size_t size) {
+  if (!s || !summary) return 0;
+  try {
+    const GhostmTaxonSummary t = static_cast<Session *>(s)->TaxonProfile(frame != 0).summary;
+    std::memcpy(summary, &t, std::min(size, sizeof(GhostmTaxonSummary)));
+    return sizeof(GhostmTaxonSummary);
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionTaxonProfileStats(void *s, GhostmTaxonProfileStats *stats, size_t size) {
+  if (!s || !stats) return 0;
+  const GhostmTaxonProfileStats st = static_cast<Session *>(s)->TaxonProfileStats();
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmTaxonProfileStats)));
+  return sizeof(GhostmTaxonProfileStats);
+}
+
 size_t GhostmSessionDeviceHits(void *s, void *dst_device, size_t cap) {
   try {
     if (!s) throw Error("null session");
@@ -686,6 +744,8 @@ int GhostmAlignMain(int argc, char **argv) {
     AlignerOptions opt = ParseAlignerOptions(argc, argv);
     if (opt.output_style == 22 || opt.output_style == 23)
       throw Error("-y 22 and -y 23 need a taxonomy: use `ghostm search` with -n nodes.tsv -a map.tsv");
+    if (opt.output_style == 24 || opt.output_style == 25)
+      throw Error("-y 24 and -y 25 need a taxonomy: use `ghostm search` with -n nodes.tsv -a map.tsv");
     { std::ofstream touch(opt.output_file.c_str()); }
     Session session(opt);
     session.Run(true);       // the output file is written while the search runs
@@ -717,14 +777,22 @@ int GhostmSearchMain(int argc, char **argv) {
   bool tile_groups = false;                // -g
   std::string tax_nodes, tax_map;          // -n, -a
   long lca_top = -1, lca_support = -1;     // -p, -P; below 0: the session's defaults
+  long profile_min = -1;                   // -R; below 0: the session's default
   int style = 0;                           // -y, as aln reads it
   optind = 1;
   opterr = 1;
   int c;
   // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B, -F, -g, -K, -C, -n, -a,
-  // -p, -P
-  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:n:a:p:P:")) >= 0) {
+  // -p, -P, -R
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:n:a:p:P:R:")) >= 0) {
     switch (c) {
+      case 'R': {  // the profile's floor, 1 or more
+        char *end = nullptr;
+        const long long v = strtoll(optarg, &end, 10);
+        if (end == optarg || *end || v < 1 || v > 0xFFFFFFFFll) return 1;
+        profile_min = (long)v;
+        break;
+      }
       case 'n': tax_nodes = optarg; break;  // the taxonomy's nodes file
       case 'a': tax_map = optarg; break;    // and the subjects' taxids
       case 'p':    // the assignment's top_pct, 0..100
@@ -798,7 +866,7 @@ int GhostmSearchMain(int argc, char **argv) {
   if (have_x && !tiled) return 1;             // -X cuts a tiled set only
   if (tile_groups && !tiled) return 1;        // -g groups a tiled set only
   if (tax_nodes.empty() != tax_map.empty()) return 1;                // -n and -a come together
-  if ((style == 22 || style == 23) && tax_nodes.empty()) return 1;  // the taxon lines need them
+  if (style >= 22 && style <= 25 && tax_nodes.empty()) return 1;  // the taxon lines and the profile need them
   try {
     aln_argv.push_back(nullptr);
     AlignerOptions opt = ParseAlignerOptions((int)aln_argv.size() - 1, aln_argv.data());
@@ -812,6 +880,7 @@ int GhostmSearchMain(int argc, char **argv) {
     if (!tax_nodes.empty()) session.SetTaxonomyFiles(tax_nodes, tax_map);  // after the database
     if (lca_top >= 0 || lca_support >= 0)
       session.SetLca(lca_top >= 0 ? (uint32_t)lca_top : 10u, lca_support >= 0 ? (uint32_t)lca_support : 100u);
+    if (profile_min >= 0) session.SetProfile((uint32_t)profile_min);
     for (size_t k = 0; k < pos.size(); k += 2) {
       try {
         { std::ofstream touch(pos[k + 1].c_str()); }

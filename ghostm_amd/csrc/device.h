@@ -111,6 +111,7 @@ struct DeviceTimes {
   GhostmReadPileupStats read_pileup{};   // k_read_pileup + k_pileup_finish<true>, counted as the pile-up
   GhostmReadCullStats cull{};            // k_read_cull
   GhostmReadLcaStats lca{};              // k_read_lca*
+  GhostmTaxonProfileStats profile{};     // k_taxon_*
 };
 
 class DeviceModule {
@@ -372,6 +373,17 @@ class DeviceModule {
   // chunk. Adds to times().lca*.
   void ReadLca(uint32_t nreads, const uint32_t *read_begin, uint32_t nhits, const GhostmLcaHit *hit, uint32_t top_pct,
                uint32_t support_pct, GhostmLcaOut *out);
+  // The taxon profile of nreads reads over the resident taxonomy (kern::k_taxon_count,
+  // k_taxon_climb, k_taxon_floor, k_taxon_final, k_taxon_sort_*, k_taxon_emit; the contract is
+  // above TaxonProfileGpu in include/ghostm_hip.h). The checks that need no
+  // count come first (ValidateTaxonProfile, taxon_profile.h; throws before any
+  // upload or launch); "cap" is known after the climb and throws once the count
+  // arrays are clean again. Nothing is written on a throw. Needs no resident
+  // chunk. Adds to times().profile*. With grow given, out and cap are not
+  // used: *grow becomes the records, however many.
+  void TaxonProfile(uint32_t nreads, const uint32_t *node, uint32_t min_reads, size_t cap, GhostmTaxonCount *out,
+                    size_t *nout, uint32_t *final_node, GhostmTaxonSummary *summary,
+                    std::vector<GhostmTaxonCount> *grow = nullptr);
 
   // The read-level banded alignment of n hits (kern::k_band_fill, k_band_walk,
   // k_band_compact; the contract is in include/ghostm_hip.h): hit i aligns
@@ -432,6 +444,7 @@ class DeviceModule {
   int device_ = -1;
   uint32_t tax_nodes_ = 0;   // the resident taxonomy's nodes; 0: none
   uint64_t tax_serial_ = 0;  // counts SetTaxonomy and DropTaxonomy
+  bool profile_dirty_ = false;  // a TaxonProfile call ended before its count arrays were clean again
   void *stream_ = nullptr;
   HostCopyFn host_copy_;
   HostParallelFn host_par_;

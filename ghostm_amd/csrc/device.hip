@@ -26,6 +26,7 @@
 #include "read_classes.h"
 #include "read_cull.h"
 #include "read_lca.h"
+#include "taxon_profile.h"
 #include "read_pileup.h"
 #include "pileup_plan.h"
 #include "qformat.h"
@@ -299,6 +300,9 @@ struct DeviceModule::Impl {
     DevBuf hit, meta, scratch, out;
   } cull, lca;
   DevBuf lca_tax;  // the taxonomy's words
+  // TaxonProfile: direct, clade, kept (all zero between calls) and fin, one word per node each, as long as the
+  // taxonomy is resident; a call's reads and final nodes, its two lists, its counters and its records
+  DevBuf prof_counts, prof_node, prof_final, prof_listed, prof_touched, prof_counter, prof_rec;
   // BandAlign [0], FrameAlign [1]: a batch's slots, its offsets / maxima / records, its direction bytes, its word
   // slots, their packed words
   struct PathBufs {
@@ -3209,15 +3213,205 @@ void DeviceModule::SetTaxonomy(uint32_t nnodes, const uint32_t *parent) {
   hipStream_t st = S(stream_);
   I.lca_tax.Reserve((size_t)nnodes * 4);
   HIP_CHECK(hipMemcpyAsync(I.lca_tax.p, words.data(), (size_t)nnodes * 4, hipMemcpyHostToDevice, st));
+  // TaxonProfile's count arrays (and fin): sized and zeroed here, once per taxonomy, so that no call has to
+  I.prof_counts.Reserve((size_t)nnodes * 16);
+  HIP_CHECK(hipMemsetAsync(I.prof_counts.p, 0, (size_t)nnodes * 16, st));
   HIP_CHECK(hipStreamSynchronize(st));
+  profile_dirty_ = false;
   tax_nodes_ = nnodes;
   ++tax_serial_;
 }
 
 void DeviceModule::DropTaxonomy() {
-  if (impl_ && tax_nodes_) impl_->lca_tax.Release();
+  if (impl_ && tax_nodes_) {
+    impl_->lca_tax.Release();
+    impl_->prof_counts.Release();
+  }
   tax_nodes_ = 0;
   ++tax_serial_;
+}
+
+static_assert(sizeof(GhostmTaxonCount) == 16 && sizeof(uint4) == 16, "k_taxon_emit writes 4 words per record");
+
+// the power of two at or above n (n <= 2^24)
+static uint32_t TaxonPow2(uint32_t n) {
+  uint32_t p = 1;
+  while (p < n) p <<= 1;
+  return p;
+}
+
+// The taxon profile of nreads reads (kern::k_taxon_*; the contract is above
+// TaxonProfileGpu in include/ghostm_hip.h). Pass 1 uploads the reads batch by
+// batch and counts them; the listed nodes' number comes back (4 bytes) and
+// sizes the touched list; climb; the touched nodes' number comes back and
+// decides "cap"; floor; with final_node given, pass 2 gathers it batch by batch
+// (a single batch is still resident and is not uploaded twice); the touched
+// list is sorted by node; emit writes the records in that order and clears the
+// counts, and 16 bytes per record come back. Every device time between two
+// read-backs is one timed span.
+void DeviceModule::TaxonProfile(uint32_t nreads, const uint32_t *node, uint32_t min_reads, size_t cap,
+                                GhostmTaxonCount *out, size_t *nout, uint32_t *final_node,
+                                GhostmTaxonSummary *summary, std::vector<GhostmTaxonCount> *grow) {
+  if (!impl_) throw Error("taxon profile: the device module is not bound to a device");
+  Use();
+  Impl &I = *impl_;
+  const std::string why = ValidateTaxonProfile(tax_nodes_, nreads, node, min_reads, cap, out, nout);
+  if (!why.empty()) throw Error("taxon profile: " + why);
+  const bool count_only = !out && cap == 0 && !grow;
+  if (grow) grow->clear();
+  GhostmTaxonProfileStats &t = times_.profile;
+  if (nreads == 0) {  // nothing to count
+    *nout = 0;
+    if (!count_only && summary) *summary = TaxonSummary(0, nullptr, 0, min_reads);
+    return;
+  }
+  hipStream_t st = S(stream_);
+  const uint32_t nnodes = tax_nodes_;
+  if (profile_dirty_) {  // an earlier call threw between its first add and its clearing: start from zero
+    HIP_CHECK(hipMemsetAsync(I.prof_counts.p, 0, (size_t)nnodes * 16, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    profile_dirty_ = false;
+  }
+  const uint32_t batch = (uint32_t)std::min<size_t>(EnvSize("GHOSTM_PROFILE_BATCH_READS", SIZE_MAX), nreads);
+  const uint32_t nbatches = (nreads + batch - 1) / batch;
+  const uint32_t listed_cap = std::min(nnodes, nreads);
+  I.prof_node.Reserve((size_t)batch * 4);
+  I.prof_listed.Reserve((size_t)listed_cap * 4);
+  I.prof_counter.Reserve(8);
+  kern::TaxonArgs a{};
+  a.tax = I.lca_tax.as<uint32_t>();
+  a.nnodes = nnodes;
+  a.min_reads = min_reads;
+  a.direct = I.prof_counts.as<uint32_t>();
+  a.clade = a.direct + nnodes;
+  a.kept = a.clade + nnodes;
+  a.fin = a.kept + nnodes;
+  a.listed = I.prof_listed.as<uint32_t>();
+  a.listed_cap = listed_cap;
+  a.counter = I.prof_counter.as<uint32_t>();
+  a.node = I.prof_node.as<uint32_t>();
+  const auto blocks = [](uint32_t n) { return dim3((n + kern::kTaxonBlock - 1) / kern::kTaxonBlock); };
+  const dim3 block(kern::kTaxonBlock);
+  double seconds = 0;
+  uint32_t counter[2] = {0, 0};
+  // one timed span, ended by the counters' read-back
+  const auto span = [&](auto launch) {
+    TimedLaunch(I.ev0, I.ev1, st, launch);
+    HIP_CHECK(hipMemcpyAsync(counter, I.prof_counter.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+  };
+  // the counts back to zero through the touched list; rec: also the records
+  const auto emit = [&](uint32_t ntouched, uint4 *rec) {
+    if (!ntouched) return;
+    kern::TaxonArgs e = a;
+    e.n = ntouched;
+    e.rec = rec;
+    hipLaunchKernelGGL(kern::k_taxon_emit, blocks(ntouched), block, 0, st, e);
+  };
+  profile_dirty_ = true;
+  HIP_CHECK(hipMemsetAsync(I.prof_counter.p, 0, 8, st));
+  for (uint32_t b = 0; b < nbatches; ++b) {  // pass 1: count
+    const uint32_t r0 = b * batch, m = std::min(batch, nreads - r0);
+    HIP_CHECK(hipMemcpyAsync(I.prof_node.p, node + r0, (size_t)m * 4, hipMemcpyHostToDevice, st));
+    span([&] {
+      kern::TaxonArgs c = a;
+      c.n = m;
+      hipLaunchKernelGGL(kern::k_taxon_count, blocks(m), block, 0, st, c);
+    });
+  }
+  const uint32_t nlisted = counter[0];
+  if (nlisted > listed_cap) throw Error("taxon profile: internal: " + std::to_string(nlisted) + " listed nodes over the bound");
+  uint32_t ntouched = 0;
+  if (nlisted) {
+    const uint32_t touched_cap = (uint32_t)std::min<uint64_t>(nnodes, (uint64_t)nlisted * kern::kTaxonSteps);
+    I.prof_touched.Reserve((size_t)TaxonPow2(touched_cap) * 4);  // the sort pads the list to a power of two
+    a.touched = I.prof_touched.as<uint32_t>();
+    a.touched_cap = touched_cap;
+    span([&] {
+      kern::TaxonArgs c = a;
+      c.n = nlisted;
+      hipLaunchKernelGGL(kern::k_taxon_climb, blocks(nlisted), block, 0, st, c);
+    });
+    ntouched = counter[1];
+    if (ntouched > touched_cap)
+      throw Error("taxon profile: internal: " + std::to_string(ntouched) + " touched nodes over the bound");
+  }
+  const auto finish = [&](uint4 *rec) {  // the clearing span; on return the arrays are clean
+    span([&] { emit(ntouched, rec); });
+    profile_dirty_ = false;
+    t.seconds_profile += seconds;
+    t.profile_launches += nbatches;
+  };
+  const std::string full = grow ? std::string() : TaxonProfileCap(ntouched, cap, out);
+  if (count_only || !full.empty()) {
+    finish(nullptr);
+    if (!full.empty()) throw Error("taxon profile: " + full);
+    *nout = ntouched;
+    t.profile_reads += nreads;
+    t.profile_nodes += ntouched;
+    return;
+  }
+  std::vector<uint32_t> fin_host;  // the final nodes as read back: final_node is written only when nothing can fail
+  if (nlisted) {
+    TimedLaunch(I.ev0, I.ev1, st, [&] {
+      kern::TaxonArgs c = a;
+      c.n = nlisted;
+      hipLaunchKernelGGL(kern::k_taxon_floor, blocks(nlisted), block, 0, st, c);
+    });
+    HIP_CHECK(hipStreamSynchronize(st));
+    seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+  }
+  if (final_node) {
+    fin_host.assign(nreads, kLcaNone);
+    if (nlisted) {  // without a listed node every final node is none
+      I.prof_final.Reserve((size_t)batch * 4);
+      for (uint32_t b = 0; b < nbatches; ++b) {  // pass 2: gather
+        const uint32_t r0 = b * batch, m = std::min(batch, nreads - r0);
+        if (nbatches > 1) HIP_CHECK(hipMemcpyAsync(I.prof_node.p, node + r0, (size_t)m * 4, hipMemcpyHostToDevice, st));
+        TimedLaunch(I.ev0, I.ev1, st, [&] {
+          kern::TaxonArgs c = a;
+          c.n = m;
+          c.final_node = I.prof_final.as<uint32_t>();
+          hipLaunchKernelGGL(kern::k_taxon_final, blocks(m), block, 0, st, c);
+        });
+        HIP_CHECK(hipMemcpyAsync(fin_host.data() + r0, I.prof_final.p, (size_t)m * 4, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+      }
+    }
+  }
+  std::vector<GhostmTaxonCount> rec(ntouched);
+  if (ntouched) I.prof_rec.Reserve((size_t)ntouched * 16);
+  TimedLaunch(I.ev0, I.ev1, st, [&] {
+    if (ntouched > 1) {  // the touched list into ascending node index
+      const uint32_t P = TaxonPow2(ntouched), T = kern::kTaxonSortTile, n = std::min(P, T);
+      uint32_t *list = I.prof_touched.as<uint32_t>();
+      if (P > ntouched) HIP_CHECK(hipMemsetAsync(list + ntouched, 0xFF, (size_t)(P - ntouched) * 4, st));
+      hipLaunchKernelGGL(kern::k_taxon_sort_tile<true>, dim3(P / n), dim3(T), 0, st, list, n, 0u);
+      for (uint32_t k = 2 * T; k <= P && k; k <<= 1) {
+        for (uint32_t j = k >> 1; j >= T; j >>= 1)
+          hipLaunchKernelGGL(kern::k_taxon_sort_step, blocks(P), block, 0, st, list, P, k, j);
+        hipLaunchKernelGGL(kern::k_taxon_sort_tile<false>, dim3(P / T), dim3(T), 0, st, list, T, k);
+      }
+    }
+    emit(ntouched, I.prof_rec.as<uint4>());
+  });
+  if (ntouched) HIP_CHECK(hipMemcpyAsync(rec.data(), I.prof_rec.p, (size_t)ntouched * 16, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
+  profile_dirty_ = false;
+  for (uint32_t k = 1; k < ntouched; ++k)
+    if (rec[k - 1].node >= rec[k].node) throw Error("taxon profile: internal: the records are not in ascending node index");
+  t.seconds_profile += seconds;
+  t.profile_launches += nbatches;
+  t.profile_reads += nreads;
+  t.profile_nodes += ntouched;
+  *nout = ntouched;
+  if (summary) *summary = TaxonSummary(nreads, rec.data(), rec.size(), min_reads);
+  if (grow) *grow = std::move(rec);
+  else std::copy(rec.begin(), rec.end(), out);
+  if (final_node) std::copy(fin_host.begin(), fin_host.end(), final_node);
 }
 
 // The taxon of nreads reads (kern::k_read_lca_wave, kern::k_read_lca; the
@@ -3302,7 +3496,7 @@ const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_read_pileup/k_pileup_finish/k_read_cull/k_read_lca_wave/k_read_lca/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_read_pileup/k_pileup_finish/k_read_cull/k_read_lca_wave/k_read_lca/k_taxon_count/k_taxon_climb/k_taxon_floor/k_taxon_final/k_taxon_sort_tile/k_taxon_sort_step/k_taxon_emit/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -3423,8 +3617,8 @@ int ReadLevelAlignGpu(const char *name, bool frame, uint32_t nhits, const Ghostm
   }
 }
 
-// A stage call that needs no resident chunk (ReadCullGpu, SetTaxonomyGpu, ReadLcaGpu): under the lock, on the first
-// device when no SetOptionGpu bound one, call(module); an error's text after the call's name
+// A stage call that needs no resident chunk (ReadCullGpu, SetTaxonomyGpu, ReadLcaGpu, TaxonProfileGpu): under the lock,
+// on the first device when no SetOptionGpu bound one, call(module); an error's text after the call's name
 template <class Call>
 int UnboundStageCall(const char *name, Call call) {
   try {
@@ -3913,6 +4107,17 @@ int ReadLcaGpu(uint32_t nreads, const uint32_t read_begin[], uint32_t nhits, con
 
 size_t GhostmStageReadLcaStats(GhostmReadLcaStats *stats, size_t size) {
   return StageStats(&DeviceTimes::lca, stats, size);
+}
+
+int TaxonProfileGpu(uint32_t nreads, const uint32_t node[], uint32_t min_reads, size_t cap, GhostmTaxonCount out[],
+                    size_t *nout, uint32_t final_node[], GhostmTaxonSummary *summary) {
+  return UnboundStageCall("TaxonProfileGpu", [&](DeviceModule &m) {
+    m.TaxonProfile(nreads, node, min_reads, cap, out, nout, final_node, summary);
+  });
+}
+
+size_t GhostmStageTaxonProfileStats(GhostmTaxonProfileStats *stats, size_t size) {
+  return StageStats(&DeviceTimes::profile, stats, size);
 }
 
 }  // extern "C"

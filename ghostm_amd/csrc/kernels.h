@@ -5974,5 +5974,185 @@ template <bool GLOBAL> __global__ __launch_bounds__(kLcaBlock) void k_read_lca(L
   if (tid == 0) LcaStore(a, rd, hdr[5], hdr[7], V, hdr[6], hdr[8], nc, unmapped, best);
 }
 
+// ------------------------------------------------- taxon profile of a sample
+// k_taxon_count, k_taxon_climb, k_taxon_floor, k_taxon_final, k_taxon_sort_*,
+// k_taxon_emit: the clade read counts of a sample with a floor (the contract is above
+// TaxonProfileGpu in include/ghostm_hip.h; taxon_profile.h has the model). The
+// three count arrays direct, clade and kept have one word per node of the
+// resident taxonomy and are all zero between calls; a call reaches them only
+// through two lists, so its work follows the nodes it touches and not nnodes:
+//   count   one lane per read of a batch. The lanes of a wave with an equal
+//           node combine: one ballot per distinct node of the wave, and the
+//           first of its lanes adds their number to direct[node]. The add that
+//           finds 0 puts the node on `listed` (once per call: a count never
+//           returns to 0 inside one).
+//   climb   one lane per listed node: its direct count is added to clade[] of
+//           every node from it to the root. The add that finds 0 puts that
+//           node on `touched`; every node with a count of any kind is there.
+//   floor   one lane per listed node: the first node on its way up with clade
+//           >= min_reads is fin[node] (none: 0xFFFFFFFF), and the node's direct
+//           count is added to kept[] there. fin has a word per node too, but a
+//           call writes every entry it reads, so it needs no clearing.
+//   final   one lane per read: final_node = fin[node]. Only when asked for.
+//   sort    the touched list into ascending node index (k_taxon_sort_tile,
+//           k_taxon_sort_step below).
+//   emit    one lane per touched node: its record (node, clade, direct, kept)
+//           in list order, then the three counts back to 0.
+// All counts move by integer atomic adds, so no result depends on the order in
+// which they land; only the order of the two lists does, and the sort removes
+// it before anything is written out. A climb ends at the root or after 256 steps (the depth is
+// 8 bits of a word); node indices are clamped below nnodes before they index
+// anything. The lists' capacities are bounds (listed: min(nnodes, reads);
+// touched: min(nnodes, 256 x listed), allocated up to the next power of two for
+// the sort's padding), and an append past one is dropped and
+// seen by the host in the counter, never written.
+struct TaxonArgs {
+  const uint32_t *node;  // the batch's reads (count, final)
+  uint32_t n;            // reads of the batch; listed or touched nodes
+  const uint32_t *tax;   // depth << 24 | parent, nnodes words
+  uint32_t nnodes, min_reads;
+  uint32_t *direct, *clade, *kept, *fin;  // nnodes words each
+  uint32_t *listed, *touched;
+  uint32_t listed_cap, touched_cap;
+  uint32_t *counter;     // [0] listed nodes, [1] touched nodes
+  uint32_t *final_node;  // the batch's (final)
+  uint4 *rec;            // one per touched node (emit); null: only clear
+};
+
+constexpr uint32_t kTaxonBlock = 256;
+constexpr uint32_t kTaxonSteps = 256;  // nodes on a path: depth <= 255
+
+__global__ __launch_bounds__(kTaxonBlock) void k_taxon_count(TaxonArgs a) {
+  GHOSTM_POISON_LDS();
+  const uint32_t i = blockIdx.x * kTaxonBlock + threadIdx.x, lane = threadIdx.x & 63;
+  uint32_t v = i < a.n ? a.node[i] : kLcaNone;
+  if (v != kLcaNone && v >= a.nnodes) v = kLcaNone;
+  const bool has = v != kLcaNone;
+  unsigned long long rem = __ballot(has);  // the same in every lane: the loop is the whole wave's
+  for (uint32_t it = 0; it < 64 && rem; ++it) {  // one distinct node per turn
+    const uint32_t first = (uint32_t)__ffsll((long long)rem) - 1;
+    const uint32_t x = (uint32_t)__shfl((int)v, (int)first);
+    const unsigned long long m = __ballot(has && v == x);
+    if (lane == first) {
+      if (atomicAdd(&a.direct[x], (uint32_t)__popcll(m)) == 0) {
+        const uint32_t p = atomicAdd(&a.counter[0], 1u);
+        if (p < a.listed_cap) a.listed[p] = x;
+      }
+    }
+    rem &= ~m & (rem - 1);  // the lanes counted leave, the first one in any case
+  }
+}
+
+__global__ __launch_bounds__(kTaxonBlock) void k_taxon_climb(TaxonArgs a) {
+  GHOSTM_POISON_LDS();
+  const uint32_t k = blockIdx.x * kTaxonBlock + threadIdx.x;
+  if (k >= a.n) return;
+  uint32_t cur = min(a.listed[k], a.nnodes - 1);
+  const uint32_t c = a.direct[cur];
+  if (c == 0) return;  // no listed node is without a count
+  for (uint32_t step = 0; step < kTaxonSteps; ++step) {
+    if (atomicAdd(&a.clade[cur], c) == 0) {
+      const uint32_t p = atomicAdd(&a.counter[1], 1u);
+      if (p < a.touched_cap) a.touched[p] = cur;
+    }
+    const uint32_t up = min(a.tax[cur] & 0xFFFFFFu, a.nnodes - 1);
+    if (up == cur) break;
+    cur = up;
+  }
+}
+
+__global__ __launch_bounds__(kTaxonBlock) void k_taxon_floor(TaxonArgs a) {
+  GHOSTM_POISON_LDS();
+  const uint32_t k = blockIdx.x * kTaxonBlock + threadIdx.x;
+  if (k >= a.n) return;
+  const uint32_t x = min(a.listed[k], a.nnodes - 1);
+  uint32_t cur = x, f = kLcaNone;
+  for (uint32_t step = 0; step < kTaxonSteps; ++step) {
+    if (a.clade[cur] >= a.min_reads) {
+      f = cur;
+      break;
+    }
+    const uint32_t up = min(a.tax[cur] & 0xFFFFFFu, a.nnodes - 1);
+    if (up == cur) break;
+    cur = up;
+  }
+  a.fin[x] = f;
+  if (f != kLcaNone) atomicAdd(&a.kept[f], a.direct[x]);
+}
+
+__global__ __launch_bounds__(kTaxonBlock) void k_taxon_final(TaxonArgs a) {
+  GHOSTM_POISON_LDS();
+  const uint32_t i = blockIdx.x * kTaxonBlock + threadIdx.x;
+  if (i >= a.n) return;
+  const uint32_t v = a.node[i];
+  a.final_node[i] = v == kLcaNone || v >= a.nnodes ? kLcaNone : a.fin[v];
+}
+
+// The touched list in ascending node index before emit: a bitonic network over
+// the list padded with 0xFFFFFFFF to P, a power of two. Tiles of kTaxonSortTile
+// entries run their steps in LDS: k_taxon_sort_tile<true> sorts every tile
+// (stages k = 2 .. the tile, entry i of the whole list ascending where i & k is
+// 0), then per stage k above the tile the steps with a partner outside the tile
+// are one k_taxon_sort_step launch each and the rest one k_taxon_sort_tile<false>.
+// A list of at most one tile is one launch.
+constexpr uint32_t kTaxonSortTile = 1024;
+
+// the steps j = from, from / 2, .. 1 of stage k on a tile in LDS; t: the lane's entry, g: its index in the list
+__device__ __forceinline__ void TaxonSortSteps(uint32_t *s, uint32_t t, uint32_t g, uint32_t n, uint32_t k,
+                                               uint32_t from) {
+  for (uint32_t j = from; j > 0; j >>= 1) {  // the same bounds in every lane: the barrier is the whole workgroup's
+    const uint32_t l = t ^ j;
+    if (t < n && l > t && l < n) {
+      const bool up = (g & k) == 0;
+      const uint32_t x = s[t], y = s[l];
+      if ((x > y) == up) {
+        s[t] = y;
+        s[l] = x;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// n: a tile's entries, kTaxonSortTile, or the whole list's when that is shorter (one workgroup then)
+template <bool FULL> __global__ __launch_bounds__(kTaxonSortTile) void k_taxon_sort_tile(uint32_t *list, uint32_t n,
+                                                                                        uint32_t stage) {
+  GHOSTM_POISON_LDS();
+  __shared__ uint32_t s[kTaxonSortTile];
+  const uint32_t t = threadIdx.x, g = blockIdx.x * n + t;
+  n = min(n, kTaxonSortTile);
+  if (t < n) s[t] = list[g];
+  __syncthreads();
+  if (FULL) {
+    for (uint32_t k = 2; k <= n; k <<= 1) TaxonSortSteps(s, t, g, n, k, k >> 1);
+  } else {
+    TaxonSortSteps(s, t, g, n, stage, n >> 1);
+  }
+  if (t < n) list[g] = s[t];
+}
+
+__global__ __launch_bounds__(kTaxonBlock) void k_taxon_sort_step(uint32_t *list, uint32_t P, uint32_t k, uint32_t j) {
+  GHOSTM_POISON_LDS();
+  const uint32_t i = blockIdx.x * kTaxonBlock + threadIdx.x, l = i ^ j;
+  if (i >= P || l <= i || l >= P) return;
+  const bool up = (i & k) == 0;
+  const uint32_t x = list[i], y = list[l];
+  if ((x > y) == up) {
+    list[i] = y;
+    list[l] = x;
+  }
+}
+
+__global__ __launch_bounds__(kTaxonBlock) void k_taxon_emit(TaxonArgs a) {
+  GHOSTM_POISON_LDS();
+  const uint32_t k = blockIdx.x * kTaxonBlock + threadIdx.x;
+  if (k >= a.n) return;
+  const uint32_t x = min(a.touched[k], a.nnodes - 1);
+  if (a.rec) a.rec[k] = make_uint4(x, a.clade[x], a.direct[x], a.kept[x]);
+  a.clade[x] = 0;
+  a.direct[x] = 0;
+  a.kept[x] = 0;
+}
+
 }  // namespace kern
 }  // namespace ghostm

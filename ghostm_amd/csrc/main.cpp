@@ -53,6 +53,11 @@ static int Usage() {
             << "        line (NCBI nodes.dmp reads as it is); map.tsv: subject name, taxid. A hit votes when its score is\n"
             << "        within topPct (0..100, default 10) per cent of the best on its stretch of the read; the taxon is\n"
             << "        the deepest node with supportPct (51..100, default 100) per cent of the votes\n"
+            << "       [-R minReads]: -y 24 and -y 25 (with -n and -a), the sample's taxon profile from the -y 22 and\n"
+            << "        -y 23 taxa: percent clade_reads kept_reads direct_reads depth taxid parent_taxid per line; first\n"
+            << "        the unclassified reads (taxid 0), then the taxa with at least minReads (default 1) reads in their\n"
+            << "        clade, depth first from the root, children by clade_reads; the reads of a smaller clade count\n"
+            << "        for the first ancestor that has minReads\n"
             << "synth: ghostm synth -d db.fasta -q queries.fasta [-n nq] [-N dbResidues] [-s seed]\n";
   return 1;
 }

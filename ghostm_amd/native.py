@@ -284,6 +284,35 @@ class GhostmReadLcaStats(ctypes.Structure):
     ]
 
 
+class GhostmTaxonCount(ctypes.Structure):
+    """one node's record of the taxon profile (16 bytes)."""
+
+    _fields_ = [
+        ("node", c_uint32),
+        ("clade_reads", c_uint32),
+        ("direct_reads", c_uint32),
+        ("kept_reads", c_uint32),
+    ]
+
+
+class GhostmTaxonSummary(ctypes.Structure):
+    """the totals of a taxon profile (TaxonProfileGpu, GhostmSessionTaxonProfileSummary)."""
+
+    _fields_ = [(n, c_uint64) for n in ("reads", "classified", "kept", "moved", "nodes", "nodes_kept")]
+
+
+class GhostmTaxonProfileStats(ctypes.Structure):
+    """the counters of the profile (GhostmSessionTaxonProfileStats,
+    GhostmStageTaxonProfileStats)."""
+
+    _fields_ = [
+        ("seconds_profile", ctypes.c_double),
+        ("profile_launches", c_uint64),
+        ("profile_reads", c_uint64),
+        ("profile_nodes", c_uint64),
+    ]
+
+
 class GhostmTaxonomyInfo(ctypes.Structure):
     """a session's taxonomy (GhostmSessionTaxonomyInfo)."""
 
@@ -475,6 +504,11 @@ SIGNATURES = {
     "GhostmReadLcaHost": (c_int, [c_uint32, u32p, c_uint32, u32p, c_uint32, POINTER(GhostmLcaHit), c_uint32, c_uint32,
                                   POINTER(GhostmLcaOut)]),
     "GhostmStageReadLcaStats": (c_size_t, [POINTER(GhostmReadLcaStats), c_size_t]),
+    "TaxonProfileGpu": (c_int, [c_uint32, u32p, c_uint32, c_size_t, POINTER(GhostmTaxonCount), POINTER(c_size_t), u32p,
+                                POINTER(GhostmTaxonSummary)]),
+    "GhostmTaxonProfileHost": (c_int, [c_uint32, u32p, c_uint32, u32p, c_uint32, c_size_t, POINTER(GhostmTaxonCount),
+                                       POINTER(c_size_t), u32p, POINTER(GhostmTaxonSummary)]),
+    "GhostmStageTaxonProfileStats": (c_size_t, [POINTER(GhostmTaxonProfileStats), c_size_t]),
     "GhostmBuildIndexGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, u32p, u32p, u32p, c_int,
                                     POINTER(c_float)]),
     "GhostmFormatQueriesGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_uint32,
@@ -555,6 +589,11 @@ SIGNATURES = {
     "GhostmSessionReadLca": (c_size_t, [c_void_p, c_int, POINTER(GhostmLcaOut), c_size_t]),
     "GhostmSessionReadLcaBegin": (c_size_t, [c_void_p, c_int, u32p, c_size_t]),
     "GhostmSessionReadLcaStats": (c_size_t, [c_void_p, POINTER(GhostmReadLcaStats), c_size_t]),
+    "GhostmSessionSetProfile": (c_int, [c_void_p, c_uint32]),
+    "GhostmSessionTaxonProfile": (c_size_t, [c_void_p, c_int, POINTER(GhostmTaxonCount), c_size_t]),
+    "GhostmSessionTaxonProfileFinal": (c_size_t, [c_void_p, c_int, u32p, c_size_t]),
+    "GhostmSessionTaxonProfileSummary": (c_size_t, [c_void_p, c_int, POINTER(GhostmTaxonSummary), c_size_t]),
+    "GhostmSessionTaxonProfileStats": (c_size_t, [c_void_p, POINTER(GhostmTaxonProfileStats), c_size_t]),
     "GhostmSessionDeviceHits": (c_size_t, [c_void_p, c_void_p, c_size_t]),
     "GhostmSessionStats": (c_int, [c_void_p, POINTER(GhostmStats)]),
     "GhostmSessionStatsSized": (c_size_t, [c_void_p, POINTER(GhostmStats), c_size_t]),

@@ -1185,6 +1185,91 @@ typedef struct GhostmReadLcaStats {
  * conventions. */
 size_t GhostmStageReadLcaStats(GhostmReadLcaStats *stats, size_t size);
 
+/* The taxon profile of a sample: how many reads fall on each clade of the
+ * resident taxonomy, and what is left once clades with only a handful of reads
+ * are discounted. A histogram and a sum up the tree: all arithmetic is on
+ * integers; the kernels equal the host model exactly.
+ *
+ * Input: the resident taxonomy (SetTaxonomyGpu), nreads reads, node[nreads] and
+ * min_reads >= 1. node[r] is a node index, or 0xFFFFFFFF for a read without a
+ * taxon (GhostmLcaOut.node is such a value).
+ *
+ *   direct(n)  the number of reads with node[r] == n.
+ *   clade(n)   the number of reads whose node has n on its path to the root,
+ *              ends included. It never shrinks towards the root.
+ *   final(r)   the floor: the first node a met climbing from node[r] to the
+ *              root, node[r] included, with clade(a) >= min_reads; 0xFFFFFFFF
+ *              when node[r] is, or when even the root's clade is below
+ *              min_reads. With min_reads == 1, final == node.
+ *   kept(n)    the number of reads with final(r) == n.
+ *
+ * Output: one record per node with clade(n) > 0, in ascending node index; the
+ * nodes under the floor are included, with kept_reads == 0. From the
+ * definitions: the direct_reads add up to `classified`, the kept_reads to
+ * `kept`; kept == classified when classified >= min_reads, else 0; the root's
+ * clade_reads == classified whenever classified > 0. */
+typedef struct GhostmTaxonCount {  /* 16 bytes */
+  uint32_t node, clade_reads, direct_reads, kept_reads;
+} GhostmTaxonCount;
+
+typedef struct GhostmTaxonSummary {
+  uint64_t reads;
+  uint64_t classified;  /* node != none */
+  uint64_t kept;        /* final != none */
+  uint64_t moved;       /* final != none && final != node */
+  uint64_t nodes;       /* records */
+  uint64_t nodes_kept;  /* records with clade_reads >= min_reads */
+} GhostmTaxonSummary;
+
+/* TaxonProfileGpu (kernels k_taxon_count, k_taxon_climb, k_taxon_floor,
+ * k_taxon_final, k_taxon_sort_tile, k_taxon_sort_step, k_taxon_emit) needs neither SetQueryGpu nor SetDbGpu.
+ * out[cap] receives the records and *nout their number; final_node[nreads]
+ * (may be NULL) every read's final node; *summary (may be NULL) the totals.
+ * A call with cap == 0 and out == NULL asks for the count: it sets *nout,
+ * writes nothing else and returns 0.
+ * Everything is checked on the host before any upload or launch; a refused
+ * call returns 1, writes nothing, and names its reason:
+ *   "param"     min_reads == 0
+ *   "null"      node null with nreads > 0; nout null; out null with cap > 0
+ *   "taxonomy"  no taxonomy is resident
+ *   "node"      a node that is neither 0xFFFFFFFF nor below nnodes; the read is
+ *               named
+ *   "cap"       more records than cap; the number needed is named. This one is
+ *               known only after the counts, so kernels have run; nothing is
+ *               written.
+ * The work and the bytes read back follow the nodes the sample touches, not
+ * the taxonomy's size: three count arrays of one word per node are allocated
+ * and zeroed when the taxonomy becomes resident (again with every
+ * SetTaxonomyGpu, freed by FreeGpu), a call reaches them through lists of the
+ * nodes it counts on and puts those entries back to zero before it returns, a
+ * refused call included. No call clears, scans or copies a whole array. The
+ * reads go up in batches of at most GHOSTM_PROFILE_BATCH_READS reads (default:
+ * no limit); the counts add up over the batches and the records do not depend
+ * on the cuts. The list of touched nodes is ordered by node index on the
+ * device, and 16 bytes per record come back. */
+int TaxonProfileGpu(uint32_t nreads, const uint32_t node[], uint32_t min_reads, size_t cap, GhostmTaxonCount out[],
+                    size_t *nout, uint32_t final_node[], GhostmTaxonSummary *summary);
+
+/* The same on the host over the taxonomy given, with no device call: the model
+ * the kernels equal exactly, with the same checks and reasons (and
+ * SetTaxonomyGpu's for the taxonomy). */
+int GhostmTaxonProfileHost(uint32_t nnodes, const uint32_t parent[], uint32_t nreads, const uint32_t node[],
+                           uint32_t min_reads, size_t cap, GhostmTaxonCount out[], size_t *nout,
+                           uint32_t final_node[], GhostmTaxonSummary *summary);
+
+/* The counters of the profile, a struct of their own like GhostmReadLcaStats;
+ * GhostmStats keeps its layout. */
+typedef struct GhostmTaxonProfileStats {
+  double seconds_profile;     /* k_taxon_*, device time */
+  uint64_t profile_launches;  /* batches of reads counted (k_taxon_count launches) */
+  uint64_t profile_reads;     /* reads of the calls that were not refused */
+  uint64_t profile_nodes;     /* records of those calls */
+} GhostmTaxonProfileStats;
+
+/* The counters behind the stage-level calls; GhostmStageReadCullStats'
+ * conventions. */
+size_t GhostmStageTaxonProfileStats(GhostmTaxonProfileStats *stats, size_t size);
+
 /* A session without a database: `aln`'s options without -d (giving it is an
  * error). With -i the query chunks are loaded as GhostmSessionCreate loads
  * them; without -i the session starts with neither input and the queries come
@@ -1659,6 +1744,37 @@ size_t GhostmSessionReadLcaBegin(void *session, int frame, uint32_t *read_begin,
 /* The assignment's counters since the last run began; GhostmSessionBandStats'
  * conventions. */
 size_t GhostmSessionReadLcaStats(void *session, GhostmReadLcaStats *stats, size_t size);
+
+/* The sample's taxon profile (the contract is above TaxonProfileGpu), built
+ * from GhostmSessionReadLca(session, frame, ...)'s node field: one read per
+ * ReadLca record. min_reads >= 1 (default 1) is the floor; a change drops only
+ * the profile, not the assignment under it. Returns 0, or 1 ("param"). */
+int GhostmSessionSetProfile(void *session, uint32_t min_reads);
+/* The records, in ascending node index (taxid[] labels them). ReadLca's
+ * conventions: with out NULL returns the count, else copies min(cap, count)
+ * records and returns that; (size_t)-1 on error (GhostmSessionReadLca's).
+ * Computed on first use by one TaxonProfileGpu call; dropped by everything
+ * that drops the assignment and by SetProfile. -y 24 (band paths) and -y 25
+ * (frame paths) print the sample's report, tab separated:
+ *   percent clade_reads kept_reads direct_reads depth taxid parent_taxid
+ * percent is clade_reads of the ReadLca record count `total` in hundredths of
+ * a per cent, (clade_reads * 10000 + total / 2) / total in 64 bits, printed
+ * I.FF. The first line is the unclassified reads (total - kept) when there
+ * are any: taxid 0, depth 0, parent_taxid 0 and all three counts that number.
+ * Then the nodes with clade_reads >= min_reads in depth-first pre-order from
+ * the root, a node's children by clade_reads descending, then taxid ascending;
+ * the root prints its own taxid as its parent's. A run without hits writes an
+ * empty file. `search -R min_reads` sets the floor. */
+size_t GhostmSessionTaxonProfile(void *session, int frame, GhostmTaxonCount *out, size_t cap);
+/* Every read's final node: one entry per ReadLca record. */
+size_t GhostmSessionTaxonProfileFinal(void *session, int frame, uint32_t *final_node, size_t cap);
+/* The profile's totals, sized like GhostmSessionTaxonomyInfo: min(size, the
+ * library's sizeof) bytes are written; returns the library's sizeof, 0 on a
+ * null argument, (size_t)-1 on error. */
+size_t GhostmSessionTaxonProfileSummary(void *session, int frame, GhostmTaxonSummary *summary, size_t size);
+/* The profile's counters since the last run began; GhostmSessionBandStats'
+ * conventions. */
+size_t GhostmSessionTaxonProfileStats(void *session, GhostmTaxonProfileStats *stats, size_t size);
 
 /* The same records resident on the session's GPU, for a device-to-device
  * gather across ranks: copies min(n, cap) records to dst_device
