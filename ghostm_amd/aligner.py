@@ -253,6 +253,48 @@ def stage_band_stats() -> dict:
     return {n: getattr(st, n) for n, _ in st._fields_}
 
 
+def _mask_call(fn, query_seqs, W, src, step, window, trigger, extend):
+    qs = np.array(query_seqs, dtype=np.uint8).reshape(-1)  # a copy: the call masks in place
+    if W <= 0 or qs.size % W:
+        raise ValueError("mask records: bad argument shapes")
+    srcs = np.ascontiguousarray(src, dtype=BAND_SOURCE_DTYPE).reshape(-1)
+    nq = qs.size // W
+    masked = np.zeros(nq, dtype=np.uint32)
+    args = [int(v) for v in (step, window, trigger, extend)]
+    if any(not 0 <= v < 1 << 32 for v in args):
+        raise GhostmError("mask records: an argument beyond 32 bits")
+    u8p, u32p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32)
+    rc = fn(qs.ctypes.data_as(u8p), nq, int(W), len(srcs), srcs.ctypes.data_as(ctypes.POINTER(native.GhostmBandSource)),
+            *args, masked.ctypes.data_as(u32p))
+    if rc != 0:
+        raise GhostmError(native.last_error())
+    return qs, masked
+
+
+def mask_records_host(query_seqs, W, src, step, window=12, trigger=220, extend=250):
+    """The host model of the low-complexity mask (GhostmMaskRecordsHost; no
+    device): query_seqs = uint8 codes of nq records of W, src =
+    BAND_SOURCE_DTYPE records (sources that share no record), step = the tile
+    step. Returns (records, masked): a masked copy of the records (masked
+    letters are code 23) and the letters masked in every record. Raises
+    GhostmError with the reason ("window", "levels", "source", "overlap")."""
+    return _mask_call(native.load().GhostmMaskRecordsHost, query_seqs, W, src, step, window, trigger, extend)
+
+
+def mask_records(query_seqs, W, src, step, window=12, trigger=220, extend=250):
+    """MaskRecordsGpu: the same through the kernels, on a chunk of its own;
+    arguments, result and refusals as mask_records_host (W at most 127)."""
+    return _mask_call(native.load().MaskRecordsGpu, query_seqs, W, src, step, window, trigger, extend)
+
+
+def stage_mask_stats() -> dict:
+    """The mask counters behind the stage-level call (GhostmStageMaskStats)."""
+    lib = native.load()
+    st = native.GhostmMaskStats()
+    lib.GhostmStageMaskStats(ctypes.byref(st), ctypes.sizeof(st))
+    return {n: getattr(st, n) for n, _ in st._fields_}
+
+
 # GhostmHitFrameInfo: one per hit beside Session.hits_frame()'s records
 HIT_FRAME_INFO_DTYPE = np.dtype([("strand", "<u4"), ("read_nt", "<u4"), ("letters", "<u4"), ("shifts", "<u4")])
 # the operations of a frame path's words: PATH_OPS and the two shifts
@@ -932,6 +974,34 @@ class Session:
         if n:
             lib.GhostmSessionQueryLengths(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n)
         return out
+
+    def set_mask(self, window: int = 12, trigger: int = 220, extend: int = 250) -> None:
+        """Low-complexity masking of the query sets made from now on
+        (GhostmSessionSetMask): window 6..32 letters, trigger <= extend in
+        hundredths of a bit, at most 500; set_mask(0) turns it off (the
+        default). It takes effect at the next set_queries*; the current set
+        stays as it is. A refusal ("window", "levels") leaves the old setting."""
+        args = [int(window), int(trigger), int(extend)]
+        if any(not 0 <= v < 1 << 32 for v in args):  # beyond the C arguments' range
+            raise GhostmError("mask: window: or levels: an argument beyond 32 bits")
+        if native.load().GhostmSessionSetMask(self._h, *args) != 0:
+            raise GhostmError(native.last_error())
+
+    def query_masked(self) -> np.ndarray:
+        """The letters masked in every query record, indexed as query_lengths()
+        (GhostmSessionQueryMasked); empty for a set made with masking off."""
+        lib = native.load()
+        n = lib.GhostmSessionQueryMasked(self._h, None, 0)
+        out = np.zeros(n, dtype=np.uint32)
+        if n:
+            lib.GhostmSessionQueryMasked(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), n)
+        return out
+
+    def mask_stats(self) -> dict:
+        """The mask counters of the current query set (GhostmSessionMaskStats)."""
+        st = native.GhostmMaskStats()
+        native.load().GhostmSessionMaskStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        return {n: getattr(st, n) for n, _ in st._fields_}
 
     def query_records(self, chunk: int) -> np.ndarray:
         """The coded records of one query chunk (the bytes of its .seq file),

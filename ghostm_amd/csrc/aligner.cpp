@@ -2187,6 +2187,38 @@ void Session::SetTileGroups(bool on) {
   tile_groups_ = on;
 }
 
+void Session::SetMask(uint32_t window, uint32_t trigger, uint32_t extend) {
+  if (shard_world_ > 1) throw Error("a shard session's query set cannot be replaced");
+  if (window == 0) {
+    mask_ = MaskParams();
+    return;
+  }
+  const std::string why = ValidateMaskParams(window, trigger, extend);
+  if (!why.empty()) throw Error("mask: " + why);
+  mask_.window = window;
+  mask_.trigger = trigger;
+  mask_.extend = extend;
+}
+
+double Session::MaskChunk(QueryData *q, const std::vector<GhostmBandSource> &src, uint32_t step) {
+  q->masked.assign(q->chunk.nseq, 0);
+  GhostmMaskStats one{};
+  DeviceModule::Get().MaskQuery(q->dev, (uint32_t)src.size(), src.data(), step, mask_, q->masked.data(), &one);
+  mask_stats_.seconds_mask += one.seconds_mask;
+  mask_stats_.mask_launches += one.mask_launches;
+  mask_stats_.mask_sources += one.mask_sources;
+  mask_stats_.mask_windows += one.mask_windows;
+  mask_stats_.masked_sources += one.masked_sources;
+  mask_stats_.masked_letters += one.masked_letters;
+  return one.seconds_mask;
+}
+
+std::vector<uint32_t> Session::AllQueryMasked() const {
+  std::vector<uint32_t> out;
+  for (const QueryData &q : queries_) out.insert(out.end(), q.masked.begin(), q.masked.end());
+  return out;
+}
+
 // The cull's input record of final hit h (ReadCull; ReadLca for the hits the
 // cull kept). The reads: consecutive hits of one
 // source record (tiled set) or of one name group (untiled set). A hit's record
@@ -3241,6 +3273,7 @@ void Session::DropQueries() {
   format_launches_ = 0;
   read_seconds_ = 0;
   load_seconds_ = 0;
+  mask_stats_ = GhostmMaskStats{};
   QueryStats();
 }
 
@@ -3292,13 +3325,19 @@ void Session::AddQueryChunk(const QueryRecordView *recs, uint32_t n, uint32_t wi
       if (q) DeviceModule::Get().Free(q->dev);
     }
   } guard{&q};
+  double mask_seconds = 0;
+  if (mask_.window) {  // every record is its own source of `width` letters
+    std::vector<GhostmBandSource> src(q.chunk.nseq);
+    for (uint32_t i = 0; i < q.chunk.nseq; ++i) src[i] = GhostmBandSource{i, 1, 1, width};
+    mask_seconds = MaskChunk(&q, src, width);
+  }
   dev.SetQueryGroups(q.dev, q.group_first.data(), q.group_last.data(), (uint32_t)q.group_first.size());
   q.global_base = queries_.empty() ? 0 : queries_.back().global_base + queries_.back().chunk.nseq;
   format_seconds_ += seconds;
   ++format_launches_;
   queries_.push_back(std::move(q));
   guard.q = nullptr;
-  load_seconds_ += NowSeconds() - t0 - seconds;
+  load_seconds_ += NowSeconds() - t0 - seconds - mask_seconds;
 }
 
 void Session::FinishQuerySet() {
@@ -3449,6 +3488,19 @@ void Session::AddQueryChunkTiled(const QueryRecordView *recs, uint32_t n, uint32
       if (q) DeviceModule::Get().Free(q->dev);
     }
   } guard{&q};
+  double mask_seconds = 0;
+  if (mask_.window) {  // a protein record's kept letters, or each of a read's six frames (tiles six records apart)
+    const uint32_t per = rule.dna ? 6 : 1;
+    std::vector<GhostmBandSource> src;
+    src.reserve((size_t)n * per);
+    for (uint32_t r = 0; r < n; ++r) {
+      const uint32_t m = rule.dna ? len[r] / 3 : len[r];
+      if (m < mask_.window) continue;  // left alone (and a source needs a letter)
+      const uint32_t tiles = TileCount(m, rule.width, rule.step);
+      for (uint32_t f = 0; f < per; ++f) src.push_back(GhostmBandSource{first[r] + f, per, tiles, m});
+    }
+    mask_seconds = MaskChunk(&q, src, rule.step);
+  }
   dev.SetQueryGroups(q.dev, q.group_first.data(), q.group_last.data(), (uint32_t)q.group_first.size());
   q.global_base = queries_.empty() ? 0 : queries_.back().global_base + queries_.back().chunk.nseq;
   if ((uint64_t)q.global_base + q.chunk.nseq > UINT32_MAX) throw Error("set queries: over 4 G tile records");
@@ -3459,7 +3511,7 @@ void Session::AddQueryChunkTiled(const QueryRecordView *recs, uint32_t n, uint32
   ++format_launches_;
   queries_.push_back(std::move(q));
   guard.q = nullptr;
-  load_seconds_ += NowSeconds() - t0 - seconds;
+  load_seconds_ += NowSeconds() - t0 - seconds - mask_seconds;
 }
 
 void Session::SetTiledRecords(const QueryRecordView *recs, uint32_t n, const TiledRule &rule) {

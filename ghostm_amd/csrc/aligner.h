@@ -23,6 +23,7 @@
 #include "../../include/ghostm_hip.h"
 #include "device.h"
 #include "formats.h"
+#include "query_mask.h"
 #include "scoring.h"
 
 namespace ghostm {
@@ -354,6 +355,18 @@ class Session {
   // refused on a shard session.
   void SetTileGroups(bool on);
   bool TileGroups() const { return tile_groups_; }
+  // Low-complexity masking (query_mask.h; the contract is above
+  // GhostmMaskRecordsHost in include/ghostm_hip.h): from the next SetQueries*
+  // call on, every chunk is masked on the device straight after it is
+  // formatted (DeviceModule::MaskQuery). window 0: off, the default; otherwise
+  // throws "window" / "levels" and keeps the old setting. The current set and
+  // its results stay as they are; refused on a shard session.
+  void SetMask(uint32_t window, uint32_t trigger, uint32_t extend);
+  // the letters masked in every query record over the chunks in order; empty
+  // for a set made with masking off
+  std::vector<uint32_t> AllQueryMasked() const;
+  // the mask counters of the current set (all 0 for a set made with masking off)
+  const GhostmMaskStats &MaskStats() const { return mask_stats_; }
   // A taxonomy for the resident database and the taxon of every read (the
   // contract is above ReadLcaGpu in include/ghostm_hip.h; the session calls
   // are described at GhostmSessionSetTaxonomy). SetTaxonomy checks everything,
@@ -408,6 +421,7 @@ class Session {
     std::vector<uint32_t> group_end;   // per query: one past the last query of its name group
     std::vector<uint32_t> group_first, group_last;  // name groups in order
     std::vector<uint32_t> qlen;        // WriteOutput's query length (last non-X + 1)
+    std::vector<uint32_t> masked;      // letters masked per record (SetMask); empty: the chunk was not masked
     uint32_t global_base = 0;          // index of the chunk's first query over all chunks
     // shard sessions: this slice is queries [slice_lo, slice_lo + nseq) of a
     // chunk of chunk_nseq queries, and plan[d] holds the whole chunk's batch
@@ -658,6 +672,10 @@ class Session {
   uint32_t cull_top_k_ = 1, cull_cover_pct_ = 50;
   GhostmReadCullStats cull_stats_{};
   bool tile_groups_ = false;
+  MaskParams mask_;                 // SetMask: the next set's masking (window 0: off)
+  GhostmMaskStats mask_stats_{};    // the current set's
+  // masks chunk q (just formatted) by mask_: its sources, DeviceModule::MaskQuery; returns the device time
+  double MaskChunk(QueryData *q, const std::vector<GhostmBandSource> &src, uint32_t step);
   struct Taxonomy {
     std::vector<uint32_t> taxid, parent, subject_node;
     std::vector<uint32_t> depth;  // per node (the report's column)

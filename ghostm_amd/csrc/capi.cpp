@@ -426,6 +426,30 @@ int GhostmSessionSetBand(void *s, uint32_t band) {
   }
 }
 
+int GhostmSessionSetMask(void *s, uint32_t window, uint32_t trigger, uint32_t extend) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetMask(window, trigger, extend);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionQueryMasked(void *s, uint32_t *masked, size_t cap) {
+  if (!s) return 0;
+  const std::vector<uint32_t> v = static_cast<Session *>(s)->AllQueryMasked();
+  if (!masked) return v.size();
+  const size_t n = std::min(cap, v.size());
+  if (n) std::memcpy(masked, v.data(), n * sizeof(uint32_t));
+  return n;
+}
+
+size_t GhostmSessionMaskStats(void *s, GhostmMaskStats *stats, size_t size) {
+  return CopyStats(s, stats, size, std::mem_fn(&Session::MaskStats));
+}
+
 size_t GhostmSessionBandStats(void *s, GhostmBandStats *stats, size_t size) {
   return CopyStats(s, stats, size, std::mem_fn(&Session::BandStats));
 }
@@ -778,14 +802,31 @@ int GhostmSearchMain(int argc, char **argv) {
   std::string tax_nodes, tax_map;          // -n, -a
   long lca_top = -1, lca_support = -1;     // -p, -P; below 0: the session's defaults
   long profile_min = -1;                   // -R; below 0: the session's default
+  MaskParams mask;                         // -Z w,k1,k2; window 0: no masking
   int style = 0;                           // -y, as aln reads it
   optind = 1;
   opterr = 1;
   int c;
   // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B, -F, -g, -K, -C, -n, -a,
-  // -p, -P, -R
-  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:n:a:p:P:R:")) >= 0) {
+  // -p, -P, -R, -Z
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:n:a:p:P:R:Z:")) >= 0) {
     switch (c) {
+      case 'Z': {  // low-complexity masking: window,trigger,extend
+        unsigned long v[3];
+        const char *at = optarg;
+        for (int k = 0; k < 3; ++k) {
+          char *end = nullptr;
+          if (*at < '0' || *at > '9') return 1;
+          v[k] = strtoul(at, &end, 10);
+          if (end == at || v[k] > 1000 || *end != (k < 2 ? ',' : '\0')) return 1;
+          at = end + 1;
+        }
+        if (!ValidateMaskParams((uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2]).empty()) return 1;
+        mask.window = (uint32_t)v[0];
+        mask.trigger = (uint32_t)v[1];
+        mask.extend = (uint32_t)v[2];
+        break;
+      }
       case 'R': {  // the profile's floor, 1 or more
         char *end = nullptr;
         const long long v = strtoll(optarg, &end, 10);
@@ -881,6 +922,7 @@ int GhostmSearchMain(int argc, char **argv) {
     if (lca_top >= 0 || lca_support >= 0)
       session.SetLca(lca_top >= 0 ? (uint32_t)lca_top : 10u, lca_support >= 0 ? (uint32_t)lca_support : 100u);
     if (profile_min >= 0) session.SetProfile((uint32_t)profile_min);
+    if (mask.window) session.SetMask(mask.window, mask.trigger, mask.extend);
     for (size_t k = 0; k < pos.size(); k += 2) {
       try {
         { std::ofstream touch(pos[k + 1].c_str()); }
@@ -900,6 +942,11 @@ int GhostmSearchMain(int argc, char **argv) {
           std::cout << "# " << pos[k] << " queries " << st.queries << " candidates " << st.candidates << " hits "
                     << st.hits << " seconds " << st.seconds_total << " query format " << st.seconds_query_format
                     << std::endl;
+          if (mask.window) {
+            const GhostmMaskStats &ms = session.MaskStats();
+            std::cout << "# " << pos[k] << " masked letters " << ms.masked_letters << " sources " << ms.masked_sources
+                      << " of " << ms.mask_sources << " seconds " << ms.seconds_mask << std::endl;
+          }
         }
       } catch (std::exception &e) {
         std::cerr << e.what() << std::endl;

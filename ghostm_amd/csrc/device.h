@@ -41,6 +41,7 @@ struct GapConfig {
 // Device-resident chunk handles (opaque to callers).
 struct DevQuery;
 struct DevDb;
+struct MaskParams;  // query_mask.h
 
 // One hit chosen by the device merge (K4), after its traceback (K3):
 // subject-relative coordinates, ml = (aln_len << 8) | matches.
@@ -112,6 +113,7 @@ struct DeviceTimes {
   GhostmReadCullStats cull{};            // k_read_cull
   GhostmReadLcaStats lca{};              // k_read_lca*
   GhostmTaxonProfileStats profile{};     // k_taxon_*
+  GhostmMaskStats mask{};                // k_mask_windows + k_mask_apply
 };
 
 class DeviceModule {
@@ -152,6 +154,15 @@ class DeviceModule {
   DevQuery *FormatQueryTiled(const uint8_t *raw, uint64_t raw_len, const uint64_t *off, const uint32_t *len,
                              const uint32_t *first, uint32_t n, uint32_t width, bool dna, uint32_t step,
                              uint32_t *qlen, double *seconds);
+  // The low-complexity mask of a resident chunk (query_mask.h; kernels:
+  // query_mask.hip), in place on the main stream, straight after FormatQuery or
+  // FormatQueryTiled: the masked letters of the nsrc sources become X in every
+  // tile record that covers them. Everything is checked before any upload or
+  // launch (throws ValidateMask's reason). Only masked[nseq], the letters
+  // stored into every record, comes back. *call (may be null): this call's
+  // counters, seconds_mask the two kernels' device time.
+  void MaskQuery(DevQuery *q, uint32_t nsrc, const GhostmBandSource *src, uint32_t step, const MaskParams &params,
+                 uint32_t *masked, GhostmMaskStats *call);
   // A resident chunk's coded records (nseq * L bytes) back on the host.
   size_t QueryBytes(const DevQuery *q) const;
   void DownloadQuery(const DevQuery *q, uint8_t *dst);

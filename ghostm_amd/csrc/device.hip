@@ -30,6 +30,7 @@
 #include "read_pileup.h"
 #include "pileup_plan.h"
 #include "qformat.h"
+#include "query_mask.h"
 #include "query_tiles.h"
 #include "score_tasks.h"
 
@@ -344,6 +345,10 @@ struct DeviceModule::Impl {
   // lengths, the kernels' tables; the kernel's events
   DevBuf qf_raw, qf_off, qf_len, qf_qlen, qf_tab, qf_first;  // qf_first: FormatQueryTiled's first output rows
   hipEvent_t ev_q0 = nullptr, ev_q1 = nullptr;
+  // MaskQuery: the sources, their flag-word offsets, the two flag arrays, the
+  // records' counts followed by the counter slots; the kernels' events
+  DevBuf mask_src, mask_off, mask_bits, mask_out;
+  hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;
   // FormatDb: the chunk's packed letters, the index build's (key, position)
   // pairs with their ping-pong copies and its scan arrays; the kernels' events
   // (coding: ev_d0..ev_d1, index: ev_d1..ev_d2), the word that comes back
@@ -442,7 +447,7 @@ void DeviceModule::Bind(int device) {
 #endif
   for (hipEvent_t *e : {&impl_->ev0, &impl_->ev1, &impl_->ev_m0, &impl_->ev_m1, &impl_->ev_t0, &impl_->ev_t1, &impl_->ev_tk,
                         &impl_->ev_done, &impl_->ev_tasks, &impl_->ev_s0, &impl_->ev_s1, &impl_->ev_nb, &impl_->ev_q0,
-                        &impl_->ev_q1, &impl_->ev_d0, &impl_->ev_d1, &impl_->ev_d2})
+                        &impl_->ev_q1, &impl_->ev_d0, &impl_->ev_d1, &impl_->ev_d2, &impl_->ev_k0, &impl_->ev_k1})
     HIP_CHECK(hipEventCreate(e));
   for (hipEvent_t &e : impl_->stage_ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   HIP_CHECK(hipFuncSetAttribute((const void *)kern::k_seed<1024, 16384, false>,
@@ -701,6 +706,65 @@ DevQuery *DeviceModule::FormatQueryTiled(const uint8_t *raw, uint64_t raw_len, c
     *seconds = ms * 1e-3;
   }
   return q.release();
+}
+
+static_assert(sizeof(GhostmBandSource) == 16, "the sources are uploaded as they are");
+
+void DeviceModule::MaskQuery(DevQuery *q, uint32_t nsrc, const GhostmBandSource *src, uint32_t step,
+                             const MaskParams &params, uint32_t *masked, GhostmMaskStats *call) {
+  if (!impl_) throw Error("mask: the device module is not bound to a device");
+  Use();
+  if (call) *call = GhostmMaskStats{};
+  if (!q || (q->nseq && !masked) || (nsrc && !src)) throw Error("mask: null: an array");
+  const std::string why = ValidateMask(q->nseq, q->L, nsrc, src, step, params.window, params.trigger, params.extend);
+  if (!why.empty()) throw Error("mask: " + why);
+  std::fill(masked, masked + q->nseq, 0u);
+  const MaskPlan plan = PlanMask(nsrc, src, params.window);
+  const size_t words = plan.word_off[nsrc];
+  if (words == 0) return;  // no source has a window
+  Impl &I = *impl_;
+  hipStream_t st = S(stream_);
+  const size_t out_bytes = ((size_t)q->nseq * 4 + 7) / 8 * 8;  // the counters behind the counts, 8-byte aligned
+  I.mask_src.Reserve((size_t)nsrc * sizeof(GhostmBandSource));
+  I.mask_off.Reserve(((size_t)nsrc + 1) * 4);
+  I.mask_bits.Reserve(words * 16);
+  const size_t slot_bytes = (size_t)kMaskCounterSlots * kMaskCounterWords * 8;
+  I.mask_out.Reserve(out_bytes + slot_bytes);
+  StagedUpload(I.mask_src.p, src, (size_t)nsrc * sizeof(GhostmBandSource));
+  StagedUpload(I.mask_off.p, plan.word_off.data(), ((size_t)nsrc + 1) * 4);
+  HIP_CHECK(hipMemsetAsync(I.mask_out.p, 0, out_bytes + slot_bytes, st));
+  uint64_t *counters = reinterpret_cast<uint64_t *>(I.mask_out.as<uint8_t>() + out_bytes);
+  HIP_CHECK(hipEventRecord(I.ev_k0, st));
+  LaunchQueryMask(stream_, q->seq.as<uint8_t>(), q->L, I.mask_src.as<GhostmBandSource>(), I.mask_off.as<uint32_t>(), nsrc,
+                  step, params, I.mask_bits.as<uint64_t>(), I.mask_bits.as<uint64_t>() + words, I.mask_out.as<uint32_t>(),
+                  counters);
+  HIP_CHECK(hipEventRecord(I.ev_k1, st));
+  std::vector<uint64_t> slots((size_t)kMaskCounterSlots * kMaskCounterWords);
+  HIP_CHECK(hipMemcpyAsync(masked, I.mask_out.p, (size_t)q->nseq * 4, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(slots.data(), counters, slot_bytes, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  uint64_t got[2] = {0, 0};
+  for (uint32_t k = 0; k < kMaskCounterSlots; ++k) {
+    got[0] += slots[(size_t)k * kMaskCounterWords];
+    got[1] += slots[(size_t)k * kMaskCounterWords + 1];
+  }
+  float ms = 0;
+  HIP_CHECK(hipEventElapsedTime(&ms, I.ev_k0, I.ev_k1));
+  GhostmMaskStats one{};
+  one.seconds_mask = ms * 1e-3;
+  one.mask_launches = 1;
+  one.mask_sources = plan.sources;
+  one.mask_windows = plan.windows;
+  one.masked_sources = got[0];
+  one.masked_letters = got[1];
+  GhostmMaskStats &t = times_.mask;
+  t.seconds_mask += one.seconds_mask;
+  t.mask_launches += 1;
+  t.mask_sources += one.mask_sources;
+  t.mask_windows += one.mask_windows;
+  t.masked_sources += one.masked_sources;
+  t.masked_letters += one.masked_letters;
+  if (call) *call = one;
 }
 
 size_t DeviceModule::QueryBytes(const DevQuery *q) const { return (size_t)q->nseq * q->L; }
@@ -4118,6 +4182,32 @@ int TaxonProfileGpu(uint32_t nreads, const uint32_t node[], uint32_t min_reads, 
 
 size_t GhostmStageTaxonProfileStats(GhostmTaxonProfileStats *stats, size_t size) {
   return StageStats(&DeviceTimes::profile, stats, size);
+}
+
+int MaskRecordsGpu(uint8_t *query_seqs, uint32_t nq, uint32_t L, uint32_t nsrc, const GhostmBandSource src[],
+                   uint32_t step, uint32_t window, uint32_t trigger, uint32_t extend, uint32_t masked[]) {
+  return UnboundStageCall("MaskRecordsGpu", [&](DeviceModule &m) {
+    if ((nq && (!query_seqs || !masked)) || (nsrc && !src)) throw Error("null: an array");
+    std::string why = ValidateMask(nq, L, nsrc, src, step, window, trigger, extend);
+    if (why.empty() && L > kMaxQueryLength) why = "source: a record width over 127";
+    if (!why.empty()) throw Error(why);
+    if (nq == 0) return;
+    // a chunk of its own, freed on every way out
+    std::unique_ptr<DevQuery, std::function<void(DevQuery *)>> q(m.UploadQuery(query_seqs, nq, L),
+                                                                 [&m](DevQuery *p) { m.Free(p); });
+    std::vector<uint32_t> count(nq);
+    MaskParams params;
+    params.window = window;
+    params.trigger = trigger;
+    params.extend = extend;
+    m.MaskQuery(q.get(), nsrc, src, step, params, count.data(), nullptr);
+    m.DownloadQuery(q.get(), query_seqs);
+    std::copy(count.begin(), count.end(), masked);
+  });
+}
+
+size_t GhostmStageMaskStats(GhostmMaskStats *stats, size_t size) {
+  return StageStats(&DeviceTimes::mask, stats, size);
 }
 
 }  // extern "C"

@@ -58,6 +58,9 @@ static int Usage() {
             << "        the unclassified reads (taxid 0), then the taxa with at least minReads (default 1) reads in their\n"
             << "        clade, depth first from the root, children by clade_reads; the reads of a smaller clade count\n"
             << "        for the first ancestor that has minReads\n"
+            << "       [-Z window,trigger,extend]: low-complexity stretches of the reads masked with X before the search\n"
+            << "        (SEG's raw segments; window 6..32, levels in hundredths of a bit, 0 <= trigger <= extend <= 500;\n"
+            << "        e.g. -Z 12,220,250)\n"
             << "synth: ghostm synth -d db.fasta -q queries.fasta [-n nq] [-N dbResidues] [-s seed]\n";
   return 1;
 }

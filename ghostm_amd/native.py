@@ -90,6 +90,19 @@ class GhostmBandSource(ctypes.Structure):
     ]
 
 
+class GhostmMaskStats(ctypes.Structure):
+    """the counters of the mask pass (GhostmSessionMaskStats, GhostmStageMaskStats)."""
+
+    _fields_ = [
+        ("seconds_mask", ctypes.c_double),
+        ("mask_launches", ctypes.c_uint64),
+        ("mask_sources", ctypes.c_uint64),
+        ("mask_windows", ctypes.c_uint64),
+        ("masked_sources", ctypes.c_uint64),
+        ("masked_letters", ctypes.c_uint64),
+    ]
+
+
 class GhostmBandStats(ctypes.Structure):
     """the counters of the band pass (GhostmSessionBandStats, GhostmStageBandStats)."""
 
@@ -471,6 +484,11 @@ SIGNATURES = {
                                     u32p, c_uint32, c_uint32, c_uint32, c_int, c_int, POINTER(GhostmHitPath), u32p,
                                     c_size_t, POINTER(c_size_t)]),
     "GhostmStageBandStats": (c_size_t, [POINTER(GhostmBandStats), c_size_t]),
+    "GhostmMaskRecordsHost": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, POINTER(GhostmBandSource),
+                                      c_uint32, c_uint32, c_uint32, c_uint32, u32p]),
+    "MaskRecordsGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, POINTER(GhostmBandSource),
+                               c_uint32, c_uint32, c_uint32, c_uint32, u32p]),
+    "GhostmStageMaskStats": (c_size_t, [POINTER(GhostmMaskStats), c_size_t]),
     "FrameAlignGpu": (c_int, [c_uint32, POINTER(GhostmBandSource), POINTER(ctypes.c_int32), u32p, u32p, c_uint32,
                               c_uint32, c_uint32, c_int, c_int, c_int, POINTER(GhostmHitPath), u32p, c_size_t,
                               POINTER(c_size_t)]),
@@ -559,6 +577,9 @@ SIGNATURES = {
     "GhostmSessionBandOps": (c_size_t, [c_void_p, u32p, c_size_t]),
     "GhostmSessionSetBand": (c_int, [c_void_p, c_uint32]),
     "GhostmSessionBandStats": (c_size_t, [c_void_p, POINTER(GhostmBandStats), c_size_t]),
+    "GhostmSessionSetMask": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32]),
+    "GhostmSessionQueryMasked": (c_size_t, [c_void_p, u32p, c_size_t]),
+    "GhostmSessionMaskStats": (c_size_t, [c_void_p, POINTER(GhostmMaskStats), c_size_t]),
     "GhostmSessionHitsFrame": (c_size_t, [c_void_p, POINTER(GhostmHitPath), c_size_t]),
     "GhostmSessionFrameOps": (c_size_t, [c_void_p, u32p, c_size_t]),
     "GhostmSessionFrameInfo": (c_size_t, [c_void_p, POINTER(GhostmHitFrameInfo), c_size_t]),

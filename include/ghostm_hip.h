@@ -680,6 +680,93 @@ typedef struct GhostmBandStats {
  * bytes and returns the library's sizeof; 0 on a null argument. */
 size_t GhostmStageBandStats(GhostmBandStats *stats, size_t size);
 
+/* Low-complexity masking of query records. Translated reads are full of
+ * low-complexity stretches (poly-Q and poly-A runs, collagen-like repeats,
+ * frames of AT-rich DNA); a read whose only similarity to a subject is such a
+ * stretch would be seeded, aligned, kept by the cull and counted in a clade.
+ * This pass hard-masks such stretches before seeding, as blastx -seg yes does:
+ * a masked letter becomes X (code 23) in the resident query records, and every
+ * pass downstream sees the same letters with no change of its own (K1 finds no
+ * seed there, the DP passes and the rows score X, the pile-ups count X).
+ *
+ * The rule is the first stage of SEG (Wootton and Federhen), the raw segments,
+ * in integer arithmetic, so that host and device agree byte for byte. SEG's
+ * second stage, which trims each raw segment to its least probable sub-stretch,
+ * is not done: a segment is masked whole.
+ *
+ * Parameters: window w, 6..32; trigger k1 and extend k2 in hundredths of a bit,
+ * 0 <= k1 <= k2 <= 500. The customary values are 12, 220, 250.
+ *
+ * A source is BandAlignGpu's: a protein record's kept letters, or one frame of
+ * a DNA read, m letters read through its tile records (letter p lies in tile
+ * min(p / step, tiles - 1)). On an untiled set every record is its own source
+ * with m = W, the record width.
+ *   T[c] = lround(1024 * c * log2(c)) for c = 1..w, T[0] = 0 (w = 12: 0, 0,
+ *          2048, 4869, 8192, 11888, 15882, 20123, 24576, 29214, 34017, 38967,
+ *          44052)
+ *   window i covers letters [i, i + w), 0 <= i <= m - w. It is evaluated only
+ *          when all its codes are below 23; B, J and Z are letters of their own.
+ *          A window with an X or a '*' in it is neither low nor a trigger, so
+ *          the stop runs of a DNA frame and the padding of a record never mask
+ *          a neighbour, and they break runs.
+ *   S = the sum over the letters a of T[count of a in the window],
+ *   d = 100 * (T[w] - S); the window is low when d <= k2 * 1024 * w and a
+ *          trigger when d <= k1 * 1024 * w
+ *   a maximal run of consecutive low windows i..j that holds at least one
+ *          trigger is a segment: letters [i, j + w) are masked
+ * A masked letter is stored as 23 into every tile record that covers it, so
+ * overlapping tiles stay consistent. '*' is never inside an evaluated window and
+ * is never rewritten. A source with m < w is left alone.
+ *
+ * The records' lengths are not recomputed: GhostmSessionQueryLengths, the
+ * E-value's query length and the band pass's m stay those of the unmasked set,
+ * as BLAST prices a filtered query.
+ *
+ * GhostmMaskRecordsHost: the rule on the host, letter by letter, with no device
+ * call (the model the kernels are checked against). query_seqs = nq records of
+ * L codes, changed in place; masked[nq] receives the letters stored as 23 into
+ * every record (a letter under two tiles counts in both). Everything is checked
+ * first; a refused call leaves the records and masked untouched and names its
+ * reason in GhostmGetLastError:
+ *   "window"   window outside 6..32
+ *   "levels"   not 0 <= trigger <= extend <= 500
+ *   "source"   BandAlignGpu's: a record outside the nq given; tiles == 0 or
+ *              letters == 0; tiles disagrees with letters, L and step; step 0 or
+ *              over L; L == 0 (MaskRecordsGpu: L over 127 too)
+ *   "overlap"  two sources share a record
+ *   "null"     a null array with nq or nsrc > 0 */
+int GhostmMaskRecordsHost(uint8_t *query_seqs, uint32_t nq, uint32_t L, uint32_t nsrc,
+                          const GhostmBandSource src[], uint32_t step, uint32_t window, uint32_t trigger,
+                          uint32_t extend, uint32_t masked[]);
+
+/* The same on the GPU (kernels k_mask_windows + k_mask_apply), stage level: the
+ * records are uploaded as a chunk of their own (SetQueryGpu's chunk is not
+ * touched), masked in place and brought back with masked[]; it exists to be
+ * compared with the model byte for byte. The same checks and reasons, all made
+ * before any upload or launch. k_mask_windows only reads the records (one wave
+ * per source, one lane per window, 64 windows at a time from 64 + w - 1 codes
+ * staged in LDS) and writes every window's low and trigger flag; k_mask_apply
+ * only writes them (one wave per source resolves the runs over the flag words
+ * with a carry in both directions, widens them by w - 1 letters and stores 23
+ * into every covering tile). So every window sees the unmasked letters. */
+int MaskRecordsGpu(uint8_t *query_seqs, uint32_t nq, uint32_t L, uint32_t nsrc, const GhostmBandSource src[],
+                   uint32_t step, uint32_t window, uint32_t trigger, uint32_t extend, uint32_t masked[]);
+
+/* The counters of the mask pass. A struct of their own, like GhostmBandStats:
+ * GhostmStats keeps its layout. */
+typedef struct GhostmMaskStats {
+  double seconds_mask;       /* k_mask_windows + k_mask_apply, device time */
+  uint64_t mask_launches;    /* passes launched (both kernels): one per chunk that has a window */
+  uint64_t mask_sources;     /* sources with at least one window (m >= w) */
+  uint64_t mask_windows;
+  uint64_t masked_sources;   /* sources with a masked letter */
+  uint64_t masked_letters;   /* letters of the sources masked (each once, under however many tiles) */
+} GhostmMaskStats;
+
+/* The mask counters behind the stage-level call; GhostmStageBandStats'
+ * conventions. */
+size_t GhostmStageMaskStats(GhostmMaskStats *stats, size_t size);
+
 /* Frameshift-aware read-level alignments of DNA reads. BandAlignGpu aligns one
  * frame; after a single-nucleotide insertion or deletion the true alignment of
  * a read continues in another frame of the same strand, and this pass follows
@@ -1546,6 +1633,27 @@ int GhostmSessionSetBand(void *session, uint32_t band);
 /* The band counters of the session since its last run (all 0 until the band
  * results are asked for); the size convention of GhostmSessionDbStats. */
 size_t GhostmSessionBandStats(void *session, GhostmBandStats *stats, size_t size);
+
+/* Low-complexity masking of the session's query sets (the rule above
+ * GhostmMaskRecordsHost). window 0 turns masking off, which is the default;
+ * otherwise window 6..32 and 0 <= trigger <= extend <= 500 (a refusal names
+ * "window" or "levels" and leaves the old setting). The setting takes effect at
+ * the next GhostmSessionSetQueries* call: each chunk is masked on the device
+ * straight after it is formatted, and only 4 bytes a record come back. The
+ * current set and its results stay as they are. Refused on a shard session, as
+ * the setters are. A set loaded from `qry`'s files is never masked.
+ * GhostmSessionQueryRecords shows the masked records as they are;
+ * GhostmSessionQueryLengths stays that of the unmasked set. */
+int GhostmSessionSetMask(void *session, uint32_t window, uint32_t trigger, uint32_t extend);
+
+/* The letters masked in every query record, in the indexing of
+ * GhostmSessionQueryLengths; the NULL/cap convention of GhostmSessionHits. 0
+ * entries for a set made with masking off. */
+size_t GhostmSessionQueryMasked(void *session, uint32_t *masked, size_t cap);
+
+/* The mask counters of the session's current query set (all 0 for a set made
+ * with masking off); the size convention of GhostmSessionDbStats. */
+size_t GhostmSessionMaskStats(void *session, GhostmMaskStats *stats, size_t size);
 
 /* The frameshift-aware read-level path of every hit of the last run (record i
  * belongs to hit i) and the run-length words they index, in hit order (the
