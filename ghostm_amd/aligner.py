@@ -680,6 +680,64 @@ def stage_read_lca_stats() -> dict:
     return {n: getattr(st, n) for n, _ in st._fields_}
 
 
+# GhostmPairHit and GhostmPairOut (include/ghostm_hip.h)
+PAIR_HIT_DTYPE = np.dtype([("subject", "<u4"), ("node", "<u4"), ("score", "<u4"), ("q_lo", "<u4"), ("q_hi", "<u4"),
+                           ("s_lo", "<u4"), ("s_hi", "<u4"), ("strand", "<u4")])
+PAIR_OUT_DTYPE = np.dtype([("joined", "<u4"), ("mates", "<u4"), ("best_score", "<u4"), ("best_span", "<u4")])
+
+
+def _pair_join_call(fn, pair_begin, offset, hits, max_span, orient, out):
+    """PairJoinGpu and GhostmPairJoinHost take the same arguments. out: the
+    (cand, partner, pairs) arrays the results go to (the refusal tests pass
+    their own), or None."""
+    pb = np.ascontiguousarray(pair_begin, dtype=np.uint32).reshape(-1)
+    off = np.ascontiguousarray(offset, dtype=np.uint32).reshape(-1)
+    h = np.ascontiguousarray(hits, dtype=PAIR_HIT_DTYPE).reshape(-1)
+    npairs = (max(len(pb), 1) - 1) // 2
+    if len(pb) not in (0, 2 * npairs + 1) or len(off) != npairs:
+        raise ValueError("pair join: pair_begin has 2 * npairs + 1 entries and offset npairs")
+    if out is None:
+        out = (np.zeros(len(h), dtype=LCA_HIT_DTYPE), np.full(len(h), 0xFFFFFFFF, dtype=np.uint32),
+               np.zeros(npairs, dtype=PAIR_OUT_DTYPE))
+    cand, partner, pairs = out
+    if (cand.dtype != LCA_HIT_DTYPE or partner.dtype != np.uint32 or pairs.dtype != PAIR_OUT_DTYPE
+            or not (cand.flags.c_contiguous and partner.flags.c_contiguous and pairs.flags.c_contiguous)
+            or len(cand) < len(h) or len(partner) < len(h) or len(pairs) < npairs):
+        raise ValueError("pair join: out must be contiguous (LCA_HIT_DTYPE per hit, uint32 per hit, PAIR_OUT_DTYPE per pair)")
+    rc = fn(npairs, pb.ctypes.data_as(_U32P) if len(pb) else None, off.ctypes.data_as(_U32P) if len(off) else None,
+            len(h), h.ctypes.data_as(ctypes.POINTER(native.GhostmPairHit)) if len(h) else None, int(max_span),
+            int(orient), cand.ctypes.data_as(ctypes.POINTER(native.GhostmLcaHit)) if len(cand) else None,
+            partner.ctypes.data_as(_U32P) if len(partner) else None,
+            pairs.ctypes.data_as(ctypes.POINTER(native.GhostmPairOut)) if len(pairs) else None)
+    if rc != 0:
+        raise GhostmError(native.last_error())
+    return cand, partner, pairs
+
+
+def pair_join_host(pair_begin, offset, hits, max_span=1000, orient=0, out=None):
+    """The host model of the mate-pair join (GhostmPairJoinHost; no device):
+    pair p's hits are hits[pair_begin[2p]:pair_begin[2p + 1]] of mate 1 and
+    hits[pair_begin[2p + 1]:pair_begin[2p + 2]] of mate 2 (PAIR_HIT_DTYPE),
+    offset[p] mate 1's length. Returns (cand, partner, pairs): one
+    LCA_HIT_DTYPE record and one partner index per hit, one PAIR_OUT_DTYPE
+    record per pair; hits outside every pair keep out's bytes."""
+    return _pair_join_call(native.load().GhostmPairJoinHost, pair_begin, offset, hits, max_span, orient, out)
+
+
+def pair_join(pair_begin, offset, hits, max_span=1000, orient=0, out=None):
+    """PairJoinGpu (k_pair_join); arguments and result as pair_join_host.
+    Needs no resident chunk."""
+    return _pair_join_call(native.load().PairJoinGpu, pair_begin, offset, hits, max_span, orient, out)
+
+
+def stage_pair_join_stats() -> dict:
+    """The join's counters behind the stage-level calls (GhostmStagePairJoinStats)."""
+    lib = native.load()
+    st = native.GhostmPairJoinStats()
+    lib.GhostmStagePairJoinStats(ctypes.byref(st), ctypes.sizeof(st))
+    return {n: getattr(st, n) for n, _ in st._fields_}
+
+
 # GhostmTaxonCount (include/ghostm_hip.h)
 TAXON_COUNT_DTYPE = np.dtype([("node", "<u4"), ("clade_reads", "<u4"), ("direct_reads", "<u4"), ("kept_reads", "<u4")])
 
@@ -1405,6 +1463,81 @@ class Session:
         """The assignment's counters since the last run (GhostmSessionReadLcaStats)."""
         st = native.GhostmReadLcaStats()
         native.load().GhostmSessionReadLcaStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        return {name: getattr(st, name) for name, _ in st._fields_}
+
+    def set_mates(self, on: bool = True, max_insert: int = 1000) -> None:
+        """Declares source records 2i and 2i + 1 of a tiled query set to be
+        mates (GhostmSessionSetMates); max_insert is the longest fragment in
+        read units (nt on a DNA set). Off by default. With mates on,
+        taxon_profile() counts fragments. A change drops only the pair results."""
+        m = int(max_insert)
+        if not 1 <= m <= 1 << 24:  # GhostmSessionSetMates' range; an int beyond uint32 would wrap
+            raise GhostmError(f"mates: param: max_insert {m} outside 1..2^24")
+        if native.load().GhostmSessionSetMates(self._h, int(bool(on)), m) != 0:
+            raise GhostmError(native.last_error())
+
+    def set_queries_fasta_mates(self, path1: str, path2: str, width: int = 75, dna: bool = False, chunk_mb: int = 0,
+                                tile_step: int = 64, max_len: int = 0) -> int:
+        """The tiled set_queries_fasta over two files of mates, interleaved
+        record by record (GhostmSessionSetQueriesFastaMatesTiled). Files of
+        different record counts are refused and leave the old set in place."""
+        cut = ctypes.c_uint64(0)
+        rc = native.load().GhostmSessionSetQueriesFastaMatesTiled(
+            self._h, str(path1).encode(), str(path2).encode(), int(width), int(bool(dna)), int(chunk_mb), int(max_len),
+            int(tile_step), ctypes.byref(cut))
+        if rc != 0:
+            raise GhostmError(native.last_error())
+        return int(cut.value)
+
+    def pair_join(self, frame: bool = False):
+        """The join of every pair's hits from read_cull(frame)
+        (GhostmSessionPairJoin, GhostmSessionPairJoinPairs). Returns (cand,
+        partner, pairs, pair_begin, pair_record): one LCA_HIT_DTYPE candidate
+        and one partner (an index of hits(), or 0xFFFFFFFF) per hit, one
+        PAIR_OUT_DTYPE record per pair with a hit, the pairs' borders in hits()
+        (two per pair and the end) and mate 1's source record. Computed on
+        first use."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        f = int(bool(frame))
+        n = lib.GhostmSessionPairJoin(self._h, f, None, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        cand = np.zeros(n, dtype=LCA_HIT_DTYPE)
+        partner = np.full(n, 0xFFFFFFFF, dtype=np.uint32)
+        if n and lib.GhostmSessionPairJoin(self._h, f, cand.ctypes.data_as(ctypes.POINTER(native.GhostmLcaHit)),
+                                           partner.ctypes.data_as(_U32P), n) == bad:
+            raise GhostmError(native.last_error())
+        m = lib.GhostmSessionPairJoinPairs(self._h, f, None, None, None, 0)
+        if m == bad:
+            raise GhostmError(native.last_error())
+        pairs = np.zeros(m, dtype=PAIR_OUT_DTYPE)
+        begin = np.zeros(2 * m + 1, dtype=np.uint32)
+        record = np.zeros(m, dtype=np.uint32)
+        if lib.GhostmSessionPairJoinPairs(self._h, f, pairs.ctypes.data_as(ctypes.POINTER(native.GhostmPairOut)),
+                                          begin.ctypes.data_as(_U32P), record.ctypes.data_as(_U32P), m) == bad:
+            raise GhostmError(native.last_error())
+        return cand, partner, pairs, begin, record
+
+    def pair_lca(self, frame: bool = False) -> np.ndarray:
+        """One LCA_OUT_DTYPE record per pair of pair_join(frame)
+        (GhostmSessionPairLca): the taxon of the fragment from the joined
+        candidates, under set_lca()'s parameters. Computed on first use."""
+        lib = native.load()
+        bad = ctypes.c_size_t(-1).value
+        f = int(bool(frame))
+        n = lib.GhostmSessionPairLca(self._h, f, None, 0)
+        if n == bad:
+            raise GhostmError(native.last_error())
+        out = np.zeros(n, dtype=LCA_OUT_DTYPE)
+        if n and lib.GhostmSessionPairLca(self._h, f, out.ctypes.data_as(ctypes.POINTER(native.GhostmLcaOut)), n) == bad:
+            raise GhostmError(native.last_error())
+        return out
+
+    def pair_join_stats(self) -> dict:
+        """The join's counters since the last run (GhostmSessionPairJoinStats)."""
+        st = native.GhostmPairJoinStats()
+        native.load().GhostmSessionPairJoinStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
         return {name: getattr(st, name) for name, _ in st._fields_}
 
     def set_profile(self, min_reads: int = 1) -> None:

@@ -30,6 +30,7 @@
 #include "db_set.h"
 #include "query_set.h"
 #include "query_tiles.h"
+#include "pair_join.h"
 #include "read_lca.h"
 #include "taxon_profile.h"
 #include "worker_pool.h"
@@ -1503,7 +1504,7 @@ const LineFormat &Session::Format() {
       opt_.output_style == 20 || opt_.output_style == 21;
   // -y 10, -y 11 and -y 16 to -y 19 replace the hit lines after the run: style 1's lines, which need no E-value, stand in
   const bool pileup = opt_.output_style == 10 || opt_.output_style == 11 || (opt_.output_style >= 16 && opt_.output_style <= 19) ||
-                      (opt_.output_style >= 22 && opt_.output_style <= 25);  // and the taxon lines, the profile
+                      (opt_.output_style >= 22 && opt_.output_style <= 27);  // and the taxon lines, the profile, the pairs
   if (!format_) format_.reset(new LineFormat(tabular ? 0 : pileup ? 1 : opt_.output_style, opt_.karlin, 4095));
   return *format_;
 }
@@ -1529,7 +1530,8 @@ static_assert(SecondsThenCounters<GhostmBandStats, 5>(&GhostmBandStats::seconds_
                   SecondsThenCounters<GhostmReadPileupStats, 6>(&GhostmReadPileupStats::seconds_read_pileup) &&
                   SecondsThenCounters<GhostmReadCullStats, 7>(&GhostmReadCullStats::seconds_cull) &&
                   SecondsThenCounters<GhostmReadLcaStats, 6>(&GhostmReadLcaStats::seconds_lca) &&
-                  SecondsThenCounters<GhostmTaxonProfileStats, 4>(&GhostmTaxonProfileStats::seconds_profile),
+                  SecondsThenCounters<GhostmTaxonProfileStats, 4>(&GhostmTaxonProfileStats::seconds_profile) &&
+                  SecondsThenCounters<GhostmPairJoinStats, 6>(&GhostmPairJoinStats::seconds_pair),
               "a pass's counters: a double, then 8-byte counters");
 static_assert(offsetof(GhostmBandStats, seconds_band) == 0 && offsetof(GhostmFrameStats, seconds_frame) == 0 &&
                   offsetof(GhostmReadRowsStats, seconds_read_rows) == 0 &&
@@ -1926,6 +1928,8 @@ void Session::DropLevel(int lv, LevelStage from) {
   }
   if (from != kFromLca) cull_[lv].Drop();
   lca_[lv].Drop();
+  pair_[lv].Drop();  // made from the cull's records and the taxonomy's nodes
+  pair_lca_[lv].Drop();
   profile_[lv].Drop();
 }
 
@@ -2501,6 +2505,148 @@ void Session::FormatLca(bool frame) {
   ReplaceText(&out);
 }
 
+void Session::SetMates(bool on, uint32_t max_insert) {
+  if (shard_world_ > 1) throw Error("a shard session has no mates");
+  if (max_insert < 1 || max_insert > kPairValueLimit)
+    throw Error("mates: param: max_insert " + std::to_string(max_insert) + " outside 1..2^24");
+  if (on == mates_ && max_insert == mates_max_insert_) return;
+  mates_ = on;
+  mates_max_insert_ = max_insert;
+  for (int lv = 0; lv < 2; ++lv) {  // the pair results and what is counted from them; the cull and the per-read taxa stay
+    pair_[lv].Drop();
+    pair_lca_[lv].Drop();
+    profile_[lv].Drop();
+  }
+}
+
+// Why a pair pass cannot run, or "".
+std::string Session::MatesRefusal() const {
+  if (!mates_) return "mates: they are off (GhostmSessionSetMates)";
+  if (tile_table_.empty()) return "mates: the query set is not tiled";
+  if (tile_read_nt_.size() % 2) return "mates: " + std::to_string(tile_read_nt_.size()) + " source records, an odd number";
+  return std::string();
+}
+
+// The join of every pair's hits (PairJoin): source records 2p and 2p + 1 are
+// the mates of pair p. The cull's reads in order, a KEPT hit a candidate with
+// the cull's record, its subject's node and its tile's strand, every other hit
+// score 0. A pair is there when either mate has a hit.
+const Session::PairJoinResult &Session::PairJoin(bool frame) {
+  const std::string why = MatesRefusal();
+  if (!why.empty()) throw Error("pair join: " + why);
+  PairJoinResult &res = pair_[frame ? 1 : 0];
+  if (res.valid) return res;
+  const ReadCullResult &cull = ReadCull(frame);
+  const std::vector<GhostmHitPath> &path = ReadLevel(frame).rec;
+  const std::vector<GhostmHit> &hits = Hits();
+  const size_t n = hits.size();
+  std::vector<GhostmPairHit> in(n, GhostmPairHit{0, kPairNone, 0, 0, 0, 0, 0, 0});
+  res.pair_begin.assign(1, 0);
+  res.pair_record.clear();
+  std::vector<uint32_t> offset;
+  uint64_t prev_pair = UINT64_MAX;
+  for (size_t r = 0; r + 1 < cull.read_begin.size() && n; ++r) {
+    const uint32_t b = cull.read_begin[r], e = cull.read_begin[r + 1];
+    uint64_t record = 0;
+    for (uint32_t h = b; h < e; ++h) {
+      const GhostmCullHit c = CullRecord(frame, h, hits[h], path[h], &record);
+      if (cull.out[h].status != GHOSTM_CULL_KEPT) continue;
+      const HitSource &hs = hit_source_[h];
+      const GhostmQueryTile &t = tile_table_[queries_[hs.qi].global_base + hs.query];
+      in[h] = GhostmPairHit{c.subject, tax_.set ? tax_.subject_node[hits[h].db_id] : kPairNone, c.score, c.q_lo, c.q_hi,
+                            c.s_lo, c.s_hi, tile_dna_ ? t.frame / 3 : 0u};
+    }
+    const uint64_t pair = record >> 1;
+    if (pair != prev_pair) {
+      if (prev_pair != UINT64_MAX && pair < prev_pair) throw Error("pair join: internal: the reads are not in record order");
+      if (prev_pair != UINT64_MAX) {  // close the pair before: without a mate 2 it ends where that would begin
+        if (res.pair_begin.size() % 2 == 1) res.pair_begin.push_back(b);
+        res.pair_begin.push_back(b);
+      }
+      prev_pair = pair;
+      res.pair_record.push_back((uint32_t)(2 * pair));
+      offset.push_back(tile_read_nt_[2 * pair]);
+      if (record & 1) res.pair_begin.push_back(b);  // mate 1 has no hit
+    } else {
+      res.pair_begin.push_back(b);  // mate 2 begins
+    }
+  }
+  if (prev_pair != UINT64_MAX) {
+    if (res.pair_begin.size() % 2 == 1) res.pair_begin.push_back((uint32_t)n);
+    res.pair_begin.push_back((uint32_t)n);
+  }
+  const uint32_t npairs = (uint32_t)res.pair_record.size();
+  if (res.pair_begin.size() != 2 * (size_t)npairs + 1) throw Error("pair join: internal: the pairs' borders");
+  res.cand.assign(n, GhostmLcaHit{0, 0, 0, 0});
+  res.partner.assign(n, kPairNone);
+  res.out.assign(npairs, GhostmPairOut{0, 0, 0, 0});
+  const uint32_t max_span = tile_dna_ ? std::max(1u, mates_max_insert_ / 3) : mates_max_insert_;
+  DeviceModule &dev = DeviceModule::Get();
+  const GhostmPairJoinStats before = dev.times().pair;
+  dev.PairJoin(npairs, res.pair_begin.data(), offset.data(), (uint32_t)n, in.data(), max_span, tile_dna_ ? 1u : 0u,
+               res.cand.data(), res.partner.data(), res.out.data());
+  AddStats(pair_stats_, StatsDelta(dev.times().pair, before));
+  res.valid = true;
+  return res;
+}
+
+// The taxon of every pair (PairLca): one ReadLca call over the joined
+// candidates with the pairs as reads.
+const Session::PairLcaResult &Session::PairLca(bool frame) {
+  if (!tax_.set) throw Error("pair lca: taxonomy: none is set (GhostmSessionSetTaxonomy)");
+  const PairJoinResult &join = PairJoin(frame);
+  PairLcaResult &res = pair_lca_[frame ? 1 : 0];
+  if (res.valid) return res;
+  const uint32_t npairs = (uint32_t)join.out.size();
+  std::vector<uint32_t> begin(npairs + (size_t)1);
+  for (uint32_t p = 0; p <= npairs; ++p) begin[p] = join.pair_begin[2 * (size_t)p];
+  DeviceModule &dev = DeviceModule::Get();
+  if (dev.taxonomy_serial() != tax_.serial) {  // SetTaxonomyGpu, FreeGpu or another session since: ours again
+    dev.SetTaxonomy((uint32_t)tax_.parent.size(), tax_.parent.data());
+    tax_.serial = dev.taxonomy_serial();
+  }
+  res.out.assign(npairs, GhostmLcaOut{});
+  const GhostmReadLcaStats before = dev.times().lca;
+  dev.ReadLca(npairs, begin.data(), (uint32_t)join.cand.size(), join.cand.data(), lca_top_pct_, lca_support_pct_,
+              res.out.data());
+  AddStats(lca_stats_, StatsDelta(dev.times().lca, before));
+  res.valid = true;
+  return res;
+}
+
+// The name of source record `record` of a tiled set: its first tile record's.
+std::string Session::SourceName(uint32_t record) const {
+  const auto it = std::lower_bound(tile_table_.begin(), tile_table_.end(), record,
+                                   [](const GhostmQueryTile &t, uint32_t r) { return t.record < r; });
+  const uint32_t g = (uint32_t)(it - tile_table_.begin());
+  for (const QueryData &q : queries_)
+    if (g >= q.global_base && g - q.global_base < q.chunk.nseq) return std::string(q.chunk.names[g - q.global_base]);
+  throw Error("pair output: internal: no tile record of source record " + std::to_string(record));
+}
+
+// -y 26 / -y 27: one line per pair with a hit, named by mate 1's record.
+void Session::FormatPairLca(bool frame) {
+  const PairLcaResult &res = PairLca(frame);
+  const PairJoinResult &join = PairJoin(frame);
+  std::string out;
+  for (size_t p = 0; p < res.out.size(); ++p) {
+    const GhostmLcaOut &o = res.out[p];
+    const GhostmPairOut &j = join.out[p];
+    out.append(SourceName(join.pair_record[p]));
+    const uint32_t cols[11] = {o.node == kLcaNone ? 0u : tax_.taxid[o.node], o.depth, o.votes, o.support,
+                               o.lca == kLcaNone ? 0u : tax_.taxid[o.lca], o.candidates, o.unmapped, o.best_score,
+                               j.mates, j.joined, j.best_span};
+    for (uint32_t c : cols) {
+      char num[16], *p2 = num;
+      *p2++ = '\t';
+      p2 = PutU32(p2, c);
+      out.append(num, (size_t)(p2 - num));
+    }
+    out.push_back('\n');
+  }
+  ReplaceText(&out);
+}
+
 void Session::SetProfile(uint32_t min_reads) {
   if (min_reads < 1) throw Error("profile: param: min_reads 0");
   if (min_reads == profile_min_reads_) return;
@@ -2509,14 +2655,15 @@ void Session::SetProfile(uint32_t min_reads) {
   profile_[1].Drop();
 }
 
-// The sample's profile (TaxonProfile): every ReadLca record is a read, its node the read's.
+// The sample's profile (TaxonProfile): every ReadLca record is a read, its node the read's. With mates on every
+// PairLca record is a fragment, counted once.
 const Session::TaxonProfileResult &Session::TaxonProfile(bool frame) {
-  const ReadLcaResult &lca = ReadLca(frame);  // throws without a taxonomy
+  const std::vector<GhostmLcaOut> &lca = mates_ ? PairLca(frame).out : ReadLca(frame).out;  // throws without a taxonomy
   TaxonProfileResult &res = profile_[frame ? 1 : 0];
   if (res.valid) return res;
-  const uint32_t nreads = (uint32_t)lca.out.size();
+  const uint32_t nreads = (uint32_t)lca.size();
   std::vector<uint32_t> node(nreads);
-  for (uint32_t r = 0; r < nreads; ++r) node[r] = lca.out[r].node;
+  for (uint32_t r = 0; r < nreads; ++r) node[r] = lca[r].node;
   DeviceModule &dev = DeviceModule::Get();
   if (dev.taxonomy_serial() != tax_.serial) {  // SetTaxonomyGpu, FreeGpu or another session since: ours again
     dev.SetTaxonomy((uint32_t)tax_.parent.size(), tax_.parent.data());
@@ -2997,9 +3144,9 @@ void Session::Run(bool stream_to_file) {
   streamed_ = false;
   stream_failed_ = false;
   stream_off_ = 0;
-  // -y 6 to -y 25 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup, HitsReadRows, ReadPileup,
-  // ReadCull, ReadLca, TaxonProfile), not while the search runs
-  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 25;
+  // -y 6 to -y 27 are written after the post-pass (HitsExt, HitsPath, HitsRows, Pileup, HitsReadRows, ReadPileup,
+  // ReadCull, ReadLca, TaxonProfile, PairLca), not while the search runs
+  const bool tabular = opt_.output_style >= 6 && opt_.output_style <= 27;
   if (stream_to_file && !tabular) {
     if (!writer_) writer_ = std::make_unique<TaskQueue>();
     // an unwritable path writes nothing, as the reference's unchecked ofstream
@@ -3034,6 +3181,7 @@ void Session::Run(bool stream_to_file) {
   cull_stats_ = GhostmReadCullStats{};
   lca_stats_ = GhostmReadLcaStats{};
   profile_stats_ = GhostmTaxonProfileStats{};
+  pair_stats_ = GhostmPairJoinStats{};
   QueryStats();
   merge_epoch_ = 0;
   DropResults();
@@ -3073,7 +3221,9 @@ void Session::Run(bool stream_to_file) {
   for (size_t k = 0; k < used_parts_; ++k)
     for (const auto &h : parts_[k].hits) stats_.hits += h.size();
   if (tabular) {
-    if (opt_.output_style == 24 || opt_.output_style == 25) {
+    if (opt_.output_style == 26 || opt_.output_style == 27) {
+      FormatPairLca(opt_.output_style == 27);
+    } else if (opt_.output_style == 24 || opt_.output_style == 25) {
       FormatProfile(opt_.output_style == 25);
     } else if (opt_.output_style == 22 || opt_.output_style == 23) {
       FormatLca(opt_.output_style == 23);
@@ -3569,13 +3719,25 @@ void Session::SetQueriesTiled(const uint8_t *raw, uint64_t raw_len, const uint64
 
 void Session::SetQueriesFastaTiled(const std::string &path, uint32_t width, bool dna, uint32_t chunk_mb,
                                    uint32_t max_len, uint32_t step, uint64_t *cut_records, bool *capped) {
+  SetFastaTiled(path, nullptr, width, dna, chunk_mb, max_len, step, cut_records, capped);
+}
+
+void Session::SetQueriesFastaMatesTiled(const std::string &path1, const std::string &path2, uint32_t width, bool dna,
+                                        uint32_t chunk_mb, uint32_t max_len, uint32_t step, uint64_t *cut_records,
+                                        bool *capped) {
+  SetFastaTiled(path1, &path2, width, dna, chunk_mb, max_len, step, cut_records, capped);
+}
+
+void Session::SetFastaTiled(const std::string &path, const std::string *path2, uint32_t width, bool dna,
+                            uint32_t chunk_mb, uint32_t max_len, uint32_t step, uint64_t *cut_records, bool *capped) {
   const WidthRule rule = QuerySetRules(width, dna, chunk_mb, capped);
   if (cut_records) *cut_records = 0;
   if (shard_world_ > 1) throw Error("a shard session's query set cannot be replaced");
   CheckTileStep(rule.width, step);
-  {
-    std::ifstream probe(path.c_str());
-    if (!probe) throw Error("set queries: cannot open " + path);
+  for (const std::string *p : {&path, path2}) {
+    if (!p) continue;
+    std::ifstream probe(p->c_str());
+    if (!probe) throw Error("set queries: cannot open " + *p);
   }
   const double t0 = NowSeconds();
   std::vector<FastaRecord> recs;
@@ -3583,6 +3745,22 @@ void Session::SetQueriesFastaTiled(const std::string &path, uint32_t width, bool
     FastaReader reader(path);
     FastaRecord r;
     while (reader.Next(&r)) recs.push_back(r);
+  }
+  if (path2) {  // the mates' file: record i of each file side by side
+    std::vector<FastaRecord> second;
+    FastaReader reader(*path2);
+    FastaRecord r;
+    while (reader.Next(&r)) second.push_back(r);
+    if (second.size() != recs.size())
+      throw Error("set queries: mates: " + path + " has " + std::to_string(recs.size()) + " records, " + *path2 + " has " +
+                  std::to_string(second.size()));
+    std::vector<FastaRecord> both;
+    both.reserve(2 * recs.size());
+    for (size_t i = 0; i < recs.size(); ++i) {
+      both.push_back(std::move(recs[i]));
+      both.push_back(std::move(second[i]));
+    }
+    recs.swap(both);
   }
   if (recs.size() > UINT32_MAX) throw Error("set queries: over 4 G records");
   std::vector<QueryRecordView> views(recs.size());

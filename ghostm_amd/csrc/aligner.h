@@ -407,6 +407,45 @@ class Session {
   };
   const TaxonProfileResult &TaxonProfile(bool frame);
   const GhostmTaxonProfileStats &TaxonProfileStats() const { return profile_stats_; }
+  // Mate pairs (the contract is above PairJoinGpu in include/ghostm_hip.h; the
+  // session calls are described at GhostmSessionSetMates): with mates on,
+  // source records 2i and 2i + 1 of a tiled set are the mates of pair i.
+  // max_insert 1..2^24 in read units (default 1000). A change drops only the
+  // pair results and the profile counted from them; refused on a shard
+  // session. A pair pass throws "mates" while mates are off, on an untiled set
+  // and on an odd number of source records.
+  void SetMates(bool on, uint32_t max_insert);
+  bool Mates() const { return mates_; }
+  // PairJoin: one DeviceModule::PairJoin call over all hits of Hits(), from
+  // ReadCull(frame): a KEPT hit is a candidate with the cull's record, its
+  // subject's node (0xFFFFFFFF without a taxonomy) and its tile's strand, every
+  // other hit has score 0. pair_begin has two entries per pair and one more
+  // (indices of Hits()); pair_record is mate 1's source record. A pair is there
+  // when either mate has a hit. PairLca: one DeviceModule::ReadLca call over
+  // cand with the pairs as reads. Both computed on first use and kept as long
+  // as the cull's and the assignment's results and SetMates' parameters.
+  struct PairJoinResult {
+    std::vector<GhostmLcaHit> cand;
+    std::vector<uint32_t> partner;
+    std::vector<GhostmPairOut> out;
+    std::vector<uint32_t> pair_begin, pair_record;
+    bool valid = false;
+    void Drop() { *this = PairJoinResult(); }
+  };
+  const PairJoinResult &PairJoin(bool frame);
+  struct PairLcaResult {
+    std::vector<GhostmLcaOut> out;
+    bool valid = false;
+    void Drop() { *this = PairLcaResult(); }
+  };
+  const PairLcaResult &PairLca(bool frame);
+  const GhostmPairJoinStats &PairJoinStats() const { return pair_stats_; }
+  // The tiled FASTA setter over two files of mates: record i of path1 and
+  // record i of path2 become source records 2i and 2i + 1. Files of different
+  // record counts are refused before the old set is dropped.
+  void SetQueriesFastaMatesTiled(const std::string &path1, const std::string &path2, uint32_t width, bool dna,
+                                 uint32_t chunk_mb, uint32_t max_len, uint32_t step, uint64_t *cut_records,
+                                 bool *capped = nullptr);
   // Hit records of the last run in device memory (this session's GPU): copies
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
@@ -687,7 +726,20 @@ class Session {
   ReadLcaResult lca_[2];  // of the band paths [0] and of the frame paths [1]
   uint32_t lca_top_pct_ = 10, lca_support_pct_ = 100;
   GhostmReadLcaStats lca_stats_{};
-  TaxonProfileResult profile_[2];  // of lca_[0] and of lca_[1]
+  bool mates_ = false;  // SetMates
+  uint32_t mates_max_insert_ = 1000;
+  PairJoinResult pair_[2];     // of cull_[0] and of cull_[1]
+  PairLcaResult pair_lca_[2];  // of pair_[0] and of pair_[1]
+  GhostmPairJoinStats pair_stats_{};
+  std::string MatesRefusal() const;              // why a pair pass cannot run, or ""
+  std::string SourceName(uint32_t record) const;  // a tiled set's source record's name
+  // -y 26 (frame false) and -y 27 (frame true): one line per pair with a hit, named by mate 1's record: the -y 22
+  // columns of the pair's record, then mates, joined, best_span; replaces the parts' text as FormatLca does
+  void FormatPairLca(bool frame);
+  // the tiled FASTA setters' common body; path2 (may be null): the mates' file, interleaved record by record
+  void SetFastaTiled(const std::string &path1, const std::string *path2, uint32_t width, bool dna, uint32_t chunk_mb,
+                     uint32_t max_len, uint32_t step, uint64_t *cut_records, bool *capped);
+  TaxonProfileResult profile_[2];  // of lca_[0] and of lca_[1]; with mates on, of pair_lca_
   uint32_t profile_min_reads_ = 1;
   GhostmTaxonProfileStats profile_stats_{};
   bool records_on_device_ = false;

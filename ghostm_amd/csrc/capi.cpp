@@ -739,6 +739,84 @@ size_t GhostmSessionTaxonProfileStats(void *s, GhostmTaxonProfileStats *stats, s
   return sizeof(GhostmTaxonProfileStats);
 }
 
+int GhostmSessionSetMates(void *s, int on, uint32_t max_insert) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetMates(on != 0, max_insert);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+int GhostmSessionSetQueriesFastaMatesTiled(void *s, const char *path1, const char *path2, uint32_t width, int dna,
+                                           uint32_t chunk_mb, uint32_t max_len, uint32_t step, uint64_t *cut_records) {
+  try {
+    if (!s) throw Error("null session");
+    if (!path1 || !path2) throw Error("set queries: null: a path");
+    static_cast<Session *>(s)->SetQueriesFastaMatesTiled(path1, path2, width, dna != 0, chunk_mb, max_len, step,
+                                                         cut_records);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionPairJoin(void *s, int frame, GhostmLcaHit *cand, uint32_t *partner, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const Session::PairJoinResult &r = static_cast<Session *>(s)->PairJoin(frame != 0);
+    if (!cand && !partner) return r.cand.size();
+    const size_t n = std::min(cap, r.cand.size());
+    if (n && cand) std::memcpy(cand, r.cand.data(), n * sizeof(GhostmLcaHit));
+    if (n && partner) std::memcpy(partner, r.partner.data(), n * sizeof(uint32_t));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionPairJoinPairs(void *s, int frame, GhostmPairOut *out, uint32_t *pair_begin, uint32_t *pair_record,
+                                  size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const Session::PairJoinResult &r = static_cast<Session *>(s)->PairJoin(frame != 0);
+    if (!out && !pair_begin && !pair_record) return r.out.size();
+    const size_t n = std::min(cap, r.out.size());
+    if (n && out) std::memcpy(out, r.out.data(), n * sizeof(GhostmPairOut));
+    if (pair_begin) std::memcpy(pair_begin, r.pair_begin.data(), (2 * n + 1) * sizeof(uint32_t));
+    if (n && pair_record) std::memcpy(pair_record, r.pair_record.data(), n * sizeof(uint32_t));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionPairLca(void *s, int frame, GhostmLcaOut *out, size_t cap) {
+  try {
+    if (!s) throw Error("null session");
+    const std::vector<GhostmLcaOut> &r = static_cast<Session *>(s)->PairLca(frame != 0).out;
+    if (!out) return r.size();
+    const size_t n = std::min(cap, r.size());
+    if (n) std::memcpy(out, r.data(), n * sizeof(GhostmLcaOut));
+    return n;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return (size_t)-1;
+  }
+}
+
+size_t GhostmSessionPairJoinStats(void *s, GhostmPairJoinStats *stats, size_t size) {
+  if (!s || !stats) return 0;
+  const GhostmPairJoinStats st = static_cast<Session *>(s)->PairJoinStats();
+  std::memcpy(stats, &st, std::min(size, sizeof(GhostmPairJoinStats)));
+  return sizeof(GhostmPairJoinStats);
+}
+
 size_t GhostmSessionDeviceHits(void *s, void *dst_device, size_t cap) {
   try {
     if (!s) throw Error("null session");
@@ -770,6 +848,8 @@ int GhostmAlignMain(int argc, char **argv) {
       throw Error("-y 22 and -y 23 need a taxonomy: use `ghostm search` with -n nodes.tsv -a map.tsv");
     if (opt.output_style == 24 || opt.output_style == 25)
       throw Error("-y 24 and -y 25 need a taxonomy: use `ghostm search` with -n nodes.tsv -a map.tsv");
+    if (opt.output_style == 26 || opt.output_style == 27)
+      throw Error("-y 26 and -y 27 need mates: use `ghostm search` with -T, -j or -J, -n nodes.tsv -a map.tsv");
     { std::ofstream touch(opt.output_file.c_str()); }
     Session session(opt);
     session.Run(true);       // the output file is written while the search runs
@@ -803,14 +883,25 @@ int GhostmSearchMain(int argc, char **argv) {
   long lca_top = -1, lca_support = -1;     // -p, -P; below 0: the session's defaults
   long profile_min = -1;                   // -R; below 0: the session's default
   MaskParams mask;                         // -Z w,k1,k2; window 0: no masking
+  bool mates_one = false, mates_two = false;  // -j: every file is interleaved mates; -J: r1.fasta r2.fasta out triples
+  long max_insert = -1;                    // -I; below 0: the session's default
   int style = 0;                           // -y, as aln reads it
   optind = 1;
   opterr = 1;
   int c;
   // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B, -F, -g, -K, -C, -n, -a,
-  // -p, -P, -R, -Z
-  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:n:a:p:P:R:Z:")) >= 0) {
+  // -p, -P, -R, -Z, -j, -J, -I
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:n:a:p:P:R:Z:jJI:")) >= 0) {
     switch (c) {
+      case 'j': mates_one = true; break;  // with -T: records 2i and 2i + 1 of every file are mates
+      case 'J': mates_two = true; break;  // with -T: the mates come in two files
+      case 'I': {  // the mates' insert limit in read units, 1..2^24
+        char *end = nullptr;
+        const long v = strtol(optarg, &end, 10);
+        if (end == optarg || *end || v < 1 || v > (1 << 24)) return 1;
+        max_insert = v;
+        break;
+      }
       case 'Z': {  // low-complexity masking: window,trigger,extend
         unsigned long v[3];
         const char *at = optarg;
@@ -902,12 +993,18 @@ int GhostmSearchMain(int argc, char **argv) {
     }
   }
   std::vector<std::string> pos(argv + optind, argv + argc);
-  if (pos.empty() || pos.size() % 2) return 1;
+  const size_t per = mates_two ? 3 : 2;  // positionals per search
+  if (pos.empty() || pos.size() % per) return 1;
+  const bool mates = mates_one || mates_two;
+  if (mates_one && mates_two) return 1;                     // one layout or the other
+  if ((mates || max_insert >= 0) && !tiled) return 1;       // mates are source records of a tiled set
+  if (max_insert >= 0 && !mates) return 1;                  // -I limits mates only
+  if ((style == 26 || style == 27) && !mates) return 1;     // the pair lines need them
   if (have_d == !db_fasta.empty()) return 1;  // -d or -f, not both
   if (have_x && !tiled) return 1;             // -X cuts a tiled set only
   if (tile_groups && !tiled) return 1;        // -g groups a tiled set only
   if (tax_nodes.empty() != tax_map.empty()) return 1;                // -n and -a come together
-  if (style >= 22 && style <= 25 && tax_nodes.empty()) return 1;  // the taxon lines and the profile need them
+  if (style >= 22 && style <= 27 && tax_nodes.empty()) return 1;  // the taxon lines, the profile and the pair lines need them
   try {
     aln_argv.push_back(nullptr);
     AlignerOptions opt = ParseAlignerOptions((int)aln_argv.size() - 1, aln_argv.data());
@@ -923,13 +1020,16 @@ int GhostmSearchMain(int argc, char **argv) {
       session.SetLca(lca_top >= 0 ? (uint32_t)lca_top : 10u, lca_support >= 0 ? (uint32_t)lca_support : 100u);
     if (profile_min >= 0) session.SetProfile((uint32_t)profile_min);
     if (mask.window) session.SetMask(mask.window, mask.trigger, mask.extend);
-    for (size_t k = 0; k < pos.size(); k += 2) {
+    if (mates) session.SetMates(true, max_insert >= 0 ? (uint32_t)max_insert : 1000u);
+    for (size_t k = 0; k < pos.size(); k += per) {
       try {
-        { std::ofstream touch(pos[k + 1].c_str()); }
-        session.SetOutputFile(pos[k + 1]);
+        { std::ofstream touch(pos[k + per - 1].c_str()); }
+        session.SetOutputFile(pos[k + per - 1]);
         std::vector<std::string> cut;
         bool capped = false;
-        if (tiled) session.SetQueriesFastaTiled(pos[k], width, dna, chunk_mb, max_len, tile_step, nullptr, &capped);
+        if (mates_two)
+          session.SetQueriesFastaMatesTiled(pos[k], pos[k + 1], width, dna, chunk_mb, max_len, tile_step, nullptr, &capped);
+        else if (tiled) session.SetQueriesFastaTiled(pos[k], width, dna, chunk_mb, max_len, tile_step, nullptr, &capped);
         else session.SetQueriesFasta(pos[k], width, dna, chunk_mb, nullptr, &cut, &capped);
         if (capped)
           std::cerr << "Warring: over upper limit of query length. Max is " << kMaxQueryLength * (dna ? 3 : 1) << "."

@@ -112,6 +112,7 @@ struct DeviceTimes {
   GhostmReadPileupStats read_pileup{};   // k_read_pileup + k_pileup_finish<true>, counted as the pile-up
   GhostmReadCullStats cull{};            // k_read_cull
   GhostmReadLcaStats lca{};              // k_read_lca*
+  GhostmPairJoinStats pair{};            // k_pair_join
   GhostmTaxonProfileStats profile{};     // k_taxon_*
   GhostmMaskStats mask{};                // k_mask_windows + k_mask_apply
 };
@@ -367,6 +368,17 @@ class DeviceModule {
   // launch, out untouched). Needs no resident chunk. Adds to times().cull*.
   void ReadCull(uint32_t nreads, const uint32_t *read_begin, uint32_t nhits, const GhostmCullHit *hit, uint32_t top_k,
                 uint32_t cover_pct, GhostmCullOut *out);
+
+  // The join of npairs mate pairs (kern::k_pair_join; the contract is above
+  // PairJoinGpu in include/ghostm_hip.h): pair p's hits are hit[pair_begin[2p],
+  // pair_begin[2p + 2]), mate 2's from pair_begin[2p + 1]; cand[i] and
+  // partner[i] are hit i's, out[p] pair p's record. Everything is checked first
+  // (ValidatePairJoin, pair_join.h; throws with the reason before any upload or
+  // launch, the outputs untouched). Needs no resident chunk. Adds to
+  // times().pair*.
+  void PairJoin(uint32_t npairs, const uint32_t *pair_begin, const uint32_t *offset, uint32_t nhits,
+                const GhostmPairHit *hit, uint32_t max_span, uint32_t orient, GhostmLcaHit *cand, uint32_t *partner,
+                GhostmPairOut *out);
 
   // The taxonomy of ReadLca (the contract is above ReadLcaGpu in
   // include/ghostm_hip.h): checked (TaxonomyDepths, read_lca.h; throws with the

@@ -25,6 +25,7 @@
 #include "read_rows.h"
 #include "read_classes.h"
 #include "read_cull.h"
+#include "pair_join.h"
 #include "read_lca.h"
 #include "taxon_profile.h"
 #include "read_pileup.h"
@@ -296,10 +297,10 @@ struct DeviceModule::Impl {
   DevBuf read_rows_hit, read_rows_ops, read_rows_out, read_rows_buf;
   // PathPileup: a batch's hits, words, plan lists and parts; a window's profile and finished arrays; the column counter
   DevBuf pileup_hit, pileup_ops, pileup_list, pileup_part, pileup_prof, pileup_out, pileup_cols;
-  // ReadCull, ReadLca: a batch's hits, its meta words (read_classes.h), its tables, its records
+  // ReadCull, ReadLca, PairJoin: a batch's hits, its meta words (read_classes.h), its tables, its records
   struct ReadBufs {
     DevBuf hit, meta, scratch, out;
-  } cull, lca;
+  } cull, lca, pair;
   DevBuf lca_tax;  // the taxonomy's words
   // TaxonProfile: direct, clade, kept (all zero between calls) and fin, one word per node each, as long as the
   // taxonomy is resident; a call's reads and final nodes, its two lists, its counters and its records
@@ -3167,7 +3168,7 @@ static_assert(sizeof(kern::CullHit) == sizeof(GhostmCullHit) && sizeof(GhostmCul
 static_assert(sizeof(GhostmCullOut) == 16, "k_read_cull writes 4 words per hit");
 static_assert(kern::kCullArrays == kCullTableArrays, "read_cull.h sizes the tables");
 
-// One batch of a per-read pass (ReadCull, ReadLca) past its plan (read_classes.h): the
+// One batch of a per-read pass (ReadCull, ReadLca, PairJoin) past its plan (read_classes.h): the
 // batch's hits and meta words go up, every class with a read is launched inside
 // one timed span by launch(class, its list on the device, its reads), called
 // once the buffers are in place, and the batch's records come back. Returns the
@@ -3255,6 +3256,99 @@ void DeviceModule::ReadCull(uint32_t nreads, const uint32_t *read_begin, uint32_
       t.cull_kept += s == GHOSTM_CULL_KEPT;
       t.cull_dups += s == GHOSTM_CULL_DUP;
       t.cull_culled += s == GHOSTM_CULL_CULLED;
+    }
+  }
+}
+
+static_assert(sizeof(kern::PairHit) == sizeof(GhostmPairHit) && sizeof(GhostmPairHit) == 32,
+              "GhostmPairHit is uploaded as it is");
+static_assert(sizeof(GhostmPairOut) == 16 && sizeof(GhostmLcaHit) == 16, "k_pair_join writes 4 words per hit and per pair");
+static_assert(kern::kJoinWave == kPairWave && kern::kJoinCap == kPairCap && kern::kJoinLimit == kPairHitLimit,
+              "pair_join.h sizes the classes");
+
+// The join of npairs mate pairs (kern::k_pair_join; the contract is above
+// PairJoinGpu in include/ghostm_hip.h). The pairs go in batches cut by their
+// bytes (hits, candidates, partners and the record); a batch's pairs with a hit
+// are listed by size class (wave, LDS, device memory) with the pair as the
+// plan's read, and every class with a pair is one launch. The mates' borders
+// and the offsets follow the plan's words. A batch's candidates, records and
+// partners come back in one copy.
+void DeviceModule::PairJoin(uint32_t npairs, const uint32_t *pair_begin, const uint32_t *offset, uint32_t nhits,
+                            const GhostmPairHit *hit, uint32_t max_span, uint32_t orient, GhostmLcaHit *cand,
+                            uint32_t *partner, GhostmPairOut *out) {
+  if (!impl_) throw Error("pair join: the device module is not bound to a device");
+  Use();
+  Impl &I = *impl_;
+  std::string why = ValidatePairJoin(npairs, pair_begin, offset, nhits, hit, max_span, orient);
+  if (why.empty() && npairs && !out) why = "null: out";
+  if (why.empty() && npairs && pair_begin[2 * (size_t)npairs] > pair_begin[0] && (!cand || !partner))
+    why = "null: cand or partner";
+  if (!why.empty()) throw Error("pair join: " + why);
+  const size_t budget = EnvSize("GHOSTM_PAIR_SCRATCH_MB", 1024) << 20;
+  const size_t max_pairs = EnvSize("GHOSTM_PAIR_BATCH_PAIRS", SIZE_MAX);
+  static const uint32_t kBounds[2] = {kPairWave, kPairCap};
+  std::vector<uint32_t> begin(npairs + (size_t)1, 0), nhit(npairs);  // a pair's first hit; its size: its hits
+  for (uint32_t p = 0; p <= npairs && npairs; ++p) begin[p] = pair_begin[2 * (size_t)p];
+  for (uint32_t p = 0; p < npairs; ++p) nhit[p] = begin[p + 1] - begin[p];
+  ReadClassPlan plan;
+  GhostmPairJoinStats &t = times_.pair;
+  std::vector<uint8_t> got;  // a batch's candidates, records and partners as read back
+  for (uint32_t b0 = 0; b0 < npairs;) {
+    size_t bytes = 0;
+    const uint32_t b1 =
+        CutBatch(b0, npairs, max_pairs, budget, [&](uint32_t p) { return (size_t)nhit[p] * 52 + 32; }, &bytes);
+    const uint32_t m = b1 - b0, p0 = b0, h0 = begin[b0], nh = begin[b1] - h0;
+    b0 = b1;
+    for (uint32_t p = 0; p < m; ++p)
+      if (nhit[p0 + p] == 0) out[p0 + p] = GhostmPairOut{0, 0, 0, 0};
+    plan.Build(begin.data() + p0, m, nhit.data() + p0, kBounds, 2, false, [](uint32_t) { return (size_t)0; });
+    if (!plan.launched) continue;
+    const size_t mid_at = plan.meta.size();  // after the plan's words: mate 2's first hits, then the offsets
+    for (uint32_t p = 0; p < m; ++p) plan.meta.push_back(pair_begin[2 * (size_t)(p0 + p) + 1]);
+    plan.meta.insert(plan.meta.end(), offset + p0, offset + p0 + m);
+    hipStream_t st = S(stream_);
+    kern::PairArgs a{};
+    a.hit_base = h0;
+    a.max_span = max_span;
+    a.orient = orient;
+    const size_t cand_bytes = (size_t)nh * 16, rec_bytes = (size_t)m * 16, part_bytes = (size_t)nh * 4;
+    got.resize(cand_bytes + rec_bytes + part_bytes);
+    t.seconds_pair += ReadClassBatch(
+        I, I.pair, st, plan, hit + h0, (size_t)nh * sizeof(GhostmPairHit), got.data(), got.size(),
+        [&](int c, const uint32_t *list, uint32_t nlist) {
+          a.hit = I.pair.hit.as<kern::PairHit>();
+          a.begin = I.pair.meta.as<uint32_t>();
+          a.mid = a.begin + mid_at;
+          a.offset = a.mid + m;
+          a.cand = I.pair.out.as<uint32_t>();
+          a.out = a.cand + cand_bytes / 4;
+          a.partner = a.out + rec_bytes / 4;
+          a.list = list;
+          a.nlist = nlist;
+          if (c == 0) {
+            const uint32_t per = kern::kJoinBlock / 64;
+            hipLaunchKernelGGL((kern::k_pair_join<kern::kJoinWave, true, false>), dim3((nlist + per - 1) / per),
+                               dim3(kern::kJoinBlock), 0, st, a);
+          } else if (c == 1) {
+            hipLaunchKernelGGL((kern::k_pair_join<kern::kJoinCap, false, false>), dim3(nlist), dim3(kern::kJoinBlock), 0,
+                               st, a);
+          } else {
+            hipLaunchKernelGGL((kern::k_pair_join<kern::kJoinCap, false, true>), dim3(nlist),
+                               dim3(kern::kJoinBlockGlobal), 0, st, a);
+          }
+        });
+    std::memcpy(cand + h0, got.data(), cand_bytes);
+    std::memcpy(partner + h0, got.data() + cand_bytes + rec_bytes, part_bytes);
+    const GhostmPairOut *rec = reinterpret_cast<const GhostmPairOut *>(got.data() + cand_bytes);
+    t.pair_launches += 1;
+    t.pair_pairs += plan.launched;
+    t.pair_hits += nh;
+    for (uint32_t p = 0; p < m; ++p) {
+      if (nhit[p0 + p] == 0) continue;
+      out[p0 + p] = rec[p];
+      t.pair_joined += rec[p].joined;
+      for (uint32_t j = pair_begin[2 * (size_t)(p0 + p) + 1]; j < begin[p0 + p + 1]; ++j)
+        t.pair_taken += hit[j].score != 0 && partner[j] != kPairNone;
     }
   }
 }
@@ -3560,7 +3654,7 @@ const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_read_pileup/k_pileup_finish/k_read_cull/k_read_lca_wave/k_read_lca/k_taxon_count/k_taxon_climb/k_taxon_floor/k_taxon_final/k_taxon_sort_tile/k_taxon_sort_step/k_taxon_emit/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_read_pileup/k_pileup_finish/k_read_cull/k_pair_join/k_read_lca_wave/k_read_lca/k_taxon_count/k_taxon_climb/k_taxon_floor/k_taxon_final/k_taxon_sort_tile/k_taxon_sort_step/k_taxon_emit/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif
@@ -3681,7 +3775,7 @@ int ReadLevelAlignGpu(const char *name, bool frame, uint32_t nhits, const Ghostm
   }
 }
 
-// A stage call that needs no resident chunk (ReadCullGpu, SetTaxonomyGpu, ReadLcaGpu, TaxonProfileGpu): under the lock,
+// A stage call that needs no resident chunk (ReadCullGpu, PairJoinGpu, SetTaxonomyGpu, ReadLcaGpu, TaxonProfileGpu): under the lock,
 // on the first device when no SetOptionGpu bound one, call(module); an error's text after the call's name
 template <class Call>
 int UnboundStageCall(const char *name, Call call) {
@@ -4171,6 +4265,18 @@ int ReadLcaGpu(uint32_t nreads, const uint32_t read_begin[], uint32_t nhits, con
 
 size_t GhostmStageReadLcaStats(GhostmReadLcaStats *stats, size_t size) {
   return StageStats(&DeviceTimes::lca, stats, size);
+}
+
+int PairJoinGpu(uint32_t npairs, const uint32_t pair_begin[], const uint32_t offset[], uint32_t nhits,
+                const GhostmPairHit hit[], uint32_t max_span, uint32_t orient, GhostmLcaHit cand[],
+                uint32_t partner[], GhostmPairOut out[]) {
+  return UnboundStageCall("PairJoinGpu", [&](DeviceModule &m) {
+    m.PairJoin(npairs, pair_begin, offset, nhits, hit, max_span, orient, cand, partner, out);
+  });
+}
+
+size_t GhostmStagePairJoinStats(GhostmPairJoinStats *stats, size_t size) {
+  return StageStats(&DeviceTimes::pair, stats, size);
 }
 
 int TaxonProfileGpu(uint32_t nreads, const uint32_t node[], uint32_t min_reads, size_t cap, GhostmTaxonCount out[],

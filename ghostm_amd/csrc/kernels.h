@@ -5717,6 +5717,173 @@ template <uint32_t P, bool WAVE, bool GLOBAL> __global__ __launch_bounds__(kCull
   CullRead<WAVE>(a, a.list[k], T, hdrs[team], WAVE ? threadIdx.x & 63 : threadIdx.x, WAVE ? 64 : kCullBlock);
 }
 
+// ------------------------------------------------- mate pairs: the join
+// k_pair_join<P, WAVE, GLOBAL>: the join of one pair's hits by one team (the
+// contract is above PairJoinGpu in include/ghostm_hip.h; pair_join.h has the
+// same phases on the host). The team is a wave (WAVE: pairs of at most 64 hits,
+// kJoinBlock / 64 pairs per workgroup) or the workgroup (the records of at most
+// P hits in LDS, or, with GLOBAL, read from device memory for any size).
+//   stage    the pair's records into LDS (subject, score | strand << 24, s_lo,
+//            s_hi) and every hit's chooser word to none
+//   choice   a lane per mate-1 hit i runs over mate 2 in index order and keeps
+//            the first concordant j of the highest score; it writes i's
+//            candidate and partner, lowers j's chooser word to i (an integer
+//            minimum: the order of the lanes cannot matter) and keeps its own
+//            part of the pair's record in registers
+//   barrier  between them the lanes' parts meet in LDS (a sum, an or, two maxima;
+//            the 64-bit maximum is score << 32 | ~i, so the highest score wins
+//            and the lowest index among equals)
+//   marks    a lane per mate-2 hit j reads its chooser word: taken, or a
+//            candidate of its own moved by the offset; the lane that holds the
+//            winning key stores its span
+// With GLOBAL the chooser words are the mate-2 hits' partner words themselves:
+// device-scope atomics lower them and a device-scope load reads them after the
+// barrier, then the same lane stores the final partner over them.
+// Every loop ends at n, which is clamped to the class's bound: what the meta
+// words hold can shorten a loop, never lengthen it or move an LDS index out.
+struct PairHit {
+  uint32_t subject, node, score, q_lo, q_hi, s_lo, s_hi, strand;
+};
+
+struct PairArgs {
+  const PairHit *hit;     // the batch's hits
+  uint32_t hit_base;      // hit[0]'s index in the call: begin and mid count from the call's first hit
+  const uint32_t *begin;  // the batch's pairs: mate 1's first hit, one more entry than pairs
+  const uint32_t *mid;    // mate 2's first hit
+  const uint32_t *offset;
+  const uint32_t *list;  // this launch's pairs: indices into begin
+  uint32_t nlist;
+  uint32_t max_span, orient;
+  uint32_t *cand;     // 4 words per hit of the batch
+  uint32_t *partner;  // 1 word per hit of the batch
+  uint32_t *out;      // 4 words per pair of the batch
+};
+
+constexpr uint32_t kJoinBlock = 256, kJoinBlockGlobal = 1024;
+constexpr uint32_t kJoinArrays = 5;
+constexpr uint32_t kJoinWave = 64, kJoinCap = 1024, kJoinLimit = 16384;  // the classes' largest pairs; the largest pair
+constexpr uint32_t kJoinNone = 0xFFFFFFFFu;
+
+template <bool WAVE, bool GLOBAL>
+__device__ __forceinline__ void PairOne(const PairArgs &a, uint32_t pr, uint32_t *T, uint32_t P, uint32_t *hdr,
+                                        unsigned long long *top, uint32_t tid, uint32_t nt) {
+  const uint32_t b = a.begin[pr], off = a.offset[pr];
+  const uint32_t n = min(a.begin[pr + 1] - b, GLOBAL ? kJoinLimit : P), n1 = min(a.mid[pr] - b, n);
+  const PairHit *hit = a.hit + (b - a.hit_base);
+  uint4 *cand = reinterpret_cast<uint4 *>(a.cand) + (b - a.hit_base);
+  uint32_t *partner = a.partner + (b - a.hit_base);
+  uint32_t *sub = T, *sw = T + P, *slo = T + 2 * P, *shi = T + 3 * P;
+  uint32_t *chooser = GLOBAL ? partner : T + 4 * P;
+  if (tid == 0) {
+    hdr[0] = hdr[1] = hdr[2] = hdr[3] = 0;
+    *top = 0;
+  }
+  for (uint32_t k = tid; k < n; k += nt) {
+    if (GLOBAL) {
+      if (k >= n1) __hip_atomic_store(&chooser[k], kJoinNone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else {
+      const PairHit h = hit[k];
+      sub[k] = h.subject;
+      sw[k] = h.score | h.strand << 24;
+      slo[k] = h.s_lo;
+      shi[k] = h.s_hi;
+      chooser[k] = kJoinNone;
+    }
+  }
+  CullSync<WAVE>();
+  // the choice
+  uint32_t joined = 0, mates = 0, best = 0, my_span = 0;
+  unsigned long long my_top = 0;
+  for (uint32_t i = tid; i < n1; i += nt) {
+    const PairHit h = hit[i];
+    uint4 c = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t pt = kJoinNone;
+    if (h.score) {
+      mates = 1;
+      uint32_t bs = 0, bj = kJoinNone, bspan = 0;
+      for (uint32_t j = n1; j < n; ++j) {
+        uint32_t s2, w2, lo2, hi2;
+        if (GLOBAL) {
+          const PairHit g = hit[j];
+          s2 = g.subject;
+          w2 = g.score | g.strand << 24;
+          lo2 = g.s_lo;
+          hi2 = g.s_hi;
+        } else {
+          s2 = sub[j];
+          w2 = sw[j];
+          lo2 = slo[j];
+          hi2 = shi[j];
+        }
+        const uint32_t sc2 = w2 & 0xFFFFFFu, span = max(h.s_hi, hi2) - min(h.s_lo, lo2) + 1;
+        if (sc2 > bs && s2 == h.subject && (a.orient == 0 || (w2 >> 24) != h.strand) && span <= a.max_span) {
+          bs = sc2;
+          bj = j;
+          bspan = span;
+        }
+      }
+      uint32_t q_hi = h.q_hi;
+      if (bj != kJoinNone) {
+        q_hi = off + hit[bj].q_hi;
+        pt = b + bj;
+        if (GLOBAL) __hip_atomic_fetch_min(&chooser[bj], i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else atomicMin(&chooser[bj], i);
+        ++joined;
+        const unsigned long long key = (unsigned long long)(h.score + bs) << 32 | (kJoinNone - i);
+        if (key > my_top) {
+          my_top = key;
+          my_span = bspan;
+        }
+      }
+      c = make_uint4(h.node, h.score + bs, h.q_lo, q_hi);
+      best = max(best, c.y);
+    }
+    cand[i] = c;
+    partner[i] = pt;
+  }
+  if (joined) atomicAdd(&hdr[0], joined);
+  if (my_top) atomicMax(top, my_top);
+  CullSync<WAVE>();
+  // the marks
+  if (my_top && my_top == *top) hdr[3] = my_span;  // one lane: the keys differ in i
+  for (uint32_t j = n1 + tid; j < n; j += nt) {
+    const PairHit h = hit[j];
+    uint4 c = make_uint4(0u, 0u, 0u, 0u);
+    uint32_t pt = kJoinNone;
+    if (h.score) {
+      mates |= 2;
+      const uint32_t i = GLOBAL ? __hip_atomic_load(&chooser[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : chooser[j];
+      if (i != kJoinNone) {
+        pt = b + i;
+      } else {
+        c = make_uint4(h.node, h.score, h.q_lo + off, h.q_hi + off);
+        best = max(best, h.score);
+      }
+    }
+    cand[j] = c;
+    partner[j] = pt;
+  }
+  if (mates) atomicOr(&hdr[1], mates);
+  if (best) atomicMax(&hdr[2], best);
+  CullSync<WAVE>();
+  if (tid == 0) reinterpret_cast<uint4 *>(a.out)[pr] = make_uint4(hdr[0], hdr[1], hdr[2], hdr[3]);
+}
+
+template <uint32_t P, bool WAVE, bool GLOBAL>
+__global__ __launch_bounds__(GLOBAL ? kJoinBlockGlobal : kJoinBlock) void k_pair_join(PairArgs a) {
+  GHOSTM_POISON_LDS();
+  constexpr uint32_t kBlock = GLOBAL ? kJoinBlockGlobal : kJoinBlock;
+  constexpr uint32_t kTeams = WAVE ? kBlock / 64 : 1;
+  __shared__ __attribute__((aligned(16))) uint32_t tab[GLOBAL ? 2 : kTeams * kJoinArrays * P];
+  __shared__ uint32_t hdrs[kTeams][4];
+  __shared__ unsigned long long tops[kTeams];
+  const uint32_t team = WAVE ? threadIdx.x >> 6 : 0;
+  const uint32_t k = blockIdx.x * kTeams + team;
+  if (k >= a.nlist) return;  // WAVE: the whole wave; otherwise the whole workgroup
+  PairOne<WAVE, GLOBAL>(a, a.list[k], tab + team * kJoinArrays * P, P, hdrs[team], &tops[team],
+                        WAVE ? threadIdx.x & 63 : threadIdx.x, WAVE ? 64 : kBlock);
+}
+
 // ------------------------------------------------- taxon per read (LCA)
 // k_read_lca_wave and k_read_lca<GLOBAL>: the assignment of one read by one
 // team (the contract is above ReadLcaGpu in include/ghostm_hip.h; read_lca.h has

@@ -61,6 +61,12 @@ static int Usage() {
             << "       [-Z window,trigger,extend]: low-complexity stretches of the reads masked with X before the search\n"
             << "        (SEG's raw segments; window 6..32, levels in hundredths of a bit, 0 <= trigger <= extend <= 500;\n"
             << "        e.g. -Z 12,220,250)\n"
+            << "       [-j | -J] [-I maxInsert]: with -T, mate pairs. -j: records 2i and 2i + 1 of every input file are\n"
+            << "        mates; -J: the positionals are triples r1.fasta r2.fasta out, interleaved record by record. A hit\n"
+            << "        of each mate on one subject, at most maxInsert (default 1000; nt for DNA) apart and, for DNA, on\n"
+            << "        opposite strands, joins into one candidate with the sum of the scores. -y 26 and -y 27 (with -n\n"
+            << "        and -a): one line per pair with a hit, named by mate 1: the -y 22 columns of the pair, then mates\n"
+            << "        (1: mate 1 has a hit, 2: mate 2, 3: both), joined, best_span; -y 24 and -y 25 count fragments\n"
             << "synth: ghostm synth -d db.fasta -q queries.fasta [-n nq] [-N dbResidues] [-s seed]\n";
   return 1;
 }

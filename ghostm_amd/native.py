@@ -297,6 +297,47 @@ class GhostmReadLcaStats(ctypes.Structure):
     ]
 
 
+class GhostmPairHit(ctypes.Structure):
+    """one hit of the mate-pair join (32 bytes): the subject and its node, the
+    score (0: not a candidate), the inclusive ranges on the hit's own mate and
+    on the subject, the strand."""
+
+    _fields_ = [
+        ("subject", c_uint32),
+        ("node", c_uint32),
+        ("score", c_uint32),
+        ("q_lo", c_uint32),
+        ("q_hi", c_uint32),
+        ("s_lo", c_uint32),
+        ("s_hi", c_uint32),
+        ("strand", c_uint32),
+    ]
+
+
+class GhostmPairOut(ctypes.Structure):
+    """one pair's record of the join (16 bytes)."""
+
+    _fields_ = [
+        ("joined", c_uint32),
+        ("mates", c_uint32),
+        ("best_score", c_uint32),
+        ("best_span", c_uint32),
+    ]
+
+
+class GhostmPairJoinStats(ctypes.Structure):
+    """the counters of the join (GhostmStagePairJoinStats)."""
+
+    _fields_ = [
+        ("seconds_pair", ctypes.c_double),
+        ("pair_launches", c_uint64),
+        ("pair_pairs", c_uint64),
+        ("pair_hits", c_uint64),
+        ("pair_joined", c_uint64),
+        ("pair_taken", c_uint64),
+    ]
+
+
 class GhostmTaxonCount(ctypes.Structure):
     """one node's record of the taxon profile (16 bytes)."""
 
@@ -522,6 +563,11 @@ SIGNATURES = {
     "GhostmReadLcaHost": (c_int, [c_uint32, u32p, c_uint32, u32p, c_uint32, POINTER(GhostmLcaHit), c_uint32, c_uint32,
                                   POINTER(GhostmLcaOut)]),
     "GhostmStageReadLcaStats": (c_size_t, [POINTER(GhostmReadLcaStats), c_size_t]),
+    "PairJoinGpu": (c_int, [c_uint32, u32p, u32p, c_uint32, POINTER(GhostmPairHit), c_uint32, c_uint32,
+                            POINTER(GhostmLcaHit), u32p, POINTER(GhostmPairOut)]),
+    "GhostmPairJoinHost": (c_int, [c_uint32, u32p, u32p, c_uint32, POINTER(GhostmPairHit), c_uint32, c_uint32,
+                                   POINTER(GhostmLcaHit), u32p, POINTER(GhostmPairOut)]),
+    "GhostmStagePairJoinStats": (c_size_t, [POINTER(GhostmPairJoinStats), c_size_t]),
     "TaxonProfileGpu": (c_int, [c_uint32, u32p, c_uint32, c_size_t, POINTER(GhostmTaxonCount), POINTER(c_size_t), u32p,
                                 POINTER(GhostmTaxonSummary)]),
     "GhostmTaxonProfileHost": (c_int, [c_uint32, u32p, c_uint32, u32p, c_uint32, c_size_t, POINTER(GhostmTaxonCount),
@@ -610,6 +656,13 @@ SIGNATURES = {
     "GhostmSessionReadLca": (c_size_t, [c_void_p, c_int, POINTER(GhostmLcaOut), c_size_t]),
     "GhostmSessionReadLcaBegin": (c_size_t, [c_void_p, c_int, u32p, c_size_t]),
     "GhostmSessionReadLcaStats": (c_size_t, [c_void_p, POINTER(GhostmReadLcaStats), c_size_t]),
+    "GhostmSessionSetMates": (c_int, [c_void_p, c_int, c_uint32]),
+    "GhostmSessionSetQueriesFastaMatesTiled": (c_int, [c_void_p, c_char_p, c_char_p, c_uint32, c_int, c_uint32,
+                                                       c_uint32, c_uint32, POINTER(c_uint64)]),
+    "GhostmSessionPairJoin": (c_size_t, [c_void_p, c_int, POINTER(GhostmLcaHit), u32p, c_size_t]),
+    "GhostmSessionPairJoinPairs": (c_size_t, [c_void_p, c_int, POINTER(GhostmPairOut), u32p, u32p, c_size_t]),
+    "GhostmSessionPairLca": (c_size_t, [c_void_p, c_int, POINTER(GhostmLcaOut), c_size_t]),
+    "GhostmSessionPairJoinStats": (c_size_t, [c_void_p, POINTER(GhostmPairJoinStats), c_size_t]),
     "GhostmSessionSetProfile": (c_int, [c_void_p, c_uint32]),
     "GhostmSessionTaxonProfile": (c_size_t, [c_void_p, c_int, POINTER(GhostmTaxonCount), c_size_t]),
     "GhostmSessionTaxonProfileFinal": (c_size_t, [c_void_p, c_int, u32p, c_size_t]),

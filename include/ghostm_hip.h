@@ -1272,6 +1272,109 @@ typedef struct GhostmReadLcaStats {
  * conventions. */
 size_t GhostmStageReadLcaStats(GhostmReadLcaStats *stats, size_t size);
 
+/* Mate pairs: the join of both mates' hits per fragment, the step between the
+ * cull and the assignment. Two reads from the two ends of one DNA fragment hit
+ * one subject close together; a hit of mate 1 and a hit of mate 2 that do are
+ * joined into one candidate with the sum of their scores, so that the pair is
+ * assigned (ReadLcaGpu, with the pairs as reads) and counted once. All
+ * arithmetic is on integers; the kernel equals the host model exactly.
+ *
+ * Input: npairs pairs; pair p's hits are hit[pair_begin[2p] .. pair_begin[2p +
+ * 1]) of mate 1 and hit[pair_begin[2p + 1] .. pair_begin[2p + 2]) of mate 2
+ * (pair_begin has 2 * npairs + 1 entries, monotone, the last at most nhits;
+ * either half may be empty). A hit is its subject, the subject's node
+ * (0xFFFFFFFF: none), its score (0: not a candidate), two inclusive ranges, q on
+ * its own mate and s on the subject, lo <= hi, and its strand (0 or 1). Scores
+ * and coordinates are below 2^24, so that a pair's sum and an offset coordinate
+ * stay below ReadLcaGpu's 2^25. offset[p], below 2^24, is mate 1's length in
+ * read units: where mate 2's coordinates start in the pair's coordinate space.
+ *
+ * Candidates i of mate 1 and j of mate 2 are concordant when their subjects
+ * are equal, orient == 0 or their strands differ, and max(s_hi) - min(s_lo) + 1
+ * <= max_span (their span on the subject). max_span is 1..2^24, orient 0 or 1.
+ *
+ * Per pair:
+ *   1. Every mate-1 candidate i takes as partner the concordant j of highest
+ *      score, of lowest index among equal scores, or none.
+ *   2. A mate-2 candidate is taken when some i chose it; its partner is the
+ *      lowest such i.
+ *   3. cand[h] and partner[h] are hit h's, in input order (no compaction;
+ *      partner is an index of the call's hit array or 0xFFFFFFFF):
+ *        mate 1, joined      node its own, score_i + score_j, [q_lo_i, offset +
+ *                            q_hi_j]; partner j
+ *        mate 1, not joined  itself; partner 0xFFFFFFFF
+ *        mate 2, taken       all zero (score 0: no candidate of its own);
+ *                            partner the lowest i that chose it
+ *        mate 2, not taken   itself with q_lo + offset and q_hi + offset;
+ *                            partner 0xFFFFFFFF
+ *        not a candidate     all zero; partner 0xFFFFFFFF
+ *   4. out[p]: joined = the mate-1 candidates with a partner; mates = bit 0 when
+ *      mate 1 has a candidate, bit 1 when mate 2 has one; best_score = the
+ *      largest cand score of the pair; best_span = the span of the joined
+ *      candidate of highest score, lowest index among equals, 0 when none.
+ * A pair without hits gets an all-zero record. Hits outside every pair are not
+ * written. The result depends on the records alone. */
+typedef struct GhostmPairHit {  /* 32 bytes */
+  uint32_t subject;
+  uint32_t node;        /* the subject's node, or 0xFFFFFFFF */
+  uint32_t score;       /* 0: not a candidate */
+  uint32_t q_lo, q_hi;  /* inclusive, on the hit's own mate */
+  uint32_t s_lo, s_hi;  /* inclusive, on the subject */
+  uint32_t strand;      /* 0 or 1 */
+} GhostmPairHit;
+
+typedef struct GhostmPairOut {  /* 16 bytes */
+  uint32_t joined;
+  uint32_t mates;       /* bit 0: mate 1 has a candidate; bit 1: mate 2 */
+  uint32_t best_score;
+  uint32_t best_span;
+} GhostmPairOut;
+
+/* PairJoinGpu (kernel k_pair_join) needs neither SetQueryGpu nor SetDbGpu: the
+ * records are all it reads. Everything is checked on the host before any
+ * upload or launch; a refused call returns 1, leaves cand, partner and out
+ * untouched, launches nothing and names its reason:
+ *   "null"    a null pointer where one is needed (hit with nhits > 0;
+ *             pair_begin, offset and out with npairs > 0; cand and partner when
+ *             a pair has a hit)
+ *   "reads"   pair_begin not monotone or ending past nhits; a pair of more than
+ *             16384 hits (the join is quadratic in a pair's hits and feeds
+ *             ReadLcaGpu, whose reads end there)
+ *   "range"   lo > hi
+ *   "bounds"  a score, a coordinate or an offset at or over 2^24; a strand
+ *             above 1
+ *   "param"   max_span or orient out of range
+ * A pair of at most 64 hits takes one wave, a pair of at most 1024 one
+ * workgroup with its records in LDS, a larger pair one workgroup reading the
+ * records from device memory; none is done on the host (a pair without hits
+ * needs no kernel). The pairs go in batches of at most GHOSTM_PAIR_BATCH_PAIRS
+ * pairs (default: no limit) and GHOSTM_PAIR_SCRATCH_MB megabytes of hits and
+ * records (default 1024); 20 bytes per hit and 16 per pair are read back. */
+int PairJoinGpu(uint32_t npairs, const uint32_t pair_begin[], const uint32_t offset[], uint32_t nhits,
+                const GhostmPairHit hit[], uint32_t max_span, uint32_t orient, GhostmLcaHit cand[],
+                uint32_t partner[], GhostmPairOut out[]);
+
+/* The same on the host, with no device call: the model the kernel equals
+ * exactly, with the same checks and reasons. */
+int GhostmPairJoinHost(uint32_t npairs, const uint32_t pair_begin[], const uint32_t offset[], uint32_t nhits,
+                       const GhostmPairHit hit[], uint32_t max_span, uint32_t orient, GhostmLcaHit cand[],
+                       uint32_t partner[], GhostmPairOut out[]);
+
+/* The counters of the join, a struct of their own like GhostmReadLcaStats;
+ * GhostmStats keeps its layout. */
+typedef struct GhostmPairJoinStats {
+  double seconds_pair;     /* k_pair_join, device time */
+  uint64_t pair_launches;  /* batches of pairs with a hit */
+  uint64_t pair_pairs;     /* pairs with a hit */
+  uint64_t pair_hits;
+  uint64_t pair_joined;    /* mate-1 candidates with a partner */
+  uint64_t pair_taken;     /* mate-2 candidates some mate-1 candidate chose */
+} GhostmPairJoinStats;
+
+/* The counters behind the stage-level calls; GhostmStageReadCullStats'
+ * conventions. */
+size_t GhostmStagePairJoinStats(GhostmPairJoinStats *stats, size_t size);
+
 /* The taxon profile of a sample: how many reads fall on each clade of the
  * resident taxonomy, and what is left once clades with only a handful of reads
  * are discounted. A histogram and a sum up the tree: all arithmetic is on
@@ -1883,6 +1986,53 @@ size_t GhostmSessionTaxonProfileSummary(void *session, int frame, GhostmTaxonSum
 /* The profile's counters since the last run began; GhostmSessionBandStats'
  * conventions. */
 size_t GhostmSessionTaxonProfileStats(void *session, GhostmTaxonProfileStats *stats, size_t size);
+
+/* Mate pairs on a session (the contract is above PairJoinGpu). on != 0
+ * declares source records 2i and 2i + 1 of a tiled query set to be the mates of
+ * pair i; max_insert, 1..2^24 (default 1000), is the longest fragment in read
+ * units (nucleotides on a DNA set). The join's max_span is max_insert on a
+ * protein set and max_insert / 3 (at least 1) on a DNA set; orient is 1 on a
+ * DNA set (the mates' hits lie on opposite strands) and 0 on a protein set.
+ * Off by default: nothing of this runs and every other result is as without
+ * it. A change drops only the pair results and the profile counted from them;
+ * a shard session refuses the call. A pair pass fails with "mates" and the
+ * reason while mates are off, on an untiled set and on an odd number of source
+ * records. With mates on, GhostmSessionTaxonProfile* count fragments: one per
+ * GhostmSessionPairLca record instead of one per GhostmSessionReadLca record. */
+int GhostmSessionSetMates(void *session, int on, uint32_t max_insert);
+/* GhostmSessionSetQueriesFastaTiled over two files of mates: record i of path1
+ * and record i of path2 become source records 2i and 2i + 1. Files of
+ * different record counts are refused, both counts named; a refusal leaves the
+ * old set in place. */
+int GhostmSessionSetQueriesFastaMatesTiled(void *session, const char *path1, const char *path2, uint32_t width,
+                                           int dna, uint32_t chunk_mb, uint32_t max_len, uint32_t step,
+                                           uint64_t *cut_records);
+/* The join of every pair's hits, from GhostmSessionReadCull(session, frame,
+ * ...): one PairJoinGpu-style pass over all hits of GhostmSessionHits, a KEPT
+ * hit a candidate with the cull's record (GhostmCullHit's fields), its
+ * subject's node (0xFFFFFFFF without a taxonomy) and its strand (frame / 3 of
+ * the hit's tile on a DNA set, else 0), every other hit with score 0. The
+ * hits are grouped by source record >> 1 and & 1, offset is mate 1's length. A
+ * pair is there when either mate has a hit. cand and partner (either may be
+ * NULL) get one entry per hit; partner indexes GhostmSessionHits. Made on first
+ * use; kept as long as the cull's and the assignment's results and
+ * GhostmSessionSetMates' parameters. With both NULL the call returns the
+ * number of hits, else the number copied (at most cap); (size_t)-1 on error. */
+size_t GhostmSessionPairJoin(void *session, int frame, GhostmLcaHit *cand, uint32_t *partner, size_t cap);
+/* The pairs of that join (each array may be NULL): one GhostmPairOut per pair,
+ * pair_begin with two entries per pair and one more (mate 1's and mate 2's
+ * first hit, then the end), pair_record mate 1's source record, which names the
+ * pair. With all NULL the number of pairs, else the number copied (at most cap
+ * pairs; pair_begin gets 2 * that + 1 entries). */
+size_t GhostmSessionPairJoinPairs(void *session, int frame, GhostmPairOut *out, uint32_t *pair_begin,
+                                  uint32_t *pair_record, size_t cap);
+/* One GhostmLcaOut per pair: one ReadLcaGpu-style pass over the joined
+ * candidates with the pairs as reads, under GhostmSessionSetLca's top_pct and
+ * support_pct. Needs a taxonomy. GhostmSessionReadLca's conventions. */
+size_t GhostmSessionPairLca(void *session, int frame, GhostmLcaOut *out, size_t cap);
+/* The join's counters since the last run began; GhostmSessionBandStats'
+ * conventions. (The pairs' assignment counts into GhostmSessionReadLcaStats.) */
+size_t GhostmSessionPairJoinStats(void *session, GhostmPairJoinStats *stats, size_t size);
 
 /* The same records resident on the session's GPU, for a device-to-device
  * gather across ranks: copies min(n, cap) records to dst_device
