@@ -295,6 +295,56 @@ def stage_mask_stats() -> dict:
     return {n: getattr(st, n) for n, _ in st._fields_}
 
 
+# GhostmQualOut: one read's record of the quality stage
+QUAL_OUT_DTYPE = np.dtype([("begin", "<u4"), ("kept", "<u4"), ("masked", "<u4"), ("bad", "<u4")])
+
+
+def _qual_call(fn, letters, quals, offsets, lengths, trim, mask, min_len):
+    ls = np.array(np.frombuffer(bytes(letters), dtype=np.uint8))  # a copy: the call masks in place
+    qs = np.frombuffer(bytes(quals), dtype=np.uint8)
+    if ls.size != qs.size:
+        raise ValueError("quality trim: letters and qualities differ in size")
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    lens = np.ascontiguousarray(lengths, dtype=np.uint32).reshape(-1)
+    if offs.size != lens.size:
+        raise ValueError("quality trim: one offset per length")
+    args = [int(v) for v in (trim, mask, min_len)]
+    if any(not 0 <= v < 1 << 32 for v in args):
+        raise GhostmError("quality trim: param: an argument beyond 32 bits")
+    out = np.zeros(lens.size, dtype=QUAL_OUT_DTYPE)
+    u8p = ctypes.POINTER(ctypes.c_uint8)
+    lp = ls.ctypes.data_as(u8p) if ls.size else None
+    qp = qs.ctypes.data_as(u8p) if qs.size else None
+    rc = fn(lp, qp, int(ls.size), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), lens.ctypes.data_as(_U32P),
+            int(lens.size), *args, out.ctypes.data_as(ctypes.POINTER(native.GhostmQualOut)))
+    if rc != 0:
+        raise GhostmError(native.last_error())
+    return ls.tobytes(), out
+
+
+def quality_trim_host(letters, quals, offsets, lengths, trim=20, mask=0, min_len=0):
+    """The host model of the quality stage (GhostmQualityTrimHost; no device):
+    read r is lengths[r] bytes at offsets[r] of letters and of quals (bytes,
+    Phred+33). Returns (letters, out): a copy of the letters with the masked
+    ones stored as N, and one QUAL_OUT_DTYPE record per read. Raises
+    GhostmError with the reason ("param", "null", "record", "length")."""
+    return _qual_call(native.load().GhostmQualityTrimHost, letters, quals, offsets, lengths, trim, mask, min_len)
+
+
+def quality_trim(letters, quals, offsets, lengths, trim=20, mask=0, min_len=0):
+    """QualityTrimGpu: the same through k_qual_trim; arguments, result and
+    refusals as quality_trim_host."""
+    return _qual_call(native.load().QualityTrimGpu, letters, quals, offsets, lengths, trim, mask, min_len)
+
+
+def stage_qual_stats() -> dict:
+    """The quality counters behind the stage-level call (GhostmStageQualStats)."""
+    lib = native.load()
+    st = native.GhostmQualStats()
+    lib.GhostmStageQualStats(ctypes.byref(st), ctypes.sizeof(st))
+    return {n: getattr(st, n) for n, _ in st._fields_}
+
+
 # GhostmHitFrameInfo: one per hit beside Session.hits_frame()'s records
 HIT_FRAME_INFO_DTYPE = np.dtype([("strand", "<u4"), ("read_nt", "<u4"), ("letters", "<u4"), ("shifts", "<u4")])
 # the operations of a frame path's words: PATH_OPS and the two shifts
@@ -949,18 +999,26 @@ class Session:
         return c["seed"], kc, pos
 
     def set_queries(self, seqs: Sequence, names: Sequence, width: int = 75, dna: bool = False,
-                    chunk_mb: int = 0, tile_step: int | None = None, max_len: int = 0) -> None:
+                    chunk_mb: int = 0, tile_step: int | None = None, max_len: int = 0, quals: Sequence | None = None) -> None:
         """Replaces the query set by these records (str or bytes letters and
         names): what `ghostm qry -l width [-t d] -L chunk_mb` would format from
         them, coded on the device (GhostmSessionSetQueries). The last run's
         results are dropped. With tile_step the set is tiled
         (GhostmSessionSetQueriesTiled): every record is cut at max_len (letters,
         nt for DNA; 0: no cut) and enters as overlapping tile records of the
-        width, tile_step letters apart; query_tiles() gives the table."""
+        width, tile_step letters apart; query_tiles() gives the table. quals
+        (tiled sets only): every record's quality bytes (Phred+33), as long as
+        its letters; the set then goes through the quality stage of
+        set_quality() (GhostmSessionSetQueriesQualTiled)."""
         if tile_step is None and max_len:
             raise ValueError("set_queries: max_len cuts a tiled set only (give tile_step)")
         if len(seqs) != len(names):
             raise ValueError("set_queries: one name per sequence")
+        if quals is not None:
+            if tile_step is None:
+                raise ValueError("set_queries: quals go with a tiled set only (give tile_step)")
+            if len(quals) != len(seqs) or any(len(q) != len(x) for q, x in zip(quals, seqs)):
+                raise ValueError("set_queries: one quality byte per letter")
         as_bytes = lambda x: x.encode() if isinstance(x, str) else bytes(x)  # noqa: E731
         bseqs = [as_bytes(x) for x in seqs]
         bnames = [as_bytes(x) for x in names]
@@ -978,7 +1036,12 @@ class Session:
                 offsets.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
                 lengths.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), name_buf, len(name_buf), n, int(width),
                 int(bool(dna)), int(chunk_mb))
-        if tile_step is None:
+        if quals is not None:
+            qraw = np.frombuffer(b"".join(as_bytes(q) for q in quals) or b"\0", dtype=np.uint8)
+            u8p = ctypes.POINTER(ctypes.c_uint8)
+            rc = native.load().GhostmSessionSetQueriesQualTiled(args[0], args[1], qraw.ctypes.data_as(u8p), *args[2:],
+                                                                int(max_len), int(tile_step))
+        elif tile_step is None:
             rc = native.load().GhostmSessionSetQueries(*args)
         else:
             rc = native.load().GhostmSessionSetQueriesTiled(*args, int(max_len), int(tile_step))
@@ -1005,6 +1068,62 @@ class Session:
         if rc != 0:
             raise GhostmError(native.last_error())
         return int(cut.value)
+
+    def set_quality(self, trim: int = 20, mask: int = 0, min_len: int = 0) -> None:
+        """Quality trimming and masking of the FASTQ and quality-carrying sets
+        made from now on (GhostmSessionSetQuality): both ends trimmed by BWA's
+        running sum at quality `trim`, kept letters below `mask` stored as N,
+        reads left shorter than min_len emptied (they stay as records).
+        set_quality(0, 0, 0) turns it off (the default). A refusal ("param")
+        leaves the old setting."""
+        args = [int(trim), int(mask), int(min_len)]
+        if any(not 0 <= v < 1 << 32 for v in args):  # beyond the C arguments' range
+            raise GhostmError("quality: param: an argument beyond 32 bits")
+        if native.load().GhostmSessionSetQuality(self._h, *args) != 0:
+            raise GhostmError(native.last_error())
+
+    def set_queries_fastq(self, path: str, width: int = 75, dna: bool = False, chunk_mb: int = 0,
+                          tile_step: int = 64, max_len: int = 0) -> int:
+        """The tiled set_queries_fasta from a four-line FASTQ file, through the
+        quality stage of set_quality() (GhostmSessionSetQueriesFastqTiled).
+        Read coordinates in every result are relative to the kept stretch;
+        query_quality()["begin"] converts them back."""
+        cut = ctypes.c_uint64(0)
+        rc = native.load().GhostmSessionSetQueriesFastqTiled(self._h, str(path).encode(), int(width), int(bool(dna)),
+                                                             int(chunk_mb), int(max_len), int(tile_step),
+                                                             ctypes.byref(cut))
+        if rc != 0:
+            raise GhostmError(native.last_error())
+        return int(cut.value)
+
+    def set_queries_fastq_mates(self, path1: str, path2: str, width: int = 75, dna: bool = False, chunk_mb: int = 0,
+                                tile_step: int = 64, max_len: int = 0) -> int:
+        """set_queries_fastq over two files of mates, interleaved record by
+        record (GhostmSessionSetQueriesFastqMatesTiled); a mate the quality
+        stage empties stays a record."""
+        cut = ctypes.c_uint64(0)
+        rc = native.load().GhostmSessionSetQueriesFastqMatesTiled(
+            self._h, str(path1).encode(), str(path2).encode(), int(width), int(bool(dna)), int(chunk_mb), int(max_len),
+            int(tile_step), ctypes.byref(cut))
+        if rc != 0:
+            raise GhostmError(native.last_error())
+        return int(cut.value)
+
+    def query_quality(self) -> np.ndarray:
+        """One QUAL_OUT_DTYPE record per source read of the current set
+        (GhostmSessionQueryQuality); empty when the quality stage did not run."""
+        lib = native.load()
+        n = lib.GhostmSessionQueryQuality(self._h, None, 0)
+        out = np.zeros(n, dtype=QUAL_OUT_DTYPE)
+        if n:
+            lib.GhostmSessionQueryQuality(self._h, out.ctypes.data_as(ctypes.POINTER(native.GhostmQualOut)), n)
+        return out
+
+    def quality_stats(self) -> dict:
+        """The quality counters of the current query set (GhostmSessionQualityStats)."""
+        st = native.GhostmQualStats()
+        native.load().GhostmSessionQualityStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        return {n: getattr(st, n) for n, _ in st._fields_}
 
     def query_tiles(self) -> np.ndarray:
         """The tile table of a tiled query set (GhostmSessionQueryTiles): one

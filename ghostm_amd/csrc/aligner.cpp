@@ -2204,6 +2204,15 @@ void Session::SetMask(uint32_t window, uint32_t trigger, uint32_t extend) {
   mask_.extend = extend;
 }
 
+void Session::SetQuality(uint32_t trim_q, uint32_t mask_q, uint32_t min_len) {
+  if (shard_world_ > 1) throw Error("a shard session's query set cannot be replaced");
+  const std::string why = ValidateQualParams(trim_q, mask_q, min_len);
+  if (!why.empty()) throw Error("quality: " + why);
+  qual_.trim_q = trim_q;
+  qual_.mask_q = mask_q;
+  qual_.min_len = min_len;
+}
+
 double Session::MaskChunk(QueryData *q, const std::vector<GhostmBandSource> &src, uint32_t step) {
   q->masked.assign(q->chunk.nseq, 0);
   GhostmMaskStats one{};
@@ -3424,6 +3433,8 @@ void Session::DropQueries() {
   read_seconds_ = 0;
   load_seconds_ = 0;
   mask_stats_ = GhostmMaskStats{};
+  qual_out_.clear();
+  qual_stats_ = GhostmQualStats{};
   QueryStats();
 }
 
@@ -3776,6 +3787,127 @@ void Session::SetFastaTiled(const std::string &path, const std::string *path2, u
   read_seconds_ = read;
   QueryStats();
   if (cut_records) *cut_records = cut;
+}
+
+// ------------------------------------------------------------------ reads with qualities
+// FASTQ files and the letters form with quality bytes take the tiled path: the
+// quality stage (read_quality.h) runs on all reads before anything of the old
+// set is touched, then each read's kept stretch is what SetTiledRecords sees.
+void Session::SetQualTiled(FastqSet *a, FastqSet *b, uint32_t width, bool dna, uint32_t chunk_mb, uint32_t max_len,
+                           uint32_t step, uint64_t *cut_records, bool *capped, double read_seconds) {
+  const WidthRule rule = QuerySetRules(width, dna, chunk_mb, capped);
+  if (cut_records) *cut_records = 0;
+  if (shard_world_ > 1) throw Error("a shard session's query set cannot be replaced");
+  CheckTileStep(rule.width, step);
+  if (b && b->len.size() != a->len.size())
+    throw Error("set queries: mates: the first file has " + std::to_string(a->len.size()) + " records, the second has " +
+                std::to_string(b->len.size()));
+  const size_t per = b ? 2 : 1, total = a->len.size() * per;
+  if (total > UINT32_MAX) throw Error("set queries: over 4 G records");
+  const QualParams params = qual_;
+  std::vector<GhostmQualOut> outs[2];
+  GhostmQualStats sum{};
+  for (size_t k = 0; k < per; ++k) {
+    FastqSet &f = k ? *b : *a;
+    const uint32_t n = (uint32_t)f.len.size();
+    outs[k].resize(n);
+    uint8_t *letters = reinterpret_cast<uint8_t *>(&f.letters[0]);
+    const uint8_t *qual = reinterpret_cast<const uint8_t *>(f.qual.data());
+    const std::string why = ValidateQuality(letters, qual, f.letters.size(), f.off.data(), f.len.data(), n, params.trim_q,
+                                            params.mask_q, params.min_len, outs[k].data());
+    if (!why.empty()) throw Error("quality: " + why);
+    if (!params.On() || n == 0) continue;
+    GhostmQualStats one{};
+    DeviceModule::Get().QualityTrim(letters, qual, f.off.data(), f.len.data(), n, params, outs[k].data(), &one);
+    for (uint32_t r = 0; r < n; ++r)
+      if (outs[k][r].bad) throw Error("fastq: record " + std::to_string(r + 1) + ": quality byte outside '!'..'~'");
+    sum.launches += one.launches;
+    sum.reads += one.reads;
+    sum.letters += one.letters;
+    sum.trimmed5 += one.trimmed5;
+    sum.trimmed3 += one.trimmed3;
+    sum.masked += one.masked;
+    sum.failed += one.failed;
+    sum.bad += one.bad;
+    sum.seconds_quality += one.seconds_quality;
+  }
+  std::vector<QueryRecordView> views(total);
+  std::vector<GhostmQualOut> all;
+  if (params.On()) all.resize(total);
+  uint64_t cut = 0;
+  for (size_t r = 0; r < total; ++r) {
+    const FastqSet &f = r % per ? *b : *a;
+    const size_t i = r / per;
+    uint32_t begin = 0, len = f.len[i];
+    if (params.On()) {
+      all[r] = outs[r % per][i];
+      begin = all[r].begin;
+      len = all[r].kept;
+    }
+    const uint32_t kept = TileKept(len, max_len);
+    cut += kept < len ? (dna ? 6 : 1) : 0;
+    views[r] = QueryRecordView{f.letters.data() + f.off[i] + begin, kept, f.names[i]};
+  }
+  SetTiledRecords(views.data(), (uint32_t)views.size(), TiledRule{rule.width, rule.max_concat, step, dna});
+  qual_out_.swap(all);
+  qual_stats_ = sum;
+  read_seconds_ = read_seconds;
+  QueryStats();
+  if (cut_records) *cut_records = cut;
+}
+
+void Session::SetQueriesFastqTiled(const std::string &path, uint32_t width, bool dna, uint32_t chunk_mb,
+                                   uint32_t max_len, uint32_t step, uint64_t *cut_records, bool *capped) {
+  const double t0 = NowSeconds();
+  FastqSet a;
+  try {
+    ReadFastqSet(path, &a);
+  } catch (FastqError &e) {
+    throw Error(e.what());
+  }
+  SetQualTiled(&a, nullptr, width, dna, chunk_mb, max_len, step, cut_records, capped, NowSeconds() - t0);
+}
+
+void Session::SetQueriesFastqMatesTiled(const std::string &path1, const std::string &path2, uint32_t width, bool dna,
+                                        uint32_t chunk_mb, uint32_t max_len, uint32_t step, uint64_t *cut_records,
+                                        bool *capped) {
+  const double t0 = NowSeconds();
+  FastqSet a, b;
+  try {
+    ReadFastqSet(path1, &a);
+    ReadFastqSet(path2, &b);
+  } catch (FastqError &e) {
+    throw Error(e.what());
+  }
+  if (a.len.size() != b.len.size())
+    throw Error("set queries: mates: " + path1 + " has " + std::to_string(a.len.size()) + " records, " + path2 + " has " +
+                std::to_string(b.len.size()));
+  SetQualTiled(&a, &b, width, dna, chunk_mb, max_len, step, cut_records, capped, NowSeconds() - t0);
+}
+
+void Session::SetQueriesQualTiled(const uint8_t *raw, const uint8_t *qual, uint64_t raw_len, const uint64_t *offsets,
+                                  const uint32_t *lengths, const char *names, uint64_t names_len, uint32_t n,
+                                  uint32_t width, bool dna, uint32_t chunk_mb, uint32_t max_len, uint32_t step,
+                                  uint64_t *cut_records) {
+  if (n && (!offsets || !lengths || !names || ((!raw || !qual) && raw_len))) throw Error("set queries: null argument");
+  FastqSet a;  // a copy: the caller's letters are not changed
+  a.off.assign(offsets, offsets + n);
+  a.len.assign(lengths, lengths + n);
+  a.names.resize(n);
+  uint64_t at = 0;
+  for (uint32_t r = 0; r < n; ++r) {
+    if (offsets[r] > raw_len || lengths[r] > raw_len - offsets[r])
+      throw Error("set queries: record " + std::to_string(r) + " outside the letter buffer");
+    const char *nl = at < names_len ? static_cast<const char *>(std::memchr(names + at, '\n', names_len - at)) : nullptr;
+    if (!nl) throw Error("set queries: fewer than " + std::to_string(n) + " newline-terminated names");
+    a.names[r].assign(names + at, (size_t)(nl - (names + at)));
+    at = (uint64_t)(nl - names) + 1;
+  }
+  if (raw_len) {
+    a.letters.assign(reinterpret_cast<const char *>(raw), raw_len);
+    a.qual.assign(reinterpret_cast<const char *>(qual), raw_len);
+  }
+  SetQualTiled(&a, nullptr, width, dna, chunk_mb, max_len, step, cut_records, nullptr, 0);
 }
 
 // ------------------------------------------------------------------ database sets

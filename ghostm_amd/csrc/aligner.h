@@ -22,8 +22,10 @@
 
 #include "../../include/ghostm_hip.h"
 #include "device.h"
+#include "fastq_reader.h"
 #include "formats.h"
 #include "query_mask.h"
+#include "read_quality.h"
 #include "scoring.h"
 
 namespace ghostm {
@@ -446,6 +448,32 @@ class Session {
   void SetQueriesFastaMatesTiled(const std::string &path1, const std::string &path2, uint32_t width, bool dna,
                                  uint32_t chunk_mb, uint32_t max_len, uint32_t step, uint64_t *cut_records,
                                  bool *capped = nullptr);
+  // Quality trimming and masking of FASTQ and quality-carrying sets
+  // (read_quality.h; the contract is above GhostmQualityTrimHost and
+  // GhostmSessionSetQuality in include/ghostm_hip.h). 0, 0, 0: off, the
+  // default; otherwise throws "param" and keeps the old setting. It takes
+  // effect at the next SetQueriesFastq*Tiled / SetQueriesQualTiled; refused on
+  // a shard session.
+  void SetQuality(uint32_t trim_q, uint32_t mask_q, uint32_t min_len);
+  // The tiled setters over reads with qualities: the file (or the two mates'
+  // files, interleaved record by record) is parsed, the quality stage runs on
+  // all reads (DeviceModule::QualityTrim, when it is on), read r enters as
+  // letters[begin, begin + kept), max_len cuts what was kept, and
+  // SetTiledRecords makes the set. A malformed file, a quality byte outside
+  // '!'..'~' and every SetQueriesTiled refusal leave the session as it was.
+  void SetQueriesFastqTiled(const std::string &path, uint32_t width, bool dna, uint32_t chunk_mb, uint32_t max_len,
+                            uint32_t step, uint64_t *cut_records, bool *capped = nullptr);
+  void SetQueriesFastqMatesTiled(const std::string &path1, const std::string &path2, uint32_t width, bool dna,
+                                 uint32_t chunk_mb, uint32_t max_len, uint32_t step, uint64_t *cut_records,
+                                 bool *capped = nullptr);
+  void SetQueriesQualTiled(const uint8_t *raw, const uint8_t *qual, uint64_t raw_len, const uint64_t *offsets,
+                           const uint32_t *lengths, const char *names, uint64_t names_len, uint32_t n, uint32_t width,
+                           bool dna, uint32_t chunk_mb, uint32_t max_len, uint32_t step, uint64_t *cut_records = nullptr);
+  // one record per source read of the current set; empty when the stage did not run for it
+  const std::vector<GhostmQualOut> &QueryQuality() const { return qual_out_; }
+  // the quality counters of the current set (all 0 when the stage did not run)
+  const GhostmQualStats &QualityStats() const { return qual_stats_; }
+  const QualParams &Quality() const { return qual_; }
   // Hit records of the last run in device memory (this session's GPU): copies
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
@@ -739,6 +767,12 @@ class Session {
   // the tiled FASTA setters' common body; path2 (may be null): the mates' file, interleaved record by record
   void SetFastaTiled(const std::string &path1, const std::string *path2, uint32_t width, bool dna, uint32_t chunk_mb,
                      uint32_t max_len, uint32_t step, uint64_t *cut_records, bool *capped);
+  QualParams qual_;                     // SetQuality: the next quality-carrying set's stage (all 0: off)
+  std::vector<GhostmQualOut> qual_out_;  // the current set's, per source read
+  GhostmQualStats qual_stats_{};
+  // the quality setters' common body: one read set, or two of mates interleaved; their letters are masked in place
+  void SetQualTiled(FastqSet *a, FastqSet *b, uint32_t width, bool dna, uint32_t chunk_mb, uint32_t max_len,
+                    uint32_t step, uint64_t *cut_records, bool *capped, double read_seconds);
   TaxonProfileResult profile_[2];  // of lca_[0] and of lca_[1]; with mates on, of pair_lca_
   uint32_t profile_min_reads_ = 1;
   GhostmTaxonProfileStats profile_stats_{};

@@ -450,6 +450,72 @@ size_t GhostmSessionMaskStats(void *s, GhostmMaskStats *stats, size_t size) {
   return CopyStats(s, stats, size, std::mem_fn(&Session::MaskStats));
 }
 
+int GhostmSessionSetQuality(void *s, uint32_t trim_q, uint32_t mask_q, uint32_t min_len) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetQuality(trim_q, mask_q, min_len);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+int GhostmSessionSetQueriesFastqTiled(void *s, const char *path, uint32_t width, int dna, uint32_t chunk_mb,
+                                      uint32_t max_len, uint32_t step, uint64_t *cut_records) {
+  try {
+    if (!s) throw Error("null session");
+    if (!path) throw Error("set queries: null path");
+    static_cast<Session *>(s)->SetQueriesFastqTiled(path, width, dna != 0, chunk_mb, max_len, step, cut_records);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+int GhostmSessionSetQueriesFastqMatesTiled(void *s, const char *path1, const char *path2, uint32_t width, int dna,
+                                           uint32_t chunk_mb, uint32_t max_len, uint32_t step, uint64_t *cut_records) {
+  try {
+    if (!s) throw Error("null session");
+    if (!path1 || !path2) throw Error("set queries: null path");
+    static_cast<Session *>(s)->SetQueriesFastqMatesTiled(path1, path2, width, dna != 0, chunk_mb, max_len, step,
+                                                         cut_records);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+int GhostmSessionSetQueriesQualTiled(void *s, const uint8_t *raw, const uint8_t *qual, uint64_t raw_len,
+                                     const uint64_t *offsets, const uint32_t *lengths, const char *names,
+                                     uint64_t names_len, uint32_t n, uint32_t width, int dna, uint32_t chunk_mb,
+                                     uint32_t max_len, uint32_t step) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetQueriesQualTiled(raw, qual, raw_len, offsets, lengths, names, names_len, n, width,
+                                                   dna != 0, chunk_mb, max_len, step);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionQueryQuality(void *s, GhostmQualOut *out, size_t cap) {
+  if (!s) return 0;
+  const std::vector<GhostmQualOut> &v = static_cast<Session *>(s)->QueryQuality();
+  if (!out) return v.size();
+  const size_t n = std::min(cap, v.size());
+  if (n) std::memcpy(out, v.data(), n * sizeof(GhostmQualOut));
+  return n;
+}
+
+size_t GhostmSessionQualityStats(void *s, GhostmQualStats *stats, size_t size) {
+  return CopyStats(s, stats, size, std::mem_fn(&Session::QualityStats));
+}
+
 size_t GhostmSessionBandStats(void *s, GhostmBandStats *stats, size_t size) {
   return CopyStats(s, stats, size, std::mem_fn(&Session::BandStats));
 }
@@ -883,6 +949,7 @@ int GhostmSearchMain(int argc, char **argv) {
   long lca_top = -1, lca_support = -1;     // -p, -P; below 0: the session's defaults
   long profile_min = -1;                   // -R; below 0: the session's default
   MaskParams mask;                         // -Z w,k1,k2; window 0: no masking
+  QualParams quality;                      // -Q trim,mask,minlen; all 0: no quality stage
   bool mates_one = false, mates_two = false;  // -j: every file is interleaved mates; -J: r1.fasta r2.fasta out triples
   long max_insert = -1;                    // -I; below 0: the session's default
   int style = 0;                           // -y, as aln reads it
@@ -890,8 +957,8 @@ int GhostmSearchMain(int argc, char **argv) {
   opterr = 1;
   int c;
   // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B, -F, -g, -K, -C, -n, -a,
-  // -p, -P, -R, -Z, -j, -J, -I
-  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:n:a:p:P:R:Z:jJI:")) >= 0) {
+  // -p, -P, -R, -Z, -j, -J, -I, -Q
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:n:a:p:P:R:Z:jJI:Q:")) >= 0) {
     switch (c) {
       case 'j': mates_one = true; break;  // with -T: records 2i and 2i + 1 of every file are mates
       case 'J': mates_two = true; break;  // with -T: the mates come in two files
@@ -900,6 +967,22 @@ int GhostmSearchMain(int argc, char **argv) {
         const long v = strtol(optarg, &end, 10);
         if (end == optarg || *end || v < 1 || v > (1 << 24)) return 1;
         max_insert = v;
+        break;
+      }
+      case 'Q': {  // FASTQ reads: trim_q,mask_q,min_len
+        unsigned long v[3];
+        const char *at = optarg;
+        for (int k = 0; k < 3; ++k) {
+          char *end = nullptr;
+          if (*at < '0' || *at > '9') return 1;
+          v[k] = strtoul(at, &end, 10);
+          if (end == at || v[k] > (1ul << 24) || *end != (k < 2 ? ',' : '\0')) return 1;
+          at = end + 1;
+        }
+        if (!ValidateQualParams((uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2]).empty()) return 1;
+        quality.trim_q = (uint32_t)v[0];
+        quality.mask_q = (uint32_t)v[1];
+        quality.min_len = (uint32_t)v[2];
         break;
       }
       case 'Z': {  // low-complexity masking: window,trigger,extend
@@ -1020,6 +1103,7 @@ int GhostmSearchMain(int argc, char **argv) {
       session.SetLca(lca_top >= 0 ? (uint32_t)lca_top : 10u, lca_support >= 0 ? (uint32_t)lca_support : 100u);
     if (profile_min >= 0) session.SetProfile((uint32_t)profile_min);
     if (mask.window) session.SetMask(mask.window, mask.trigger, mask.extend);
+    if (quality.On()) session.SetQuality(quality.trim_q, quality.mask_q, quality.min_len);
     if (mates) session.SetMates(true, max_insert >= 0 ? (uint32_t)max_insert : 1000u);
     for (size_t k = 0; k < pos.size(); k += per) {
       try {
@@ -1027,7 +1111,14 @@ int GhostmSearchMain(int argc, char **argv) {
         session.SetOutputFile(pos[k + per - 1]);
         std::vector<std::string> cut;
         bool capped = false;
-        if (mates_two)
+        // a file whose first byte is '@' is FASTQ (the mates' two files go by the first)
+        const bool fastq = LooksLikeFastq(pos[k]);
+        if (fastq && !tiled) throw Error("fastq: needs -T");
+        if (quality.On() && !fastq) throw Error("quality: " + pos[k] + " has no qualities");
+        if (fastq && mates_two)
+          session.SetQueriesFastqMatesTiled(pos[k], pos[k + 1], width, dna, chunk_mb, max_len, tile_step, nullptr, &capped);
+        else if (fastq) session.SetQueriesFastqTiled(pos[k], width, dna, chunk_mb, max_len, tile_step, nullptr, &capped);
+        else if (mates_two)
           session.SetQueriesFastaMatesTiled(pos[k], pos[k + 1], width, dna, chunk_mb, max_len, tile_step, nullptr, &capped);
         else if (tiled) session.SetQueriesFastaTiled(pos[k], width, dna, chunk_mb, max_len, tile_step, nullptr, &capped);
         else session.SetQueriesFasta(pos[k], width, dna, chunk_mb, nullptr, &cut, &capped);
@@ -1046,6 +1137,12 @@ int GhostmSearchMain(int argc, char **argv) {
             const GhostmMaskStats &ms = session.MaskStats();
             std::cout << "# " << pos[k] << " masked letters " << ms.masked_letters << " sources " << ms.masked_sources
                       << " of " << ms.mask_sources << " seconds " << ms.seconds_mask << std::endl;
+          }
+          if (quality.On()) {
+            const GhostmQualStats &qs = session.QualityStats();
+            std::cout << "# " << pos[k] << " quality trimmed 5' " << qs.trimmed5 << " 3' " << qs.trimmed3 << " masked "
+                      << qs.masked << " failed reads " << qs.failed << " of " << qs.reads << " seconds "
+                      << qs.seconds_quality << std::endl;
           }
         }
       } catch (std::exception &e) {

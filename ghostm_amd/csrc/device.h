@@ -42,6 +42,7 @@ struct GapConfig {
 struct DevQuery;
 struct DevDb;
 struct MaskParams;  // query_mask.h
+struct QualParams;  // read_quality.h
 
 // One hit chosen by the device merge (K4), after its traceback (K3):
 // subject-relative coordinates, ml = (aln_len << 8) | matches.
@@ -115,6 +116,7 @@ struct DeviceTimes {
   GhostmPairJoinStats pair{};            // k_pair_join
   GhostmTaxonProfileStats profile{};     // k_taxon_*
   GhostmMaskStats mask{};                // k_mask_windows + k_mask_apply
+  GhostmQualStats qual{};                // k_qual_trim
 };
 
 class DeviceModule {
@@ -164,6 +166,16 @@ class DeviceModule {
   // counters, seconds_mask the two kernels' device time.
   void MaskQuery(DevQuery *q, uint32_t nsrc, const GhostmBandSource *src, uint32_t step, const MaskParams &params,
                  uint32_t *masked, GhostmMaskStats *call);
+  // The quality stage of n reads (read_quality.h; kernel: read_quality.hip) on
+  // the main stream: read r is len[r] bytes at off[r] of letters and of qual.
+  // The reads go up in pieces of at most a fixed number of bytes (whole reads,
+  // packed one after the other), each piece is trimmed and masked by one
+  // launch, and its records and, with mask_q on, its masked letters come back
+  // before the next piece goes up: the device never holds more than one piece.
+  // The caller has made ValidateQuality's checks and params.On() holds. *call
+  // (may be null): this call's counters, seconds_quality the kernel's device time.
+  void QualityTrim(uint8_t *letters, const uint8_t *qual, const uint64_t *off, const uint32_t *len, uint32_t n,
+                   const QualParams &params, GhostmQualOut *out, GhostmQualStats *call);
   // A resident chunk's coded records (nseq * L bytes) back on the host.
   size_t QueryBytes(const DevQuery *q) const;
   void DownloadQuery(const DevQuery *q, uint8_t *dst);

@@ -32,6 +32,7 @@
 #include "pileup_plan.h"
 #include "qformat.h"
 #include "query_mask.h"
+#include "read_quality.h"
 #include "query_tiles.h"
 #include "score_tasks.h"
 
@@ -350,6 +351,10 @@ struct DeviceModule::Impl {
   // records' counts followed by the counter slots; the kernels' events
   DevBuf mask_src, mask_off, mask_bits, mask_out;
   hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;
+  // QualityTrim: a piece's letters, qualities, offsets and lengths, its records
+  // followed by the counter slots; the kernel's events
+  DevBuf rq_letters, rq_qual, rq_off, rq_len, rq_out;
+  hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;
   // FormatDb: the chunk's packed letters, the index build's (key, position)
   // pairs with their ping-pong copies and its scan arrays; the kernels' events
   // (coding: ev_d0..ev_d1, index: ev_d1..ev_d2), the word that comes back
@@ -448,7 +453,8 @@ void DeviceModule::Bind(int device) {
 #endif
   for (hipEvent_t *e : {&impl_->ev0, &impl_->ev1, &impl_->ev_m0, &impl_->ev_m1, &impl_->ev_t0, &impl_->ev_t1, &impl_->ev_tk,
                         &impl_->ev_done, &impl_->ev_tasks, &impl_->ev_s0, &impl_->ev_s1, &impl_->ev_nb, &impl_->ev_q0,
-                        &impl_->ev_q1, &impl_->ev_d0, &impl_->ev_d1, &impl_->ev_d2, &impl_->ev_k0, &impl_->ev_k1})
+                        &impl_->ev_q1, &impl_->ev_d0, &impl_->ev_d1, &impl_->ev_d2, &impl_->ev_k0, &impl_->ev_k1, &impl_->ev_r0,
+                        &impl_->ev_r1})
     HIP_CHECK(hipEventCreate(e));
   for (hipEvent_t &e : impl_->stage_ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   HIP_CHECK(hipFuncSetAttribute((const void *)kern::k_seed<1024, 16384, false>,
@@ -765,6 +771,100 @@ void DeviceModule::MaskQuery(DevQuery *q, uint32_t nsrc, const GhostmBandSource 
   t.mask_windows += one.mask_windows;
   t.masked_sources += one.masked_sources;
   t.masked_letters += one.masked_letters;
+  if (call) *call = one;
+}
+
+static_assert(sizeof(GhostmQualOut) == 16, "the records come back as they are");
+
+void DeviceModule::QualityTrim(uint8_t *letters, const uint8_t *qual, const uint64_t *off, const uint32_t *len,
+                               uint32_t n, const QualParams &params, GhostmQualOut *out, GhostmQualStats *call) {
+  if (!impl_) throw Error("quality: the device module is not bound to a device");
+  Use();
+  if (call) *call = GhostmQualStats{};
+  if (n == 0 || !params.On()) return;
+  Impl &I = *impl_;
+  hipStream_t st = S(stream_);
+  // a piece: whole reads while their letters stay within kPiece (one read alone is at most 2^24) and at most kPieceReads
+  constexpr uint64_t kPiece = 64ull << 20;
+  constexpr uint32_t kPieceReads = 1u << 22;
+  const size_t slot_words = (size_t)kQualCounterSlots * kQualCounterWords, slot_bytes = slot_words * 8;
+  std::vector<uint8_t> pack_l, pack_q;
+  std::vector<uint64_t> pack_off;
+  std::vector<uint64_t> slots(slot_words);
+  GhostmQualStats one{};
+  for (uint32_t r0 = 0; r0 < n;) {
+    uint32_t r1 = r0;
+    uint64_t bytes = 0;
+    while (r1 < n && r1 - r0 < kPieceReads && (r1 == r0 || bytes + len[r1] <= kPiece)) bytes += len[r1++];
+    const uint32_t m = r1 - r0;
+    pack_l.resize(bytes);
+    pack_q.resize(bytes);
+    pack_off.resize(m);
+    uint64_t at = 0;
+    for (uint32_t r = r0; r < r1; ++r) {
+      pack_off[r - r0] = at;
+      if (len[r]) {
+        std::memcpy(pack_l.data() + at, letters + off[r], len[r]);
+        std::memcpy(pack_q.data() + at, qual + off[r], len[r]);
+      }
+      at += len[r];
+    }
+    const size_t out_bytes = (size_t)m * sizeof(GhostmQualOut);  // a multiple of 16: the slots behind it are aligned
+    I.rq_letters.Reserve(bytes);
+    I.rq_qual.Reserve(bytes);
+    I.rq_off.Reserve((size_t)m * 8);
+    I.rq_len.Reserve((size_t)m * 4);
+    I.rq_out.Reserve(out_bytes + slot_bytes);
+    StagedUpload(I.rq_letters.p, pack_l.data(), bytes);
+    StagedUpload(I.rq_qual.p, pack_q.data(), bytes);
+    StagedUpload(I.rq_off.p, pack_off.data(), (size_t)m * 8);
+    StagedUpload(I.rq_len.p, len + r0, (size_t)m * 4);
+    HIP_CHECK(hipMemsetAsync(I.rq_out.p, 0, out_bytes + slot_bytes, st));
+    uint64_t *counters = reinterpret_cast<uint64_t *>(I.rq_out.as<uint8_t>() + out_bytes);
+    HIP_CHECK(hipEventRecord(I.ev_r0, st));
+    LaunchQualityTrim(stream_, I.rq_letters.as<uint8_t>(), I.rq_qual.as<uint8_t>(), I.rq_off.as<uint64_t>(),
+                      I.rq_len.as<uint32_t>(), m, params, I.rq_out.as<GhostmQualOut>(), counters);
+    HIP_CHECK(hipEventRecord(I.ev_r1, st));
+    HIP_CHECK(hipMemcpyAsync(out + r0, I.rq_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(slots.data(), counters, slot_bytes, hipMemcpyDeviceToHost, st));
+    if (params.mask_q && bytes) HIP_CHECK(hipMemcpyAsync(pack_l.data(), I.rq_letters.p, bytes, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (params.mask_q) {  // only the masked letters changed; reads that share bytes keep each other's
+      for (uint32_t r = r0; r < r1; ++r) {
+        const GhostmQualOut &o = out[r];
+        if (!o.masked) continue;
+        const uint8_t *from = pack_l.data() + pack_off[r - r0];
+        uint8_t *to = letters + off[r];
+        for (uint32_t i = o.begin; i < o.begin + o.kept; ++i)
+          if (from[i] == 'N') to[i] = 'N';
+      }
+    }
+    for (uint32_t k = 0; k < kQualCounterSlots; ++k) {
+      const uint64_t *w = &slots[(size_t)k * kQualCounterWords];
+      one.trimmed5 += w[0];
+      one.trimmed3 += w[1];
+      one.masked += w[2];
+      one.failed += w[3];
+      one.bad += w[4];
+    }
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, I.ev_r0, I.ev_r1));
+    one.seconds_quality += ms * 1e-3;
+    one.launches += 1;
+    one.reads += m;
+    one.letters += bytes;
+    r0 = r1;
+  }
+  GhostmQualStats &t = times_.qual;
+  t.launches += one.launches;
+  t.reads += one.reads;
+  t.letters += one.letters;
+  t.trimmed5 += one.trimmed5;
+  t.trimmed3 += one.trimmed3;
+  t.masked += one.masked;
+  t.failed += one.failed;
+  t.bad += one.bad;
+  t.seconds_quality += one.seconds_quality;
   if (call) *call = one;
 }
 
@@ -4314,6 +4414,33 @@ int MaskRecordsGpu(uint8_t *query_seqs, uint32_t nq, uint32_t L, uint32_t nsrc, 
 
 size_t GhostmStageMaskStats(GhostmMaskStats *stats, size_t size) {
   return StageStats(&DeviceTimes::mask, stats, size);
+}
+
+int QualityTrimGpu(uint8_t *letters, const uint8_t *qual, uint64_t total, const uint64_t offsets[],
+                   const uint32_t lengths[], uint32_t n, uint32_t trim_q, uint32_t mask_q, uint32_t min_len,
+                   GhostmQualOut out[]) {
+  // everything is checked before the device is as much as bound
+  const std::string why = ValidateQuality(letters, qual, total, offsets, lengths, n, trim_q, mask_q, min_len, out);
+  if (!why.empty()) {
+    SetError("QualityTrimGpu: " + why);
+    return 1;
+  }
+  QualParams params;
+  params.trim_q = trim_q;
+  params.mask_q = mask_q;
+  params.min_len = min_len;
+  if (!params.On()) {  // off: nothing is launched
+    for (uint32_t r = 0; r < n; ++r) out[r] = GhostmQualOut{0, lengths[r], 0, 0};
+    return 0;
+  }
+  if (n == 0) return 0;
+  return UnboundStageCall("QualityTrimGpu", [&](DeviceModule &m) {
+    m.QualityTrim(letters, qual, offsets, lengths, n, params, out, nullptr);
+  });
+}
+
+size_t GhostmStageQualStats(GhostmQualStats *stats, size_t size) {
+  return StageStats(&DeviceTimes::qual, stats, size);
 }
 
 }  // extern "C"

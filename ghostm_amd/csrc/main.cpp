@@ -61,6 +61,9 @@ static int Usage() {
             << "       [-Z window,trigger,extend]: low-complexity stretches of the reads masked with X before the search\n"
             << "        (SEG's raw segments; window 6..32, levels in hundredths of a bit, 0 <= trigger <= extend <= 500;\n"
             << "        e.g. -Z 12,220,250)\n"
+            << "       [-Q trimQ,maskQ,minLen]: FASTQ reads (a file that begins with '@'; needs -T) trimmed at both ends by\n"
+            << "        BWA's running sum at quality trimQ, kept letters below maskQ stored as N, reads left shorter than\n"
+            << "        minLen emptied; 0..93, 0..93, 0..2^24 (e.g. -Q 20,0,30); read coordinates are of the kept stretch\n"
             << "       [-j | -J] [-I maxInsert]: with -T, mate pairs. -j: records 2i and 2i + 1 of every input file are\n"
             << "        mates; -J: the positionals are triples r1.fasta r2.fasta out, interleaved record by record. A hit\n"
             << "        of each mate on one subject, at most maxInsert (default 1000; nt for DNA) apart and, for DNA, on\n"

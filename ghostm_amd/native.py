@@ -103,6 +103,33 @@ class GhostmMaskStats(ctypes.Structure):
     ]
 
 
+class GhostmQualOut(ctypes.Structure):
+    """one read's record of the quality stage (GhostmQualityTrimHost, GhostmSessionQueryQuality)."""
+
+    _fields_ = [
+        ("begin", ctypes.c_uint32),
+        ("kept", ctypes.c_uint32),
+        ("masked", ctypes.c_uint32),
+        ("bad", ctypes.c_uint32),
+    ]
+
+
+class GhostmQualStats(ctypes.Structure):
+    """the counters of the quality stage (GhostmSessionQualityStats, GhostmStageQualStats)."""
+
+    _fields_ = [
+        ("launches", ctypes.c_uint64),
+        ("reads", ctypes.c_uint64),
+        ("letters", ctypes.c_uint64),
+        ("trimmed5", ctypes.c_uint64),
+        ("trimmed3", ctypes.c_uint64),
+        ("masked", ctypes.c_uint64),
+        ("failed", ctypes.c_uint64),
+        ("bad", ctypes.c_uint64),
+        ("seconds_quality", ctypes.c_double),
+    ]
+
+
 class GhostmBandStats(ctypes.Structure):
     """the counters of the band pass (GhostmSessionBandStats, GhostmStageBandStats)."""
 
@@ -530,6 +557,11 @@ SIGNATURES = {
     "MaskRecordsGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint32, c_uint32, c_uint32, POINTER(GhostmBandSource),
                                c_uint32, c_uint32, c_uint32, c_uint32, u32p]),
     "GhostmStageMaskStats": (c_size_t, [POINTER(GhostmMaskStats), c_size_t]),
+    "GhostmQualityTrimHost": (c_int, [POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64),
+                                      u32p, c_uint32, c_uint32, c_uint32, c_uint32, POINTER(GhostmQualOut)]),
+    "QualityTrimGpu": (c_int, [POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p,
+                               c_uint32, c_uint32, c_uint32, c_uint32, POINTER(GhostmQualOut)]),
+    "GhostmStageQualStats": (c_size_t, [POINTER(GhostmQualStats), c_size_t]),
     "FrameAlignGpu": (c_int, [c_uint32, POINTER(GhostmBandSource), POINTER(ctypes.c_int32), u32p, u32p, c_uint32,
                               c_uint32, c_uint32, c_int, c_int, c_int, POINTER(GhostmHitPath), u32p, c_size_t,
                               POINTER(c_size_t)]),
@@ -626,6 +658,16 @@ SIGNATURES = {
     "GhostmSessionSetMask": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32]),
     "GhostmSessionQueryMasked": (c_size_t, [c_void_p, u32p, c_size_t]),
     "GhostmSessionMaskStats": (c_size_t, [c_void_p, POINTER(GhostmMaskStats), c_size_t]),
+    "GhostmSessionSetQuality": (c_int, [c_void_p, c_uint32, c_uint32, c_uint32]),
+    "GhostmSessionSetQueriesFastqTiled": (c_int, [c_void_p, c_char_p, c_uint32, c_int, c_uint32, c_uint32, c_uint32,
+                                                  POINTER(c_uint64)]),
+    "GhostmSessionSetQueriesFastqMatesTiled": (c_int, [c_void_p, c_char_p, c_char_p, c_uint32, c_int, c_uint32,
+                                                       c_uint32, c_uint32, POINTER(c_uint64)]),
+    "GhostmSessionSetQueriesQualTiled": (c_int, [c_void_p, POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint8), c_uint64,
+                                                 POINTER(c_uint64), u32p, c_char_p, c_uint64, c_uint32, c_uint32,
+                                                 c_int, c_uint32, c_uint32, c_uint32]),
+    "GhostmSessionQueryQuality": (c_size_t, [c_void_p, POINTER(GhostmQualOut), c_size_t]),
+    "GhostmSessionQualityStats": (c_size_t, [c_void_p, POINTER(GhostmQualStats), c_size_t]),
     "GhostmSessionHitsFrame": (c_size_t, [c_void_p, POINTER(GhostmHitPath), c_size_t]),
     "GhostmSessionFrameOps": (c_size_t, [c_void_p, u32p, c_size_t]),
     "GhostmSessionFrameInfo": (c_size_t, [c_void_p, POINTER(GhostmHitFrameInfo), c_size_t]),

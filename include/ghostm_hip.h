@@ -767,6 +767,82 @@ typedef struct GhostmMaskStats {
  * conventions. */
 size_t GhostmStageMaskStats(GhostmMaskStats *stats, size_t size);
 
+/* Quality trimming and masking of FASTQ reads. A miscalled 3' tail translates
+ * into wrong residues in all six frames, which seed, vote and land in a clade;
+ * the base qualities say where it begins. The stage runs on the GPU on the
+ * reads' letters, before they are formatted and before the low-complexity mask.
+ *
+ * Integer arithmetic, so that host and device agree byte for byte. A read has n
+ * letters and n quality bytes; q[i] = min(max(byte, 33), 126) - 33 (Phred+33);
+ * a byte outside '!'..'~' is counted in `bad`.
+ *
+ * Parameters: trim_q 0..93, mask_q 0..93, min_len 0..2^24. All three 0: off.
+ *
+ * End trimming: the running-sum rule of BWA (-q) and cutadapt. Both ends are
+ * found on the untrimmed read, d[i] = trim_q - q[i].
+ *   3' end: i = n - 1, n - 2, ... with s += d[i], stopping at the first s < 0;
+ *           end = the i where s first reached its greatest value > 0 (the
+ *           largest such i), or n when there is none
+ *   5' end: i = 0, 1, ... likewise; begin = i + 1 for the i where s first
+ *           reached its greatest value > 0 (the smallest such i), or 0
+ *   kept = end - begin when end > begin; else begin = 0, kept = 0
+ * With trim_q 0 nothing is trimmed.
+ * Floor: kept < min_len gives kept = 0, begin = 0, masked = 0 and leaves the
+ * letters untouched (the read stays in the set as an empty record).
+ * Masking: every kept letter with q[i] < mask_q is stored as 'N' (the query
+ * formatter turns a codon with an N into X) and counted in `masked`. Letters
+ * outside [begin, begin + kept) are never rewritten.
+ *
+ * GhostmQualityTrimHost: the rule on the host, letter by letter, with no device
+ * call (the model the kernel is checked against). Read r is lengths[r] bytes at
+ * offsets[r] of letters and of qual (both `total` bytes); letters are masked in
+ * place, out[n] receives one record per read. With all three parameters 0 the
+ * qualities are not read and out[r] = {0, lengths[r], 0, 0}. Everything is
+ * checked first; a refused call leaves letters and out untouched and names its
+ * reason in GhostmGetLastError:
+ *   "param"   a parameter out of range
+ *   "null"    a null array with n > 0
+ *   "record"  an offset or a length outside `total`
+ *   "length"  a read of over 2^24 letters (the running sums are 32 bits wide) */
+typedef struct GhostmQualOut {
+  uint32_t begin;   /* the first kept letter */
+  uint32_t kept;    /* kept letters; 0: the read is empty (crossing ends, or the floor) */
+  uint32_t masked;  /* kept letters stored as 'N' */
+  uint32_t bad;     /* quality bytes outside '!'..'~', over the whole read */
+} GhostmQualOut;
+int GhostmQualityTrimHost(uint8_t *letters, const uint8_t *qual, uint64_t total, const uint64_t offsets[],
+                          const uint32_t lengths[], uint32_t n, uint32_t trim_q, uint32_t mask_q,
+                          uint32_t min_len, GhostmQualOut out[]);
+
+/* The same on the GPU (kernel k_qual_trim: one wave per read, 64 positions at a
+ * time from each end, the running sum a wave prefix scan on top of the carried
+ * sum, the stop the lowest bit of a ballot), stage level: the reads go up in
+ * bounded pieces of whole reads, so a large sample is never staged whole, and
+ * the records and the masked letters come back piece by piece. The same checks
+ * and reasons, all made before any upload or launch; with n == 0 or all three
+ * parameters 0 nothing is launched. */
+int QualityTrimGpu(uint8_t *letters, const uint8_t *qual, uint64_t total, const uint64_t offsets[],
+                   const uint32_t lengths[], uint32_t n, uint32_t trim_q, uint32_t mask_q, uint32_t min_len,
+                   GhostmQualOut out[]);
+
+/* The counters of the quality stage. A read left empty counts all its letters
+ * as trimmed3, so letters = trimmed5 + trimmed3 + the kept letters. */
+typedef struct GhostmQualStats {
+  uint64_t launches;   /* k_qual_trim launches: one per piece */
+  uint64_t reads;
+  uint64_t letters;
+  uint64_t trimmed5;   /* letters cut at the 5' end of reads that keep any */
+  uint64_t trimmed3;   /* letters cut at the 3' end, and all letters of the reads left empty */
+  uint64_t masked;     /* letters stored as 'N' */
+  uint64_t failed;     /* reads emptied by the floor (kept < min_len) */
+  uint64_t bad;        /* quality bytes outside '!'..'~' */
+  double seconds_quality;  /* k_qual_trim, device time */
+} GhostmQualStats;
+
+/* The quality counters behind the stage-level call; GhostmStageBandStats'
+ * conventions. */
+size_t GhostmStageQualStats(GhostmQualStats *stats, size_t size);
+
 /* Frameshift-aware read-level alignments of DNA reads. BandAlignGpu aligns one
  * frame; after a single-nucleotide insertion or deletion the true alignment of
  * a read continues in another frame of the same strand, and this pass follows
@@ -1757,6 +1833,54 @@ size_t GhostmSessionQueryMasked(void *session, uint32_t *masked, size_t cap);
 /* The mask counters of the session's current query set (all 0 for a set made
  * with masking off); the size convention of GhostmSessionDbStats. */
 size_t GhostmSessionMaskStats(void *session, GhostmMaskStats *stats, size_t size);
+
+/* Quality trimming and masking of the session's FASTQ and quality-carrying
+ * query sets (the rule above GhostmQualityTrimHost). 0, 0, 0 is off, the
+ * default; otherwise trim_q and mask_q 0..93 and min_len 0..2^24 (a refusal
+ * names "param" and leaves the old setting). The setting takes effect at the
+ * next GhostmSessionSetQueriesFastq*Tiled / GhostmSessionSetQueriesQualTiled
+ * call; the current set and its results stay as they are. Refused on a shard
+ * session, as the setters are. */
+int GhostmSessionSetQuality(void *session, uint32_t trim_q, uint32_t mask_q, uint32_t min_len);
+
+/* GhostmSessionSetQueriesFastaTiled from a FASTQ file: strict four-line records
+ * ('@' name, letters, '+' line, qualities of the letters' length; CRLF is
+ * tolerated; blank lines only between records and at the end; the name is the
+ * header after '@' with leading blanks dropped, as for '>'). Multi-line FASTQ
+ * and compressed files are not read. A malformed file is refused with
+ * "fastq: record N: <reason>", N counted from 1.
+ * The path: the file is parsed, the quality stage runs on all reads (when it is
+ * on), read r enters as letters[begin, begin + kept) under its name, max_len
+ * then cuts what was kept, and the set is tiled as ever. A read left empty stays
+ * a source record with one all-X tile per frame, so record indices and mates do
+ * not move. Every read coordinate the session reports is relative to the kept
+ * stretch; GhostmSessionQueryQuality's begin converts it back.
+ * A read with a quality byte outside '!'..'~' refuses the set ("fastq: record N:
+ * quality byte outside '!'..'~'"). Any refusal leaves the session as it was.
+ * With quality off the stage is not launched and the set is that of the FASTA
+ * file of the same names and letters. */
+int GhostmSessionSetQueriesFastqTiled(void *session, const char *path, uint32_t width, int dna, uint32_t chunk_mb,
+                                      uint32_t max_len, uint32_t step, uint64_t *cut_records);
+/* The same over two FASTQ files of mates (GhostmSessionSetQueriesFastaMatesTiled):
+ * a mate left empty stays a record, so the pairing holds. */
+int GhostmSessionSetQueriesFastqMatesTiled(void *session, const char *path1, const char *path2, uint32_t width,
+                                           int dna, uint32_t chunk_mb, uint32_t max_len, uint32_t step,
+                                           uint64_t *cut_records);
+/* The letters form: GhostmSessionSetQueriesTiled's arguments with the reads'
+ * quality bytes, qual[raw_len] laid out as raw. raw is not changed. */
+int GhostmSessionSetQueriesQualTiled(void *session, const uint8_t *raw, const uint8_t *qual, uint64_t raw_len,
+                                     const uint64_t *offsets, const uint32_t *lengths, const char *names,
+                                     uint64_t names_len, uint32_t n, uint32_t width, int dna, uint32_t chunk_mb,
+                                     uint32_t max_len, uint32_t step);
+
+/* One record per source read of the current set, in the reads' order; the
+ * NULL/cap convention of GhostmSessionHits. 0 entries when the quality stage did
+ * not run for the set. */
+size_t GhostmSessionQueryQuality(void *session, GhostmQualOut *out, size_t cap);
+
+/* The quality counters of the session's current query set (all 0 when the stage
+ * did not run); the size convention of GhostmSessionDbStats. */
+size_t GhostmSessionQualityStats(void *session, GhostmQualStats *stats, size_t size);
 
 /* The frameshift-aware read-level path of every hit of the last run (record i
  * belongs to hit i) and the run-length words they index, in hit order (the
