@@ -62,7 +62,7 @@ inline BandRows BandRowRange(uint32_t m, int32_t D, uint32_t B, uint32_t s_lo, u
 // operation advances i or j, i over the rows and j over rows + 2B columns.
 inline uint32_t BandDirStride(uint32_t B) { return (2 * B + 1 + 3) & ~3u; }
 inline size_t BandDirBytes(uint32_t rows, uint32_t B) { return (size_t)rows * BandDirStride(B); }
-inline size_t BandOpsSlot(uint32_t rows, uint32_t B) { return rows ? 2 * (size_t)rows + 2 * B + 2 : 0; }
+constexpr size_t BandOpsSlot(uint32_t rows, uint32_t B) { return rows ? 2 * (size_t)rows + 2 * B + 2 : 0; }
 
 // Letter p of a source through the tile table: the record and the byte in it.
 inline size_t BandLetterAt(const GhostmBandSource &s, uint32_t p, uint32_t W, uint32_t step) {

@@ -107,8 +107,8 @@ struct DeviceTimes {
   uint64_t pileup_launches = 0, pileup_windows = 0, pileup_parts = 0, pileup_columns = 0;  // k_pileup launches,
                                                   // profile windows, (tile, part) workgroups, columns added
   // the read-level passes' counters as the public structs hand them out (include/ghostm_hip.h)
-  GhostmBandStats band{};                // k_band_fill + k_band_walk + k_band_compact
-  GhostmFrameStats frame{};              // k_frame_fill + k_frame_walk + k_frame_compact, counted as the band pass
+  GhostmBandStats band{};                // k_band_fill<false> + k_band_walk<false> + k_ops_compact
+  GhostmFrameStats frame{};              // the <true> instantiations + k_ops_compact, counted as the band pass
   GhostmReadRowsStats read_rows{};       // k_read_rows
   GhostmReadPileupStats read_pileup{};   // k_read_pileup + k_pileup_finish<true>, counted as the pile-up
   GhostmReadCullStats cull{};            // k_read_cull
@@ -306,7 +306,7 @@ class DeviceModule {
   // CutBatch (hit_batches.h) with the direction buffer's bytes as the cost,
   // GHOSTM_PATH_SCRATCH_MB (default 1024) as the budget and
   // GHOSTM_PATH_BATCH_HITS as the hit cap; a batch's slots are packed on the
-  // device (kern::k_tb_path_compact, the offsets from the host's prefix sum
+  // device (kern::k_ops_compact, the offsets from the host's prefix sum
   // over the records) and the batches' words joined in hit order on the host.
   // Throws what RefuseHits says (L > 127, L + window >= 32768, an empty
   // window, a hit outside the chunks). Adds its device time, batches, cells
@@ -420,8 +420,8 @@ class DeviceModule {
                     size_t *nout, uint32_t *final_node, GhostmTaxonSummary *summary,
                     std::vector<GhostmTaxonCount> *grow = nullptr);
 
-  // The read-level banded alignment of n hits (kern::k_band_fill, k_band_walk,
-  // k_band_compact; the contract is in include/ghostm_hip.h): hit i aligns
+  // The read-level banded alignment of n hits (kern::k_band_fill<false>,
+  // k_band_walk<false>, k_ops_compact; the contract is in include/ghostm_hip.h): hit i aligns
   // source src[i] of chunk q (W = q's record width, tile step `step`) to
   // subject range [s_lo[i], s_hi[i]] of chunk d around diagonal D[i] with
   // half-width B. Everything is checked first (ValidateBand, band_align.h;
@@ -435,8 +435,8 @@ class DeviceModule {
                  const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B, int open, int ext,
                  GhostmHitPath *rec, std::vector<uint32_t> *ops);
 
-  // The frameshift-aware read-level alignment (kern::k_frame_fill,
-  // k_frame_walk, k_frame_compact): BandAlign with strand sources (src[i] names
+  // The frameshift-aware read-level alignment (kern::k_band_fill<true>,
+  // k_band_walk<true>, k_ops_compact): BandAlign with strand sources (src[i] names
   // frame 0 of a strand; ValidateFrame, frame_align.h) and the frameshift cost
   // `shift`. Buffers of its own, the budget GHOSTM_FRAME_SCRATCH_MB, the cap
   // GHOSTM_FRAME_BATCH_HITS, and the frame_* fields of times().

@@ -2712,11 +2712,12 @@ void DeviceModule::TraceBackPath(DevQuery *q, DevDb *d, uint32_t n, const uint32
     if (ops && packed) {
       I.tb_path_cmp.Reserve(packed * 4);
       HIP_CHECK(hipMemcpyAsync(d_off, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
-      a.cmp_off = d_off;
-      a.cmp = I.tb_path_cmp.as<uint32_t>();
-      TimedLaunch(I.ev0, I.ev1, S(stream_),
-                  [&] { hipLaunchKernelGGL(kern::k_tb_path_compact, lane_grid, block, 0, S(stream_), a); });
-      HIP_CHECK(hipMemcpyAsync(pw.batch_words.back().data(), a.cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
+      uint32_t *cmp = I.tb_path_cmp.as<uint32_t>();
+      const dim3 wave_grid((m + kern::kTbBlock / 64 - 1) / (kern::kTbBlock / 64));  // one wave per slot
+      TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
+        hipLaunchKernelGGL(kern::k_ops_compact, wave_grid, block, 0, S(stream_), a.rec, a.ops, a.ops_off, cmp, d_off, m);
+      });
+      HIP_CHECK(hipMemcpyAsync(pw.batch_words.back().data(), cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
       HIP_CHECK(hipStreamSynchronize(S(stream_)));
       times_.traceback_path += ElapsedMs(I.ev0, I.ev1) * 1e-3;
     }
@@ -2910,8 +2911,8 @@ void DeviceModule::FrameAlign(DevQuery *q, DevDb *d, uint32_t n, const GhostmBan
 }
 
 // Both read-level passes: the band pass, and the frame pass (frame: the rows
-// are the three nucleotide rows of every codon row, the kernels k_frame_*, and
-// buffers, limits and counters of its own).
+// are the three nucleotide rows of every codon row, the kernels' <true>
+// instantiations, and buffers, limits and counters of its own).
 void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32_t n, const GhostmBandSource *src,
                             const int32_t *D, const uint32_t *s_lo, const uint32_t *s_hi, uint32_t step, uint32_t B,
                             int open, int ext, GhostmHitPath *rec, std::vector<uint32_t> *ops) {
@@ -3002,6 +3003,7 @@ void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32
     a.stride = stride;
     a.open = open;
     a.ext = ext;
+    a.shift = shift;
     a.dir = buf.dir.as<uint8_t>();
     a.best = d_best;
     a.ops_off = d_off;
@@ -3011,15 +3013,9 @@ void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32
     const dim3 wave_grid((m + kern::kTbBlock / 64 - 1) / (kern::kTbBlock / 64));  // one wave per slot
     const dim3 lane_grid((m + kern::kTbBlock - 1) / kern::kTbBlock);              // one lane per slot
     TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
-      if (frame) {
-        hipLaunchKernelGGL(kern::k_frame_fill, wave_grid, block, 0, S(stream_), (kern::FrameArgs{a, shift}));
-        HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(kern::k_frame_walk, lane_grid, block, 0, S(stream_), (kern::FrameArgs{a, shift}));
-      } else {
-        hipLaunchKernelGGL(kern::k_band_fill, wave_grid, block, 0, S(stream_), a);
-        HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(kern::k_band_walk, lane_grid, block, 0, S(stream_), a);
-      }
+      hipLaunchKernelGGL(frame ? kern::k_band_fill<true> : kern::k_band_fill<false>, wave_grid, block, 0, S(stream_), a);
+      HIP_CHECK(hipGetLastError());
+      hipLaunchKernelGGL(frame ? kern::k_band_walk<true> : kern::k_band_walk<false>, lane_grid, block, 0, S(stream_), a);
     });
     h_rec.resize((size_t)m * 6);
     HIP_CHECK(hipMemcpyAsync(h_rec.data(), d_rec, (size_t)m * 24, hipMemcpyDeviceToHost, S(stream_)));
@@ -3035,15 +3031,11 @@ void DeviceModule::BandPass(bool frame, int shift, DevQuery *q, DevDb *d, uint32
     if (ops && packed) {
       buf.cmp.Reserve(packed * 4);
       HIP_CHECK(hipMemcpyAsync(d_off + m, off.data(), (size_t)m * 8, hipMemcpyHostToDevice, S(stream_)));
-      a.cmp_off = d_off + m;
-      a.cmp = buf.cmp.as<uint32_t>();
+      uint32_t *cmp = buf.cmp.as<uint32_t>();
       TimedLaunch(I.ev0, I.ev1, S(stream_), [&] {
-        if (frame)
-          hipLaunchKernelGGL(kern::k_frame_compact, wave_grid, block, 0, S(stream_), (kern::FrameArgs{a, shift}));
-        else
-          hipLaunchKernelGGL(kern::k_band_compact, wave_grid, block, 0, S(stream_), a);
+        hipLaunchKernelGGL(kern::k_ops_compact, wave_grid, block, 0, S(stream_), a.rec, a.ops, a.ops_off, cmp, d_off + m, m);
       });
-      HIP_CHECK(hipMemcpyAsync(pw.batch_words.back().data(), a.cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
+      HIP_CHECK(hipMemcpyAsync(pw.batch_words.back().data(), cmp, packed * 4, hipMemcpyDeviceToHost, S(stream_)));
       HIP_CHECK(hipStreamSynchronize(S(stream_)));
       lv.seconds += ElapsedMs(I.ev0, I.ev1) * 1e-3;
     }
@@ -3754,7 +3746,7 @@ const char *SourceHash();  // build_hash.cpp, generated by the Makefile (ghostm_
 const char *DeviceBuildInfo() {
   static const std::string info =
       std::string("ghostm_hip gfx950: K1 k_seed_lists/k_seed_filter/k_seed_hash/k_seed, K2 k_score16f/k_score16/"
-                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_tb_path_compact/k_path_rows/k_read_rows/k_pileup/k_read_pileup/k_pileup_finish/k_read_cull/k_pair_join/k_read_lca_wave/k_read_lca/k_taxon_count/k_taxon_climb/k_taxon_floor/k_taxon_final/k_taxon_sort_tile/k_taxon_sort_step/k_taxon_emit/k_band_fill/k_band_walk/k_band_compact/k_frame_fill/k_frame_walk/k_frame_compact, K4 k_merge_wave/k_merge"
+                  "k_score, K3 k_tb_scan/k_traceback_key/k_traceback/k_traceback_ext/k_tb_path_fill/k_tb_path_walk/k_ops_compact/k_path_rows/k_read_rows/k_pileup/k_read_pileup/k_pileup_finish/k_read_cull/k_pair_join/k_read_lca_wave/k_read_lca/k_taxon_count/k_taxon_climb/k_taxon_floor/k_taxon_final/k_taxon_sort_tile/k_taxon_sort_step/k_taxon_emit/k_band_fill/k_band_walk, K4 k_merge_wave/k_merge"
 #ifdef GHOSTM_LDS_POISON
                   "; LDS poison build"
 #endif

@@ -69,7 +69,7 @@ inline size_t FrameDirBytes(uint32_t rows, uint32_t B) { return (size_t)rows * B
 //                   p has grown by at least the first one's 3 (a pair with its
 //                   shift still advances p by 2, a 'D' leaves it)
 // so words <= 2 * (codons + 2B) + codons = rows + 4B; the slot adds 4 spare.
-inline size_t FrameOpsSlot(uint32_t rows, uint32_t B) { return rows ? (size_t)rows + 4 * B + 4 : 0; }
+constexpr size_t FrameOpsSlot(uint32_t rows, uint32_t B) { return rows ? (size_t)rows + 4 * B + 4 : 0; }
 
 // The scratch bytes of one hit in a batch: its direction bytes and word slot.
 inline size_t FrameScratchBytes(uint32_t rows, uint32_t B) { return FrameDirBytes(rows, B) + 4 * FrameOpsSlot(rows, B); }

@@ -7,8 +7,8 @@
 // term its H took, which of the three continuations its pair took and whether
 // its E and F extended or opened; then the walk from the first strict maximum,
 // forward in both sequences. The recurrence is run cell by cell, sequentially;
-// no device call: this is the model k_frame_fill / k_frame_walk (kernels.h) are
-// checked against.
+// no device call: this is the model k_band_fill<true> / k_band_walk<true>
+// (kernels.h) are checked against.
 #include <algorithm>
 #include <cstdint>
 #include <string>

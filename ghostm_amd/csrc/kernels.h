@@ -24,6 +24,8 @@
 
 #include <type_traits>
 
+#include "band_align.h"
+#include "frame_align.h"
 #include "lds_poison.h"
 #include "libstdcxx_sort.h"
 #include "score_task.h"
@@ -3072,7 +3074,7 @@ __device__ inline int ShiftUpI(int v) { return __builtin_amdgcn_update_dpp(0, v,
 //   F: emits 'I', goes to F(j, k+1) if fext else H(j, k+1).
 // It writes run-length words len << 4 | op into the slot's ncols + L words at
 // ops + ops_off[s] and six record words (q_start, q_end, s_start, s_end, score,
-// n_runs). k_tb_path_compact then copies every slot's n_runs words to its
+// n_runs). k_ops_compact then copies every slot's n_runs words to its
 // place in one packed array (the offsets are the host's prefix sum over the
 // records it read back), so only the words used travel to the host. Padding rows (query position >= L) hold kPadCode: their H stays 0
 // and their E and F stay negative, so row L - 1 sees the same H and the same
@@ -3094,9 +3096,6 @@ struct TbPathArgs {
   const unsigned long long *ops_off;  // per slot: first of its ncols + L run-length words
   uint32_t *ops;
   uint32_t *rec;                      // per slot: q_start, q_end, s_start, s_end, score, n_runs
-  // compaction (k_tb_path_compact): the slots' words packed in slot order
-  const unsigned long long *cmp_off;  // per slot: its first word in cmp (the host's prefix sum of n_runs)
-  uint32_t *cmp;
 };
 constexpr uint32_t kPathEExt = 4u, kPathFExt = 8u;
 
@@ -3220,6 +3219,24 @@ __global__ __launch_bounds__(kTbBlock) void k_tb_path_fill(TbPathArgs a) {
   WaveAddCells(a.cells, (valid && i == 0) ? (unsigned long long)ncols * a.L : 0ull);
 }
 
+// The run-length words of a walk (this one's and k_band_walk's): the operations
+// come one by one, a word is len << 4 | op, and words past cap are dropped.
+struct RunWords {
+  uint32_t *out;
+  uint32_t cap, nruns = 0, cur = 0, len = 0;
+  __device__ __forceinline__ void emit(uint32_t op) {
+    if (op != cur) {
+      finish();
+      len = 0;
+    }
+    cur = op;
+    ++len;
+  }
+  __device__ __forceinline__ void finish() {
+    if (len && nruns < cap) out[nruns++] = len << 4 | cur;
+  }
+};
+
 // log2w: log2 of the fill's S / 8
 __global__ __launch_bounds__(kTbBlock) void k_tb_path_walk(TbPathArgs a, uint32_t log2w) {
   GHOSTM_POISON_LDS();
@@ -3231,11 +3248,10 @@ __global__ __launch_bounds__(kTbBlock) void k_tb_path_walk(TbPathArgs a, uint32_
   const uint8_t *qs = a.qseq + (size_t)a.qid[hit] * a.L;
   const uint32_t *dir = a.dir + a.dir_off[slot];
   const size_t colw = (size_t)a.G << log2w;
-  uint32_t *out = a.ops + a.ops_off[slot];
   const uint32_t cap = width + a.L;
+  RunWords w{a.ops + a.ops_off[slot], cap};
   const uint32_t bj = a.best[3 * (size_t)slot], bk = a.best[3 * (size_t)slot + 1], score = a.best[3 * (size_t)slot + 2];
   int j = (int)bj, k = (int)bk;
-  uint32_t nruns = 0, cur = 0, len = 0;
   if (score > 0 && bj < width) {
     int state = 0;
     // every operation consumes a query or a subject residue: at most cap of them
@@ -3259,14 +3275,9 @@ __global__ __launch_bounds__(kTbBlock) void k_tb_path_walk(TbPathArgs a, uint32_
         state = (b & kPathFExt) ? 2 : 0;
         ++k;
       }
-      if (len && op != cur) {
-        if (nruns < cap) out[nruns++] = len << 4 | cur;
-        len = 0;
-      }
-      cur = op;
-      ++len;
+      w.emit(op);
     }
-    if (len && nruns < cap) out[nruns++] = len << 4 | cur;
+    w.finish();
   }
   uint32_t *r = a.rec + 6 * (size_t)slot;
   r[0] = bk;
@@ -3274,17 +3285,23 @@ __global__ __launch_bounds__(kTbBlock) void k_tb_path_walk(TbPathArgs a, uint32_
   r[2] = p0 - bj;
   r[3] = score > 0 ? p0 - (uint32_t)(j + 1) : p0 - bj;
   r[4] = score;
-  r[5] = nruns;
+  r[5] = w.nruns;
 }
 
-__global__ __launch_bounds__(kTbBlock) void k_tb_path_compact(TbPathArgs a) {
+// The compaction of the three path passes (this one, band and frame): slot s's
+// rec[6s + 5] words at ops + ops_off[s] go to cmp + cmp_off[s]. One wave per
+// slot, consecutive lanes on consecutive words.
+__global__ __launch_bounds__(kTbBlock) void k_ops_compact(const uint32_t *rec, const uint32_t *ops,
+                                                          const unsigned long long *ops_off, uint32_t *cmp,
+                                                          const unsigned long long *cmp_off, uint32_t n) {
   GHOSTM_POISON_LDS();
-  const uint32_t slot = blockIdx.x * kTbBlock + threadIdx.x;
-  if (slot >= a.n) return;
-  const uint32_t n = a.rec[6 * (size_t)slot + 5];
-  const uint32_t *src = a.ops + a.ops_off[slot];
-  uint32_t *dst = a.cmp + a.cmp_off[slot];
-  for (uint32_t k = 0; k < n; ++k) dst[k] = src[k];
+  const uint32_t lane = threadIdx.x & 63;
+  const uint32_t slot = blockIdx.x * (kTbBlock / 64) + (threadIdx.x >> 6);
+  if (slot >= n) return;
+  const uint32_t words = rec[6 * (size_t)slot + 5];
+  const uint32_t *src = ops + ops_off[slot];
+  uint32_t *dst = cmp + cmp_off[slot];
+  for (uint32_t k = lane; k < words; k += 64) dst[k] = src[k];
 }
 
 // ------------------------------------------------------------------ aligned residue rows
@@ -5083,9 +5100,12 @@ __global__ __launch_bounds__(kScanBlock) void k_tb_scan(TbScanArgs a) {
 }
 
 // ------------------------------------------------------------------ read-level banded alignment
-// k_band_fill + k_band_walk + k_band_compact: the read-level path of every hit
-// (BandAlignGpu, include/ghostm_hip.h; host model band_align_host.cpp). One
-// wave per hit; lane b = j - i - D + B (0..2B, at most 63 lanes) owns one
+// k_band_fill<FRAME> + k_band_walk<FRAME> + k_ops_compact: the read-level path
+// of every hit, at the band level (<false>: BandAlignGpu, include/ghostm_hip.h;
+// host model band_align_host.cpp) and at the frame level (<true>: FrameAlignGpu;
+// host model frame_align_host.cpp). The band level first; the frame level is
+// stated below as what it changes.
+// One wave per hit; lane b = j - i - D + B (0..2B, at most 63 lanes) owns one
 // diagonal of the band, so in the reverse DP over rows i = i_top .. i_top -
 // rows + 1
 //   the diagonal term H(i+1, j+1) is the lane's own H of the previous row,
@@ -5103,16 +5123,42 @@ __global__ __launch_bounds__(kScanBlock) void k_tb_scan(TbScanArgs a) {
 // tie opens as in the model. Every lane keeps its first strict maximum (value,
 // i); the wave reduces by (value, i, lane), the model's first strict maximum in
 // processing order. The letters: q[i] is wave-uniform and read through the
-// tile table (BandLetter, a restatement of band_align.h / query_tiles.h), db[j]
-// one byte per lane; both are loaded one row ahead of their use.
+// tile table (BandLetterByte, which restates BandLetterAt of band_align.h),
+// db[j] one byte per lane; both are loaded one row ahead of their use.
 // Direction bytes, one per lane and row at dir + dir_off + (i_top - i) *
 // stride + b (consecutive lanes, consecutive bytes): bits 0-1 hsel, bit 2
 // eext, bit 3 fext, bit 4 the two codes are equal (so the walk reads no
 // sequence). k_band_walk follows them with one lane per hit, a separate launch
-// so the bytes are visible, and writes run-length words into the slot's
-// 2 * rows + 2B + 2 words and six record words; k_band_compact packs the
+// so the bytes are visible, and writes run-length words (RunWords) into the
+// slot's BandOpsSlot / FrameOpsSlot words and six record words; k_ops_compact packs the
 // slots' words (one wave per slot, consecutive lanes on consecutive words).
 // The host has checked every index (ValidateBand, band_align.h).
+//
+// The frame level: the rows are strand positions p = 3c + g of one strand's
+// three frames. Lane b = j - c - D + B owns one codon diagonal, so a lane's
+// column j = c + D - B + b is the same in the three rows of a codon and moves by
+// one between codons. The lane keeps its H of rows p+1 .. p+4 and its F of rows
+// p+1 .. p+3 in registers. In row p, by g = p % 3 (the rows of a codon are
+// unrolled, g is a constant in each):
+//   H(p+3, j+1)             the lane's own H3 (one codon up, same diagonal)
+//   H(p+3, j), F(p+3, j)    lane b-1's H3, F3 (DPP wave_shr)
+//   H(p+2, j+1)             g = 0: row p+2 is in this codon, lane b+1's H2
+//                           (shuffle down, 0 past the wave); else the lane's own
+//   H(p+4, j+1)             g = 2: row p+4 is two codons up, lane b-1's H4
+//                           (DPP wave_shr, lane 0 reads 0); else the lane's own
+// and the pair term is the largest of H3, H2 + shift, H4 + shift plus the
+// score, the first on a tie; bits 5-6 of the direction byte hold which (fsel).
+// Rows at or past 3m and above the rows run are the registers' initial values:
+// the model's neighbour values. Everything past the pair term is the band
+// level's: the lane range (BandLaneOf), F, the E chain, the selection and the
+// bits (BandCellStep), the best cell (BandStoreBest, by (value, p, lane)). A
+// codon's three letters q(3c), q(3c+1), q(3c+2) are byte c of the frames'
+// records, W bytes apart: the tile arithmetic runs once per codon, and they and
+// db[j] are loaded one codon ahead. BandHit.i_top / rows are the codon rows
+// c_top / codons; the rows run are 3 * codons, p_top = 3 * c_top + 2. The walk
+// adds the shift ops 5 ('/', to p+2) and 4 ('\', to p+4) after a pair column
+// whose fsel is 1 / 2. The host has checked every index (ValidateFrame,
+// frame_align.h).
 constexpr int kBandNeg = -(1 << 29);  // = ghostm::kBandNegInf (checked in device.hip)
 struct BandHit {                      // 48 bytes, one per batch slot
   uint32_t first_record, stride, tiles, letters;
@@ -5131,21 +5177,29 @@ struct BandArgs {
   uint32_t n;                         // slots of the batch
   uint32_t B, stride;                 // half-width; direction bytes per row
   int open, ext;
+  int shift;                          // the frame level's shift cost, <= 0 (the band level ignores it)
   uint8_t *dir;
-  uint32_t *best;                     // per slot: i*, j*, score
+  uint32_t *best;                     // per slot: i* (frame: p*), j*, score
   const unsigned long long *ops_off;  // per slot: first of its run-length words
   uint32_t *ops;
   uint32_t *rec;                      // per slot: q_start, q_end, s_start, s_end, score, n_runs
-  const unsigned long long *cmp_off;  // per slot: its first word in cmp
-  uint32_t *cmp;
 };
 
-__device__ __forceinline__ uint32_t BandLetter(const uint8_t *qseq, const BandHit &h, uint32_t p, uint32_t W,
-                                               uint32_t step) {
+// byte of letter p of the hit's source in qseq, through the tile table
+__device__ __forceinline__ size_t BandLetterByte(const BandHit &h, uint32_t p, uint32_t W, uint32_t step) {
   const uint32_t t = min(p / step, h.tiles - 1);
   const uint32_t start = t + 1 < h.tiles ? t * step : (h.letters > W ? h.letters - W : 0u);
   const uint32_t rec = h.first_record + (h.tiles > 1 ? h.stride * t : 0u);
-  return qseq[(size_t)rec * W + (p - start)];
+  return (size_t)rec * W + (p - start);
+}
+// the band level's letter q[i]
+__device__ __forceinline__ uint32_t BandLetter(const BandArgs &a, const BandHit &h, uint32_t i) {
+  return a.qseq[BandLetterByte(h, i, a.W, a.step)] & 31u;
+}
+// the frame level's letters of codon c of the three frames: g's in bits 8g .. 8g+4
+__device__ __forceinline__ uint32_t FrameLetters(const BandArgs &a, const BandHit &h, uint32_t c) {
+  const uint8_t *q = a.qseq + BandLetterByte(h, c, a.W, a.step);
+  return (q[0] & 31u) | (q[a.W] & 31u) << 8 | (q[2 * (size_t)a.W] & 31u) << 16;
 }
 
 // lane l receives lane l+d's value, the lanes past the wave's end `fill`
@@ -5154,6 +5208,86 @@ __device__ __forceinline__ int BandShiftDown(int v, uint32_t d, uint32_t lane, i
   return lane + d > 63u ? fill : x;
 }
 
+// A lane's part of a hit: its column in (codon) row i is i + j0 and a band cell
+// for i in [lo, hi] (an empty range for the lanes above 2B); dbp[i] is its
+// residue there (read only where valid), dir its byte of the first row.
+struct BandLane {
+  int lo, hi;
+  const uint8_t *dbp;
+  uint8_t *dir;
+  bool writes;
+};
+__device__ __forceinline__ BandLane BandLaneOf(const BandArgs &a, const BandHit &hit, uint32_t lane) {
+  const long long j0 = (long long)hit.D - (long long)a.B + (long long)lane;
+  const long long i_bot = (long long)hit.i_top - (long long)hit.rows + 1;
+  long long vlo = (long long)hit.s_lo - j0, vhi = (long long)hit.s_hi - j0;
+  if (lane > 2u * a.B) vhi = -1, vlo = 0;  // never
+  BandLane l;
+  l.lo = (int)min(max(vlo, i_bot), (long long)hit.i_top + 1);
+  l.hi = (int)max(min(vhi, (long long)hit.i_top), i_bot - 1);
+  l.dbp = a.db + j0;
+  l.dir = a.dir + hit.dir_off + lane;
+  l.writes = lane < a.stride;
+  return l;
+}
+
+// One cell from its pair term s (the diagonal's H plus the score) and the
+// lane's own H and F of the row (codon) above, Hu and Fu, of which F takes lane
+// b-1's: the cell's H, its F for the row below and its direction byte; H 0, F
+// minus infinity and byte 0 where the cell is no band cell.
+struct BandCell {
+  int H, F;
+  uint32_t bits;
+};
+__device__ __forceinline__ BandCell BandCellStep(const BandArgs &a, uint32_t lane, int s, int Hu, int Fu, bool valid,
+                                                 bool same, uint32_t fsel) {
+  // both shifts by every lane (a DPP move reads its neighbour only while that lane is enabled), then lane 0's F
+  int Hb = (int)ShiftUp((uint32_t)Hu), Fb = (int)ShiftUp((uint32_t)Fu);
+  if (lane == 0) Fb = kBandNeg;  // (Hb is 0 there: bound_ctrl)
+  const int fe = Fb + a.ext, fo = Hb + a.open;
+  const int F = max(fe, fo);
+  const int Hh = valid ? max(max(s, F), 0) : 0;
+  // the E chain: E(b) = max over b' > b of Hh(b') + open + ext * (b' - b - 1)
+  int E = BandShiftDown(Hh + a.open, 1, lane, kBandNeg);
+  for (uint32_t d = 1; d <= 2u * a.B; d <<= 1) E = max(E, BandShiftDown(E, d, lane, kBandNeg) + a.ext * (int)d);
+  int cell = 0;
+  uint32_t bits = 0;
+  if (s > 0) { cell = s; bits = 1; }
+  if (E > cell) { cell = E; bits = 2; }
+  if (F > cell) { cell = F; bits = 3; }
+  const int Hc = valid ? cell : 0, Ec = valid ? E : kBandNeg;
+  // eext from lane b+1's final values (no band cell: H 0, E minus infinity)
+  const int Er = BandShiftDown(Ec, 1, lane, kBandNeg), Hr = BandShiftDown(Hc, 1, lane, 0);
+  bits |= (Er + a.ext > Hr + a.open ? 4u : 0u) | (fe > fo ? 8u : 0u) | (same ? 16u : 0u) | fsel << 5;
+  return BandCell{Hc, valid ? F : kBandNeg, valid ? bits : 0u};
+}
+
+// The wave's first strict maximum in processing order from the lanes' (best,
+// row): largest value, then largest row, then largest lane. UNIT rows make one
+// codon row (the lane's column moves with the codon row).
+template <uint32_t UNIT>
+__device__ __forceinline__ void BandStoreBest(const BandArgs &a, const BandHit &hit, uint32_t slot, uint32_t lane,
+                                              int best, uint32_t best_row) {
+  uint32_t bl = lane;
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const int ov = __shfl_xor(best, d);
+    const uint32_t orow = (uint32_t)__shfl_xor((int)best_row, d), ol = (uint32_t)__shfl_xor((int)bl, d);
+    if (ov > best || (ov == best && (orow > best_row || (orow == best_row && ol > bl)))) {
+      best = ov;
+      best_row = orow;
+      bl = ol;
+    }
+  }
+  if (lane == 0) {
+    uint32_t *o = a.best + 3 * (size_t)slot;
+    o[0] = best > 0 ? best_row : 0u;
+    o[1] = best > 0 ? (uint32_t)((long long)(best_row / UNIT) + hit.D - (long long)a.B + (long long)bl) : hit.s_lo;
+    o[2] = (uint32_t)best;
+  }
+}
+
+template <bool FRAME>
 __global__ __launch_bounds__(kTbBlock) void k_band_fill(BandArgs a) {
   GHOSTM_POISON_LDS();
   __shared__ int s_mat[32 * 32];
@@ -5163,106 +5297,111 @@ __global__ __launch_bounds__(kTbBlock) void k_band_fill(BandArgs a) {
   const uint32_t slot = blockIdx.x * (kTbBlock / 64) + (threadIdx.x >> 6);
   if (slot >= a.n) return;  // the whole wave
   const BandHit hit = a.hit[slot];
-  const int B = (int)a.B;
   int best = 0;
-  uint32_t best_i = 0;
+  uint32_t best_row = 0;  // i, at the frame level p
   if (hit.rows) {
-    // this lane's column in row i is i + j0; it is a band cell for i in [vlo, vhi]
-    const long long j0 = (long long)hit.D - B + (long long)lane;
-    const long long i_bot = (long long)hit.i_top - (long long)hit.rows + 1;
-    long long vlo = (long long)hit.s_lo - j0, vhi = (long long)hit.s_hi - j0;
-    if (lane > 2u * a.B) vhi = -1, vlo = 0;  // never
-    const int lo = (int)min(max(vlo, i_bot), (long long)hit.i_top + 1);
-    const int hi = (int)max(min(vhi, (long long)hit.i_top), i_bot - 1);
-    const uint8_t *dbp = a.db + j0;  // dbp[i] is the lane's residue in row i (read only where valid)
-    uint8_t *dir = a.dir + hit.dir_off + lane;
-    const bool writes = lane < a.stride;
-    int Hp = 0, Fp = kBandNeg;
-    int i = (int)hit.i_top;
-    uint32_t qn = BandLetter(a.qseq, hit, (uint32_t)i, a.W, a.step) & 31u;
-    uint32_t dn = i >= lo && i <= hi ? dbp[i] & 31u : 0u;
-    for (uint32_t r = 0; r < hit.rows; ++r, --i) {
-      const uint32_t qc = qn, dc = dn;
-      const bool valid = i >= lo && i <= hi;
-      if (r + 1 < hit.rows) {  // the next row's letters
-        qn = BandLetter(a.qseq, hit, (uint32_t)(i - 1), a.W, a.step) & 31u;
-        dn = i - 1 >= lo && i - 1 <= hi ? dbp[i - 1] & 31u : 0u;
+    const BandLane l = BandLaneOf(a, hit, lane);
+    int i = (int)hit.i_top;  // the (codon) row
+    // the letters of the first (codon) row (the subject's byte first costs both fills two VGPRs)
+    uint32_t qn = FRAME ? FrameLetters(a, hit, (uint32_t)i) : BandLetter(a, hit, (uint32_t)i);
+    uint32_t dn = i >= l.lo && i <= l.hi ? l.dbp[i] & 31u : 0u;
+    if constexpr (!FRAME) {
+      int Hp = 0, Fp = kBandNeg;
+      for (uint32_t r = 0; r < hit.rows; ++r, --i) {
+        const uint32_t qc = qn, dc = dn;
+        const bool valid = i >= l.lo && i <= l.hi;
+        if (r + 1 < hit.rows) {  // the next row's letters
+          qn = BandLetter(a, hit, (uint32_t)(i - 1));
+          dn = i - 1 >= l.lo && i - 1 <= l.hi ? l.dbp[i - 1] & 31u : 0u;
+        }
+        const BandCell c = BandCellStep(a, lane, Hp + s_mat[dc * 32 + qc], Hp, Fp, valid, dc == qc, 0);
+        if (l.writes) l.dir[(size_t)r * a.stride] = (uint8_t)c.bits;
+        if (c.H > best) {
+          best = c.H;
+          best_row = (uint32_t)i;
+        }
+        Hp = c.H;
+        Fp = c.F;
       }
-      int Hb = (int)ShiftUp((uint32_t)Hp), Fb = (int)ShiftUp((uint32_t)Fp);
-      if (lane == 0) Fb = kBandNeg;  // (Hb is 0 there: bound_ctrl)
-      const int s = Hp + s_mat[dc * 32 + qc];
-      const int fe = Fb + a.ext, fo = Hb + a.open;
-      const int F = max(fe, fo);
-      const int Hh = valid ? max(max(s, F), 0) : 0;
-      // the E chain: E(b) = max over b' > b of Hh(b') + open + ext * (b' - b - 1)
-      int E = BandShiftDown(Hh + a.open, 1, lane, kBandNeg);
-      for (uint32_t d = 1; d <= 2u * a.B; d <<= 1) E = max(E, BandShiftDown(E, d, lane, kBandNeg) + a.ext * (int)d);
-      int cell = 0;
-      uint32_t bits = 0;
-      if (s > 0) { cell = s; bits = 1; }
-      if (E > cell) { cell = E; bits = 2; }
-      if (F > cell) { cell = F; bits = 3; }
-      const int Hc = valid ? cell : 0, Ec = valid ? E : kBandNeg;
-      // eext from lane b+1's final values (no band cell: H 0, E minus infinity)
-      const int Er = BandShiftDown(Ec, 1, lane, kBandNeg), Hr = BandShiftDown(Hc, 1, lane, 0);
-      bits |= (Er + a.ext > Hr + a.open ? 4u : 0u) | (fe > fo ? 8u : 0u) | (dc == qc ? 16u : 0u);
-      if (writes) dir[(size_t)r * a.stride] = valid ? (uint8_t)bits : (uint8_t)0;
-      if (Hc > best) {
-        best = Hc;
-        best_i = (uint32_t)i;
-      }
-      Hp = Hc;
-      Fp = valid ? F : kBandNeg;
-    }
-  }
-  // the first strict maximum in processing order: largest value, then largest i, then largest lane
-  uint32_t bl = lane;
+    } else {
+      int H1 = 0, H2 = 0, H3 = 0, H4 = 0, F1 = kBandNeg, F2 = kBandNeg, F3 = kBandNeg;
+      size_t row = 0;
+      for (uint32_t k = 0; k < hit.rows; ++k, --i) {
+        const uint32_t q3 = qn, dc = dn;
+        const int *mrow = s_mat + dc * 32;
+        const bool valid = i >= l.lo && i <= l.hi;
+        if (k + 1 < hit.rows) {  // the next codon's letters
+          qn = FrameLetters(a, hit, (uint32_t)(i - 1));
+          dn = i - 1 >= l.lo && i - 1 <= l.hi ? l.dbp[i - 1] & 31u : 0u;
+        }
 #pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const int ov = __shfl_xor(best, d);
-    const uint32_t oi = (uint32_t)__shfl_xor((int)best_i, d), ol = (uint32_t)__shfl_xor((int)bl, d);
-    if (ov > best || (ov == best && (oi > best_i || (oi == best_i && ol > bl)))) {
-      best = ov;
-      best_i = oi;
-      bl = ol;
+        for (int g = 2; g >= 0; --g, ++row) {
+          const uint32_t qc = (q3 >> (8 * g)) & 31u;
+          const int d1 = (g == 0 ? BandShiftDown(H2, 1, lane, 0) : H2) + a.shift;
+          const int d2 = (g == 2 ? (int)ShiftUp((uint32_t)H4) : H4) + a.shift;
+          int diag = H3;
+          uint32_t fsel = 0;
+          if (d1 > diag) { diag = d1; fsel = 1; }
+          if (d2 > diag) { diag = d2; fsel = 2; }
+          const BandCell c = BandCellStep(a, lane, diag + mrow[qc], H3, F3, valid, dc == qc, fsel);
+          if (l.writes) l.dir[row * a.stride] = (uint8_t)c.bits;
+          if (c.H > best) {
+            best = c.H;
+            best_row = 3u * (uint32_t)i + (uint32_t)g;
+          }
+          H4 = H3;
+          H3 = H2;
+          H2 = H1;
+          H1 = c.H;
+          F3 = F2;
+          F2 = F1;
+          F1 = c.F;
+        }
+      }
     }
   }
-  if (lane == 0) {
-    uint32_t *o = a.best + 3 * (size_t)slot;
-    o[0] = best > 0 ? best_i : 0u;
-    o[1] = best > 0 ? (uint32_t)((long long)best_i + hit.D - B + (long long)bl) : hit.s_lo;
-    o[2] = (uint32_t)best;
-  }
+  BandStoreBest<FRAME ? 3 : 1>(a, hit, slot, lane, best, best_row);
 }
 
+template <bool FRAME>
 __global__ __launch_bounds__(kTbBlock) void k_band_walk(BandArgs a) {
   GHOSTM_POISON_LDS();
   const uint32_t slot = blockIdx.x * kTbBlock + threadIdx.x;
   if (slot >= a.n) return;
   const BandHit hit = a.hit[slot];
   const uint8_t *dir = a.dir + hit.dir_off;
-  uint32_t *out = a.ops + a.ops_off[slot];
-  const uint32_t cap = hit.rows ? 2 * hit.rows + 2 * a.B + 2 : 0;
+  constexpr long long U = FRAME ? 3 : 1;  // rows of a codon row
+  // the slot the host gave the hit (band_align.h, frame_align.h, where the bound is derived)
+  const uint32_t cap = (uint32_t)(FRAME ? FrameOpsSlot(3 * hit.rows, a.B) : BandOpsSlot(hit.rows, a.B));
+  RunWords w{a.ops + a.ops_off[slot], cap};
   const uint32_t bi = a.best[3 * (size_t)slot], bj = a.best[3 * (size_t)slot + 1], score = a.best[3 * (size_t)slot + 2];
-  long long i = bi, j = bj;
-  const long long i_bot = (long long)hit.i_top - (long long)hit.rows + 1;
-  uint32_t nruns = 0, cur = 0, len = 0;
+  long long i = bi, j = bj;  // the row: i, at the frame level p
+  const long long top = U * hit.i_top + (U - 1), bot = top - U * hit.rows + 1;
   if (score > 0) {
     int state = 0;
-    // every operation consumes a query or a subject residue: at most cap of them, and a state change between two
+    // every iteration emits an operation or changes to a gap state that emits in the next one
     for (uint32_t it = 0; it < 2 * cap + 2; ++it) {
-      const long long b = j - i - hit.D + (long long)a.B;
-      // the band cells (inside them the row is one of the rows run)
-      if (i >= (long long)hit.letters || j > (long long)hit.s_hi || b < 0 || b > 2ll * a.B) break;
-      if (i > (long long)hit.i_top || i < i_bot) break;
-      const uint32_t d = dir[(size_t)((long long)hit.i_top - i) * a.stride + (size_t)b];
-      uint32_t op;
+      // the band cells (inside them the row is one of the rows run, so i >= 0)
+      if (i > top || i < bot || i >= U * hit.letters || j > (long long)hit.s_hi) break;
+      const long long b = j - i / U - hit.D + (long long)a.B;
+      if (b < 0 || b > 2ll * a.B) break;
+      const uint32_t d = dir[(size_t)(top - i) * a.stride + (size_t)b];
+      uint32_t op;  // emitted behind the states (an emit in each costs the band level two VGPRs)
       if (state == 0) {
         const uint32_t sel = d & 3u;
         if (sel == 0) break;
         if (sel != 1) { state = sel == 2 ? 1 : 2; continue; }
         op = (d & 16u) ? 0u : 1u;
-        ++i;
+        if constexpr (FRAME) {  // the pair's shift op follows it
+          const uint32_t fsel = (d >> 5) & 3u;
+          if (fsel == 1 || fsel == 2) {
+            w.emit(op);
+            op = fsel == 1 ? 5u : 4u;
+          }
+          i += fsel == 1 ? 2 : fsel == 2 ? 4 : 3;
+        } else {
+          ++i;
+        }
         ++j;
       } else if (state == 1) {
         op = 3u;
@@ -5271,16 +5410,11 @@ __global__ __launch_bounds__(kTbBlock) void k_band_walk(BandArgs a) {
       } else {
         op = 2u;
         state = (d & 8u) ? 2 : 0;
-        ++i;
+        i += U;
       }
-      if (len && op != cur) {
-        if (nruns < cap) out[nruns++] = len << 4 | cur;
-        len = 0;
-      }
-      cur = op;
-      ++len;
+      w.emit(op);
     }
-    if (len && nruns < cap) out[nruns++] = len << 4 | cur;
+    w.finish();
   }
   uint32_t *r = a.rec + 6 * (size_t)slot;
   r[0] = bi;
@@ -5288,231 +5422,7 @@ __global__ __launch_bounds__(kTbBlock) void k_band_walk(BandArgs a) {
   r[2] = bj;
   r[3] = score > 0 ? (uint32_t)(j - 1) : bj;
   r[4] = score;
-  r[5] = nruns;
-}
-
-__global__ __launch_bounds__(kTbBlock) void k_band_compact(BandArgs a) {
-  GHOSTM_POISON_LDS();
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t slot = blockIdx.x * (kTbBlock / 64) + (threadIdx.x >> 6);
-  if (slot >= a.n) return;
-  const uint32_t n = a.rec[6 * (size_t)slot + 5];
-  const uint32_t *src = a.ops + a.ops_off[slot];
-  uint32_t *dst = a.cmp + a.cmp_off[slot];
-  for (uint32_t k = lane; k < n; k += 64) dst[k] = src[k];
-}
-
-// ------------------------------------------------------------------ frameshift-aware read-level alignment
-// k_frame_fill + k_frame_walk + k_frame_compact: the frame path of every hit
-// (FrameAlignGpu, include/ghostm_hip.h; host model frame_align_host.cpp). The
-// band kernels' structure with rows that are strand positions p = 3c + g of one
-// strand's three frames: one wave per hit, lane b = j - c - D + B owns one
-// codon diagonal, so a lane's column j = c + D - B + b is the same in the three
-// rows of a codon and moves by one between codons. The lane keeps its H of rows
-// p+1 .. p+4 and its F of rows p+1 .. p+3 in registers. In row p, by g = p % 3
-// (the rows of a codon are unrolled, g is a constant in each):
-//   H(p+3, j+1)             the lane's own H3 (one codon up, same diagonal)
-//   H(p+3, j), F(p+3, j)    lane b-1's H3, F3 (DPP wave_shr)
-//   H(p+2, j+1)             g = 0: row p+2 is in this codon, lane b+1's H2
-//                           (shuffle down, 0 past the wave); else the lane's own
-//   H(p+4, j+1)             g = 2: row p+4 is two codons up, lane b-1's H4
-//                           (DPP wave_shr, lane 0 reads 0); else the lane's own
-// A lane whose cell is no band cell carries H = 0, E = F = kBandNeg, and rows
-// at or past 3m and above the rows run are the registers' initial values: the
-// model's neighbour values. The E chain, eext / fext, the best-cell reduction
-// (value, p, lane) and the direction bytes are k_band_fill's; bits 5-6 of a byte
-// hold fsel. A codon's three letters q(3c), q(3c+1), q(3c+2) are byte c of the
-// frames' records, W bytes apart: the tile arithmetic runs once per codon, and
-// they and db[j] are loaded one codon ahead. BandHit.i_top / rows are the codon
-// rows c_top / codons; the rows run are 3 * codons, p_top = 3 * c_top + 2.
-// k_frame_walk adds the shift ops 5 ('/', to p+2) and 4 ('\', to p+4) after a
-// pair column whose fsel is 1 / 2. The host has checked every index
-// (ValidateFrame, frame_align.h).
-struct FrameArgs {
-  BandArgs band;
-  int shift;  // <= 0
-};
-
-// the letters of codon c of the three frames: g's in bits 8g .. 8g+4
-__device__ __forceinline__ uint32_t FrameLetters(const uint8_t *qseq, const BandHit &h, uint32_t c, uint32_t W,
-                                                 uint32_t step) {
-  const uint32_t t = min(c / step, h.tiles - 1);
-  const uint32_t start = t + 1 < h.tiles ? t * step : (h.letters > W ? h.letters - W : 0u);
-  const uint32_t rec = h.first_record + (h.tiles > 1 ? h.stride * t : 0u);
-  const uint8_t *q = qseq + (size_t)rec * W + (c - start);
-  return (q[0] & 31u) | (q[W] & 31u) << 8 | (q[2 * (size_t)W] & 31u) << 16;
-}
-
-__global__ __launch_bounds__(kTbBlock) void k_frame_fill(FrameArgs fa) {
-  GHOSTM_POISON_LDS();
-  const BandArgs &a = fa.band;
-  __shared__ int s_mat[32 * 32];
-  for (uint32_t e = threadIdx.x; e < 32 * 32; e += kTbBlock) s_mat[e] = a.mat[e];
-  __syncthreads();
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t slot = blockIdx.x * (kTbBlock / 64) + (threadIdx.x >> 6);
-  if (slot >= a.n) return;  // the whole wave
-  const BandHit hit = a.hit[slot];
-  const int B = (int)a.B;
-  int best = 0;
-  uint32_t best_p = 0;
-  if (hit.rows) {
-    // this lane's column in codon row c is c + j0; it is a band cell for c in [vlo, vhi]
-    const long long j0 = (long long)hit.D - B + (long long)lane;
-    const long long c_bot = (long long)hit.i_top - (long long)hit.rows + 1;
-    long long vlo = (long long)hit.s_lo - j0, vhi = (long long)hit.s_hi - j0;
-    if (lane > 2u * a.B) vhi = -1, vlo = 0;  // never
-    const int lo = (int)min(max(vlo, c_bot), (long long)hit.i_top + 1);
-    const int hi = (int)max(min(vhi, (long long)hit.i_top), c_bot - 1);
-    const uint8_t *dbp = a.db + j0;  // dbp[c] is the lane's residue in codon row c (read only where valid)
-    uint8_t *dir = a.dir + hit.dir_off + lane;
-    const bool writes = lane < a.stride;
-    int H1 = 0, H2 = 0, H3 = 0, H4 = 0, F1 = kBandNeg, F2 = kBandNeg, F3 = kBandNeg;
-    int c = (int)hit.i_top;
-    uint32_t qn = FrameLetters(a.qseq, hit, (uint32_t)c, a.W, a.step);
-    uint32_t dn = c >= lo && c <= hi ? dbp[c] & 31u : 0u;
-    size_t row = 0;
-    for (uint32_t k = 0; k < hit.rows; ++k, --c) {
-      const uint32_t q3 = qn;
-      const int *mrow = s_mat + dn * 32;
-      const uint32_t dc = dn;
-      const bool valid = c >= lo && c <= hi;
-      if (k + 1 < hit.rows) {  // the next codon's letters
-        qn = FrameLetters(a.qseq, hit, (uint32_t)(c - 1), a.W, a.step);
-        dn = c - 1 >= lo && c - 1 <= hi ? dbp[c - 1] & 31u : 0u;
-      }
-#pragma unroll
-      for (int g = 2; g >= 0; --g, ++row) {
-        const uint32_t qc = (q3 >> (8 * g)) & 31u;
-        int Hb = (int)ShiftUp((uint32_t)H3), Fb = (int)ShiftUp((uint32_t)F3);
-        if (lane == 0) Fb = kBandNeg;  // (Hb is 0 there: bound_ctrl)
-        const int d1 = (g == 0 ? BandShiftDown(H2, 1, lane, 0) : H2) + fa.shift;
-        const int d2 = (g == 2 ? (int)ShiftUp((uint32_t)H4) : H4) + fa.shift;
-        int diag = H3;
-        uint32_t fsel = 0;
-        if (d1 > diag) { diag = d1; fsel = 1; }
-        if (d2 > diag) { diag = d2; fsel = 2; }
-        const int s = diag + mrow[qc];
-        const int fe = Fb + a.ext, fo = Hb + a.open;
-        const int F = max(fe, fo);
-        const int Hh = valid ? max(max(s, F), 0) : 0;
-        // the E chain: E(b) = max over b' > b of Hh(b') + open + ext * (b' - b - 1)
-        int E = BandShiftDown(Hh + a.open, 1, lane, kBandNeg);
-        for (uint32_t d = 1; d <= 2u * a.B; d <<= 1) E = max(E, BandShiftDown(E, d, lane, kBandNeg) + a.ext * (int)d);
-        int cell = 0;
-        uint32_t bits = 0;
-        if (s > 0) { cell = s; bits = 1; }
-        if (E > cell) { cell = E; bits = 2; }
-        if (F > cell) { cell = F; bits = 3; }
-        const int Hc = valid ? cell : 0, Ec = valid ? E : kBandNeg;
-        const int Er = BandShiftDown(Ec, 1, lane, kBandNeg), Hr = BandShiftDown(Hc, 1, lane, 0);
-        bits |= (Er + a.ext > Hr + a.open ? 4u : 0u) | (fe > fo ? 8u : 0u) | (dc == qc ? 16u : 0u) | fsel << 5;
-        if (writes) dir[row * a.stride] = valid ? (uint8_t)bits : (uint8_t)0;
-        if (Hc > best) {
-          best = Hc;
-          best_p = 3u * (uint32_t)c + (uint32_t)g;
-        }
-        H4 = H3;
-        H3 = H2;
-        H2 = H1;
-        H1 = Hc;
-        F3 = F2;
-        F2 = F1;
-        F1 = valid ? F : kBandNeg;
-      }
-    }
-  }
-  // the first strict maximum in processing order: largest value, then largest p, then largest lane
-  uint32_t bl = lane;
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) {
-    const int ov = __shfl_xor(best, d);
-    const uint32_t op = (uint32_t)__shfl_xor((int)best_p, d), ol = (uint32_t)__shfl_xor((int)bl, d);
-    if (ov > best || (ov == best && (op > best_p || (op == best_p && ol > bl)))) {
-      best = ov;
-      best_p = op;
-      bl = ol;
-    }
-  }
-  if (lane == 0) {
-    uint32_t *o = a.best + 3 * (size_t)slot;
-    o[0] = best > 0 ? best_p : 0u;
-    o[1] = best > 0 ? (uint32_t)((long long)(best_p / 3) + hit.D - B + (long long)bl) : hit.s_lo;
-    o[2] = (uint32_t)best;
-  }
-}
-
-__global__ __launch_bounds__(kTbBlock) void k_frame_walk(FrameArgs fa) {
-  GHOSTM_POISON_LDS();
-  const BandArgs &a = fa.band;
-  const uint32_t slot = blockIdx.x * kTbBlock + threadIdx.x;
-  if (slot >= a.n) return;
-  const BandHit hit = a.hit[slot];
-  const uint8_t *dir = a.dir + hit.dir_off;
-  uint32_t *out = a.ops + a.ops_off[slot];
-  const uint32_t cap = hit.rows ? 3 * hit.rows + 4 * a.B + 4 : 0;
-  const uint32_t bp = a.best[3 * (size_t)slot], bj = a.best[3 * (size_t)slot + 1], score = a.best[3 * (size_t)slot + 2];
-  long long p = bp, j = bj;
-  const long long p_top = 3ll * hit.i_top + 2, p_bot = p_top - 3ll * hit.rows + 1;
-  uint32_t nruns = 0, cur = 0, len = 0;
-  auto emit = [&](uint32_t op) {
-    if (len && op != cur) {
-      if (nruns < cap) out[nruns++] = len << 4 | cur;
-      len = 0;
-    }
-    cur = op;
-    ++len;
-  };
-  if (score > 0) {
-    int state = 0;
-    // every iteration emits an operation or changes to a gap state that emits in the next one
-    for (uint32_t it = 0; it < 2 * cap + 2; ++it) {
-      // the band cells (inside them the row is one of the rows run, so p >= 0)
-      if (p > p_top || p < p_bot || p >= 3ll * hit.letters || j > (long long)hit.s_hi) break;
-      const long long b = j - p / 3 - hit.D + (long long)a.B;
-      if (b < 0 || b > 2ll * a.B) break;
-      const uint32_t d = dir[(size_t)(p_top - p) * a.stride + (size_t)b];
-      if (state == 0) {
-        const uint32_t sel = d & 3u;
-        if (sel == 0) break;
-        if (sel != 1) { state = sel == 2 ? 1 : 2; continue; }
-        emit((d & 16u) ? 0u : 1u);
-        const uint32_t fsel = (d >> 5) & 3u;
-        if (fsel == 1) emit(5u);
-        if (fsel == 2) emit(4u);
-        p += fsel == 1 ? 2 : fsel == 2 ? 4 : 3;
-        ++j;
-      } else if (state == 1) {
-        emit(3u);
-        state = (d & 4u) ? 1 : 0;
-        ++j;
-      } else {
-        emit(2u);
-        state = (d & 8u) ? 2 : 0;
-        p += 3;
-      }
-    }
-    if (len && nruns < cap) out[nruns++] = len << 4 | cur;
-  }
-  uint32_t *r = a.rec + 6 * (size_t)slot;
-  r[0] = bp;
-  r[1] = score > 0 ? (uint32_t)(p - 1) : bp;
-  r[2] = bj;
-  r[3] = score > 0 ? (uint32_t)(j - 1) : bj;
-  r[4] = score;
-  r[5] = nruns;
-}
-
-__global__ __launch_bounds__(kTbBlock) void k_frame_compact(FrameArgs fa) {
-  GHOSTM_POISON_LDS();
-  const BandArgs &a = fa.band;
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t slot = blockIdx.x * (kTbBlock / 64) + (threadIdx.x >> 6);
-  if (slot >= a.n) return;
-  const uint32_t n = a.rec[6 * (size_t)slot + 5];
-  const uint32_t *src = a.ops + a.ops_off[slot];
-  uint32_t *dst = a.cmp + a.cmp_off[slot];
-  for (uint32_t k = lane; k < n; k += 64) dst[k] = src[k];
+  r[5] = w.nruns;
 }
 
 // ------------------------------------------------------------ read-level cull

@@ -626,7 +626,7 @@ typedef struct GhostmBandSource {          /* 16 bytes */
   uint32_t letters;                        /* m, at least 1 */
 } GhostmBandSource;
 
-/* The read-level path of every hit (kernels k_band_fill + k_band_walk), stage
+/* The read-level path of every hit (kernels k_band_fill<false> + k_band_walk<false>), stage
  * level like TraceBackPathGpu (after SetQueryGpu and SetDbGpu);
  * query_sequence_length is the records' width W, step the tile step. Record i
  * belongs to hit i; the hits' words follow each other in hit order. ops ==
@@ -667,7 +667,7 @@ int GhostmBandAlignHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, cons
 /* The counters of the band pass. A struct of their own, like GhostmDbSetStats:
  * GhostmStats keeps its layout. */
 typedef struct GhostmBandStats {
-  double seconds_band;       /* k_band_fill + k_band_walk + k_band_compact, device time */
+  double seconds_band;       /* k_band_fill<false> + k_band_walk<false> + k_ops_compact, device time */
   uint64_t band_launches;    /* batches of hits */
   uint64_t band_hits;
   uint64_t band_cells;       /* sum over the hits of rows run x (2B + 1) */
@@ -906,7 +906,7 @@ size_t GhostmStageQualStats(GhostmQualStats *stats, size_t size);
  * (a frame's record outside the chunk is "source"), plus
  *   "shift"   shift_cost > 0 or shift_cost < -(1 << 20)
  * A refused call leaves rec, ops and *ops_used untouched. One wave runs one
- * hit (kernels k_frame_fill + k_frame_walk + k_frame_compact), lane b = j -
+ * hit (kernels k_band_fill<true> + k_band_walk<true> + k_ops_compact), lane b = j -
  * floor(p / 3) - D + B, over the nucleotide rows of the codon rows BandAlignGpu
  * would run: p from 3 x c_top + 2 down to 3 x c_bot. A hit's direction buffer
  * is rows x ((2B + 1 + 3) & ~3) bytes, bits 5-6 of a byte holding fsel; its
@@ -930,7 +930,7 @@ int GhostmFrameAlignHost(const uint8_t *query_seqs, uint32_t nq, uint32_t L, con
 
 /* The counters of the frame pass, a struct of their own like GhostmBandStats. */
 typedef struct GhostmFrameStats {
-  double seconds_frame;      /* k_frame_fill + k_frame_walk + k_frame_compact, device time */
+  double seconds_frame;      /* k_band_fill<true> + k_band_walk<true> + k_ops_compact, device time */
   uint64_t frame_launches;   /* batches of hits */
   uint64_t frame_hits;
   uint64_t frame_cells;      /* sum over the hits of rows run x (2B + 1) */

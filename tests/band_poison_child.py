@@ -3,7 +3,7 @@
 
 Runs with GHOSTM_LIB_PATH = the LDS poison build (every kernel fills its whole
 LDS allocation with GHOSTM_LDS_POISON_PATTERN before its own code) and checks
-k_band_fill, k_band_walk and k_band_compact against the host model on one stage
+k_band_fill<false>, k_band_walk<false> and k_ops_compact against the host model on one stage
 case (m = 2W + step + 3, B = 31, 60 hits): a path that depended on LDS the
 kernels never wrote would differ under one of the two patterns. Prints one
 JSON line."""

@@ -3,7 +3,7 @@
 
 Runs with GHOSTM_LIB_PATH = the LDS poison build (every kernel fills its whole
 LDS allocation with GHOSTM_LDS_POISON_PATTERN before its own code) and checks
-k_frame_fill, k_frame_walk and k_frame_compact against the host model on the
+k_band_fill<true>, k_band_walk<true> and k_ops_compact against the host model on the
 stage cases and the lane cases of frame_cases.py: a path that depended on LDS
 the kernels never wrote would differ under one of the two patterns. Prints one
 JSON line."""

@@ -21,8 +21,10 @@ from __future__ import annotations
 
 import ctypes
 import itertools
+import os
 import random
 import re
+import subprocess
 
 import numpy as np
 
@@ -191,6 +193,62 @@ def dense_case(L, seed=11, n=60):
         db += list(tx.codes("".join(subj))) + [tx.END]
     return (np.concatenate(qseq), np.array(db, dtype=np.uint8), np.array(qid, dtype=np.uint32),
             np.array(end, dtype=np.uint32))
+
+
+RUNS = ("runs",)  # in place of the fixture's options: the hits of runs_hits
+
+
+def runs_hits(root: str, L: int, base: int):
+    """The compaction's boundary, (d, chunk, tb) like tx.fixture_hits, for the
+    window `base` the caller will run: in one
+    batch, hits of more than 64 run words (a read copied with every other
+    residue replaced by its mildest mismatch: L runs of one column), of none (a
+    read over W and C against a subject over D, E, N, K and R: every pair
+    scores below zero, so the score is 0) and of one (an exact copy). The
+    first hit is one of L words."""
+    from ghostm_amd import traceback_path_host
+
+    M = [int(x) for x in tx.blosum62()]
+    rnd = random.Random(17)
+    reads, subjects = [], []
+
+    def near(a):  # the residue with the mildest score below zero against a
+        return max((s, b) for s, b in ((M[tx.AA.index(b) * 32 + tx.AA.index(a)], b) for b in tx.AA) if s < 0)[1]
+
+    for kind in (0, 1, 0, 2, 1, 0):
+        if kind == 1:
+            read = "".join(rnd.choice("WC") for _ in range(L))
+            subj = "".join(rnd.choice("DENKR") for _ in range(L + 30))
+        else:
+            read = "".join(rnd.choice(tx.AA) for _ in range(L))
+            subj = read if kind == 2 else "".join(near(a) if i % 2 else a for i, a in enumerate(read))
+        reads.append(read)
+        subjects.append(subj)
+    d = os.path.join(root, f"tbpath_runs_L{L}")
+    stamp = os.path.join(d, ".done")
+    if not os.path.exists(stamp):
+        os.makedirs(d, exist_ok=True)
+        with open(os.path.join(d, "db.fa"), "w") as f:
+            f.write("".join(tx._fasta(f"s{i}", s) for i, s in enumerate(subjects)))
+        with open(os.path.join(d, "q.fa"), "w") as f:
+            f.write("".join(tx._fasta(f"r{i}", s) for i, s in enumerate(reads)))
+        subprocess.run([tx.cases.GHOSTM, "db", "-i", f"{d}/db.fa", "-o", f"{d}/db"], check=True, capture_output=True)
+        subprocess.run([tx.cases.GHOSTM, "qry", "-i", f"{d}/q.fa", "-o", f"{d}/q", "-l", str(L)], check=True,
+                       capture_output=True)
+        open(stamp, "w").close()
+    chunk = tx.load_chunk(d)
+    nq, L_, qseq, dbseq, pos = chunk
+    assert (nq, L_) == (len(reads), L)
+    for i, s in enumerate(subjects):
+        assert np.array_equal(qseq[i * L:(i + 1) * L], tx.codes(reads[i]))
+        assert np.array_equal(dbseq[int(pos[i]):int(pos[i]) + len(s)], tx.codes(s))
+    qid = np.arange(nq, dtype=np.uint32)
+    end = np.array([int(pos[i]) + len(s) - 1 for i, s in enumerate(subjects)], dtype=np.uint32)
+    rec, _ = traceback_path_host(qseq, L, dbseq, tx.blosum62(), qid, end, base)
+    n = [int(x) for x in rec["n_runs"]]
+    assert n[0] > 64 and n[0] % 64 and 0 in n and 1 in n, n  # what the case is for
+    tb = np.stack([qid, end, rec["s_start"].astype(np.uint32)], axis=1)
+    return d, chunk, np.ascontiguousarray(tb)
 
 
 # ---------------------------------------------------------------- stage level

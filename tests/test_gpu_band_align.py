@@ -1,5 +1,5 @@
-"""The read-level band pass on the device: k_band_fill, k_band_walk and
-k_band_compact at the stage level (BandAlignGpu against the host model, record
+"""The read-level band pass on the device: k_band_fill<false>, k_band_walk<false>
+and k_ops_compact at the stage level (BandAlignGpu against the host model, record
 for record and word for word, the checker on every hit), in batches, the
 refusals, the kernels under the LDS poison build; the session post-pass
 (Session.hits_band) on tiled protein and DNA sets, on untiled sets, over several

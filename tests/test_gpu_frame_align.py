@@ -1,5 +1,5 @@
-"""The frameshift-aware read-level pass on the device: k_frame_fill,
-k_frame_walk and k_frame_compact at the stage level (FrameAlignGpu against the
+"""The frameshift-aware read-level pass on the device: k_band_fill<true>,
+k_band_walk<true> and k_ops_compact at the stage level (FrameAlignGpu against the
 host model, record for record and word for word, the checker on every hit), the
 lane neighbours at the band's edges, batches, the refusals, the kernels under
 the LDS poison build; the session post-pass (Session.hits_frame) on tiled DNA

@@ -1,7 +1,7 @@
-"""The alignment paths on the device: k_tb_path_fill and k_tb_path_walk at the
-stage level (TraceBackPathGpu against the host model), in batches, the session
-post-pass (Session.hits_path), the -y 7 output, shards, the CLI, and the
-kernels under the LDS poison build."""
+"""The alignment paths on the device: k_tb_path_fill, k_tb_path_walk and
+k_ops_compact at the stage level (TraceBackPathGpu against the host model), in
+batches, the session post-pass (Session.hits_path), the -y 7 output, shards,
+the CLI, and the kernels under the LDS poison build."""
 import ctypes
 import json
 import os
@@ -51,17 +51,24 @@ class _Env:
     (127, (), 16, "blosum62", (-11, -1)),   # the widest group
     (75, ("-r", "64"), 64, "blosum62", (-11, -1)),
     (75, ("-M", cases.PAM250, "-G", "14", "-E", "2"), 16, "pam250", (-14, -2)),
-], ids=["L24", "L40", "L75", "L127", "L75_r64", "L75_pam250_g14e2"])
+    (127, tp.RUNS, 16, "blosum62", (-11, -1)),  # slots of more than 64 words and of none in one batch
+], ids=["L24", "L40", "L75", "L127", "L75_r64", "L75_pam250_g14e2", "L127_runs"])
 def test_stage_equals_host_model(L, opts, region, matrix, gaps, data_root):
-    """With and without the known starts, on 60, 1 and 0 hits; reads 0 to 3 of
-    the fixture cover the window clipped at DB position 0 and the END break."""
-    d, chunk, tb = tx.fixture_hits(data_root, L, opts)
+    """With and without the known starts, on all hits, 1 and 0 hits; reads 0 to
+    3 of the fixture cover the window clipped at DB position 0 and the END
+    break, tp.runs_hits the compaction (k_ops_compact: one wave per slot, 64
+    words at a time)."""
+    d, chunk, tb = (tp.runs_hits(data_root, L, _base(L, region)) if opts is tp.RUNS
+                    else tx.fixture_hits(data_root, L, opts))
     M = tx.blosum62() if matrix == "blosum62" else tx.pam250()
     rec, ops = tp.stage_check(native.load(), d, chunk, tb, M, _base(L, region), gaps[0], gaps[1])
     if not opts:
         tp.assert_gapped(rec, ops)
     nq, L_, qseq, dbseq, pos = chunk
     for h in range(len(tb)):
+        if rec["score"][h] == 0:  # no path to re-walk: only the runs case has such hits
+            assert opts is tp.RUNS and rec["n_runs"][h] == 0
+            continue
         q = int(tb[h, 0])
         tp.check_path(qseq[q * L:(q + 1) * L], dbseq, M, rec[h], tp.hit_words(rec, ops, h), gaps[0], gaps[1],
                       db_start=tb[h, 2])

@@ -1,5 +1,5 @@
-"""Time the read-level band post-pass (-y 12; k_band_fill, k_band_walk,
-k_band_compact) beside the per-tile path post-pass it sits behind (-y 7).
+"""Time the read-level band post-pass (-y 12; k_band_fill<false>,
+k_band_walk<false>, k_ops_compact) beside the per-tile path post-pass it sits behind (-y 7).
 
 Protein reads of 300-600 letters: a random flank, a 140-400 letter stretch of
 a subject of a preset's database (ghostm_amd/workloads.py) copied at an 8 %

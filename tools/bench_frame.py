@@ -1,5 +1,5 @@
-"""Time the frameshift-aware read-level post-pass (-y 13; k_frame_fill,
-k_frame_walk, k_frame_compact) beside the band pass (-y 12) and the per-tile
+"""Time the frameshift-aware read-level post-pass (-y 13; k_band_fill<true>,
+k_band_walk<true>, k_ops_compact) beside the band pass (-y 12) and the per-tile
 path pass on the same hits of the same session.
 
 DNA reads of 900-1800 nt: a random flank, a 140-400 residue stretch of a
