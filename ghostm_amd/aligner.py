@@ -345,6 +345,64 @@ def stage_qual_stats() -> dict:
     return {n: getattr(st, n) for n, _ in st._fields_}
 
 
+# GhostmAdapterOut: one read's record of the adapter stage
+ADAPTER_OUT_DTYPE = np.dtype([("kept", "<u4"), ("adapter_at", "<u4"), ("pair_len", "<u4"),
+                              ("adapter_mismatches", "<u2"), ("pair_mismatches", "<u2")])
+
+
+def _adapter_text(adapter) -> bytes:
+    text = adapter.encode("latin-1") if isinstance(adapter, str) else bytes(adapter)
+    if b"\0" in text:
+        raise GhostmError("adapter trim: adapter: a NUL byte")
+    return text
+
+
+def _adapter_call(fn, letters, offsets, lengths, adapter1, adapter2, min_overlap, err_pct, pair_overlap):
+    ls = np.frombuffer(letters, dtype=np.uint8)  # no copy: the call only reads them
+    offs = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    lens = np.ascontiguousarray(lengths, dtype=np.uint32).reshape(-1)
+    if offs.size != lens.size:
+        raise ValueError("adapter trim: one offset per length")
+    args = [int(v) for v in (min_overlap, err_pct, pair_overlap)]
+    if any(not 0 <= v < 1 << 32 for v in args):
+        raise GhostmError("adapter trim: param: an argument beyond 32 bits")
+    out = np.zeros(lens.size, dtype=ADAPTER_OUT_DTYPE)
+    lp = ls.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if ls.size else None
+    rc = fn(lp, int(ls.size), offs.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), lens.ctypes.data_as(_U32P),
+            int(lens.size), _adapter_text(adapter1), _adapter_text(adapter2), *args,
+            out.ctypes.data_as(ctypes.POINTER(native.GhostmAdapterOut)))
+    if rc != 0:
+        raise GhostmError(native.last_error())
+    return out
+
+
+def adapter_trim_host(letters, offsets, lengths, adapter1="", adapter2="", min_overlap=5, err_pct=10, pair_overlap=0):
+    """The host model of the adapter stage (GhostmAdapterTrimHost; no device):
+    read r is lengths[r] bytes at offsets[r] of letters; adapter1 is looked for
+    at every read's 3' end (adapter2, when given, in the odd records), and with
+    pair_overlap > 0 records 2i and 2i + 1 are mates whose read-through is found
+    from their overlap. Returns one ADAPTER_OUT_DTYPE record per read; the
+    letters are not changed. Raises GhostmError with the reason ("param",
+    "adapter", "null", "record", "length", "pairs")."""
+    return _adapter_call(native.load().GhostmAdapterTrimHost, letters, offsets, lengths, adapter1, adapter2,
+                         min_overlap, err_pct, pair_overlap)
+
+
+def adapter_trim(letters, offsets, lengths, adapter1="", adapter2="", min_overlap=5, err_pct=10, pair_overlap=0):
+    """AdapterTrimGpu: the same through k_adapter_find and k_pair_overlap;
+    arguments, result and refusals as adapter_trim_host."""
+    return _adapter_call(native.load().AdapterTrimGpu, letters, offsets, lengths, adapter1, adapter2, min_overlap,
+                         err_pct, pair_overlap)
+
+
+def stage_adapter_stats() -> dict:
+    """The adapter counters behind the stage-level call (GhostmStageAdapterStats)."""
+    lib = native.load()
+    st = native.GhostmAdapterStats()
+    lib.GhostmStageAdapterStats(ctypes.byref(st), ctypes.sizeof(st))
+    return {n: getattr(st, n) for n, _ in st._fields_}
+
+
 # GhostmHitFrameInfo: one per hit beside Session.hits_frame()'s records
 HIT_FRAME_INFO_DTYPE = np.dtype([("strand", "<u4"), ("read_nt", "<u4"), ("letters", "<u4"), ("shifts", "<u4")])
 # the operations of a frame path's words: PATH_OPS and the two shifts
@@ -1081,6 +1139,38 @@ class Session:
             raise GhostmError("quality: param: an argument beyond 32 bits")
         if native.load().GhostmSessionSetQuality(self._h, *args) != 0:
             raise GhostmError(native.last_error())
+
+    def set_adapters(self, adapter1: str = "", adapter2: str = "", min_overlap: int = 5, err_pct: int = 10,
+                     pair_overlap: int = 0) -> None:
+        """Adapter removal on the FASTQ and quality-carrying DNA sets made from
+        now on (GhostmSessionSetAdapters), ahead of the quality stage: adapter1
+        (adapter2 in the odd records, when given) is looked for at every read's
+        3' end with at least min_overlap letters and at most err_pct % of
+        mismatches, and with pair_overlap > 0 (20 or more is sensible) records
+        2i and 2i + 1 are mates whose read-through is cut at their overlap.
+        set_adapters() turns it off (the default). A refusal ("param",
+        "adapter") leaves the old setting."""
+        args = [int(min_overlap), int(err_pct), int(pair_overlap)]
+        if any(not 0 <= v < 1 << 32 for v in args):  # beyond the C arguments' range
+            raise GhostmError("adapters: param: an argument beyond 32 bits")
+        if native.load().GhostmSessionSetAdapters(self._h, _adapter_text(adapter1), _adapter_text(adapter2), *args) != 0:
+            raise GhostmError(native.last_error())
+
+    def query_adapters(self) -> np.ndarray:
+        """One ADAPTER_OUT_DTYPE record per source read of the current set
+        (GhostmSessionQueryAdapters); empty when the adapter stage did not run."""
+        lib = native.load()
+        n = lib.GhostmSessionQueryAdapters(self._h, None, 0)
+        out = np.zeros(n, dtype=ADAPTER_OUT_DTYPE)
+        if n:
+            lib.GhostmSessionQueryAdapters(self._h, out.ctypes.data_as(ctypes.POINTER(native.GhostmAdapterOut)), n)
+        return out
+
+    def adapter_stats(self) -> dict:
+        """The adapter counters of the current query set (GhostmSessionAdapterStats)."""
+        st = native.GhostmAdapterStats()
+        native.load().GhostmSessionAdapterStats(self._h, ctypes.byref(st), ctypes.sizeof(st))
+        return {n: getattr(st, n) for n, _ in st._fields_}
 
     def set_queries_fastq(self, path: str, width: int = 75, dna: bool = False, chunk_mb: int = 0,
                           tile_step: int = 64, max_len: int = 0) -> int:

@@ -2213,6 +2213,14 @@ void Session::SetQuality(uint32_t trim_q, uint32_t mask_q, uint32_t min_len) {
   qual_.min_len = min_len;
 }
 
+void Session::SetAdapters(const std::string &adapter1, const std::string &adapter2, uint32_t min_overlap,
+                          uint32_t err_pct, uint32_t pair_overlap) {
+  if (shard_world_ > 1) throw Error("a shard session's query set cannot be replaced");
+  const std::string why =
+      MakeAdapterParams(adapter1.c_str(), adapter2.c_str(), min_overlap, err_pct, pair_overlap, &adapter_);  // sets it only on ""
+  if (!why.empty()) throw Error("adapters: " + why);
+}
+
 double Session::MaskChunk(QueryData *q, const std::vector<GhostmBandSource> &src, uint32_t step) {
   q->masked.assign(q->chunk.nseq, 0);
   GhostmMaskStats one{};
@@ -3435,6 +3443,8 @@ void Session::DropQueries() {
   mask_stats_ = GhostmMaskStats{};
   qual_out_.clear();
   qual_stats_ = GhostmQualStats{};
+  adapter_out_.clear();
+  adapter_stats_ = GhostmAdapterStats{};
   QueryStats();
 }
 
@@ -3791,8 +3801,9 @@ void Session::SetFastaTiled(const std::string &path, const std::string *path2, u
 
 // ------------------------------------------------------------------ reads with qualities
 // FASTQ files and the letters form with quality bytes take the tiled path: the
-// quality stage (read_quality.h) runs on all reads before anything of the old
-// set is touched, then each read's kept stretch is what SetTiledRecords sees.
+// adapter stage (read_adapter.h) and then the quality stage (read_quality.h) run
+// on all reads before anything of the old set is touched, then each read's kept
+// stretch is what SetTiledRecords sees.
 void Session::SetQualTiled(FastqSet *a, FastqSet *b, uint32_t width, bool dna, uint32_t chunk_mb, uint32_t max_len,
                            uint32_t step, uint64_t *cut_records, bool *capped, double read_seconds) {
   const WidthRule rule = QuerySetRules(width, dna, chunk_mb, capped);
@@ -3804,21 +3815,47 @@ void Session::SetQualTiled(FastqSet *a, FastqSet *b, uint32_t width, bool dna, u
                 std::to_string(b->len.size()));
   const size_t per = b ? 2 : 1, total = a->len.size() * per;
   if (total > UINT32_MAX) throw Error("set queries: over 4 G records");
+  // the adapter stage first, over the whole set in the records' order: records 2i and 2i + 1 are mates
+  const AdapterParams adapters = adapter_;
+  std::vector<GhostmAdapterOut> cuts;
+  GhostmAdapterStats adapter_sum{};
+  std::vector<uint32_t> cut_len[2];  // the reads' lengths from here on
+  if (adapters.On()) {
+    if (!dna) throw Error("adapters: a protein set");
+    if (adapters.pair_overlap && (total & 1))
+      throw Error("adapters: pairs: " + std::to_string(total) + " records are no whole pairs");
+    std::vector<const uint8_t *> reads(total);
+    std::vector<uint32_t> lens(total);
+    for (size_t r = 0; r < total; ++r) {
+      const FastqSet &f = r % per ? *b : *a;
+      const size_t i = r / per;
+      if (f.off[i] > f.letters.size() || f.len[i] > f.letters.size() - f.off[i])
+        throw Error("adapters: record: read " + std::to_string(r) + " outside the letters given");
+      if (f.len[i] > kAdapterLengthMax) throw Error("adapters: length: read " + std::to_string(r) + " has over 2^24 letters");
+      reads[r] = reinterpret_cast<const uint8_t *>(f.letters.data()) + f.off[i];
+      lens[r] = f.len[i];
+    }
+    cuts.resize(total);
+    if (total) DeviceModule::Get().AdapterTrim(reads.data(), lens.data(), (uint32_t)total, adapters, cuts.data(), &adapter_sum);
+    for (size_t k = 0; k < per; ++k) cut_len[k].resize(a->len.size());
+    for (size_t r = 0; r < total; ++r) cut_len[r % per][r / per] = cuts[r].kept;
+  }
   const QualParams params = qual_;
   std::vector<GhostmQualOut> outs[2];
   GhostmQualStats sum{};
   for (size_t k = 0; k < per; ++k) {
     FastqSet &f = k ? *b : *a;
     const uint32_t n = (uint32_t)f.len.size();
+    const uint32_t *lens = adapters.On() ? cut_len[k].data() : f.len.data();
     outs[k].resize(n);
     uint8_t *letters = reinterpret_cast<uint8_t *>(&f.letters[0]);
     const uint8_t *qual = reinterpret_cast<const uint8_t *>(f.qual.data());
-    const std::string why = ValidateQuality(letters, qual, f.letters.size(), f.off.data(), f.len.data(), n, params.trim_q,
+    const std::string why = ValidateQuality(letters, qual, f.letters.size(), f.off.data(), lens, n, params.trim_q,
                                             params.mask_q, params.min_len, outs[k].data());
     if (!why.empty()) throw Error("quality: " + why);
     if (!params.On() || n == 0) continue;
     GhostmQualStats one{};
-    DeviceModule::Get().QualityTrim(letters, qual, f.off.data(), f.len.data(), n, params, outs[k].data(), &one);
+    DeviceModule::Get().QualityTrim(letters, qual, f.off.data(), lens, n, params, outs[k].data(), &one);
     for (uint32_t r = 0; r < n; ++r)
       if (outs[k][r].bad) throw Error("fastq: record " + std::to_string(r + 1) + ": quality byte outside '!'..'~'");
     sum.launches += one.launches;
@@ -3838,7 +3875,7 @@ void Session::SetQualTiled(FastqSet *a, FastqSet *b, uint32_t width, bool dna, u
   for (size_t r = 0; r < total; ++r) {
     const FastqSet &f = r % per ? *b : *a;
     const size_t i = r / per;
-    uint32_t begin = 0, len = f.len[i];
+    uint32_t begin = 0, len = adapters.On() ? cuts[r].kept : f.len[i];
     if (params.On()) {
       all[r] = outs[r % per][i];
       begin = all[r].begin;
@@ -3851,6 +3888,8 @@ void Session::SetQualTiled(FastqSet *a, FastqSet *b, uint32_t width, bool dna, u
   SetTiledRecords(views.data(), (uint32_t)views.size(), TiledRule{rule.width, rule.max_concat, step, dna});
   qual_out_.swap(all);
   qual_stats_ = sum;
+  adapter_out_.swap(cuts);
+  adapter_stats_ = adapter_sum;
   read_seconds_ = read_seconds;
   QueryStats();
   if (cut_records) *cut_records = cut;

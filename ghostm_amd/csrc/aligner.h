@@ -25,6 +25,7 @@
 #include "fastq_reader.h"
 #include "formats.h"
 #include "query_mask.h"
+#include "read_adapter.h"
 #include "read_quality.h"
 #include "scoring.h"
 
@@ -474,6 +475,19 @@ class Session {
   // the quality counters of the current set (all 0 when the stage did not run)
   const GhostmQualStats &QualityStats() const { return qual_stats_; }
   const QualParams &Quality() const { return qual_; }
+  // Adapter removal on FASTQ and quality-carrying sets (read_adapter.h; the
+  // contract is above GhostmAdapterTrimHost and GhostmSessionSetAdapters in
+  // include/ghostm_hip.h). Both adapters empty and pair_overlap 0: off, the
+  // default; throws "param" or "adapter" and keeps the old setting. It takes
+  // effect at the next SetQueriesFastq*Tiled / SetQueriesQualTiled, where the
+  // stage runs ahead of the quality stage; refused on a shard session.
+  void SetAdapters(const std::string &adapter1, const std::string &adapter2, uint32_t min_overlap, uint32_t err_pct,
+                   uint32_t pair_overlap);
+  // one record per source read of the current set; empty when the stage did not run for it
+  const std::vector<GhostmAdapterOut> &QueryAdapters() const { return adapter_out_; }
+  // the adapter counters of the current set (all 0 when the stage did not run)
+  const GhostmAdapterStats &AdapterStats() const { return adapter_stats_; }
+  const AdapterParams &Adapters() const { return adapter_; }
   // Hit records of the last run in device memory (this session's GPU): copies
   // min(n, cap) records to dst_device; returns n.
   size_t DeviceHits(void *dst_device, size_t cap);
@@ -770,6 +784,9 @@ class Session {
   QualParams qual_;                     // SetQuality: the next quality-carrying set's stage (all 0: off)
   std::vector<GhostmQualOut> qual_out_;  // the current set's, per source read
   GhostmQualStats qual_stats_{};
+  AdapterParams adapter_;                       // SetAdapters: the next quality-carrying set's stage (off by default)
+  std::vector<GhostmAdapterOut> adapter_out_;  // the current set's, per source read
+  GhostmAdapterStats adapter_stats_{};
   // the quality setters' common body: one read set, or two of mates interleaved; their letters are masked in place
   void SetQualTiled(FastqSet *a, FastqSet *b, uint32_t width, bool dna, uint32_t chunk_mb, uint32_t max_len,
                     uint32_t step, uint64_t *cut_records, bool *capped, double read_seconds);

@@ -516,6 +516,32 @@ size_t GhostmSessionQualityStats(void *s, GhostmQualStats *stats, size_t size) {
   return CopyStats(s, stats, size, std::mem_fn(&Session::QualityStats));
 }
 
+int GhostmSessionSetAdapters(void *s, const char *adapter1, const char *adapter2, uint32_t min_overlap, uint32_t err_pct,
+                             uint32_t pair_overlap) {
+  try {
+    if (!s) throw Error("null session");
+    static_cast<Session *>(s)->SetAdapters(adapter1 ? adapter1 : "", adapter2 ? adapter2 : "", min_overlap, err_pct,
+                                           pair_overlap);
+    return 0;
+  } catch (std::exception &e) {
+    SetLastErrorMessage(e.what());
+    return 1;
+  }
+}
+
+size_t GhostmSessionQueryAdapters(void *s, GhostmAdapterOut *out, size_t cap) {
+  if (!s) return 0;
+  const std::vector<GhostmAdapterOut> &v = static_cast<Session *>(s)->QueryAdapters();
+  if (!out) return v.size();
+  const size_t n = std::min(cap, v.size());
+  if (n) std::memcpy(out, v.data(), n * sizeof(GhostmAdapterOut));
+  return n;
+}
+
+size_t GhostmSessionAdapterStats(void *s, GhostmAdapterStats *stats, size_t size) {
+  return CopyStats(s, stats, size, std::mem_fn(&Session::AdapterStats));
+}
+
 size_t GhostmSessionBandStats(void *s, GhostmBandStats *stats, size_t size) {
   return CopyStats(s, stats, size, std::mem_fn(&Session::BandStats));
 }
@@ -950,6 +976,9 @@ int GhostmSearchMain(int argc, char **argv) {
   long profile_min = -1;                   // -R; below 0: the session's default
   MaskParams mask;                         // -Z w,k1,k2; window 0: no masking
   QualParams quality;                      // -Q trim,mask,minlen; all 0: no quality stage
+  std::string adapter1, adapter2;          // -A SEQ1[,SEQ2]; both empty: no adapter rule
+  bool have_O = false;                     // -O min_overlap,err_pct[,pair_overlap]
+  uint32_t ad_overlap = 5, ad_err = 10, ad_pair = 0;
   bool mates_one = false, mates_two = false;  // -j: every file is interleaved mates; -J: r1.fasta r2.fasta out triples
   long max_insert = -1;                    // -I; below 0: the session's default
   int style = 0;                           // -y, as aln reads it
@@ -957,9 +986,37 @@ int GhostmSearchMain(int argc, char **argv) {
   opterr = 1;
   int c;
   // aln's options (aligner.cpp ParseAlignerOptions) plus -q, -w, -c, -f, -k, -m and -T, -X, -B, -F, -g, -K, -C, -n, -a,
-  // -p, -P, -R, -Z, -j, -J, -I, -Q
-  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:n:a:p:P:R:Z:jJI:Q:")) >= 0) {
+  // -p, -P, -R, -Z, -j, -J, -I, -Q, -A, -O
+  while ((c = getopt(argc, argv, "b:d:D:e:E:G:i:l:M:o:r:s:t:S:L:y:vq:w:c:f:k:m:T:X:B:F:gK:C:n:a:p:P:R:Z:jJI:Q:A:O:")) >= 0) {
     switch (c) {
+      case 'A': {  // FASTQ reads: the 3' adapter, and mate 2's after a comma
+        const char *comma = strchr(optarg, ',');
+        adapter1 = comma ? std::string(optarg, (size_t)(comma - optarg)) : std::string(optarg);
+        adapter2 = comma ? std::string(comma + 1) : std::string();
+        if (adapter1.empty() || (comma && adapter2.empty())) return 1;
+        AdapterParams checked;
+        if (!MakeAdapterParams(adapter1.c_str(), adapter2.c_str(), 5, 10, 0, &checked).empty()) return 1;
+        break;
+      }
+      case 'O': {  // the adapter stage's min_overlap,err_pct[,pair_overlap]
+        unsigned long v[3] = {0, 0, 0};
+        const char *at = optarg;
+        for (int k = 0; k < 3; ++k) {
+          char *end = nullptr;
+          if (*at < '0' || *at > '9') return 1;
+          v[k] = strtoul(at, &end, 10);
+          if (end == at || v[k] > 1024) return 1;
+          if (*end == '\0' && k >= 1) break;  // the pair value may be left out
+          if (*end != ',' || k == 2) return 1;
+          at = end + 1;
+        }
+        if (!ValidateAdapterParams((uint32_t)v[0], (uint32_t)v[1], (uint32_t)v[2]).empty()) return 1;
+        have_O = true;
+        ad_overlap = (uint32_t)v[0];
+        ad_err = (uint32_t)v[1];
+        ad_pair = (uint32_t)v[2];
+        break;
+      }
       case 'j': mates_one = true; break;  // with -T: records 2i and 2i + 1 of every file are mates
       case 'J': mates_two = true; break;  // with -T: the mates come in two files
       case 'I': {  // the mates' insert limit in read units, 1..2^24
@@ -1083,6 +1140,9 @@ int GhostmSearchMain(int argc, char **argv) {
   if ((mates || max_insert >= 0) && !tiled) return 1;       // mates are source records of a tiled set
   if (max_insert >= 0 && !mates) return 1;                  // -I limits mates only
   if ((style == 26 || style == 27) && !mates) return 1;     // the pair lines need them
+  if ((!adapter2.empty() || ad_pair) && !mates) return 1;   // mate 2's adapter and the pair rule need mates
+  if (have_O && adapter1.empty() && !ad_pair) return 1;     // -O alone sets nothing
+  const bool adapters_on = !adapter1.empty() || ad_pair;
   if (have_d == !db_fasta.empty()) return 1;  // -d or -f, not both
   if (have_x && !tiled) return 1;             // -X cuts a tiled set only
   if (tile_groups && !tiled) return 1;        // -g groups a tiled set only
@@ -1104,6 +1164,7 @@ int GhostmSearchMain(int argc, char **argv) {
     if (profile_min >= 0) session.SetProfile((uint32_t)profile_min);
     if (mask.window) session.SetMask(mask.window, mask.trigger, mask.extend);
     if (quality.On()) session.SetQuality(quality.trim_q, quality.mask_q, quality.min_len);
+    if (adapters_on) session.SetAdapters(adapter1, adapter2, ad_overlap, ad_err, ad_pair);
     if (mates) session.SetMates(true, max_insert >= 0 ? (uint32_t)max_insert : 1000u);
     for (size_t k = 0; k < pos.size(); k += per) {
       try {
@@ -1115,6 +1176,7 @@ int GhostmSearchMain(int argc, char **argv) {
         const bool fastq = LooksLikeFastq(pos[k]);
         if (fastq && !tiled) throw Error("fastq: needs -T");
         if (quality.On() && !fastq) throw Error("quality: " + pos[k] + " has no qualities");
+        if (adapters_on && !fastq) throw Error("adapters: " + pos[k] + " is not FASTQ");
         if (fastq && mates_two)
           session.SetQueriesFastqMatesTiled(pos[k], pos[k + 1], width, dna, chunk_mb, max_len, tile_step, nullptr, &capped);
         else if (fastq) session.SetQueriesFastqTiled(pos[k], width, dna, chunk_mb, max_len, tile_step, nullptr, &capped);
@@ -1143,6 +1205,13 @@ int GhostmSearchMain(int argc, char **argv) {
             std::cout << "# " << pos[k] << " quality trimmed 5' " << qs.trimmed5 << " 3' " << qs.trimmed3 << " masked "
                       << qs.masked << " failed reads " << qs.failed << " of " << qs.reads << " seconds "
                       << qs.seconds_quality << std::endl;
+          }
+          if (adapters_on) {
+            const GhostmAdapterStats &as = session.AdapterStats();
+            std::cout << "# " << pos[k] << " adapters cut reads " << as.cut_reads << " letters " << as.cut_letters
+                      << " adapter found " << as.adapter_found << " pairs found " << as.pair_found << " skipped "
+                      << as.pair_skipped << " emptied " << as.emptied << " of " << as.reads << " seconds "
+                      << as.seconds_adapter << std::endl;
           }
         }
       } catch (std::exception &e) {

@@ -43,6 +43,7 @@ struct DevQuery;
 struct DevDb;
 struct MaskParams;  // query_mask.h
 struct QualParams;  // read_quality.h
+struct AdapterParams;  // read_adapter.h
 
 // One hit chosen by the device merge (K4), after its traceback (K3):
 // subject-relative coordinates, ml = (aln_len << 8) | matches.
@@ -117,6 +118,7 @@ struct DeviceTimes {
   GhostmTaxonProfileStats profile{};     // k_taxon_*
   GhostmMaskStats mask{};                // k_mask_windows + k_mask_apply
   GhostmQualStats qual{};                // k_qual_trim
+  GhostmAdapterStats adapter{};          // k_adapter_find + k_pair_overlap
 };
 
 class DeviceModule {
@@ -176,6 +178,17 @@ class DeviceModule {
   // (may be null): this call's counters, seconds_quality the kernel's device time.
   void QualityTrim(uint8_t *letters, const uint8_t *qual, const uint64_t *off, const uint32_t *len, uint32_t n,
                    const QualParams &params, GhostmQualOut *out, GhostmQualStats *call);
+  // The adapter stage of n reads (read_adapter.h; kernels: read_adapter.hip) on
+  // the main stream: read r is len[r] bytes at reads[r], which need not share a
+  // buffer (the mates of two files are interleaved this way). The reads go up
+  // in pieces as QualityTrim's do, of whole pairs with the pair rule on (n is
+  // then even), each piece is searched by k_adapter_find (when an adapter is
+  // set) and k_pair_overlap (when the pair rule is on), and its records come
+  // back before the next piece goes up. The letters are only read. The caller
+  // has made ValidateAdapters' checks and params.On() holds. *call (may be
+  // null): this call's counters, seconds_adapter the kernels' device time.
+  void AdapterTrim(const uint8_t *const *reads, const uint32_t *len, uint32_t n, const AdapterParams &params,
+                   GhostmAdapterOut *out, GhostmAdapterStats *call);
   // A resident chunk's coded records (nseq * L bytes) back on the host.
   size_t QueryBytes(const DevQuery *q) const;
   void DownloadQuery(const DevQuery *q, uint8_t *dst);

@@ -32,6 +32,7 @@
 #include "pileup_plan.h"
 #include "qformat.h"
 #include "query_mask.h"
+#include "read_adapter.h"
 #include "read_quality.h"
 #include "query_tiles.h"
 #include "score_tasks.h"
@@ -352,7 +353,8 @@ struct DeviceModule::Impl {
   DevBuf mask_src, mask_off, mask_bits, mask_out;
   hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;
   // QualityTrim: a piece's letters, qualities, offsets and lengths, its records
-  // followed by the counter slots; the kernel's events
+  // followed by the counter slots; the kernel's events. AdapterTrim, which runs
+  // before it and has synchronised by then, uses the same (all but rq_qual).
   DevBuf rq_letters, rq_qual, rq_off, rq_len, rq_out;
   hipEvent_t ev_r0 = nullptr, ev_r1 = nullptr;
   // FormatDb: the chunk's packed letters, the index build's (key, position)
@@ -865,6 +867,92 @@ void DeviceModule::QualityTrim(uint8_t *letters, const uint8_t *qual, const uint
   t.failed += one.failed;
   t.bad += one.bad;
   t.seconds_quality += one.seconds_quality;
+  if (call) *call = one;
+}
+
+static_assert(sizeof(GhostmAdapterOut) == 16, "the records come back as they are");
+
+void DeviceModule::AdapterTrim(const uint8_t *const *reads, const uint32_t *len, uint32_t n,
+                               const AdapterParams &params, GhostmAdapterOut *out, GhostmAdapterStats *call) {
+  if (!impl_) throw Error("adapters: the device module is not bound to a device");
+  Use();
+  if (call) *call = GhostmAdapterStats{};
+  if (n == 0 || !params.On()) return;
+  Impl &I = *impl_;
+  hipStream_t st = S(stream_);
+  // a piece: whole reads (whole pairs with the pair rule on, so a piece starts at an even record) while their
+  // letters stay within kPiece (one read alone is at most 2^24) and at most kPieceReads
+  constexpr uint64_t kPiece = 64ull << 20;
+  constexpr uint32_t kPieceReads = 1u << 22;
+  const uint32_t unit = params.pair_overlap ? 2 : 1;  // n is a multiple of it
+  const size_t slot_words = (size_t)kAdapterCounterSlots * kAdapterCounterWords, slot_bytes = slot_words * 8;
+  std::vector<uint8_t> pack_l;
+  std::vector<uint64_t> pack_off;
+  std::vector<uint64_t> slots(slot_words);
+  GhostmAdapterStats one{};
+  for (uint32_t r0 = 0; r0 < n;) {
+    uint32_t r1 = r0;
+    uint64_t bytes = 0;
+    while (r1 < n && r1 - r0 < kPieceReads) {
+      uint64_t add = 0;
+      for (uint32_t k = 0; k < unit; ++k) add += len[r1 + k];
+      if (r1 != r0 && bytes + add > kPiece) break;
+      bytes += add;
+      r1 += unit;
+    }
+    const uint32_t m = r1 - r0;
+    pack_l.resize(bytes);
+    pack_off.resize(m);
+    uint64_t at = 0;
+    for (uint32_t r = r0; r < r1; ++r) {
+      pack_off[r - r0] = at;
+      if (len[r]) std::memcpy(pack_l.data() + at, reads[r], len[r]);
+      at += len[r];
+    }
+    const size_t out_bytes = (size_t)m * sizeof(GhostmAdapterOut);  // a multiple of 16: the slots behind it are aligned
+    I.rq_letters.Reserve(bytes);
+    I.rq_off.Reserve((size_t)m * 8);
+    I.rq_len.Reserve((size_t)m * 4);
+    I.rq_out.Reserve(out_bytes + slot_bytes);
+    StagedUpload(I.rq_letters.p, pack_l.data(), bytes);
+    StagedUpload(I.rq_off.p, pack_off.data(), (size_t)m * 8);
+    StagedUpload(I.rq_len.p, len + r0, (size_t)m * 4);
+    HIP_CHECK(hipMemsetAsync(I.rq_out.p, 0, out_bytes + slot_bytes, st));
+    uint64_t *counters = reinterpret_cast<uint64_t *>(I.rq_out.as<uint8_t>() + out_bytes);
+    HIP_CHECK(hipEventRecord(I.ev_r0, st));
+    one.launches += LaunchAdapterTrim(stream_, I.rq_letters.as<uint8_t>(), I.rq_off.as<uint64_t>(), I.rq_len.as<uint32_t>(),
+                                      m, params, I.rq_out.as<GhostmAdapterOut>(), counters);
+    HIP_CHECK(hipEventRecord(I.ev_r1, st));
+    HIP_CHECK(hipMemcpyAsync(out + r0, I.rq_out.p, out_bytes, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(slots.data(), counters, slot_bytes, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (uint32_t k = 0; k < kAdapterCounterSlots; ++k) {
+      const uint64_t *w = &slots[(size_t)k * kAdapterCounterWords];
+      one.cut_reads += w[0];
+      one.cut_letters += w[1];
+      one.adapter_found += w[2];
+      one.pair_found += w[3];
+      one.pair_skipped += w[4];
+      one.emptied += w[5];
+    }
+    float ms = 0;
+    HIP_CHECK(hipEventElapsedTime(&ms, I.ev_r0, I.ev_r1));
+    one.seconds_adapter += ms * 1e-3;
+    one.reads += m;
+    one.letters += bytes;
+    r0 = r1;
+  }
+  GhostmAdapterStats &t = times_.adapter;
+  t.launches += one.launches;
+  t.reads += one.reads;
+  t.letters += one.letters;
+  t.cut_reads += one.cut_reads;
+  t.cut_letters += one.cut_letters;
+  t.adapter_found += one.adapter_found;
+  t.pair_found += one.pair_found;
+  t.pair_skipped += one.pair_skipped;
+  t.emptied += one.emptied;
+  t.seconds_adapter += one.seconds_adapter;
   if (call) *call = one;
 }
 
@@ -4433,6 +4521,33 @@ int QualityTrimGpu(uint8_t *letters, const uint8_t *qual, uint64_t total, const 
 
 size_t GhostmStageQualStats(GhostmQualStats *stats, size_t size) {
   return StageStats(&DeviceTimes::qual, stats, size);
+}
+
+int AdapterTrimGpu(const uint8_t *letters, uint64_t total, const uint64_t offsets[], const uint32_t lengths[],
+                   uint32_t n, const char *adapter1, const char *adapter2, uint32_t min_overlap, uint32_t err_pct,
+                   uint32_t pair_overlap, GhostmAdapterOut out[]) {
+  // everything is checked before the device is as much as bound
+  AdapterParams params;
+  std::string why = MakeAdapterParams(adapter1, adapter2, min_overlap, err_pct, pair_overlap, &params);
+  if (why.empty()) why = ValidateAdapters(letters, total, offsets, lengths, n, params.On() ? pair_overlap : 0, out);
+  if (!why.empty()) {
+    SetError("AdapterTrimGpu: " + why);
+    return 1;
+  }
+  if (!params.On()) {  // off: nothing is launched
+    for (uint32_t r = 0; r < n; ++r) out[r] = AdapterResult(lengths[r], lengths[r], 0, 0, 0);
+    return 0;
+  }
+  if (n == 0) return 0;
+  std::vector<const uint8_t *> reads(n);
+  for (uint32_t r = 0; r < n; ++r) reads[r] = letters + offsets[r];
+  return UnboundStageCall("AdapterTrimGpu", [&](DeviceModule &m) {
+    m.AdapterTrim(reads.data(), lengths, n, params, out, nullptr);
+  });
+}
+
+size_t GhostmStageAdapterStats(GhostmAdapterStats *stats, size_t size) {
+  return StageStats(&DeviceTimes::adapter, stats, size);
 }
 
 }  // extern "C"

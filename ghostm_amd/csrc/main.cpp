@@ -64,6 +64,11 @@ static int Usage() {
             << "       [-Q trimQ,maskQ,minLen]: FASTQ reads (a file that begins with '@'; needs -T) trimmed at both ends by\n"
             << "        BWA's running sum at quality trimQ, kept letters below maskQ stored as N, reads left shorter than\n"
             << "        minLen emptied; 0..93, 0..93, 0..2^24 (e.g. -Q 20,0,30); read coordinates are of the kept stretch\n"
+            << "       [-A SEQ1[,SEQ2]] [-O minOverlap,errPct[,pairOverlap]]: FASTQ reads cut at their 3' adapter before -Q:\n"
+            << "        SEQ1 (SEQ2 for mate 2 of -j/-J; 1..64 letters of ACGTN) is looked for ungapped from each start,\n"
+            << "        accepted with at least minOverlap letters (1..64, default 5) and at most errPct % mismatches\n"
+            << "        (0..50, default 10); pairOverlap (with -j/-J; 0: off, 1..1024, 20 or more is sensible) also cuts\n"
+            << "        both mates of a read-through pair at the end of their overlap, with or without -A\n"
             << "       [-j | -J] [-I maxInsert]: with -T, mate pairs. -j: records 2i and 2i + 1 of every input file are\n"
             << "        mates; -J: the positionals are triples r1.fasta r2.fasta out, interleaved record by record. A hit\n"
             << "        of each mate on one subject, at most maxInsert (default 1000; nt for DNA) apart and, for DNA, on\n"

@@ -130,6 +130,35 @@ class GhostmQualStats(ctypes.Structure):
     ]
 
 
+class GhostmAdapterOut(ctypes.Structure):
+    """one read's record of the adapter stage (GhostmAdapterTrimHost, GhostmSessionQueryAdapters)."""
+
+    _fields_ = [
+        ("kept", ctypes.c_uint32),
+        ("adapter_at", ctypes.c_uint32),
+        ("pair_len", ctypes.c_uint32),
+        ("adapter_mismatches", ctypes.c_uint16),
+        ("pair_mismatches", ctypes.c_uint16),
+    ]
+
+
+class GhostmAdapterStats(ctypes.Structure):
+    """the counters of the adapter stage (GhostmSessionAdapterStats, GhostmStageAdapterStats)."""
+
+    _fields_ = [
+        ("launches", ctypes.c_uint64),
+        ("reads", ctypes.c_uint64),
+        ("letters", ctypes.c_uint64),
+        ("cut_reads", ctypes.c_uint64),
+        ("cut_letters", ctypes.c_uint64),
+        ("adapter_found", ctypes.c_uint64),
+        ("pair_found", ctypes.c_uint64),
+        ("pair_skipped", ctypes.c_uint64),
+        ("emptied", ctypes.c_uint64),
+        ("seconds_adapter", ctypes.c_double),
+    ]
+
+
 class GhostmBandStats(ctypes.Structure):
     """the counters of the band pass (GhostmSessionBandStats, GhostmStageBandStats)."""
 
@@ -562,6 +591,11 @@ SIGNATURES = {
     "QualityTrimGpu": (c_int, [POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p,
                                c_uint32, c_uint32, c_uint32, c_uint32, POINTER(GhostmQualOut)]),
     "GhostmStageQualStats": (c_size_t, [POINTER(GhostmQualStats), c_size_t]),
+    "GhostmAdapterTrimHost": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_char_p,
+                                      c_char_p, c_uint32, c_uint32, c_uint32, POINTER(GhostmAdapterOut)]),
+    "AdapterTrimGpu": (c_int, [POINTER(ctypes.c_uint8), c_uint64, POINTER(c_uint64), u32p, c_uint32, c_char_p,
+                               c_char_p, c_uint32, c_uint32, c_uint32, POINTER(GhostmAdapterOut)]),
+    "GhostmStageAdapterStats": (c_size_t, [POINTER(GhostmAdapterStats), c_size_t]),
     "FrameAlignGpu": (c_int, [c_uint32, POINTER(GhostmBandSource), POINTER(ctypes.c_int32), u32p, u32p, c_uint32,
                               c_uint32, c_uint32, c_int, c_int, c_int, POINTER(GhostmHitPath), u32p, c_size_t,
                               POINTER(c_size_t)]),
@@ -668,6 +702,9 @@ SIGNATURES = {
                                                  c_int, c_uint32, c_uint32, c_uint32]),
     "GhostmSessionQueryQuality": (c_size_t, [c_void_p, POINTER(GhostmQualOut), c_size_t]),
     "GhostmSessionQualityStats": (c_size_t, [c_void_p, POINTER(GhostmQualStats), c_size_t]),
+    "GhostmSessionSetAdapters": (c_int, [c_void_p, c_char_p, c_char_p, c_uint32, c_uint32, c_uint32]),
+    "GhostmSessionQueryAdapters": (c_size_t, [c_void_p, POINTER(GhostmAdapterOut), c_size_t]),
+    "GhostmSessionAdapterStats": (c_size_t, [c_void_p, POINTER(GhostmAdapterStats), c_size_t]),
     "GhostmSessionHitsFrame": (c_size_t, [c_void_p, POINTER(GhostmHitPath), c_size_t]),
     "GhostmSessionFrameOps": (c_size_t, [c_void_p, u32p, c_size_t]),
     "GhostmSessionFrameInfo": (c_size_t, [c_void_p, POINTER(GhostmHitFrameInfo), c_size_t]),

@@ -843,6 +843,101 @@ typedef struct GhostmQualStats {
  * conventions. */
 size_t GhostmStageQualStats(GhostmQualStats *stats, size_t size);
 
+/* Adapter removal for FASTQ reads. A fragment shorter than the read is read
+ * through into the sequencing adapter; the tail is translated in all six
+ * frames, seeds, votes and piles up, the same wrong residues in every
+ * contaminated read. The stage runs on the GPU on the reads' letters, before
+ * the quality stage, and only ever shortens a read at its 3' end, so
+ * GhostmQualOut.begin and every read coordinate keep their meaning.
+ *
+ * Integer arithmetic, so that host and device agree byte for byte.
+ *
+ * Letters: a read byte is upper-cased (ASCII letters only) and compared; a byte
+ * that is then none of A, C, G, T mismatches everything but an adapter's N. An
+ * adapter is 1..64 letters of ACGTN in either case; its N matches any read byte.
+ *
+ * Parameters: min_overlap 1..64, err_pct 0..50, pair_overlap 0 (the pair rule
+ * is off) or 1..1024. Both adapters empty (or NULL) and pair_overlap 0: off.
+ *
+ * Adapter rule, a read of n letters and an adapter of m: for a start p in
+ * 0..n-1, L = min(m, n - p) and mm(p) = the i < L where read[p + i] does not
+ * match adapter[i]; p is accepted when L >= min_overlap and mm(p) * 100 <=
+ * err_pct * L; adapter_at = the smallest accepted p, or n. No insertions or
+ * deletions are considered: this is fastp's and Trimmomatic's rule, not
+ * cutadapt's semiglobal alignment. adapter1 is used for every record, but a
+ * non-empty adapter2 for the odd records (mate 2 of interleaved mates).
+ *
+ * Pair rule (pair_overlap > 0), records 2i and 2i + 1 being mates of n1 and n2
+ * letters: for a fragment length f in pair_overlap..min(n1, n2), pm(f) = the
+ * i < f where R1[i] is not the complement of R2[f - 1 - i], a byte that is none
+ * of A, C, G, T on either mate counting as a mismatch; f is accepted when
+ * pm(f) * 100 <= err_pct * f; pair_len = the greatest accepted f, or 0. The
+ * greatest is the conservative one: poly-A against poly-T accepts every f and
+ * loses nothing. A pair with a mate of over 1024 letters is not examined (the
+ * check is quadratic, and read-through needs a fragment shorter than the read)
+ * and counted in pair_skipped; neither is one with min(n1, n2) < pair_overlap.
+ * Overlaps with f > min(n1, n2) are not looked for and mates are not merged.
+ *
+ * Per read: kept = min(adapter_at, pair_len ? pair_len : n). The read goes on
+ * as its first kept letters; kept == 0 leaves an empty record, so record
+ * indices and the pairing hold. The letters are never written.
+ *
+ * GhostmAdapterTrimHost: the rule on the host, letter by letter, with no device
+ * call (the model the kernels are checked against). Read r is lengths[r] bytes
+ * at offsets[r] of letters (`total` bytes); out[n] receives one record per read.
+ * With the stage off out[r] = {lengths[r], lengths[r], 0, 0, 0}. Everything is
+ * checked first; a refused call leaves out untouched and names its reason in
+ * GhostmGetLastError:
+ *   "param"    a parameter out of range
+ *   "adapter"  an adapter letter outside ACGTN, or an adapter of over 64 letters
+ *   "null"     a null array with n > 0
+ *   "record"   an offset or a length outside `total`
+ *   "length"   a read of over 2^24 letters
+ *   "pairs"    pair_overlap > 0 with an odd n */
+typedef struct GhostmAdapterOut {
+  uint32_t kept;        /* the letters the read goes on with */
+  uint32_t adapter_at;  /* the adapter rule's cut; the read's length: none */
+  uint32_t pair_len;    /* the pair rule's fragment length, the same in both mates; 0: none */
+  uint16_t adapter_mismatches;  /* mm(adapter_at); 0 when none */
+  uint16_t pair_mismatches;     /* pm(pair_len); 0 when none */
+} GhostmAdapterOut;
+int GhostmAdapterTrimHost(const uint8_t *letters, uint64_t total, const uint64_t offsets[], const uint32_t lengths[],
+                          uint32_t n, const char *adapter1, const char *adapter2, uint32_t min_overlap,
+                          uint32_t err_pct, uint32_t pair_overlap, GhostmAdapterOut out[]);
+
+/* The same on the GPU, stage level. k_adapter_find: one wave per read, the
+ * lanes own 64 consecutive starts at a time from the 5' end, each counts its
+ * mismatches over a window of the read staged in LDS, and the wave leaves at
+ * the first group with an accepted lane (the ballot's lowest bit).
+ * k_pair_overlap: one wave per pair, both mates staged in LDS once, mate 2
+ * reverse-complemented, the lanes own 64 fragment lengths at a time from
+ * min(n1, n2) downwards. The reads go up in bounded pieces of whole reads (of
+ * whole pairs with the pair rule on). The same checks and reasons, all made
+ * before any upload or launch; with n == 0 or the stage off nothing is
+ * launched. */
+int AdapterTrimGpu(const uint8_t *letters, uint64_t total, const uint64_t offsets[], const uint32_t lengths[],
+                   uint32_t n, const char *adapter1, const char *adapter2, uint32_t min_overlap, uint32_t err_pct,
+                   uint32_t pair_overlap, GhostmAdapterOut out[]);
+
+/* The counters of the adapter stage. */
+typedef struct GhostmAdapterStats {
+  uint64_t launches;       /* kernel launches: per piece one k_adapter_find when an adapter is set and one
+                              k_pair_overlap when the pair rule is on */
+  uint64_t reads;
+  uint64_t letters;
+  uint64_t cut_reads;      /* reads with kept below their length */
+  uint64_t cut_letters;    /* the letters they lost */
+  uint64_t adapter_found;  /* reads with adapter_at below their length */
+  uint64_t pair_found;     /* pairs with pair_len > 0 */
+  uint64_t pair_skipped;   /* pairs not examined for a mate of over 1024 letters */
+  uint64_t emptied;        /* reads with letters that keep none */
+  double seconds_adapter;  /* both kernels, device time */
+} GhostmAdapterStats;
+
+/* The adapter counters behind the stage-level call; GhostmStageBandStats'
+ * conventions. */
+size_t GhostmStageAdapterStats(GhostmAdapterStats *stats, size_t size);
+
 /* Frameshift-aware read-level alignments of DNA reads. BandAlignGpu aligns one
  * frame; after a single-nucleotide insertion or deletion the true alignment of
  * a read continues in another frame of the same strand, and this pass follows
@@ -1881,6 +1976,34 @@ size_t GhostmSessionQueryQuality(void *session, GhostmQualOut *out, size_t cap);
 /* The quality counters of the session's current query set (all 0 when the stage
  * did not run); the size convention of GhostmSessionDbStats. */
 size_t GhostmSessionQualityStats(void *session, GhostmQualStats *stats, size_t size);
+
+/* Adapter removal on the session's FASTQ and quality-carrying query sets (the
+ * rule above GhostmAdapterTrimHost). Both adapters empty or NULL and
+ * pair_overlap 0 is off, the default; a refusal names "param" or "adapter" and
+ * leaves the old setting. The setting takes effect at the next
+ * GhostmSessionSetQueriesFastq*Tiled / GhostmSessionSetQueriesQualTiled call;
+ * the current set and its results stay as they are. Refused on a shard
+ * session, as the setters are.
+ * In those setters the stage runs first, over the whole set in the records'
+ * order (the mates of two files interleaved, so records 2i and 2i + 1 are
+ * mates; GhostmSessionSetMates is independent of it). Each read then enters the
+ * quality stage and the tiler as its first `kept` letters: the quality rule
+ * sees the cut read, its `bad` counts the cut read's bytes, and with quality
+ * off the set is that of the reads cut by hand. A protein set is refused
+ * ("adapters: a protein set"), and so is an odd record count with
+ * pair_overlap > 0 ("adapters: pairs: ..."); any refusal leaves the session as
+ * it was. While the stage is off nothing is launched and nothing changes. */
+int GhostmSessionSetAdapters(void *session, const char *adapter1, const char *adapter2, uint32_t min_overlap,
+                             uint32_t err_pct, uint32_t pair_overlap);
+
+/* One record per source read of the current set, in the reads' order; the
+ * NULL/cap convention of GhostmSessionHits. 0 entries when the adapter stage
+ * did not run for the set. */
+size_t GhostmSessionQueryAdapters(void *session, GhostmAdapterOut *out, size_t cap);
+
+/* The adapter counters of the session's current query set (all 0 when the
+ * stage did not run); the size convention of GhostmSessionDbStats. */
+size_t GhostmSessionAdapterStats(void *session, GhostmAdapterStats *stats, size_t size);
 
 /* The frameshift-aware read-level path of every hit of the last run (record i
  * belongs to hit i) and the run-length words they index, in hit order (the
